@@ -8,15 +8,19 @@ synthetic images per GPU.  Work per GPU is fixed as N grows ("weak" scaling);
 images are independent, so ranks exchange nothing on the data path: the only
 collective is the one-time RCCL broadcast of the packed parameter blob.
 
-    python bench.py                          # 1 GPU, defaults finish in ~1-2 min
+    python bench.py                          # 1 GPU: set up, warm up, time the steps, print the line
+    python bench.py --full                   # + roofline pass, issue probe, side figures, other configs, CPU baseline (~1-2 min)
+    python bench.py --dump-outputs DIR       # + DIR/classes.npy: the classes of the last timed step (float32)
     python bench.py --gpus N --steps K --warmup W      # starts its own N ranks (one fresh process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # or under a launcher: same ranks, same line
 
 Everything the timed region runs goes through the product's C ABI
-(include/bnn_mi355x.h).  oracle/ is touched only by the cpu_baseline leg (rank
-0, N=1): the CPU restatement timed on this host's cores on a bounded sample,
-which doubles as a parity check of the GPU classes on that sample.
+(include/bnn_mi355x.h).  A plain run does only what the headline figure needs;
+everything else it measures or checks runs with --full only.  oracle/ is touched
+only by --full: the cpu_baseline leg (rank 0, N=1: the CPU restatement timed on
+this host's cores on a bounded sample, which doubles as a parity check of the GPU
+classes on that sample), the other configs' and the N-rank line's self-checks.
 """
 import argparse
 import ctypes as C
@@ -397,6 +401,19 @@ def measure_config(network, dataset, batch, dev, device_index, steps, warmup, ch
             "classes_equal_oracle": same, "checked_images": k}
 
 
+DUMP_MAX_VALUES = 15_000_000   # float32: 60 MB, under the 64 MB that --dump-outputs may write
+
+
+def dump_outputs(out_dir, classes):
+    """DIR/classes.npy: what a caller of the timed path receives (one int32 class per image), as float32 (exact for class
+    indices).  Above DUMP_MAX_VALUES images: a fixed, seeded sample of them, in image order."""
+    os.makedirs(out_dir, exist_ok=True)
+    c = classes.astype(np.float32)
+    if c.size > DUMP_MAX_VALUES:
+        c = c[np.sort(np.random.default_rng(0).choice(c.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(out_dir, "classes.npy"), c)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -405,9 +422,14 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=131072, help="images per GPU per step")
     ap.add_argument("--network", default="cnvW1A1")
     ap.add_argument("--dataset", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: the per-stage roofline pass, the issue probe, the side figures, "
+                         "the other configs, the CPU baseline and the N-rank self-check (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the classes the last timed step computed (all ranks, in rank order) to DIR/classes.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target length of the CPU baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive and integer-pipe-first-layer side measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the issue probe, the side figures and the other configs")
     ap.add_argument("--dist-world1", action="store_true",
                     help="run the multi-GPU code path (process group, broadcast, gathers, self-check) with a world of ONE rank over "
                          "the real backend: what a one-GPU box can exercise of the RCCL calls")
@@ -537,8 +559,19 @@ def main():
         step()
     barrier()
     elapsed = time.perf_counter() - t0
+    cdev = "cpu" if a.rehearse_gloo else dev
+    if a.dump_outputs:
+        # the classes of the last timed step, every rank's shard in rank order (outside the timed region)
+        last = classes
+        if use_dist:
+            mine = classes.to(cdev).contiguous()
+            parts = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine)
+            last = torch.cat(parts)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, last.cpu().numpy())
     second_pass_ms = None
-    if not events_in_region:
+    if not events_in_region and a.full:
         L.bnn_mi355x_profile(1)
         barrier()
         t1 = time.perf_counter()
@@ -548,15 +581,16 @@ def main():
         second_pass_ms = (time.perf_counter() - t1) / a.steps * 1e3
     stage_ms = (C.c_float * 16)()
     nchunks = C.c_int(0)
-    nst = L.bnn_mi355x_profile_read(stage_ms, 16, C.byref(nchunks))
+    # (a plain run without events in its timed region has no stage times: no roofline, no second pass for one)
+    nst = L.bnn_mi355x_profile_read(stage_ms, 16, C.byref(nchunks)) if events_in_region or a.full else 0
     L.bnn_mi355x_profile(0)
     multi = None
     if use_dist:
-        cdev = "cpu" if a.rehearse_gloo else dev
         own_elapsed = elapsed
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if use_dist and a.full:
         # ---- self-validation of the N-rank run (all of it outside the timed region): every rank reports its own
         # rate, how long its side of the broadcast took and the CRC-32 of the parameter bytes its GPU holds; the
         # first 2048 images and classes of every rank go to rank 0, which classifies them with the CPU
@@ -596,62 +630,64 @@ def main():
 
     total_images = a.batch * a.steps * world
     value = total_images / elapsed
-    # ---- roofline: whole fused path priced at its algorithmic bytes, over the device time of all stages
-    launches = max(nchunks.value, 1)
-    per_stage = [stage_ms[i] / a.steps for i in range(nst)]          # ms per step (all chunks of a step)
-    imgs_per_launch = a.batch * a.steps / launches
-    names = [L.bnn_mi355x_stage_name(i).decode() for i in range(nst)]
-    dom = int(np.argmax(per_stage))
-    dev_ms = sum(per_stage)
-    alg = ALG_BYTES["cnv" if is_cnv else "lfc"]
-    achieved = alg * a.batch / (dev_ms * 1e-3) / 1e9
-    traffic, traffic_source, traffic_stages = None, None, None
-    tf = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tf):
-        try:
-            t = json.load(open(tf)).get(a.network, {})
-            traffic_source = ("profiles/traffic.json: FETCH_SIZE (x2, gfx950 correction) + WRITE_SIZE per image from the builder's "
-                              "two rocprofv3 --pmc passes (%s), scaled to this launch; not re-measured in this run" % t.get("source", "profiles/"))
-            # measured HBM bytes per image (PMC passes, profiles/) x the images of one launch
-            traffic = int((t["fetch_bytes_per_image_x2"] + t["write_bytes_per_image"]) * imgs_per_launch)
-            # per stage, in launch order: where the bytes above the 3 076 algorithmic ones go (the maps between the stages,
-            # each written once and read once: no fusion)
-            traffic_stages = {names[i] if i < len(names) else st["kernel"]: {"kernel": st["kernel"], "fetch_x2": st["fetch_bytes_per_image_x2"],
-                                                                              "write": st["write_bytes_per_image"]}
-                              for i, st in enumerate(t.get("stages", []))} or None
-        except Exception:
-            traffic = None
-    # the dominant kernel on its own: bytes that one stage must move per image (input map + output map)
-    own_bytes = {"k_conv0 (L0)": 3072 + 7200, "k_quad L1+pool": 7200 + 1568, "k_quad L2": 1568 + 2304, "k_quad L3+pool": 2304 + 400,
-                 "k_vec L0": 104 + 128, "k_vec L1": 256, "k_vec L2": 256}
-    planes = 2 if a.network.endswith("A2") else 1
-    dom_alg = own_bytes.get(names[dom])
-    dominant = {"name": names[dom], "ms_per_launch": round(per_stage[dom] * a.steps / launches, 4)}
-    if dom_alg:
-        dom_alg *= planes
-        dominant.update({"algorithmic_bytes_per_image": dom_alg,
-                         "achieved": round(dom_alg * a.batch / (per_stage[dom] * 1e-3) / 1e9, 2), "unit": "GB/s",
-                         "frac": round(dom_alg * a.batch / (per_stage[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)})
-    # what HBM really moved (the PMC passes' bytes per image x this launch) over the time of a step: "rocprof HBM GB/s against the
-    # chip's peak" in the north-star's words; `achieved` prices the path at its ALGORITHMIC bytes
-    hbm_measured = None
-    if traffic:
-        gbs = traffic / (elapsed / a.steps) / 1e9 * (a.batch / imgs_per_launch)
-        hbm_measured = {"gbs": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 5), "unit": "GB/s",
-                        "note": "roofline.traffic (stored PMC passes, scaled to the images of a step) / ms_per_step"}
-    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_source, "hbm_measured": hbm_measured,
-                "traffic_bytes_per_image_by_stage": traffic_stages,
-                "kernel": "all %d stages of one batch (dominant: %s, %.1f%% of device time)" % (
-                    nst, names[dom], 100.0 * per_stage[dom] / dev_ms),
-                "algorithmic_bytes_per_image": alg, "images_per_launch": int(imgs_per_launch),
-                "device_ms_per_step": round(dev_ms, 4), "dominant_kernel": dominant,
-                "stage_times_source": "HIP events around every stage inside the timed region" if events_in_region else
-                "second pass of the same steps with HIP events (staged form, one compute lane); `value` is timed without them on the shipped "
-                "dispatch policy, which at this size " + ("forks the pass over two compute lanes (the halves' kernels overlap: ms_per_step is "
-                "below the sum of the stages)" if forks else "may be a single launch"),
-                "second_pass_ms_per_step": None if second_pass_ms is None else round(second_pass_ms, 4),
-                "stages_ms": {names[i]: round(per_stage[i], 4) for i in range(nst)}}
+    roofline = None
+    if nst:
+        # ---- roofline: whole fused path priced at its algorithmic bytes, over the device time of all stages
+        launches = max(nchunks.value, 1)
+        per_stage = [stage_ms[i] / a.steps for i in range(nst)]          # ms per step (all chunks of a step)
+        imgs_per_launch = a.batch * a.steps / launches
+        names = [L.bnn_mi355x_stage_name(i).decode() for i in range(nst)]
+        dom = int(np.argmax(per_stage))
+        dev_ms = sum(per_stage)
+        alg = ALG_BYTES["cnv" if is_cnv else "lfc"]
+        achieved = alg * a.batch / (dev_ms * 1e-3) / 1e9
+        traffic, traffic_source, traffic_stages = None, None, None
+        tf = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tf):
+            try:
+                t = json.load(open(tf)).get(a.network, {})
+                traffic_source = ("profiles/traffic.json: FETCH_SIZE (x2, gfx950 correction) + WRITE_SIZE per image from the builder's "
+                                  "two rocprofv3 --pmc passes (%s), scaled to this launch; not re-measured in this run" % t.get("source", "profiles/"))
+                # measured HBM bytes per image (PMC passes, profiles/) x the images of one launch
+                traffic = int((t["fetch_bytes_per_image_x2"] + t["write_bytes_per_image"]) * imgs_per_launch)
+                # per stage, in launch order: where the bytes above the 3 076 algorithmic ones go (the maps between the stages,
+                # each written once and read once: no fusion)
+                traffic_stages = {names[i] if i < len(names) else st["kernel"]: {"kernel": st["kernel"], "fetch_x2": st["fetch_bytes_per_image_x2"],
+                                                                                  "write": st["write_bytes_per_image"]}
+                                  for i, st in enumerate(t.get("stages", []))} or None
+            except Exception:
+                traffic = None
+        # the dominant kernel on its own: bytes that one stage must move per image (input map + output map)
+        own_bytes = {"k_conv0 (L0)": 3072 + 7200, "k_quad L1+pool": 7200 + 1568, "k_quad L2": 1568 + 2304, "k_quad L3+pool": 2304 + 400,
+                     "k_vec L0": 104 + 128, "k_vec L1": 256, "k_vec L2": 256}
+        planes = 2 if a.network.endswith("A2") else 1
+        dom_alg = own_bytes.get(names[dom])
+        dominant = {"name": names[dom], "ms_per_launch": round(per_stage[dom] * a.steps / launches, 4)}
+        if dom_alg:
+            dom_alg *= planes
+            dominant.update({"algorithmic_bytes_per_image": dom_alg,
+                             "achieved": round(dom_alg * a.batch / (per_stage[dom] * 1e-3) / 1e9, 2), "unit": "GB/s",
+                             "frac": round(dom_alg * a.batch / (per_stage[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)})
+        # what HBM really moved (the PMC passes' bytes per image x this launch) over the time of a step: "rocprof HBM GB/s against the
+        # chip's peak" in the north-star's words; `achieved` prices the path at its ALGORITHMIC bytes
+        hbm_measured = None
+        if traffic:
+            gbs = traffic / (elapsed / a.steps) / 1e9 * (a.batch / imgs_per_launch)
+            hbm_measured = {"gbs": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 5), "unit": "GB/s",
+                            "note": "roofline.traffic (stored PMC passes, scaled to the images of a step) / ms_per_step"}
+        roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_source, "hbm_measured": hbm_measured,
+                    "traffic_bytes_per_image_by_stage": traffic_stages,
+                    "kernel": "all %d stages of one batch (dominant: %s, %.1f%% of device time)" % (
+                        nst, names[dom], 100.0 * per_stage[dom] / dev_ms),
+                    "algorithmic_bytes_per_image": alg, "images_per_launch": int(imgs_per_launch),
+                    "device_ms_per_step": round(dev_ms, 4), "dominant_kernel": dominant,
+                    "stage_times_source": "HIP events around every stage inside the timed region" if events_in_region else
+                    "second pass of the same steps with HIP events (staged form, one compute lane); `value` is timed without them on the shipped "
+                    "dispatch policy, which at this size " + ("forks the pass over two compute lanes (the halves' kernels overlap: ms_per_step is "
+                    "below the sum of the stages)" if forks else "may be a single launch"),
+                    "second_pass_ms_per_step": None if second_pass_ms is None else round(second_pass_ms, 4),
+                    "stages_ms": {names[i]: round(per_stage[i], 4) for i in range(nst)}}
     out = {"metric": METRIC if a.network == "cnvW1A1"
            else "images/sec (whole node) %s batch" % a.network,
            "value": round(value, 1), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -660,7 +696,9 @@ def main():
            "config": {"workload": "%s, %d synthetic %s images per GPU per step, inputs resident in HBM, params %s/%s"
                       % (a.network, a.batch, "32x32x3 uint8" if is_cnv else "28x28 uint8", dataset, a.network),
                       "images_per_gpu_per_step": a.batch, "parallelism": "dp%d (batch shards, no data-path collective)" % world},
-           "roofline": roofline}
+           "full": a.full}
+    if roofline:
+        out["roofline"] = roofline
     if multi:
         out["multi_gpu"] = multi
     floor_cyc = issue_floor_cycles(a.network)
@@ -675,13 +713,13 @@ def main():
                            "pair rate and clock tools/issue_probe.hip measured on this device in this run (valu.calibration)"}
     # ---- the issue ceiling measured on this device, in this run, outside the timed region
     cal = None
-    if world == 1 and not a.no_extras:
+    if a.full and world == 1 and not a.no_extras:
         cal = calibrate_issue()
         out["valu"]["calibration"] = cal
         out["valu"].update(valu_measured(a.network, per_gpu, cal))
 
     # ---- secondary figures (single GPU only, outside the timed region of `value`)
-    if world == 1 and not a.no_extras:
+    if a.full and world == 1 and not a.no_extras:
         # (a) PCIe-inclusive: the same batch from pageable HOST memory to int32 classes in host memory
         host_imgs = imgs.cpu().numpy()
         usec = C.c_float(0)
@@ -775,7 +813,7 @@ def main():
 
     # ---- the other single-GPU BASELINE configs (2: LFC-W1A1 at its quoted 10 000-image batch; 4: CNV-W2A2), outside
     # the timed region of `value`: a few ms of GPU time each, classes of a sample checked against the oracle
-    if world == 1 and not a.no_extras and a.network == "cnvW1A1":
+    if a.full and world == 1 and not a.no_extras and a.network == "cnvW1A1":
         out["other_configs"] = {
             "lfcW1A1_10000": measure_config("lfcW1A1", "mnist", 10000, dev, local_rank, 300, 20, cal=cal),
             "lfcW1A1_131072": measure_config("lfcW1A1", "mnist", 131072, dev, local_rank, 40, 5, cal=cal),
@@ -820,7 +858,7 @@ def main():
             sys.exit("PARITY FAILURE in other_configs")
 
     # ---- CPU baseline: the CPU restatement on this host's cores, bounded sample, same images
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         import oracle_lib as ol
         o = ol.Oracle(a.network, ol.param_dir(dataset, a.network))
         host = imgs[: min(a.batch, 262144)].cpu().numpy()

@@ -68,9 +68,9 @@ def test_a_rank_that_dies_is_reported_as_json(monkeypatch, capsys):
 def test_plain_start_of_a_two_rank_rehearsal_runs_end_to_end():
     """`python3 bench.py --gpus 2 --rehearse-gloo` from the plain command on the one-GPU box: two fresh rank
     processes (gloo, both on cuda:0), one broadcast, shards, the line's self-check (CRC of the parameters on every
-    rank, first 2048 classes of every rank against the CPU restatement)"""
+    rank, first 2048 classes of every rank against the CPU restatement: with --full)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--rehearse-gloo", "--steps", "3", "--warmup", "1", "--batch", "16384"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--rehearse-gloo", "--full", "--steps", "3", "--warmup", "1", "--batch", "16384"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -7,14 +7,14 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/final2
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+python3 $R/bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json
 echo "bench default done"; tail -c 600 $O/bench_default.json; echo
-for n in cnvW1A2 cnvW2A2 lfcW1A1 lfcW1A2; do python3 $R/bench.py --network $n --no-extras 2>/dev/null | tail -1 > $O/bench_$n.json; done
+for n in cnvW1A2 cnvW2A2 lfcW1A1 lfcW1A2; do python3 $R/bench.py --full --network $n --no-extras 2>/dev/null | tail -1 > $O/bench_$n.json; done
 echo "bench lines done"
-B="python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 BNN_MI355X_NO_WARMUP=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- $B > $O/prof_bench.json 2>$O/prof.err  # (without the load-time warm-up, whose small launches of the same kernels would be averaged in)
 echo "kernel trace done"
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- $B > $O/pmc_fetch.json 2>$O/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- $B > $O/pmc_write.json 2>$O/pmc_write.err
 echo "pmc traffic done"

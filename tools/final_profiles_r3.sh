@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 #  durations are those of the bench line's stage table; `value` itself is timed on the shipped policy, which forks)
 # 1. HBM traffic of the final kernels (two PMC passes, no load-time warm-up: its small launches of the same kernels would
 #    be averaged in), then traffic.json, which the bench line quotes per stage
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
 BNN_MI355X_LANES=1 BNN_MI355X_NO_WARMUP=1 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- $B > $O/pmc_fetch.json 2>$O/pmc_fetch.err
 BNN_MI355X_LANES=1 BNN_MI355X_NO_WARMUP=1 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- $B > $O/pmc_write.json 2>$O/pmc_write.err
 python3 $R/tools/pmc_summary.py $O/pmc_fetch $O/pmc_write 131072 > $O/pmc_traffic_cnvW1A1.txt
@@ -25,17 +25,17 @@ cp $(ls $O/pmc_write/*/*counter_collection.csv | head -1) $O/pmc_write_counter_c
 rm -rf $O/pmc_fetch $O/pmc_write
 echo "pmc traffic done"
 # 2. bench lines
-python3 $R/bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+python3 $R/bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json
 echo "bench default done"; tail -c 400 $O/bench_default.json; echo
-for n in cnvW1A2 cnvW2A2 lfcW1A1 lfcW1A2; do python3 $R/bench.py --network $n --no-extras 2>/dev/null | tail -1 > $O/bench_$n.json; done
+for n in cnvW1A2 cnvW2A2 lfcW1A1 lfcW1A2; do python3 $R/bench.py --full --network $n --no-extras 2>/dev/null | tail -1 > $O/bench_$n.json; done
 echo "bench lines done"
 # 3. kernel trace of the bench command
-B="python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 BNN_MI355X_LANES=1 BNN_MI355X_NO_WARMUP=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- $B > $O/prof_bench.json 2>$O/prof.err
 cp $(ls $O/prof/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv; rm -rf $O/prof
 echo "kernel trace done"
 # 4. SQ passes: the bench (all nine CNV stages incl. k_conv0_tile), k_lfc_block_s at 10 000 images
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
 export BNN_MI355X_NO_WARMUP=1 BNN_MI355X_LANES=1
 bash $R/tools/sq_passes.sh final3/sq_bench -- $B
 BATCHES=10000 bash $R/tools/sq_passes.sh final3/sq_lfc10k -- python3 $R/tools/batch_sweep.py lfcW1A1
@@ -51,12 +51,12 @@ cd $R
 python3 tools/latency.py 2>&1 | grep -v "^Setting\|amdgpu.ids" > $O/latency.txt; cat $O/latency.txt
 # 6. the plain multi-rank start on this one-GPU box: the JSON error, and the 4-rank gloo rehearsal
 set +e
-python3 bench.py --gpus 2 --steps 2 --warmup 1 > $O/bench_gpus2_on_one_gpu.json 2>/dev/null; echo "rc=$?" >> $O/bench_gpus2_on_one_gpu.json
+python3 bench.py --full --gpus 2 --steps 2 --warmup 1 > $O/bench_gpus2_on_one_gpu.json 2>/dev/null; echo "rc=$?" >> $O/bench_gpus2_on_one_gpu.json
 set -e
-python3 bench.py --gpus 4 --rehearse-gloo --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/rehearse_gloo_4_plain_start.json
-python3 bench.py --dist-world1 --steps 5 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/rccl_world1.json
+python3 bench.py --full --gpus 4 --rehearse-gloo --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/rehearse_gloo_4_plain_start.json
+python3 bench.py --full --dist-world1 --steps 5 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/rccl_world1.json
 # (the same two-rank rehearsal under a launcher, as the bench contract words it)
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --rehearse-gloo --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/rehearse_gloo_2_torchrun.json
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --rehearse-gloo --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/rehearse_gloo_2_torchrun.json
 tail -c 300 $O/rehearse_gloo_2_torchrun.json; echo
 # 7. host paths and sweeps on the final build
 python3 tools/path_rates.py cnvW1A1 131072 7 2>/dev/null | grep -v Setting > $O/path_rates.txt

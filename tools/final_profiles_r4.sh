@@ -15,11 +15,11 @@ if [ $PART = A ]; then
   timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
   tail -2 $O/tests.log
   python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v "^Setting" | tail -3
-  python3 $R/bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+  python3 $R/bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json
   echo "bench default done"; tail -c 300 $O/bench_default.json; echo
-  for n in cnvW1A2 cnvW2A2 lfcW1A1 lfcW1A2; do python3 $R/bench.py --network $n --no-extras 2>/dev/null | tail -1 > $O/bench_$n.json; done
+  for n in cnvW1A2 cnvW2A2 lfcW1A1 lfcW1A2; do python3 $R/bench.py --full --network $n --no-extras 2>/dev/null | tail -1 > $O/bench_$n.json; done
   cd /tmp && export TMPDIR=/tmp
-  B="python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+  B="python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
   BNN_MI355X_LANES=1 BNN_MI355X_NO_WARMUP=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- $B > $O/prof_bench.json 2>$O/prof.err
   cp $(ls $O/prof/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv; rm -rf $O/prof
   echo "part A done"
@@ -28,7 +28,7 @@ if [ $PART = B ]; then
   cd /tmp && export TMPDIR=/tmp
   export BNN_MI355X_LANES=1 BNN_MI355X_NO_WARMUP=1
   for NET in cnvW2A2 cnvW1A2; do
-    B="python3 $R/bench.py --network $NET --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+    B="python3 $R/bench.py --full --network $NET --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch_$NET -- $B > $O/pmc_fetch_$NET.json 2>$O/pmc_fetch_$NET.err
     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write_$NET -- $B > $O/pmc_write_$NET.json 2>$O/pmc_write_$NET.err
     python3 $R/tools/pmc_summary.py $O/pmc_fetch_$NET $O/pmc_write_$NET 131072 > $O/pmc_traffic_$NET.txt
@@ -37,12 +37,12 @@ if [ $PART = B ]; then
     cp $(ls $O/pmc_fetch_$NET/*/*counter_collection.csv | head -1) $O/pmc_fetch_counter_collection_$NET.csv
     cp $(ls $O/pmc_write_$NET/*/*counter_collection.csv | head -1) $O/pmc_write_counter_collection_$NET.csv
     rm -rf $O/pmc_fetch_$NET $O/pmc_write_$NET
-    B="python3 $R/bench.py --network $NET --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+    B="python3 $R/bench.py --full --network $NET --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
     rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$NET -- $B > $O/prof_bench_$NET.json 2>$O/prof_$NET.err
     cp $(ls $O/prof_$NET/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats_$NET.csv; rm -rf $O/prof_$NET
     echo "$NET traffic + trace done"
   done
-  B="python3 $R/bench.py --network cnvW2A2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+  B="python3 $R/bench.py --full --network cnvW2A2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
   bash $R/tools/sq_passes.sh final4/sq_cnvW2A2 -- $B
   echo "part B done"
 fi

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final4; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export BNN_MI355X_LANES=1 BNN_MI355X_NO_WARMUP=1
 for NET in lfcW1A1 lfcW1A2; do
-  B="python3 $R/bench.py --network $NET --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+  B="python3 $R/bench.py --full --network $NET --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch_$NET -- $B > $O/pmc_fetch_$NET.json 2>$O/pmc_fetch_$NET.err
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write_$NET -- $B > $O/pmc_write_$NET.json 2>$O/pmc_write_$NET.err
   python3 $R/tools/pmc_summary.py $O/pmc_fetch_$NET $O/pmc_write_$NET 131072 > $O/pmc_traffic_$NET.txt

@@ -194,6 +194,25 @@ class PynqBNN:
         self._report_multi(usec.value, size.value)
         return result
 
+    # extension: num_runs independent campaigns in one call, side by side on the GPU
+    def inference_multiple_with_faults_runs(self, path, num_runs, num_faults, word_size, target_type, target_layers=[],
+                                            seed=0):
+        """-> int32 array (num_runs, n): row r is what load_parameters + set_fault_seed(seed + r) +
+        inference_multiple_with_faults returns (seed 0: every run seeds from std::random_device).  The loaded
+        parameters are not changed.  usecPerImage: device time of the call / (num_runs * n)."""
+        tl = np.array(list(target_layers), dtype=np.int32)
+        targets = tl.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if len(tl) else None
+        size = ctypes.c_int(0)
+        usec = ctypes.c_float(0)
+        ptr = self.interface.bnn_mi355x_fault_campaigns(
+            path.encode(), len(self.classes), num_runs, seed, num_faults, word_size, target_type, targets, len(tl),
+            ctypes.byref(size), ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("fault campaigns failed: " + self.interface.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        self.usecPerImage = usec.value
+        return result
+
     def inference_multiple_detail(self, path):
         size = ctypes.c_int(0)
         usec = ctypes.c_float(0)
@@ -336,6 +355,10 @@ class CnvClassifier:
         return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_with_faults(
             p, num_faults, word_size, target_type, target_layers))
 
+    def classify_images_with_faults_runs(self, imgs, num_runs, num_faults, word_size, target_type, target_layers=[], seed=0):
+        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_with_faults_runs(
+            p, num_runs, num_faults, word_size, target_type, target_layers, seed))
+
     def classify_cifars(self, path):
         result = self.bnn.inference_multiple(path)
         self.usecPerImage = self.bnn.usecPerImage
@@ -343,6 +366,12 @@ class CnvClassifier:
 
     def classify_cifars_with_faults(self, path, num_faults, word_size, target_type, target_layers=[]):
         result = self.bnn.inference_multiple_with_faults(path, num_faults, word_size, target_type, target_layers)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_cifars_with_faults_runs(self, path, num_runs, num_faults, word_size, target_type, target_layers=[], seed=0):
+        result = self.bnn.inference_multiple_with_faults_runs(path, num_runs, num_faults, word_size, target_type,
+                                                              target_layers, seed)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
@@ -399,6 +428,13 @@ class LfcClassifier:
         return result
 
     # extension
+    def classify_mnists_with_faults_runs(self, mnist_format_file, num_runs, num_faults, flip_word, target_type,
+                                         target_layers=[], seed=0):
+        result = self.bnn.inference_multiple_with_faults_runs(mnist_format_file, num_runs, num_faults, flip_word,
+                                                              target_type, target_layers, seed)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
     def classify_array(self, images):
         result = self.bnn.inference_array(images)
         self.usecPerImage = self.bnn.usecPerImage

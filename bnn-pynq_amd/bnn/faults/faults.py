@@ -8,7 +8,9 @@ fault counts x {any, weight, threshold} x {bit, word}, writes the raw accuracies
 (min / max / average, "effective" runs = runs whose accuracy differs from the control) as JSON.
 
 On the MI355X runtime a run of 10 000 CIFAR-10 images with 100 upsets takes about 5 ms plus the
-3 ms parameter reload (tools/fault_campaign_rate.py).
+3 ms parameter reload (tools/fault_campaign_rate.py).  ``batched=True`` runs all of a test's runs in ONE
+call instead (``classify_*_with_faults_runs``: the runs side by side on the GPU, tools/fault_campaigns_rate.py);
+with the same ``seed`` (run i seeded with seed + i) both paths return identical results.
 """
 from .. import bnn as _bnn
 from .. import util
@@ -36,17 +38,27 @@ class FaultTest:
         self.labels = labels
         self.runtime = runtime
 
-    def run_test(self, num_runs, num_flips, word_size=1, target_type=-1, target_layers=()):
-        """-> (results per run, usec per image per run, accuracy per run)"""
+    def _describe(self, i, num_runs, num_flips, word_size, target_type, target_layers):
+        return "{}-{} run {} of {} (flipping {}{} {}(s) in {})".format(
+            self.network, self.dataset, i + 1, num_runs, num_flips,
+            " weight" if target_type == 0 else " threshold" if target_type == 1 else "",
+            "word" if word_size > 1 else "bit",
+            "any layer" if not target_layers else "layer(s) {}".format(target_layers))
+
+    def run_test(self, num_runs, num_flips, word_size=1, target_type=-1, target_layers=(), batched=False, seed=0):
+        """-> (results per run, usec per image per run, accuracy per run).
+        batched: all runs in one call, side by side on the GPU (the usec figure is then the call's, per image of
+        every run).  seed != 0: run i seeds the fault planner with seed + i (0: std::random_device), so that
+        both forms give the same results."""
         target_layers = list(target_layers)
+        if batched:
+            return self._run_test_batched(num_runs, num_flips, word_size, target_type, target_layers, seed)
         results, times, accuracies = [], [], []
         for i in range(num_runs):
             classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
-            print("{}-{} run {} of {} (flipping {}{} {}(s) in {})".format(
-                self.network, self.dataset, i + 1, num_runs, num_flips,
-                " weight" if target_type == 0 else " threshold" if target_type == 1 else "",
-                "word" if word_size > 1 else "bit",
-                "any layer" if not target_layers else "layer(s) {}".format(target_layers)))
+            if seed:
+                classifier.bnn.interface.bnn_mi355x_set_fault_seed(seed + i)
+            print(self._describe(i, num_runs, num_flips, word_size, target_type, target_layers))
             if self.dataset == "cifar10":
                 got = classifier.classify_cifars_with_faults(self.input_file, num_flips, word_size, target_type, target_layers)
             elif self.dataset == "mnist":
@@ -58,6 +70,28 @@ class FaultTest:
             accuracies.append(util.calculate_accuracy(results[-1], self.labels))
             print("Accuracy:", accuracies[-1])
             print()
+        if seed and num_runs:
+            classifier.bnn.interface.bnn_mi355x_set_fault_seed(0)  # (the library outlives the classifier: back to the default)
+        return (results, times, accuracies)
+
+    def _run_test_batched(self, num_runs, num_flips, word_size, target_type, target_layers, seed):
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        print(self._describe(0, num_runs, num_flips, word_size, target_type, target_layers).replace(
+            "run 1 of {}".format(num_runs), "{} run(s) in one call".format(num_runs)))
+        if self.dataset == "cifar10":
+            got = classifier.classify_cifars_with_faults_runs(self.input_file, num_runs, num_flips, word_size, target_type,
+                                                              target_layers, seed)
+        elif self.dataset == "mnist":
+            got = classifier.classify_mnists_with_faults_runs(self.input_file, num_runs, num_flips, word_size, target_type,
+                                                              target_layers, seed)
+        else:
+            got = classifier.classify_images_with_faults_runs(self.input_file, num_runs, num_flips, word_size, target_type,
+                                                              target_layers, seed)
+        results = [row.tolist() for row in got]
+        times = [classifier.usecPerImage] * num_runs
+        accuracies = [util.calculate_accuracy(r, self.labels) for r in results]
+        print("Accuracies:", accuracies)
+        print()
         return (results, times, accuracies)
 
 
@@ -123,9 +157,9 @@ class NetworkTest:
         self.fault_test = fault_test
         self.control = None
 
-    def _run_control(self):
+    def _run_control(self, batched=False):
         print("Running", self.fault_test.network + "-" + self.fault_test.dataset, "control test")
-        _, _, accuracy = self.fault_test.run_test(num_runs=1, num_flips=0)
+        _, _, accuracy = self.fault_test.run_test(num_runs=1, num_flips=0, batched=batched)
         self.control = accuracy[0]
 
     def _raw(self, name, num_runs, num_flips, layers, accuracies):
@@ -149,22 +183,24 @@ class NetworkTest:
             out["results"][name] = entry
         return out
 
-    def _run_tests(self, folder, num_runs, num_flips, test_types, target_layers):
+    def _run_tests(self, folder, num_runs, num_flips, test_types, target_layers, batched=False, seed=0):
         raw = []
         for test in test_types:
-            _, _, accuracies = self.fault_test.run_test(num_runs, num_flips, test.word_size, test.target_type, target_layers)
+            _, _, accuracies = self.fault_test.run_test(num_runs, num_flips, test.word_size, test.target_type, target_layers,
+                                                        batched, seed)
             raw.append(self._raw(test.name, num_runs, num_flips, target_layers, accuracies))
             util.write_dict_to_file("{}/temp/{}_results_{}.json".format(folder, self.fault_test.network, test.name.replace(" ", "-")), raw[-1])
         return self._stats(util.dict_of_dicts_merge(*raw))
 
-    def test_network(self, output_folder, num_runs, flip_counts, test_types, target_layers=()):
-        """one statistics file per fault count under output_folder/<network>/<dataset>/<n>flips/"""
+    def test_network(self, output_folder, num_runs, flip_counts, test_types, target_layers=(), batched=False, seed=0):
+        """one statistics file per fault count under output_folder/<network>/<dataset>/<n>flips/.
+        batched / seed: see FaultTest.run_test (each test's runs in one call; run i seeded with seed + i)."""
         output_folder = "{}/{}/{}/".format(output_folder, self.fault_test.network, self.fault_test.dataset)
         if self.control is None:
-            self._run_control()
+            self._run_control(batched)
         for num_flips in flip_counts:
             folder = "{}/{}flips/".format(output_folder, num_flips)
-            stats = self._run_tests(folder, num_runs, num_flips, test_types, target_layers)
+            stats = self._run_tests(folder, num_runs, num_flips, test_types, target_layers, batched, seed)
             name = "{}/{}_{}".format(folder, self.fault_test.network, self.fault_test.dataset)
             name += "_stats_layer{}.json".format(list(target_layers)) if len(target_layers) > 0 else "_stats.json"
             util.write_dict_to_file(name, stats)

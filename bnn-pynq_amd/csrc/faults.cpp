@@ -106,4 +106,15 @@ int apply_fault(const NetSpec &net, RawParams &raw, const Fault &f) {
   return f.ind * L.fold.pe + f.mem;
 }
 
+uint64_t *fault_word(const NetSpec &net, RawParams &raw, const Fault &f) {
+  if (f.layer < 0 || f.layer >= net.nlayers || f.word_size < 1 || f.word_size > 64) return nullptr;
+  const LayerSpec &L = net.L[f.layer];
+  if (f.target == 0) {
+    if (f.mem >= L.fold.pe || f.ind >= L.fold.wmem) return nullptr;
+    return &raw.w[f.layer][f.mem][f.ind];
+  }
+  if (L.nthr == 0 || f.mem >= L.fold.pe || f.ind >= L.fold.tmem || f.thresh >= L.nthr) return nullptr;
+  return &raw.t[f.layer][f.mem][(size_t)f.ind * L.nthr + f.thresh];
+}
+
 }  // namespace bnn

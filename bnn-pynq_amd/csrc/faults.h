@@ -32,4 +32,8 @@ std::string plan_faults(const NetSpec &net, uint64_t seed, int num_images, unsig
 // inject_fault_impl on the raw memories; returns the matrix row whose packed form changed, or -1
 int apply_fault(const NetSpec &net, RawParams &raw, const Fault &f);
 
+// the raw word apply_fault(net, raw, f) modifies, or null where it would return -1.  apply_fault is not an involution
+// (a layer-0 threshold is read back as its integer part): undoing a fault means restoring this word.
+uint64_t *fault_word(const NetSpec &net, RawParams &raw, const Fault &f);
+
 }  // namespace bnn

@@ -78,4 +78,32 @@ void l1_mfma_table(const uint32_t *rows, uint8_t *dst);
 hipError_t run_cnv(NetId net, const CnvLaunch &a);
 hipError_t run_lfc(NetId net, const LfcLaunch &a);
 
+// Many fault campaigns side by side (bnn_mi355x_fault_campaigns).  Run r has its own copy of the blob in HBM,
+// `stride` bytes behind run r-1's.  One multi-run launch classifies a SEGMENT of images per record: `len`
+// resident images from `image` on, with run `run`'s parameters, their activations at slots slot..slot+len-1 of
+// the activation buffers; results land at run * n + image.  The stage kernels' MULTI instantiations take the
+// record from blockIdx.y.
+struct MultiSeg { int run, image, slot, len; };
+struct MultiLaunch {
+  const uint8_t *images;      // device, the call's resident images (every run classifies the same ones)
+  const MultiSeg *segs;       // device, this launch's records (at most 65 535)
+  int nsegs, max_len, total;  // records; the longest segment; images over all of them (<= the workspace's capacity)
+  int n;                      // images per run
+  void *buf0, *buf1;          // activation buffers (cnv/lfc_workspace_bytes per image, `total` images)
+  const uint32_t *rows[9];    // run 0's copy: per-layer packed rows
+  const uint8_t *l0_mfma;     // run 0's copy: layer-0 MFMA table (CNV); null: integer-pipe k_conv0
+  size_t stride;              // bytes between two runs' copies (a multiple of 256)
+  bool has_two;               // cnvW2A2: some run's copy holds a weight of -2 (the -2-aware instantiations)
+  int32_t *classes;           // CNV: device, class per image of every run (run-major)
+  uint64_t *words;            // LFC: device, raw output word per image of every run (run-major)
+  int number_class;
+  hipStream_t stream;
+};
+hipError_t run_cnv_multi(NetId net, const MultiLaunch &a);
+hipError_t run_lfc_multi(NetId net, const MultiLaunch &a);
+
+// copy `bytes` from staging + src to copies + dst for each span (one block per span); offsets and sizes are multiples of 4
+struct PatchSpan { uint64_t dst; uint32_t src, bytes; };
+hipError_t scatter_patches(const uint8_t *staging, const PatchSpan *spans, int nspans, uint8_t *copies, hipStream_t s);
+
 }  // namespace bnn

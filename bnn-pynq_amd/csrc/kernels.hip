@@ -73,6 +73,31 @@ __device__ __forceinline__ BlockMap map_block(int groups, int n_items) {
   return m;
 }
 
+// Multi-run launches (the MULTI instantiations, bnn_mi355x_fault_campaigns): blockIdx.y picks a segment record
+// (kernels.h, MultiSeg) and the stage runs on it as on a batch of its own -- rows from that run's blob copy,
+// n_items = len * ipi, work items offset by the segment's slot.  A block never straddles two runs: the rows stay
+// block-uniform (scalar loads).  Defaulted on every other launch, where it is not read.
+struct MultiArgs {
+  const MultiSeg *segs;  // the launch's records
+  unsigned stride_dw;    // dwords between two runs' blob copies
+  int ipi;               // work items per image of this stage
+  int res_images;        // > 0 (last stages): results go to image run * res_images + image, not to the slot
+};
+__device__ __forceinline__ MultiSeg multi_seg(const MultiArgs &ma) {
+  kptr32 p = (kptr32)(uintptr_t)(ma.segs + blockIdx.y);
+  return MultiSeg{(int)p[0], (int)p[1], (int)p[2], (int)p[3]};
+}
+// the common prologue: offsets `rows` to the run's copy, sets n_items, returns the first work item of the slot.
+// Results of a last stage (one item per image, `out_per_item` words of T each) are redirected to their run-major place.
+template <typename T>
+__device__ __forceinline__ int multi_prologue(const MultiArgs &ma, const uint32_t *__restrict__ &rows, T *__restrict__ &out, int &n_items, int out_per_item) {
+  const MultiSeg sg = multi_seg(ma);
+  rows += (size_t)sg.run * ma.stride_dw;
+  n_items = sg.len * ma.ipi;
+  if (ma.res_images > 0) out += ((size_t)sg.run * ma.res_images + sg.image - sg.slot) * out_per_item;  // (>= 0: a run's slot lies below run * n)
+  return sg.slot * ma.ipi;
+}
+
 __device__ __forceinline__ int pc64(uint64_t x) { return __builtin_popcountll(x); }
 
 // A single-image call may ask for a completion mark in pinned host memory (runtime.hip, infer_direct): the wave that
@@ -224,9 +249,16 @@ __device__ __forceinline__ void gather_taps(const uint8_t *__restrict__ imgs, in
   for (int j = 0; j < 7; j++) a[j] = quantise4(a[j]);
 }
 
-template <bool OUT2>
+template <bool OUT2, bool MULTI = false>
 __global__ __launch_bounds__(kBlock) void k_conv0(const uint8_t *__restrict__ imgs, uint32_t *__restrict__ out,
-                                                   const uint32_t *__restrict__ rows, int n_items, int groups, int gpb) {
+                                                   const uint32_t *__restrict__ rows, int n_items, int groups, int gpb, MultiArgs ma = {}) {
+  if constexpr (MULTI) {  // (item counts pixels of the segment's images; the outputs start at its slot)
+    const MultiSeg sg = multi_seg(ma);
+    rows += (size_t)sg.run * ma.stride_dw;
+    n_items = sg.len * 900;
+    imgs += (size_t)sg.image * 3072;
+    out += (size_t)sg.slot * 900 * (OUT2 ? 4 : 2);
+  }
   const BlockMap bm = map_block(groups / gpb, n_items);
   if (!bm.valid) return;
   const int item = bm.item;
@@ -406,13 +438,21 @@ __device__ __forceinline__ uint32_t lds_run(const uint32_t *aligned, uint32_t sh
   return __builtin_amdgcn_alignbyte(aligned[OFF / 4 + 1], aligned[OFF / 4], shift);
 }
 
-template <bool OUT2>
+template <bool OUT2, bool MULTI = false>
 __global__ __launch_bounds__(kBlock, 2) void k_conv0_tile(const uint8_t *__restrict__ imgs, uint32_t *__restrict__ out,
-                                                        const uint8_t *__restrict__ l0tab, int n_images) {
+                                                        const uint8_t *__restrict__ l0tab, int n_images, MultiArgs ma = {}) {
   __shared__ uint4 q4[kL0Imgs * kL0Image / 16];  // quantised images, planar CHW int8
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int img0 = blockIdx.x * kL0Imgs;
+  if constexpr (MULTI) {  // (the whole block returns, before any barrier, when the segment is shorter)
+    const MultiSeg sg = multi_seg(ma);
+    if (img0 >= sg.len) return;
+    l0tab += (size_t)sg.run * ma.stride_dw * 4;
+    n_images = sg.len;
+    imgs += (size_t)sg.image * 3072;
+    out += (size_t)sg.slot * 900 * (OUT2 ? 4 : 2);
+  }
   const int cnt = __builtin_amdgcn_readfirstlane(min(kL0Imgs, n_images - img0));  // >= 1 by the grid size
   const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(imgs + (size_t)img0 * 3072);
   for (int i = tid; i < cnt * 192; i += kBlock) {
@@ -705,13 +745,15 @@ __device__ __forceinline__ void store_group(uint32_t *__restrict__ out, size_t i
   else reinterpret_cast<uint8_t *>(out)[index] = (uint8_t)bits;
 }
 
-template <int CW, int ID, bool POOL, int NPB = 32>
+template <int CW, int ID, bool POOL, int NPB = 32, bool MULTI = false>
 __global__ __launch_bounds__(kBlock) void k_quad_x(const uint64_t *__restrict__ in, uint32_t *__restrict__ out,
-                                                    const uint32_t *__restrict__ rows, int n_items, int groups, int gpb) {
+                                                    const uint32_t *__restrict__ rows, int n_items, int groups, int gpb, MultiArgs ma = {}) {
   constexpr int OD = ID - 2, QD = OD / 2, NQ = QD * QD, KW = 9 * CW, ROW_DW = 2 + 2 * KW;
+  int item0 = 0;
+  if constexpr (MULTI) item0 = multi_prologue(ma, rows, out, n_items, 0);
   const BlockMap bm = map_block(groups / gpb, n_items);
   if (!bm.valid) return;
-  const int item = bm.item;
+  const int item = bm.item + item0;
   const int img = item / NQ, q = item - img * NQ;
   const int qy = q / QD, qx = q - qy * QD;
   const uint64_t *__restrict__ base = in + ((size_t)img * ID * ID + (size_t)(2 * qy) * ID + 2 * qx) * CW;
@@ -771,14 +813,17 @@ __global__ __launch_bounds__(kBlock) void k_quad_x(const uint64_t *__restrict__ 
 // POOL (with SINGLE): lane = one output pixel of a 2x2-pooled conv layer, the four pixels of a pooling
 // quad on four consecutive lanes (item = 4 * quad + 2 dy + dx); the pooled bits are the OR over those
 // lanes.  Small batches only: four times the lanes of k_quad_x, a quarter of the work per lane.
-template <int KW, bool SINGLE, int CW, int ID, int NPB = 32, bool POOL = false>
+template <int KW, bool SINGLE, int CW, int ID, int NPB = 32, bool POOL = false, bool MULTI = false>
 __global__ __launch_bounds__(kBlock) void k_vec_x(const uint64_t *__restrict__ in, uint32_t *__restrict__ out,
-                                                   const uint32_t *__restrict__ rows, int n_items, int groups, int gpb) {
+                                                   const uint32_t *__restrict__ rows, int n_items, int groups, int gpb, MultiArgs ma = {}) {
   constexpr int ROW_DW = 2 + 2 * KW;
   static_assert(!POOL || SINGLE, "pooling needs the window form");
+  static_assert(!MULTI || NPB == 32, "multi-run launches use the 32-neuron form");
+  int item0 = 0;
+  if constexpr (MULTI) item0 = multi_prologue(ma, rows, out, n_items, groups);
   const BlockMap bm = map_block(groups / gpb, n_items);
   if (!bm.valid) return;  // (POOL: n_items is a multiple of 4, so a quad is valid or invalid as a whole)
-  const int item = bm.item;
+  const int item = bm.item + item0;
   uint32_t al[KW], ah[KW];
   if constexpr (SINGLE) {
     constexpr int OD = ID - 2;
@@ -931,14 +976,16 @@ __device__ __forceinline__ void finish_bits(uint32_t &b0, uint32_t &b1) {
 // 3x3 valid conv, one lane = a 2x2 quad of output pixels (4x4 window in VGPRs), optional pool.
 // Replaces ConvolutionInputGenerator + Matrix_Vector_Activate_Batch + ThresholdsActivation
 // (+ StreamingMaxPool_Precision_Batch) for CNV layers 1..3 of the A2 networks.
-template <int ARITH, int CW, int ID, bool POOL, bool OUT2, int NPB = 32, bool TWO = false>
+template <int ARITH, int CW, int ID, bool POOL, bool OUT2, int NPB = 32, bool TWO = false, bool MULTI = false>
 __global__ __launch_bounds__(kBlock) void k_quad(const uint64_t *__restrict__ in, uint32_t *__restrict__ out,
-                                                  const uint32_t *__restrict__ rows, int n_items, int groups, int gpb) {
+                                                  const uint32_t *__restrict__ rows, int n_items, int groups, int gpb, MultiArgs ma = {}) {
   constexpr int OD = ID - 2, QD = OD / 2, NQ = QD * QD, PL = planes_in<ARITH>(), WPL = wplanes<ARITH>();
   constexpr int KW = 9 * CW, ROW_DW = row_dw<ARITH, KW>(), ZW = (PL == 2) ? CW : 1;
+  int item0 = 0;
+  if constexpr (MULTI) item0 = multi_prologue(ma, rows, out, n_items, 0);
   const BlockMap bm = map_block(groups / gpb, n_items);
   if (!bm.valid) return;
-  const int item = bm.item;
+  const int item = bm.item + item0;
   const int img = item / NQ, q = item - img * NQ;
   const int qy = q / QD, qx = q - qy * QD;
   const uint64_t *__restrict__ base = in + ((size_t)img * ID * ID + (size_t)(2 * qy) * ID + 2 * qx) * CW * PL;
@@ -1049,15 +1096,18 @@ __global__ __launch_bounds__(kBlock) void k_quad(const uint64_t *__restrict__ in
 // Generic "KW words in, thresholded bits out": one lane = one vector (FC layers, CNV layer 5,
 // and with SINGLE the 3x3 window gather of CNV layer 4).  Two neurons per iteration.
 // POOL: as in k_vec_x (lane = output pixel, quad on four consecutive lanes, OR of the fire words).
-template <int ARITH, int KW, bool OUT2, bool SINGLE, int CW, int ID, int NPB = 32, bool POOL = false, bool TWO = false>
+template <int ARITH, int KW, bool OUT2, bool SINGLE, int CW, int ID, int NPB = 32, bool POOL = false, bool TWO = false, bool MULTI = false>
 __global__ __launch_bounds__(kBlock) void k_vec(const uint64_t *__restrict__ in, uint32_t *__restrict__ out,
-                                                 const uint32_t *__restrict__ rows, int n_items, int groups, int gpb) {
+                                                 const uint32_t *__restrict__ rows, int n_items, int groups, int gpb, MultiArgs ma = {}) {
   constexpr int PL = planes_in<ARITH>(), WPL = wplanes<ARITH>();
   constexpr int ROW_DW = row_dw<ARITH, KW>(), ZW = (PL == 2) ? KW : 1;
   static_assert(!POOL || SINGLE, "pooling needs the window form");
+  static_assert(!MULTI || NPB == 32, "multi-run launches use the 32-neuron form");
+  int item0 = 0;
+  if constexpr (MULTI) item0 = multi_prologue(ma, rows, out, n_items, groups);  // (results: the 1-bit FC form, `groups` dwords per image)
   const BlockMap bm = map_block(groups / gpb, n_items);
   if (!bm.valid) return;
-  const int item = bm.item;
+  const int item = bm.item + item0;
   uint32_t as[KW][2], az[ZW][2];
   auto load_word = [&](int dst, const uint64_t *__restrict__ src) {
     const uint64_t v = src[0];
@@ -1161,12 +1211,20 @@ __global__ __launch_bounds__(kBlock) void k_vec(const uint64_t *__restrict__ in,
 // strict maximum over the first number_class scores, floored at 0.
 // AR_XNOR score = popcount of matches = MW - m; ternary nets: the signed sum.
 // ---------------------------------------------------------------------------
-template <int ARITH, int KW, bool TWO = false>
+template <int ARITH, int KW, bool TWO = false, bool MULTI = false>
 __global__ __launch_bounds__(kBlock) void k_fclast(const uint64_t *__restrict__ in, int16_t *__restrict__ scores,
                                                     int32_t *__restrict__ classes, const uint32_t *__restrict__ rows,
-                                                    int n_items, int number_class) {
+                                                    int n_items, int number_class, MultiArgs ma = {}) {
   constexpr int PL = planes_in<ARITH>(), WPL = wplanes<ARITH>();
   constexpr int ROW_DW = row_dw<ARITH, KW>();
+  if constexpr (MULTI) {  // (classes only: item counts the segment's images, read at its slot, written run-major)
+    const MultiSeg sg = multi_seg(ma);
+    rows += (size_t)sg.run * ma.stride_dw;
+    n_items = sg.len;
+    in += (size_t)sg.slot * KW * PL;
+    classes += (size_t)sg.run * ma.res_images + sg.image;
+    scores = nullptr;
+  }
   const int item = blockIdx.x * kBlock + threadIdx.x;
   if (item >= n_items) return;
   uint64_t as[KW], az[PL == 2 ? KW : 1];
@@ -1451,8 +1509,15 @@ __global__ __launch_bounds__(512) void k_cnv_tail_a2(const uint64_t *__restrict_
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t msb4(uint32_t d) { return (((d >> 7) & 0x01010101u) * 0x01020408u) >> 24; }
 
+template <bool MULTI = false>
 __global__ __launch_bounds__(kBlock) void k_lfc_binarize(const uint8_t *__restrict__ imgs, uint64_t *__restrict__ out,
-                                                          int n_words) {
+                                                          int n_words, MultiArgs ma = {}) {
+  if constexpr (MULTI) {  // (t counts the words of the segment's images; they start at its slot)
+    const MultiSeg sg = multi_seg(ma);
+    n_words = sg.len * 13;
+    imgs += (size_t)sg.image * 784;
+    out += (size_t)sg.slot * 13;
+  }
   const int t = blockIdx.x * kBlock + threadIdx.x;
   if (t >= n_words) return;
   const int img = t / 13, k = t - img * 13;
@@ -1911,6 +1976,16 @@ __global__ __launch_bounds__(kBlock) void k_lfc_decode(const uint64_t *__restric
   classes[i] = w ? 63 - __builtin_clzll(w) : 0;
 }
 
+// fault campaigns (bnn_mi355x_fault_campaigns): before a wave, each run's next fault patch -- the rebuilt row (and for
+// layer 0 the MFMA table) -- goes from the staging area into that run's blob copy.  One block per span.
+__global__ __launch_bounds__(kBlock) void k_patch(const uint8_t *__restrict__ staging, const PatchSpan *__restrict__ spans,
+                                                   uint8_t *__restrict__ copies) {
+  const PatchSpan p = spans[blockIdx.x];
+  const uint32_t *__restrict__ src = reinterpret_cast<const uint32_t *>(staging + p.src);
+  uint32_t *__restrict__ dst = reinterpret_cast<uint32_t *>(copies + p.dst);
+  for (uint32_t i = threadIdx.x; i < p.bytes / 4; i += kBlock) dst[i] = src[i];
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -2081,6 +2156,54 @@ void run_cnv_t(const CnvLaunch &a) {
   BNN_MARK(a.events, 9, s);
 }
 
+// One multi-run launch of a stage over the records of `a` (kernels.h, MultiLaunch): the 32-neuron staged form only,
+// grid.x from the longest segment (grid_for keeps map_block's XCD grouping), grid.y = one row of blocks per record.
+// RES: the last stage, whose results go to their run-major place.
+#define BNN_MULTI(kern, ipi, groups32, in, out, rows, RES)                                                               \
+  do {                                                                                                                   \
+    const long long it_ = (long long)a.total * (ipi);                                                                    \
+    const int gpb_ = gpb_for(it_, (groups32));                                                                           \
+    const MultiArgs ma_{a.segs, (unsigned)(a.stride / 4), (ipi), (RES) ? a.n : 0};                                       \
+    dim3 g_ = grid_for((long long)a.max_len * (ipi), (groups32) / gpb_);                                                 \
+    g_.y = (unsigned)a.nsegs;                                                                                            \
+    BNN_LAUNCH(kern, g_, s, in, out, rows, (int)it_, (groups32), gpb_, ma_);                                             \
+  } while (0)
+
+template <int ARITH, bool OUT2, bool TWO = false>
+void run_cnv_multi_t(const MultiLaunch &a) {
+  uint32_t *A = reinterpret_cast<uint32_t *>(a.buf0), *B = reinterpret_cast<uint32_t *>(a.buf1);
+  const uint64_t *A64 = reinterpret_cast<const uint64_t *>(a.buf0), *B64 = reinterpret_cast<const uint64_t *>(a.buf1);
+  hipStream_t s = a.stream;
+  if (a.l0_mfma) {
+    const MultiArgs ma{a.segs, (unsigned)(a.stride / 4), 1, 0};
+    BNN_LAUNCH((k_conv0_tile<OUT2, true>), dim3((unsigned)((a.max_len + kL0Imgs - 1) / kL0Imgs), (unsigned)a.nsegs), s, a.images, A,
+               a.l0_mfma, 0, ma);
+  } else {
+    BNN_MULTI((k_conv0<OUT2, true>), 900, 2, a.images, A, a.rows[0], false);
+  }
+  if constexpr (ARITH == AR_XNOR && !OUT2) {
+    BNN_MULTI((k_quad_x<1, 30, true, 32, true>), 196, 2, A64, B, a.rows[1], false);
+    BNN_MULTI((k_quad_x<1, 14, false, 32, true>), 36, 4, B64, A, a.rows[2], false);
+    BNN_MULTI((k_quad_x<2, 12, true, 32, true>), 25, 4, A64, B, a.rows[3], false);
+    BNN_MULTI((k_vec_x<18, true, 2, 5, 32, false, true>), 9, 8, B64, A, a.rows[4], false);
+    BNN_MULTI((k_vec_x<36, false, 1, 1, 32, false, true>), 1, 8, A64, B, a.rows[5], false);
+    BNN_MULTI((k_vec_x<4, false, 1, 1, 32, false, true>), 1, 16, B64, A, a.rows[6], false);
+    BNN_MULTI((k_vec_x<8, false, 1, 1, 32, false, true>), 1, 16, A64, B, a.rows[7], false);
+  } else {
+    BNN_MULTI((k_quad<ARITH, 1, 30, true, OUT2, 32, TWO, true>), 196, 2, A64, B, a.rows[1], false);
+    BNN_MULTI((k_quad<ARITH, 1, 14, false, OUT2, 32, TWO, true>), 36, 4, B64, A, a.rows[2], false);
+    BNN_MULTI((k_quad<ARITH, 2, 12, true, OUT2, 32, TWO, true>), 25, 4, A64, B, a.rows[3], false);
+    BNN_MULTI((k_vec<ARITH, 18, OUT2, true, 2, 5, 32, false, TWO, true>), 9, 8, B64, A, a.rows[4], false);
+    BNN_MULTI((k_vec<ARITH, 36, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 8, A64, B, a.rows[5], false);
+    BNN_MULTI((k_vec<ARITH, 4, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 16, B64, A, a.rows[6], false);
+    BNN_MULTI((k_vec<ARITH, 8, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 16, A64, B, a.rows[7], false);
+  }
+  const MultiArgs ma{a.segs, (unsigned)(a.stride / 4), 1, a.n};
+  dim3 g = grid_for(a.max_len, 1);
+  g.y = (unsigned)a.nsegs;
+  BNN_LAUNCH((k_fclast<ARITH, 8, TWO, true>), g, s, B64, nullptr, a.classes, a.rows[8], a.total, a.number_class, ma);
+}
+
 }  // namespace
 
 const char *stage_name(bool is_cnv, int stage) {
@@ -2229,7 +2352,7 @@ hipError_t run_lfc(NetId net, const LfcLaunch &a) {
     if (a.last_stage == 0) (void)hipMemcpyAsync(A64, a.images, (size_t)n * 13 * 8, hipMemcpyDeviceToDevice, s);
     else L0in = reinterpret_cast<const uint64_t *>(a.images);
   } else if (a.last_stage >= 0) {
-    BNN_LAUNCH(k_lfc_binarize, grid_for(n * 13, 1), s, a.images, A64, (int)(n * 13));
+    BNN_LAUNCH(k_lfc_binarize<>, grid_for(n * 13, 1), s, a.images, A64, (int)(n * 13));
   }
   BNN_MARK(a.events, 1, s);
   uint32_t *W32 = reinterpret_cast<uint32_t *>(a.words);
@@ -2257,6 +2380,56 @@ hipError_t run_lfc(NetId net, const LfcLaunch &a) {
   if (a.classes && a.last_stage >= 5) BNN_LAUNCH(k_lfc_decode, grid_for(n, 1), s, a.words, a.classes, (int)n, a.number_class);
   BNN_MARK(a.events, 6, s);
   if (a.t1) (void)hipEventRecord(a.t1, s);
+  return hipGetLastError();
+}
+
+hipError_t run_cnv_multi(NetId net, const MultiLaunch &a) {
+  if (a.nsegs <= 0 || a.total <= 0) return hipSuccess;
+  if (a.nsegs > 65535) return hipErrorInvalidValue;  // (grid.y)
+  switch (net) {
+    case NET_CNVW1A1: run_cnv_multi_t<AR_XNOR, false>(a); break;
+    case NET_CNVW1A2: run_cnv_multi_t<AR_TB, true>(a); break;
+    case NET_CNVW2A2:
+      if (a.has_two) run_cnv_multi_t<AR_TT, true, true>(a);
+      else run_cnv_multi_t<AR_TT, true>(a);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t run_lfc_multi(NetId net, const MultiLaunch &a) {
+  if (a.nsegs <= 0 || a.total <= 0) return hipSuccess;
+  if (a.nsegs > 65535) return hipErrorInvalidValue;
+  uint32_t *A = reinterpret_cast<uint32_t *>(a.buf0), *B = reinterpret_cast<uint32_t *>(a.buf1);
+  uint64_t *A64 = reinterpret_cast<uint64_t *>(a.buf0), *B64 = reinterpret_cast<uint64_t *>(a.buf1);
+  uint32_t *W32 = reinterpret_cast<uint32_t *>(a.words);
+  hipStream_t s = a.stream;
+  {
+    const MultiArgs ma{a.segs, 0, 13, 0};
+    dim3 g = grid_for((long long)a.max_len * 13, 1);
+    g.y = (unsigned)a.nsegs;
+    BNN_LAUNCH(k_lfc_binarize<true>, g, s, a.images, A64, a.total * 13, ma);
+  }
+  if (net == NET_LFCW1A1) {
+    BNN_MULTI((k_vec_x<13, false, 1, 1, 32, false, true>), 1, 32, A64, B, a.rows[0], false);
+    BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 32, B64, A, a.rows[1], false);
+    BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 32, A64, B, a.rows[2], false);
+    BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 2, B64, W32, a.rows[3], true);
+  } else if (net == NET_LFCW1A2) {
+    BNN_MULTI((k_vec<AR_XNOR, 13, true, false, 1, 1, 32, false, false, true>), 1, 32, A64, B, a.rows[0], false);
+    BNN_MULTI((k_vec<AR_TB, 16, true, false, 1, 1, 32, false, false, true>), 1, 32, B64, A, a.rows[1], false);
+    BNN_MULTI((k_vec<AR_TB, 16, true, false, 1, 1, 32, false, false, true>), 1, 32, A64, B, a.rows[2], false);
+    BNN_MULTI((k_vec<AR_TB, 16, false, false, 1, 1, 32, false, false, true>), 1, 2, B64, W32, a.rows[3], true);
+  } else {
+    return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t scatter_patches(const uint8_t *staging, const PatchSpan *spans, int nspans, uint8_t *copies, hipStream_t s) {
+  if (nspans <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_patch, dim3((unsigned)nspans), dim3(kBlock), 0, s, staging, spans, copies);
   return hipGetLastError();
 }
 

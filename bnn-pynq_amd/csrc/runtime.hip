@@ -60,6 +60,7 @@ namespace bnn {
 namespace {
 
 constexpr int kMaxChunk = 131072;  // images per pass through the stages
+constexpr int kMaxRuns = 4096;      // campaigns per bnn_mi355x_fault_campaigns call (each holds a copy of the blob in HBM)
 constexpr int kForkMin = 16384;     // images: a device-pointer pass of a CNV net of this size and more forks over the two compute lanes
 constexpr int kStageSlots = 4;      // HBM staging buffers of the host paths: two on one compute lane, four on two
 // Events that only TIME device work: a device-scope release at the record point instead of a flush to system scope
@@ -233,6 +234,11 @@ struct Runtime {
   hipEvent_t file_sent[2] = {nullptr, nullptr};
   uint8_t *d_all = nullptr;  // a whole input file's images, resident (fault campaigns)
   size_t all_cap = 0;
+  // bnn_mi355x_fault_campaigns: the runs' blob copies; the staging area (patches, patch spans, segment records); results
+  uint8_t *d_copies = nullptr, *d_camp = nullptr, *d_camp_res = nullptr;
+  size_t copies_cap = 0, camp_cap = 0, camp_res_cap = 0;
+  std::vector<Fault> camp_faults;  // the faults of the last such call, run-major; camp_run[i]: the run of camp_faults[i]
+  std::vector<int> camp_run;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -378,7 +384,7 @@ int upload_blob() {
 void free_workspace() {
   Runtime &r = rt();
   if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.file_cap && !r.all_cap && !r.h_io &&
-      !r.h_classes && !r.h_words)
+      !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap)
     return;
   if (r.device >= 0) (void)hipSetDevice(r.device);
   (void)hipDeviceSynchronize();
@@ -402,6 +408,9 @@ void free_workspace() {
   (void)hipFree(r.d_all);
   r.d_all = nullptr;
   r.all_cap = 0;
+  (void)hipFree(r.d_copies); (void)hipFree(r.d_camp); (void)hipFree(r.d_camp_res);
+  r.d_copies = r.d_camp = r.d_camp_res = nullptr;
+  r.copies_cap = r.camp_cap = r.camp_res_cap = 0;
   (void)hipFree(r.d_file[0]); (void)hipFree(r.d_file[1]);
   r.d_file[0] = r.d_file[1] = nullptr;
   r.h_file[0].reset(); r.h_file[1].reset();
@@ -1837,6 +1846,246 @@ int *inference_multiple_with_faults(const char *path, int number_class, int *ima
   if (image_number) *image_number = n;
   if (usecPerImage) *usecPerImage = usec;
   return result;
+}
+
+int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                unsigned int flip_count, int word_size, int target, const int *target_layers,
+                                unsigned int num_targets, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  r.camp_faults.clear();
+  r.camp_run.clear();
+  if (num_runs < 1 || num_runs > kMaxRuns) {
+    fail("fault_campaigns: num_runs must be 1 ... " + std::to_string(kMaxRuns));
+    return nullptr;
+  }
+  const int R = num_runs;
+  // run q seeds with seed + q: none of them may be 0, which would mean std::random_device
+  if (seed != 0 && 0ull - (uint64_t)seed < (uint64_t)R) {
+    fail("fault_campaigns: seed + run wraps to 0 for a run (0 seeds from std::random_device)");
+    return nullptr;
+  }
+  if (flip_count == 0) {  // like inference_multiple_with_faults: the fault-free classes, once per run
+    int n = 0;
+    float usec = 0.f;
+    int *one = inference_multiple(path, number_class, &n, &usec, 0);
+    if (!one) return nullptr;
+    int *res = new (std::nothrow) int[(size_t)R * n + 1];
+    if (!res) { free_results(one); fail("out of memory"); return nullptr; }
+    for (int q = 0; q < R; q++) std::memcpy(res + (size_t)q * n, one, (size_t)n * sizeof(int));
+    free_results(one);
+    if (image_number) *image_number = n;
+    if (usecPerImage) *usecPerImage = usec / (float)R;
+    return res;
+  }
+#ifdef BNN_VARIANT
+  fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+  return nullptr;
+#endif
+  if (!ready()) return nullptr;
+  if (r.raw.empty()) {
+    fail("fault injection needs the parameter files (load_parameters), not an imported blob");
+    return nullptr;
+  }
+  if (r.l1_mfma || r.l1_literal) {
+    fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the matrix-pipe table is not patched)");
+    return nullptr;
+  }
+  ImageFile f;
+  if (open_image_file(path, f)) return nullptr;
+  const int n = (int)f.n;
+  const size_t total = (size_t)R * n;
+  // every run's plan, drawn exactly as inference_multiple_with_faults draws it with the fault seed set to seed + q
+  std::vector<Fault> faults;
+  std::vector<int> run_of;
+  for (int q = 0; q < R; q++) {
+    std::vector<Fault> plan;
+    const std::string pe = plan_faults(r.spec, seed ? (uint64_t)seed + (uint64_t)q : 0, n, flip_count, word_size, target, target_layers,
+                                       num_targets, plan);
+    if (!pe.empty()) { fail(pe); return nullptr; }
+    faults.insert(faults.end(), plan.begin(), plan.end());
+    run_of.insert(run_of.end(), plan.size(), q);
+  }
+  int *result = new (std::nothrow) int[total + 1];
+  if (!result) { fail("out of memory"); return nullptr; }
+  const int F = (int)flip_count;  // (n > 0: every run has exactly F faults, sorted by image)
+  double device_us = 0.0;
+  auto run = [&]() -> int {
+    if (n == 0) return 0;
+    if (faults.size() != (size_t)R * F) return fail("internal: fault plans of unequal length");
+    // -- host: the patches.  ONE working copy of the memories and the blob; each run's faults are applied in order, every
+    // rebuilt row recorded as that fault's patch, then undone (the touched words restored, the touched rows rebuilt).
+    RawParams raw = r.raw;
+    std::vector<uint8_t> blob = r.blob;
+    PackedHeader h;
+    std::memcpy(&h, blob.data(), sizeof(h));
+    const size_t stride = (blob.size() + 255) & ~(size_t)255;
+    const bool tab = h.l0_mfma_offset && r.l0_mfma;  // layer-0 faults patch the MFMA table too (kernels read it)
+    std::vector<uint8_t> staging;
+    std::vector<std::vector<PatchSpan>> by_wave((size_t)F + 1);  // wave k (>= 1): the k-th patch of every run
+    std::vector<char> wave_two((size_t)F + 1, 0);                // wave k: some run's copy holds a -2 row (cnvW2A2)
+    auto two_flag = [&](int l, int row) -> int {
+      if (r.spec.L[l].arith != AR_TT) return 0;
+      const uint32_t *rows = reinterpret_cast<const uint32_t *>(blob.data() + h.layer[l].offset);
+      return rows[(size_t)row * h.layer[l].row_dwords + 2 + 6 * h.layer[l].kw] != 0;
+    };
+    auto add_span = [&](int k, int q, size_t off, size_t bytes) {
+      by_wave[(size_t)k].push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
+      staging.insert(staging.end(), blob.begin() + off, blob.begin() + off + bytes);
+    };
+    const int base_two = count_two_rows(r.spec, blob);  // (once: per fault the count follows the patched row)
+    struct Saved { uint64_t *word; uint64_t old; };
+    std::vector<Saved> saved;
+    std::vector<std::pair<int, int>> touched;
+    for (int q = 0; q < R; q++) {
+      int two = base_two;
+      if (two > 0) wave_two[0] = 1;
+      saved.clear();
+      touched.clear();
+      for (int k = 0; k < F; k++) {
+        const Fault &flt = faults[(size_t)q * F + k];
+        if (uint64_t *w = fault_word(r.spec, raw, flt)) {
+          saved.push_back({w, *w});
+          const int row = apply_fault(r.spec, raw, flt);
+          const int before = two_flag(flt.layer, row);
+          size_t off = 0, bytes = 0;
+          repack_row(r.spec, raw, flt.layer, row, blob, &off, &bytes);
+          touched.emplace_back(flt.layer, row);
+          two += two_flag(flt.layer, row) - before;
+          if (flt.layer == 0 && h.l0_mfma_offset) {  // repack_row's span runs from the row to the table's end: the two parts
+            const size_t rb = (size_t)h.layer[0].row_dwords * 4;
+            add_span(k + 1, q, h.layer[0].offset + (size_t)row * rb, rb);
+            if (tab) add_span(k + 1, q, h.l0_mfma_offset, kL0MfmaBytes);
+          } else {
+            add_span(k + 1, q, off, bytes);
+          }
+        }
+        if (two > 0) wave_two[(size_t)k + 1] = 1;
+      }
+      for (size_t i = saved.size(); i-- > 0;) *saved[i].word = saved[i].old;
+      for (auto &t : touched) {
+        size_t off, bytes;
+        repack_row(r.spec, raw, t.first, t.second, blob, &off, &bytes);
+      }
+    }
+    if (staging.size() > 0xFFFFFFF0u) return fail("fault_campaigns: too many faults for one call (patch staging above 4 GB)");
+    // -- segments: wave k classifies, for every run, the images between its k-th and (k+1)-th fault time.  A launch holds
+    // at most `cap` images (the activation workspace) and 65 535 records (grid.y); a longer wave is cut over several.
+    const int cap = (int)std::min<size_t>(kMaxChunk, total);
+    struct Launch { size_t seg0; int nsegs, max_len, total, wave; };
+    std::vector<MultiSeg> segs;
+    std::vector<Launch> launches;
+    for (int k = 0; k <= F; k++) {
+      Launch cur{segs.size(), 0, 0, 0, k};
+      auto close = [&]() {
+        if (cur.nsegs) launches.push_back(cur);
+        cur = Launch{segs.size(), 0, 0, 0, k};
+      };
+      for (int q = 0; q < R; q++) {
+        int b = k ? faults[(size_t)q * F + k - 1].image : 0;
+        const int e = k < F ? faults[(size_t)q * F + k].image : n;
+        while (b < e) {
+          if (cur.total == cap || cur.nsegs == 65535) close();
+          const int m = std::min(e - b, cap - cur.total);
+          segs.push_back(MultiSeg{q, b, cur.total, m});
+          cur.nsegs++;
+          cur.total += m;
+          cur.max_len = std::max(cur.max_len, m);
+          b += m;
+        }
+      }
+      close();
+    }
+    // -- one upload: patches, then patch spans by wave, then segment records
+    std::vector<size_t> span_first((size_t)F + 2, 0);
+    for (int k = 0; k <= F; k++) span_first[(size_t)k + 1] = span_first[(size_t)k] + by_wave[(size_t)k].size();
+    const size_t spans_off = (staging.size() + 255) & ~(size_t)255;
+    const size_t segs_off = spans_off + span_first[(size_t)F + 1] * sizeof(PatchSpan);
+    std::vector<uint8_t> upload(segs_off + segs.size() * sizeof(MultiSeg));
+    std::memcpy(upload.data(), staging.data(), staging.size());
+    for (int k = 0; k <= F; k++)
+      if (!by_wave[(size_t)k].empty())
+        std::memcpy(upload.data() + spans_off + span_first[(size_t)k] * sizeof(PatchSpan), by_wave[(size_t)k].data(), by_wave[(size_t)k].size() * sizeof(PatchSpan));
+    if (!segs.empty()) std::memcpy(upload.data() + segs_off, segs.data(), segs.size() * sizeof(MultiSeg));
+    // -- device buffers
+    const bool cnv = r.spec.is_cnv;
+    if (load_file_resident(f, n) || reserve(cap)) return -1;
+    if (grow(r.d_copies, r.copies_cap, (size_t)R * stride) || grow(r.d_camp, r.camp_cap, upload.size()) ||
+        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+      return -1;
+    std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
+    if (!cnv) w.resize(total);
+    DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+    if (settle_handover(r.stream)) return -1;
+    while (r.time_events.size() < 2) {
+      hipEvent_t e;
+      HIP_OK(hipEventCreateWithFlags(&e, kTimeEventFlags));
+      r.time_events.push_back(e);
+    }
+    // -- all of it on one stream, one wait at the end
+    HIP_OK(hipEventRecord(r.time_events[0], r.stream));
+    HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, blob.size(), hipMemcpyDeviceToDevice, r.stream));
+    for (size_t have = 1; have < (size_t)R; have *= 2) {  // replicate by doubling
+      const size_t c = std::min(have, (size_t)R - have);
+      HIP_OK(hipMemcpyAsync(r.d_copies + have * stride, r.d_copies, c * stride, hipMemcpyDeviceToDevice, r.stream));
+    }
+    HIP_OK(hipMemcpyAsync(r.d_camp, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
+    const PatchSpan *d_spans = reinterpret_cast<const PatchSpan *>(r.d_camp + spans_off);
+    const MultiSeg *d_segs = reinterpret_cast<const MultiSeg *>(r.d_camp + segs_off);
+    size_t li = 0;
+    for (int k = 0; k <= F; k++) {
+      const int ns = (int)(span_first[(size_t)k + 1] - span_first[(size_t)k]);
+      hipError_t e = scatter_patches(r.d_camp, d_spans + span_first[(size_t)k], ns, r.d_copies, r.stream);
+      if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      for (; li < launches.size() && launches[li].wave == k; li++) {
+        const Launch &L = launches[li];
+        MultiLaunch a{};
+        a.images = r.d_all;
+        a.segs = d_segs + L.seg0;
+        a.nsegs = L.nsegs; a.max_len = L.max_len; a.total = L.total; a.n = n;
+        a.buf0 = r.buf0; a.buf1 = r.buf1;
+        for (int l = 0; l < r.spec.nlayers; l++) a.rows[l] = reinterpret_cast<const uint32_t *>(r.d_copies + h.layer[l].offset);
+        a.l0_mfma = tab ? r.d_copies + h.l0_mfma_offset : nullptr;
+        a.stride = stride;
+        a.has_two = wave_two[(size_t)k] != 0;
+        a.classes = reinterpret_cast<int32_t *>(r.d_camp_res);
+        a.words = reinterpret_cast<uint64_t *>(r.d_camp_res);
+        a.number_class = number_class;
+        a.stream = r.stream;
+        e = cnv ? run_cnv_multi(r.spec.id, a) : run_lfc_multi(r.spec.id, a);
+        if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      }
+    }
+    HIP_OK(hipEventRecord(r.time_events[1], r.stream));
+    if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    for (size_t i = 0; !cnv && i < total; i++) result[i] = lfc_class_batched(w[i], number_class);
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, r.time_events[0], r.time_events[1]));
+    drain.ok();
+    device_us = ms * 1000.0;
+    return 0;
+  };
+  if (run() < 0) {
+    delete[] result;
+    return nullptr;
+  }
+  r.camp_faults = std::move(faults);
+  r.camp_run = std::move(run_of);
+  if (image_number) *image_number = n;
+  if (usecPerImage) *usecPerImage = total ? (float)(device_us / (double)total) : 0.f;
+  return result;
+}
+
+int bnn_mi355x_last_campaign_faults(int *records, int cap_records) {
+  Runtime &r = rt();
+  const int n = (int)r.camp_faults.size();
+  for (int i = 0; i < n && i < cap_records && records; i++) {
+    const Fault &f = r.camp_faults[(size_t)i];
+    const int v[9] = {r.camp_run[(size_t)i], f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
+    for (int j = 0; j < 9; j++) records[i * 9 + j] = v[j];
+  }
+  return n;
 }
 
 void free_results(int *result) { delete[] result; }

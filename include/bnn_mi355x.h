@@ -180,6 +180,24 @@ int bnn_mi355x_chunk_plan(int n_images, int from_file, int *bases, int cap);
  * returns the number of faults. */
 int bnn_mi355x_set_fault_seed(unsigned long long seed);
 int bnn_mi355x_last_faults(int *records, int cap_records);
+/* Many campaigns in one call, side by side on the GPU: num_runs independent campaigns over the images of
+ * `path`, run r exactly what load_parameters(<current>) + bnn_mi355x_set_fault_seed(seed + r) +
+ * inference_multiple_with_faults(...) returns.  Returns a new int[num_runs * n], run-major (free_results).
+ * seed == 0: each run seeds from std::random_device; else run r uses seed + r (refused if any seed + r is
+ * 0 mod 2^64).  Every run starts from the parameters loaded at the time of the call, faults of earlier calls
+ * included; the loaded parameters are NOT changed.  usecPerImage: device time of the whole call / (num_runs * n).
+ * Refuses (NULL + last_error) what inference_multiple_with_faults refuses -- the hardened variants, an imported
+ * blob, the BNN_MI355X_L1 comparison forms -- and num_runs outside 1 ... 4096.  flip_count == 0: the fault-free
+ * classes, once per run.  HBM: num_runs x bnn_mi355x_params_bytes() for the runs' parameter copies.
+ * The runs go in waves: in wave k every run classifies the images between its k-th and (k+1)-th fault time, all
+ * runs in the same launches.
+ * last_campaign_faults: the faults of the last fault_campaigns call as records of 9 ints {run, image, target,
+ * layer, mem, ind, thresh, bit, word_size}, run-major, each run in the order bnn_mi355x_last_faults would list
+ * it; returns the count. */
+int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                unsigned int flip_count, int word_size, int target, const int *target_layers,
+                                unsigned int num_targets, int *image_number, float *usecPerImage);
+int bnn_mi355x_last_campaign_faults(int *records, int cap_records);
 /* Host-only helpers of the same machinery (no GPU touched): draw a fault plan; pack a parameter
  * directory with a list of fault records applied (what the GPU holds after those faults). */
 int bnn_mi355x_plan_faults(unsigned long long seed, int num_images, unsigned int flip_count, int word_size, int target,

@@ -161,7 +161,10 @@ def run(obj):
     fns = functions(disassemble(obj))
     report, ok = {}, True
     for prefix, logic_ops, pairs, other, *rest in CHECKS:
-        names = [n for n in fns if ("::" + prefix + "(") in n or n.startswith("void " + prefix + "(") or (prefix + "(") in n]
+        # (the stage kernels carry one more, defaulted template flag -- MULTI = false on these launches -- since the
+        # multi-run forms of bnn_mi355x_fault_campaigns: the same instantiation under its longer name)
+        forms = (prefix, prefix[:-1] + ", false>") if prefix.endswith(">") else (prefix,)
+        names = [n for n in fns if any(("::" + f + "(") in n or n.startswith("void " + f + "(") or (f + "(") in n for f in forms)]
         if len(names) != 1:
             report[prefix] = {"problems": ["kernel not found in the code object (%d matches)" % len(names)]}
             ok = False

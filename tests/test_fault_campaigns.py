@@ -242,3 +242,55 @@ def test_fault_test_batched_equals_sequential(tmp_path):
     bat = ft.run_test(4, 30, 1, -1, (), batched=True, seed=1000)
     assert seq[0] == bat[0] and seq[2] == bat[2] and len(bat[1]) == 4
     assert len({tuple(r) for r in bat[0]}) > 1
+
+
+# Multi-run launches choose their groups per block from the launch's image count (run_cnv_multi_t, gpb_for over
+# total x items per image): the campaigns below put a launch on each side of every change point of that choice
+# (dispatch_forms.multi_forms), one flip per run, so that wave 0 classifies sum(t) images and wave 1 runs x images - sum(t)
+# (t: the runs' fault times).  (runs, images, seed) -> the two wave totals, checked from the returned records; the last
+# campaign's waves hold more than a launch takes and are cut at 131 072.
+MULTI_CAMPAIGNS = [(4, 1337, 2368, (2673, 2675)), (7, 4159, 5410, (14557, 14556)), (7, 5989, 15395, (20962, 20961)),
+                   (27, 4313, 2581, (58226, 58225)), (64, 4500, 1, (152194, 135806))]
+MULTI_SETS = [("cnvW1A1", "cifar10"), ("cnvW1A2", "cifar10"), ("cnvW2A2", "cifar10"), ("cnvW2A2", None)]
+
+
+def launch_totals(wave_totals, cap):
+    return [min(cap, w - b) for w in wave_totals for b in range(0, w, cap)]
+
+
+def test_multi_campaigns_straddle_every_edge():
+    import dispatch_forms as df
+    edges = df.edges(df.multi_forms)
+    totals = set()
+    for runs, n, _, waves in MULTI_CAMPAIGNS:
+        totals |= set(launch_totals(waves, min(KMAX_CHUNK, runs * n)))
+    assert all(e - 1 in totals or e - 2 in totals for e in edges) and all(e in totals or e + 1 in totals for e in edges)
+    assert launch_totals((152194, 135806), KMAX_CHUNK) == [131072, 21122, 131072, 4734]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("network,dataset", MULTI_SETS, ids=lambda x: x or "neg2")
+def test_multi_run_forms_at_every_edge(network, dataset, tmp_path):
+    """every run of each campaign equal to its sequential call; for the random -2 set of cnvW2A2 (dataset None) every
+    wave takes the -2-aware kernels, its base parameters holding -2 rows"""
+    L = gl.load(network)
+    if dataset:
+        pdir = gl.param_dir(dataset, network)
+    else:
+        import random_params
+        pdir = str(tmp_path / "neg2")
+        random_params.make(pdir, network, 5, neg2=0.03)
+        assert (ol.Oracle(network, pdir).weights(1) == -2).any()
+    try:
+        for runs, n, seed, waves in MULTI_CAMPAIGNS:
+            imgs, path = write_images(network, n, tmp_path, seed=n)
+            got, recs = check_against_sequential(L, pdir, path, runs, seed, 1, 1, 0)
+            assert len(recs) == runs and sorted(recs[:, 0].tolist()) == list(range(runs))
+            t = int(recs[:, 1].sum())
+            assert (t, runs * n - t) == waves, (runs, n, seed)
+            if network == "cnvW1A2" and runs == 4:  # two runs replayed fault by fault in the restatement
+                for r in (0, 3):
+                    want = oracle_replay(ol.Oracle(network, pdir), imgs, recs[recs[:, 0] == r][:, 1:])
+                    assert got[r].tolist() == want.tolist()
+    finally:
+        L.load_parameters(gl.param_dir("cifar10", network).encode())

@@ -213,6 +213,49 @@ class PynqBNN:
         self.usecPerImage = usec.value
         return result
 
+    # extension: exhaustive single-fault sweeps (which bits matter)
+    def enumerate_faults(self, layer, target, word_size=1):
+        """-> int32 array (k, 8): every distinct fault of one layer's weight (target 0) or threshold (target 1)
+        memory as records of bnn_mi355x_plan_faults (image 0), ordered by (mem, ind, thresh, bit)."""
+        lib = self.interface
+        k = lib.bnn_mi355x_enumerate_faults(layer, target, word_size, 0, None, 0)
+        if k < 0:
+            raise ValueError(lib.bnn_mi355x_last_error().decode())
+        recs = np.zeros((k, 8), np.int32)
+        for first in range(0, k, 1 << 20):  # (cap_records is an int)
+            m = min(1 << 20, k - first)
+            lib.bnn_mi355x_enumerate_faults(layer, target, word_size, first,
+                                            recs[first:].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), m)
+        return recs
+
+    def fault_sweep(self, path, records, max_diffs=None):
+        """Every record (8 ints, the image field ignored) alone for every image of `path`: -> (changed, diffs) with
+        changed[f] the images whose class differs from the fault-free one and diffs int32 (k, 3) rows {fault, image,
+        class} of those images in (fault, image) order (the first max_diffs of them; None: all).  The loaded
+        parameters are not changed.  usecPerImage: device time / (faults * images)."""
+        lib = self.interface
+        recs = np.ascontiguousarray(records, np.int32).reshape(-1, 8)
+        nf = recs.shape[0]
+        changed = np.zeros(max(nf, 1), np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        cap = (1 << 22) if max_diffs is None else int(max_diffs)
+        while True:
+            diffs = np.zeros((max(cap, 1), 3), np.int32)
+            total = lib.bnn_mi355x_fault_sweep(path.encode(), len(self.classes), recs.ctypes.data_as(ip), nf,
+                                               changed.ctypes.data_as(ip), diffs.ctypes.data_as(ip), cap, ctypes.byref(size),
+                                               ctypes.byref(usec))
+            if total < 0:
+                raise RuntimeError("fault sweep failed: " + lib.bnn_mi355x_last_error().decode())
+            if max_diffs is not None or total <= cap:
+                break
+            cap = total  # (all of them asked for, more than guessed: once more with room for every one)
+        self.usecPerImage = usec.value
+        if nf and size.value:
+            print("Fault sweep took %.2f microseconds for %d faults x %d images, %.4f usec per image" % (
+                usec.value * nf * size.value, nf, size.value, usec.value))
+        return changed[:nf], diffs[:min(cap, total)]
+
     def inference_multiple_detail(self, path):
         size = ctypes.c_int(0)
         usec = ctypes.c_float(0)
@@ -375,6 +418,15 @@ class CnvClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
+    # extension: exhaustive single-fault sweeps (PynqBNN.fault_sweep)
+    def classify_images_fault_sweep(self, imgs, records, max_diffs=None):
+        return self._with_tmp(imgs, lambda p: self.bnn.fault_sweep(p, records, max_diffs))
+
+    def classify_cifars_fault_sweep(self, path, records, max_diffs=None):
+        result = self.bnn.fault_sweep(path, records, max_diffs)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
     def classify_images_details(self, imgs):
         return self._with_tmp(imgs, self.bnn.inference_multiple_detail)
 
@@ -432,6 +484,11 @@ class LfcClassifier:
                                          target_layers=[], seed=0):
         result = self.bnn.inference_multiple_with_faults_runs(mnist_format_file, num_runs, num_faults, flip_word,
                                                               target_type, target_layers, seed)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_mnists_fault_sweep(self, mnist_format_file, records, max_diffs=None):
+        result = self.bnn.fault_sweep(mnist_format_file, records, max_diffs)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

@@ -11,7 +11,14 @@ On the MI355X runtime a run of 10 000 CIFAR-10 images with 100 upsets takes abou
 3 ms parameter reload (tools/fault_campaign_rate.py).  ``batched=True`` runs all of a test's runs in ONE
 call instead (``classify_*_with_faults_runs``: the runs side by side on the GPU, tools/fault_campaigns_rate.py);
 with the same ``seed`` (run i seeded with seed + i) both paths return identical results.
+
+``FaultTest.sensitivity`` / ``NetworkTest.sensitivity_map`` answer the question random campaigns can only
+sample: which bits matter.  Every distinct single fault of the chosen layers is evaluated alone on the whole input
+set (``PynqBNN.fault_sweep``: the fault-free pass once, each fault from its own layer on, (fault, image) pairs
+dropped as soon as their activations equal the fault-free ones).
 """
+import numpy as np
+
 from .. import bnn as _bnn
 from .. import util
 
@@ -93,6 +100,40 @@ class FaultTest:
         print("Accuracies:", accuracies)
         print()
         return (results, times, accuracies)
+
+
+    def _classify(self, classifier, method, *args):
+        """classifier.classify_<set>_<method>(input, *args) for this test's input set"""
+        kind = {"cifar10": "cifars", "mnist": "mnists"}.get(self.dataset, "images")
+        return getattr(classifier, "classify_{}{}".format(kind, method))(self.input_file, *args)
+
+    def sensitivity(self, layers, target_type=0, word_size=1):
+        """Every distinct single fault of `layers` (target_type 0 weights / 1 thresholds, word_size adjacent bits),
+        each alone on the whole input set.  -> (records int32 [k, 8], changed [k]: images whose class the fault
+        changes, accuracy [k] in percent), plus the fault-free accuracy as `self.control_accuracy`.  The accuracies
+        come from the labels, the fault-free classes and the sparse per-fault differences."""
+        if target_type not in (0, 1):
+            raise ValueError("sensitivity: target_type must be 0 (weights) or 1 (thresholds)")
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        records = [classifier.bnn.enumerate_faults(l, target_type, word_size) for l in layers]
+        records = np.concatenate(records) if records else np.zeros((0, 8), np.int32)
+        clean = np.asarray(self._classify(classifier, ""), np.int64)
+        labels = np.asarray(list(self.labels), np.int64)
+        n = len(labels)
+        right = clean[:n] == labels
+        changed, diffs = self._classify(classifier, "_fault_sweep", records)
+        # per fault: the fault-free count of right answers, minus those a changed class breaks, plus those it mends
+        delta = np.zeros(len(records), np.int64)
+        img, cls = diffs[:, 1], diffs[:, 2].astype(np.int64)
+        ok = img < n
+        now = np.zeros(len(diffs), np.int64)
+        now[ok] = (cls[ok] == labels[img[ok]]).astype(np.int64) - right[img[ok]].astype(np.int64)
+        np.add.at(delta, diffs[:, 0], now)
+        self.control_accuracy = 100.0 * right.sum() / n if n else 0.0
+        accuracy = 100.0 * (right.sum() + delta) / n if n else np.zeros(len(records))
+        print("{}-{}: {} single faults in layer(s) {} swept, {} change some image".format(
+            self.network, self.dataset, len(records), list(layers), int((changed > 0).sum())))
+        return records, changed, accuracy
 
 
 class CNVFaultTest(FaultTest):
@@ -204,6 +245,36 @@ class NetworkTest:
             name = "{}/{}_{}".format(folder, self.fault_test.network, self.fault_test.dataset)
             name += "_stats_layer{}.json".format(list(target_layers)) if len(target_layers) > 0 else "_stats.json"
             util.write_dict_to_file(name, stats)
+
+    def sensitivity_map(self, output_folder, layers, test_types):
+        """Exhaustive single-fault sweeps (FaultTest.sensitivity): per layer and test type (its target_type: weights or
+        thresholds, and word size) one file output_folder/<network>/<dataset>/sensitivity/<network>_layer<L>_<type>.json
+        with every fault's record, changed-image count and accuracy, and one per-layer summary file next to them: per
+        test type the mean and max changed-image count, the fraction of faults that change any image, mean / min
+        accuracy and the fault-free accuracy."""
+        folder = "{}/{}/{}/sensitivity/".format(output_folder, self.fault_test.network, self.fault_test.dataset)
+        for layer in layers:
+            summary = {"network": self.fault_test.network, "dataset": self.fault_test.dataset, "layer": layer, "results": {}}
+            for test in test_types:
+                if test.target_type not in (0, 1):
+                    raise ValueError("sensitivity_map: test types target weights or thresholds, not any")
+                records, changed, accuracy = self.fault_test.sensitivity([layer], test.target_type, test.word_size)
+                summary["control"] = self.fault_test.control_accuracy
+                name = test.name.replace(" ", "-")
+                util.write_dict_to_file("{}/{}_layer{}_{}.json".format(folder, self.fault_test.network, layer, name), {
+                    "network": self.fault_test.network, "dataset": self.fault_test.dataset, "layer": layer,
+                    "test": test.name, "word size": test.word_size, "control": self.fault_test.control_accuracy,
+                    "fields": ["target", "layer", "mem", "ind", "thresh", "bit", "word_size", "changed", "accuracy"],
+                    "faults": [[int(x) for x in r[1:]] + [int(c), float(a)] for r, c, a in zip(records, changed, accuracy)]})
+                k = len(records)
+                summary["results"][test.name] = {
+                    "faults": k,
+                    "mean changed": float(changed.mean()) if k else 0.0,
+                    "max changed": int(changed.max()) if k else 0,
+                    "fraction changing any image": float((changed > 0).mean()) if k else 0.0,
+                    "mean accuracy": float(accuracy.mean()) if k else summary["control"],
+                    "min accuracy": float(accuracy.min()) if k else summary["control"]}
+            util.write_dict_to_file("{}/{}_layer{}_summary.json".format(folder, self.fault_test.network, layer), summary)
 
     def comprehensive_test(self, output_folder, num_runs, flip_counts, target_layers=()):
         """all six combinations of {any, weight, threshold} x {bit, 8-bit word}.  (The reference's version

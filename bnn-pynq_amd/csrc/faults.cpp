@@ -117,4 +117,40 @@ uint64_t *fault_word(const NetSpec &net, RawParams &raw, const Fault &f) {
   return &raw.t[f.layer][f.mem][(size_t)f.ind * L.nthr + f.thresh];
 }
 
+long enumerate_faults(const NetSpec &net, int layer, int target, int word_size, long first, Fault *out, long cap) {
+  if (layer < 0 || layer >= net.nlayers || (target != 0 && target != 1) || word_size < 1 || word_size > 64) return -1;
+  const LayerSpec &L = net.L[layer];
+  // element width and (mem, ind, thresh) shape of the memory; `per` aligned positions of the bit in an element
+  const long esz = target == 0 ? (long)L.fold.simd * L.wbits : (long)elem_bits(L);
+  const long inds = target == 0 ? L.fold.wmem : L.fold.tmem, thr = target == 0 ? 1 : L.nthr;
+  const long per = (esz + word_size - 1) / word_size;
+  const long total = target == 0 || L.nthr > 0 ? (long)L.fold.pe * inds * thr * per : 0;
+  for (long i = std::max(first, 0L), k = 0; out && i < total && k < cap; i++, k++) {
+    Fault f{};
+    long e = i / per;
+    f.bit = (int)((i - e * per) * word_size);
+    f.thresh = (int)(e % thr);
+    e /= thr;
+    f.ind = (int)(e % inds);
+    f.mem = (int)(e / inds);
+    f.layer = layer;
+    f.target = target;
+    f.word_size = word_size;
+    out[k] = f;
+  }
+  return total;
+}
+
+std::string check_fault(const NetSpec &net, const Fault &f) {
+  if (f.layer < 0 || f.layer >= net.nlayers) return "fault record: layer out of range";
+  if (f.target != 0 && f.target != 1) return "fault record: target must be 0 (weights) or 1 (thresholds)";
+  if (f.word_size < 1 || f.word_size > 64) return "fault record: word_size must be 1 ... 64";
+  const LayerSpec &L = net.L[f.layer];
+  const int esz = f.target == 0 ? L.fold.simd * L.wbits : (int)elem_bits(L);
+  if (f.target == 1 && L.nthr == 0) return "fault record: layer " + std::to_string(f.layer) + " has no threshold memory";
+  const bool in = f.mem >= 0 && f.mem < L.fold.pe && f.ind >= 0 && f.ind < (f.target == 0 ? L.fold.wmem : L.fold.tmem) &&
+                  f.thresh >= 0 && f.thresh < (f.target == 0 ? 1 : L.nthr) && f.bit >= 0 && f.bit < esz;
+  return in ? "" : "fault record outside the layer's memories (layer " + std::to_string(f.layer) + ")";
+}
+
 }  // namespace bnn

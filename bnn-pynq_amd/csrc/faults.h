@@ -36,4 +36,13 @@ int apply_fault(const NetSpec &net, RawParams &raw, const Fault &f);
 // (a layer-0 threshold is read back as its integer part): undoing a fault means restoring this word.
 uint64_t *fault_word(const NetSpec &net, RawParams &raw, const Fault &f);
 
+// Every distinct single fault of one layer's weight (target 0) or threshold (target 1) memory: the positions
+// plan_faults can draw, the bit aligned down to a multiple of word_size as apply_fault aligns it, ordered by
+// (mem, ind, thresh, bit).  Returns their number (0: a layer without threshold memory), -1 for a bad layer, target
+// or word_size; writes faults first .. first + cap - 1 of them to out (image 0).
+long enumerate_faults(const NetSpec &net, int layer, int target, int word_size, long first, Fault *out, long cap);
+
+// "" when f lies inside the memories plan_faults draws from (the bit inside its element), else the reason
+std::string check_fault(const NetSpec &net, const Fault &f);
+
 }  // namespace bnn

@@ -98,6 +98,9 @@ struct MultiLaunch {
   uint64_t *words;            // LFC: device, raw output word per image of every run (run-major)
   int number_class;
   hipStream_t stream;
+  // run the stages of layers first..last only (bnn_mi355x_fault_sweep); layer l's stage reads layer l-1's output where
+  // the full pass leaves it (stage_output_bytes).  LFC: layer 0's stage includes the binariser.
+  int first = 0, last = 1 << 30;
 };
 hipError_t run_cnv_multi(NetId net, const MultiLaunch &a);
 hipError_t run_lfc_multi(NetId net, const MultiLaunch &a);
@@ -105,5 +108,19 @@ hipError_t run_lfc_multi(NetId net, const MultiLaunch &a);
 // copy `bytes` from staging + src to copies + dst for each span (one block per span); offsets and sizes are multiples of 4
 struct PatchSpan { uint64_t dst; uint32_t src, bytes; };
 hipError_t scatter_patches(const uint8_t *staging, const PatchSpan *spans, int nspans, uint8_t *copies, hipStream_t s);
+
+// Single-fault sweeps (bnn_mi355x_fault_sweep).  Row (q, j) of a broadcast, j < rows: dst + q * dst_run_stride +
+// j * row_bytes <- src + j * row_bytes, for q < runs (row_bytes a multiple of 4).
+hipError_t sweep_broadcast(const uint8_t *src, size_t row_bytes, int rows, int runs, uint8_t *dst, size_t dst_run_stride,
+                           hipStream_t s);
+// alive[slot] = 1 for every image of the records whose `row_bytes` (a multiple of 16) at act + slot * row_bytes differ
+// from base + image * row_bytes; other entries are left as they are.  One wave per image.
+hipError_t sweep_mark(const uint8_t *act, const uint8_t *base, int row_bytes, const MultiSeg *segs, int nsegs, int max_len,
+                      uint8_t *alive, hipStream_t s);
+// run q < runs: counts[q] = #{j < win : classes[q * n + j] != base[j]}.  sweep_emit: the pairs {j, classes[q * n + j]} of
+// those images to out + 2 * offsets[q] ..., in image order (counts as sweep_count left them).
+hipError_t sweep_count(const int32_t *classes, const int32_t *base, int n, int win, int runs, int *counts, hipStream_t s);
+hipError_t sweep_emit(const int32_t *classes, const int32_t *base, int n, int win, int runs, const int *counts, const long long *offsets,
+                      int *out, hipStream_t s);
 
 }  // namespace bnn

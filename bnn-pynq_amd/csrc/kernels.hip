@@ -1986,6 +1986,81 @@ __global__ __launch_bounds__(kBlock) void k_patch(const uint8_t *__restrict__ st
   for (uint32_t i = threadIdx.x; i < p.bytes / 4; i += kBlock) dst[i] = src[i];
 }
 
+// Single-fault sweeps (bnn_mi355x_fault_sweep).  k_sweep_bcast: the fault-free activations (or results) of the window's
+// images into every run's slots -- a lane per V bytes, the rows of a run contiguous on both sides.
+template <int V>
+__global__ __launch_bounds__(kBlock) void k_sweep_bcast(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, long long per_run,
+                                                        long long units, unsigned long long dst_run_stride) {
+  typedef typename std::conditional<V == 16, uint4, uint32_t>::type U;
+  const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= units) return;
+  const long long q = t / per_run, u = t - q * per_run;
+  reinterpret_cast<U *>(dst + q * dst_run_stride)[u] = reinterpret_cast<const U *>(src)[u];
+}
+
+// k_sweep_mark: does an image's stage output differ from its fault-free output?  One wave per image (blockIdx.y the
+// record, four images per block), 16-byte loads, one ballot; only the differing images are written (the runtime clears
+// `alive` first).  Memory-bound: 2 x row_bytes read per image.
+__global__ __launch_bounds__(kBlock) void k_sweep_mark(const uint8_t *__restrict__ act, const uint8_t *__restrict__ base, int row_units,
+                                                       const MultiSeg *__restrict__ segs, uint8_t *__restrict__ alive) {
+  const MultiSeg sg = segs[blockIdx.y];
+  const int j = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (j >= sg.len) return;  // (wave-uniform)
+  const uint4 *__restrict__ a = reinterpret_cast<const uint4 *>(act) + (size_t)(sg.slot + j) * row_units;
+  const uint4 *__restrict__ b = reinterpret_cast<const uint4 *>(base) + (size_t)(sg.image + j) * row_units;
+  uint32_t d = 0;
+  for (int u = lane; u < row_units; u += 64) {
+    const uint4 x = a[u], y = b[u];
+    d |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+  }
+  if (__ballot(d != 0) && lane == 0) alive[sg.slot + j] = 1;
+}
+
+// k_sweep_classes: a block per run over the window's images; changed = the class differs from the fault-free one.
+// Counts, or (EMIT) the changed images' {image, class} pairs in image order from the run's offset (wave ballots and a
+// prefix over the block's four waves).
+template <bool EMIT>
+__global__ __launch_bounds__(kBlock) void k_sweep_classes(const int32_t *__restrict__ classes, const int32_t *__restrict__ base, int n,
+                                                          int win, int *__restrict__ counts, const long long *__restrict__ offsets,
+                                                          int *__restrict__ out) {
+  __shared__ int wave_n[kBlock / 64];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t *__restrict__ c = classes + (size_t)q * n;
+  long long at = 0;
+  if constexpr (EMIT) {
+    if (counts[q] == 0) return;  // (block-uniform)
+    at = offsets[q];
+  }
+  int total = 0;
+  for (int j0 = 0; j0 < win; j0 += kBlock) {
+    const int j = j0 + tid;
+    const int32_t v = j < win ? c[j] : 0;
+    const bool ch = j < win && v != base[j];
+    if constexpr (EMIT) {
+      const uint64_t m = __ballot(ch);
+      if (lane == 0) wave_n[wave] = __popcll(m);
+      __syncthreads();
+      int before = 0, all = 0;
+      for (int w = 0; w < kBlock / 64; w++) {
+        before += w < wave ? wave_n[w] : 0;
+        all += wave_n[w];
+      }
+      if (ch) {
+        const long long o = at + before + __popcll(m & ((1ull << lane) - 1));
+        out[2 * o] = j;
+        out[2 * o + 1] = v;
+      }
+      at += all;
+      __syncthreads();  // (wave_n is rewritten by the next round)
+    } else {
+      total += __syncthreads_count(ch);
+    }
+  }
+  if constexpr (!EMIT) {
+    if (tid == 0) counts[q] = total;
+  }
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -2174,30 +2249,32 @@ void run_cnv_multi_t(const MultiLaunch &a) {
   uint32_t *A = reinterpret_cast<uint32_t *>(a.buf0), *B = reinterpret_cast<uint32_t *>(a.buf1);
   const uint64_t *A64 = reinterpret_cast<const uint64_t *>(a.buf0), *B64 = reinterpret_cast<const uint64_t *>(a.buf1);
   hipStream_t s = a.stream;
-  if (a.l0_mfma) {
+  const auto in = [&](int l) { return a.first <= l && l <= a.last; };  // (layer l's stage is run)
+  if (in(0) && a.l0_mfma) {
     const MultiArgs ma{a.segs, (unsigned)(a.stride / 4), 1, 0};
     BNN_LAUNCH((k_conv0_tile<OUT2, true>), dim3((unsigned)((a.max_len + kL0Imgs - 1) / kL0Imgs), (unsigned)a.nsegs), s, a.images, A,
                a.l0_mfma, 0, ma);
-  } else {
+  } else if (in(0)) {
     BNN_MULTI((k_conv0<OUT2, true>), 900, 2, a.images, A, a.rows[0], false);
   }
   if constexpr (ARITH == AR_XNOR && !OUT2) {
-    BNN_MULTI((k_quad_x<1, 30, true, 32, true>), 196, 2, A64, B, a.rows[1], false);
-    BNN_MULTI((k_quad_x<1, 14, false, 32, true>), 36, 4, B64, A, a.rows[2], false);
-    BNN_MULTI((k_quad_x<2, 12, true, 32, true>), 25, 4, A64, B, a.rows[3], false);
-    BNN_MULTI((k_vec_x<18, true, 2, 5, 32, false, true>), 9, 8, B64, A, a.rows[4], false);
-    BNN_MULTI((k_vec_x<36, false, 1, 1, 32, false, true>), 1, 8, A64, B, a.rows[5], false);
-    BNN_MULTI((k_vec_x<4, false, 1, 1, 32, false, true>), 1, 16, B64, A, a.rows[6], false);
-    BNN_MULTI((k_vec_x<8, false, 1, 1, 32, false, true>), 1, 16, A64, B, a.rows[7], false);
+    if (in(1)) BNN_MULTI((k_quad_x<1, 30, true, 32, true>), 196, 2, A64, B, a.rows[1], false);
+    if (in(2)) BNN_MULTI((k_quad_x<1, 14, false, 32, true>), 36, 4, B64, A, a.rows[2], false);
+    if (in(3)) BNN_MULTI((k_quad_x<2, 12, true, 32, true>), 25, 4, A64, B, a.rows[3], false);
+    if (in(4)) BNN_MULTI((k_vec_x<18, true, 2, 5, 32, false, true>), 9, 8, B64, A, a.rows[4], false);
+    if (in(5)) BNN_MULTI((k_vec_x<36, false, 1, 1, 32, false, true>), 1, 8, A64, B, a.rows[5], false);
+    if (in(6)) BNN_MULTI((k_vec_x<4, false, 1, 1, 32, false, true>), 1, 16, B64, A, a.rows[6], false);
+    if (in(7)) BNN_MULTI((k_vec_x<8, false, 1, 1, 32, false, true>), 1, 16, A64, B, a.rows[7], false);
   } else {
-    BNN_MULTI((k_quad<ARITH, 1, 30, true, OUT2, 32, TWO, true>), 196, 2, A64, B, a.rows[1], false);
-    BNN_MULTI((k_quad<ARITH, 1, 14, false, OUT2, 32, TWO, true>), 36, 4, B64, A, a.rows[2], false);
-    BNN_MULTI((k_quad<ARITH, 2, 12, true, OUT2, 32, TWO, true>), 25, 4, A64, B, a.rows[3], false);
-    BNN_MULTI((k_vec<ARITH, 18, OUT2, true, 2, 5, 32, false, TWO, true>), 9, 8, B64, A, a.rows[4], false);
-    BNN_MULTI((k_vec<ARITH, 36, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 8, A64, B, a.rows[5], false);
-    BNN_MULTI((k_vec<ARITH, 4, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 16, B64, A, a.rows[6], false);
-    BNN_MULTI((k_vec<ARITH, 8, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 16, A64, B, a.rows[7], false);
+    if (in(1)) BNN_MULTI((k_quad<ARITH, 1, 30, true, OUT2, 32, TWO, true>), 196, 2, A64, B, a.rows[1], false);
+    if (in(2)) BNN_MULTI((k_quad<ARITH, 1, 14, false, OUT2, 32, TWO, true>), 36, 4, B64, A, a.rows[2], false);
+    if (in(3)) BNN_MULTI((k_quad<ARITH, 2, 12, true, OUT2, 32, TWO, true>), 25, 4, A64, B, a.rows[3], false);
+    if (in(4)) BNN_MULTI((k_vec<ARITH, 18, OUT2, true, 2, 5, 32, false, TWO, true>), 9, 8, B64, A, a.rows[4], false);
+    if (in(5)) BNN_MULTI((k_vec<ARITH, 36, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 8, A64, B, a.rows[5], false);
+    if (in(6)) BNN_MULTI((k_vec<ARITH, 4, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 16, B64, A, a.rows[6], false);
+    if (in(7)) BNN_MULTI((k_vec<ARITH, 8, OUT2, false, 1, 1, 32, false, TWO, true>), 1, 16, A64, B, a.rows[7], false);
   }
+  if (!in(8)) return;
   const MultiArgs ma{a.segs, (unsigned)(a.stride / 4), 1, a.n};
   dim3 g = grid_for(a.max_len, 1);
   g.y = (unsigned)a.nsegs;
@@ -2405,22 +2482,23 @@ hipError_t run_lfc_multi(NetId net, const MultiLaunch &a) {
   uint64_t *A64 = reinterpret_cast<uint64_t *>(a.buf0), *B64 = reinterpret_cast<uint64_t *>(a.buf1);
   uint32_t *W32 = reinterpret_cast<uint32_t *>(a.words);
   hipStream_t s = a.stream;
-  {
+  const auto in = [&](int l) { return a.first <= l && l <= a.last; };  // (layer l's stage is run; layer 0's binarises first)
+  if (in(0)) {
     const MultiArgs ma{a.segs, 0, 13, 0};
     dim3 g = grid_for((long long)a.max_len * 13, 1);
     g.y = (unsigned)a.nsegs;
     BNN_LAUNCH(k_lfc_binarize<true>, g, s, a.images, A64, a.total * 13, ma);
   }
   if (net == NET_LFCW1A1) {
-    BNN_MULTI((k_vec_x<13, false, 1, 1, 32, false, true>), 1, 32, A64, B, a.rows[0], false);
-    BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 32, B64, A, a.rows[1], false);
-    BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 32, A64, B, a.rows[2], false);
-    BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 2, B64, W32, a.rows[3], true);
+    if (in(0)) BNN_MULTI((k_vec_x<13, false, 1, 1, 32, false, true>), 1, 32, A64, B, a.rows[0], false);
+    if (in(1)) BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 32, B64, A, a.rows[1], false);
+    if (in(2)) BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 32, A64, B, a.rows[2], false);
+    if (in(3)) BNN_MULTI((k_vec_x<16, false, 1, 1, 32, false, true>), 1, 2, B64, W32, a.rows[3], true);
   } else if (net == NET_LFCW1A2) {
-    BNN_MULTI((k_vec<AR_XNOR, 13, true, false, 1, 1, 32, false, false, true>), 1, 32, A64, B, a.rows[0], false);
-    BNN_MULTI((k_vec<AR_TB, 16, true, false, 1, 1, 32, false, false, true>), 1, 32, B64, A, a.rows[1], false);
-    BNN_MULTI((k_vec<AR_TB, 16, true, false, 1, 1, 32, false, false, true>), 1, 32, A64, B, a.rows[2], false);
-    BNN_MULTI((k_vec<AR_TB, 16, false, false, 1, 1, 32, false, false, true>), 1, 2, B64, W32, a.rows[3], true);
+    if (in(0)) BNN_MULTI((k_vec<AR_XNOR, 13, true, false, 1, 1, 32, false, false, true>), 1, 32, A64, B, a.rows[0], false);
+    if (in(1)) BNN_MULTI((k_vec<AR_TB, 16, true, false, 1, 1, 32, false, false, true>), 1, 32, B64, A, a.rows[1], false);
+    if (in(2)) BNN_MULTI((k_vec<AR_TB, 16, true, false, 1, 1, 32, false, false, true>), 1, 32, A64, B, a.rows[2], false);
+    if (in(3)) BNN_MULTI((k_vec<AR_TB, 16, false, false, 1, 1, 32, false, false, true>), 1, 2, B64, W32, a.rows[3], true);
   } else {
     return hipErrorInvalidValue;
   }
@@ -2430,6 +2508,41 @@ hipError_t run_lfc_multi(NetId net, const MultiLaunch &a) {
 hipError_t scatter_patches(const uint8_t *staging, const PatchSpan *spans, int nspans, uint8_t *copies, hipStream_t s) {
   if (nspans <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_patch, dim3((unsigned)nspans), dim3(kBlock), 0, s, staging, spans, copies);
+  return hipGetLastError();
+}
+
+hipError_t sweep_broadcast(const uint8_t *src, size_t row_bytes, int rows, int runs, uint8_t *dst, size_t dst_run_stride,
+                           hipStream_t s) {
+  if (rows <= 0 || runs <= 0 || row_bytes == 0) return hipSuccess;
+  if (row_bytes % 4) return hipErrorInvalidValue;
+  const bool wide = row_bytes % 16 == 0 && dst_run_stride % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+  const long long per_run = (long long)rows * (long long)(row_bytes / (wide ? 16 : 4)), units = per_run * runs;
+  const dim3 g((unsigned)((units + kBlock - 1) / kBlock));
+  if (wide) hipLaunchKernelGGL(k_sweep_bcast<16>, g, dim3(kBlock), 0, s, src, dst, per_run, units, (unsigned long long)dst_run_stride);
+  else hipLaunchKernelGGL(k_sweep_bcast<4>, g, dim3(kBlock), 0, s, src, dst, per_run, units, (unsigned long long)dst_run_stride);
+  return hipGetLastError();
+}
+
+hipError_t sweep_mark(const uint8_t *act, const uint8_t *base, int row_bytes, const MultiSeg *segs, int nsegs, int max_len,
+                      uint8_t *alive, hipStream_t s) {
+  if (nsegs <= 0 || max_len <= 0) return hipSuccess;
+  if (nsegs > 65535 || row_bytes % 16) return hipErrorInvalidValue;
+  const dim3 g((unsigned)((max_len + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)nsegs);
+  hipLaunchKernelGGL(k_sweep_mark, g, dim3(kBlock), 0, s, act, base, row_bytes / 16, segs, alive);
+  return hipGetLastError();
+}
+
+hipError_t sweep_count(const int32_t *classes, const int32_t *base, int n, int win, int runs, int *counts, hipStream_t s) {
+  if (runs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sweep_classes<false>, dim3((unsigned)runs), dim3(kBlock), 0, s, classes, base, n, win, counts, nullptr, nullptr);
+  return hipGetLastError();
+}
+
+hipError_t sweep_emit(const int32_t *classes, const int32_t *base, int n, int win, int runs, const int *counts, const long long *offsets,
+                      int *out, hipStream_t s) {
+  if (runs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sweep_classes<true>, dim3((unsigned)runs), dim3(kBlock), 0, s, classes, base, n, win, const_cast<int *>(counts),
+                     offsets, out);
   return hipGetLastError();
 }
 

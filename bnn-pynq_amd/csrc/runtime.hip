@@ -33,6 +33,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
 #include <memory>
 #include <string>
@@ -61,6 +62,7 @@ namespace {
 
 constexpr int kMaxChunk = 131072;  // images per pass through the stages
 constexpr int kMaxRuns = 4096;      // campaigns per bnn_mi355x_fault_campaigns call (each holds a copy of the blob in HBM)
+constexpr long long kMaxSweepPairs = 16LL * kMaxChunk;  // (fault, image) pairs of one bnn_mi355x_fault_sweep run group
 constexpr int kForkMin = 16384;     // images: a device-pointer pass of a CNV net of this size and more forks over the two compute lanes
 constexpr int kStageSlots = 4;      // HBM staging buffers of the host paths: two on one compute lane, four on two
 // Events that only TIME device work: a device-scope release at the record point instead of a flush to system scope
@@ -239,6 +241,12 @@ struct Runtime {
   size_t copies_cap = 0, camp_cap = 0, camp_res_cap = 0;
   std::vector<Fault> camp_faults;  // the faults of the last such call, run-major; camp_run[i]: the run of camp_faults[i]
   std::vector<int> camp_run;
+  // bnn_mi355x_fault_sweep (the runs' blob copies: d_copies): the fault-free stage outputs and results of the call's images;
+  // a run group's patches (staging + spans), segment records, survivor flags, results, counts + offsets, {image, class} pairs
+  uint8_t *d_sw_base = nullptr, *d_sw_stage = nullptr, *d_sw_segs = nullptr, *d_sw_alive = nullptr, *d_sw_res = nullptr,
+          *d_sw_cnt = nullptr, *d_sw_diffs = nullptr;
+  size_t sw_base_cap = 0, sw_stage_cap = 0, sw_segs_cap = 0, sw_alive_cap = 0, sw_res_cap = 0, sw_cnt_cap = 0, sw_diffs_cap = 0;
+  std::vector<long> sweep_pairs;  // the last sweep: per layer, the (fault, image) pairs it had to run (bnn_mi355x_last_sweep_stages)
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -384,7 +392,8 @@ int upload_blob() {
 void free_workspace() {
   Runtime &r = rt();
   if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.file_cap && !r.all_cap && !r.h_io &&
-      !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap)
+      !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
+      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap)
     return;
   if (r.device >= 0) (void)hipSetDevice(r.device);
   (void)hipDeviceSynchronize();
@@ -411,6 +420,11 @@ void free_workspace() {
   (void)hipFree(r.d_copies); (void)hipFree(r.d_camp); (void)hipFree(r.d_camp_res);
   r.d_copies = r.d_camp = r.d_camp_res = nullptr;
   r.copies_cap = r.camp_cap = r.camp_res_cap = 0;
+  for (uint8_t **b : {&r.d_sw_base, &r.d_sw_stage, &r.d_sw_segs, &r.d_sw_alive, &r.d_sw_res, &r.d_sw_cnt, &r.d_sw_diffs}) {
+    (void)hipFree(*b);
+    *b = nullptr;
+  }
+  r.sw_base_cap = r.sw_stage_cap = r.sw_segs_cap = r.sw_alive_cap = r.sw_res_cap = r.sw_cnt_cap = r.sw_diffs_cap = 0;
   (void)hipFree(r.d_file[0]); (void)hipFree(r.d_file[1]);
   r.d_file[0] = r.d_file[1] = nullptr;
   r.h_file[0].reset(); r.h_file[1].reset();
@@ -2086,6 +2100,414 @@ int bnn_mi355x_last_campaign_faults(int *records, int cap_records) {
     for (int j = 0; j < 9; j++) records[i * 9 + j] = v[j];
   }
   return n;
+}
+
+long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long first, int *records, int cap_records) {
+  const NetSpec &net = rt().spec;
+  const long total = enumerate_faults(net, layer, target, word_size, 0, nullptr, 0);
+  if (total < 0 || first < 0) return fail("enumerate_faults: bad layer, target (0 weights, 1 thresholds), word_size (1 ... 64) or first");
+  if (records && cap_records > 0 && first < total) {
+    std::vector<Fault> v((size_t)std::min<long>(cap_records, total - first));
+    enumerate_faults(net, layer, target, word_size, first, v.data(), (long)v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      const Fault &f = v[i];
+      const int w[8] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
+      std::memcpy(records + i * 8, w, sizeof w);
+    }
+  }
+  return total;
+}
+
+long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
+                            long cap_diffs, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  r.sweep_pairs.clear();
+  if (n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs))
+    return fail("fault_sweep: bad arguments (records / changed missing, or cap_diffs without diffs)");
+#ifdef BNN_VARIANT
+  return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+#endif
+  if (!ready()) return -1;
+  if (r.raw.empty()) return fail("fault injection needs the parameter files (load_parameters), not an imported blob");
+  if (r.l1_mfma || r.l1_literal)
+    return fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the matrix-pipe table is not patched)");
+  const NetSpec &net = r.spec;
+  std::vector<Fault> faults((size_t)n_faults);
+  for (int i = 0; i < n_faults; i++) {
+    const int *v = records + (size_t)i * 8;
+    faults[(size_t)i] = Fault{0, v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    const std::string e = check_fault(net, faults[(size_t)i]);
+    if (!e.empty()) return fail("fault_sweep: record " + std::to_string(i) + ": " + e);
+  }
+  ImageFile f;
+  if (open_image_file(path, f)) return -1;
+  const int n = (int)f.n, S = net.nlayers;
+  const bool cnv = net.is_cnv;
+  std::vector<long> pairs((size_t)S, 0);
+  if (n_faults) std::fill(changed, changed + n_faults, 0);
+  long total_changed = 0;
+  double device_us = 0.0;
+  // the first cap_diffs diffs in (fault, image) order: per fault its {image, class} pairs; a fault's list is dropped
+  // once the lists of the faults before it hold cap_diffs pairs
+  std::map<int, std::vector<int>> kept;
+  long kept_n = 0;
+  auto keep = [&](int fi, const int *pv, long cnt) {
+    if (cap_diffs == 0 || cnt == 0) return;
+    std::vector<int> &d = kept[fi];
+    d.insert(d.end(), pv, pv + 2 * cnt);
+    kept_n += cnt;
+    while (!kept.empty() && kept_n - (long)(kept.rbegin()->second.size() / 2) >= cap_diffs) {
+      kept_n -= (long)(kept.rbegin()->second.size() / 2);
+      kept.erase(std::prev(kept.end()));
+    }
+  };
+  auto run = [&]() -> int {
+    if (n == 0 || n_faults == 0) return 0;
+    // -- geometry.  Layer l < S-1 leaves `ob[l]` bytes per image in buffer `obuf[l]` (stage_output_bytes); the fault-free
+    // outputs of all n images are kept at base + boff[l], the fault-free results (class / raw word, rb bytes) behind them.
+    std::vector<size_t> ob((size_t)S, 0), boff((size_t)S + 1, 0);
+    std::vector<int> obuf((size_t)S, 0);
+    const std::vector<int> ipi = cnv ? std::vector<int>{900, 196, 36, 25, 9, 1, 1, 1, 1} : std::vector<int>{1, 1, 1, 1};  // work items per image
+    const size_t rb = cnv ? sizeof(int32_t) : sizeof(uint64_t);
+    for (int l = 0; l < S; l++) {
+      if (l + 1 < S) ob[(size_t)l] = stage_output_bytes(cnv, net.abits, cnv ? l : l + 1, &obuf[(size_t)l]);
+      boff[(size_t)l + 1] = boff[(size_t)l] + (((l + 1 < S ? ob[(size_t)l] : rb) * (size_t)n + 255) & ~(size_t)255);
+    }
+    size_t b0, b1;
+    if (cnv) cnv_workspace_bytes(net.abits, &b0, &b1);
+    else lfc_workspace_bytes(net.abits, &b0, &b1);
+    const int wcap = (int)std::min<long long>(kMaxChunk, (long long)n_faults * n);  // images of activation workspace
+    // A run group with its faults in layer L holds the outputs of layers L-1 .. S-2 in the workspace at once, (run, image)
+    // slot by slot: its pairs are bounded by the bytes per image of those outputs, not by the layer-0 sizing of the
+    // workspace -- the FC layers take ~25x the pairs of the conv layers.
+    std::vector<int> G((size_t)S, 0), win((size_t)S, 0);
+    std::vector<std::vector<int>> by_layer((size_t)S);
+    for (int i = 0; i < n_faults; i++) by_layer[(size_t)faults[(size_t)i].layer].push_back(i);
+    long long max_pairs = 0;
+    int max_runs = 0;
+    for (int L = 0; L < S; L++) {
+      if (by_layer[(size_t)L].empty()) continue;
+      long long c = kMaxSweepPairs;
+      for (int l = std::max(L - 1, 0); l + 1 < S; l++)
+        c = std::min<long long>(c, (long long)((size_t)wcap * (obuf[(size_t)l] ? b1 : b0) / ob[(size_t)l]));
+      if (L == 0) c = std::min<long long>(c, wcap);  // (the first stage writes the layer-0 sizes)
+      const int g = (int)std::max<long long>(1, std::min<long long>({c / n, (long long)kMaxRuns, (long long)by_layer[(size_t)L].size()}));
+      G[(size_t)L] = g;
+      win[(size_t)L] = g > 1 ? n : (int)std::min<long long>(n, c);
+      max_pairs = std::max(max_pairs, (long long)g * win[(size_t)L]);
+      max_runs = std::max(max_runs, g);
+    }
+    // -- host: the working copy of the memories and the blob that patches are built on (restored after every fault)
+    RawParams raw = r.raw;
+    std::vector<uint8_t> blob = r.blob;
+    PackedHeader h;
+    std::memcpy(&h, blob.data(), sizeof(h));
+    const size_t stride = (blob.size() + 255) & ~(size_t)255;
+    const bool tab = h.l0_mfma_offset && r.l0_mfma;  // layer-0 faults patch the MFMA table too (kernels read it)
+    const int base_two = count_two_rows(net, r.blob);
+    auto two_flag = [&](int l, int row) -> int {
+      if (net.L[l].arith != AR_TT) return 0;
+      const uint32_t *rows = reinterpret_cast<const uint32_t *>(blob.data() + h.layer[l].offset);
+      return rows[(size_t)row * h.layer[l].row_dwords + 2 + 6 * h.layer[l].kw] != 0;
+    };
+    // -- device buffers
+    const size_t res_n = std::max<size_t>((size_t)max_pairs, (size_t)n);
+    if (load_file_resident(f, n) || reserve(wcap)) return -1;
+    if (grow(r.d_copies, r.copies_cap, (size_t)max_runs * stride) || grow(r.d_sw_base, r.sw_base_cap, boff[(size_t)S]) ||
+        grow(r.d_sw_segs, r.sw_segs_cap, (size_t)max_pairs * sizeof(MultiSeg)) || grow(r.d_sw_alive, r.sw_alive_cap, (size_t)max_pairs) ||
+        grow(r.d_sw_res, r.sw_res_cap, res_n * rb) || grow(r.d_sw_cnt, r.sw_cnt_cap, (size_t)max_runs * 12 + 512) ||
+        grow(r.d_sw_diffs, r.sw_diffs_cap, (size_t)max_pairs * 8))
+      return -1;
+    uint8_t *const bufs[2] = {static_cast<uint8_t *>(r.buf0), static_cast<uint8_t *>(r.buf1)};
+    uint8_t *const base_res = r.d_sw_base + boff[(size_t)S - 1];
+    int *const d_counts = reinterpret_cast<int *>(r.d_sw_cnt);
+    long long *const d_offsets = reinterpret_cast<long long *>(r.d_sw_cnt + (((size_t)max_runs * 4 + 255) & ~(size_t)255));
+    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
+    // host buffers the queued copies read or write (declared before `drain`)
+    std::vector<MultiSeg> segs, ran;
+    std::vector<uint8_t> alive, upload;
+    std::vector<int> counts, pv;
+    std::vector<long long> offs;
+    std::vector<uint64_t> words;
+    std::vector<int> base_cls((size_t)n);
+    DrainOnFailure drain;
+    if (settle_handover(r.stream)) return -1;
+    while (r.time_events.size() < 2) {
+      hipEvent_t e;
+      HIP_OK(hipEventCreateWithFlags(&e, kTimeEventFlags));
+      r.time_events.push_back(e);
+    }
+    // device time: the sum of the bursts of work between two host waits
+    bool open = false;
+    auto begin = [&]() -> int {
+      if (!open) HIP_OK(hipEventRecord(r.time_events[0], r.stream));
+      open = true;
+      return 0;
+    };
+    auto finish = [&]() -> int {
+      if (open) HIP_OK(hipEventRecord(r.time_events[1], r.stream));
+      HIP_OK(hipStreamSynchronize(r.stream));
+      if (open) {
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, r.time_events[0], r.time_events[1]));
+        device_us += ms * 1000.0;
+      }
+      open = false;
+      return 0;
+    };
+    // launches over `segs`: grouped by length class (grid.x follows a launch's longest record), at most 65 535 records each
+    struct Batch { size_t seg0; int nsegs, max_len, total; };
+    std::vector<Batch> batches;
+    std::vector<MultiSeg> sorted;
+    auto plan = [&]() -> int {
+      batches.clear();
+      size_t cnt[33] = {}, at[33] = {};
+      auto cls = [](int len) { return 32 - __builtin_clz((unsigned)len); };
+      for (const MultiSeg &sg : segs) cnt[cls(sg.len)]++;
+      for (int c = 1; c < 33; c++) at[c] = at[c - 1] + cnt[c - 1];
+      sorted.resize(segs.size());
+      for (const MultiSeg &sg : segs) sorted[at[cls(sg.len)]++] = sg;
+      segs.swap(sorted);
+      for (size_t i = 0; i < segs.size();) {
+        Batch b{i, 0, 0, 0};
+        const int c = cls(segs[i].len);
+        for (; i < segs.size() && cls(segs[i].len) == c && b.nsegs < 65535; i++) {
+          b.nsegs++;
+          b.total += segs[i].len;
+          b.max_len = std::max(b.max_len, segs[i].len);
+        }
+        batches.push_back(b);
+      }
+      HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
+      return 0;
+    };
+    auto stage = [&](int l, const uint8_t *copies, bool two) -> int {
+      for (const Batch &b : batches) {
+        MultiLaunch a{};
+        a.images = r.d_all;
+        a.segs = d_segs + b.seg0;
+        a.nsegs = b.nsegs; a.max_len = b.max_len; a.total = b.total; a.n = n;
+        a.buf0 = r.buf0; a.buf1 = r.buf1;
+        for (int k = 0; k < S; k++) a.rows[k] = reinterpret_cast<const uint32_t *>(copies + h.layer[k].offset);
+        a.l0_mfma = tab ? copies + h.l0_mfma_offset : nullptr;
+        a.stride = stride;
+        a.has_two = two;
+        a.classes = reinterpret_cast<int32_t *>(copies == r.d_blob ? base_res : r.d_sw_res);
+        a.words = reinterpret_cast<uint64_t *>(copies == r.d_blob ? base_res : r.d_sw_res);
+        a.number_class = number_class;
+        a.stream = r.stream;
+        a.first = a.last = l;
+        const hipError_t e = cnv ? run_cnv_multi(net.id, a) : run_lfc_multi(net.id, a);
+        if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      }
+      return 0;
+    };
+    // -- the fault-free pass, once: every layer's output and the results of all n images
+    const uint8_t *const clean = static_cast<const uint8_t *>(r.d_blob);
+    for (int i0 = 0; i0 < n; i0 += kMaxChunk) {
+      const int m = std::min(kMaxChunk, n - i0);
+      if (begin()) return -1;
+      segs.assign(1, MultiSeg{0, i0, 0, m});
+      if (plan()) return -1;
+      for (int l = 0; l < S; l++) {
+        if (stage(l, clean, base_two > 0)) return -1;
+        if (l + 1 < S)
+          HIP_OK(hipMemcpyAsync(r.d_sw_base + boff[(size_t)l] + (size_t)i0 * ob[(size_t)l], bufs[obuf[(size_t)l]], (size_t)m * ob[(size_t)l],
+                                hipMemcpyDeviceToDevice, r.stream));
+      }
+      if (finish()) return -1;
+    }
+    if (!cnv) {  // (LFC: the classes are decoded on the host, like the campaign path)
+      words.resize((size_t)n);
+      HIP_OK(hipMemcpy(words.data(), base_res, (size_t)n * 8, hipMemcpyDeviceToHost));
+      for (int i = 0; i < n; i++) base_cls[(size_t)i] = lfc_class_batched(words[(size_t)i], number_class);
+    }
+    // -- the runs' blob copies
+    if (begin()) return -1;
+    HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, blob.size(), hipMemcpyDeviceToDevice, r.stream));
+    for (size_t have = 1; have < (size_t)max_runs; have *= 2) {  // replicate by doubling
+      const size_t c = std::min(have, (size_t)max_runs - have);
+      HIP_OK(hipMemcpyAsync(r.d_copies + have * stride, r.d_copies, c * stride, hipMemcpyDeviceToDevice, r.stream));
+    }
+    // -- run groups: g faults of one layer L, one per copy; window by window of the images
+    for (int L = 0; L < S; L++) {
+      const std::vector<int> &idx = by_layer[(size_t)L];
+      for (size_t c0 = 0; c0 < idx.size(); c0 += (size_t)G[(size_t)L]) {
+        const int g = (int)std::min<size_t>((size_t)G[(size_t)L], idx.size() - c0);
+        // host: each fault's patch (the rebuilt row; layer 0: and the MFMA table) and the original bytes it replaces
+        std::vector<uint8_t> staging;
+        std::vector<PatchSpan> patch, undo;
+        bool two = base_two > 0;
+        auto add_span = [&](int q, size_t off, size_t bytes) {
+          patch.push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
+          staging.insert(staging.end(), blob.begin() + off, blob.begin() + off + bytes);
+          undo.push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
+          staging.insert(staging.end(), r.blob.begin() + off, r.blob.begin() + off + bytes);
+        };
+        for (int q = 0; q < g; q++) {
+          const Fault &flt = faults[(size_t)idx[c0 + (size_t)q]];
+          uint64_t *w = fault_word(net, raw, flt);
+          const uint64_t old = *w;
+          const int row = apply_fault(net, raw, flt);
+          const int before = two_flag(L, row);
+          size_t off = 0, bytes = 0;
+          repack_row(net, raw, L, row, blob, &off, &bytes);
+          if (base_two + two_flag(L, row) - before > 0) two = true;
+          if (L == 0 && h.l0_mfma_offset) {  // repack_row's span runs from the row to the table's end: the two parts
+            const size_t rbytes = (size_t)h.layer[0].row_dwords * 4;
+            add_span(q, h.layer[0].offset + (size_t)row * rbytes, rbytes);
+            if (tab) add_span(q, h.l0_mfma_offset, kL0MfmaBytes);
+          } else {
+            add_span(q, off, bytes);
+          }
+          *w = old;
+          repack_row(net, raw, L, row, blob, &off, &bytes);
+        }
+        const size_t spans_off = (staging.size() + 255) & ~(size_t)255;
+        upload.assign(spans_off + (patch.size() + undo.size()) * sizeof(PatchSpan), 0);
+        std::memcpy(upload.data(), staging.data(), staging.size());
+        std::memcpy(upload.data() + spans_off, patch.data(), patch.size() * sizeof(PatchSpan));
+        std::memcpy(upload.data() + spans_off + patch.size() * sizeof(PatchSpan), undo.data(), undo.size() * sizeof(PatchSpan));
+        if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+        HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
+        const PatchSpan *d_spans = reinterpret_cast<const PatchSpan *>(r.d_sw_stage + spans_off);
+        hipError_t e = scatter_patches(r.d_sw_stage, d_spans, (int)patch.size(), r.d_copies, r.stream);
+        if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+        const int wl = win[(size_t)L];
+        for (int i0 = 0; i0 < n; i0 += wl) {
+          const int m = std::min(wl, n - i0);  // (g > 1: m = n)
+          if (begin()) return -1;
+          // the runs start from the fault-free output of layer L-1 (slot q * m + j) and the fault-free results
+          if (L > 0) {
+            const size_t bb = ob[(size_t)L - 1];
+            e = sweep_broadcast(r.d_sw_base + boff[(size_t)L - 1] + (size_t)i0 * bb, bb, m, g, bufs[obuf[(size_t)L - 1]], (size_t)m * bb, r.stream);
+            if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+          }
+          e = sweep_broadcast(base_res + (size_t)i0 * rb, rb, m, g, r.d_sw_res + (size_t)i0 * rb, (size_t)n * rb, r.stream);
+          if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+          segs.clear();
+          for (int q = 0; q < g; q++) segs.push_back(MultiSeg{q, i0, q * m, m});
+          for (int l = L; l < S; l++) {
+            if (plan() || stage(l, r.d_copies, two)) return -1;
+            if (l == L) pairs[(size_t)l] += (long)g * m;
+            if (l + 1 == S) break;
+            // prune: only the (run, image) pairs whose output differs from the fault-free one go on (and the gaps between them below `bridge`)
+            HIP_OK(hipMemsetAsync(r.d_sw_alive, 0, (size_t)g * m, r.stream));
+            for (const Batch &b : batches) {
+              e = sweep_mark(bufs[obuf[(size_t)l]], r.d_sw_base + boff[(size_t)l], (int)ob[(size_t)l], d_segs + b.seg0, b.nsegs, b.max_len,
+                             r.d_sw_alive, r.stream);
+              if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+            }
+            alive.resize((size_t)g * m);
+            HIP_OK(hipMemcpyAsync(alive.data(), r.d_sw_alive, alive.size(), hipMemcpyDeviceToHost, r.stream));
+            if (finish()) return -1;
+            // the survivors as segments, cut from the records that just ran; a gap shorter than the next stage's smallest
+            // grid per record (8 blocks of work items, map_block) is run through rather than cut: a pair that ran this
+            // stage with the fault-free output gives the fault-free outputs again, and a record costs that grid however
+            // short it is.  (Never across records: a pair dropped earlier holds stale activations.)
+            const int bridge = std::max(1, 8 * 256 / ipi[(size_t)l + 1]);
+            ran.swap(segs);
+            segs.clear();
+            for (const MultiSeg &sg : ran) {
+              const uint8_t *al = alive.data() + sg.slot;
+              int b = -1, e2 = -1;  // the open segment [b, e2) of this record
+              for (int j = 0; j < sg.len;) {
+                uint64_t z;
+                if (j + 8 <= sg.len && (std::memcpy(&z, al + j, 8), z == 0)) { j += 8; continue; }
+                if (!al[j]) { j++; continue; }
+                if (b >= 0 && j - e2 >= bridge) {
+                  segs.push_back(MultiSeg{sg.run, sg.image + b, sg.slot + b, e2 - b});
+                  b = -1;
+                }
+                if (b < 0) b = j;
+                const int a0 = j;
+                while (j < sg.len && al[j]) j++;
+                pairs[(size_t)l + 1] += j - a0;
+                e2 = j;
+              }
+              if (b >= 0) segs.push_back(MultiSeg{sg.run, sg.image + b, sg.slot + b, e2 - b});
+            }
+            if (segs.empty()) break;
+            if (begin()) return -1;
+          }
+          // classes against the fault-free ones (pairs pruned at any layer kept the fault-free result)
+          if (begin()) return -1;
+          if (cnv) {
+            const int32_t *cls = reinterpret_cast<const int32_t *>(r.d_sw_res) + i0, *bcls = reinterpret_cast<const int32_t *>(base_res) + i0;
+            e = sweep_count(cls, bcls, n, m, g, d_counts, r.stream);
+            if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+            counts.resize((size_t)g);
+            HIP_OK(hipMemcpyAsync(counts.data(), d_counts, (size_t)g * 4, hipMemcpyDeviceToHost, r.stream));
+            if (finish()) return -1;
+            offs.assign((size_t)g, 0);
+            long long tot = 0;
+            for (int q = 0; q < g; q++) {
+              offs[(size_t)q] = tot;
+              tot += counts[(size_t)q];
+            }
+            pv.resize((size_t)tot * 2);
+            if (tot > 0 && cap_diffs > 0) {
+              if (begin()) return -1;
+              HIP_OK(hipMemcpyAsync(d_offsets, offs.data(), (size_t)g * 8, hipMemcpyHostToDevice, r.stream));
+              e = sweep_emit(cls, bcls, n, m, g, d_counts, d_offsets, reinterpret_cast<int *>(r.d_sw_diffs), r.stream);
+              if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+              HIP_OK(hipMemcpyAsync(pv.data(), r.d_sw_diffs, (size_t)tot * 8, hipMemcpyDeviceToHost, r.stream));
+              if (finish()) return -1;
+              for (size_t k = 0; k < (size_t)tot; k++) pv[2 * k] += i0;
+            }
+            for (int q = 0; q < g; q++) {
+              const int fi = idx[c0 + (size_t)q];
+              changed[fi] += counts[(size_t)q];
+              total_changed += counts[(size_t)q];
+              keep(fi, pv.data() + 2 * offs[(size_t)q], counts[(size_t)q]);
+            }
+          } else {  // (LFC: the raw words back, decoded on the host)
+            const size_t span = (size_t)(g - 1) * n + m;
+            words.resize(span);
+            HIP_OK(hipMemcpyAsync(words.data(), r.d_sw_res + (size_t)i0 * 8, span * 8, hipMemcpyDeviceToHost, r.stream));
+            if (finish()) return -1;
+            for (int q = 0; q < g; q++) {
+              const int fi = idx[c0 + (size_t)q];
+              pv.clear();
+              for (int j = 0; j < m; j++) {
+                const int c = lfc_class_batched(words[(size_t)q * n + j], number_class);
+                if (c != base_cls[(size_t)i0 + j]) { pv.push_back(i0 + j); pv.push_back(c); }
+              }
+              const long cnt = (long)pv.size() / 2;
+              changed[fi] += (int)cnt;
+              total_changed += cnt;
+              keep(fi, pv.data(), cnt);
+            }
+          }
+        }
+        // the copies back to the loaded parameters
+        if (begin()) return -1;
+        e = scatter_patches(r.d_sw_stage, d_spans + patch.size(), (int)undo.size(), r.d_copies, r.stream);
+        if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      }
+    }
+    if (finish()) return -1;
+    drain.ok();
+    return 0;
+  };
+  if (run() < 0) return -1;
+  long k = 0;
+  for (auto &e : kept)
+    for (size_t i = 0; i + 1 < e.second.size() && k < cap_diffs; i += 2, k++) {
+      diffs[3 * k] = e.first;
+      diffs[3 * k + 1] = e.second[i];
+      diffs[3 * k + 2] = e.second[i + 1];
+    }
+  r.sweep_pairs = std::move(pairs);
+  if (image_number) *image_number = n;
+  if (usecPerImage) *usecPerImage = (n > 0 && n_faults > 0) ? (float)(device_us / ((double)n_faults * n)) : 0.f;
+  return total_changed;
+}
+
+int bnn_mi355x_last_sweep_stages(long *pairs_per_stage, int cap) {
+  const std::vector<long> &p = rt().sweep_pairs;
+  for (int i = 0; pairs_per_stage && i < cap && i < (int)p.size(); i++) pairs_per_stage[i] = p[(size_t)i];
+  return (int)p.size();
 }
 
 void free_results(int *result) { delete[] result; }

@@ -203,6 +203,32 @@ int bnn_mi355x_last_campaign_faults(int *records, int cap_records);
 int bnn_mi355x_plan_faults(unsigned long long seed, int num_images, unsigned int flip_count, int word_size, int target,
                            const int *target_layers, unsigned int num_targets, int *records, int cap_records);
 size_t bnn_mi355x_pack_params_faulty(const char *path, const int *records, int n_faults, void *dst, size_t cap);
+/* Exhaustive single-fault sweeps: which bits matter.
+ * enumerate_faults: every distinct fault of one layer -- target 0 weights / 1 thresholds, word_size 1..64.
+ * "Distinct" = the positions plan_faults can draw, with bit aligned down to a multiple of word_size the way
+ * apply_fault does (so no two records have the same effect), ordered by (mem, ind, thresh, bit).  Writes records
+ * [first, first + cap_records) in the 8-int format of bnn_mi355x_plan_faults (image = 0); returns the total count
+ * (records may be NULL; 0 for the thresholds of a layer without any), -1 + last_error on a bad layer / target /
+ * word_size.  Host only.
+ * fault_sweep: for each of the n_faults records (8 ints; the image field is ignored: the fault is present for every
+ * image) classify every image of `path` with the loaded parameters plus that one fault, independently of the other
+ * records.  changed[f] = images whose class differs from the fault-free class.  diffs (optional): triples {fault,
+ * image, class} of every changed image in (fault, image) order, at most cap_diffs of them.  Returns the total number
+ * of changed (fault, image) pairs (which may exceed cap_diffs), or -1 + last_error.  The loaded parameters,
+ * last_faults and last_campaign_faults are unchanged.  Refuses what bnn_mi355x_fault_campaigns refuses (hardened
+ * variants, an imported blob, the BNN_MI355X_L1 forms) and records outside their layer's memories, before anything
+ * runs on the device.  usecPerImage: device time / (n_faults * n).
+ * The fault-free pass runs once and keeps every layer's output; a fault in layer L starts from the fault-free output
+ * of layer L-1, and after every layer a (fault, image) pair whose activations equal the fault-free ones is dropped:
+ * it keeps the fault-free class.
+ * last_sweep_stages: of the last sweep, per layer s the number of (fault, image) pairs layer s has to run: all pairs
+ * of the faults in layer s, and those of faults in earlier layers whose activations still differ from the fault-free
+ * ones there (the stage runs a few more where cutting a record short would cost more); returns the number of layers
+ * (0 before the first sweep). */
+long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long first, int *records, int cap_records);
+long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
+                            long cap_diffs, int *image_number, float *usecPerImage);
+int bnn_mi355x_last_sweep_stages(long *pairs_per_stage, int cap);
 
 /* The step before the path: CnvClassifier.image_to_cifar (bnn/bnn.py:226-242) on the
  * device.  The reference shrinks a picture with PIL's Image.thumbnail((32, 32), ANTIALIAS) -- Lanczos-3,

@@ -20,7 +20,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_profile_read", "bnn_mi355x_stage_name", "bnn_mi355x_thumbnail_size", "bnn_mi355x_images_to_cifar",
        "bnn_mi355x_params_bytes", "bnn_mi355x_import_params_device", "bnn_mi355x_params_crc", "bnn_mi355x_chunk_plan",
        "bnn_mi355x_binarize_pack", "bnn_mi355x_fault_campaigns", "bnn_mi355x_last_campaign_faults",
-       "bnn_mi355x_enumerate_faults", "bnn_mi355x_fault_sweep", "bnn_mi355x_last_sweep_stages"]
+       "bnn_mi355x_enumerate_faults", "bnn_mi355x_fault_sweep", "bnn_mi355x_last_sweep_stages",
+       "bnn_mi355x_enumerate_act_faults", "bnn_mi355x_act_fault_sweep", "bnn_mi355x_last_act_sweep_stages"]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -80,6 +81,11 @@ def declare_extensions(L):
     L.bnn_mi355x_fault_sweep.argtypes = [C.c_char_p, C.c_int, ip, C.c_int, ip, ip, C.c_long, ip, fp]
     L.bnn_mi355x_fault_sweep.restype = C.c_long
     L.bnn_mi355x_last_sweep_stages.argtypes = [C.POINTER(C.c_long), C.c_int]
+    L.bnn_mi355x_enumerate_act_faults.argtypes = [C.c_int, C.c_long, ip, C.c_int]
+    L.bnn_mi355x_enumerate_act_faults.restype = C.c_long
+    L.bnn_mi355x_act_fault_sweep.argtypes = [C.c_char_p, C.c_int, ip, C.c_int, ip, ip, C.c_long, ip, fp]
+    L.bnn_mi355x_act_fault_sweep.restype = C.c_long
+    L.bnn_mi355x_last_act_sweep_stages.argtypes = [C.POINTER(C.c_long), C.c_int]
     L.bnn_mi355x_pack_params_faulty.argtypes = [C.c_char_p, ip, C.c_int, C.c_void_p, C.c_size_t]
     L.bnn_mi355x_pack_params_faulty.restype = C.c_size_t
     L.bnn_mi355x_debug_stage_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]

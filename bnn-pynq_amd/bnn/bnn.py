@@ -256,6 +256,48 @@ class PynqBNN:
                 usec.value * nf * size.value, nf, size.value, usec.value))
         return changed[:nf], diffs[:min(cap, total)]
 
+    # extension: activation-fault sweeps (which datapath bits matter)
+    def enumerate_act_faults(self, layer):
+        """-> int32 array (k, 5): every site x shift of layer `layer`'s output map (any layer but the last) as records
+        {layer, y, x, channel, shift}, ordered by (y, x, channel, shift); HWC order of the oracle's layer outputs."""
+        lib = self.interface
+        k = lib.bnn_mi355x_enumerate_act_faults(layer, 0, None, 0)
+        if k < 0:
+            raise ValueError(lib.bnn_mi355x_last_error().decode())
+        recs = np.zeros((k, 5), np.int32)
+        for first in range(0, k, 1 << 20):  # (cap_records is an int)
+            m = min(1 << 20, k - first)
+            lib.bnn_mi355x_enumerate_act_faults(layer, first, recs[first:].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), m)
+        return recs
+
+    def act_fault_sweep(self, path, records, max_diffs=None):
+        """Every record {layer, y, x, channel, shift} alone for every image of `path`: that activation of the layer's
+        output moved `shift` levels on (mod the levels) while the image is classified.  -> (changed, diffs) as
+        fault_sweep returns them.  The loaded parameters are not changed.  usecPerImage: device time / (records *
+        images)."""
+        lib = self.interface
+        recs = np.ascontiguousarray(records, np.int32).reshape(-1, 5)
+        nf = recs.shape[0]
+        changed = np.zeros(max(nf, 1), np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        cap = (1 << 22) if max_diffs is None else int(max_diffs)
+        while True:
+            diffs = np.zeros((max(cap, 1), 3), np.int32)
+            total = lib.bnn_mi355x_act_fault_sweep(path.encode(), len(self.classes), recs.ctypes.data_as(ip), nf,
+                                                   changed.ctypes.data_as(ip), diffs.ctypes.data_as(ip), cap, ctypes.byref(size),
+                                                   ctypes.byref(usec))
+            if total < 0:
+                raise RuntimeError("activation fault sweep failed: " + lib.bnn_mi355x_last_error().decode())
+            if max_diffs is not None or total <= cap:
+                break
+            cap = total  # (all of them asked for, more than guessed: once more with room for every one)
+        self.usecPerImage = usec.value
+        if nf and size.value:
+            print("Activation fault sweep took %.2f microseconds for %d sites x %d images, %.4f usec per image" % (
+                usec.value * nf * size.value, nf, size.value, usec.value))
+        return changed[:nf], diffs[:min(cap, total)]
+
     def inference_multiple_detail(self, path):
         size = ctypes.c_int(0)
         usec = ctypes.c_float(0)
@@ -427,6 +469,14 @@ class CnvClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
+    def classify_images_act_fault_sweep(self, imgs, records, max_diffs=None):
+        return self._with_tmp(imgs, lambda p: self.bnn.act_fault_sweep(p, records, max_diffs))
+
+    def classify_cifars_act_fault_sweep(self, path, records, max_diffs=None):
+        result = self.bnn.act_fault_sweep(path, records, max_diffs)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
     def classify_images_details(self, imgs):
         return self._with_tmp(imgs, self.bnn.inference_multiple_detail)
 
@@ -489,6 +539,11 @@ class LfcClassifier:
 
     def classify_mnists_fault_sweep(self, mnist_format_file, records, max_diffs=None):
         result = self.bnn.fault_sweep(mnist_format_file, records, max_diffs)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_mnists_act_fault_sweep(self, mnist_format_file, records, max_diffs=None):
+        result = self.bnn.act_fault_sweep(mnist_format_file, records, max_diffs)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

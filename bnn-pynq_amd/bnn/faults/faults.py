@@ -16,6 +16,9 @@ with the same ``seed`` (run i seeded with seed + i) both paths return identical 
 sample: which bits matter.  Every distinct single fault of the chosen layers is evaluated alone on the whole input
 set (``PynqBNN.fault_sweep``: the fault-free pass once, each fault from its own layer on, (fault, image) pairs
 dropped as soon as their activations equal the fault-free ones).
+
+``FaultTest.activation_sensitivity`` / ``NetworkTest.activation_sensitivity_map`` ask the same of the datapath: every
+single activation of a layer's output, moved to another level while one image passes (``PynqBNN.act_fault_sweep``).
 """
 import numpy as np
 
@@ -122,18 +125,50 @@ class FaultTest:
         n = len(labels)
         right = clean[:n] == labels
         changed, diffs = self._classify(classifier, "_fault_sweep", records)
+        accuracy = self._accuracies(len(records), diffs, labels, right)
+        print("{}-{}: {} single faults in layer(s) {} swept, {} change some image".format(
+            self.network, self.dataset, len(records), list(layers), int((changed > 0).sum())))
+        return records, changed, accuracy
+
+    def _accuracies(self, k, diffs, labels, right):
+        """accuracy in percent of each of k faults from its sparse differences; sets self.control_accuracy"""
+        n = len(labels)
         # per fault: the fault-free count of right answers, minus those a changed class breaks, plus those it mends
-        delta = np.zeros(len(records), np.int64)
+        delta = np.zeros(k, np.int64)
         img, cls = diffs[:, 1], diffs[:, 2].astype(np.int64)
         ok = img < n
         now = np.zeros(len(diffs), np.int64)
         now[ok] = (cls[ok] == labels[img[ok]]).astype(np.int64) - right[img[ok]].astype(np.int64)
         np.add.at(delta, diffs[:, 0], now)
         self.control_accuracy = 100.0 * right.sum() / n if n else 0.0
-        accuracy = 100.0 * (right.sum() + delta) / n if n else np.zeros(len(records))
-        print("{}-{}: {} single faults in layer(s) {} swept, {} change some image".format(
+        return 100.0 * (right.sum() + delta) / n if n else np.zeros(k)
+
+    def activation_sensitivity(self, layers):
+        """Every single activation fault of the outputs of `layers` (any layer but the last): each site x shift alone on
+        the whole input set.  -> {layer: dict} with "records" int32 [k, 5] {layer, y, x, channel, shift}, "changed" [k]
+        (images whose class the fault changes), "accuracy" [k] in percent, and the same two reshaped to the layer's map,
+        "changed map" / "accuracy map" of shape (H, W, C) for 1-bit activations, (H, W, C, 2) for 2-bit ones (the
+        shifts).  The fault-free accuracy is `self.control_accuracy`."""
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        per = [classifier.bnn.enumerate_act_faults(l) for l in layers]
+        records = np.concatenate(per) if per else np.zeros((0, 5), np.int32)
+        clean = np.asarray(self._classify(classifier, ""), np.int64)
+        labels = np.asarray(list(self.labels), np.int64)
+        right = clean[:len(labels)] == labels
+        changed, diffs = self._classify(classifier, "_act_fault_sweep", records)
+        accuracy = self._accuracies(len(records), diffs, labels, right)
+        out, at = {}, 0
+        for layer, rec in zip(layers, per):
+            k = len(rec)
+            h, w, c = (int(rec[:, i].max()) + 1 for i in (1, 2, 3))
+            shifts = int(rec[:, 4].max())
+            shape = (h, w, c) if shifts == 1 else (h, w, c, shifts)
+            out[layer] = {"records": rec, "changed": changed[at:at + k], "accuracy": accuracy[at:at + k],
+                          "changed map": changed[at:at + k].reshape(shape), "accuracy map": accuracy[at:at + k].reshape(shape)}
+            at += k
+        print("{}-{}: {} activation faults in layer(s) {} swept, {} change some image".format(
             self.network, self.dataset, len(records), list(layers), int((changed > 0).sum())))
-        return records, changed, accuracy
+        return out
 
 
 class CNVFaultTest(FaultTest):
@@ -275,6 +310,34 @@ class NetworkTest:
                     "mean accuracy": float(accuracy.mean()) if k else summary["control"],
                     "min accuracy": float(accuracy.min()) if k else summary["control"]}
             util.write_dict_to_file("{}/{}_layer{}_summary.json".format(folder, self.fault_test.network, layer), summary)
+
+    def activation_sensitivity_map(self, output_folder, layers):
+        """Activation-fault sweeps (FaultTest.activation_sensitivity), next to sensitivity_map's files: per layer one
+        file output_folder/<network>/<dataset>/sensitivity/<network>_layer<L>_activations.json with the layer's totals
+        (sites, faults, mean / max changed images, fraction of faults that change any image, mean / min accuracy, the
+        fault-free accuracy) and its vulnerability -- the fraction of images a fault changes, averaged over the shifts --
+        per channel (over the pixels) and per pixel (over the channels, an H x W grid), plus every fault's changed
+        count in record order."""
+        folder = "{}/{}/{}/sensitivity/".format(output_folder, self.fault_test.network, self.fault_test.dataset)
+        res = self.fault_test.activation_sensitivity(list(layers))
+        n = max(len(list(self.fault_test.labels)), 1)
+        for layer, r in res.items():
+            cm = r["changed map"].astype(np.float64)
+            vul = (cm if cm.ndim == 3 else cm.mean(axis=3)) / n  # (H, W, C)
+            k = len(r["records"])
+            util.write_dict_to_file("{}/{}_layer{}_activations.json".format(folder, self.fault_test.network, layer), {
+                "network": self.fault_test.network, "dataset": self.fault_test.dataset, "layer": layer,
+                "control": self.fault_test.control_accuracy, "map": list(vul.shape), "shifts": 1 if cm.ndim == 3 else cm.shape[3],
+                "totals": {"sites": int(vul.size), "faults": k,
+                           "mean changed": float(r["changed"].mean()) if k else 0.0,
+                           "max changed": int(r["changed"].max()) if k else 0,
+                           "fraction changing any image": float((r["changed"] > 0).mean()) if k else 0.0,
+                           "mean accuracy": float(r["accuracy"].mean()) if k else self.fault_test.control_accuracy,
+                           "min accuracy": float(r["accuracy"].min()) if k else self.fault_test.control_accuracy},
+                "per channel vulnerability": vul.mean(axis=(0, 1)).tolist(),
+                "per pixel vulnerability": vul.mean(axis=2).tolist(),
+                "fields": ["layer", "y", "x", "channel", "shift", "changed"],
+                "changed": [int(c) for c in r["changed"]]})
 
     def comprehensive_test(self, output_folder, num_runs, flip_counts, target_layers=()):
         """all six combinations of {any, weight, threshold} x {bit, 8-bit word}.  (The reference's version

@@ -123,4 +123,13 @@ hipError_t sweep_count(const int32_t *classes, const int32_t *base, int n, int w
 hipError_t sweep_emit(const int32_t *classes, const int32_t *base, int n, int win, int runs, const int *counts, const long long *offsets,
                       int *out, hipStream_t s);
 
+// Activation-fault sweeps (bnn_mi355x_act_fault_sweep).  The site of run q: in the 16-byte unit `unit` of an output
+// row, activation bit `bit` (0..127 of the unit's four dwords: 1-bit maps; 0..63 of the (sign, non-zero) u64 pair:
+// 2-bit maps) -- its level index i becomes (i + shift) mod levels.
+struct ActPatch { uint32_t unit, bit, shift, pad; };
+// For every record: act + (slot + j) * row_bytes <- base + (image + j) * row_bytes with run `run`'s site changed,
+// j < len (all records of a launch as long as max_len or shorter; row_bytes a multiple of 16).
+hipError_t act_seed(const uint8_t *base, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len, const ActPatch *patches,
+                    uint8_t *act, hipStream_t s);
+
 }  // namespace bnn

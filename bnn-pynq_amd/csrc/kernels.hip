@@ -2061,6 +2061,41 @@ __global__ __launch_bounds__(kBlock) void k_sweep_classes(const int32_t *__restr
   }
 }
 
+// Activation-fault sweeps (bnn_mi355x_act_fault_sweep).  k_act_seed: for every record, the fault-free output rows of
+// its images into its slots with the run's site changed -- a lane per 16 bytes (memory-bound, as k_sweep_bcast), the
+// site's unit patched in registers.  1-bit maps: bit c of a dword is channel c (the stage kernels shift neurons in
+// 31 -> 0), flipped.  2-bit maps: the unit is the (sign, non-zero) u64 pair of 64 channels; level index i (-1, 0, +1)
+// becomes (i + shift) mod 3 in the form the stage kernels write (0: neither bit set).
+template <bool TWO_BIT>
+__global__ __launch_bounds__(kBlock) void k_act_seed(const uint8_t *__restrict__ base, uint8_t *__restrict__ act, int row_units,
+                                                     const MultiSeg *__restrict__ segs, const ActPatch *__restrict__ patches, int per_seg,
+                                                     long long units) {
+  const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= units) return;
+  const long long q = t / per_seg;
+  const int r = (int)(t - q * per_seg), j = r / row_units, u = r - j * row_units;
+  const MultiSeg sg = segs[q];
+  if (j >= sg.len) return;
+  uint4 v = reinterpret_cast<const uint4 *>(base)[(size_t)(sg.image + j) * row_units + u];
+  const ActPatch p = patches[sg.run];
+  if (u == (int)p.unit) {
+    const uint32_t m = 1u << (p.bit & 31), h = p.bit >> 5;
+    if constexpr (!TWO_BIT) {
+      v.x ^= h == 0 ? m : 0u;
+      v.y ^= h == 1 ? m : 0u;
+      v.z ^= h == 2 ? m : 0u;
+      v.w ^= h == 3 ? m : 0u;
+    } else {
+      uint32_t sgn = h ? v.y : v.x, nz = h ? v.w : v.z;
+      const uint32_t i = (sgn & m) ? 0u : ((nz & m) ? 2u : 1u), k = (i + p.shift) % 3u;
+      sgn = k == 0 ? (sgn | m) : (sgn & ~m);
+      nz = k != 1 ? (nz | m) : (nz & ~m);
+      if (h) { v.y = sgn; v.w = nz; } else { v.x = sgn; v.z = nz; }
+    }
+  }
+  reinterpret_cast<uint4 *>(act)[(size_t)(sg.slot + j) * row_units + u] = v;
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -2543,6 +2578,17 @@ hipError_t sweep_emit(const int32_t *classes, const int32_t *base, int n, int wi
   if (runs <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_sweep_classes<true>, dim3((unsigned)runs), dim3(kBlock), 0, s, classes, base, n, win, const_cast<int *>(counts),
                      offsets, out);
+  return hipGetLastError();
+}
+
+hipError_t act_seed(const uint8_t *base, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len, const ActPatch *patches,
+                    uint8_t *act, hipStream_t s) {
+  if (nsegs <= 0 || max_len <= 0) return hipSuccess;
+  const long long per_seg = (long long)max_len * (row_bytes / 16), units = per_seg * nsegs;
+  if (row_bytes <= 0 || row_bytes % 16 || (uintptr_t)base % 16 || (uintptr_t)act % 16 || per_seg > 0x7fffffff) return hipErrorInvalidValue;
+  const dim3 g((unsigned)((units + kBlock - 1) / kBlock));
+  if (two_bit) hipLaunchKernelGGL(k_act_seed<true>, g, dim3(kBlock), 0, s, base, act, row_bytes / 16, segs, patches, (int)per_seg, units);
+  else hipLaunchKernelGGL(k_act_seed<false>, g, dim3(kBlock), 0, s, base, act, row_bytes / 16, segs, patches, (int)per_seg, units);
   return hipGetLastError();
 }
 

@@ -43,6 +43,7 @@
 
 #include "../../include/bnn_mi355x.h"
 #include "faults.h"
+#include "act_faults.h"
 #include "kernels.h"
 #include "preprocess.h"
 #include "resample.h"
@@ -247,6 +248,7 @@ struct Runtime {
           *d_sw_cnt = nullptr, *d_sw_diffs = nullptr;
   size_t sw_base_cap = 0, sw_stage_cap = 0, sw_segs_cap = 0, sw_alive_cap = 0, sw_res_cap = 0, sw_cnt_cap = 0, sw_diffs_cap = 0;
   std::vector<long> sweep_pairs;  // the last sweep: per layer, the (fault, image) pairs it had to run (bnn_mi355x_last_sweep_stages)
+  std::vector<long> act_sweep_pairs;  // the same of the last activation-fault sweep (bnn_mi355x_last_act_sweep_stages)
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -2118,27 +2120,20 @@ long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long firs
   return total;
 }
 
-long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
-                            long cap_diffs, int *image_number, float *usecPerImage) {
+// The body both single-fault sweeps share, behind their entry points' checks: bnn_mi355x_fault_sweep (parameter faults,
+// `faults`) and bnn_mi355x_act_fault_sweep (activation sites, `sites`); the other one is null.  A group of records in
+// layer L starts at stage s0: a parameter fault at L itself, from blob copies patched for the group and the broadcast
+// fault-free output of layer L-1; an activation site at L+1, from the loaded blob (copy stride 0) and k_act_seed's rows.
+// The per-layer pair counts go to `stage_pairs` on success.
+static long single_fault_sweep(const char *path, int number_class, const std::vector<Fault> *faults, const std::vector<ActSite> *sites,
+                               int *changed, int *diffs, long cap_diffs, int *image_number, float *usecPerImage,
+                               std::vector<long> &stage_pairs) {
   Runtime &r = rt();
-  r.sweep_pairs.clear();
-  if (n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs))
-    return fail("fault_sweep: bad arguments (records / changed missing, or cap_diffs without diffs)");
-#ifdef BNN_VARIANT
-  return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
-#endif
-  if (!ready()) return -1;
-  if (r.raw.empty()) return fail("fault injection needs the parameter files (load_parameters), not an imported blob");
-  if (r.l1_mfma || r.l1_literal)
-    return fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the matrix-pipe table is not patched)");
   const NetSpec &net = r.spec;
-  std::vector<Fault> faults((size_t)n_faults);
-  for (int i = 0; i < n_faults; i++) {
-    const int *v = records + (size_t)i * 8;
-    faults[(size_t)i] = Fault{0, v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
-    const std::string e = check_fault(net, faults[(size_t)i]);
-    if (!e.empty()) return fail("fault_sweep: record " + std::to_string(i) + ": " + e);
-  }
+  const bool act = sites != nullptr;
+  const int n_faults = (int)(act ? sites->size() : faults->size());
+  const auto layer_of = [&](int i) { return act ? (*sites)[(size_t)i].layer : (*faults)[(size_t)i].layer; };
+  const auto start_of = [&](int L) { return act ? L + 1 : L; };
   ImageFile f;
   if (open_image_file(path, f)) return -1;
   const int n = (int)f.n, S = net.nlayers;
@@ -2177,28 +2172,31 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
     if (cnv) cnv_workspace_bytes(net.abits, &b0, &b1);
     else lfc_workspace_bytes(net.abits, &b0, &b1);
     const int wcap = (int)std::min<long long>(kMaxChunk, (long long)n_faults * n);  // images of activation workspace
-    // A run group with its faults in layer L holds the outputs of layers L-1 .. S-2 in the workspace at once, (run, image)
+    // A run group that starts at stage s0 holds the outputs of layers s0-1 .. S-2 in the workspace at once, (run, image)
     // slot by slot: its pairs are bounded by the bytes per image of those outputs, not by the layer-0 sizing of the
-    // workspace -- the FC layers take ~25x the pairs of the conv layers.
+    // workspace -- the FC layers take ~25x the pairs of the conv layers.  Activation sites need no blob copies: their
+    // groups are not bounded by kMaxRuns.
     std::vector<int> G((size_t)S, 0), win((size_t)S, 0);
     std::vector<std::vector<int>> by_layer((size_t)S);
-    for (int i = 0; i < n_faults; i++) by_layer[(size_t)faults[(size_t)i].layer].push_back(i);
+    for (int i = 0; i < n_faults; i++) by_layer[(size_t)layer_of(i)].push_back(i);
     long long max_pairs = 0;
     int max_runs = 0;
     for (int L = 0; L < S; L++) {
       if (by_layer[(size_t)L].empty()) continue;
+      const int s0 = start_of(L);
       long long c = kMaxSweepPairs;
-      for (int l = std::max(L - 1, 0); l + 1 < S; l++)
+      for (int l = std::max(s0 - 1, 0); l + 1 < S; l++)
         c = std::min<long long>(c, (long long)((size_t)wcap * (obuf[(size_t)l] ? b1 : b0) / ob[(size_t)l]));
-      if (L == 0) c = std::min<long long>(c, wcap);  // (the first stage writes the layer-0 sizes)
-      const int g = (int)std::max<long long>(1, std::min<long long>({c / n, (long long)kMaxRuns, (long long)by_layer[(size_t)L].size()}));
+      if (s0 == 0) c = std::min<long long>(c, wcap);  // (the first stage writes the layer-0 sizes)
+      const long long runs_cap = act ? kMaxSweepPairs : (long long)kMaxRuns;
+      const int g = (int)std::max<long long>(1, std::min<long long>({c / n, runs_cap, (long long)by_layer[(size_t)L].size()}));
       G[(size_t)L] = g;
       win[(size_t)L] = g > 1 ? n : (int)std::min<long long>(n, c);
       max_pairs = std::max(max_pairs, (long long)g * win[(size_t)L]);
       max_runs = std::max(max_runs, g);
     }
     // -- host: the working copy of the memories and the blob that patches are built on (restored after every fault)
-    RawParams raw = r.raw;
+    RawParams raw = act ? RawParams{} : r.raw;  // (activation sites patch nothing)
     std::vector<uint8_t> blob = r.blob;
     PackedHeader h;
     std::memcpy(&h, blob.data(), sizeof(h));
@@ -2213,7 +2211,7 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
     // -- device buffers
     const size_t res_n = std::max<size_t>((size_t)max_pairs, (size_t)n);
     if (load_file_resident(f, n) || reserve(wcap)) return -1;
-    if (grow(r.d_copies, r.copies_cap, (size_t)max_runs * stride) || grow(r.d_sw_base, r.sw_base_cap, boff[(size_t)S]) ||
+    if (grow(r.d_copies, r.copies_cap, act ? 0 : (size_t)max_runs * stride) || grow(r.d_sw_base, r.sw_base_cap, boff[(size_t)S]) ||
         grow(r.d_sw_segs, r.sw_segs_cap, (size_t)max_pairs * sizeof(MultiSeg)) || grow(r.d_sw_alive, r.sw_alive_cap, (size_t)max_pairs) ||
         grow(r.d_sw_res, r.sw_res_cap, res_n * rb) || grow(r.d_sw_cnt, r.sw_cnt_cap, (size_t)max_runs * 12 + 512) ||
         grow(r.d_sw_diffs, r.sw_diffs_cap, (size_t)max_pairs * 8))
@@ -2281,7 +2279,8 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
       HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
       return 0;
     };
-    auto stage = [&](int l, const uint8_t *copies, bool two) -> int {
+    // layer l's stage over the batches: rows from `copies` (run q's copy at q * cstride), results to `res`
+    auto stage = [&](int l, const uint8_t *copies, size_t cstride, bool two, uint8_t *res) -> int {
       for (const Batch &b : batches) {
         MultiLaunch a{};
         a.images = r.d_all;
@@ -2290,10 +2289,10 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
         a.buf0 = r.buf0; a.buf1 = r.buf1;
         for (int k = 0; k < S; k++) a.rows[k] = reinterpret_cast<const uint32_t *>(copies + h.layer[k].offset);
         a.l0_mfma = tab ? copies + h.l0_mfma_offset : nullptr;
-        a.stride = stride;
+        a.stride = cstride;
         a.has_two = two;
-        a.classes = reinterpret_cast<int32_t *>(copies == r.d_blob ? base_res : r.d_sw_res);
-        a.words = reinterpret_cast<uint64_t *>(copies == r.d_blob ? base_res : r.d_sw_res);
+        a.classes = reinterpret_cast<int32_t *>(res);
+        a.words = reinterpret_cast<uint64_t *>(res);
         a.number_class = number_class;
         a.stream = r.stream;
         a.first = a.last = l;
@@ -2310,7 +2309,7 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
       segs.assign(1, MultiSeg{0, i0, 0, m});
       if (plan()) return -1;
       for (int l = 0; l < S; l++) {
-        if (stage(l, clean, base_two > 0)) return -1;
+        if (stage(l, clean, stride, base_two > 0, base_res)) return -1;
         if (l + 1 < S)
           HIP_OK(hipMemcpyAsync(r.d_sw_base + boff[(size_t)l] + (size_t)i0 * ob[(size_t)l], bufs[obuf[(size_t)l]], (size_t)m * ob[(size_t)l],
                                 hipMemcpyDeviceToDevice, r.stream));
@@ -2322,63 +2321,94 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
       HIP_OK(hipMemcpy(words.data(), base_res, (size_t)n * 8, hipMemcpyDeviceToHost));
       for (int i = 0; i < n; i++) base_cls[(size_t)i] = lfc_class_batched(words[(size_t)i], number_class);
     }
-    // -- the runs' blob copies
+    // -- the runs' blob copies (parameter faults)
     if (begin()) return -1;
-    HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, blob.size(), hipMemcpyDeviceToDevice, r.stream));
-    for (size_t have = 1; have < (size_t)max_runs; have *= 2) {  // replicate by doubling
-      const size_t c = std::min(have, (size_t)max_runs - have);
-      HIP_OK(hipMemcpyAsync(r.d_copies + have * stride, r.d_copies, c * stride, hipMemcpyDeviceToDevice, r.stream));
+    if (!act) {
+      HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, blob.size(), hipMemcpyDeviceToDevice, r.stream));
+      for (size_t have = 1; have < (size_t)max_runs; have *= 2) {  // replicate by doubling
+        const size_t c = std::min(have, (size_t)max_runs - have);
+        HIP_OK(hipMemcpyAsync(r.d_copies + have * stride, r.d_copies, c * stride, hipMemcpyDeviceToDevice, r.stream));
+      }
     }
     // -- run groups: g faults of one layer L, one per copy; window by window of the images
     for (int L = 0; L < S; L++) {
       const std::vector<int> &idx = by_layer[(size_t)L];
       for (size_t c0 = 0; c0 < idx.size(); c0 += (size_t)G[(size_t)L]) {
-        const int g = (int)std::min<size_t>((size_t)G[(size_t)L], idx.size() - c0);
+        const int g = (int)std::min<size_t>((size_t)G[(size_t)L], idx.size() - c0), s0 = start_of(L);
         // host: each fault's patch (the rebuilt row; layer 0: and the MFMA table) and the original bytes it replaces
         std::vector<uint8_t> staging;
         std::vector<PatchSpan> patch, undo;
         bool two = base_two > 0;
-        auto add_span = [&](int q, size_t off, size_t bytes) {
-          patch.push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
-          staging.insert(staging.end(), blob.begin() + off, blob.begin() + off + bytes);
-          undo.push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
-          staging.insert(staging.end(), r.blob.begin() + off, r.blob.begin() + off + bytes);
-        };
-        for (int q = 0; q < g; q++) {
-          const Fault &flt = faults[(size_t)idx[c0 + (size_t)q]];
-          uint64_t *w = fault_word(net, raw, flt);
-          const uint64_t old = *w;
-          const int row = apply_fault(net, raw, flt);
-          const int before = two_flag(L, row);
-          size_t off = 0, bytes = 0;
-          repack_row(net, raw, L, row, blob, &off, &bytes);
-          if (base_two + two_flag(L, row) - before > 0) two = true;
-          if (L == 0 && h.l0_mfma_offset) {  // repack_row's span runs from the row to the table's end: the two parts
-            const size_t rbytes = (size_t)h.layer[0].row_dwords * 4;
-            add_span(q, h.layer[0].offset + (size_t)row * rbytes, rbytes);
-            if (tab) add_span(q, h.l0_mfma_offset, kL0MfmaBytes);
-          } else {
-            add_span(q, off, bytes);
+        hipError_t e = hipSuccess;
+        const PatchSpan *d_spans = nullptr;
+        const ActPatch *d_sites = nullptr;
+        if (act) {  // activation sites: each run's site as k_act_seed patches it
+          ActShape sh{};
+          act_shape(net, L, &sh);
+          const bool two_bit = sh.levels == 3;
+          std::vector<ActPatch> ap((size_t)g);
+          for (int q = 0; q < g; q++) {
+            const ActSite &st = (*sites)[(size_t)idx[c0 + (size_t)q]];
+            const uint32_t pix = (uint32_t)(st.y * sh.w + st.x), c = (uint32_t)st.channel;
+            if (two_bit) {  // [pixel][C/64][sign, non-zero] u64: one 16-byte unit per 64 channels
+              ap[(size_t)q] = ActPatch{pix * (uint32_t)(sh.c / 64) + c / 64, c % 64, (uint32_t)st.shift, 0};
+            } else {  // [pixel][C/32] dwords: four per unit
+              const uint32_t d = pix * (uint32_t)(sh.c / 32) + c / 32;
+              ap[(size_t)q] = ActPatch{d / 4, (d % 4) * 32 + c % 32, (uint32_t)st.shift, 0};
+            }
           }
-          *w = old;
-          repack_row(net, raw, L, row, blob, &off, &bytes);
+          upload.assign(ap.size() * sizeof(ActPatch), 0);
+          std::memcpy(upload.data(), ap.data(), upload.size());
+          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
+          d_sites = reinterpret_cast<const ActPatch *>(r.d_sw_stage);
+        } else {  // parameter faults: the patches of the group's copies
+          auto add_span = [&](int q, size_t off, size_t bytes) {
+            patch.push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
+            staging.insert(staging.end(), blob.begin() + off, blob.begin() + off + bytes);
+            undo.push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
+            staging.insert(staging.end(), r.blob.begin() + off, r.blob.begin() + off + bytes);
+          };
+          for (int q = 0; q < g; q++) {
+            const Fault &flt = (*faults)[(size_t)idx[c0 + (size_t)q]];
+            uint64_t *w = fault_word(net, raw, flt);
+            const uint64_t old = *w;
+            const int row = apply_fault(net, raw, flt);
+            const int before = two_flag(L, row);
+            size_t off = 0, bytes = 0;
+            repack_row(net, raw, L, row, blob, &off, &bytes);
+            if (base_two + two_flag(L, row) - before > 0) two = true;
+            if (L == 0 && h.l0_mfma_offset) {  // repack_row's span runs from the row to the table's end: the two parts
+              const size_t rbytes = (size_t)h.layer[0].row_dwords * 4;
+              add_span(q, h.layer[0].offset + (size_t)row * rbytes, rbytes);
+              if (tab) add_span(q, h.l0_mfma_offset, kL0MfmaBytes);
+            } else {
+              add_span(q, off, bytes);
+            }
+            *w = old;
+            repack_row(net, raw, L, row, blob, &off, &bytes);
+          }
+          const size_t spans_off = (staging.size() + 255) & ~(size_t)255;
+          upload.assign(spans_off + (patch.size() + undo.size()) * sizeof(PatchSpan), 0);
+          std::memcpy(upload.data(), staging.data(), staging.size());
+          std::memcpy(upload.data() + spans_off, patch.data(), patch.size() * sizeof(PatchSpan));
+          std::memcpy(upload.data() + spans_off + patch.size() * sizeof(PatchSpan), undo.data(), undo.size() * sizeof(PatchSpan));
+          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
+          d_spans = reinterpret_cast<const PatchSpan *>(r.d_sw_stage + spans_off);
+          e = scatter_patches(r.d_sw_stage, d_spans, (int)patch.size(), r.d_copies, r.stream);
+          if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
         }
-        const size_t spans_off = (staging.size() + 255) & ~(size_t)255;
-        upload.assign(spans_off + (patch.size() + undo.size()) * sizeof(PatchSpan), 0);
-        std::memcpy(upload.data(), staging.data(), staging.size());
-        std::memcpy(upload.data() + spans_off, patch.data(), patch.size() * sizeof(PatchSpan));
-        std::memcpy(upload.data() + spans_off + patch.size() * sizeof(PatchSpan), undo.data(), undo.size() * sizeof(PatchSpan));
-        if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
-        HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
-        const PatchSpan *d_spans = reinterpret_cast<const PatchSpan *>(r.d_sw_stage + spans_off);
-        hipError_t e = scatter_patches(r.d_sw_stage, d_spans, (int)patch.size(), r.d_copies, r.stream);
-        if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+        if (act && trace().on)
+          std::fprintf(stderr, "bnn-mi355x trace act_fault_sweep: layer %d sites %zu..%zu of %zu, window %d of %d images\n", L, c0, c0 + g - 1,
+                       idx.size(), std::min(win[(size_t)L], n), n);
         const int wl = win[(size_t)L];
         for (int i0 = 0; i0 < n; i0 += wl) {
           const int m = std::min(wl, n - i0);  // (g > 1: m = n)
           if (begin()) return -1;
-          // the runs start from the fault-free output of layer L-1 (slot q * m + j) and the fault-free results
-          if (L > 0) {
+          // the runs start from the fault-free output of layer s0-1 (slot q * m + j) and the fault-free results; activation
+          // sites: with the site changed (k_act_seed, below)
+          if (!act && L > 0) {
             const size_t bb = ob[(size_t)L - 1];
             e = sweep_broadcast(r.d_sw_base + boff[(size_t)L - 1] + (size_t)i0 * bb, bb, m, g, bufs[obuf[(size_t)L - 1]], (size_t)m * bb, r.stream);
             if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
@@ -2387,9 +2417,15 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
           if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
           segs.clear();
           for (int q = 0; q < g; q++) segs.push_back(MultiSeg{q, i0, q * m, m});
-          for (int l = L; l < S; l++) {
-            if (plan() || stage(l, r.d_copies, two)) return -1;
-            if (l == L) pairs[(size_t)l] += (long)g * m;
+          for (int l = s0; l < S; l++) {
+            if (plan()) return -1;
+            if (act && l == s0) {
+              e = act_seed(r.d_sw_base + boff[(size_t)L], (int)ob[(size_t)L], net.L[L].out_planes == 2, d_segs, (int)segs.size(), m, d_sites,
+                           bufs[obuf[(size_t)L]], r.stream);
+              if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+            }
+            if (act ? stage(l, clean, 0, two, r.d_sw_res) : stage(l, r.d_copies, stride, two, r.d_sw_res)) return -1;
+            if (l == s0) pairs[(size_t)l] += (long)g * m;
             if (l + 1 == S) break;
             // prune: only the (run, image) pairs whose output differs from the fault-free one go on (and the gaps between them below `bridge`)
             HIP_OK(hipMemsetAsync(r.d_sw_alive, 0, (size_t)g * m, r.stream));
@@ -2481,6 +2517,7 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
           }
         }
         // the copies back to the loaded parameters
+        if (act) continue;
         if (begin()) return -1;
         e = scatter_patches(r.d_sw_stage, d_spans + patch.size(), (int)undo.size(), r.d_copies, r.stream);
         if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
@@ -2498,14 +2535,85 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
       diffs[3 * k + 1] = e.second[i];
       diffs[3 * k + 2] = e.second[i + 1];
     }
-  r.sweep_pairs = std::move(pairs);
+  stage_pairs = std::move(pairs);
   if (image_number) *image_number = n;
   if (usecPerImage) *usecPerImage = (n > 0 && n_faults > 0) ? (float)(device_us / ((double)n_faults * n)) : 0.f;
   return total_changed;
 }
 
+long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
+                            long cap_diffs, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  r.sweep_pairs.clear();
+  if (n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs))
+    return fail("fault_sweep: bad arguments (records / changed missing, or cap_diffs without diffs)");
+#ifdef BNN_VARIANT
+  return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+#endif
+  if (!ready()) return -1;
+  if (r.raw.empty()) return fail("fault injection needs the parameter files (load_parameters), not an imported blob");
+  if (r.l1_mfma || r.l1_literal)
+    return fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the matrix-pipe table is not patched)");
+  const NetSpec &net = r.spec;
+  std::vector<Fault> faults((size_t)n_faults);
+  for (int i = 0; i < n_faults; i++) {
+    const int *v = records + (size_t)i * 8;
+    faults[(size_t)i] = Fault{0, v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    const std::string e = check_fault(net, faults[(size_t)i]);
+    if (!e.empty()) return fail("fault_sweep: record " + std::to_string(i) + ": " + e);
+  }
+  return single_fault_sweep(path, number_class, &faults, nullptr, changed, diffs, cap_diffs, image_number, usecPerImage, r.sweep_pairs);
+}
+
 int bnn_mi355x_last_sweep_stages(long *pairs_per_stage, int cap) {
   const std::vector<long> &p = rt().sweep_pairs;
+  for (int i = 0; pairs_per_stage && i < cap && i < (int)p.size(); i++) pairs_per_stage[i] = p[(size_t)i];
+  return (int)p.size();
+}
+
+long bnn_mi355x_enumerate_act_faults(int layer, long first, int *records, int cap_records) {
+  const NetSpec &net = rt().spec;
+  const long total = enumerate_act_faults(net, layer, 0, nullptr, 0);
+  if (total < 0 || first < 0)
+    return fail("enumerate_act_faults: bad layer (0 ... " + std::to_string(net.nlayers - 2) + ": the last layer has no activations) or first");
+  if (records && cap_records > 0 && first < total) {
+    std::vector<ActSite> v((size_t)std::min<long>(cap_records, total - first));
+    enumerate_act_faults(net, layer, first, v.data(), (long)v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      const int w[5] = {v[i].layer, v[i].y, v[i].x, v[i].channel, v[i].shift};
+      std::memcpy(records + i * 5, w, sizeof w);
+    }
+  }
+  return total;
+}
+
+long bnn_mi355x_act_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
+                                long cap_diffs, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  r.act_sweep_pairs.clear();
+  if (n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs))
+    return fail("act_fault_sweep: bad arguments (records / changed missing, or cap_diffs without diffs)");
+#ifdef BNN_VARIANT
+  return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+#endif
+  const NetSpec &net = r.spec;
+  std::vector<ActSite> sites((size_t)n_faults);
+  for (int i = 0; i < n_faults; i++) {  // (host only: before anything runs on the device)
+    const int *v = records + (size_t)i * 5;
+    sites[(size_t)i] = ActSite{v[0], v[1], v[2], v[3], v[4]};
+    const std::string e = check_act_fault(net, sites[(size_t)i]);
+    if (!e.empty())
+      return fail("act_fault_sweep: record " + std::to_string(i) + " {" + std::to_string(v[0]) + ", " + std::to_string(v[1]) + ", " +
+                  std::to_string(v[2]) + ", " + std::to_string(v[3]) + ", " + std::to_string(v[4]) + "}: " + e);
+  }
+  if (!ready()) return -1;
+  if (r.l1_mfma || r.l1_literal)
+    return fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the sweeps run the standard multi-run stages)");
+  return single_fault_sweep(path, number_class, nullptr, &sites, changed, diffs, cap_diffs, image_number, usecPerImage, r.act_sweep_pairs);
+}
+
+int bnn_mi355x_last_act_sweep_stages(long *pairs_per_stage, int cap) {
+  const std::vector<long> &p = rt().act_sweep_pairs;
   for (int i = 0; pairs_per_stage && i < cap && i < (int)p.size(); i++) pairs_per_stage[i] = p[(size_t)i];
   return (int)p.size();
 }

@@ -229,6 +229,31 @@ long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long firs
 long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
                             long cap_diffs, int *image_number, float *usecPerImage);
 int bnn_mi355x_last_sweep_stages(long *pairs_per_stage, int cap);
+/* Activation-fault sweeps: which datapath bits matter (a soft error in the stream between two layers, one image).
+ * A site is one activation of layer L's output as layer L+1 reads it (CNV layers 1 and 3: after the max-pool), L any
+ * layer but the last; records are 5 ints {layer, y, x, channel, shift} in the value domain and HWC order of the
+ * oracle's layer_ref (FC layers: y = x = 0, channel = the neuron).  The fault replaces the activation's level index
+ * i (1-bit: -1, +1; 2-bit: -1, 0, +1) by (i + shift) mod levels, 1 <= shift < levels: it changes the activation of
+ * every image.  This model is the project's own (the reference has none).
+ * enumerate_act_faults: every site x shift of layer L ordered by (y, x, channel, shift); writes records
+ * [first, first + cap_records) and returns the total (records may be NULL); -1 + last_error for the last layer or a
+ * layer out of range.  Host only.
+ * act_fault_sweep: for each record, classify every image of `path` with that one activation changed while that image
+ * is classified, independently of the other records; changed / diffs / return value / usecPerImage as fault_sweep.
+ * The loaded parameters and last_faults / last_campaign_faults / last_sweep_stages are unchanged.  Every record is
+ * validated on the host before anything runs on the device.  Refused (-1 + last_error): bad arguments; a record
+ * whose layer has no sites (the last one, out of range) or whose site or shift lies outside it (the message names
+ * the record); the hardened variants ("not modelled", as every fault entry point); the BNN_MI355X_L1 comparison
+ * forms.  An imported blob is fine: activation faults patch no parameter.
+ * The fault-free pass runs once and keeps every layer's output; a site in layer L starts at layer L+1 from that
+ * output with the site changed, and pairs whose activations return to the fault-free ones are dropped as in
+ * fault_sweep.
+ * last_act_sweep_stages: of the last activation sweep, per layer the (fault, image) pairs it had to run (0 up to
+ * layer L of the earliest site); returns the number of layers (0 before the first such sweep). */
+long bnn_mi355x_enumerate_act_faults(int layer, long first, int *records, int cap_records);
+long bnn_mi355x_act_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
+                                long cap_diffs, int *image_number, float *usecPerImage);
+int bnn_mi355x_last_act_sweep_stages(long *pairs_per_stage, int cap);
 
 /* The step before the path: CnvClassifier.image_to_cifar (bnn/bnn.py:226-242) on the
  * device.  The reference shrinks a picture with PIL's Image.thumbnail((32, 32), ANTIALIAS) -- Lanczos-3,

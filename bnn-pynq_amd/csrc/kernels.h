@@ -15,6 +15,8 @@ struct CnvLaunch {
   const uint8_t *l0_mfma;     // device, layer-0 MFMA table (packed_params.h); null: integer-pipe k_conv0
   const uint8_t *l1_mfma;     // device, cnvW1A1 layer 1 as FP4 MFMA operands (l1_mfma_table); null: the XNOR-popcount kernel.
                               // Side experiment only (BNN_MI355X_L1=mfma): never the default path.
+  const uint8_t *conv_mfma;   // device, cnvW1A1 layers 1-3 as FP4 MFMA operands (conv_mfma_table); null: the XNOR-popcount
+                              // kernels only (BNN_MI355X_CONV=valu, and the fault-injection paths)
   bool l1_literal;            // cnvW1A1, BNN_MI355X_L1=lds: layer 1 in the north-star's literal formulation (comparison figure only)
   bool has_two;               // cnvW2A2: some row holds a weight of -2 (fault injection): the -2-aware kernel variants
   int16_t *scores;            // device, n x 64, may be null
@@ -73,6 +75,15 @@ void lfc_workspace_bytes(int abits, size_t *buf0, size_t *buf1);
 // "mismatches < t").  rows: layer 1 of the packed blob (host pointer).  Returns the table's bytes.
 constexpr size_t kL1MfmaWeights = 9 * 2 * 64 * 16, kL1MfmaBytes = kL1MfmaWeights + 2 * 2 * 16 * 4;
 void l1_mfma_table(const uint32_t *rows, uint8_t *dst);
+
+// cnvW1A1 layers 1-3 for the matrix pipe (the throughput path from conv_mfma_min() images on): one table
+// per layer, each [k step][neuron tile][lane 0..63][16 bytes] of FP4 weights (k step = tap * (Cin / 64) + 64-channel
+// block; lane (r, h) holds channels 32h..32h+31 of the step for neuron 32 * tile + r), then the seeds [tile][h][16]
+// floats -(theta + 1).  Layer 1's table is laid out as l1_mfma_table's.  Made on the device from the packed rows.
+constexpr size_t kConvMfmaL2Off = kL1MfmaBytes, kConvMfmaL3Off = kConvMfmaL2Off + 9 * 4 * 64 * 16 + 4 * 32 * 4,
+                 kConvMfmaBytes = kConvMfmaL3Off + 18 * 4 * 64 * 16 + 4 * 32 * 4;
+// rows: device pointers to cnvW1A1's packed layers (rows[1..3] are read); enqueued on s
+hipError_t conv_mfma_table(const uint32_t *const rows[9], uint8_t *dst, hipStream_t s);
 
 // enqueue all stages of one batch on a.stream; returns the launch error, if any
 hipError_t run_cnv(NetId net, const CnvLaunch &a);

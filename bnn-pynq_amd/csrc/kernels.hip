@@ -24,7 +24,8 @@
 //     stored once: outputs are already in the bit-packed layout the next stage
 //     reads.  Max-pool is a min/max over the quad's 4 accumulators before the
 //     threshold compare (thresholding is monotone), so it is free.
-//   * No MFMA in the bitwise layers.  No LDS in the throughput kernels: there is no data shared
+//   * No MFMA in the bitwise layers, except cnvW1A1 layers 1-3 on the throughput path (k_conv_mfma: exact FP4 implicit
+//     GEMMs, DESIGN.md 5 "The matrix pipe").  No LDS in the XNOR-popcount throughput kernels: there is no data shared
 //     between lanes that the scalar path does not already broadcast for free.  The exceptions,
 //     each argued where it is defined: the int8 first layer runs on the matrix pipe
 //     (k_conv0_mfma); small batches, where a lane per item leaves the chip empty, use a lane
@@ -684,6 +685,139 @@ __global__ __launch_bounds__(256, 2) void k_l1_mfma(const uint32_t *__restrict__
       if (h == 0 && c < 28 && !(c & 1))
         *reinterpret_cast<uint2 *>(out + ((size_t)(img0 + i) * 196 + r * 14 + (c >> 1)) * 2) = make_uint2(word[0], word[1]);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// cnvW1A1 layers 1-3 on the matrix pipe: the throughput path from conv_mfma_min() images on ("The matrix
+// pipe").  The implicit GEMM of k_l1_mfma -- +-1 as FP4 E2M1, f32 accumulators seeded with -(theta + 1), sign bit =
+// !fire -- with the pixel tile filled across rows and images: rows of 28 / 12 / 10 output pixels would leave 4 / 20 /
+// 22 of a tile's 32 lanes idle.  A WORK ITEM is one column x of one output row PAIR (2rp, 2rp + 1) of one image, items
+// numbered (image, rp, x) over the block's G images, 32 consecutive items per tile (lane c).
+//   * A block takes G images at a time (2 for layer 1, 8 for layers 2 and 3): their bit-packed maps are expanded once
+//     into FP4 planes in LDS ([image][32-channel block q][pixel] x 16 bytes; lane (c, h) reads block 2 kh + h); the
+//     next group's bits are requested into registers before the current group's MFMAs are issued (as in k_l1_mfma).
+//   * A wave owns one neuron tile (32 neurons) for the whole kernel: its FP4 weights sit in VGPRs (36 for layers 1 and
+//     2, 72 for layer 3), so no wave spills (k_l1_mfma keeps two tiles and spills).  The waves read the same B operands.
+//   * Per tile and 64-channel step kh, per column offset kx: 4 ds_read_b128 (input rows 2rp .. 2rp + 3) feed 6
+//     MFMAs (output rows 2rp, 2rp + 1 x ky), as k_l1_mfma's row pairs do.
+//   * No pool (layer 2): lane half h stores output row 2rp + h (after the half swap both halves hold the word).
+//     Pool (layers 1, 3): vertical max = v_max_f32 of the two rows' accumulators, horizontal = AND of !fire with lane
+//     c ^ 1 (DPP; items per image and per row are even, so x and x ^ 1 of a row pair sit in lanes c and c ^ 1).
+// Items past the last image repeat the last valid one (their results are dropped).  Outputs are the XNOR kernels'
+// bit-packed HWC words, byte for byte.
+// ---------------------------------------------------------------------------
+// WIN: input width (square map), CD: input dwords per pixel (2: 64 channels, 4: 128), NT: neuron tiles (output dwords
+// per pixel), POOL: 2x2 max-pool behind, G: images per block and group.  Layer 1 (NT = 2): waves w and w + 2 own the
+// same neuron tile and take alternate pixel tiles.
+template <int WIN, int CD, int NT, bool POOL, int G>
+__global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                       const uint8_t *__restrict__ tab, int n_images) {
+  constexpr int WOUT = WIN - 2, RP = WOUT / 2, IPI = RP * WOUT, KH = CD / 2, KS = 9 * KH, STREAMS = 4 / NT;
+  constexpr int PIX = WIN * WIN, DWI = PIX * CD, NPF = (G * DWI + 255) / 256;
+  static_assert(WOUT % 2 == 0 && IPI % 2 == 0 && (NT == 2 || NT == 4), "tile geometry");
+  __shared__ uint4 plane[G][CD][PIX];
+  __shared__ uint32_t lut[256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mt = wave % NT, c = lane & 31, h = lane >> 5;
+  lut[tid] = fp4_pm1((uint32_t)tid);
+  // weights [k step = tap * KH + kh][neuron tile][lane] x 16 bytes, then the seeds [tile][h][16] floats
+  const uint4 *__restrict__ wt = reinterpret_cast<const uint4 *>(tab);
+  v8i wreg[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ks++) {
+    const uint4 v = wt[(ks * NT + mt) * 64 + lane];
+    wreg[ks] = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+  }
+  const v16f seed = reinterpret_cast<const v16f *>(tab + (size_t)KS * NT * 64 * 16)[mt * 2 + h];
+  const int ngroups = (n_images + G - 1) / G;
+  uint32_t pre[NPF];
+  auto fetch = [&](int grp) {
+    const int img0 = grp * G, lim = min(G, n_images - img0) * DWI;
+#pragma unroll
+    for (int j = 0; j < NPF; j++) {
+      const int d = tid + 256 * j;
+      pre[j] = d < lim ? in[(size_t)img0 * DWI + d] : 0u;
+    }
+  };
+  if (blockIdx.x < ngroups) fetch(blockIdx.x);
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int img0 = grp * G, nimg = min(G, n_images - img0), nitems = nimg * IPI;
+    __syncthreads();  // the previous group's planes are no longer read
+#pragma unroll
+    for (int j = 0; j < NPF; j++) {  // one source dword (32 channels of a pixel) per iteration
+      const int d = tid + 256 * j;
+      if (d < nimg * DWI) {
+        const int i = d / DWI, e = d - i * DWI, pix = e / CD, q = e % CD;
+        const uint32_t bits = pre[j];
+        plane[i][q][pix] = make_uint4(lut[bits & 255], lut[(bits >> 8) & 255], lut[(bits >> 16) & 255], lut[bits >> 24]);
+      }
+    }
+    if (grp + (int)gridDim.x < ngroups) fetch(grp + gridDim.x);
+    __syncthreads();
+    for (int t0 = (wave / NT) * 32; t0 < nitems; t0 += 32 * STREAMS) {
+      const int item = min(t0 + c, nitems - 1);
+      const int i = item / IPI, rem = item - i * IPI, rp = rem / WOUT, x = rem - rp * WOUT;
+      v16f acc[2] = {seed, seed};  // output rows 2rp, 2rp + 1
+#pragma unroll
+      for (int kh = 0; kh < KH; kh++) {
+        const uint4 *__restrict__ P = &plane[i][kh * 2 + h][2 * rp * WIN + x];
+#pragma unroll
+        for (int kx = 0; kx < 3; kx++) {
+          v8i b[4];  // input rows 2rp .. 2rp + 3 at column x + kx
+#pragma unroll
+          for (int y = 0; y < 4; y++) {
+            const uint4 v = P[y * WIN + kx];
+            b[y] = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+          }
+#pragma unroll
+          for (int ky = 0; ky < 3; ky++)
+#pragma unroll
+            for (int dy = 0; dy < 2; dy++)
+              acc[dy] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wreg[(ky * 3 + kx) * KH + kh], b[ky + dy], acc[dy], 4, 4, 0,
+                                                                         0x7F7F7F7F, 0, 0x7F7F7F7F);
+        }
+      }
+      const bool valid = t0 + c < nitems;
+      const size_t img = (size_t)(img0 + i);
+      if constexpr (POOL) {
+        int v[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[k] = __float_as_int(fmaxf(acc[0][k], acc[1][k]));
+        const uint32_t nf = or_halves(sign_nibbles(v, h));
+        const uint32_t pooled = nf & (uint32_t)__builtin_amdgcn_mov_dpp((int)nf, 0xB1, 0xF, 0xF, true);  // & lane c ^ 1
+        if (valid && h == 0 && !(x & 1)) out[(img * (RP * RP) + rp * RP + (x >> 1)) * NT + mt] = ~pooled;
+      } else {
+        uint32_t nf[2];
+#pragma unroll
+        for (int dy = 0; dy < 2; dy++) {
+          int v[16];
+#pragma unroll
+          for (int k = 0; k < 16; k++) v[k] = __float_as_int(acc[dy][k]);
+          nf[dy] = or_halves(sign_nibbles(v, h));
+        }
+        if (valid) out[(img * (WOUT * WOUT) + (2 * rp + h) * WOUT + x) * NT + mt] = ~(h ? nf[1] : nf[0]);
+      }
+    }
+  }
+}
+
+// The operand tables of the matrix forms of cnvW1A1 layers 1-3 (kernels.h, conv_mfma_table), made from the packed rows
+// in HBM.  One thread per 16-byte weight entry [k step][neuron tile][lane], then one per seed [tile][h][16].
+__global__ __launch_bounds__(256) void k_conv_mfma_table(const uint32_t *__restrict__ rows, int row_dw, int ksteps, int tiles,
+                                                          int mw, uint8_t *__restrict__ dst) {
+  const int idx = blockIdx.x * 256 + threadIdx.x, nw = ksteps * tiles * 64;
+  if (idx < nw) {
+    const int ks = idx / (tiles * 64), mt = (idx / 64) % tiles, lane = idx & 63, n = 32 * mt + (lane & 31), h = lane >> 5;
+    const uint32_t bits = rows[(size_t)n * row_dw + 2 + 2 * ks + h];  // channels 32h .. 32h + 31 of k step ks
+    reinterpret_cast<uint4 *>(dst)[idx] = make_uint4(fp4_pm1(bits & 255), fp4_pm1((bits >> 8) & 255), fp4_pm1((bits >> 16) & 255),
+                                                     fp4_pm1(bits >> 24));
+  } else if (idx < nw + tiles * 32) {
+    const int j = idx - nw, mt = j >> 5, h = (j >> 4) & 1, reg = j & 15;
+    const int n = 32 * mt + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    // as l1_mfma_table: fire <=> dot > mw - 2t =: theta; the clamp keeps never / always firing rows exact in f32
+    long long t = (int)rows[(size_t)n * row_dw];
+    t = t < -1 ? -1 : (t > mw + 2 ? mw + 2 : t);
+    reinterpret_cast<float *>(dst + (size_t)nw * 16)[j] = (float)(-(mw - 2 * t) - 1);
   }
 }
 
@@ -2129,6 +2263,26 @@ inline long long l0_tile_min() {
   return v;
 }
 
+// images: from here on cnvW1A1 layers 1-3 run on the matrix pipe (k_conv_mfma) when the runtime has made their operand
+// tables (not under BNN_MI355X_CONV=valu, not in the fault-injection paths) -- measured (tools/batch_sweep.py, us per
+// batch, matrix vs XNOR-popcount forms): 512 images 62 vs 73, 1 024 78 vs 122, 4 096 165 vs 373, 16 384 553 vs 1 328
+// (profiles/r05_batch_sweep.txt; smaller batches not measured).  BNN_MI355X_CONV_MFMA_MIN overrides
+inline long long conv_mfma_min() {
+  static const long long v = [] {
+    const char *e = std::getenv("BNN_MI355X_CONV_MFMA_MIN");
+    return e ? std::atoll(e) : 512LL;
+  }();
+  return v;
+}
+// persistent grid of the matrix forms: at most `cap` blocks (what stays resident on the 256 CUs), the `units` (image pairs
+// or groups) dealt evenly over them
+inline unsigned persistent_grid(long long units, long long cap) {
+  const long long per = (units + cap - 1) / cap;
+  return (unsigned)((units + per - 1) / per);
+}
+constexpr long long kConvMfmaGrid = 512;  // 2 blocks per CU (VGPRs; LDS 59 / 51 / 75 KB per block)
+constexpr int kConvMfmaImgsL1 = 2, kConvMfmaImgs = 8;  // images per block and group: layer 1, layers 2 and 3
+
 // neuron groups per block: all of them once the work items alone fill the chip (256 CUs x 8 blocks),
 // so that a lane writes whole output words and reads its window once; otherwise one (parallelism first)
 inline int gpb_for(long long items, int groups) { return (items + kBlock - 1) / kBlock >= 2048 ? groups : 1; }
@@ -2191,6 +2345,11 @@ void run_cnv_t(const CnvLaunch &a) {
     // tiny batches: a lane per output PIXEL instead of per 2x2 quad (k_vec_x in its window form, 8 neurons
     // per block): four times the lanes, a quarter of the serial work of each
     const bool pix = n <= kPixelLaneMax;
+    // the matrix forms of layers 1-3 ("The matrix pipe"); the XNOR-popcount kernels below stay the path
+    // for smaller batches, BNN_MI355X_CONV=valu and the fault-injection paths
+    const uint8_t *const cm = n >= conv_mfma_min() ? a.conv_mfma : nullptr;
+    const dim3 g1(persistent_grid((n + kConvMfmaImgsL1 - 1) / kConvMfmaImgsL1, kConvMfmaGrid)),
+        gm(persistent_grid((n + kConvMfmaImgs - 1) / kConvMfmaImgs, kConvMfmaGrid));
     if (a.last_stage >= 1) {
       if (a.l1_literal) {  // comparison figure (BNN_MI355X_L1=lds): the north-star's wording, untuned
         BNN_LAUNCH(k_l1_literal, dim3((unsigned)((n * 784 + kBlock - 1) / kBlock)), s, A64, reinterpret_cast<uint64_t *>(B), a.rows[1], (int)(n * 784));
@@ -2198,17 +2357,22 @@ void run_cnv_t(const CnvLaunch &a) {
         const long long pairs = (n + 1) / 2;
         hipLaunchKernelGGL(k_l1_mfma, dim3((unsigned)(pairs < 512 ? pairs : 512)), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(a.buf0), B,
                            a.l1_mfma, (int)n);
+      } else if (cm) {
+        hipLaunchKernelGGL((k_conv_mfma<30, 2, 2, true, kConvMfmaImgsL1>), g1, dim3(256), 0, s, reinterpret_cast<const uint32_t *>(a.buf0), B, cm,
+                           (int)n);
       } else if (pix) BNN_LAUNCH((k_vec_x<9, true, 1, 30, 8, true>), grid_for(n * 784, 8), s, A64, B, a.rows[1], (int)(n * 784), 8, 1);
       else BNN_STAGE((k_quad_x<1, 30, true>), (k_quad_x<1, 30, true, 8>), n * 196, 2, A64, B, a.rows[1]);
     }
     BNN_MARK(a.events, 2, s);
     if (a.last_stage >= 2) {
-      if (pix) BNN_LAUNCH((k_vec_x<9, true, 1, 14, 8>), grid_for(n * 144, 16), s, B64, A, a.rows[2], (int)(n * 144), 16, 1);
+      if (cm) hipLaunchKernelGGL((k_conv_mfma<14, 2, 4, false, kConvMfmaImgs>), gm, dim3(256), 0, s, B, A, cm + kConvMfmaL2Off, (int)n);
+      else if (pix) BNN_LAUNCH((k_vec_x<9, true, 1, 14, 8>), grid_for(n * 144, 16), s, B64, A, a.rows[2], (int)(n * 144), 16, 1);
       else BNN_STAGE((k_quad_x<1, 14, false>), (k_quad_x<1, 14, false, 8>), n * 36, 4, B64, A, a.rows[2]);
     }
     BNN_MARK(a.events, 3, s);
     if (a.last_stage >= 3) {
-      if (pix) BNN_LAUNCH((k_vec_x<18, true, 2, 12, 8, true>), grid_for(n * 100, 16), s, A64, B, a.rows[3], (int)(n * 100), 16, 1);
+      if (cm) hipLaunchKernelGGL((k_conv_mfma<12, 4, 4, true, kConvMfmaImgs>), gm, dim3(256), 0, s, A, B, cm + kConvMfmaL3Off, (int)n);
+      else if (pix) BNN_LAUNCH((k_vec_x<18, true, 2, 12, 8, true>), grid_for(n * 100, 16), s, A64, B, a.rows[3], (int)(n * 100), 16, 1);
       else BNN_STAGE((k_quad_x<2, 12, true>), (k_quad_x<2, 12, true, 8>), n * 25, 4, A64, B, a.rows[3]);
     }
     BNN_MARK(a.events, 4, s);
@@ -2373,6 +2537,17 @@ void l1_mfma_table(const uint32_t *rows, uint8_t *dst) {
         t = t < -1 ? -1 : (t > 578 ? 578 : t);
         seeds[(mt * 2 + h) * 16 + reg] = (float)(-(576 - 2 * t) - 1);
       }
+}
+
+hipError_t conv_mfma_table(const uint32_t *const rows[9], uint8_t *dst, hipStream_t s) {
+  // layer: rows, k steps (taps x 64-channel blocks), table offset; 128 neurons in layers 2 and 3, 64 in layer 1
+  const struct { int layer, ksteps, tiles; size_t off; } part[3] = {{1, 9, 2, 0}, {2, 9, 4, kConvMfmaL2Off}, {3, 18, 4, kConvMfmaL3Off}};
+  for (const auto &p : part) {
+    const int entries = p.ksteps * p.tiles * 64 + p.tiles * 32;
+    hipLaunchKernelGGL(k_conv_mfma_table, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, rows[p.layer], 2 + 2 * p.ksteps, p.ksteps,
+                       p.tiles, 64 * p.ksteps, dst + p.off);
+  }
+  return hipGetLastError();
 }
 
 hipError_t run_cnv(NetId net, const CnvLaunch &a) {

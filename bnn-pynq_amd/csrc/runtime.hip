@@ -187,6 +187,10 @@ struct Runtime {
   const uint8_t *l0_mfma = nullptr;  // layer 0 as an MFMA operand (CNV nets), unless BNN_MI355X_L0=valu
   uint8_t *d_l1_mfma = nullptr;      // cnvW1A1, BNN_MI355X_L1=mfma only: layer 1 as FP4 MFMA operands (side experiment)
   bool l1_mfma = false, l1_literal = false;  // BNN_MI355X_L1=mfma / =lds (comparison figures, never the default)
+  // cnvW1A1 layers 1-3 as FP4 MFMA operands (kernels.h, conv_mfma_table), made on the device from the blob's rows whenever
+  // they change; null under BNN_MI355X_CONV=valu.  conv_xnor: the call in progress runs the XNOR-popcount kernels only.
+  uint8_t *d_conv_mfma = nullptr;
+  bool conv_mfma = false, conv_xnor = false;
   bool warmed = false;  // warm_up() has run since the last deinit()
   int two_rows = 0;  // rows holding a weight of -2 (2-bit-weight net under fault injection): kernels.hip, two_extra
   // workspace
@@ -361,6 +365,16 @@ struct DrainOnFailure {
   }
 };
 
+// (re)make the matrix forms' operand tables from the rows in HBM, behind whatever changed them on stream s
+int make_conv_tables(hipStream_t s) {
+  Runtime &r = rt();
+  if (!r.conv_mfma) return 0;
+  if (!r.d_conv_mfma) HIP_OK(hipMalloc(reinterpret_cast<void **>(&r.d_conv_mfma), kConvMfmaBytes));
+  HIP_OK(conv_mfma_table(r.rows, r.d_conv_mfma, s));
+  HIP_OK(hipStreamSynchronize(s));  // (the second compute lane reads them too)
+  return 0;
+}
+
 int upload_blob() {
   Runtime &r = rt();
   if (bind_device()) return -1;
@@ -388,7 +402,9 @@ int upload_blob() {
     if (!r.d_l1_mfma) HIP_OK(hipMalloc(reinterpret_cast<void **>(&r.d_l1_mfma), kL1MfmaBytes));
     HIP_OK(hipMemcpy(r.d_l1_mfma, tab.data(), kL1MfmaBytes, hipMemcpyHostToDevice));
   }
-  return 0;
+  const char *cv = std::getenv("BNN_MI355X_CONV");
+  r.conv_mfma = r.spec.id == NET_CNVW1A1 && !(cv && std::strcmp(cv, "valu") == 0);
+  return make_conv_tables(r.stream);
 }
 
 void free_workspace() {
@@ -697,6 +713,7 @@ int enqueue(const uint8_t *d_imgs, int n, int ncls, int32_t *d_classes, int16_t 
     a.l0_mfma = r.l0_mfma;
     a.l1_mfma = r.l1_mfma ? r.d_l1_mfma : nullptr;
     a.l1_literal = r.l1_literal;
+    a.conv_mfma = r.conv_mfma && !r.conv_xnor ? r.d_conv_mfma : nullptr;
     a.has_two = r.two_rows > 0;
     a.scores = d_scores; a.classes = d_classes; a.number_class = ncls; a.stream = s; a.events = evs;
     a.last_stage = r.debug_last_stage >= 0 ? r.debug_last_stage : kCnvStages - 1;
@@ -1851,8 +1868,12 @@ int *inference_multiple_with_faults(const char *path, int number_class, int *ima
     drain.ok();
     return (int)(ms_total * 1000.0 + 0.5);  // device microseconds of the campaign
   };
+  // The campaign runs the XNOR-popcount kernels (its row patches land between the batches, the matrix forms' tables are
+  // made from the rows once); the patches persist, so the tables are remade from the patched rows behind them.
+  r.conv_xnor = true;
   const int total_us = run();
-  if (total_us < 0) {
+  r.conv_xnor = false;
+  if (make_conv_tables(r.stream) || total_us < 0) {
     delete[] result;
     return nullptr;
   }

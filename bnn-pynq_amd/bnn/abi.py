@@ -21,7 +21,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_params_bytes", "bnn_mi355x_import_params_device", "bnn_mi355x_params_crc", "bnn_mi355x_chunk_plan",
        "bnn_mi355x_binarize_pack", "bnn_mi355x_fault_campaigns", "bnn_mi355x_last_campaign_faults",
        "bnn_mi355x_enumerate_faults", "bnn_mi355x_fault_sweep", "bnn_mi355x_last_sweep_stages",
-       "bnn_mi355x_enumerate_act_faults", "bnn_mi355x_act_fault_sweep", "bnn_mi355x_last_act_sweep_stages"]
+       "bnn_mi355x_enumerate_act_faults", "bnn_mi355x_act_fault_sweep", "bnn_mi355x_last_act_sweep_stages",
+       "bnn_mi355x_matrix_stages"]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -68,6 +69,9 @@ def declare_extensions(L):
                                               C.c_void_p]
     L.bnn_mi355x_reserve.argtypes = [C.c_int]
     L.bnn_mi355x_chunk_plan.argtypes = [C.c_int, C.c_int, ip, C.c_int]
+    if hasattr(L, "bnn_mi355x_matrix_stages"):  # (an older build of the same ABI under BNN_MI355X_LIBDIR lacks it)
+        L.bnn_mi355x_matrix_stages.argtypes = [C.c_int]
+        L.bnn_mi355x_matrix_stages.restype = C.c_int
     L.bnn_mi355x_binarize_pack.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bnn_mi355x_set_fault_seed.argtypes = [C.c_ulonglong]
     L.bnn_mi355x_last_faults.argtypes = [ip, C.c_int]

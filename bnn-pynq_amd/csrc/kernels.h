@@ -15,8 +15,9 @@ struct CnvLaunch {
   const uint8_t *l0_mfma;     // device, layer-0 MFMA table (packed_params.h); null: integer-pipe k_conv0
   const uint8_t *l1_mfma;     // device, cnvW1A1 layer 1 as FP4 MFMA operands (l1_mfma_table); null: the XNOR-popcount kernel.
                               // Side experiment only (BNN_MI355X_L1=mfma): never the default path.
-  const uint8_t *conv_mfma;   // device, cnvW1A1 layers 1-3 as FP4 MFMA operands (conv_mfma_table); null: the XNOR-popcount
-                              // kernels only (BNN_MI355X_CONV=valu, and the fault-injection paths)
+  const uint8_t *conv_mfma;   // device, layers 1-3 as FP4 MFMA operands (cnvW1A1: conv_mfma_table, the 2-bit nets:
+                              // conv_mfma_a2_table); null: the XNOR-popcount kernels only (BNN_MI355X_CONV=valu, and the
+                              // fault-injection paths)
   bool l1_literal;            // cnvW1A1, BNN_MI355X_L1=lds: layer 1 in the north-star's literal formulation (comparison figure only)
   bool has_two;               // cnvW2A2: some row holds a weight of -2 (fault injection): the -2-aware kernel variants
   int16_t *scores;            // device, n x 64, may be null
@@ -84,6 +85,17 @@ constexpr size_t kConvMfmaL2Off = kL1MfmaBytes, kConvMfmaL3Off = kConvMfmaL2Off 
                  kConvMfmaBytes = kConvMfmaL3Off + 18 * 4 * 64 * 16 + 4 * 32 * 4;
 // rows: device pointers to cnvW1A1's packed layers (rows[1..3] are read); enqueued on s
 hipError_t conv_mfma_table(const uint32_t *const rows[9], uint8_t *dst, hipStream_t s);
+
+// The same for cnvW1A2 and cnvW2A2 (k_conv_mfma_a2): per layer the weights [k step][neuron tile][lane][16 bytes] (FP4 -1, 0,
+// +1, and -2 where cnvW2A2's row marks it), then the seeds [tile][h][16] floats -(t0 + 1/2), then [tile][h][16] floats t1 - t0.
+constexpr size_t kConvMfmaA2L2Off = 9 * 2 * 64 * 16 + 2 * 64 * 4, kConvMfmaA2L3Off = kConvMfmaA2L2Off + 9 * 4 * 64 * 16 + 4 * 64 * 4,
+                 kConvMfmaA2Bytes = kConvMfmaA2L3Off + 18 * 4 * 64 * 16 + 4 * 64 * 4;
+// rows: device pointers to the net's packed layers (rows[1..3] are read: AR_TB rows for cnvW1A2, AR_TT for cnvW2A2)
+hipError_t conv_mfma_a2_table(NetId net, const uint32_t *const rows[9], uint8_t *dst, hipStream_t s);
+
+// bit k set: stage k of run_cnv(net, a) runs on the matrix pipe (layer 0's MFMA forms count).  Decided by the code that
+// run_cnv itself decides with; nothing is launched.
+int cnv_matrix_stages(NetId net, const CnvLaunch &a);
 
 // enqueue all stages of one batch on a.stream; returns the launch error, if any
 hipError_t run_cnv(NetId net, const CnvLaunch &a);

@@ -24,8 +24,8 @@
 //     stored once: outputs are already in the bit-packed layout the next stage
 //     reads.  Max-pool is a min/max over the quad's 4 accumulators before the
 //     threshold compare (thresholding is monotone), so it is free.
-//   * No MFMA in the bitwise layers, except cnvW1A1 layers 1-3 on the throughput path (k_conv_mfma: exact FP4 implicit
-//     GEMMs, DESIGN.md 5 "The matrix pipe").  No LDS in the XNOR-popcount throughput kernels: there is no data shared
+//   * No MFMA in the bitwise layers, except layers 1-3 of the three CNV nets on the throughput path (k_conv_mfma,
+//     k_conv_mfma_a2: exact FP4 implicit GEMMs, DESIGN.md 5 "The matrix pipe").  No LDS in the XNOR-popcount throughput kernels: there is no data shared
 //     between lanes that the scalar path does not already broadcast for free.  The exceptions,
 //     each argued where it is defined: the int8 first layer runs on the matrix pipe
 //     (k_conv0_mfma); small batches, where a lane per item leaves the chip empty, use a lane
@@ -818,6 +818,190 @@ __global__ __launch_bounds__(256) void k_conv_mfma_table(const uint32_t *__restr
     long long t = (int)rows[(size_t)n * row_dw];
     t = t < -1 ? -1 : (t > mw + 2 ? mw + 2 : t);
     reinterpret_cast<float *>(dst + (size_t)nw * 16)[j] = (float)(-(mw - 2 * t) - 1);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// cnvW1A2 and cnvW2A2 layers 1-3 on the matrix pipe: k_conv_mfma for 2-bit activations (and, through the table, 2-bit
+// weights).  Same tiling, same work items, same LDS planes (16 bytes per 32 channels of a pixel), same MFMA and
+// ds_read_b128 counts per tile.  What differs:
+//   * Source: [image][pixel][C/64][plane] u64, plane 0 = sign, plane 1 = non-zero -- one uint4 per pixel and 64 channels,
+//     fetched as such (the prefetch registers double).  A channel becomes the FP4 nibble 0x2 (+1), 0xA (-1) or 0x0 (0;
+//     the sign bit of a zero activation is ignored, as za & (sa ^ w) ignores it): nibble = 2 * [nz] + 8 * [nz & sign],
+//     two table lookups per source byte OR-ed (lutz: bit i -> 0x2 in nibble i, luts: -> 0x8).
+//   * Weights come ready from the table: +-1 (cnvW1A2), or -1 / 0 / +1 / -2 = 0xA / 0x0 / 0x2 / 0xC (cnvW2A2; -2 exists
+//     only after fault injection).  All are exact FP4 E2M1 values, so rows with -2 need no kernel variant here.
+//   * Two decisions on d = sum of w * a, the reference's accumulator: fire_i <=> t_i < d.  The accumulators are seeded
+//     with -(t0 + 1/2), so that acc = d - t0 - 1/2 and fire0 <=> sign bit clear; one v_sub_f32 with the per-neuron
+//     constant t1 - t0 gives d - t1 - 1/2, whose sign bit decides fire1.
+//     Exactness: |d| <= 2 * 1152, thresholds are clamped in the table to [-2 * MW - 1, 2 * MW] (which changes no
+//     decision), so every partial sum, seed and difference is a multiple of 1/2 below 2^14: exact in f32 in any order of
+//     summation.  The half is there for the sign of zero: products like -1 * 0 are -0, and a decision value that is
+//     an odd multiple of 1/2 is never zero, so the sign bit read is never that of a -0 or +0 however the matrix core
+//     signs its zeros.  (With -(t0 + 1) the value 0 would have to come out as +0 at d = t0 + 1.)
+//   * Thresholds may be unordered (random sets, faults): each fire_i alone is monotone in d, so max-pool = v_max_f32 of
+//     the row pair's accumulators before both decisions, then per decision the AND of !fire_i with lane c ^ 1; the
+//     planes are formed last, as finish_bits<true> forms them: sign = ~(f0 | f1), non-zero = ~(f0 ^ f1).
+//   * Store: a 32-neuron tile is one half of each plane's u64: dword ((pixel * NT/2 + mt/2) * 2 + plane) * 2 + (mt & 1).
+//     With a pool behind, lane half h stores plane h of the pooled pixel; without, half h stores both planes of row 2rp + h.
+// ---------------------------------------------------------------------------
+// bit i of a byte -> 0x1 in nibble i
+__device__ __forceinline__ uint32_t nibble_spread(uint32_t byte) {
+  uint32_t t = byte & 0xFFu;
+  t = (t | (t << 12)) & 0x000F000Fu;
+  t = (t | (t << 6)) & 0x03030303u;
+  return (t | (t << 3)) & 0x11111111u;
+}
+// 32 channels (non-zero bits nz, sign bits sg) -> 32 FP4 nibbles through the two tables
+__device__ __forceinline__ uint4 fp4_planes(const uint32_t *lutz, const uint32_t *luts, uint32_t sg, uint32_t nz) {
+  const uint32_t m = sg & nz;
+  return make_uint4(lutz[nz & 255] | luts[m & 255], lutz[(nz >> 8) & 255] | luts[(m >> 8) & 255],
+                    lutz[(nz >> 16) & 255] | luts[(m >> 16) & 255], lutz[nz >> 24] | luts[m >> 24]);
+}
+// !fire0 and !fire1 words (32 neurons, both lane halves) of 16 pooled or plain accumulators
+__device__ __forceinline__ void not_fired(const v16f &acc, const v16f &dt, int h, uint32_t &n0, uint32_t &n1) {
+  int v[16], u[16];
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    v[k] = __float_as_int(acc[k]);
+    u[k] = __float_as_int(acc[k] - dt[k]);
+  }
+  n0 = or_halves(sign_nibbles(v, h));
+  n1 = or_halves(sign_nibbles(u, h));
+}
+
+template <int WIN, int CD, int NT, bool POOL, int G>
+__global__ __launch_bounds__(256, 2) void k_conv_mfma_a2(const uint4 *__restrict__ in, uint32_t *__restrict__ out,
+                                                          const uint8_t *__restrict__ tab, int n_images) {
+  constexpr int WOUT = WIN - 2, RP = WOUT / 2, IPI = RP * WOUT, KH = CD / 2, KS = 9 * KH, STREAMS = 4 / NT;
+  constexpr int PIX = WIN * WIN, QWI = PIX * KH, NPF = (G * QWI + 255) / 256;  // QWI: source uint4 per image
+  static_assert(WOUT % 2 == 0 && IPI % 2 == 0 && (NT == 2 || NT == 4), "tile geometry");
+  __shared__ uint4 plane[G][CD][PIX];
+  __shared__ uint32_t lutz[256], luts[256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mt = wave % NT, c = lane & 31, h = lane >> 5;
+  lutz[tid] = nibble_spread((uint32_t)tid) << 1;
+  luts[tid] = nibble_spread((uint32_t)tid) << 3;
+  // weights [k step = tap * KH + kh][neuron tile][lane] x 16 bytes, then the seeds and the t1 - t0, each [tile][h][16] floats
+  const uint4 *__restrict__ wt = reinterpret_cast<const uint4 *>(tab);
+  v8i wreg[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ks++) {
+    const uint4 v = wt[(ks * NT + mt) * 64 + lane];
+    wreg[ks] = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+  }
+  const v16f *__restrict__ cst = reinterpret_cast<const v16f *>(tab + (size_t)KS * NT * 64 * 16);
+  const v16f seed = cst[mt * 2 + h], dt = cst[NT * 2 + mt * 2 + h];
+  const int ngroups = (n_images + G - 1) / G;
+  uint4 pre[NPF];
+  auto fetch = [&](int grp) {
+    const int img0 = grp * G, lim = min(G, n_images - img0) * QWI;
+#pragma unroll
+    for (int j = 0; j < NPF; j++) {
+      const int d = tid + 256 * j;
+      pre[j] = d < lim ? in[(size_t)img0 * QWI + d] : make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+  if (blockIdx.x < ngroups) fetch(blockIdx.x);
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int img0 = grp * G, nimg = min(G, n_images - img0), nitems = nimg * IPI;
+    __syncthreads();  // the previous group's planes are no longer read
+#pragma unroll
+    for (int j = 0; j < NPF; j++) {  // one source uint4 (64 channels of a pixel: sign lo, hi, non-zero lo, hi) per iteration
+      const int d = tid + 256 * j;
+      if (d < nimg * QWI) {
+        const int i = d / QWI, e = d - i * QWI, pix = e / KH, cw = e % KH;
+        const uint4 v = pre[j];
+        plane[i][2 * cw][pix] = fp4_planes(lutz, luts, v.x, v.z);
+        plane[i][2 * cw + 1][pix] = fp4_planes(lutz, luts, v.y, v.w);
+      }
+    }
+    if (grp + (int)gridDim.x < ngroups) fetch(grp + gridDim.x);
+    __syncthreads();
+    for (int t0 = (wave / NT) * 32; t0 < nitems; t0 += 32 * STREAMS) {
+      const int item = min(t0 + c, nitems - 1);
+      const int i = item / IPI, rem = item - i * IPI, rp = rem / WOUT, x = rem - rp * WOUT;
+      v16f acc[2] = {seed, seed};  // output rows 2rp, 2rp + 1
+#pragma unroll
+      for (int kh = 0; kh < KH; kh++) {
+        const uint4 *__restrict__ P = &plane[i][kh * 2 + h][2 * rp * WIN + x];
+#pragma unroll
+        for (int kx = 0; kx < 3; kx++) {
+          v8i b[4];  // input rows 2rp .. 2rp + 3 at column x + kx
+#pragma unroll
+          for (int y = 0; y < 4; y++) {
+            const uint4 v = P[y * WIN + kx];
+            b[y] = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+          }
+#pragma unroll
+          for (int ky = 0; ky < 3; ky++)
+#pragma unroll
+            for (int dy = 0; dy < 2; dy++)
+              acc[dy] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wreg[(ky * 3 + kx) * KH + kh], b[ky + dy], acc[dy], 4, 4, 0,
+                                                                         0x7F7F7F7F, 0, 0x7F7F7F7F);
+        }
+      }
+      const bool valid = t0 + c < nitems;
+      const size_t img = (size_t)(img0 + i);
+      if constexpr (POOL) {
+        v16f top;
+#pragma unroll
+        for (int k = 0; k < 16; k++) top[k] = fmaxf(acc[0][k], acc[1][k]);
+        uint32_t n0, n1;
+        not_fired(top, dt, h, n0, n1);
+        n0 &= (uint32_t)__builtin_amdgcn_mov_dpp((int)n0, 0xB1, 0xF, 0xF, true);  // & lane c ^ 1
+        n1 &= (uint32_t)__builtin_amdgcn_mov_dpp((int)n1, 0xB1, 0xF, 0xF, true);
+        const size_t w64 = (img * (RP * RP) + rp * RP + (x >> 1)) * (NT / 2) + mt / 2;
+        if (valid && !(x & 1)) out[(w64 * 2 + h) * 2 + (mt & 1)] = h ? ~(n0 ^ n1) : (n0 & n1);
+      } else {
+        uint32_t n0[2], n1[2];
+#pragma unroll
+        for (int dy = 0; dy < 2; dy++) not_fired(acc[dy], dt, h, n0[dy], n1[dy]);
+        const uint32_t m0 = h ? n0[1] : n0[0], m1 = h ? n1[1] : n1[0];
+        const size_t w64 = (img * (WOUT * WOUT) + (2 * rp + h) * WOUT + x) * (NT / 2) + mt / 2;
+        if (valid) {
+          out[(w64 * 2 + 0) * 2 + (mt & 1)] = m0 & m1;
+          out[(w64 * 2 + 1) * 2 + (mt & 1)] = ~(m0 ^ m1);
+        }
+      }
+    }
+  }
+}
+
+// The operand tables of k_conv_mfma_a2 (kernels.h, conv_mfma_a2_table), made from the packed rows in HBM: one thread per
+// 16-byte weight entry [k step][neuron tile][lane], then one per seed and one per t1 - t0, each [tile][h][16].
+// TT: AR_TT rows {t0, t1, ksteps x {sign u64 (1 <=> negative), non-zero u64}, ksteps x "weight is -2" u64, flag, pad}
+// (packed_params.cpp; a -2 column is also set in both planes); else AR_TB rows {t0, t1, ksteps x u64, 1 <=> -1}.
+template <bool TT>
+__global__ __launch_bounds__(256) void k_conv_mfma_a2_table(const uint32_t *__restrict__ rows, int ksteps, int tiles,
+                                                             uint8_t *__restrict__ dst) {
+  const int idx = blockIdx.x * 256 + threadIdx.x, nw = ksteps * tiles * 64, row_dw = TT ? 4 + 6 * ksteps : 2 + 2 * ksteps;
+  if (idx < nw) {
+    const int ks = idx / (tiles * 64), mt = (idx / 64) % tiles, lane = idx & 63, n = 32 * mt + (lane & 31), h = lane >> 5;
+    const uint32_t *__restrict__ row = rows + (size_t)n * row_dw;
+    uint32_t b1, b2 = 0, b3;  // channels 32h .. 32h + 31 of k step ks: bits 1, 2, 3 of their nibbles
+    if constexpr (TT) {
+      const uint32_t sg = row[2 + 4 * ks + h], two = row[2 + 4 * ksteps + 2 * ks + h], nz = row[2 + 4 * ks + 2 + h] | two;
+      b1 = nz & ~two;         // +-1: 0x2 / 0xA
+      b2 = two;               // -2: 0xC
+      b3 = (sg & nz) | two;
+    } else {
+      b1 = 0xFFFFFFFFu;
+      b3 = row[2 + 2 * ks + h];
+    }
+    uint32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      v[k] = (nibble_spread(b1 >> (8 * k)) << 1) | (nibble_spread(b2 >> (8 * k)) << 2) | (nibble_spread(b3 >> (8 * k)) << 3);
+    reinterpret_cast<uint4 *>(dst)[idx] = make_uint4(v[0], v[1], v[2], v[3]);
+  } else if (idx < nw + tiles * 64) {
+    const int j = idx - nw, second = j >= tiles * 32, jj = second ? j - tiles * 32 : j, mt = jj >> 5, h = (jj >> 4) & 1, reg = jj & 15;
+    const int n = 32 * mt + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    // fire_i <=> t_i < d and |d| <= 2 * MW: a threshold outside [-2 MW - 1, 2 MW] decides like the nearer end of it
+    const int lim = 2 * 64 * ksteps;
+    int t0 = (int)rows[(size_t)n * row_dw], t1 = (int)rows[(size_t)n * row_dw + 1];
+    t0 = t0 < -lim - 1 ? -lim - 1 : (t0 > lim ? lim : t0);
+    t1 = t1 < -lim - 1 ? -lim - 1 : (t1 > lim ? lim : t1);
+    reinterpret_cast<float *>(dst + (size_t)nw * 16)[j] = second ? (float)(t1 - t0) : -(float)t0 - 0.5f;
   }
 }
 
@@ -2267,12 +2451,33 @@ inline long long l0_tile_min() {
 // tables (not under BNN_MI355X_CONV=valu, not in the fault-injection paths) -- measured (tools/batch_sweep.py, us per
 // batch, matrix vs XNOR-popcount forms): 512 images 62 vs 73, 1 024 78 vs 122, 4 096 165 vs 373, 16 384 553 vs 1 328
 // (profiles/r05_batch_sweep.txt; smaller batches not measured).  BNN_MI355X_CONV_MFMA_MIN overrides
+constexpr long long kConvMfmaMinW1A2 = 384, kConvMfmaMinW2A2 = 256;  // the 2-bit nets' edges: conv_mfma_a2_min() below
 inline long long conv_mfma_min() {
   static const long long v = [] {
     const char *e = std::getenv("BNN_MI355X_CONV_MFMA_MIN");
     return e ? std::atoll(e) : 512LL;
   }();
   return v;
+}
+// The same edge for the 2-bit nets (k_conv_mfma_a2), each its own -- measured (tools/batch_sweep.py cnvW1A2 / cnvW2A2 with
+// BNN_MI355X_CONV_MFMA_MIN=1 against BNN_MI355X_CONV=valu, 64 ... 16 384 images, profiles/r08_batch_sweep_a2.txt): the
+// smallest measured size from which the matrix forms win at every larger measured one.  us per batch, matrix vs
+// XNOR-popcount forms -- cnvW1A2: 256 images 66 vs 55, 384 71 vs 73, 512 74 vs 88, 16 384 677 vs 1 659; cnvW2A2: 128
+// images 68 vs 53, 256 73 vs 77, 512 84 vs 128, 16 384 744 vs 2 639.  BNN_MI355X_CONV_MFMA_MIN overrides
+template <int ARITH>
+inline long long conv_mfma_a2_min() {
+  static const long long v = [] {
+    const char *e = std::getenv("BNN_MI355X_CONV_MFMA_MIN");
+    return e ? std::atoll(e) : (ARITH == AR_TT ? kConvMfmaMinW2A2 : kConvMfmaMinW1A2);
+  }();
+  return v;
+}
+// the operand tables a batch of a.n images runs layers 1-3 from, or null: the XNOR-popcount kernels (too small a batch,
+// BNN_MI355X_CONV=valu, a fault-injection path).  run_cnv_t and cnv_matrix_stages both decide here
+template <int ARITH, bool OUT2>
+inline const uint8_t *conv_mfma_for(const CnvLaunch &a) {
+  if constexpr (ARITH == AR_XNOR && !OUT2) return a.n >= conv_mfma_min() ? a.conv_mfma : nullptr;
+  else return a.n >= conv_mfma_a2_min<ARITH>() ? a.conv_mfma : nullptr;
 }
 // persistent grid of the matrix forms: at most `cap` blocks (what stays resident on the 256 CUs), the `units` (image pairs
 // or groups) dealt evenly over them
@@ -2347,7 +2552,7 @@ void run_cnv_t(const CnvLaunch &a) {
     const bool pix = n <= kPixelLaneMax;
     // the matrix forms of layers 1-3 ("The matrix pipe"); the XNOR-popcount kernels below stay the path
     // for smaller batches, BNN_MI355X_CONV=valu and the fault-injection paths
-    const uint8_t *const cm = n >= conv_mfma_min() ? a.conv_mfma : nullptr;
+    const uint8_t *const cm = conv_mfma_for<ARITH, OUT2>(a);
     const dim3 g1(persistent_grid((n + kConvMfmaImgsL1 - 1) / kConvMfmaImgsL1, kConvMfmaGrid)),
         gm(persistent_grid((n + kConvMfmaImgs - 1) / kConvMfmaImgs, kConvMfmaGrid));
     if (a.last_stage >= 1) {
@@ -2392,18 +2597,26 @@ void run_cnv_t(const CnvLaunch &a) {
     BNN_MARK(a.events, 8, s);
   } else {
     const bool pix = n <= kPixelLaneMax;  // tiny batches: a lane per output pixel (see the XNOR branch)
+    // the matrix forms of layers 1-3, as in the XNOR branch (their tables encode -2 weights: the same kernels under TWO)
+    const uint8_t *const cm = conv_mfma_for<ARITH, OUT2>(a);
+    const uint4 *const A128 = reinterpret_cast<const uint4 *>(a.buf0), *const B128 = reinterpret_cast<const uint4 *>(a.buf1);
+    const dim3 g1(persistent_grid((n + kConvMfmaImgsL1 - 1) / kConvMfmaImgsL1, kConvMfmaGrid)),
+        gm(persistent_grid((n + kConvMfmaImgs - 1) / kConvMfmaImgs, kConvMfmaGrid));
     if (a.last_stage >= 1) {
-      if (pix) BNN_LAUNCH((k_vec<ARITH, 9, OUT2, true, 1, 30, 8, true, TWO>), grid_for(n * 784, 8), s, A64, B, a.rows[1], (int)(n * 784), 8, 1);
+      if (cm) hipLaunchKernelGGL((k_conv_mfma_a2<30, 2, 2, true, kConvMfmaImgsL1>), g1, dim3(256), 0, s, A128, B, cm, (int)n);
+      else if (pix) BNN_LAUNCH((k_vec<ARITH, 9, OUT2, true, 1, 30, 8, true, TWO>), grid_for(n * 784, 8), s, A64, B, a.rows[1], (int)(n * 784), 8, 1);
       else BNN_STAGE((k_quad<ARITH, 1, 30, true, OUT2, 32, TWO>), (k_quad<ARITH, 1, 30, true, OUT2, 8, TWO>), n * 196, 2, A64, B, a.rows[1]);
     }
     BNN_MARK(a.events, 2, s);
     if (a.last_stage >= 2) {
-      if (pix) BNN_LAUNCH((k_vec<ARITH, 9, OUT2, true, 1, 14, 8, false, TWO>), grid_for(n * 144, 16), s, B64, A, a.rows[2], (int)(n * 144), 16, 1);
+      if (cm) hipLaunchKernelGGL((k_conv_mfma_a2<14, 2, 4, false, kConvMfmaImgs>), gm, dim3(256), 0, s, B128, A, cm + kConvMfmaA2L2Off, (int)n);
+      else if (pix) BNN_LAUNCH((k_vec<ARITH, 9, OUT2, true, 1, 14, 8, false, TWO>), grid_for(n * 144, 16), s, B64, A, a.rows[2], (int)(n * 144), 16, 1);
       else BNN_STAGE((k_quad<ARITH, 1, 14, false, OUT2, 32, TWO>), (k_quad<ARITH, 1, 14, false, OUT2, 8, TWO>), n * 36, 4, B64, A, a.rows[2]);
     }
     BNN_MARK(a.events, 3, s);
     if (a.last_stage >= 3) {
-      if (pix) BNN_LAUNCH((k_vec<ARITH, 18, OUT2, true, 2, 12, 8, true, TWO>), grid_for(n * 100, 16), s, A64, B, a.rows[3], (int)(n * 100), 16, 1);
+      if (cm) hipLaunchKernelGGL((k_conv_mfma_a2<12, 4, 4, true, kConvMfmaImgs>), gm, dim3(256), 0, s, A128, B, cm + kConvMfmaA2L3Off, (int)n);
+      else if (pix) BNN_LAUNCH((k_vec<ARITH, 18, OUT2, true, 2, 12, 8, true, TWO>), grid_for(n * 100, 16), s, A64, B, a.rows[3], (int)(n * 100), 16, 1);
       else BNN_STAGE((k_quad<ARITH, 2, 12, true, OUT2, 32, TWO>), (k_quad<ARITH, 2, 12, true, OUT2, 8, TWO>), n * 25, 4, A64, B, a.rows[3]);
     }
     BNN_MARK(a.events, 4, s);
@@ -2428,6 +2641,15 @@ void run_cnv_t(const CnvLaunch &a) {
     else BNN_LAUNCH((k_fclast<ARITH, 8, TWO>), grid_for(n, 1), s, B64, a.scores, a.classes, a.rows[8], (int)n, a.number_class);
   }
   BNN_MARK(a.events, 9, s);
+}
+
+// which stages run_cnv_t<ARITH, OUT2> takes to the matrix pipe for `a` (kernels.h, cnv_matrix_stages)
+template <int ARITH, bool OUT2>
+int matrix_stages_t(const CnvLaunch &a) {
+  const bool cm = conv_mfma_for<ARITH, OUT2>(a) != nullptr;
+  bool l1 = cm;
+  if constexpr (ARITH == AR_XNOR && !OUT2) l1 = !a.l1_literal && (a.l1_mfma || cm);  // (the order of run_cnv_t's layer-1 branches)
+  return (a.l0_mfma ? 1 : 0) | (l1 ? 2 : 0) | (cm ? 12 : 0);
 }
 
 // One multi-run launch of a stage over the records of `a` (kernels.h, MultiLaunch): the 32-neuron staged form only,
@@ -2548,6 +2770,25 @@ hipError_t conv_mfma_table(const uint32_t *const rows[9], uint8_t *dst, hipStrea
                        p.tiles, 64 * p.ksteps, dst + p.off);
   }
   return hipGetLastError();
+}
+
+hipError_t conv_mfma_a2_table(NetId net, const uint32_t *const rows[9], uint8_t *dst, hipStream_t s) {
+  const struct { int layer, ksteps, tiles; size_t off; } part[3] = {{1, 9, 2, 0}, {2, 9, 4, kConvMfmaA2L2Off}, {3, 18, 4, kConvMfmaA2L3Off}};
+  for (const auto &p : part) {
+    const dim3 grid((unsigned)((p.ksteps * p.tiles * 64 + p.tiles * 64 + 255) / 256));
+    if (net == NET_CNVW2A2) hipLaunchKernelGGL(k_conv_mfma_a2_table<true>, grid, dim3(256), 0, s, rows[p.layer], p.ksteps, p.tiles, dst + p.off);
+    else hipLaunchKernelGGL(k_conv_mfma_a2_table<false>, grid, dim3(256), 0, s, rows[p.layer], p.ksteps, p.tiles, dst + p.off);
+  }
+  return hipGetLastError();
+}
+
+int cnv_matrix_stages(NetId net, const CnvLaunch &a) {
+  switch (net) {
+    case NET_CNVW1A1: return matrix_stages_t<AR_XNOR, false>(a);
+    case NET_CNVW1A2: return matrix_stages_t<AR_TB, true>(a);
+    case NET_CNVW2A2: return matrix_stages_t<AR_TT, true>(a);
+    default: return 0;
+  }
 }
 
 hipError_t run_cnv(NetId net, const CnvLaunch &a) {

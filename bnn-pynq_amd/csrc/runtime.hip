@@ -187,8 +187,8 @@ struct Runtime {
   const uint8_t *l0_mfma = nullptr;  // layer 0 as an MFMA operand (CNV nets), unless BNN_MI355X_L0=valu
   uint8_t *d_l1_mfma = nullptr;      // cnvW1A1, BNN_MI355X_L1=mfma only: layer 1 as FP4 MFMA operands (side experiment)
   bool l1_mfma = false, l1_literal = false;  // BNN_MI355X_L1=mfma / =lds (comparison figures, never the default)
-  // cnvW1A1 layers 1-3 as FP4 MFMA operands (kernels.h, conv_mfma_table), made on the device from the blob's rows whenever
-  // they change; null under BNN_MI355X_CONV=valu.  conv_xnor: the call in progress runs the XNOR-popcount kernels only.
+  // CNV layers 1-3 as FP4 MFMA operands (kernels.h, conv_mfma_table / conv_mfma_a2_table), made on the device from the blob's
+  // rows whenever they change; null under BNN_MI355X_CONV=valu.  conv_xnor: the call in progress runs the XNOR-popcount kernels only.
   uint8_t *d_conv_mfma = nullptr;
   bool conv_mfma = false, conv_xnor = false;
   bool warmed = false;  // warm_up() has run since the last deinit()
@@ -369,8 +369,9 @@ struct DrainOnFailure {
 int make_conv_tables(hipStream_t s) {
   Runtime &r = rt();
   if (!r.conv_mfma) return 0;
-  if (!r.d_conv_mfma) HIP_OK(hipMalloc(reinterpret_cast<void **>(&r.d_conv_mfma), kConvMfmaBytes));
-  HIP_OK(conv_mfma_table(r.rows, r.d_conv_mfma, s));
+  const bool a2 = r.spec.id != NET_CNVW1A1;  // cnvW1A2, cnvW2A2: two planes in, two thresholds
+  if (!r.d_conv_mfma) HIP_OK(hipMalloc(reinterpret_cast<void **>(&r.d_conv_mfma), a2 ? kConvMfmaA2Bytes : kConvMfmaBytes));
+  HIP_OK(a2 ? conv_mfma_a2_table(r.spec.id, r.rows, r.d_conv_mfma, s) : conv_mfma_table(r.rows, r.d_conv_mfma, s));
   HIP_OK(hipStreamSynchronize(s));  // (the second compute lane reads them too)
   return 0;
 }
@@ -403,7 +404,7 @@ int upload_blob() {
     HIP_OK(hipMemcpy(r.d_l1_mfma, tab.data(), kL1MfmaBytes, hipMemcpyHostToDevice));
   }
   const char *cv = std::getenv("BNN_MI355X_CONV");
-  r.conv_mfma = r.spec.id == NET_CNVW1A1 && !(cv && std::strcmp(cv, "valu") == 0);
+  r.conv_mfma = r.spec.is_cnv && !(cv && std::strcmp(cv, "valu") == 0);
   return make_conv_tables(r.stream);
 }
 
@@ -687,6 +688,16 @@ int settle_handover(hipStream_t s) {
 
 // enqueue one chunk (n <= cap) whose images are already in HBM
 // t0 / t1 (optional): this chunk's device time is t0 -> t1 (kernels.h)
+// the kernel forms a CNV batch may take with the parameters and switches now in force (run_cnv picks among them by size)
+void set_forms(CnvLaunch &a) {
+  Runtime &r = rt();
+  a.l0_mfma = r.l0_mfma;
+  a.l1_mfma = r.l1_mfma ? r.d_l1_mfma : nullptr;
+  a.l1_literal = r.l1_literal;
+  a.conv_mfma = r.conv_mfma && !r.conv_xnor ? r.d_conv_mfma : nullptr;
+  a.has_two = r.two_rows > 0;
+}
+
 int enqueue(const uint8_t *d_imgs, int n, int ncls, int32_t *d_classes, int16_t *d_scores, uint64_t *d_words,
             hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, int lane = 0, bool t_dispatch = false, bool packed = false,
             unsigned *done_flag = nullptr, unsigned done_seq = 0) {
@@ -710,11 +721,7 @@ int enqueue(const uint8_t *d_imgs, int n, int ncls, int32_t *d_classes, int16_t 
     CnvLaunch a{};
     a.images = d_imgs; a.n = n; a.buf0 = ws0; a.buf1 = ws1;
     for (int l = 0; l < 9; l++) a.rows[l] = r.rows[l];
-    a.l0_mfma = r.l0_mfma;
-    a.l1_mfma = r.l1_mfma ? r.d_l1_mfma : nullptr;
-    a.l1_literal = r.l1_literal;
-    a.conv_mfma = r.conv_mfma && !r.conv_xnor ? r.d_conv_mfma : nullptr;
-    a.has_two = r.two_rows > 0;
+    set_forms(a);
     a.scores = d_scores; a.classes = d_classes; a.number_class = ncls; a.stream = s; a.events = evs;
     a.last_stage = r.debug_last_stage >= 0 ? r.debug_last_stage : kCnvStages - 1;
     a.t0 = t0; a.t1 = t1; a.done_flag = done_flag; a.done_seq = done_seq;
@@ -2782,6 +2789,16 @@ int bnn_mi355x_debug_lfc_wstamps(unsigned long long *dst) {
   return bnn::lfc_wstamps_read(dst) == hipSuccess ? 0 : -1;
 }
 #endif
+
+int bnn_mi355x_matrix_stages(int n_images) {
+  Runtime &r = rt();
+  if (!r.d_blob) return -1;
+  if (!r.spec.is_cnv || n_images <= 0) return 0;
+  CnvLaunch a{};
+  a.n = n_images;
+  set_forms(a);
+  return cnv_matrix_stages(r.spec.id, a);
+}
 
 int bnn_mi355x_chunk_plan(int n_images, int from_file, int *bases, int cap) {
   if (n_images < 0) return fail("chunk_plan: bad arguments");

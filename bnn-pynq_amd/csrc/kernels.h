@@ -15,7 +15,7 @@ struct CnvLaunch {
   const uint8_t *l0_mfma;     // device, layer-0 MFMA table (packed_params.h); null: integer-pipe k_conv0
   const uint8_t *l1_mfma;     // device, cnvW1A1 layer 1 as FP4 MFMA operands (l1_mfma_table); null: the XNOR-popcount kernel.
                               // Side experiment only (BNN_MI355X_L1=mfma): never the default path.
-  const uint8_t *conv_mfma;   // device, layers 1-3 as FP4 MFMA operands (cnvW1A1: conv_mfma_table, the 2-bit nets:
+  const uint8_t *conv_mfma;   // device, layers 1-7 as FP4 MFMA operands (cnvW1A1: conv_mfma_table, the 2-bit nets:
                               // conv_mfma_a2_table); null: the XNOR-popcount kernels only (BNN_MI355X_CONV=valu, and the
                               // fault-injection paths)
   bool l1_literal;            // cnvW1A1, BNN_MI355X_L1=lds: layer 1 in the north-star's literal formulation (comparison figure only)
@@ -82,15 +82,21 @@ void l1_mfma_table(const uint32_t *rows, uint8_t *dst);
 // block; lane (r, h) holds channels 32h..32h+31 of the step for neuron 32 * tile + r), then the seeds [tile][h][16]
 // floats -(theta + 1).  Layer 1's table is laid out as l1_mfma_table's.  Made on the device from the packed rows.
 constexpr size_t kConvMfmaL2Off = kL1MfmaBytes, kConvMfmaL3Off = kConvMfmaL2Off + 9 * 4 * 64 * 16 + 4 * 32 * 4,
-                 kConvMfmaBytes = kConvMfmaL3Off + 18 * 4 * 64 * 16 + 4 * 32 * 4;
-// rows: device pointers to cnvW1A1's packed layers (rows[1..3] are read); enqueued on s
+                 kTailMfmaL4Off = kConvMfmaL3Off + 18 * 4 * 64 * 16 + 4 * 32 * 4;
+// ... and layers 4-7 (k_tail_mfma, from tail_mfma_min() images on) behind them, in the same form: k step = the layer's ks-th
+// 64 inputs (layer 4: tap * 2 + 64-channel block; layers 5-7: the image's ks-th 64 bits), 8 / 8 / 16 / 16 neuron tiles
+constexpr size_t kTailMfmaL5Off = kTailMfmaL4Off + 18 * 8 * 64 * 16 + 8 * 32 * 4, kTailMfmaL6Off = kTailMfmaL5Off + 36 * 8 * 64 * 16 + 8 * 32 * 4,
+                 kTailMfmaL7Off = kTailMfmaL6Off + 4 * 16 * 64 * 16 + 16 * 32 * 4, kConvMfmaBytes = kTailMfmaL7Off + 8 * 16 * 64 * 16 + 16 * 32 * 4;
+// rows: device pointers to cnvW1A1's packed layers (rows[1..7] are read); enqueued on s
 hipError_t conv_mfma_table(const uint32_t *const rows[9], uint8_t *dst, hipStream_t s);
 
 // The same for cnvW1A2 and cnvW2A2 (k_conv_mfma_a2): per layer the weights [k step][neuron tile][lane][16 bytes] (FP4 -1, 0,
 // +1, and -2 where cnvW2A2's row marks it), then the seeds [tile][h][16] floats -(t0 + 1/2), then [tile][h][16] floats t1 - t0.
 constexpr size_t kConvMfmaA2L2Off = 9 * 2 * 64 * 16 + 2 * 64 * 4, kConvMfmaA2L3Off = kConvMfmaA2L2Off + 9 * 4 * 64 * 16 + 4 * 64 * 4,
-                 kConvMfmaA2Bytes = kConvMfmaA2L3Off + 18 * 4 * 64 * 16 + 4 * 64 * 4;
-// rows: device pointers to the net's packed layers (rows[1..3] are read: AR_TB rows for cnvW1A2, AR_TT for cnvW2A2)
+                 kTailMfmaA2L4Off = kConvMfmaA2L3Off + 18 * 4 * 64 * 16 + 4 * 64 * 4;
+constexpr size_t kTailMfmaA2L5Off = kTailMfmaA2L4Off + 18 * 8 * 64 * 16 + 8 * 64 * 4, kTailMfmaA2L6Off = kTailMfmaA2L5Off + 36 * 8 * 64 * 16 + 8 * 64 * 4,
+                 kTailMfmaA2L7Off = kTailMfmaA2L6Off + 4 * 16 * 64 * 16 + 16 * 64 * 4, kConvMfmaA2Bytes = kTailMfmaA2L7Off + 8 * 16 * 64 * 16 + 16 * 64 * 4;
+// rows: device pointers to the net's packed layers (rows[1..7] are read: AR_TB rows for cnvW1A2, AR_TT for cnvW2A2)
 hipError_t conv_mfma_a2_table(NetId net, const uint32_t *const rows[9], uint8_t *dst, hipStream_t s);
 
 // bit k set: stage k of run_cnv(net, a) runs on the matrix pipe (layer 0's MFMA forms count).  Decided by the code that

@@ -24,8 +24,8 @@
 //     stored once: outputs are already in the bit-packed layout the next stage
 //     reads.  Max-pool is a min/max over the quad's 4 accumulators before the
 //     threshold compare (thresholding is monotone), so it is free.
-//   * No MFMA in the bitwise layers, except layers 1-3 of the three CNV nets on the throughput path (k_conv_mfma,
-//     k_conv_mfma_a2: exact FP4 implicit GEMMs, DESIGN.md 5 "The matrix pipe").  No LDS in the XNOR-popcount throughput kernels: there is no data shared
+//   * No MFMA in the bitwise layers, except layers 1-7 of the three CNV nets on the throughput path (k_conv_mfma,
+//     k_conv_mfma_a2, k_tail_mfma: exact FP4 implicit GEMMs, DESIGN.md 5 "The matrix pipe").  No LDS in the XNOR-popcount throughput kernels: there is no data shared
 //     between lanes that the scalar path does not already broadcast for free.  The exceptions,
 //     each argued where it is defined: the int8 first layer runs on the matrix pipe
 //     (k_conv0_mfma); small batches, where a lane per item leaves the chip empty, use a lane
@@ -1002,6 +1002,136 @@ __global__ __launch_bounds__(256) void k_conv_mfma_a2_table(const uint32_t *__re
     t0 = t0 < -lim - 1 ? -lim - 1 : (t0 > lim ? lim : t0);
     t1 = t1 < -lim - 1 ? -lim - 1 : (t1 > lim ? lim : t1);
     reinterpret_cast<float *>(dst + (size_t)nw * 16)[j] = second ? (float)(t1 - t0) : -(float)t0 - 0.5f;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// CNV layers 4-7 of the three nets on the matrix pipe: the throughput path from tail_mfma_min() images on (DESIGN.md 5,
+// "The matrix pipe").  The arithmetic, the FP4 encodings, the seeds and the decisions are those of k_conv_mfma (A2 =
+// false: cnvW1A1) and k_conv_mfma_a2 (A2 = true: cnvW1A2, cnvW2A2); the tables come from the same table kernels.  What
+// differs is the tiling: these layers have few work items per image, so a tile's 32 lanes run across images.
+//   * CONV (layer 4, 5x5x128 -> 3x3x256, no pool): work item = (image, output pixel), 9 per image, numbered over the
+//     block's G images, 32 consecutive items per tile.  K step ks = tap * 2 + 64-channel block.  LDS planes
+//     [image][32-channel block q][pixel] x 16 bytes, as k_conv_mfma's.
+//   * else (layer 5 = a dense layer over the image's 2304 contiguous HWC bits, layers 6 and 7): work item = image.
+//     K step ks = the image's ks-th 64 bits.  LDS planes [32-bit block q = 2 ks + h][image] x 16 bytes, rows padded by
+//     one entry so that the expansion's writes (consecutive threads = consecutive q) spread over the banks; lane (c, h)
+//     reads entry c of row 2 ks + h: consecutive lanes, consecutive 16 bytes.
+//   * A block takes G images at a time, expands them once into the planes (the next group's words are requested into
+//     registers before this group's MFMAs are issued) and every wave walks all the group's item tiles.  A wave owns
+//     NT / WAVES neuron tiles for the whole kernel, their FP4 weights in VGPRs (4 per tile and k step); one ds_read_b128
+//     per k step feeds the MFMAs of all its tiles.  Seeds (and t1 - t0) are read from LDS at the start of every tile.
+//   * Exactness: |d| <= K <= 2304 (1-bit), <= 2 K (2-bit nets with -2 weights); seeds, partial sums and t1 - t0 are
+//     multiples of 1/2 below 2^14: f32 accumulation is exact in any order, as for layers 1-3.
+// Items past the last image repeat the last valid one (their results are dropped).  Outputs are k_vec_x's / k_vec's
+// words, byte for byte: 1-bit [item][NT] dwords, 2-bit [item][NT / 2][plane] u64.
+// ---------------------------------------------------------------------------
+// KS: k steps (K / 64), NT: neuron tiles, WAVES: waves per block, G: images per block and group.
+template <bool A2, int KS, int NT, bool CONV, int WAVES, int G>
+__global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void k_tail_mfma(const std::conditional_t<A2, uint4, uint32_t> *__restrict__ in,
+                                                                      uint32_t *__restrict__ out, const uint8_t *__restrict__ tab,
+                                                                      int n_images) {
+  using U = std::conditional_t<A2, uint4, uint32_t>;  // source unit: 64 channels in two planes, or 32 channels
+  constexpr int T = 64 * WAVES, TPW = NT / WAVES, IPI = CONV ? 9 : 1, W64 = CONV ? 25 * 2 : KS, UPI = A2 ? W64 : 2 * W64;
+  constexpr int GP = G + 1, NPL = CONV ? G * 4 * 25 : 2 * KS * GP, NPF = (G * UPI + T - 1) / T, NC = (A2 ? 2 : 1) * NT * 2;
+  static_assert(NT % WAVES == 0 && (!CONV || KS == 18) && (G * IPI) % 32 == 0, "tile geometry");
+  __shared__ uint4 plane[NPL];
+  __shared__ uint32_t lut[A2 ? 512 : 256];  // A2: lutz, then luts (fp4_planes)
+  __shared__ v16f cst[NC];                  // seeds [tile][h], then (A2) t1 - t0 [tile][h]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mt0 = wave * TPW, c = lane & 31, h = lane >> 5;
+  for (int k = tid; k < 256; k += T) {
+    if constexpr (A2) {
+      lut[k] = nibble_spread((uint32_t)k) << 1;
+      lut[256 + k] = nibble_spread((uint32_t)k) << 3;
+    } else {
+      lut[k] = fp4_pm1((uint32_t)k);
+    }
+  }
+  for (int k = tid; k < NC * 16; k += T) reinterpret_cast<float *>(cst)[k] = reinterpret_cast<const float *>(tab + (size_t)KS * NT * 64 * 16)[k];
+  // weights [k step][neuron tile][lane] x 16 bytes
+  const uint4 *__restrict__ wt = reinterpret_cast<const uint4 *>(tab);
+  v8i wreg[TPW][KS];
+#pragma unroll
+  for (int j = 0; j < TPW; j++)
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++) {
+      const uint4 v = wt[(ks * NT + mt0 + j) * 64 + lane];
+      wreg[j][ks] = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+    }
+  const int ngroups = (n_images + G - 1) / G;
+  U pre[NPF];
+  auto fetch = [&](int grp) {
+    const int img0 = grp * G, lim = min(G, n_images - img0) * UPI;
+#pragma unroll
+    for (int j = 0; j < NPF; j++) {
+      const int d = tid + T * j;
+      pre[j] = d < lim ? in[(size_t)img0 * UPI + d] : U{};
+    }
+  };
+  if (blockIdx.x < ngroups) fetch(blockIdx.x);
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int img0 = grp * G, nimg = min(G, n_images - img0), nitems = nimg * IPI;
+    __syncthreads();  // the previous group's planes are no longer read (first pass: lut and cst are written)
+#pragma unroll
+    for (int j = 0; j < NPF; j++) {
+      const int d = tid + T * j;
+      if (d < nimg * UPI) {
+        const int i = d / UPI, e = d - i * UPI;
+        if constexpr (A2) {  // one source uint4: sign lo, hi, non-zero lo, hi of 64 channels
+          const uint4 v = pre[j];
+          const int p0 = CONV ? (i * 4 + 2 * (e & 1)) * 25 + (e >> 1) : 2 * e * GP + i, step = CONV ? 25 : GP;
+          plane[p0] = fp4_planes(lut, lut + 256, v.x, v.z);
+          plane[p0 + step] = fp4_planes(lut, lut + 256, v.y, v.w);
+        } else {  // one source dword: 32 channels
+          const uint32_t bits = pre[j];
+          const int p0 = CONV ? (i * 4 + (e & 3)) * 25 + (e >> 2) : e * GP + i;
+          plane[p0] = make_uint4(lut[bits & 255], lut[(bits >> 8) & 255], lut[(bits >> 16) & 255], lut[bits >> 24]);
+        }
+      }
+    }
+    if (grp + (int)gridDim.x < ngroups) fetch(grp + gridDim.x);
+    __syncthreads();
+#pragma unroll 1
+    for (int t0 = 0; t0 < nitems; t0 += 32) {
+      const int item = min(t0 + c, nitems - 1);
+      int base;
+      if constexpr (CONV) {
+        const int i = item / 9, p = item - i * 9, oy = p / 3, ox = p - oy * 3;
+        base = (i * 4 + h) * 25 + oy * 5 + ox;
+      } else {
+        base = h * GP + item;
+      }
+      v16f acc[TPW];
+#pragma unroll
+      for (int j = 0; j < TPW; j++) acc[j] = cst[(mt0 + j) * 2 + h];
+#pragma unroll
+      for (int ks = 0; ks < KS; ks++) {
+        const int off = CONV ? (ks & 1) * 2 * 25 + ((ks >> 1) / 3) * 5 + (ks >> 1) % 3 : ks * 2 * GP;
+        const uint4 v = plane[base + off];
+        const v8i b = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < TPW; j++)
+          acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wreg[j][ks], b, acc[j], 4, 4, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+      }
+      const bool valid = t0 + c < nitems;
+      const size_t gitem = (size_t)img0 * IPI + item;
+#pragma unroll
+      for (int j = 0; j < TPW; j++) {
+        const int mt = mt0 + j;
+        if constexpr (A2) {
+          uint32_t n0, n1;
+          not_fired(acc[j], cst[NT * 2 + mt * 2 + h], h, n0, n1);
+          const size_t w64 = gitem * (NT / 2) + mt / 2;  // lane half h stores plane h
+          if (valid) out[(w64 * 2 + h) * 2 + (mt & 1)] = h ? ~(n0 ^ n1) : (n0 & n1);
+        } else {
+          int v[16];
+#pragma unroll
+          for (int k = 0; k < 16; k++) v[k] = __float_as_int(acc[j][k]);
+          const uint32_t nf = or_halves(sign_nibbles(v, h));
+          if (valid && h == (j & 1)) out[gitem * NT + mt] = ~nf;
+        }
+      }
+    }
   }
 }
 
@@ -2479,6 +2609,32 @@ inline const uint8_t *conv_mfma_for(const CnvLaunch &a) {
   if constexpr (ARITH == AR_XNOR && !OUT2) return a.n >= conv_mfma_min() ? a.conv_mfma : nullptr;
   else return a.n >= conv_mfma_a2_min<ARITH>() ? a.conv_mfma : nullptr;
 }
+// images: from here on layers 4-7 run on the matrix pipe (k_tail_mfma) when the runtime has made the operand tables -- each
+// net its own edge, measured (tools/batch_sweep.py with BNN_MI355X_TAIL_MFMA_MIN=1 against =200000, 64 ... 16 384 images,
+// profiles/r09_batch_sweep_l47.txt): the smallest measured size from which the matrix forms win at every larger measured
+// one.  us per batch, matrix vs integer-pipe forms of layers 4-7 (below 1 025 images the latter is the one-launch k_cnv_tail*)
+// -- cnvW1A1: 2 048 images 111 vs 108, 3 072 141 vs 144, 4 096 159 vs 165, 16 384 514 vs 553; cnvW1A2: 2 048 136 vs 135,
+// 3 072 173 vs 181, 4 096 197 vs 210, 16 384 601 vs 673; cnvW2A2: 768 107 vs 106, 1 024 111 vs 117, 1 025 118 vs 136,
+// 16 384 606 vs 741.  BNN_MI355X_TAIL_MFMA_MIN overrides (above 131 072: the forms are off; layers 1-3 are not touched)
+constexpr long long kTailMfmaMinW1A1 = 3072, kTailMfmaMinW1A2 = 3072, kTailMfmaMinW2A2 = 1024;
+constexpr int kTailMfmaStages = 0xF0;  // the stages that have a matrix form the policy may pick (bit k: stage k)
+template <int ARITH>
+inline long long tail_mfma_min() {
+  static const long long v = [] {
+    const char *e = std::getenv("BNN_MI355X_TAIL_MFMA_MIN");
+    return e ? std::atoll(e) : (ARITH == AR_XNOR ? kTailMfmaMinW1A1 : ARITH == AR_TB ? kTailMfmaMinW1A2 : kTailMfmaMinW2A2);
+  }();
+  return v;
+}
+// the operand tables a batch of a.n images runs layers 4-7 from, or null: the integer-pipe kernels (too small a batch,
+// BNN_MI355X_CONV=valu, a fault-injection path, or the single-image call that carries a completion word, which only
+// k_cnv_tail* sets).  Non-null at or below kCnvTailMax, the matrix forms take precedence over k_cnv_tail*.  run_cnv_t and
+// cnv_matrix_stages both decide here
+template <int ARITH>
+inline const uint8_t *tail_mfma_for(const CnvLaunch &a) {
+  if (a.done_flag && a.n == 1) return nullptr;
+  return a.n >= tail_mfma_min<ARITH>() ? a.conv_mfma : nullptr;
+}
 // persistent grid of the matrix forms: at most `cap` blocks (what stays resident on the 256 CUs), the `units` (image pairs
 // or groups) dealt evenly over them
 inline unsigned persistent_grid(long long units, long long cap) {
@@ -2487,6 +2643,14 @@ inline unsigned persistent_grid(long long units, long long cap) {
 }
 constexpr long long kConvMfmaGrid = 512;  // 2 blocks per CU (VGPRs; LDS 59 / 51 / 75 KB per block)
 constexpr int kConvMfmaImgsL1 = 2, kConvMfmaImgs = 8;  // images per block and group: layer 1, layers 2 and 3
+// layers 4-7 (k_tail_mfma): images per block and group, and the blocks that stay resident: layers 4, 5 and 7 run 8 waves
+// per block, one block per CU (up to 256 VGPRs a wave: layer 5 keeps 144 of weights); layer 6 runs 4 waves, two blocks
+constexpr int kTailMfmaImgsL4 = 32, kTailMfmaImgsL5 = 32, kTailMfmaImgsFc = 128;
+constexpr long long kTailMfmaGrid8 = 256;
+// one stage of layers 4-7 on the matrix pipe: layer L of KS k steps and NT neuron tiles, table at `off`
+#define BNN_TAIL_MFMA(A2, KS, NT, CONV, WAVES, G, cap, in, out, tab)                                                               \
+  hipLaunchKernelGGL((k_tail_mfma<A2, KS, NT, CONV, WAVES, G>), dim3(persistent_grid((n + (G) - 1) / (G), (cap))), dim3(64 * (WAVES)), 0, s, \
+                     in, out, tab, (int)n)
 
 // neuron groups per block: all of them once the work items alone fill the chip (256 CUs x 8 blocks),
 // so that a lane writes whole output words and reads its window once; otherwise one (parallelism first)
@@ -2581,19 +2745,34 @@ void run_cnv_t(const CnvLaunch &a) {
       else BNN_STAGE((k_quad_x<2, 12, true>), (k_quad_x<2, 12, true, 8>), n * 25, 4, A64, B, a.rows[3]);
     }
     BNN_MARK(a.events, 4, s);
-    if (n <= kCnvTailMax && !a.events && a.last_stage >= kCnvStages - 1) {
+    // the matrix forms of layers 4-7; from their edge on they go before the one-launch tail too
+    const uint8_t *const tm = tail_mfma_for<ARITH>(a);
+    const uint32_t *const A32 = A, *const B32 = B;
+    if (!tm && n <= kCnvTailMax && !a.events && a.last_stage >= kCnvStages - 1) {
       // small batch: layers 4..8 as one launch (no per-stage events there: there are no stages)
       hipLaunchKernelGGL(k_cnv_tail, dim3((unsigned)n), dim3(512), 0, s, B64, a.scores, a.classes, a.rows[4], a.rows[5], a.rows[6],
                          a.rows[7], a.rows[8], a.number_class, n == 1 ? a.done_flag : nullptr, a.done_seq);
       return;
     }
-    if (a.last_stage >= 4) BNN_STAGE((k_vec_x<18, true, 2, 5>), (k_vec_x<18, true, 2, 5, 8>), n * 9, 8, B64, A, a.rows[4]);
+    if (a.last_stage >= 4) {
+      if (tm && (kTailMfmaStages & 16)) BNN_TAIL_MFMA(false, 18, 8, true, 8, kTailMfmaImgsL4, kTailMfmaGrid8, B32, A, tm + kTailMfmaL4Off);
+      else BNN_STAGE((k_vec_x<18, true, 2, 5>), (k_vec_x<18, true, 2, 5, 8>), n * 9, 8, B64, A, a.rows[4]);
+    }
     BNN_MARK(a.events, 5, s);
-    if (a.last_stage >= 5) BNN_STAGE((k_vec_x<36, false, 1, 1>), (k_vec_x<36, false, 1, 1, 8>), n, 8, A64, B, a.rows[5]);
+    if (a.last_stage >= 5) {
+      if (tm && (kTailMfmaStages & 32)) BNN_TAIL_MFMA(false, 36, 8, false, 8, kTailMfmaImgsL5, kTailMfmaGrid8, A32, B, tm + kTailMfmaL5Off);
+      else BNN_STAGE((k_vec_x<36, false, 1, 1>), (k_vec_x<36, false, 1, 1, 8>), n, 8, A64, B, a.rows[5]);
+    }
     BNN_MARK(a.events, 6, s);
-    if (a.last_stage >= 6) BNN_STAGE((k_vec_x<4, false, 1, 1>), (k_vec_x<4, false, 1, 1, 8>), n, 16, B64, A, a.rows[6]);
+    if (a.last_stage >= 6) {
+      if (tm && (kTailMfmaStages & 64)) BNN_TAIL_MFMA(false, 4, 16, false, 4, kTailMfmaImgsFc, kConvMfmaGrid, B32, A, tm + kTailMfmaL6Off);
+      else BNN_STAGE((k_vec_x<4, false, 1, 1>), (k_vec_x<4, false, 1, 1, 8>), n, 16, B64, A, a.rows[6]);
+    }
     BNN_MARK(a.events, 7, s);
-    if (a.last_stage >= 7) BNN_STAGE((k_vec_x<8, false, 1, 1>), (k_vec_x<8, false, 1, 1, 8>), n, 16, A64, B, a.rows[7]);
+    if (a.last_stage >= 7) {
+      if (tm && (kTailMfmaStages & 128)) BNN_TAIL_MFMA(false, 8, 16, false, 8, kTailMfmaImgsFc, kTailMfmaGrid8, A32, B, tm + kTailMfmaL7Off);
+      else BNN_STAGE((k_vec_x<8, false, 1, 1>), (k_vec_x<8, false, 1, 1, 8>), n, 16, A64, B, a.rows[7]);
+    }
     BNN_MARK(a.events, 8, s);
   } else {
     const bool pix = n <= kPixelLaneMax;  // tiny batches: a lane per output pixel (see the XNOR branch)
@@ -2620,20 +2799,34 @@ void run_cnv_t(const CnvLaunch &a) {
       else BNN_STAGE((k_quad<ARITH, 2, 12, true, OUT2, 32, TWO>), (k_quad<ARITH, 2, 12, true, OUT2, 8, TWO>), n * 25, 4, A64, B, a.rows[3]);
     }
     BNN_MARK(a.events, 4, s);
+    // the matrix forms of layers 4-7, as in the XNOR branch
+    const uint8_t *const tm = tail_mfma_for<ARITH>(a);
     if constexpr (!TWO) {  // (the -2-aware variant of this kernel would spill: such runs take the staged layers)
-      if (n <= kCnvTailMax && !a.events && a.last_stage >= kCnvStages - 1) {
+      if (!tm && n <= kCnvTailMax && !a.events && a.last_stage >= kCnvStages - 1) {
         hipLaunchKernelGGL((k_cnv_tail_a2<ARITH>), dim3((unsigned)n), dim3(512), 0, s, B64, a.scores, a.classes, a.rows[4], a.rows[5],
                            a.rows[6], a.rows[7], a.rows[8], a.number_class, n == 1 ? a.done_flag : nullptr, a.done_seq);
         return;
       }
     }
-    if (a.last_stage >= 4) BNN_STAGE((k_vec<ARITH, 18, OUT2, true, 2, 5, 32, false, TWO>), (k_vec<ARITH, 18, OUT2, true, 2, 5, 8, false, TWO>), n * 9, 8, B64, A, a.rows[4]);
+    if (a.last_stage >= 4) {
+      if (tm && (kTailMfmaStages & 16)) BNN_TAIL_MFMA(true, 18, 8, true, 8, kTailMfmaImgsL4, kTailMfmaGrid8, B128, A, tm + kTailMfmaA2L4Off);
+      else BNN_STAGE((k_vec<ARITH, 18, OUT2, true, 2, 5, 32, false, TWO>), (k_vec<ARITH, 18, OUT2, true, 2, 5, 8, false, TWO>), n * 9, 8, B64, A, a.rows[4]);
+    }
     BNN_MARK(a.events, 5, s);
-    if (a.last_stage >= 5) BNN_STAGE((k_vec<ARITH, 36, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 36, OUT2, false, 1, 1, 8, false, TWO>), n, 8, A64, B, a.rows[5]);
+    if (a.last_stage >= 5) {
+      if (tm && (kTailMfmaStages & 32)) BNN_TAIL_MFMA(true, 36, 8, false, 8, kTailMfmaImgsL5, kTailMfmaGrid8, A128, B, tm + kTailMfmaA2L5Off);
+      else BNN_STAGE((k_vec<ARITH, 36, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 36, OUT2, false, 1, 1, 8, false, TWO>), n, 8, A64, B, a.rows[5]);
+    }
     BNN_MARK(a.events, 6, s);
-    if (a.last_stage >= 6) BNN_STAGE((k_vec<ARITH, 4, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 4, OUT2, false, 1, 1, 8, false, TWO>), n, 16, B64, A, a.rows[6]);
+    if (a.last_stage >= 6) {
+      if (tm && (kTailMfmaStages & 64)) BNN_TAIL_MFMA(true, 4, 16, false, 4, kTailMfmaImgsFc, kConvMfmaGrid, B128, A, tm + kTailMfmaA2L6Off);
+      else BNN_STAGE((k_vec<ARITH, 4, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 4, OUT2, false, 1, 1, 8, false, TWO>), n, 16, B64, A, a.rows[6]);
+    }
     BNN_MARK(a.events, 7, s);
-    if (a.last_stage >= 7) BNN_STAGE((k_vec<ARITH, 8, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 8, OUT2, false, 1, 1, 8, false, TWO>), n, 16, A64, B, a.rows[7]);
+    if (a.last_stage >= 7) {
+      if (tm && (kTailMfmaStages & 128)) BNN_TAIL_MFMA(true, 8, 16, false, 8, kTailMfmaImgsFc, kTailMfmaGrid8, A128, B, tm + kTailMfmaA2L7Off);
+      else BNN_STAGE((k_vec<ARITH, 8, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 8, OUT2, false, 1, 1, 8, false, TWO>), n, 16, A64, B, a.rows[7]);
+    }
     BNN_MARK(a.events, 8, s);
   }
   if (a.last_stage >= 8) {
@@ -2649,7 +2842,7 @@ int matrix_stages_t(const CnvLaunch &a) {
   const bool cm = conv_mfma_for<ARITH, OUT2>(a) != nullptr;
   bool l1 = cm;
   if constexpr (ARITH == AR_XNOR && !OUT2) l1 = !a.l1_literal && (a.l1_mfma || cm);  // (the order of run_cnv_t's layer-1 branches)
-  return (a.l0_mfma ? 1 : 0) | (l1 ? 2 : 0) | (cm ? 12 : 0);
+  return (a.l0_mfma ? 1 : 0) | (l1 ? 2 : 0) | (cm ? 12 : 0) | (tail_mfma_for<ARITH>(a) ? kTailMfmaStages : 0);
 }
 
 // One multi-run launch of a stage over the records of `a` (kernels.h, MultiLaunch): the 32-neuron staged form only,
@@ -2762,8 +2955,9 @@ void l1_mfma_table(const uint32_t *rows, uint8_t *dst) {
 }
 
 hipError_t conv_mfma_table(const uint32_t *const rows[9], uint8_t *dst, hipStream_t s) {
-  // layer: rows, k steps (taps x 64-channel blocks), table offset; 128 neurons in layers 2 and 3, 64 in layer 1
-  const struct { int layer, ksteps, tiles; size_t off; } part[3] = {{1, 9, 2, 0}, {2, 9, 4, kConvMfmaL2Off}, {3, 18, 4, kConvMfmaL3Off}};
+  // layer: rows, k steps (K / 64: taps x 64-channel blocks), neuron tiles, table offset
+  const struct { int layer, ksteps, tiles; size_t off; } part[7] = {{1, 9, 2, 0},  {2, 9, 4, kConvMfmaL2Off},  {3, 18, 4, kConvMfmaL3Off}, {4, 18, 8, kTailMfmaL4Off},
+                                                                   {5, 36, 8, kTailMfmaL5Off}, {6, 4, 16, kTailMfmaL6Off}, {7, 8, 16, kTailMfmaL7Off}};
   for (const auto &p : part) {
     const int entries = p.ksteps * p.tiles * 64 + p.tiles * 32;
     hipLaunchKernelGGL(k_conv_mfma_table, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, rows[p.layer], 2 + 2 * p.ksteps, p.ksteps,
@@ -2773,7 +2967,8 @@ hipError_t conv_mfma_table(const uint32_t *const rows[9], uint8_t *dst, hipStrea
 }
 
 hipError_t conv_mfma_a2_table(NetId net, const uint32_t *const rows[9], uint8_t *dst, hipStream_t s) {
-  const struct { int layer, ksteps, tiles; size_t off; } part[3] = {{1, 9, 2, 0}, {2, 9, 4, kConvMfmaA2L2Off}, {3, 18, 4, kConvMfmaA2L3Off}};
+  const struct { int layer, ksteps, tiles; size_t off; } part[7] = {{1, 9, 2, 0},  {2, 9, 4, kConvMfmaA2L2Off},  {3, 18, 4, kConvMfmaA2L3Off}, {4, 18, 8, kTailMfmaA2L4Off},
+                                                                   {5, 36, 8, kTailMfmaA2L5Off}, {6, 4, 16, kTailMfmaA2L6Off}, {7, 8, 16, kTailMfmaA2L7Off}};
   for (const auto &p : part) {
     const dim3 grid((unsigned)((p.ksteps * p.tiles * 64 + p.tiles * 64 + 255) / 256));
     if (net == NET_CNVW2A2) hipLaunchKernelGGL(k_conv_mfma_a2_table<true>, grid, dim3(256), 0, s, rows[p.layer], p.ksteps, p.tiles, dst + p.off);

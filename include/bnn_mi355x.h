@@ -174,12 +174,15 @@ int bnn_mi355x_reserve(int max_images);
 int bnn_mi355x_chunk_plan(int n_images, int from_file, int *bases, int cap);
 
 /* Which stages of a CNV network one pass of n_images images runs on the matrix cores, with the parameters and switches
- * (BNN_MI355X_CONV, BNN_MI355X_CONV_MFMA_MIN, BNN_MI355X_L0, BNN_MI355X_L1) now in force: bit k set = layer k runs as an MFMA
- * kernel (layer 0's int8 forms, layers 1-3 as FP4 implicit GEMMs), clear = on the integer pipe.  The results never tell --
- * both paths are bit-identical -- so this is how a caller or a test sees which one a size takes.  A pass is what
+ * (BNN_MI355X_CONV, BNN_MI355X_CONV_MFMA_MIN, BNN_MI355X_TAIL_MFMA_MIN, BNN_MI355X_L0, BNN_MI355X_L1) now in force: bit k
+ * set = layer k runs as an MFMA kernel (layer 0's int8 forms; layers 1-3 and, from an edge of their own, layers 4-7 as FP4
+ * GEMMs), clear = on the integer pipe.  Bit 8 is never set: layer 8 has no matrix form.  The results never tell -- both
+ * paths are bit-identical -- so this is how a caller or a test sees which one a size takes.  A pass is what
  * bnn_mi355x_inference_device enqueues on one stream; calls the runtime splits (the chunks of chunk_plan, the two halves of a
- * device call of 16 384 images and more) decide per piece: ask with the piece's size.  The fault-injection entry points
- * always run layers 1-3 on the integer pipe.  0 for the LFC networks, -1 before load_parameters.  Host only. */
+ * device call of 16 384 images and more) decide per piece: ask with the piece's size.  The answer is for a pass without a
+ * completion word: the host-timed single-image call (BNN_MI355X_DIRECT_TIMING=host) keeps layers 4-8 in one launch on the
+ * integer pipe.  The fault-injection entry points always run layers 1-7 on the integer pipe.  0 for the LFC networks, -1
+ * before load_parameters.  Host only. */
 int bnn_mi355x_matrix_stages(int n_images);
 
 /* Fault campaigns: fix the seed of the fault planner (0 = std::random_device like the

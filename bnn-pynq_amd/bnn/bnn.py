@@ -298,6 +298,40 @@ class PynqBNN:
                 usec.value * nf * size.value, nf, size.value, usec.value))
         return changed[:nf], diffs[:min(cap, total)]
 
+    # extension: datapath upset-rate campaigns (every activation upset with probability p)
+    def act_noise_rates(self, rates):
+        """rates as probabilities in [0, 1) -- a scalar for every layer, or one per layer but the last -- -> uint32 array
+        of floor(p * 2^32), the unit of bnn_mi355x_act_noise_campaigns"""
+        layers = 8 if self.interface.bnn_mi355x_network().startswith(b"cnv") else 3  # (every layer but the last)
+        p = np.full(layers, float(rates)) if np.isscalar(rates) else np.asarray(list(rates), np.float64)
+        if p.shape != (layers,) or (p < 0).any() or (p >= 1).any():
+            raise ValueError("rates: a probability in [0, 1) for each of the {} layers that have activations".format(layers))
+        return np.floor(p * 4294967296.0).astype(np.uint64).astype(np.uint32)
+
+    def inference_multiple_act_noise(self, path, num_runs, rates, seed=0):
+        """num_runs independent runs over the images of `path`, every activation of layer L's output upset with
+        probability rates[L] (act_noise_rates) before the next layer reads it; run r draws with seed + r (seed 0: every
+        run's seed from std::random_device, then in self.act_noise_seeds).  -> (classes int32 (num_runs, n), counts int64
+        (num_runs, layers - 1): the sites actually upset per run and layer, over all n images).  The loaded parameters
+        are not changed.  usecPerImage: device time of the call / (num_runs * n)."""
+        lib = self.interface
+        q = np.ascontiguousarray(self.act_noise_rates(rates), np.uint32)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_act_noise_campaigns(path.encode(), len(self.classes), num_runs, seed,
+                                                 q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), len(q), ctypes.byref(size),
+                                                 ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("activation noise campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_act_noise_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_act_noise_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_act_noise_seeds(seeds, num_runs)
+        self.act_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, -1)
+
     def inference_multiple_detail(self, path):
         size = ctypes.c_int(0)
         usec = ctypes.c_float(0)
@@ -477,6 +511,15 @@ class CnvClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
+    # extension: datapath upset-rate campaigns (PynqBNN.inference_multiple_act_noise)
+    def classify_images_act_noise(self, imgs, num_runs, rates, seed=0):
+        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_act_noise(p, num_runs, rates, seed))
+
+    def classify_cifars_act_noise(self, path, num_runs, rates, seed=0):
+        result = self.bnn.inference_multiple_act_noise(path, num_runs, rates, seed)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
     def classify_images_details(self, imgs):
         return self._with_tmp(imgs, self.bnn.inference_multiple_detail)
 
@@ -544,6 +587,11 @@ class LfcClassifier:
 
     def classify_mnists_act_fault_sweep(self, mnist_format_file, records, max_diffs=None):
         result = self.bnn.act_fault_sweep(mnist_format_file, records, max_diffs)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_mnists_act_noise(self, mnist_format_file, num_runs, rates, seed=0):
+        result = self.bnn.inference_multiple_act_noise(mnist_format_file, num_runs, rates, seed)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

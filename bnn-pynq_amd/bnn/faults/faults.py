@@ -19,6 +19,10 @@ dropped as soon as their activations equal the fault-free ones).
 
 ``FaultTest.activation_sensitivity`` / ``NetworkTest.activation_sensitivity_map`` ask the same of the datapath: every
 single activation of a layer's output, moved to another level while one image passes (``PynqBNN.act_fault_sweep``).
+
+``FaultTest.run_noise_test`` / ``NetworkTest.upset_rate_curve`` give the datapath's accuracy-versus-upset-rate curve:
+every activation of the chosen layers' outputs upset with probability p, independently per run, image and site
+(``PynqBNN.inference_multiple_act_noise``), with the spread over the runs and the rate the runs actually saw.
 """
 import numpy as np
 
@@ -169,6 +173,21 @@ class FaultTest:
         print("{}-{}: {} activation faults in layer(s) {} swept, {} change some image".format(
             self.network, self.dataset, len(records), list(layers), int((changed > 0).sum())))
         return out
+
+
+    def run_noise_test(self, num_runs, rates, seed=0):
+        """num_runs independent runs with every activation of layer L's output upset with probability rates[L] (a
+        scalar: every layer but the last) -> accuracy per run in percent.  Run r draws with seed + r (0:
+        std::random_device).  Left behind: self.noise_results (classes, [run, image]), self.noise_counts (upsets,
+        [run, layer]) and self.noise_usec (device time per image of every run)."""
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        print("{}-{}: {} run(s) in one call, activation upset rate(s) {}".format(self.network, self.dataset, num_runs, rates))
+        results, counts = self._classify(classifier, "_act_noise", num_runs, rates, seed)
+        self.noise_results, self.noise_counts, self.noise_usec = results, counts, classifier.usecPerImage
+        accuracies = [util.calculate_accuracy(row.tolist(), self.labels) for row in results]
+        print("Accuracies:", accuracies)
+        print()
+        return accuracies
 
 
 class CNVFaultTest(FaultTest):
@@ -338,6 +357,37 @@ class NetworkTest:
                 "per pixel vulnerability": vul.mean(axis=2).tolist(),
                 "fields": ["layer", "y", "x", "channel", "shift", "changed"],
                 "changed": [int(c) for c in r["changed"]]})
+
+    def upset_rate_curve(self, output_folder, num_runs, rates, layers=(), seed=0):
+        """The accuracy-versus-upset-rate curve of the datapath (FaultTest.run_noise_test).  `layers`: layer sets -- each
+        a list of layers whose outputs are upset, or one layer number; empty: one set, every layer but the last.  Per
+        (layer set, rate p) one statistics file in the format test_network writes,
+        output_folder/<network>/<dataset>/upsets/<network>_<dataset>_rate<p>_stats[_layer<set>].json: the runs'
+        accuracies with min / max / average and the effective runs, plus "stddev accuracy", the nominal "rate" and
+        the "effective rate" the runs actually saw (upsets counted on the device / sites exposed), with the upsets per
+        layer summed over the runs."""
+        ft = self.fault_test
+        folder = "{}/{}/{}/upsets/".format(output_folder, ft.network, ft.dataset)
+        if self.control is None:  # (rate 0: the fault-free classes)
+            self.control = ft.run_noise_test(1, 0.0, seed or 1)[0]
+        classifier = ft.classifier_cls(ft.network, ft.dataset, ft.runtime)
+        nl = len(classifier.bnn.act_noise_rates(0.0))
+        sets = [[int(l)] if np.isscalar(l) else [int(x) for x in l] for l in layers] or [list(range(nl))]
+        sites = np.array([len(classifier.bnn.enumerate_act_faults(l)) // (2 if ft.network.endswith("A2") else 1) for l in range(nl)])
+        for which in sets:
+            for p in rates:
+                per_layer = [float(p) if l in which else 0.0 for l in range(nl)]
+                accuracies = ft.run_noise_test(num_runs, per_layer, seed)
+                name = "upset rate {:g}".format(p)
+                stats = self._stats(self._raw(name, num_runs, 0, which, accuracies))
+                exposed = float(sites[which].sum()) * num_runs * ft.noise_results.shape[1]
+                stats["results"][name].update({
+                    "stddev accuracy": float(np.std(accuracies)), "rate": float(p),
+                    "effective rate": float(ft.noise_counts[:, which].sum()) / exposed if exposed else 0.0,
+                    "upsets per layer": [int(c) for c in ft.noise_counts.sum(axis=0)]})
+                out = "{}/{}_{}_rate{:g}_stats".format(folder, ft.network, ft.dataset, p)
+                out += ".json" if len(which) == nl else "_layer{}.json".format(which)
+                util.write_dict_to_file(out, stats)
 
     def comprehensive_test(self, output_folder, num_runs, flip_counts, target_layers=()):
         """all six combinations of {any, weight, threshold} x {bit, 8-bit word}.  (The reference's version

@@ -43,4 +43,25 @@ std::string check_act_fault(const NetSpec &net, const ActSite &a) {
   return "";
 }
 
+long act_noise_mask(const NetSpec &net, uint64_t run_seed, int image, int layer, uint32_t rate_q32, long first, ActSite *out, long cap) {
+  ActShape s;
+  if (!act_shape(net, layer, &s)) return -1;
+  const long sites = (long)s.h * s.w * s.c;  // (a multiple of 32 for every layer of the five networks)
+  long total = 0;
+  if (rate_q32 == 0) return 0;
+  for (long b = 0; 4 * b < sites; b++) {
+    uint32_t u[4];
+    act_noise_block((uint32_t)run_seed, (uint32_t)(run_seed >> 32), (uint32_t)image, (uint32_t)layer, (uint32_t)b, u);
+    for (int e = 0; e < 4 && 4 * b + e < sites; e++) {
+      if (u[e] >= rate_q32) continue;
+      if (out && total >= first && total - first < cap) {
+        long p = (4 * b + e) / s.c;
+        out[total - first] = ActSite{layer, (int)(p / s.w), (int)(p % s.w), (int)((4 * b + e) % s.c), s.levels == 3 ? 1 + (int)(u[e] & 1) : 1};
+      }
+      total++;
+    }
+  }
+  return total;
+}
+
 }  // namespace bnn

@@ -161,4 +161,11 @@ struct ActPatch { uint32_t unit, bit, shift, pad; };
 hipError_t act_seed(const uint8_t *base, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len, const ActPatch *patches,
                     uint8_t *act, hipStream_t s);
 
+// Random activation upsets (bnn_mi355x_act_noise_campaigns).  In place on the `row_bytes` per image of a layer's packed
+// output at act + (slot + j) * row_bytes, j < len, for every record: each site upset where act_noise_block (act_faults.h)
+// of (seeds[run], image + j, layer, site) says so for `rate_q32`; counts[run * nlayers + layer] += the sites upset.
+// Nothing is launched for rate 0.
+hipError_t act_noise(uint8_t *act, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len, const unsigned long long *seeds,
+                     int layer, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
+
 }  // namespace bnn

@@ -41,6 +41,8 @@
 #include <cstring>
 #include <type_traits>
 
+#define BNN_HD __host__ __device__
+#include "act_faults.h"
 #include "kernels.h"
 #include "packed_params.h"
 static_assert(bnn::kL0TileOffset == (int)bnn::kL0MfmaTileOffset && bnn::kL0BigBytes == (int)bnn::kL0MfmaBigBytes,
@@ -2544,6 +2546,58 @@ __global__ __launch_bounds__(kBlock) void k_act_seed(const uint8_t *__restrict__
   reinterpret_cast<uint4 *>(act)[(size_t)(sg.slot + j) * row_units + u] = v;
 }
 
+// Random activation upsets (bnn_mi355x_act_noise_campaigns).  k_act_noise: in place on layer L's packed output of every
+// (run, image) pair of the records, a lane per 32 sites: a dword of a 1-bit map (bit c = channel c, site = 32 * dword +
+// bit), or the 32-channel half of a 2-bit map's 16-byte unit (sign dword h, non-zero dword 2 + h; site = 64 * unit + 32 h
+// + bit).  Eight Philox blocks (act_noise_block, four sites each) give the lane's upset mask and, for 2-bit maps, the
+// mask of the sites shifted by two levels; the levels are rotated bitwise in registers, a lane without an upset stores
+// nothing, and the wave's upsets go to the (run, layer) counter with one atomic.  No LDS.  The integer pipe bounds it:
+// 8 x 10 rounds x two 32 x 32 -> 64 multiplies per lane.
+template <bool TWO_BIT>
+__global__ __launch_bounds__(kBlock) void k_act_noise(uint32_t *__restrict__ act, unsigned row_words, const MultiSeg *__restrict__ segs,
+                                                      const unsigned long long *__restrict__ seeds, unsigned layer, unsigned rate,
+                                                      unsigned long long *__restrict__ counts, unsigned nlayers) {
+  const MultiSeg sg = segs[blockIdx.y];
+  const unsigned t = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t fired = 0;
+  if (t < (unsigned)sg.len * row_words) {
+    const unsigned j = t / row_words, w = t - j * row_words;
+    const unsigned long long seed = seeds[sg.run];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), image = (uint32_t)sg.image + j;
+    uint32_t two = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+      uint32_t u[4];
+      act_noise_block(k0, k1, image, layer, w * 8 + b, u);
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const uint32_t f = u[e] < rate ? 1u : 0u;
+        fired |= f << (4 * b + e);
+        if constexpr (TWO_BIT) two |= (f & u[e]) << (4 * b + e);
+      }
+    }
+    if (fired) {
+      const size_t row = (size_t)(sg.slot + j) * row_words;
+      if constexpr (!TWO_BIT) {
+        act[row + w] ^= fired;
+      } else {
+        uint32_t *const p = act + 2 * row + (size_t)(w >> 1) * 4 + (w & 1);
+        const uint32_t sgn = p[0], nz = p[2], one = fired & ~two;
+        // level index 0 (-1): sign set; 1 (0): neither; 2 (+1): non-zero alone -- moved on by 1 (`one`) or 2 (`two`) mod 3
+        const uint32_t i0 = sgn, i1 = ~sgn & ~nz, i2 = ~sgn & nz;
+        const uint32_t n0 = (i2 & one) | (i1 & two), n1 = (i0 & one) | (i2 & two);
+        p[0] = (sgn & ~fired) | n0;
+        p[2] = (nz & ~fired) | (fired & ~n1);
+      }
+    }
+  }
+  // the wave's upsets (every lane takes part: none has left)
+  unsigned c = __popc(fired);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + (size_t)sg.run * nlayers + layer, (unsigned long long)c);
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -3200,6 +3254,19 @@ hipError_t act_seed(const uint8_t *base, int row_bytes, bool two_bit, const Mult
   const dim3 g((unsigned)((units + kBlock - 1) / kBlock));
   if (two_bit) hipLaunchKernelGGL(k_act_seed<true>, g, dim3(kBlock), 0, s, base, act, row_bytes / 16, segs, patches, (int)per_seg, units);
   else hipLaunchKernelGGL(k_act_seed<false>, g, dim3(kBlock), 0, s, base, act, row_bytes / 16, segs, patches, (int)per_seg, units);
+  return hipGetLastError();
+}
+
+hipError_t act_noise(uint8_t *act, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len, const unsigned long long *seeds,
+                     int layer, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s) {
+  if (nsegs <= 0 || max_len <= 0 || rate_q32 == 0) return hipSuccess;
+  const int sites = row_bytes * (two_bit ? 4 : 8);
+  const long long lanes = (long long)max_len * (sites / 32);
+  if (nsegs > 65535 || row_bytes <= 0 || sites % (two_bit ? 64 : 32) || (uintptr_t)act % 16 || lanes > 0x7fffffffLL) return hipErrorInvalidValue;
+  const dim3 g((unsigned)((lanes + kBlock - 1) / kBlock), (unsigned)nsegs);
+  uint32_t *const a = reinterpret_cast<uint32_t *>(act);
+  if (two_bit) hipLaunchKernelGGL(k_act_noise<true>, g, dim3(kBlock), 0, s, a, (unsigned)(sites / 32), segs, seeds, (unsigned)layer, rate_q32, counts, (unsigned)nlayers);
+  else hipLaunchKernelGGL(k_act_noise<false>, g, dim3(kBlock), 0, s, a, (unsigned)(sites / 32), segs, seeds, (unsigned)layer, rate_q32, counts, (unsigned)nlayers);
   return hipGetLastError();
 }
 

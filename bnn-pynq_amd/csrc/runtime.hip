@@ -35,6 +35,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <random>
 #include <memory>
 #include <string>
 #include <thread>
@@ -253,6 +254,12 @@ struct Runtime {
   size_t sw_base_cap = 0, sw_stage_cap = 0, sw_segs_cap = 0, sw_alive_cap = 0, sw_res_cap = 0, sw_cnt_cap = 0, sw_diffs_cap = 0;
   std::vector<long> sweep_pairs;  // the last sweep: per layer, the (fault, image) pairs it had to run (bnn_mi355x_last_sweep_stages)
   std::vector<long> act_sweep_pairs;  // the same of the last activation-fault sweep (bnn_mi355x_last_act_sweep_stages)
+  // bnn_mi355x_act_noise_campaigns: run seeds and [run][layer] upset counters in HBM (segment records: d_sw_segs, results:
+  // d_camp_res); the counts and seeds of the last such call
+  uint8_t *d_noise = nullptr;
+  size_t noise_cap = 0;
+  std::vector<long> noise_counts;
+  std::vector<unsigned long long> noise_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -412,7 +419,7 @@ void free_workspace() {
   Runtime &r = rt();
   if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.file_cap && !r.all_cap && !r.h_io &&
       !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
-      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap)
+      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.noise_cap)
     return;
   if (r.device >= 0) (void)hipSetDevice(r.device);
   (void)hipDeviceSynchronize();
@@ -444,6 +451,9 @@ void free_workspace() {
     *b = nullptr;
   }
   r.sw_base_cap = r.sw_stage_cap = r.sw_segs_cap = r.sw_alive_cap = r.sw_res_cap = r.sw_cnt_cap = r.sw_diffs_cap = 0;
+  (void)hipFree(r.d_noise);
+  r.d_noise = nullptr;
+  r.noise_cap = 0;
   (void)hipFree(r.d_file[0]); (void)hipFree(r.d_file[1]);
   r.d_file[0] = r.d_file[1] = nullptr;
   r.h_file[0].reset(); r.h_file[1].reset();
@@ -2644,6 +2654,186 @@ int bnn_mi355x_last_act_sweep_stages(long *pairs_per_stage, int cap) {
   const std::vector<long> &p = rt().act_sweep_pairs;
   for (int i = 0; pairs_per_stage && i < cap && i < (int)p.size(); i++) pairs_per_stage[i] = p[(size_t)i];
   return (int)p.size();
+}
+
+// Random activation upsets, many runs in one call.  The work items are (run, image) pairs in run-major order, cut into
+// groups of at most one activation workspace; every group runs every layer's MULTI stage on the loaded blob (copy stride
+// 0, the integer-pipe kernels of the fault paths) with k_act_noise between two stages where the layer's rate is not 0.
+// The draw keys on the image's index in the file, so the grouping never shows in the results.
+int *bnn_mi355x_act_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                    const unsigned int *rate_q32, int n_rates, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  r.noise_counts.clear();
+  r.noise_seeds.clear();
+  const int S = net.nlayers;
+  if (!path || !rate_q32 || n_rates != S - 1) {
+    fail("act_noise_campaigns: bad arguments (path / rate_q32 missing, or n_rates is not " + std::to_string(S - 1) + ": one rate per layer but the last)");
+    return nullptr;
+  }
+  if (num_runs < 1 || num_runs > kMaxRuns) {
+    fail("act_noise_campaigns: num_runs must be 1 ... " + std::to_string(kMaxRuns));
+    return nullptr;
+  }
+  const int R = num_runs;
+  if (seed != 0 && 0ull - (uint64_t)seed < (uint64_t)R) {
+    fail("act_noise_campaigns: seed + run wraps to 0 for a run (0 seeds from std::random_device)");
+    return nullptr;
+  }
+#ifdef BNN_VARIANT
+  fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+  return nullptr;
+#endif
+  if (!ready()) return nullptr;
+  if (r.l1_mfma || r.l1_literal) {
+    fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the campaigns run the standard multi-run stages)");
+    return nullptr;
+  }
+  ImageFile f;
+  if (open_image_file(path, f)) return nullptr;
+  const int n = (int)f.n;
+  const size_t total = (size_t)R * n;
+  const bool cnv = net.is_cnv;
+  std::vector<unsigned long long> seeds((size_t)R);
+  {
+    std::random_device rd;
+    for (int q = 0; q < R; q++) {
+      unsigned long long k = seed ? seed + (unsigned long long)q : 0;  // (seed 0: every run from std::random_device, never 0)
+      while (k == 0) k = ((unsigned long long)rd() << 32) | rd();
+      seeds[(size_t)q] = k;
+    }
+  }
+  int *result = new (std::nothrow) int[total + 1];
+  if (!result) { fail("out of memory"); return nullptr; }
+  std::vector<unsigned long long> counts((size_t)R * (S - 1), 0);
+  double device_us = 0.0;
+  auto run = [&]() -> int {
+    if (n == 0) return 0;
+    size_t cap = std::min<size_t>(kMaxChunk, total);  // pairs per group: the activation workspace
+    if (const char *e = std::getenv("BNN_MI355X_NOISE_GROUP")) {  // tests: many small groups
+      const long long v = std::atoll(e);
+      if (v > 0) cap = std::min<size_t>(cap, (size_t)v);
+    }
+    std::vector<size_t> ob((size_t)S, 0);
+    std::vector<int> obuf((size_t)S, 0);
+    for (int l = 0; l + 1 < S; l++) ob[(size_t)l] = stage_output_bytes(cnv, net.abits, cnv ? l : l + 1, &obuf[(size_t)l]);
+    // the records of every group: a run's images, cut at the group's end
+    struct Group { size_t seg0; int nsegs, max_len, total; };
+    std::vector<MultiSeg> segs;
+    std::vector<Group> groups;
+    for (size_t p0 = 0; p0 < total; p0 += cap) {
+      const size_t p1 = std::min(total, p0 + cap);
+      Group g{segs.size(), 0, 0, 0};
+      for (size_t p = p0; p < p1;) {
+        const int q = (int)(p / (size_t)n), i = (int)(p % (size_t)n), m = (int)std::min<size_t>((size_t)(n - i), p1 - p);
+        segs.push_back(MultiSeg{q, i, g.total, m});
+        g.nsegs++;
+        g.total += m;
+        g.max_len = std::max(g.max_len, m);
+        p += (size_t)m;
+      }
+      groups.push_back(g);
+    }
+    PackedHeader h;
+    std::memcpy(&h, r.blob.data(), sizeof(h));
+    const bool tab = h.l0_mfma_offset && r.l0_mfma;
+    const size_t counts_off = ((size_t)R * 8 + 255) & ~(size_t)255;
+    if (load_file_resident(f, n) || reserve((int)cap)) return -1;
+    if (grow(r.d_sw_segs, r.sw_segs_cap, segs.size() * sizeof(MultiSeg)) || grow(r.d_noise, r.noise_cap, counts_off + counts.size() * 8) ||
+        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+      return -1;
+    const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+    unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
+    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
+    uint8_t *const bufs[2] = {static_cast<uint8_t *>(r.buf0), static_cast<uint8_t *>(r.buf1)};
+    const uint8_t *const clean = static_cast<const uint8_t *>(r.d_blob);
+    std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
+    if (!cnv) w.resize(total);
+    DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+    if (settle_handover(r.stream)) return -1;
+    while (r.time_events.size() < 2) {
+      hipEvent_t e;
+      HIP_OK(hipEventCreateWithFlags(&e, kTimeEventFlags));
+      r.time_events.push_back(e);
+    }
+    // -- all of it on one stream, one wait at the end
+    HIP_OK(hipEventRecord(r.time_events[0], r.stream));
+    HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
+    HIP_OK(hipMemsetAsync(d_counts, 0, counts.size() * 8, r.stream));
+    HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
+    for (const Group &g : groups) {
+      for (int l = 0; l < S; l++) {
+        MultiLaunch a{};
+        a.images = r.d_all;
+        a.segs = d_segs + g.seg0;
+        a.nsegs = g.nsegs; a.max_len = g.max_len; a.total = g.total; a.n = n;
+        a.buf0 = r.buf0; a.buf1 = r.buf1;
+        for (int k = 0; k < S; k++) a.rows[k] = reinterpret_cast<const uint32_t *>(clean + h.layer[k].offset);
+        a.l0_mfma = tab ? clean + h.l0_mfma_offset : nullptr;
+        a.stride = 0;  // every run reads the one loaded blob
+        a.has_two = r.two_rows > 0;
+        a.classes = reinterpret_cast<int32_t *>(r.d_camp_res);
+        a.words = reinterpret_cast<uint64_t *>(r.d_camp_res);
+        a.number_class = number_class;
+        a.stream = r.stream;
+        a.first = a.last = l;
+        hipError_t e = cnv ? run_cnv_multi(net.id, a) : run_lfc_multi(net.id, a);
+        if (e == hipSuccess && l + 1 < S)
+          e = act_noise(bufs[obuf[(size_t)l]], (int)ob[(size_t)l], net.L[l].out_planes == 2, a.segs, g.nsegs, g.max_len, d_seeds, l,
+                        rate_q32[l], d_counts, S - 1, r.stream);
+        if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      }
+    }
+    HIP_OK(hipEventRecord(r.time_events[1], r.stream));
+    HIP_OK(hipMemcpyAsync(counts.data(), d_counts, counts.size() * 8, hipMemcpyDeviceToHost, r.stream));
+    if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    for (size_t i = 0; !cnv && i < total; i++) result[i] = lfc_class_batched(w[i], number_class);
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, r.time_events[0], r.time_events[1]));
+    drain.ok();
+    device_us = ms * 1000.0;
+    return 0;
+  };
+  if (run() < 0) {
+    delete[] result;
+    return nullptr;
+  }
+  r.noise_counts.assign(counts.begin(), counts.end());
+  r.noise_seeds = std::move(seeds);
+  if (image_number) *image_number = n;
+  if (usecPerImage) *usecPerImage = total ? (float)(device_us / (double)total) : 0.f;
+  return result;
+}
+
+int bnn_mi355x_last_act_noise_counts(long *upsets, int cap) {
+  const std::vector<long> &c = rt().noise_counts;
+  for (int i = 0; upsets && i < cap && i < (int)c.size(); i++) upsets[i] = c[(size_t)i];
+  return (int)c.size();
+}
+
+int bnn_mi355x_last_act_noise_seeds(unsigned long long *seeds, int cap) {
+  const std::vector<unsigned long long> &k = rt().noise_seeds;
+  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
+  return (int)k.size();
+}
+
+long bnn_mi355x_act_noise_mask(unsigned long long run_seed, int image, int layer, unsigned int rate_q32, long first, int *records,
+                               int cap_records) {
+  const NetSpec &net = rt().spec;
+  const long total = act_noise_mask(net, run_seed, image, layer, rate_q32, 0, nullptr, 0);
+  if (total < 0 || first < 0 || image < 0)
+    return fail("act_noise_mask: bad layer (0 ... " + std::to_string(net.nlayers - 2) + ": the last layer has no activations), image or first");
+  if (records && cap_records > 0 && first < total) {
+    std::vector<ActSite> v((size_t)std::min<long>(cap_records, total - first));
+    act_noise_mask(net, run_seed, image, layer, rate_q32, first, v.data(), (long)v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      const int w[5] = {v[i].layer, v[i].y, v[i].x, v[i].channel, v[i].shift};
+      std::memcpy(records + i * 5, w, sizeof w);
+    }
+  }
+  return total;
 }
 
 void free_results(int *result) { delete[] result; }

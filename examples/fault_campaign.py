@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A fault-injection campaign with the reference's `bnn.faults` drivers (the flow of the fork's fault
 notebooks) on an MI355X: 2 000 synthetic CIFAR-10-shaped images whose "labels" are the fault-free
-classes (control accuracy 100 %), three runs for each of {50, 500} upsets x {weight bit, threshold word}.
+classes (control accuracy 100 %), three runs for each of {50, 500} upsets x {weight bit, threshold word}, then the
+datapath's accuracy-versus-upset-rate curve: every activation upset with probability 2^-14 ... 2^-6, ten runs each.
 
     python examples/fault_campaign.py [output_dir]
 """
@@ -33,4 +34,13 @@ for flips in (50, 500):
     for name, e in stats["results"].items():
         print("%4d x %-14s accuracy min %.2f avg %.2f max %.2f (%d of 3 runs changed something)"
               % (flips, name, e["min accuracy"], e["avg accuracy"], e["max accuracy"], e["effective count"]))
+
+net = bnn.faults.NetworkTest(test)
+rates = [2.0 ** -e for e in (14, 12, 10, 8, 6)]
+net.upset_rate_curve(out, 10, rates, seed=1)
+for p in rates:
+    stats = json.load(open(os.path.join(out, "cnvW1A1", "cifar10", "upsets", "cnvW1A1_cifar10_rate%g_stats.json" % p)))
+    e = stats["results"]["upset rate %g" % p]
+    print("upset rate %-12g (effective %.3g) accuracy min %.2f avg %.2f max %.2f stddev %.2f"
+          % (p, e["effective rate"], e["min accuracy"], e["avg accuracy"], e["max accuracy"], e["stddev accuracy"]))
 print("results under", out)

@@ -267,6 +267,39 @@ long bnn_mi355x_act_fault_sweep(const char *path, int number_class, const int *r
                                 long cap_diffs, int *image_number, float *usecPerImage);
 int bnn_mi355x_last_act_sweep_stages(long *pairs_per_stage, int cap);
 
+/* Datapath upset-rate campaigns: the accuracy when EVERY activation of the stream is upset with probability p.  The
+ * random, many-at-once form of the activation-fault model above (sites, their order and `shift` as
+ * bnn_mi355x_enumerate_act_faults lists them; the project's own model).  rate_q32[L], L = 0 ... layers - 2:
+ * the rate of layer L's output in units of 2^-32 (0: never).  For run seed k, image i (its index in the file), layer L
+ * and site s (counting y, x, channel):
+ *     u = philox4x32_10(counter {i, L, s >> 2, 0}, key {k & 0xffffffff, k >> 32})[s & 3]
+ * with the constants of the Philox paper; the site is upset iff u < rate_q32[L], with shift 1 + (u & 1) for 2-bit
+ * activations and 1 for 1-bit ones.  All upsets of layer L's output are applied together, to the map actually flowing
+ * in that (run, image) pair -- already disturbed by the upsets of earlier layers -- before layer L + 1 reads it.  The
+ * draw keys on the image's index in the file and on nothing else of the call: results do not depend on batch size,
+ * grouping of runs or chunking.
+ * act_noise_campaigns: num_runs (1 ... 4096) independent runs over the images of `path`, run r with seed + r (refused
+ * if that is 0 mod 2^64 for a run; seed == 0: every run's seed from std::random_device, read them back with
+ * last_act_noise_seeds).  Returns a new int[num_runs * n] of classes, run-major (free_results).  n_rates must be
+ * layers - 1.  All rates 0: the fault-free classes once per run.  The loaded parameters, last_faults,
+ * last_campaign_faults and both last_*sweep_stages are unchanged.  Refused (NULL + last_error) before any device work:
+ * bad arguments, the hardened variants ("not modelled", as every fault entry point), the BNN_MI355X_L1 comparison
+ * forms.  An imported blob is fine: no parameter is patched.  usecPerImage: device time / (num_runs * n).  Every pair
+ * runs every layer on the integer-pipe kernels of the fault paths; groups of pairs are bounded by the activation
+ * workspace (BNN_MI355X_NOISE_GROUP=<pairs> makes them smaller: tests).
+ * last_act_noise_counts: of the last such call, the sites actually upset per [run][layer], run-major, counted on the
+ * device by the kernel that applies them; returns runs * (layers - 1) (0 before the first call).
+ * last_act_noise_seeds: the runs' seeds of the last call; returns their number.
+ * act_noise_mask: host only, touches no GPU.  The upset sites of one (run seed, image, layer) at `rate_q32` as 5-int
+ * act_fault_sweep records in site order: writes records [first, first + cap_records) and returns the total (records
+ * may be NULL); -1 + last_error for a layer without sites or a negative image / first. */
+int *bnn_mi355x_act_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                    const unsigned int *rate_q32, int n_rates, int *image_number, float *usecPerImage);
+int bnn_mi355x_last_act_noise_counts(long *upsets, int cap);
+int bnn_mi355x_last_act_noise_seeds(unsigned long long *seeds, int cap);
+long bnn_mi355x_act_noise_mask(unsigned long long run_seed, int image, int layer, unsigned int rate_q32, long first,
+                               int *records, int cap_records);
+
 /* The step before the path: CnvClassifier.image_to_cifar (bnn/bnn.py:226-242) on the
  * device.  The reference shrinks a picture with PIL's Image.thumbnail((32, 32), ANTIALIAS) -- Lanczos-3,
  * Pillow's 8-bit fixed-point two-pass resampler -- pastes it centred on a white 32x32 canvas and writes

@@ -22,7 +22,7 @@ def make(directory, network, seed, neg2=0.0):
         nthr = max(L["nthr"], 1)
         if cnv and l == 0:
             centre, spread, lo, hi = 0.0, 1800.0, -(1 << 23), (1 << 23) - 1     # 2*sum(+-q), 2^-8 units
-        elif not a2 or (network == "lfcW1A2" and l == 0 and False):
+        elif not a2:
             centre, spread, lo, hi = mw / 2.0, 2.5 * np.sqrt(mw), -32768, 32767  # popcount of matches
         else:
             centre, spread, lo, hi = 0.0, 2.5 * np.sqrt(mw), -32768, 32767       # signed sums

@@ -161,6 +161,19 @@ struct ActPatch { uint32_t unit, bit, shift, pad; };
 hipError_t act_seed(const uint8_t *base, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len, const ActPatch *patches,
                     uint8_t *act, hipStream_t s);
 
+// The layer right after an activation site, evaluated only inside the window the site reaches (CNV, `layer` = the
+// site's layer + 1 = 1, 2 or 3).  Run q's site: pixel (y, x) of the layer-(layer-1) map, channel 64 * word + bit, level
+// index i -> (i + shift) mod levels.  `base`: the fault-free output rows of layer-1 of ALL the call's images (image i at
+// i * row bytes, 16-byte aligned).  For every record and j < len the launch recomputes, from base's rows of image
+// `image + j` with the site changed in registers, the act_window_pixels(layer) output pixels of slot `slot + j` the site
+// can reach (9 conv pixels; pooled layers: the up to 2 x 2 pooled pixels = 16 conv pixels) and overwrites those words
+// of the slot's row in the layer's output buffer (where run_cnv_multi leaves it); the rest of the row -- the
+// fault-free output, put there by sweep_broadcast -- is left as it is.  Of `a`: segs, nsegs, max_len, total, buf0,
+// buf1, rows, stride and stream are read (cnvW2A2's window kernels are -2-aware whether or not a row holds a -2).
+struct ActWinSite { int y, x, word, bit, shift, pad[3]; };
+int act_window_pixels(int layer);
+hipError_t act_window(NetId net, int layer, const MultiLaunch &a, const uint8_t *base, const ActWinSite *sites);
+
 // Random activation upsets (bnn_mi355x_act_noise_campaigns).  In place on the `row_bytes` per image of a layer's packed
 // output at act + (slot + j) * row_bytes, j < len, for every record: each site upset where act_noise_block (act_faults.h)
 // of (seeds[run], image + j, layer, site) says so for `rate_q32`; counts[run * nlayers + layer] += the sites upset.

@@ -1258,6 +1258,31 @@ __global__ __launch_bounds__(kBlock) void k_quad_x(const uint64_t *__restrict__ 
   }
 }
 
+// k_vec_x's neuron loop, statement for statement, for k_win_x (below): one group of NPB neurons, rows from `w` on,
+// against the lane's KW words; the fire bits, channel c on bit c.  (k_vec_x keeps its own copy: moved onto this
+// function its instantiations compile to different code, and the shipped bodies are pinned.)
+template <int KW, int NPB>
+__device__ __forceinline__ uint32_t vec_x_group(kptr32 w, const uint32_t (&al)[KW], const uint32_t (&ah)[KW], uint32_t &t) {
+  constexpr int ROW_DW = 2 + 2 * KW;
+  uint32_t b = 0;
+  for (int c = NPB - 1; c >= 0; c -= 2) {
+    kptr32 r1 = w + c * ROW_DW, r0 = r1 - ROW_DW;
+    int m1 = xpop_seed(r1[2], al[0], -(int)r1[0], t), m0 = xpop_seed(r0[2], al[0], -(int)r0[0], t);
+    xpop(m1, r1[3], ah[0], t);
+    xpop(m0, r0[3], ah[0], t);
+#pragma unroll
+    for (int k = 1; k < KW; k++) {
+      xpop(m1, r1[2 + 2 * k], al[k], t);
+      xpop(m0, r0[2 + 2 * k], al[k], t);
+      xpop(m1, r1[3 + 2 * k], ah[k], t);
+      xpop(m0, r0[3 + 2 * k], ah[k], t);
+    }
+    b = shift_in_sign(b, m1);
+    b = shift_in_sign(b, m0);
+  }
+  return b;
+}
+
 // one lane = one vector of KW words (FC layers, CNV layer 5; SINGLE: CNV layer 4 window gather).
 // Two neurons per iteration: two independent v_bcnt chains per lane.
 // POOL (with SINGLE): lane = one output pixel of a 2x2-pooled conv layer, the four pixels of a pooling
@@ -1316,6 +1341,7 @@ __global__ __launch_bounds__(kBlock) void k_vec_x(const uint64_t *__restrict__ i
   for (int cg = bm.cg * gpb, cg_end = cg + gpb; cg < cg_end; cg++) {  // see k_conv0
     kptr32 w = (kptr32)(uintptr_t)(rows + (size_t)cg * NPB * ROW_DW);
     uint32_t b = 0;
+    // (this neuron loop exists a second time, as vec_x_group above for k_win_x: an edit here goes there too)
     for (int c = NPB - 1; c >= 0; c -= 2) {
       kptr32 r1 = w + c * ROW_DW, r0 = r1 - ROW_DW;
       int m1 = xpop_seed(r1[2], al[0], -(int)r1[0], t), m0 = xpop_seed(r0[2], al[0], -(int)r0[0], t);
@@ -1543,6 +1569,51 @@ __global__ __launch_bounds__(kBlock) void k_quad(const uint64_t *__restrict__ in
   }
 }
 
+// k_vec's neuron loop, statement for statement, for k_win (below): one group of NPB neurons, rows from `w` on, against
+// the lane's KW words (`nn`: AR_TB, the vector's non-zero activations); the fire words of the two thresholds, before
+// finish_bits.  (k_vec keeps its own copy, as k_vec_x does.)
+template <int ARITH, int KW, bool OUT2, int NPB, bool TWO, int ZW>
+__device__ __forceinline__ void vec_group(kptr32 w, const uint32_t (&as)[KW][2], const uint32_t (&az)[ZW][2], int nn, uint32_t &t,
+                                          uint32_t &b0, uint32_t &b1) {
+  constexpr int PL = planes_in<ARITH>(), WPL = wplanes<ARITH>(), ROW_DW = row_dw<ARITH, KW>();
+  for (int c = NPB - 1; c >= 0; c -= 2) {
+    kptr32 rA = w + c * ROW_DW, rB = rA - ROW_DW;
+    const int tA0 = (int)rA[0], tA1 = (int)rA[1], tB0 = (int)rB[0], tB1 = (int)rB[1];
+    int mA = 0, zA = 0, mB = 0, zB = 0;  // (never materialised: the first statement of a chain writes them)
+#pragma unroll
+    for (int k = 0; k < KW; k++)
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const uint32_t s_ = as[k][h], z_ = az[PL == 2 ? k : 0][h];
+        if (k == 0 && h == 0) {
+          mac32<ARITH, true>(mA, zA, s_, z_, rA + 2 + 2 * WPL * k, h, t, -tA0);
+          mac32<ARITH, true>(mB, zB, s_, z_, rB + 2 + 2 * WPL * k, h, t, -tB0);
+        } else {
+          mac32<ARITH>(mA, zA, s_, z_, rA + 2 + 2 * WPL * k, h, t);
+          mac32<ARITH>(mB, zB, s_, z_, rB + 2 + 2 * WPL * k, h, t);
+        }
+      }
+    if constexpr (TWO) {
+      if (rA[2 + 6 * KW] | rB[2 + 6 * KW]) {  // weights of -2 in one of the two rows (fault injection only)
+#pragma unroll
+        for (int k = 0; k < KW; k++)
+#pragma unroll
+          for (int h = 0; h < 2; h++) {
+            zA += two_extra(rA[2 + 4 * KW + 2 * k + h], as[k][h], az[k][h]);
+            zB += two_extra(rB[2 + 4 * KW + 2 * k + h], as[k][h], az[k][h]);
+          }
+      }
+    }
+    if constexpr (ARITH == AR_XNOR) {  // seeded with -t0: the chain's end is the decision value
+      decide<OUT2>(b0, b1, mA, tA0 - tA1);
+      decide<OUT2>(b0, b1, mB, tB0 - tB1);
+    } else {
+      decide<OUT2>(b0, b1, tA0 - d_of<ARITH>(mA, ARITH == AR_TB ? nn : zA), tA1 - tA0);
+      decide<OUT2>(b0, b1, tB0 - d_of<ARITH>(mB, ARITH == AR_TB ? nn : zB), tB1 - tB0);
+    }
+  }
+}
+
 // Generic "KW words in, thresholded bits out": one lane = one vector (FC layers, CNV layer 5,
 // and with SINGLE the 3x3 window gather of CNV layer 4).  Two neurons per iteration.
 // POOL: as in k_vec_x (lane = output pixel, quad on four consecutive lanes, OR of the fire words).
@@ -1605,6 +1676,7 @@ __global__ __launch_bounds__(kBlock) void k_vec(const uint64_t *__restrict__ in,
   for (int cg = bm.cg * gpb, cg_end = cg + gpb; cg < cg_end; cg++) {  // see k_conv0
     kptr32 w = (kptr32)(uintptr_t)(rows + (size_t)cg * NPB * ROW_DW);
     uint32_t b0 = 0, b1 = 0;
+    // (this neuron loop exists a second time, as vec_group above for k_win: an edit here goes there too)
     for (int c = NPB - 1; c >= 0; c -= 2) {
       kptr32 rA = w + c * ROW_DW, rB = rA - ROW_DW;
       const int tA0 = (int)rA[0], tA1 = (int)rA[1], tB0 = (int)rB[0], tB1 = (int)rB[1];
@@ -1651,6 +1723,152 @@ __global__ __launch_bounds__(kBlock) void k_vec(const uint64_t *__restrict__ in,
     }
     finish_bits<OUT2>(b0, b1);
     if (!POOL || (item & 3) == 0) store_bits<OUT2, NPB>(out, (size_t)(POOL ? item >> 2 : item), groups, cg, b0, b1);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Activation-fault sweeps: the layer right after the site, inside the window the site reaches
+// (bnn_mi355x_act_fault_sweep, site layers 0..2 of the CNV nets).  One changed
+// activation at (y, x) of an ID x ID map reaches the conv outputs oy in [max(0, y - 2), min(OD - 1, y)]
+// (ox likewise): at most 3 x 3.  The (run, image) pair's slot row already holds the fault-free output
+// of this layer (k_sweep_bcast); these kernels overwrite the window's words alone.  A lane per output
+// pixel in k_vec_x's / k_vec's window forms: !POOL 9 lanes per pair; POOL the 2 x 2 pool quads those
+// outputs fall into, whole (a quad's other conv pixels are kept nowhere before the pool), 16 lanes per
+// pair with a quad on four consecutive lanes.  The 3 x 3 input window is gathered from the FAULT-FREE
+// layer-L rows and the site changed in registers with k_act_seed's arithmetic: no faulted row is written.
+// Window positions outside the map repeat a valid one and store nothing.  Block -> record and run as
+// in the MULTI stages (blockIdx.y); the site is the run's, block-uniform.
+// ---------------------------------------------------------------------------
+struct WinItem { int slot, image, oy, ox, opix; bool store; };
+template <int ID, bool POOL>
+__device__ __forceinline__ WinItem win_item(int item, const MultiSeg &sg, int y, int x) {
+  constexpr int OD = ID - 2, IPI = POOL ? 16 : 9;
+  WinItem wi;
+  wi.slot = item / IPI;
+  wi.image = sg.image + wi.slot - sg.slot;
+  const int w = item - wi.slot * IPI;
+  if constexpr (POOL) {
+    constexpr int QD = OD / 2;
+    const int quad = w >> 2, sub = w & 3;
+    const int qy0 = max(y - 2, 0) >> 1, qx0 = max(x - 2, 0) >> 1;
+    const bool oky = qy0 + (quad >> 1) <= (min(y, OD - 1) >> 1), okx = qx0 + (quad & 1) <= (min(x, OD - 1) >> 1);
+    const int qy = oky ? qy0 + (quad >> 1) : qy0, qx = okx ? qx0 + (quad & 1) : qx0;
+    wi.oy = 2 * qy + (sub >> 1);
+    wi.ox = 2 * qx + (sub & 1);
+    wi.opix = qy * QD + qx;
+    wi.store = oky && okx && sub == 0;
+  } else {
+    const int dy = w / 3, dx = w - 3 * dy;
+    const int oy0 = max(y - 2, 0), ox0 = max(x - 2, 0);
+    const bool oky = oy0 + dy <= min(y, OD - 1), okx = ox0 + dx <= min(x, OD - 1);
+    wi.oy = oky ? oy0 + dy : oy0;
+    wi.ox = okx ? ox0 + dx : ox0;
+    wi.opix = wi.oy * OD + wi.ox;
+    wi.store = oky && okx;
+  }
+  return wi;
+}
+__device__ __forceinline__ ActWinSite win_site(const ActWinSite *__restrict__ sites, int run) {
+  kptr32 p = (kptr32)(uintptr_t)(sites + run);
+  return ActWinSite{(int)p[0], (int)p[1], (int)p[2], (int)p[3], (int)p[4], {0, 0, 0}};
+}
+
+// 1-bit maps (cnvW1A1): k_vec_x's window form on the site's window
+template <int CW, int ID, bool POOL>
+__global__ __launch_bounds__(kBlock) void k_win_x(const uint64_t *__restrict__ base, uint32_t *__restrict__ out,
+                                                   const uint32_t *__restrict__ rows, int n_items, int groups, int gpb, MultiArgs ma,
+                                                   const ActWinSite *__restrict__ sites) {
+  constexpr int KW = 9 * CW, ROW_DW = 2 + 2 * KW, OD = ID - 2, NPIX = POOL ? (OD / 2) * (OD / 2) : OD * OD;
+  const MultiSeg sg = multi_seg(ma);
+  const int item0 = multi_prologue(ma, rows, out, n_items, 0);
+  const BlockMap bm = map_block(groups / gpb, n_items);
+  if (!bm.valid) return;  // (POOL: n_items is a multiple of 16, so a quad is valid or invalid as a whole)
+  const ActWinSite st = win_site(sites, sg.run);
+  const WinItem wi = win_item<ID, POOL>(bm.item + item0, sg, st.y, st.x);
+  const uint64_t *__restrict__ in = base + ((size_t)wi.image * ID * ID + (size_t)wi.oy * ID + wi.ox) * CW;
+  uint32_t al[KW], ah[KW];
+#pragma unroll
+  for (int ky = 0; ky < 3; ky++)
+#pragma unroll
+    for (int kx = 0; kx < 3; kx++) {
+      const bool hit = wi.oy + ky == st.y && wi.ox + kx == st.x;
+#pragma unroll
+      for (int k = 0; k < CW; k++) {
+        uint64_t v = in[(ky * ID + kx) * CW + k];
+        if (hit && k == st.word) v ^= 1ull << st.bit;  // a sign flip
+        al[(ky * 3 + kx) * CW + k] = (uint32_t)v;
+        ah[(ky * 3 + kx) * CW + k] = (uint32_t)(v >> 32);
+      }
+    }
+  uint32_t t = chain_temp();
+  for (int cg = bm.cg * gpb, cg_end = cg + gpb; cg < cg_end; cg++) {  // see k_conv0
+    kptr32 w = (kptr32)(uintptr_t)(rows + (size_t)cg * 32 * ROW_DW);
+    uint32_t b = vec_x_group<KW, 32>(w, al, ah, t);
+    if constexpr (POOL) {
+      b |= __shfl_xor(b, 1, 64);
+      b |= __shfl_xor(b, 2, 64);
+    }
+    if (wi.store) store_group<32>(out, ((size_t)wi.slot * NPIX + wi.opix) * groups + cg, b);
+  }
+}
+
+// 2-bit maps (cnvW1A2, cnvW2A2): k_vec's window form on the site's window; the site's level index i (-1, 0, +1) becomes
+// (i + shift) mod 3 in the (sign, non-zero) planes.  cnvW2A2 always runs the -2-aware loop (k_vec's TWO): here it costs
+// one scalar flag test per two neurons and no occupancy (93 against 84 VGPRs for layer 3, 61 against 52 for layers 1
+// and 2), while the plain layer-3 form keeps so many weights in flight that it spills SGPRs.
+template <int ARITH, int CW, int ID, bool POOL>
+__global__ __launch_bounds__(kBlock) void k_win(const uint64_t *__restrict__ base, uint32_t *__restrict__ out,
+                                                 const uint32_t *__restrict__ rows, int n_items, int groups, int gpb, MultiArgs ma,
+                                                 const ActWinSite *__restrict__ sites) {
+  static_assert(planes_in<ARITH>() == 2, "2-bit activations");
+  constexpr bool TWO = ARITH == AR_TT;
+  constexpr int KW = 9 * CW, ROW_DW = row_dw<ARITH, KW>(), OD = ID - 2, NPIX = POOL ? (OD / 2) * (OD / 2) : OD * OD;
+  const MultiSeg sg = multi_seg(ma);
+  const int item0 = multi_prologue(ma, rows, out, n_items, 0);
+  const BlockMap bm = map_block(groups / gpb, n_items);
+  if (!bm.valid) return;
+  const ActWinSite st = win_site(sites, sg.run);
+  const WinItem wi = win_item<ID, POOL>(bm.item + item0, sg, st.y, st.x);
+  const uint64_t *__restrict__ in = base + ((size_t)wi.image * ID * ID + (size_t)wi.oy * ID + wi.ox) * CW * 2;
+  uint32_t as[KW][2], az[KW][2];
+#pragma unroll
+  for (int ky = 0; ky < 3; ky++)
+#pragma unroll
+    for (int kx = 0; kx < 3; kx++) {
+      const bool hit = wi.oy + ky == st.y && wi.ox + kx == st.x;
+#pragma unroll
+      for (int k = 0; k < CW; k++) {
+        const uint64_t *__restrict__ src = in + ((ky * ID + kx) * CW + k) * 2;
+        uint64_t sgn = src[0], nz = src[1];
+        if (hit && k == st.word) {
+          const uint64_t m = 1ull << st.bit;
+          const uint32_t i = (sgn & m) ? 0u : ((nz & m) ? 2u : 1u), lv = (i + (uint32_t)st.shift) % 3u;
+          sgn = lv == 0 ? (sgn | m) : (sgn & ~m);
+          nz = lv != 1 ? (nz | m) : (nz & ~m);
+        }
+        const int d = (ky * 3 + kx) * CW + k;
+        as[d][0] = (uint32_t)sgn; as[d][1] = (uint32_t)(sgn >> 32);
+        az[d][0] = (uint32_t)nz; az[d][1] = (uint32_t)(nz >> 32);
+      }
+    }
+  int nn = 0;  // AR_TB: non-zero activations of the window
+  if constexpr (ARITH == AR_TB) {
+#pragma unroll
+    for (int k = 0; k < KW; k++) nn += __builtin_popcount(az[k][0]) + __builtin_popcount(az[k][1]);
+  }
+  uint32_t t = chain_temp();
+  for (int cg = bm.cg * gpb, cg_end = cg + gpb; cg < cg_end; cg++) {  // see k_conv0
+    kptr32 w = (kptr32)(uintptr_t)(rows + (size_t)cg * 32 * ROW_DW);
+    uint32_t b0 = 0, b1 = 0;
+    vec_group<ARITH, KW, true, 32, TWO>(w, as, az, nn, t, b0, b1);
+    if constexpr (POOL) {  // max-pool of a thresholded map = OR of each threshold's fire bits over the quad
+      b0 |= __shfl_xor(b0, 1, 64);
+      b0 |= __shfl_xor(b0, 2, 64);
+      b1 |= __shfl_xor(b1, 1, 64);
+      b1 |= __shfl_xor(b1, 2, 64);
+    }
+    finish_bits<true>(b0, b1);
+    if (wi.store) store_bits<true, 32>(out, (size_t)wi.slot * NPIX + wi.opix, groups, cg, b0, b1);
   }
 }
 
@@ -2949,6 +3167,31 @@ void run_cnv_multi_t(const MultiLaunch &a) {
   BNN_LAUNCH((k_fclast<ARITH, 8, TWO, true>), g, s, B64, nullptr, a.classes, a.rows[8], a.total, a.number_class, ma);
 }
 
+// The windowed first stage of an activation-site group (kernels.h, act_window): `layer` = the layer after the site.
+#define BNN_WIN(kern, ipi, groups32, out, rows)                                                                          \
+  do {                                                                                                                   \
+    const long long it_ = (long long)a.total * (ipi);                                                                    \
+    const int gpb_ = gpb_for(it_, (groups32));                                                                           \
+    const MultiArgs ma_{a.segs, (unsigned)(a.stride / 4), (ipi), 0};                                                     \
+    dim3 g_ = grid_for((long long)a.max_len * (ipi), (groups32) / gpb_);                                                 \
+    g_.y = (unsigned)a.nsegs;                                                                                            \
+    BNN_LAUNCH(kern, g_, a.stream, base, out, rows, (int)it_, (groups32), gpb_, ma_, sites);                             \
+  } while (0)
+
+template <int ARITH>
+void act_window_t(int layer, const MultiLaunch &a, const uint64_t *base, const ActWinSite *sites) {
+  uint32_t *A = reinterpret_cast<uint32_t *>(a.buf0), *B = reinterpret_cast<uint32_t *>(a.buf1);
+  if constexpr (ARITH == AR_XNOR) {
+    if (layer == 1) BNN_WIN((k_win_x<1, 30, true>), 16, 2, B, a.rows[1]);
+    if (layer == 2) BNN_WIN((k_win_x<1, 14, false>), 9, 4, A, a.rows[2]);
+    if (layer == 3) BNN_WIN((k_win_x<2, 12, true>), 16, 4, B, a.rows[3]);
+  } else {
+    if (layer == 1) BNN_WIN((k_win<ARITH, 1, 30, true>), 16, 2, B, a.rows[1]);
+    if (layer == 2) BNN_WIN((k_win<ARITH, 1, 14, false>), 9, 4, A, a.rows[2]);
+    if (layer == 3) BNN_WIN((k_win<ARITH, 2, 12, true>), 16, 4, B, a.rows[3]);
+  }
+}
+
 }  // namespace
 
 const char *stage_name(bool is_cnv, int stage) {
@@ -3254,6 +3497,21 @@ hipError_t act_seed(const uint8_t *base, int row_bytes, bool two_bit, const Mult
   const dim3 g((unsigned)((units + kBlock - 1) / kBlock));
   if (two_bit) hipLaunchKernelGGL(k_act_seed<true>, g, dim3(kBlock), 0, s, base, act, row_bytes / 16, segs, patches, (int)per_seg, units);
   else hipLaunchKernelGGL(k_act_seed<false>, g, dim3(kBlock), 0, s, base, act, row_bytes / 16, segs, patches, (int)per_seg, units);
+  return hipGetLastError();
+}
+
+int act_window_pixels(int layer) { return layer == 2 ? 9 : (layer == 1 || layer == 3) ? 16 : 0; }
+
+hipError_t act_window(NetId net, int layer, const MultiLaunch &a, const uint8_t *base8, const ActWinSite *sites) {
+  if (a.nsegs <= 0 || a.total <= 0) return hipSuccess;
+  if (a.nsegs > 65535 || !act_window_pixels(layer) || (uintptr_t)base8 % 16) return hipErrorInvalidValue;
+  const uint64_t *base = reinterpret_cast<const uint64_t *>(base8);
+  switch (net) {
+    case NET_CNVW1A1: act_window_t<AR_XNOR>(layer, a, base, sites); break;
+    case NET_CNVW1A2: act_window_t<AR_TB>(layer, a, base, sites); break;
+    case NET_CNVW2A2: act_window_t<AR_TT>(layer, a, base, sites); break;  // (-2-aware whatever a.has_two says)
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

@@ -2161,7 +2161,9 @@ long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long firs
 // The body both single-fault sweeps share, behind their entry points' checks: bnn_mi355x_fault_sweep (parameter faults,
 // `faults`) and bnn_mi355x_act_fault_sweep (activation sites, `sites`); the other one is null.  A group of records in
 // layer L starts at stage s0: a parameter fault at L itself, from blob copies patched for the group and the broadcast
-// fault-free output of layer L-1; an activation site at L+1, from the loaded blob (copy stride 0) and k_act_seed's rows.
+// fault-free output of layer L-1; an activation site at L+1, from the loaded blob (copy stride 0) and k_act_seed's rows --
+// or, for the CNV site layers 0..2, with layer L+1 evaluated only inside the window the site reaches (act_window: the
+// fault-free layer-(L+1) rows broadcast, the window's pixels recomputed over them; no faulted layer-L row is written).
 // The per-layer pair counts go to `stage_pairs` on success.
 static long single_fault_sweep(const char *path, int number_class, const std::vector<Fault> *faults, const std::vector<ActSite> *sites,
                                int *changed, int *diffs, long cap_diffs, int *image_number, float *usecPerImage,
@@ -2210,10 +2212,24 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     if (cnv) cnv_workspace_bytes(net.abits, &b0, &b1);
     else lfc_workspace_bytes(net.abits, &b0, &b1);
     const int wcap = (int)std::min<long long>(kMaxChunk, (long long)n_faults * n);  // images of activation workspace
+    // activation sites (read at every call): BNN_MI355X_ACT_WINDOW=0 keeps the dense first stage for every layer, any other
+    // value takes the windowed one for every CNV site layer 0..2 (the A/B switch, and the tests' two routes); unset, the
+    // policy below decides.  BNN_MI355X_SWEEP_GROUP=<pairs> caps a run group's pairs (tests: several groups and image
+    // windows on few images).
+    // Policy: per (net, site layer) the windowed route only where a record of tools/act_fault_sweep_rate.py --window-ab has
+    // it faster than the dense one by more than the spread between repeats.  No such record yet: every case stays dense.
+    static const bool kWindowFaster[3][3] = {{false, false, false}, {false, false, false}, {false, false, false}};
+    const char *const env_win = std::getenv("BNN_MI355X_ACT_WINDOW");
+    const auto windowed = [&](int L) {
+      if (!act || !cnv || L > 2) return false;
+      return env_win ? std::atoi(env_win) != 0 : kWindowFaster[net.id][L];
+    };
+    long long group_cap = 0;
+    if (const char *e = act ? std::getenv("BNN_MI355X_SWEEP_GROUP") : nullptr) group_cap = std::atoll(e);
     // A run group that starts at stage s0 holds the outputs of layers s0-1 .. S-2 in the workspace at once, (run, image)
     // slot by slot: its pairs are bounded by the bytes per image of those outputs, not by the layer-0 sizing of the
     // workspace -- the FC layers take ~25x the pairs of the conv layers.  Activation sites need no blob copies: their
-    // groups are not bounded by kMaxRuns.
+    // groups are not bounded by kMaxRuns; a windowed group never holds layer s0-1's output either.
     std::vector<int> G((size_t)S, 0), win((size_t)S, 0);
     std::vector<std::vector<int>> by_layer((size_t)S);
     for (int i = 0; i < n_faults; i++) by_layer[(size_t)layer_of(i)].push_back(i);
@@ -2223,9 +2239,10 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
       if (by_layer[(size_t)L].empty()) continue;
       const int s0 = start_of(L);
       long long c = kMaxSweepPairs;
-      for (int l = std::max(s0 - 1, 0); l + 1 < S; l++)
+      for (int l = windowed(L) ? s0 : std::max(s0 - 1, 0); l + 1 < S; l++)
         c = std::min<long long>(c, (long long)((size_t)wcap * (obuf[(size_t)l] ? b1 : b0) / ob[(size_t)l]));
       if (s0 == 0) c = std::min<long long>(c, wcap);  // (the first stage writes the layer-0 sizes)
+      if (group_cap > 0) c = std::min(c, group_cap);
       const long long runs_cap = act ? kMaxSweepPairs : (long long)kMaxRuns;
       const int g = (int)std::max<long long>(1, std::min<long long>({c / n, runs_cap, (long long)by_layer[(size_t)L].size()}));
       G[(size_t)L] = g;
@@ -2318,7 +2335,8 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
       return 0;
     };
     // layer l's stage over the batches: rows from `copies` (run q's copy at q * cstride), results to `res`
-    auto stage = [&](int l, const uint8_t *copies, size_t cstride, bool two, uint8_t *res) -> int {
+    // (`window`: the windowed first stage of an activation-site group instead, from the fault-free layer l-1 rows)
+    auto stage = [&](int l, const uint8_t *copies, size_t cstride, bool two, uint8_t *res, const ActWinSite *window = nullptr) -> int {
       for (const Batch &b : batches) {
         MultiLaunch a{};
         a.images = r.d_all;
@@ -2334,7 +2352,9 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
         a.number_class = number_class;
         a.stream = r.stream;
         a.first = a.last = l;
-        const hipError_t e = cnv ? run_cnv_multi(net.id, a) : run_lfc_multi(net.id, a);
+        const hipError_t e = window ? act_window(net.id, l, a, r.d_sw_base + boff[(size_t)l - 1], window)
+                             : cnv  ? run_cnv_multi(net.id, a)
+                                    : run_lfc_multi(net.id, a);
         if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
       }
       return 0;
@@ -2380,7 +2400,20 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
         hipError_t e = hipSuccess;
         const PatchSpan *d_spans = nullptr;
         const ActPatch *d_sites = nullptr;
-        if (act) {  // activation sites: each run's site as k_act_seed patches it
+        const ActWinSite *d_wsites = nullptr;
+        const bool wnd = windowed(L);
+        if (wnd) {  // activation sites of CNV layers 0..2: each run's site as the window kernels change it
+          std::vector<ActWinSite> ws((size_t)g);
+          for (int q = 0; q < g; q++) {
+            const ActSite &st = (*sites)[(size_t)idx[c0 + (size_t)q]];
+            ws[(size_t)q] = ActWinSite{st.y, st.x, st.channel / 64, st.channel % 64, st.shift, {0, 0, 0}};
+          }
+          upload.assign(ws.size() * sizeof(ActWinSite), 0);
+          std::memcpy(upload.data(), ws.data(), upload.size());
+          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
+          d_wsites = reinterpret_cast<const ActWinSite *>(r.d_sw_stage);
+        } else if (act) {  // activation sites: each run's site as k_act_seed patches it
           ActShape sh{};
           act_shape(net, L, &sh);
           const bool two_bit = sh.levels == 3;
@@ -2440,12 +2473,20 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
         if (act && trace().on)
           std::fprintf(stderr, "bnn-mi355x trace act_fault_sweep: layer %d sites %zu..%zu of %zu, window %d of %d images\n", L, c0, c0 + g - 1,
                        idx.size(), std::min(win[(size_t)L], n), n);
+        if (act && trace().on)
+          std::fprintf(stderr, "bnn-mi355x trace act_fault_sweep window: layer %d, %lld pairs windowed, %d pixels per pair\n", L,
+                       wnd ? (long long)g * n : 0LL, wnd ? act_window_pixels(s0) : 0);
         const int wl = win[(size_t)L];
         for (int i0 = 0; i0 < n; i0 += wl) {
           const int m = std::min(wl, n - i0);  // (g > 1: m = n)
           if (begin()) return -1;
           // the runs start from the fault-free output of layer s0-1 (slot q * m + j) and the fault-free results; activation
-          // sites: with the site changed (k_act_seed, below)
+          // sites: with the site changed (k_act_seed, below), or -- windowed -- from the fault-free output of layer s0 itself
+          if (wnd) {
+            const size_t bb = ob[(size_t)s0];
+            e = sweep_broadcast(r.d_sw_base + boff[(size_t)s0] + (size_t)i0 * bb, bb, m, g, bufs[obuf[(size_t)s0]], (size_t)m * bb, r.stream);
+            if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+          }
           if (!act && L > 0) {
             const size_t bb = ob[(size_t)L - 1];
             e = sweep_broadcast(r.d_sw_base + boff[(size_t)L - 1] + (size_t)i0 * bb, bb, m, g, bufs[obuf[(size_t)L - 1]], (size_t)m * bb, r.stream);
@@ -2457,12 +2498,13 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           for (int q = 0; q < g; q++) segs.push_back(MultiSeg{q, i0, q * m, m});
           for (int l = s0; l < S; l++) {
             if (plan()) return -1;
-            if (act && l == s0) {
+            const ActWinSite *const window = (wnd && l == s0) ? d_wsites : nullptr;  // (in place of k_act_seed + the whole stage)
+            if (act && l == s0 && !window) {
               e = act_seed(r.d_sw_base + boff[(size_t)L], (int)ob[(size_t)L], net.L[L].out_planes == 2, d_segs, (int)segs.size(), m, d_sites,
                            bufs[obuf[(size_t)L]], r.stream);
               if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
             }
-            if (act ? stage(l, clean, 0, two, r.d_sw_res) : stage(l, r.d_copies, stride, two, r.d_sw_res)) return -1;
+            if (act ? stage(l, clean, 0, two, r.d_sw_res, window) : stage(l, r.d_copies, stride, two, r.d_sw_res)) return -1;
             if (l == s0) pairs[(size_t)l] += (long)g * m;
             if (l + 1 == S) break;
             // prune: only the (run, image) pairs whose output differs from the fault-free one go on (and the gaps between them below `bridge`)

@@ -259,7 +259,15 @@ int bnn_mi355x_last_sweep_stages(long *pairs_per_stage, int cap);
  * forms.  An imported blob is fine: activation faults patch no parameter.
  * The fault-free pass runs once and keeps every layer's output; a site in layer L starts at layer L+1 from that
  * output with the site changed, and pairs whose activations return to the fault-free ones are dropped as in
- * fault_sweep.
+ * fault_sweep.  CNV sites of layers 0, 1 and 2: layer L+1 -- a 3x3 convolution over a map wider than what one changed
+ * activation reaches -- is evaluated only inside that window (at most 3x3 conv outputs; behind a max-pool the up to
+ * 2x2 pool quads they fall into), over the fault-free layer-(L+1) output; the results are the dense route's bit for bit.
+ * Two switches, read at every call: BNN_MI355X_ACT_WINDOW=0 evaluates layer L+1 whole for every site layer, any other
+ * value takes the window for every CNV site layer 0..2 (the A/B switch); unset, a (net, site layer) case runs windowed
+ * only where that was measured faster than the dense route -- so far none, the default is the dense route.
+ * BNN_MI355X_SWEEP_GROUP=<pairs> caps the (site, image) pairs of a run group (tests: several groups and image windows
+ * on a few dozen images).  Under BNN_MI355X_TRACE every group prints a second line, "act_fault_sweep window:",
+ * with its layer, the pairs whose first stage ran windowed and the output pixels recomputed per pair.
  * last_act_sweep_stages: of the last activation sweep, per layer the (fault, image) pairs it had to run (0 up to
  * layer L of the earliest site); returns the number of layers (0 before the first such sweep). */
 long bnn_mi355x_enumerate_act_faults(int layer, long first, int *records, int cap_records);

@@ -332,6 +332,67 @@ class PynqBNN:
         self.usecPerImage = usec.value
         return result, np.array(counts[:k], np.int64).reshape(num_runs, -1)
 
+    # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
+    def enumerate_input_faults(self):
+        """-> int32 array (image_bytes * 8, 2): every bit of the input image as records {byte, bit} in site order (byte in
+        the layout of inference_array: CNV planar CHW, LFC row-major; bit 0 the LSB)."""
+        lib = self.interface
+        k = lib.bnn_mi355x_enumerate_input_faults(0, None, 0)
+        recs = np.zeros((k, 2), np.int32)
+        lib.bnn_mi355x_enumerate_input_faults(0, recs.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), k)
+        return recs
+
+    def input_fault_sweep(self, path, records, max_diffs=None):
+        """Every record {byte, bit} alone for every image of `path`: that bit of the image flipped while it is
+        classified.  -> (changed, diffs) as fault_sweep returns them.  The loaded parameters are not changed.
+        usecPerImage: device time / (records * images)."""
+        lib = self.interface
+        recs = np.ascontiguousarray(records, np.int32).reshape(-1, 2)
+        nf = recs.shape[0]
+        changed = np.zeros(max(nf, 1), np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        cap = (1 << 22) if max_diffs is None else int(max_diffs)
+        while True:
+            diffs = np.zeros((max(cap, 1), 3), np.int32)
+            total = lib.bnn_mi355x_input_fault_sweep(path.encode(), len(self.classes), recs.ctypes.data_as(ip), nf,
+                                                     changed.ctypes.data_as(ip), diffs.ctypes.data_as(ip), cap, ctypes.byref(size),
+                                                     ctypes.byref(usec))
+            if total < 0:
+                raise RuntimeError("input fault sweep failed: " + lib.bnn_mi355x_last_error().decode())
+            if max_diffs is not None or total <= cap:
+                break
+            cap = total  # (all of them asked for, more than guessed: once more with room for every one)
+        self.usecPerImage = usec.value
+        if nf and size.value:
+            print("Input fault sweep took %.2f microseconds for %d sites x %d images, %.4f usec per image" % (
+                usec.value * nf * size.value, nf, size.value, usec.value))
+        return changed[:nf], diffs[:min(cap, total)]
+
+    def inference_multiple_input_noise(self, path, num_runs, rate, seed=0):
+        """num_runs independent runs over the images of `path`, every bit of every image flipped with probability `rate`
+        (in [0, 1); floor(rate * 2^32) is what the library takes) while that image is classified; run r draws with seed + r
+        (seed 0: every run's seed from std::random_device, then in self.input_noise_seeds).  -> (classes int32 (num_runs,
+        n), counts int64 (num_runs,): the bits actually flipped per run, over all n images).  The loaded parameters are not
+        changed.  usecPerImage: device time of the call / (num_runs * n)."""
+        lib = self.interface
+        if not 0.0 <= float(rate) < 1.0:
+            raise ValueError("rate: a probability in [0, 1)")
+        q = int(np.floor(float(rate) * 4294967296.0))
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_input_noise_campaigns(path.encode(), len(self.classes), num_runs, seed, q, ctypes.byref(size),
+                                                   ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("input noise campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        counts = (ctypes.c_long * num_runs)()
+        lib.bnn_mi355x_last_input_noise_counts(counts, num_runs)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_input_noise_seeds(seeds, num_runs)
+        self.input_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        return result, np.array(counts[:num_runs], np.int64)
+
     def inference_multiple_detail(self, path):
         size = ctypes.c_int(0)
         usec = ctypes.c_float(0)
@@ -520,6 +581,23 @@ class CnvClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
+    # extension: input-buffer faults (PynqBNN.input_fault_sweep, PynqBNN.inference_multiple_input_noise)
+    def classify_images_input_fault_sweep(self, imgs, records, max_diffs=None):
+        return self._with_tmp(imgs, lambda p: self.bnn.input_fault_sweep(p, records, max_diffs))
+
+    def classify_cifars_input_fault_sweep(self, path, records, max_diffs=None):
+        result = self.bnn.input_fault_sweep(path, records, max_diffs)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_images_input_noise(self, imgs, num_runs, rate, seed=0):
+        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_input_noise(p, num_runs, rate, seed))
+
+    def classify_cifars_input_noise(self, path, num_runs, rate, seed=0):
+        result = self.bnn.inference_multiple_input_noise(path, num_runs, rate, seed)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
     def classify_images_details(self, imgs):
         return self._with_tmp(imgs, self.bnn.inference_multiple_detail)
 
@@ -592,6 +670,16 @@ class LfcClassifier:
 
     def classify_mnists_act_noise(self, mnist_format_file, num_runs, rates, seed=0):
         result = self.bnn.inference_multiple_act_noise(mnist_format_file, num_runs, rates, seed)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_mnists_input_fault_sweep(self, mnist_format_file, records, max_diffs=None):
+        result = self.bnn.input_fault_sweep(mnist_format_file, records, max_diffs)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_mnists_input_noise(self, mnist_format_file, num_runs, rate, seed=0):
+        result = self.bnn.inference_multiple_input_noise(mnist_format_file, num_runs, rate, seed)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

@@ -23,6 +23,11 @@ single activation of a layer's output, moved to another level while one image pa
 ``FaultTest.run_noise_test`` / ``NetworkTest.upset_rate_curve`` give the datapath's accuracy-versus-upset-rate curve:
 every activation of the chosen layers' outputs upset with probability p, independently per run, image and site
 (``PynqBNN.inference_multiple_act_noise``), with the spread over the runs and the rate the runs actually saw.
+
+``FaultTest.input_sensitivity`` / ``NetworkTest.input_sensitivity_map`` and ``FaultTest.run_input_noise_test`` /
+``NetworkTest.input_upset_rate_curve`` are their twins for the image buffer every classification starts from: every
+single bit of the input image flipped alone (``PynqBNN.input_fault_sweep``), and every bit flipped with probability p
+(``PynqBNN.inference_multiple_input_noise``).
 """
 import numpy as np
 
@@ -188,6 +193,36 @@ class FaultTest:
         print("Accuracies:", accuracies)
         print()
         return accuracies
+
+    def input_sensitivity(self, records=None):
+        """Single input-bit faults: each record {byte, bit} (None: every bit of the image, in site order) flipped alone
+        while each image of the input set is classified.  -> (records int32 [k, 2], changed [k]: images whose class the
+        flip changes, accuracy [k] in percent), plus the fault-free accuracy as `self.control_accuracy`."""
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        records = classifier.bnn.enumerate_input_faults() if records is None else np.asarray(records, np.int32).reshape(-1, 2)
+        clean = np.asarray(self._classify(classifier, ""), np.int64)
+        labels = np.asarray(list(self.labels), np.int64)
+        right = clean[:len(labels)] == labels
+        changed, diffs = self._classify(classifier, "_input_fault_sweep", records)
+        accuracy = self._accuracies(len(records), diffs, labels, right)
+        print("{}-{}: {} input bits swept, {} change some image".format(
+            self.network, self.dataset, len(records), int((changed > 0).sum())))
+        return records, changed, accuracy
+
+    def run_input_noise_test(self, num_runs, rate, seed=0):
+        """num_runs independent runs with every bit of every input image flipped with probability `rate` -> accuracy per
+        run in percent.  Run r draws with seed + r (0: std::random_device).  Left behind: self.input_noise_results
+        (classes, [run, image]), self.input_noise_counts (bits flipped, [run]) and self.input_noise_usec (device time
+        per image of every run)."""
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        print("{}-{}: {} run(s) in one call, input-buffer upset rate {}".format(self.network, self.dataset, num_runs, rate))
+        results, counts = self._classify(classifier, "_input_noise", num_runs, rate, seed)
+        self.input_noise_results, self.input_noise_counts, self.input_noise_usec = results, counts, classifier.usecPerImage
+        accuracies = [util.calculate_accuracy(row.tolist(), self.labels) for row in results]
+        print("Accuracies:", accuracies)
+        print()
+        return accuracies
+
 
 
 class CNVFaultTest(FaultTest):
@@ -388,6 +423,58 @@ class NetworkTest:
                 out = "{}/{}_{}_rate{:g}_stats".format(folder, ft.network, ft.dataset, p)
                 out += ".json" if len(which) == nl else "_layer{}.json".format(which)
                 util.write_dict_to_file(out, stats)
+
+    def input_sensitivity_map(self, output_folder):
+        """The input-bit sweep (FaultTest.input_sensitivity) over every bit of the image, next to sensitivity_map's files:
+        output_folder/<network>/<dataset>/sensitivity/<network>_input.json with the totals (sites, mean / max changed
+        images, fraction of bits that change any image, mean / min accuracy, the fault-free accuracy), the vulnerability
+        -- the fraction of images a flip changes -- per bit position (over the pixels) and per pixel (over the bits), and
+        every site's changed count in site order.  -> the changed counts shaped like the image with a last axis of 8
+        bits (bit 0 the LSB): (3, 32, 32, 8) for the CNV networks (planar CHW), (28, 28, 8) for the LFC ones."""
+        ft = self.fault_test
+        folder = "{}/{}/{}/sensitivity/".format(output_folder, ft.network, ft.dataset)
+        records, changed, accuracy = ft.input_sensitivity()
+        shape = (3, 32, 32, 8) if len(records) == 3072 * 8 else (28, 28, 8)
+        cm = np.asarray(changed).reshape(shape)
+        n = max(len(list(ft.labels)), 1)
+        vul = cm.astype(np.float64) / n
+        k = len(records)
+        util.write_dict_to_file("{}/{}_input.json".format(folder, ft.network), {
+            "network": ft.network, "dataset": ft.dataset, "control": ft.control_accuracy, "map": list(shape),
+            "totals": {"sites": k,
+                       "mean changed": float(changed.mean()) if k else 0.0,
+                       "max changed": int(changed.max()) if k else 0,
+                       "fraction changing any image": float((changed > 0).mean()) if k else 0.0,
+                       "mean accuracy": float(accuracy.mean()) if k else ft.control_accuracy,
+                       "min accuracy": float(accuracy.min()) if k else ft.control_accuracy},
+            "per bit vulnerability": vul.reshape(-1, 8).mean(axis=0).tolist(),
+            "per pixel vulnerability": vul.mean(axis=-1).tolist(),
+            "fields": ["byte", "bit", "changed"],
+            "changed": [int(c) for c in changed]})
+        return cm
+
+    def input_upset_rate_curve(self, output_folder, num_runs, rates, seed=0):
+        """The accuracy-versus-upset-rate curve of the input buffer (FaultTest.run_input_noise_test).  Per rate p one
+        statistics file in the format test_network writes,
+        output_folder/<network>/<dataset>/input-upsets/<network>_<dataset>_rate<p>_stats.json: the runs' accuracies with
+        min / max / average and the effective runs, plus "stddev accuracy", the nominal "rate", the "effective rate" the
+        runs actually saw (bits flipped on the device / bits exposed) and the flips summed over the runs."""
+        ft = self.fault_test
+        folder = "{}/{}/{}/input-upsets/".format(output_folder, ft.network, ft.dataset)
+        if self.control is None:  # (rate 0: the fault-free classes)
+            self.control = ft.run_input_noise_test(1, 0.0, seed or 1)[0]
+        classifier = ft.classifier_cls(ft.network, ft.dataset, ft.runtime)
+        bits = len(classifier.bnn.enumerate_input_faults())
+        for p in rates:
+            accuracies = ft.run_input_noise_test(num_runs, float(p), seed)
+            name = "input upset rate {:g}".format(p)
+            stats = self._stats(self._raw(name, num_runs, 0, [], accuracies))
+            exposed = float(bits) * num_runs * ft.input_noise_results.shape[1]
+            stats["results"][name].update({
+                "stddev accuracy": float(np.std(accuracies)), "rate": float(p),
+                "effective rate": float(ft.input_noise_counts.sum()) / exposed if exposed else 0.0,
+                "flips": int(ft.input_noise_counts.sum())})
+            util.write_dict_to_file("{}/{}_{}_rate{:g}_stats.json".format(folder, ft.network, ft.dataset, p), stats)
 
     def comprehensive_test(self, output_folder, num_runs, flip_counts, target_layers=()):
         """all six combinations of {any, weight, threshold} x {bit, 8-bit word}.  (The reference's version

@@ -181,4 +181,17 @@ hipError_t act_window(NetId net, int layer, const MultiLaunch &a, const uint8_t 
 hipError_t act_noise(uint8_t *act, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len, const unsigned long long *seeds,
                      int layer, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
 
+// Input-buffer faults (bnn_mi355x_input_fault_sweep, bnn_mi355x_input_noise_campaigns): faulted copies of the call's
+// resident images (`image_bytes` each, a multiple of 16; both pointers 16-byte aligned) in a staging buffer that the
+// stages then read as images.
+// input_seed: for every record, staged + (slot + j) * image_bytes <- images + (image + j) * image_bytes with run `run`'s
+// bit flipped, j < len: patch.unit the 16-byte lane of the image, patch.bit 0..127 inside it (shift is not read).
+hipError_t input_seed(const uint8_t *images, int image_bytes, const MultiSeg *segs, int nsegs, int max_len, const ActPatch *patches,
+                      uint8_t *staged, hipStream_t s);
+// input_noise: pair p = pair0 + k, k < npairs, is run p / n on image p % n; staged + k * image_bytes <- that image with
+// every bit flipped where act_noise_block of (seeds[run], image, kInputNoiseTag, site) says so for `rate_q32`
+// (input_faults.h); counts[run] += the bits flipped.  Nothing is launched for rate 0.
+hipError_t input_noise(const uint8_t *images, int image_bytes, unsigned long long pair0, int npairs, int n, const unsigned long long *seeds,
+                       uint32_t rate_q32, unsigned long long *counts, uint8_t *staged, hipStream_t s);
+
 }  // namespace bnn

@@ -43,6 +43,7 @@
 
 #define BNN_HD __host__ __device__
 #include "act_faults.h"
+#include "input_faults.h"
 #include "kernels.h"
 #include "packed_params.h"
 static_assert(bnn::kL0TileOffset == (int)bnn::kL0MfmaTileOffset && bnn::kL0BigBytes == (int)bnn::kL0MfmaBigBytes,
@@ -2816,6 +2817,71 @@ __global__ __launch_bounds__(kBlock) void k_act_noise(uint32_t *__restrict__ act
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + (size_t)sg.run * nlayers + layer, (unsigned long long)c);
 }
 
+// Input-buffer faults (bnn_mi355x_input_fault_sweep, bnn_mi355x_input_noise_campaigns): both kernels write whole
+// faulted IMAGES into a staging buffer, which the ordinary stages then classify like any other images.  A lane takes
+// 16 bytes (`units` of them per image: 192 CNV, 49 LFC).
+// k_input_seed: for every record, image `image + j` into slot `slot + j` with the run's one bit flipped (p.unit: the
+// 16-byte lane of the image, p.bit: 0..127 inside it).  Memory-bound, as k_act_seed.
+__global__ __launch_bounds__(kBlock) void k_input_seed(const uint8_t *__restrict__ images, uint8_t *__restrict__ staged, int units,
+                                                       const MultiSeg *__restrict__ segs, const ActPatch *__restrict__ patches, int per_seg,
+                                                       long long lanes) {
+  const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= lanes) return;
+  const long long q = t / per_seg;
+  const int r = (int)(t - q * per_seg), j = r / units, u = r - j * units;
+  const MultiSeg sg = segs[q];
+  if (j >= sg.len) return;
+  uint4 v = reinterpret_cast<const uint4 *>(images)[(size_t)(sg.image + j) * units + u];
+  const ActPatch p = patches[sg.run];
+  if (u == (int)p.unit) {
+    const uint32_t m = 1u << (p.bit & 31), h = p.bit >> 5;
+    v.x ^= h == 0 ? m : 0u;
+    v.y ^= h == 1 ? m : 0u;
+    v.z ^= h == 2 ? m : 0u;
+    v.w ^= h == 3 ? m : 0u;
+  }
+  reinterpret_cast<uint4 *>(staged)[(size_t)(sg.slot + j) * units + u] = v;
+}
+
+// k_input_noise: the (run, image) pairs pair0 .. pair0 + npairs - 1 of a campaign in run-major order (pair p = run
+// p / n, image p % n) into slots 0 .. npairs - 1.  A pair takes `upp` lanes, `units` rounded up to whole waves, so a
+// wave never straddles two runs.  The lane's 16 bytes are 128 sites = 32 Philox blocks (act_noise_block with the input
+// tag in the layer's place; site = 128 * unit + 8 * byte + bit, which is bit 32 * dword + ... of the little-endian
+// uint4); the XOR mask is built in registers, the 16 bytes are stored whether or not a bit flipped (the staged image
+// must be complete), and the wave's flips go to the run's counter with one atomic.  No LDS.  The integer pipe bounds
+// it: 32 x 10 rounds x two 32 x 32 -> 64 multiplies per lane.
+__global__ __launch_bounds__(kBlock) void k_input_noise(const uint8_t *__restrict__ images, uint8_t *__restrict__ staged, unsigned units,
+                                                        unsigned upp, unsigned long long pair0, unsigned npairs, unsigned n,
+                                                        const unsigned long long *__restrict__ seeds, unsigned rate,
+                                                        unsigned long long *__restrict__ counts) {
+  const unsigned long long t = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
+  const unsigned pair = (unsigned)(t / upp), u = (unsigned)(t - (unsigned long long)pair * upp);
+  if (pair >= npairs) return;  // (wave-uniform: upp is a multiple of 64)
+  const unsigned long long p = pair0 + pair;
+  const unsigned run = (unsigned)(p / n), image = (unsigned)(p - (unsigned long long)run * n);
+  unsigned c = 0;
+  if (u < units) {
+    const unsigned long long seed = seeds[run];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint4 v = reinterpret_cast<const uint4 *>(images)[(size_t)image * units + u];
+    uint32_t m[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < 32; b++) {
+      uint32_t w[4];
+      act_noise_block(k0, k1, image, kInputNoiseTag, u * 32 + b, w);
+#pragma unroll
+      for (int e = 0; e < 4; e++) m[b >> 3] |= (w[e] < rate ? 1u : 0u) << (4 * (b & 7) + e);
+    }
+    v.x ^= m[0]; v.y ^= m[1]; v.z ^= m[2]; v.w ^= m[3];
+    reinterpret_cast<uint4 *>(staged)[(size_t)pair * units + u] = v;
+    c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
+  }
+  // the wave's flips (every lane of the wave takes part: none has left)
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + run, (unsigned long long)c);
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -3525,6 +3591,28 @@ hipError_t act_noise(uint8_t *act, int row_bytes, bool two_bit, const MultiSeg *
   uint32_t *const a = reinterpret_cast<uint32_t *>(act);
   if (two_bit) hipLaunchKernelGGL(k_act_noise<true>, g, dim3(kBlock), 0, s, a, (unsigned)(sites / 32), segs, seeds, (unsigned)layer, rate_q32, counts, (unsigned)nlayers);
   else hipLaunchKernelGGL(k_act_noise<false>, g, dim3(kBlock), 0, s, a, (unsigned)(sites / 32), segs, seeds, (unsigned)layer, rate_q32, counts, (unsigned)nlayers);
+  return hipGetLastError();
+}
+
+hipError_t input_seed(const uint8_t *images, int image_bytes, const MultiSeg *segs, int nsegs, int max_len, const ActPatch *patches,
+                      uint8_t *staged, hipStream_t s) {
+  if (nsegs <= 0 || max_len <= 0) return hipSuccess;
+  const long long per_seg = (long long)max_len * (image_bytes / 16), lanes = per_seg * nsegs;
+  if (image_bytes <= 0 || image_bytes % 16 || (uintptr_t)images % 16 || (uintptr_t)staged % 16 || per_seg > 0x7fffffff) return hipErrorInvalidValue;
+  const dim3 g((unsigned)((lanes + kBlock - 1) / kBlock));
+  hipLaunchKernelGGL(k_input_seed, g, dim3(kBlock), 0, s, images, staged, image_bytes / 16, segs, patches, (int)per_seg, lanes);
+  return hipGetLastError();
+}
+
+hipError_t input_noise(const uint8_t *images, int image_bytes, unsigned long long pair0, int npairs, int n, const unsigned long long *seeds,
+                       uint32_t rate_q32, unsigned long long *counts, uint8_t *staged, hipStream_t s) {
+  if (npairs <= 0 || rate_q32 == 0) return hipSuccess;
+  const unsigned units = (unsigned)(image_bytes / 16), upp = (units + 63) / 64 * 64;  // (whole waves per pair)
+  const unsigned long long lanes = (unsigned long long)npairs * upp;
+  if (n <= 0 || image_bytes <= 0 || image_bytes % 16 || (uintptr_t)images % 16 || (uintptr_t)staged % 16 || lanes / kBlock >= 0x7fffffffULL)
+    return hipErrorInvalidValue;
+  const dim3 g((unsigned)((lanes + kBlock - 1) / kBlock));
+  hipLaunchKernelGGL(k_input_noise, g, dim3(kBlock), 0, s, images, staged, units, upp, pair0, (unsigned)npairs, (unsigned)n, seeds, rate_q32, counts);
   return hipGetLastError();
 }
 

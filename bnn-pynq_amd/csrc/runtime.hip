@@ -45,6 +45,7 @@
 #include "../../include/bnn_mi355x.h"
 #include "faults.h"
 #include "act_faults.h"
+#include "input_faults.h"
 #include "kernels.h"
 #include "preprocess.h"
 #include "resample.h"
@@ -65,6 +66,7 @@ namespace {
 constexpr int kMaxChunk = 131072;  // images per pass through the stages
 constexpr int kMaxRuns = 4096;      // campaigns per bnn_mi355x_fault_campaigns call (each holds a copy of the blob in HBM)
 constexpr long long kMaxSweepPairs = 16LL * kMaxChunk;  // (fault, image) pairs of one bnn_mi355x_fault_sweep run group
+constexpr int kInputStagePairs = kMaxChunk;  // (run or site, image) pairs of one group of the input-fault entry points: their staged images in HBM
 constexpr int kForkMin = 16384;     // images: a device-pointer pass of a CNV net of this size and more forks over the two compute lanes
 constexpr int kStageSlots = 4;      // HBM staging buffers of the host paths: two on one compute lane, four on two
 // Events that only TIME device work: a device-scope release at the record point instead of a flush to system scope
@@ -260,6 +262,12 @@ struct Runtime {
   size_t noise_cap = 0;
   std::vector<long> noise_counts;
   std::vector<unsigned long long> noise_seeds;
+  // bnn_mi355x_input_fault_sweep / bnn_mi355x_input_noise_campaigns: a group's faulted images; the last sweep's pairs per layer;
+  // the flips per run and the seeds of the last campaign
+  uint8_t *d_in_stage = nullptr;
+  size_t in_stage_cap = 0;
+  std::vector<long> input_sweep_pairs, input_noise_counts;
+  std::vector<unsigned long long> input_noise_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -419,7 +427,7 @@ void free_workspace() {
   Runtime &r = rt();
   if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.file_cap && !r.all_cap && !r.h_io &&
       !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
-      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.noise_cap)
+      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.noise_cap && !r.in_stage_cap)
     return;
   if (r.device >= 0) (void)hipSetDevice(r.device);
   (void)hipDeviceSynchronize();
@@ -454,6 +462,9 @@ void free_workspace() {
   (void)hipFree(r.d_noise);
   r.d_noise = nullptr;
   r.noise_cap = 0;
+  (void)hipFree(r.d_in_stage);
+  r.d_in_stage = nullptr;
+  r.in_stage_cap = 0;
   (void)hipFree(r.d_file[0]); (void)hipFree(r.d_file[1]);
   r.d_file[0] = r.d_file[1] = nullptr;
   r.h_file[0].reset(); r.h_file[1].reset();
@@ -2158,21 +2169,25 @@ long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long firs
   return total;
 }
 
-// The body both single-fault sweeps share, behind their entry points' checks: bnn_mi355x_fault_sweep (parameter faults,
-// `faults`) and bnn_mi355x_act_fault_sweep (activation sites, `sites`); the other one is null.  A group of records in
+// The body the single-fault sweeps share, behind their entry points' checks: bnn_mi355x_fault_sweep (parameter faults,
+// `faults`), bnn_mi355x_act_fault_sweep (activation sites, `sites`) and bnn_mi355x_input_fault_sweep (bits of the image
+// buffer, `inputs`: a site "layer" before layer 0); the other two are null.  A group of records in
 // layer L starts at stage s0: a parameter fault at L itself, from blob copies patched for the group and the broadcast
 // fault-free output of layer L-1; an activation site at L+1, from the loaded blob (copy stride 0) and k_act_seed's rows --
 // or, for the CNV site layers 0..2, with layer L+1 evaluated only inside the window the site reaches (act_window: the
 // fault-free layer-(L+1) rows broadcast, the window's pixels recomputed over them; no faulted layer-L row is written).
+// An input site starts at layer 0 (LFC: its binariser) like a layer-0 parameter fault, but from k_input_seed's faulted
+// copies of the images in a staging buffer and the loaded blob: layer 0's records then name the staged slot as their image.
 // The per-layer pair counts go to `stage_pairs` on success.
 static long single_fault_sweep(const char *path, int number_class, const std::vector<Fault> *faults, const std::vector<ActSite> *sites,
-                               int *changed, int *diffs, long cap_diffs, int *image_number, float *usecPerImage,
-                               std::vector<long> &stage_pairs) {
+                               const std::vector<InputSite> *inputs, int *changed, int *diffs, long cap_diffs, int *image_number,
+                               float *usecPerImage, std::vector<long> &stage_pairs) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  const bool act = sites != nullptr;
-  const int n_faults = (int)(act ? sites->size() : faults->size());
-  const auto layer_of = [&](int i) { return act ? (*sites)[(size_t)i].layer : (*faults)[(size_t)i].layer; };
+  const bool act = sites != nullptr, inp = inputs != nullptr;
+  const bool unpatched = act || inp;  // (neither patches a parameter: the loaded blob, copy stride 0, no group bound by kMaxRuns)
+  const int n_faults = (int)(inp ? inputs->size() : act ? sites->size() : faults->size());
+  const auto layer_of = [&](int i) { return inp ? 0 : act ? (*sites)[(size_t)i].layer : (*faults)[(size_t)i].layer; };
   const auto start_of = [&](int L) { return act ? L + 1 : L; };
   ImageFile f;
   if (open_image_file(path, f)) return -1;
@@ -2225,7 +2240,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
       return env_win ? std::atoi(env_win) != 0 : kWindowFaster[net.id][L];
     };
     long long group_cap = 0;
-    if (const char *e = act ? std::getenv("BNN_MI355X_SWEEP_GROUP") : nullptr) group_cap = std::atoll(e);
+    if (const char *e = unpatched ? std::getenv("BNN_MI355X_SWEEP_GROUP") : nullptr) group_cap = std::atoll(e);
     // A run group that starts at stage s0 holds the outputs of layers s0-1 .. S-2 in the workspace at once, (run, image)
     // slot by slot: its pairs are bounded by the bytes per image of those outputs, not by the layer-0 sizing of the
     // workspace -- the FC layers take ~25x the pairs of the conv layers.  Activation sites need no blob copies: their
@@ -2242,8 +2257,9 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
       for (int l = windowed(L) ? s0 : std::max(s0 - 1, 0); l + 1 < S; l++)
         c = std::min<long long>(c, (long long)((size_t)wcap * (obuf[(size_t)l] ? b1 : b0) / ob[(size_t)l]));
       if (s0 == 0) c = std::min<long long>(c, wcap);  // (the first stage writes the layer-0 sizes)
+      if (inp) c = std::min<long long>(c, kInputStagePairs);  // (the staged images)
       if (group_cap > 0) c = std::min(c, group_cap);
-      const long long runs_cap = act ? kMaxSweepPairs : (long long)kMaxRuns;
+      const long long runs_cap = unpatched ? kMaxSweepPairs : (long long)kMaxRuns;
       const int g = (int)std::max<long long>(1, std::min<long long>({c / n, runs_cap, (long long)by_layer[(size_t)L].size()}));
       G[(size_t)L] = g;
       win[(size_t)L] = g > 1 ? n : (int)std::min<long long>(n, c);
@@ -2251,7 +2267,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
       max_runs = std::max(max_runs, g);
     }
     // -- host: the working copy of the memories and the blob that patches are built on (restored after every fault)
-    RawParams raw = act ? RawParams{} : r.raw;  // (activation sites patch nothing)
+    RawParams raw = unpatched ? RawParams{} : r.raw;  // (activation and input sites patch nothing)
     std::vector<uint8_t> blob = r.blob;
     PackedHeader h;
     std::memcpy(&h, blob.data(), sizeof(h));
@@ -2266,8 +2282,10 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     // -- device buffers
     const size_t res_n = std::max<size_t>((size_t)max_pairs, (size_t)n);
     if (load_file_resident(f, n) || reserve(wcap)) return -1;
-    if (grow(r.d_copies, r.copies_cap, act ? 0 : (size_t)max_runs * stride) || grow(r.d_sw_base, r.sw_base_cap, boff[(size_t)S]) ||
-        grow(r.d_sw_segs, r.sw_segs_cap, (size_t)max_pairs * sizeof(MultiSeg)) || grow(r.d_sw_alive, r.sw_alive_cap, (size_t)max_pairs) ||
+    const size_t isz = (size_t)net.image_bytes();
+    if (grow(r.d_copies, r.copies_cap, unpatched ? 0 : (size_t)max_runs * stride) || grow(r.d_sw_base, r.sw_base_cap, boff[(size_t)S]) ||
+        grow(r.d_in_stage, r.in_stage_cap, inp ? (size_t)max_pairs * isz + 256 : 0) ||
+        grow(r.d_sw_segs, r.sw_segs_cap, (size_t)max_pairs * sizeof(MultiSeg) * (inp ? 2 : 1)) || grow(r.d_sw_alive, r.sw_alive_cap, (size_t)max_pairs) ||
         grow(r.d_sw_res, r.sw_res_cap, res_n * rb) || grow(r.d_sw_cnt, r.sw_cnt_cap, (size_t)max_runs * 12 + 512) ||
         grow(r.d_sw_diffs, r.sw_diffs_cap, (size_t)max_pairs * 8))
       return -1;
@@ -2276,8 +2294,9 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     int *const d_counts = reinterpret_cast<int *>(r.d_sw_cnt);
     long long *const d_offsets = reinterpret_cast<long long *>(r.d_sw_cnt + (((size_t)max_runs * 4 + 255) & ~(size_t)255));
     const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
+    MultiSeg *const d_seed_segs = reinterpret_cast<MultiSeg *>(r.d_sw_segs) + max_pairs;  // (input sites: layer 0's records, below)
     // host buffers the queued copies read or write (declared before `drain`)
-    std::vector<MultiSeg> segs, ran;
+    std::vector<MultiSeg> segs, ran, seed_segs;
     std::vector<uint8_t> alive, upload;
     std::vector<int> counts, pv;
     std::vector<long long> offs;
@@ -2335,12 +2354,14 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
       return 0;
     };
     // layer l's stage over the batches: rows from `copies` (run q's copy at q * cstride), results to `res`
-    // (`window`: the windowed first stage of an activation-site group instead, from the fault-free layer l-1 rows)
-    auto stage = [&](int l, const uint8_t *copies, size_t cstride, bool two, uint8_t *res, const ActWinSite *window = nullptr) -> int {
+    // (`window`: the windowed first stage of an activation-site group instead, from the fault-free layer l-1 rows;
+    // `staged`: layer 0 of an input-site group, its images the staged ones that the records of `staged_segs` name)
+    auto stage = [&](int l, const uint8_t *copies, size_t cstride, bool two, uint8_t *res, const ActWinSite *window = nullptr,
+                     const uint8_t *staged = nullptr, const MultiSeg *staged_segs = nullptr) -> int {
       for (const Batch &b : batches) {
         MultiLaunch a{};
-        a.images = r.d_all;
-        a.segs = d_segs + b.seg0;
+        a.images = staged ? staged : r.d_all;
+        a.segs = (staged ? staged_segs : d_segs) + b.seg0;
         a.nsegs = b.nsegs; a.max_len = b.max_len; a.total = b.total; a.n = n;
         a.buf0 = r.buf0; a.buf1 = r.buf1;
         for (int k = 0; k < S; k++) a.rows[k] = reinterpret_cast<const uint32_t *>(copies + h.layer[k].offset);
@@ -2381,7 +2402,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     }
     // -- the runs' blob copies (parameter faults)
     if (begin()) return -1;
-    if (!act) {
+    if (!unpatched) {
       HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, blob.size(), hipMemcpyDeviceToDevice, r.stream));
       for (size_t have = 1; have < (size_t)max_runs; have *= 2) {  // replicate by doubling
         const size_t c = std::min(have, (size_t)max_runs - have);
@@ -2413,6 +2434,17 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
           HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
           d_wsites = reinterpret_cast<const ActWinSite *>(r.d_sw_stage);
+        } else if (inp) {  // input sites: each run's bit as k_input_seed flips it (the image's 16-byte lane, the bit inside it)
+          std::vector<ActPatch> ap((size_t)g);
+          for (int q = 0; q < g; q++) {
+            const InputSite &st = (*inputs)[(size_t)idx[c0 + (size_t)q]];
+            ap[(size_t)q] = ActPatch{(uint32_t)st.byte / 16, ((uint32_t)st.byte % 16) * 8 + (uint32_t)st.bit, 0, 0};
+          }
+          upload.assign(ap.size() * sizeof(ActPatch), 0);
+          std::memcpy(upload.data(), ap.data(), upload.size());
+          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
+          d_sites = reinterpret_cast<const ActPatch *>(r.d_sw_stage);
         } else if (act) {  // activation sites: each run's site as k_act_seed patches it
           ActShape sh{};
           act_shape(net, L, &sh);
@@ -2504,7 +2536,17 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
                            bufs[obuf[(size_t)L]], r.stream);
               if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
             }
-            if (act ? stage(l, clean, 0, two, r.d_sw_res, window) : stage(l, r.d_copies, stride, two, r.d_sw_res)) return -1;
+            const bool from_staged = inp && l == 0;
+            if (from_staged) {  // the group's faulted images, and layer 0's records: the same segments, their image the staged slot
+              e = input_seed(r.d_all, (int)isz, d_segs, (int)segs.size(), m, d_sites, r.d_in_stage, r.stream);
+              if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+              seed_segs = segs;
+              for (MultiSeg &sg : seed_segs) sg.image = sg.slot;
+              HIP_OK(hipMemcpyAsync(d_seed_segs, seed_segs.data(), seed_segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
+            }
+            if (unpatched ? stage(l, clean, 0, two, r.d_sw_res, window, from_staged ? r.d_in_stage : nullptr, d_seed_segs)
+                          : stage(l, r.d_copies, stride, two, r.d_sw_res))
+              return -1;
             if (l == s0) pairs[(size_t)l] += (long)g * m;
             if (l + 1 == S) break;
             // prune: only the (run, image) pairs whose output differs from the fault-free one go on (and the gaps between them below `bridge`)
@@ -2597,7 +2639,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           }
         }
         // the copies back to the loaded parameters
-        if (act) continue;
+        if (unpatched) continue;
         if (begin()) return -1;
         e = scatter_patches(r.d_sw_stage, d_spans + patch.size(), (int)undo.size(), r.d_copies, r.stream);
         if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
@@ -2642,7 +2684,7 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
     const std::string e = check_fault(net, faults[(size_t)i]);
     if (!e.empty()) return fail("fault_sweep: record " + std::to_string(i) + ": " + e);
   }
-  return single_fault_sweep(path, number_class, &faults, nullptr, changed, diffs, cap_diffs, image_number, usecPerImage, r.sweep_pairs);
+  return single_fault_sweep(path, number_class, &faults, nullptr, nullptr, changed, diffs, cap_diffs, image_number, usecPerImage, r.sweep_pairs);
 }
 
 int bnn_mi355x_last_sweep_stages(long *pairs_per_stage, int cap) {
@@ -2689,7 +2731,7 @@ long bnn_mi355x_act_fault_sweep(const char *path, int number_class, const int *r
   if (!ready()) return -1;
   if (r.l1_mfma || r.l1_literal)
     return fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the sweeps run the standard multi-run stages)");
-  return single_fault_sweep(path, number_class, nullptr, &sites, changed, diffs, cap_diffs, image_number, usecPerImage, r.act_sweep_pairs);
+  return single_fault_sweep(path, number_class, nullptr, &sites, nullptr, changed, diffs, cap_diffs, image_number, usecPerImage, r.act_sweep_pairs);
 }
 
 int bnn_mi355x_last_act_sweep_stages(long *pairs_per_stage, int cap) {
@@ -2873,6 +2915,197 @@ long bnn_mi355x_act_noise_mask(unsigned long long run_seed, int image, int layer
     for (size_t i = 0; i < v.size(); i++) {
       const int w[5] = {v[i].layer, v[i].y, v[i].x, v[i].channel, v[i].shift};
       std::memcpy(records + i * 5, w, sizeof w);
+    }
+  }
+  return total;
+}
+
+long bnn_mi355x_enumerate_input_faults(long first, int *records, int cap_records) {
+  const NetSpec &net = rt().spec;
+  const long total = input_sites(net);
+  if (first < 0) return fail("enumerate_input_faults: first must not be negative");
+  if (records && cap_records > 0 && first < total) {
+    std::vector<InputSite> v((size_t)std::min<long>(cap_records, total - first));
+    enumerate_input_faults(net, first, v.data(), (long)v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      records[2 * i] = v[i].byte;
+      records[2 * i + 1] = v[i].bit;
+    }
+  }
+  return total;
+}
+
+long bnn_mi355x_input_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
+                                  long cap_diffs, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  r.input_sweep_pairs.clear();
+  if (!path || n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs) || number_class < 1 ||
+      number_class > 64)
+    return fail("input_fault_sweep: bad arguments (path / records / changed missing, cap_diffs without diffs, or number_class outside 1 ... 64)");
+#ifdef BNN_VARIANT
+  return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+#endif
+  const NetSpec &net = r.spec;
+  std::vector<InputSite> sites((size_t)n_faults);
+  for (int i = 0; i < n_faults; i++) {  // (host only: before anything runs on the device)
+    const int *v = records + (size_t)i * 2;
+    sites[(size_t)i] = InputSite{v[0], v[1]};
+    const std::string e = check_input_fault(net, sites[(size_t)i]);
+    if (!e.empty()) return fail("input_fault_sweep: record " + std::to_string(i) + " {" + std::to_string(v[0]) + ", " + std::to_string(v[1]) + "}: " + e);
+  }
+  if (!ready()) return -1;
+  if (r.l1_mfma || r.l1_literal)
+    return fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the sweeps run the standard multi-run stages)");
+  return single_fault_sweep(path, number_class, nullptr, nullptr, &sites, changed, diffs, cap_diffs, image_number, usecPerImage,
+                            r.input_sweep_pairs);
+}
+
+int bnn_mi355x_last_input_sweep_stages(long *pairs_per_stage, int cap) {
+  const std::vector<long> &p = rt().input_sweep_pairs;
+  for (int i = 0; pairs_per_stage && i < cap && i < (int)p.size(); i++) pairs_per_stage[i] = p[(size_t)i];
+  return (int)p.size();
+}
+
+// Random input-buffer upsets, many runs in one call.  The work items are (run, image) pairs in run-major order, cut into
+// groups of at most one staging buffer; k_input_noise writes a group's faulted images there (rate 0: plain copies, no
+// upset launch) and the group is classified like any other batch of that many images in HBM -- the pass of
+// bnn_mi355x_inference_device, matrix-core stages included, with the loaded parameters.  The draw keys on the image's
+// index in the file, so the grouping never shows in the results.
+int *bnn_mi355x_input_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed, unsigned int rate_q32,
+                                      int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  r.input_noise_counts.clear();
+  r.input_noise_seeds.clear();
+  if (!path || number_class < 1 || number_class > 64) {
+    fail("input_noise_campaigns: bad arguments (path missing, or number_class outside 1 ... 64)");
+    return nullptr;
+  }
+  if (num_runs < 1 || num_runs > kMaxRuns) {
+    fail("input_noise_campaigns: num_runs must be 1 ... " + std::to_string(kMaxRuns));
+    return nullptr;
+  }
+  const int R = num_runs;
+  if (seed != 0 && 0ull - (uint64_t)seed < (uint64_t)R) {
+    fail("input_noise_campaigns: seed + run wraps to 0 for a run (0 seeds from std::random_device)");
+    return nullptr;
+  }
+#ifdef BNN_VARIANT
+  fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+  return nullptr;
+#endif
+  if (!ready()) return nullptr;
+  if (r.l1_mfma || r.l1_literal) {
+    fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (a comparison figure's kernels, not a path to study)");
+    return nullptr;
+  }
+  ImageFile f;
+  if (open_image_file(path, f)) return nullptr;
+  const int n = (int)f.n;
+  const size_t total = (size_t)R * n;
+  const bool cnv = net.is_cnv;
+  std::vector<unsigned long long> seeds((size_t)R);
+  {
+    std::random_device rd;
+    for (int q = 0; q < R; q++) {
+      unsigned long long k = seed ? seed + (unsigned long long)q : 0;  // (seed 0: every run from std::random_device, never 0)
+      while (k == 0) k = ((unsigned long long)rd() << 32) | rd();
+      seeds[(size_t)q] = k;
+    }
+  }
+  int *result = new (std::nothrow) int[total + 1];
+  if (!result) { fail("out of memory"); return nullptr; }
+  std::vector<unsigned long long> counts((size_t)R, 0);
+  double device_us = 0.0;
+  auto run = [&]() -> int {
+    if (n == 0) return 0;
+    size_t cap = std::min<size_t>(kInputStagePairs, total);  // pairs per group: the staging buffer
+    if (const char *e = std::getenv("BNN_MI355X_NOISE_GROUP")) {  // tests: many small groups
+      const long long v = std::atoll(e);
+      if (v > 0) cap = std::min<size_t>(cap, (size_t)v);
+    }
+    const size_t isz = (size_t)net.image_bytes(), counts_off = ((size_t)R * 8 + 255) & ~(size_t)255;
+    if (load_file_resident(f, n)) return -1;
+    if (grow(r.d_in_stage, r.in_stage_cap, cap * isz + 256) || grow(r.d_noise, r.noise_cap, counts_off + counts.size() * 8) ||
+        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+      return -1;
+    const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+    unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
+    std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
+    if (!cnv) w.resize(total);
+    DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+    if (settle_handover(r.stream)) return -1;
+    while (r.time_events.size() < 2) {
+      hipEvent_t e;
+      HIP_OK(hipEventCreateWithFlags(&e, kTimeEventFlags));
+      r.time_events.push_back(e);
+    }
+    // -- all of it on one stream, one wait at the end
+    HIP_OK(hipEventRecord(r.time_events[0], r.stream));
+    HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
+    HIP_OK(hipMemsetAsync(d_counts, 0, counts.size() * 8, r.stream));
+    for (size_t p0 = 0; p0 < total; p0 += cap) {
+      const int m = (int)std::min(cap, total - p0);
+      if (rate_q32 != 0) {
+        const hipError_t e = input_noise(r.d_all, (int)isz, p0, m, n, d_seeds, rate_q32, d_counts, r.d_in_stage, r.stream);
+        if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      } else {  // the same pairs through the same passes: each run's stretch of the group copied as it is
+        for (size_t p = p0; p < p0 + (size_t)m;) {
+          const size_t i = p % (size_t)n, len = std::min((size_t)n - i, p0 + (size_t)m - p);
+          HIP_OK(hipMemcpyAsync(r.d_in_stage + (p - p0) * isz, r.d_all + i * isz, len * isz, hipMemcpyDeviceToDevice, r.stream));
+          p += len;
+        }
+      }
+      // (the device entry point itself, on the library's stream: whatever pass it takes for m images is the pass taken here)
+      if (bnn_mi355x_inference_device(r.d_in_stage, m, number_class, cnv ? reinterpret_cast<int32_t *>(r.d_camp_res) + p0 : nullptr, nullptr,
+                                      cnv ? nullptr : reinterpret_cast<uint64_t *>(r.d_camp_res) + p0, r.stream))
+        return -1;
+    }
+    HIP_OK(hipEventRecord(r.time_events[1], r.stream));
+    HIP_OK(hipMemcpyAsync(counts.data(), d_counts, counts.size() * 8, hipMemcpyDeviceToHost, r.stream));
+    if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    for (size_t i = 0; !cnv && i < total; i++) result[i] = lfc_class_batched(w[i], number_class);
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, r.time_events[0], r.time_events[1]));
+    drain.ok();
+    device_us = ms * 1000.0;
+    return 0;
+  };
+  if (run() < 0) {
+    delete[] result;
+    return nullptr;
+  }
+  r.input_noise_counts.assign(counts.begin(), counts.end());
+  r.input_noise_seeds = std::move(seeds);
+  if (image_number) *image_number = n;
+  if (usecPerImage) *usecPerImage = total ? (float)(device_us / (double)total) : 0.f;
+  return result;
+}
+
+int bnn_mi355x_last_input_noise_counts(long *upsets, int cap) {
+  const std::vector<long> &c = rt().input_noise_counts;
+  for (int i = 0; upsets && i < cap && i < (int)c.size(); i++) upsets[i] = c[(size_t)i];
+  return (int)c.size();
+}
+
+int bnn_mi355x_last_input_noise_seeds(unsigned long long *seeds, int cap) {
+  const std::vector<unsigned long long> &k = rt().input_noise_seeds;
+  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
+  return (int)k.size();
+}
+
+long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigned int rate_q32, long first, int *records, int cap_records) {
+  const NetSpec &net = rt().spec;
+  if (first < 0 || image < 0) return fail("input_noise_mask: image and first must not be negative");
+  const long total = input_noise_mask(net, run_seed, image, rate_q32, 0, nullptr, 0);
+  if (records && cap_records > 0 && first < total) {
+    std::vector<InputSite> v((size_t)std::min<long>(cap_records, total - first));
+    input_noise_mask(net, run_seed, image, rate_q32, first, v.data(), (long)v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      records[2 * i] = v[i].byte;
+      records[2 * i + 1] = v[i].bit;
     }
   }
   return total;

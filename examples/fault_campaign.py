@@ -2,7 +2,9 @@
 """A fault-injection campaign with the reference's `bnn.faults` drivers (the flow of the fork's fault
 notebooks) on an MI355X: 2 000 synthetic CIFAR-10-shaped images whose "labels" are the fault-free
 classes (control accuracy 100 %), three runs for each of {50, 500} upsets x {weight bit, threshold word}, then the
-datapath's accuracy-versus-upset-rate curve: every activation upset with probability 2^-14 ... 2^-6, ten runs each.
+datapath's accuracy-versus-upset-rate curve: every activation upset with probability 2^-14 ... 2^-6, ten runs each; and
+the same two questions of the image buffer: the curve for input-bit upsets, and which bit positions of a pixel matter
+(every bit of the image flipped alone, on the first 200 images).
 
     python examples/fault_campaign.py [output_dir]
 """
@@ -43,4 +45,17 @@ for p in rates:
     e = stats["results"]["upset rate %g" % p]
     print("upset rate %-12g (effective %.3g) accuracy min %.2f avg %.2f max %.2f stddev %.2f"
           % (p, e["effective rate"], e["min accuracy"], e["avg accuracy"], e["max accuracy"], e["stddev accuracy"]))
+
+# the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
+net.input_upset_rate_curve(out, 10, rates, seed=1)
+for p in rates:
+    stats = json.load(open(os.path.join(out, "cnvW1A1", "cifar10", "input-upsets", "cnvW1A1_cifar10_rate%g_stats.json" % p)))
+    e = stats["results"]["input upset rate %g" % p]
+    print("input upset rate %-6g (effective %.3g) accuracy min %.2f avg %.2f max %.2f stddev %.2f"
+          % (p, e["effective rate"], e["min accuracy"], e["avg accuracy"], e["max accuracy"], e["stddev accuracy"]))
+small = os.path.join(out, "set200.bin")
+rec[:200].tofile(small)
+cm = bnn.faults.NetworkTest(bnn.faults.CNVFaultTest.CIFARTest(bnn.NETWORK_CNVW1A1, small, labels[:200])).input_sensitivity_map(out)
+print("images (of 200) whose class one flipped input bit changes, mean per bit position 0..7:",
+      np.round(cm.reshape(-1, 8).mean(axis=0), 3).tolist())
 print("results under", out)

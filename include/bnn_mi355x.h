@@ -181,7 +181,8 @@ int bnn_mi355x_chunk_plan(int n_images, int from_file, int *bases, int cap);
  * bnn_mi355x_inference_device enqueues on one stream; calls the runtime splits (the chunks of chunk_plan, the two halves of a
  * device call of 16 384 images and more) decide per piece: ask with the piece's size.  The answer is for a pass without a
  * completion word: the host-timed single-image call (BNN_MI355X_DIRECT_TIMING=host) keeps layers 4-8 in one launch on the
- * integer pipe.  The fault-injection entry points always run layers 1-7 on the integer pipe.  0 for the LFC networks, -1
+ * integer pipe.  The fault-injection entry points always run layers 1-7 on the integer pipe (all but
+ * bnn_mi355x_input_noise_campaigns, which classifies its faulted images by this very pass).  0 for the LFC networks, -1
  * before load_parameters.  Host only. */
 int bnn_mi355x_matrix_stages(int n_images);
 
@@ -307,6 +308,57 @@ int bnn_mi355x_last_act_noise_counts(long *upsets, int cap);
 int bnn_mi355x_last_act_noise_seeds(unsigned long long *seeds, int cap);
 long bnn_mi355x_act_noise_mask(unsigned long long run_seed, int image, int layer, unsigned int rate_q32, long first,
                                int *records, int cap_records);
+
+/* Input-buffer faults: which pixel bits matter, and the accuracy at input-buffer upset rate p (on the FPGA the DRAM / AXI
+ * input buffer; here HBM or pinned memory).  A site is one bit of one input byte, the bytes in the layout of
+ * bnn_mi355x_inference_buffer: bnn_mi355x_image_bytes() per image (CNV 3072, planar CHW; LFC 784, row-major); the label
+ * byte of a CIFAR record and the idx header are not sites.  Site number s = byte * 8 + bit, bit 0 the LSB: image_bytes * 8
+ * sites per image.  A fault XORs that bit while that image is classified -- a faulted image is just another image, so
+ * every result below equals what bnn_mi355x_inference_buffer returns for the bytes with those bits flipped on the host.
+ * The model is the project's own (the reference has no input injection).  Records are 2 ints {byte, bit}.
+ * enumerate_input_faults: every site in site order; writes records [first, first + cap_records) and returns the total
+ * (records may be NULL); -1 + last_error for a negative first.  Host only.
+ * input_fault_sweep: for each record, classify every image of `path` with that one bit flipped while that image is
+ * classified, independently of the other records; changed / diffs / return value / usecPerImage as act_fault_sweep.
+ * The loaded parameters and every other last_* state are unchanged.  Every record is validated on the host before
+ * anything runs on the device.  Refused (-1 + last_error): bad arguments; a record whose byte or bit lies outside the
+ * image (the message names the record); the hardened variants ("not modelled", as every fault entry point); the
+ * BNN_MI355X_L1 comparison forms.  An imported blob is fine: no parameter is patched.
+ * The fault-free pass runs once and keeps every layer's output; a group's pairs start at layer 0 (LFC: at the binariser)
+ * from faulted copies of their images, and pairs whose activations equal the fault-free ones after a layer are dropped as
+ * in fault_sweep (an LFC bit 0 ... 6 never survives the binariser's layer: it reads bit 7 only).
+ * BNN_MI355X_SWEEP_GROUP=<pairs> caps the (site, image) pairs of a run group as for act_fault_sweep.
+ * last_input_sweep_stages: of the last input sweep, per layer the (fault, image) pairs it had to run; returns the number
+ * of layers (0 before the first such sweep).
+ * Random form.  For run seed k, image i (its index in the file) and site s:
+ *     u = philox4x32_10(counter {i, 0xffffffff, s >> 2, 0}, key {k & 0xffffffff, k >> 32})[s & 3]
+ * and the bit is flipped iff u < rate_q32 (units of 2^-32).  The second counter word is where act_noise_campaigns puts the
+ * layer; no layer has that tag, so the two draws never share a stream.  Results are a function of (seed, run, image index,
+ * site) alone: not of batch size, grouping, chunking or the kernel path that runs the network.
+ * input_noise_campaigns: num_runs (1 ... 4096) independent runs over the images of `path`, run r with seed + r (refused if
+ * that is 0 mod 2^64 for a run; seed == 0: every run's seed from std::random_device, read them back with
+ * last_input_noise_seeds).  Returns a new int[num_runs * n] of classes, run-major (free_results).  rate_q32 == 0: the
+ * fault-free classes once per run, no upset kernel is launched.  Refused (NULL + last_error) before any device work: bad
+ * arguments, the hardened variants ("not modelled"), the BNN_MI355X_L1 comparison forms.  An imported blob is fine.
+ * usecPerImage: device time / (num_runs * n).  The (run, image) pairs go in groups of faulted images in a staging buffer
+ * (131 072 pairs; BNN_MI355X_NOISE_GROUP=<pairs> makes them smaller: tests), and a group is classified with the loaded,
+ * unpatched parameters by the pass bnn_mi355x_inference_device takes for that many images, matrix-core stages included.
+ * last_input_noise_counts: of the last such call, the bits actually flipped per run, counted on the device by the kernel
+ * that flips them; returns the number of runs (0 before the first call).
+ * last_input_noise_seeds: the runs' seeds of the last call; returns their number.
+ * input_noise_mask: host only, touches no GPU.  The flipped sites of one (run seed, image) at `rate_q32` as 2-int sweep
+ * records in site order: writes records [first, first + cap_records) and returns the total (records may be NULL);
+ * -1 + last_error for a negative image / first. */
+long bnn_mi355x_enumerate_input_faults(long first, int *records, int cap_records);
+long bnn_mi355x_input_fault_sweep(const char *path, int number_class, const int *records, int n_faults, int *changed, int *diffs,
+                                  long cap_diffs, int *image_number, float *usecPerImage);
+int bnn_mi355x_last_input_sweep_stages(long *pairs_per_stage, int cap);
+int *bnn_mi355x_input_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                      unsigned int rate_q32, int *image_number, float *usecPerImage);
+int bnn_mi355x_last_input_noise_counts(long *upsets, int cap);
+int bnn_mi355x_last_input_noise_seeds(unsigned long long *seeds, int cap);
+long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigned int rate_q32, long first, int *records,
+                                 int cap_records);
 
 /* The step before the path: CnvClassifier.image_to_cifar (bnn/bnn.py:226-242) on the
  * device.  The reference shrinks a picture with PIL's Image.thumbnail((32, 32), ANTIALIAS) -- Lanczos-3,

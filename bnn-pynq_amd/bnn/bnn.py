@@ -393,6 +393,30 @@ class PynqBNN:
         self.usecPerImage = usec.value
         return result, np.array(counts[:num_runs], np.int64)
 
+    # extension: propagation profiles of the single-fault sweeps (where a fault is masked)
+    def sweep_profile(self, enable):
+        """True: fault_sweep, act_fault_sweep and input_fault_sweep called from now on also record, per record and layer,
+        the images and the activations that differ from the fault-free ones (last_sweep_profile).  -> the previous
+        setting.  The setting belongs to the library, which outlives this object."""
+        return bool(self.interface.bnn_mi355x_sweep_profile(1 if enable else 0))
+
+    def last_sweep_profile(self):
+        """The profile of the last sweep that ran with profiling on -> (alive, flipped), int64 arrays of shape
+        (records, layers - 1) in the order of that call's records.  alive[f, l]: the images whose layer-l output (CNV layers
+        1 and 3: after the max-pool) differs from the fault-free one; flipped[f, l]: the activations that differ, summed
+        over those images.  Columns before the first layer the sweep evaluates for a record (a parameter fault's layer,
+        the layer after an activation site, layer 0 for an input bit) are 0."""
+        lib = self.interface
+        cols = ctypes.c_int(0)
+        rows = lib.bnn_mi355x_last_sweep_profile(0, None, None, 0, ctypes.byref(cols))
+        if rows < 0:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        alive = np.zeros((rows, cols.value), np.int64)
+        flipped = np.zeros((rows, cols.value), np.int64)
+        lp = ctypes.POINTER(ctypes.c_long)
+        lib.bnn_mi355x_last_sweep_profile(0, alive.ctypes.data_as(lp), flipped.ctypes.data_as(lp), rows, None)
+        return alive, flipped
+
     def inference_multiple_detail(self, path):
         size = ctypes.c_int(0)
         usec = ctypes.c_float(0)

@@ -28,11 +28,31 @@ every activation of the chosen layers' outputs upset with probability p, indepen
 ``NetworkTest.input_upset_rate_curve`` are their twins for the image buffer every classification starts from: every
 single bit of the input image flipped alone (``PynqBNN.input_fault_sweep``), and every bit flipped with probability p
 (``PynqBNN.inference_multiple_input_noise``).
+
+``FaultTest.propagation`` / ``NetworkTest.propagation_map`` ask where a fault is masked: any of the three single-fault
+sweeps with ``PynqBNN.sweep_profile`` on, which adds per fault and layer the images and the activations that differ from
+the fault-free ones; ``propagation_curves`` reduces the two arrays to a masking curve and a mean error size per layer.
 """
 import numpy as np
 
 from .. import bnn as _bnn
 from .. import util
+
+
+def propagation_curves(alive, flipped, n_images, first=0):
+    """A sweep's propagation profile (PynqBNN.last_sweep_profile: alive[f, l] images, flipped[f, l] activations that
+    differ from the fault-free ones after layer l) reduced over the faults, for the columns from `first` on (the first
+    layer the sweep evaluates for these faults).  -> (share alive, mean error size), two float lists with an entry per
+    column: the share of the faults x n_images (fault, image) pairs still alive after that layer -- the masking curve --
+    and the mean of flipped / alive over the faults with alive > 0 there, the activations an image that is still wrong
+    has wrong (0.0 where no fault is alive)."""
+    alive = np.asarray(alive, np.int64)[:, first:]
+    flipped = np.asarray(flipped, np.int64)[:, first:]
+    pairs = alive.shape[0] * int(n_images)
+    share = alive.sum(axis=0) / float(pairs) if pairs else np.zeros(alive.shape[1])
+    live = alive > 0
+    size = np.where(live, flipped / np.maximum(alive, 1), 0.0).sum(axis=0) / np.maximum(live.sum(axis=0), 1)
+    return [float(x) for x in share], [float(x) for x in size]
 
 
 class FaultTest:
@@ -208,6 +228,36 @@ class FaultTest:
         print("{}-{}: {} input bits swept, {} change some image".format(
             self.network, self.dataset, len(records), int((changed > 0).sum())))
         return records, changed, accuracy
+
+    def propagation(self, kind, layers=(), target_type=0, word_size=1, records=None):
+        """Where single faults are masked.  kind "parameter": every distinct fault of `layers` (target_type 0 weights / 1
+        thresholds, word_size adjacent bits); "activation": every site x shift of the outputs of `layers`; "input": every
+        bit of the image -- or the given `records` of that kind -- each alone on the whole input set, with the sweep's
+        propagation profile recorded (PynqBNN.sweep_profile; the setting found is put back afterwards).  -> dict with
+        "records", "changed" [k] (images whose class the fault changes), "alive" and "flipped" int64 [k, layers - 1]
+        (PynqBNN.last_sweep_profile) and "images", the size of the input set."""
+        methods = {"parameter": ("_fault_sweep", 8), "activation": ("_act_fault_sweep", 5), "input": ("_input_fault_sweep", 2)}
+        if kind not in methods:
+            raise ValueError('propagation: kind is one of "parameter", "activation", "input"')
+        method, width = methods[kind]
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        if records is not None:
+            records = np.asarray(records, np.int32).reshape(-1, width)
+        elif kind == "input":
+            records = classifier.bnn.enumerate_input_faults()
+        else:
+            per = [classifier.bnn.enumerate_faults(l, target_type, word_size) if kind == "parameter"
+                   else classifier.bnn.enumerate_act_faults(l) for l in layers]
+            records = np.concatenate(per) if per else np.zeros((0, width), np.int32)
+        before = classifier.bnn.sweep_profile(True)
+        try:
+            changed, _ = self._classify(classifier, method, records, 0)
+            alive, flipped = classifier.bnn.last_sweep_profile()
+        finally:
+            classifier.bnn.sweep_profile(before)
+        print("{}-{}: {} {} faults swept with their propagation, {} change some image".format(
+            self.network, self.dataset, len(records), kind, int((changed > 0).sum())))
+        return {"records": records, "changed": changed, "alive": alive, "flipped": flipped, "images": len(list(self.labels))}
 
     def run_input_noise_test(self, num_runs, rate, seed=0):
         """num_runs independent runs with every bit of every input image flipped with probability `rate` -> accuracy per
@@ -452,6 +502,37 @@ class NetworkTest:
             "fields": ["byte", "bit", "changed"],
             "changed": [int(c) for c in changed]})
         return cm
+
+    def propagation_map(self, output_folder, kind, layers=(), target_type=0, word_size=1):
+        """Masking per layer (FaultTest.propagation), next to sensitivity_map's files: per site layer of `layers` (kind
+        "input": one site layer, the image) one file output_folder/<network>/<dataset>/sensitivity/<network>_layer<L>_
+        <kind>_propagation.json (input: <network>_input_propagation.json) with the totals the other maps give (faults,
+        mean / max changed images, fraction of faults that change any image) and, for every downstream layer from the
+        first one the sweep evaluates for these faults on, "share alive" -- the share of (fault, image) pairs whose output
+        of that layer still differs from the fault-free one, the masking curve -- and "mean error size", the activations
+        that differ per image still alive, averaged over the faults alive there (propagation_curves).  -> {site layer:
+        the file's dict}."""
+        ft = self.fault_test
+        folder = "{}/{}/{}/sensitivity/".format(output_folder, ft.network, ft.dataset)
+        out = {}
+        for layer in (["input"] if kind == "input" else list(layers)):
+            r = ft.propagation(kind, [] if kind == "input" else [layer], target_type, word_size)
+            first = 0 if kind == "input" else min(layer + (1 if kind == "activation" else 0), r["alive"].shape[1])
+            share, size = propagation_curves(r["alive"], r["flipped"], r["images"], first)
+            changed, k = r["changed"], len(r["records"])
+            out[layer] = {
+                "network": ft.network, "dataset": ft.dataset, "kind": kind, "layer": layer, "images": r["images"],
+                "totals": {"faults": k,
+                           "mean changed": float(changed.mean()) if k else 0.0,
+                           "max changed": int(changed.max()) if k else 0,
+                           "fraction changing any image": float((changed > 0).mean()) if k else 0.0},
+                "downstream layers": list(range(first, r["alive"].shape[1])),
+                "share alive": share, "mean error size": size}
+            if kind == "parameter":
+                out[layer].update({"target": target_type, "word size": word_size})
+            name = "{}_input_propagation.json" if kind == "input" else "{}_layer" + str(layer) + "_" + kind + "_propagation.json"
+            util.write_dict_to_file(folder + name.format(ft.network), out[layer])
+        return out
 
     def input_upset_rate_curve(self, output_folder, num_runs, rates, seed=0):
         """The accuracy-versus-upset-rate curve of the input buffer (FaultTest.run_input_noise_test).  Per rate p one

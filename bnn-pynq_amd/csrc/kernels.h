@@ -146,6 +146,11 @@ hipError_t sweep_broadcast(const uint8_t *src, size_t row_bytes, int rows, int r
 // from base + image * row_bytes; other entries are left as they are.  One wave per image.
 hipError_t sweep_mark(const uint8_t *act, const uint8_t *base, int row_bytes, const MultiSeg *segs, int nsegs, int max_len,
                       uint8_t *alive, hipStream_t s);
+// sweep_mark that also counts (bnn_mi355x_sweep_profile): `alive` as above, and for every record counts[2 * run] += its
+// images that differ, counts[2 * run + 1] += the activations that differ in them -- differing bits of a 1-bit map,
+// channels whose (sign, non-zero) pair differs of a `two_bit` one (16-byte units of 64 channels).  The caller zeroes counts.
+hipError_t sweep_profile(const uint8_t *act, const uint8_t *base, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len,
+                         uint8_t *alive, unsigned long long *counts, hipStream_t s);
 // run q < runs: counts[q] = #{j < win : classes[q * n + j] != base[j]}.  sweep_emit: the pairs {j, classes[q * n + j]} of
 // those images to out + 2 * offsets[q] ..., in image order (counts as sweep_count left them).
 hipError_t sweep_count(const int32_t *classes, const int32_t *base, int n, int win, int runs, int *counts, hipStream_t s);

@@ -2685,6 +2685,50 @@ __global__ __launch_bounds__(kBlock) void k_sweep_mark(const uint8_t *__restrict
   if (__ballot(d != 0) && lane == 0) alive[sg.slot + j] = 1;
 }
 
+// k_sweep_profile: k_sweep_mark that also counts (bnn_mi355x_sweep_profile).  Same geometry, same loads, the same
+// `alive` flags; the lane counts the activations of its units that differ instead of OR-ing the difference -- 1-bit maps:
+// the set bits of the XOR; 2-bit maps: per 64-channel unit (x, y the sign dwords, z, w the non-zero ones) the channels
+// whose sign or non-zero bit differs (the stage kernels write level 0 with neither bit set, see k_act_seed, so differing
+// levels are differing bits and nothing else is).  An image's count (at most 57 600) is summed over the wave with shuffles,
+// the block's four waves -- one record, so one run -- meet in LDS, and a block with a difference adds its images that
+// differ and their activations to counts[2 * run] and [2 * run + 1] with two atomics.  A wave beyond the record's images
+// takes no part but in the barrier (the guard is wave-uniform, as k_sweep_mark's return).
+template <bool TWO_BIT>
+__global__ __launch_bounds__(kBlock) void k_sweep_profile(const uint8_t *__restrict__ act, const uint8_t *__restrict__ base, int row_units,
+                                                          const MultiSeg *__restrict__ segs, uint8_t *__restrict__ alive,
+                                                          unsigned long long *__restrict__ counts) {
+  __shared__ uint32_t wave_c[kBlock / 64];
+  const MultiSeg sg = segs[blockIdx.y];
+  const int wave = threadIdx.x >> 6, j = blockIdx.x * (kBlock / 64) + wave, lane = threadIdx.x & 63;
+  uint32_t c = 0;
+  if (j < sg.len) {  // (wave-uniform)
+    const uint4 *__restrict__ a = reinterpret_cast<const uint4 *>(act) + (size_t)(sg.slot + j) * row_units;
+    const uint4 *__restrict__ b = reinterpret_cast<const uint4 *>(base) + (size_t)(sg.image + j) * row_units;
+    for (int u = lane; u < row_units; u += 64) {
+      const uint4 x = a[u], y = b[u];
+      if constexpr (TWO_BIT) c += __popc((x.x ^ y.x) | (x.z ^ y.z)) + __popc((x.y ^ y.y) | (x.w ^ y.w));
+      else c += __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    if (c && lane == 0) alive[sg.slot + j] = 1;
+  }
+  if (lane == 0) wave_c[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t images = 0, flipped = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; w++) {
+      images += wave_c[w] != 0;
+      flipped += wave_c[w];
+    }
+    if (flipped) {
+      atomicAdd(counts + 2 * (size_t)sg.run, (unsigned long long)images);
+      atomicAdd(counts + 2 * (size_t)sg.run + 1, (unsigned long long)flipped);
+    }
+  }
+}
+
 // k_sweep_classes: a block per run over the window's images; changed = the class differs from the fault-free one.
 // Counts, or (EMIT) the changed images' {image, class} pairs in image order from the run's offset (wave ballots and a
 // prefix over the block's four waves).
@@ -3538,6 +3582,16 @@ hipError_t sweep_mark(const uint8_t *act, const uint8_t *base, int row_bytes, co
   if (nsegs > 65535 || row_bytes % 16) return hipErrorInvalidValue;
   const dim3 g((unsigned)((max_len + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)nsegs);
   hipLaunchKernelGGL(k_sweep_mark, g, dim3(kBlock), 0, s, act, base, row_bytes / 16, segs, alive);
+  return hipGetLastError();
+}
+
+hipError_t sweep_profile(const uint8_t *act, const uint8_t *base, int row_bytes, bool two_bit, const MultiSeg *segs, int nsegs, int max_len,
+                         uint8_t *alive, unsigned long long *counts, hipStream_t s) {
+  if (nsegs <= 0 || max_len <= 0) return hipSuccess;
+  if (nsegs > 65535 || row_bytes % 16) return hipErrorInvalidValue;
+  const dim3 g((unsigned)((max_len + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)nsegs);
+  if (two_bit) hipLaunchKernelGGL(k_sweep_profile<true>, g, dim3(kBlock), 0, s, act, base, row_bytes / 16, segs, alive, counts);
+  else hipLaunchKernelGGL(k_sweep_profile<false>, g, dim3(kBlock), 0, s, act, base, row_bytes / 16, segs, alive, counts);
   return hipGetLastError();
 }
 

@@ -256,6 +256,14 @@ struct Runtime {
   size_t sw_base_cap = 0, sw_stage_cap = 0, sw_segs_cap = 0, sw_alive_cap = 0, sw_res_cap = 0, sw_cnt_cap = 0, sw_diffs_cap = 0;
   std::vector<long> sweep_pairs;  // the last sweep: per layer, the (fault, image) pairs it had to run (bnn_mi355x_last_sweep_stages)
   std::vector<long> act_sweep_pairs;  // the same of the last activation-fault sweep (bnn_mi355x_last_act_sweep_stages)
+  // bnn_mi355x_sweep_profile: whether the single-fault sweeps record a propagation profile; a run group's [run][2]
+  // counters in HBM; the last profiled sweep's [record][layer] images and activations that differ, its records and columns
+  bool sweep_profile = false;
+  uint8_t *d_sw_prof = nullptr;
+  size_t sw_prof_cap = 0;
+  std::vector<long> prof_alive, prof_flipped;
+  long prof_rows = 0;
+  int prof_cols = 0;
   // bnn_mi355x_act_noise_campaigns: run seeds and [run][layer] upset counters in HBM (segment records: d_sw_segs, results:
   // d_camp_res); the counts and seeds of the last such call
   uint8_t *d_noise = nullptr;
@@ -427,7 +435,7 @@ void free_workspace() {
   Runtime &r = rt();
   if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.file_cap && !r.all_cap && !r.h_io &&
       !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
-      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.noise_cap && !r.in_stage_cap)
+      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.sw_prof_cap && !r.noise_cap && !r.in_stage_cap)
     return;
   if (r.device >= 0) (void)hipSetDevice(r.device);
   (void)hipDeviceSynchronize();
@@ -454,11 +462,11 @@ void free_workspace() {
   (void)hipFree(r.d_copies); (void)hipFree(r.d_camp); (void)hipFree(r.d_camp_res);
   r.d_copies = r.d_camp = r.d_camp_res = nullptr;
   r.copies_cap = r.camp_cap = r.camp_res_cap = 0;
-  for (uint8_t **b : {&r.d_sw_base, &r.d_sw_stage, &r.d_sw_segs, &r.d_sw_alive, &r.d_sw_res, &r.d_sw_cnt, &r.d_sw_diffs}) {
+  for (uint8_t **b : {&r.d_sw_base, &r.d_sw_stage, &r.d_sw_segs, &r.d_sw_alive, &r.d_sw_res, &r.d_sw_cnt, &r.d_sw_diffs, &r.d_sw_prof}) {
     (void)hipFree(*b);
     *b = nullptr;
   }
-  r.sw_base_cap = r.sw_stage_cap = r.sw_segs_cap = r.sw_alive_cap = r.sw_res_cap = r.sw_cnt_cap = r.sw_diffs_cap = 0;
+  r.sw_base_cap = r.sw_stage_cap = r.sw_segs_cap = r.sw_alive_cap = r.sw_res_cap = r.sw_cnt_cap = r.sw_diffs_cap = r.sw_prof_cap = 0;
   (void)hipFree(r.d_noise);
   r.d_noise = nullptr;
   r.noise_cap = 0;
@@ -2169,6 +2177,15 @@ long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long firs
   return total;
 }
 
+// A sweep that runs with profiling on replaces the last profile: none is left if it fails (bnn_mi355x_last_sweep_profile).
+static void sweep_profile_begin(Runtime &r) {
+  if (!r.sweep_profile) return;
+  r.prof_alive.clear();
+  r.prof_flipped.clear();
+  r.prof_rows = 0;
+  r.prof_cols = 0;
+}
+
 // The body the single-fault sweeps share, behind their entry points' checks: bnn_mi355x_fault_sweep (parameter faults,
 // `faults`), bnn_mi355x_act_fault_sweep (activation sites, `sites`) and bnn_mi355x_input_fault_sweep (bits of the image
 // buffer, `inputs`: a site "layer" before layer 0); the other two are null.  A group of records in
@@ -2194,6 +2211,10 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
   const int n = (int)f.n, S = net.nlayers;
   const bool cnv = net.is_cnv;
   std::vector<long> pairs((size_t)S, 0);
+  // the propagation profile (bnn_mi355x_sweep_profile): per record and layer with an output map, the images and the
+  // activations that differ from the fault-free output
+  const bool profile = r.sweep_profile;
+  std::vector<long> prof_alive(profile ? (size_t)n_faults * (size_t)(S - 1) : 0, 0), prof_flipped(prof_alive.size(), 0);
   if (n_faults) std::fill(changed, changed + n_faults, 0);
   long total_changed = 0;
   double device_us = 0.0;
@@ -2287,7 +2308,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
         grow(r.d_in_stage, r.in_stage_cap, inp ? (size_t)max_pairs * isz + 256 : 0) ||
         grow(r.d_sw_segs, r.sw_segs_cap, (size_t)max_pairs * sizeof(MultiSeg) * (inp ? 2 : 1)) || grow(r.d_sw_alive, r.sw_alive_cap, (size_t)max_pairs) ||
         grow(r.d_sw_res, r.sw_res_cap, res_n * rb) || grow(r.d_sw_cnt, r.sw_cnt_cap, (size_t)max_runs * 12 + 512) ||
-        grow(r.d_sw_diffs, r.sw_diffs_cap, (size_t)max_pairs * 8))
+        grow(r.d_sw_diffs, r.sw_diffs_cap, (size_t)max_pairs * 8) || grow(r.d_sw_prof, r.sw_prof_cap, profile ? (size_t)max_runs * 16 : 0))
       return -1;
     uint8_t *const bufs[2] = {static_cast<uint8_t *>(r.buf0), static_cast<uint8_t *>(r.buf1)};
     uint8_t *const base_res = r.d_sw_base + boff[(size_t)S - 1];
@@ -2298,6 +2319,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     // host buffers the queued copies read or write (declared before `drain`)
     std::vector<MultiSeg> segs, ran, seed_segs;
     std::vector<uint8_t> alive, upload;
+    std::vector<unsigned long long> prof;
     std::vector<int> counts, pv;
     std::vector<long long> offs;
     std::vector<uint64_t> words;
@@ -2551,14 +2573,27 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
             if (l + 1 == S) break;
             // prune: only the (run, image) pairs whose output differs from the fault-free one go on (and the gaps between them below `bridge`)
             HIP_OK(hipMemsetAsync(r.d_sw_alive, 0, (size_t)g * m, r.stream));
+            if (profile) HIP_OK(hipMemsetAsync(r.d_sw_prof, 0, (size_t)g * 16, r.stream));
             for (const Batch &b : batches) {
-              e = sweep_mark(bufs[obuf[(size_t)l]], r.d_sw_base + boff[(size_t)l], (int)ob[(size_t)l], d_segs + b.seg0, b.nsegs, b.max_len,
-                             r.d_sw_alive, r.stream);
+              e = profile ? sweep_profile(bufs[obuf[(size_t)l]], r.d_sw_base + boff[(size_t)l], (int)ob[(size_t)l], net.L[l].out_planes == 2,
+                                          d_segs + b.seg0, b.nsegs, b.max_len, r.d_sw_alive,
+                                          reinterpret_cast<unsigned long long *>(r.d_sw_prof), r.stream)
+                          : sweep_mark(bufs[obuf[(size_t)l]], r.d_sw_base + boff[(size_t)l], (int)ob[(size_t)l], d_segs + b.seg0, b.nsegs, b.max_len,
+                                       r.d_sw_alive, r.stream);
               if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
             }
             alive.resize((size_t)g * m);
             HIP_OK(hipMemcpyAsync(alive.data(), r.d_sw_alive, alive.size(), hipMemcpyDeviceToHost, r.stream));
+            if (profile) {
+              prof.resize((size_t)g * 2);
+              HIP_OK(hipMemcpyAsync(prof.data(), r.d_sw_prof, (size_t)g * 16, hipMemcpyDeviceToHost, r.stream));
+            }
             if (finish()) return -1;
+            for (int q = 0; profile && q < g; q++) {  // (g = 1: a fault's images come window by window)
+              const size_t at = (size_t)idx[c0 + (size_t)q] * (size_t)(S - 1) + (size_t)l;
+              prof_alive[at] += (long)prof[2 * (size_t)q];
+              prof_flipped[at] += (long)prof[2 * (size_t)q + 1];
+            }
             // the survivors as segments, cut from the records that just ran; a gap shorter than the next stage's smallest
             // grid per record (8 blocks of work items, map_block) is run through rather than cut: a pair that ran this
             // stage with the fault-free output gives the fault-free outputs again, and a record costs that grid however
@@ -2650,6 +2685,12 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     return 0;
   };
   if (run() < 0) return -1;
+  if (profile) {
+    r.prof_alive = std::move(prof_alive);
+    r.prof_flipped = std::move(prof_flipped);
+    r.prof_rows = n_faults;
+    r.prof_cols = S - 1;
+  }
   long k = 0;
   for (auto &e : kept)
     for (size_t i = 0; i + 1 < e.second.size() && k < cap_diffs; i += 2, k++) {
@@ -2667,6 +2708,7 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
                             long cap_diffs, int *image_number, float *usecPerImage) {
   Runtime &r = rt();
   r.sweep_pairs.clear();
+  sweep_profile_begin(r);
   if (n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs))
     return fail("fault_sweep: bad arguments (records / changed missing, or cap_diffs without diffs)");
 #ifdef BNN_VARIANT
@@ -2693,6 +2735,25 @@ int bnn_mi355x_last_sweep_stages(long *pairs_per_stage, int cap) {
   return (int)p.size();
 }
 
+int bnn_mi355x_sweep_profile(int enable) {
+  Runtime &r = rt();
+  const int before = r.sweep_profile ? 1 : 0;
+  r.sweep_profile = enable != 0;
+  return before;
+}
+
+long bnn_mi355x_last_sweep_profile(long first, long *alive, long *flipped, long cap_rows, int *columns) {
+  const Runtime &r = rt();
+  if (first < 0) return fail("last_sweep_profile: negative first");
+  if (columns) *columns = r.spec.nlayers - 1;
+  const size_t cols = (size_t)r.prof_cols;
+  for (long i = first; i < r.prof_rows && i - first < cap_rows; i++) {
+    if (alive) std::memcpy(alive + (size_t)(i - first) * cols, r.prof_alive.data() + (size_t)i * cols, cols * sizeof(long));
+    if (flipped) std::memcpy(flipped + (size_t)(i - first) * cols, r.prof_flipped.data() + (size_t)i * cols, cols * sizeof(long));
+  }
+  return r.prof_rows;
+}
+
 long bnn_mi355x_enumerate_act_faults(int layer, long first, int *records, int cap_records) {
   const NetSpec &net = rt().spec;
   const long total = enumerate_act_faults(net, layer, 0, nullptr, 0);
@@ -2713,6 +2774,7 @@ long bnn_mi355x_act_fault_sweep(const char *path, int number_class, const int *r
                                 long cap_diffs, int *image_number, float *usecPerImage) {
   Runtime &r = rt();
   r.act_sweep_pairs.clear();
+  sweep_profile_begin(r);
   if (n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs))
     return fail("act_fault_sweep: bad arguments (records / changed missing, or cap_diffs without diffs)");
 #ifdef BNN_VARIANT
@@ -2939,6 +3001,7 @@ long bnn_mi355x_input_fault_sweep(const char *path, int number_class, const int 
                                   long cap_diffs, int *image_number, float *usecPerImage) {
   Runtime &r = rt();
   r.input_sweep_pairs.clear();
+  sweep_profile_begin(r);
   if (!path || n_faults < 0 || (n_faults > 0 && (!records || !changed)) || cap_diffs < 0 || (cap_diffs > 0 && !diffs) || number_class < 1 ||
       number_class > 64)
     return fail("input_fault_sweep: bad arguments (path / records / changed missing, cap_diffs without diffs, or number_class outside 1 ... 64)");

@@ -58,4 +58,11 @@ rec[:200].tofile(small)
 cm = bnn.faults.NetworkTest(bnn.faults.CNVFaultTest.CIFARTest(bnn.NETWORK_CNVW1A1, small, labels[:200])).input_sensitivity_map(out)
 print("images (of 200) whose class one flipped input bit changes, mean per bit position 0..7:",
       np.round(cm.reshape(-1, 8).mean(axis=0), 3).tolist())
+
+# where faults are masked: the propagation of every activation site of layers 0 and 4, and of every input bit, on the 200 images
+small_net = bnn.faults.NetworkTest(bnn.faults.CNVFaultTest.CIFARTest(bnn.NETWORK_CNVW1A1, small, labels[:200]))
+for layer, doc in list(small_net.propagation_map(out, "activation", [0, 4]).items()) + list(small_net.propagation_map(out, "input").items()):
+    print("sites of %s: share of (fault, image) pairs still alive after layers %s: %s; activations wrong per live image: %s"
+          % ("layer %d" % layer if layer != "input" else "the image", doc["downstream layers"],
+             np.round(doc["share alive"], 4).tolist(), np.round(doc["mean error size"], 1).tolist()))
 print("results under", out)

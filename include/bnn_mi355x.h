@@ -360,6 +360,30 @@ int bnn_mi355x_last_input_noise_seeds(unsigned long long *seeds, int cap);
 long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigned int rate_q32, long first, int *records,
                                  int cap_records);
 
+/* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
+ * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column
+ * l = the output of layer l, l = 0 ... 7 (layers 1 and 3: after the max-pool); LFC column l = the output of layer l,
+ * l = 0 ... 2 (the binarised input is no column).  For record f of a sweep over n images
+ *     alive[f][l]   = the images whose layer-l output differs from the fault-free layer-l output of that image,
+ *     flipped[f][l] = the activations (one channel of one pixel) that differ, summed over those images:
+ * 1-bit maps, the differing bits of the packed rows; 2-bit maps, the channels whose level differs (the stages write the
+ * level 0 in one form only, so the (sign, non-zero) bits differ exactly where the levels do).  Columns before the first
+ * layer the sweep evaluates for the record are 0; that layer is L for a parameter fault in layer L, L + 1 for an
+ * activation site of layer L, 0 for an input site.  So a parameter fault in the last layer and an activation site of
+ * the last hidden layer have all-zero rows: changed[f] is their only result.  Dropping the pairs whose activations
+ * equal the fault-free ones loses nothing: such a pair has the fault-free output at every later layer, so the profile
+ * equals the one of classifying every pair through every layer.  The counts come from the compare that prunes the
+ * pairs (a kernel that counts the differing activations where the default one only notes that there are some).
+ * sweep_profile: 1: the single-fault sweeps called from now on (fault_sweep, act_fault_sweep, input_fault_sweep) also
+ * record a propagation profile; 0 (the default): they do not.  Returns the previous setting.  Host only.
+ * last_sweep_profile: the profile of the last sweep that ran with profiling on, rows in the order of that call's
+ * records.  Writes rows [first, first + cap_rows) of `columns` longs each into alive and flipped (either may be NULL),
+ * *columns (may be NULL) = layers - 1.  Returns the number of rows of the profile (0 before the first profiled sweep),
+ * -1 + last_error for a negative first.  A profiled sweep that fails leaves no profile; a sweep with profiling off
+ * leaves the previous one in place.  Host only. */
+int bnn_mi355x_sweep_profile(int enable);
+long bnn_mi355x_last_sweep_profile(long first, long *alive, long *flipped, long cap_rows, int *columns);
+
 /* The step before the path: CnvClassifier.image_to_cifar (bnn/bnn.py:226-242) on the
  * device.  The reference shrinks a picture with PIL's Image.thumbnail((32, 32), ANTIALIAS) -- Lanczos-3,
  * Pillow's 8-bit fixed-point two-pass resampler -- pastes it centred on a white 32x32 canvas and writes

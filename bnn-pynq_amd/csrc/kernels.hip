@@ -698,28 +698,50 @@ __global__ __launch_bounds__(256, 2) void k_l1_mfma(const uint32_t *__restrict__
 // 22 of a tile's 32 lanes idle.  A WORK ITEM is one column x of one output row PAIR (2rp, 2rp + 1) of one image, items
 // numbered (image, rp, x) over the block's G images, 32 consecutive items per tile (lane c).
 //   * A block takes G images at a time (2 for layer 1, 8 for layers 2 and 3): their bit-packed maps are expanded once
-//     into FP4 planes in LDS ([image][32-channel block q][pixel] x 16 bytes; lane (c, h) reads block 2 kh + h); the
-//     next group's bits are requested into registers before the current group's MFMAs are issued (as in k_l1_mfma).
+//     into FP4 planes in LDS ([image][32-channel block q][row][column] x 16 bytes; lane (c, h) reads block 2 kh + h);
+//     the next group's bits are requested into registers before the current group's MFMAs are issued (as in
+//     k_l1_mfma).  Layer 3's rows are 13 slots apart for 12 columns and its images 626 for 624
+//     (conv_mfma_row_stride, conv_mfma_img_stride): a tile's items then sit in consecutive slots modulo 16 across the
+//     row-pair and image wraps and no ds_read_b128 lane group hits a bank twice; layers 1 and 2 have that unpadded.
 //   * A wave owns one neuron tile (32 neurons) for the whole kernel: its FP4 weights sit in VGPRs (36 for layers 1 and
 //     2, 72 for layer 3), so no wave spills (k_l1_mfma keeps two tiles and spills).  The waves read the same B operands.
 //   * Per tile and 64-channel step kh, per column offset kx: 4 ds_read_b128 (input rows 2rp .. 2rp + 3) feed 6
-//     MFMAs (output rows 2rp, 2rp + 1 x ky), as k_l1_mfma's row pairs do.
+//     MFMAs (output rows 2rp, 2rp + 1 x ky), as k_l1_mfma's row pairs do.  The reads of a column are issued one
+//     column ahead, behind the MFMAs of the column before, into a second register set: every wait inside a tile is a
+//     counted lgkmcnt for a read that is five MFMAs old (tests/test_conv_matrix_duty_build.py).
 //   * No pool (layer 2): lane half h stores output row 2rp + h (after the half swap both halves hold the word).
 //     Pool (layers 1, 3): vertical max = v_max_f32 of the two rows' accumulators, horizontal = AND of !fire with lane
 //     c ^ 1 (DPP; items per image and per row are even, so x and x ^ 1 of a row pair sit in lanes c and c ^ 1).
 // Items past the last image repeat the last valid one (their results are dropped).  Outputs are the XNOR kernels'
 // bit-packed HWC words, byte for byte.
 // ---------------------------------------------------------------------------
+// Row stride of an LDS plane, in pixels: the smallest one >= win for which the step from the last column of a row pair
+// to the first column of the next keeps the 16-byte slots of a tile's consecutive items consecutive modulo 16 (the 16
+// lanes of a ds_read_b128 group then hit 16 different slots), and the image stride, in slots, that does the same for
+// the step from one image's last item to the next image's first.
+constexpr int conv_mfma_row_stride(int win) {
+  int ws = win;
+  while ((2 * ws - (win - 2)) % 16) ws++;
+  return ws;
+}
+constexpr int conv_mfma_img_stride(int win, int cd) {
+  const int ws = conv_mfma_row_stride(win);
+  int s = cd * win * ws;
+  while ((s - 2 * ((win - 2) / 2 - 1) * ws - (win - 2)) % 16) s++;
+  return s;
+}
+
 // WIN: input width (square map), CD: input dwords per pixel (2: 64 channels, 4: 128), NT: neuron tiles (output dwords
 // per pixel), POOL: 2x2 max-pool behind, G: images per block and group.  Layer 1 (NT = 2): waves w and w + 2 own the
 // same neuron tile and take alternate pixel tiles.
 template <int WIN, int CD, int NT, bool POOL, int G>
 __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
                                                        const uint8_t *__restrict__ tab, int n_images) {
-  constexpr int WOUT = WIN - 2, RP = WOUT / 2, IPI = RP * WOUT, KH = CD / 2, KS = 9 * KH, STREAMS = 4 / NT;
+  constexpr int WOUT = WIN - 2, RP = WOUT / 2, IPI = RP * WOUT, KH = CD / 2, KS = 9 * KH, NS = 3 * KH, STREAMS = 4 / NT;
   constexpr int PIX = WIN * WIN, DWI = PIX * CD, NPF = (G * DWI + 255) / 256;
+  constexpr int WS = conv_mfma_row_stride(WIN), PIXS = WIN * WS, IMGS = conv_mfma_img_stride(WIN, CD);  // 30 / 14 / 13 pixels, 1800 / 392 / 626 slots
   static_assert(WOUT % 2 == 0 && IPI % 2 == 0 && (NT == 2 || NT == 4), "tile geometry");
-  __shared__ uint4 plane[G][CD][PIX];
+  __shared__ uint4 plane[G * IMGS];  // [image][32-channel block q][row][column], strides IMGS, PIXS, WS, 1
   __shared__ uint32_t lut[256];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mt = wave % NT, c = lane & 31, h = lane >> 5;
   lut[tid] = fp4_pm1((uint32_t)tid);
@@ -742,6 +764,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
       pre[j] = d < lim ? in[(size_t)img0 * DWI + d] : 0u;
     }
   };
+  // source dword d of the group (32 channels of a pixel) -> its 16-byte slot in the planes
+  auto slot = [&](int d) {
+    const int i = d / DWI, e = d - i * DWI, pix = e / CD, q = e % CD;
+    return i * IMGS + q * PIXS + (WS == WIN ? pix : pix / WIN * WS + pix % WIN);
+  };
   if (blockIdx.x < ngroups) fetch(blockIdx.x);
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int img0 = grp * G, nimg = min(G, n_images - img0), nitems = nimg * IPI;
@@ -750,9 +777,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
     for (int j = 0; j < NPF; j++) {  // one source dword (32 channels of a pixel) per iteration
       const int d = tid + 256 * j;
       if (d < nimg * DWI) {
-        const int i = d / DWI, e = d - i * DWI, pix = e / CD, q = e % CD;
         const uint32_t bits = pre[j];
-        plane[i][q][pix] = make_uint4(lut[bits & 255], lut[(bits >> 8) & 255], lut[(bits >> 16) & 255], lut[bits >> 24]);
+        plane[slot(d)] = make_uint4(lut[bits & 255], lut[(bits >> 8) & 255], lut[(bits >> 16) & 255], lut[bits >> 24]);
       }
     }
     if (grp + (int)gridDim.x < ngroups) fetch(grp + gridDim.x);
@@ -761,25 +787,32 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
       const int item = min(t0 + c, nitems - 1);
       const int i = item / IPI, rem = item - i * IPI, rp = rem / WOUT, x = rem - rp * WOUT;
       v16f acc[2] = {seed, seed};  // output rows 2rp, 2rp + 1
+      const uint4 *__restrict__ P = &plane[i * IMGS + h * PIXS + 2 * rp * WS + x];
+      // step s = 3 kh + kx: input rows 2rp .. 2rp + 3 at column x + kx of channel block 2 kh + h (4 ds_read_b128), then the
+      // 6 MFMAs of output rows 2rp, 2rp + 1 x ky
+      auto read = [&](v8i &b, int s, int y) {  // input row 2rp + y
+        const uint4 v = P[(s / 3) * 2 * PIXS + y * WS + s % 3];
+        b = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+      };
+      auto mfma = [&](const v8i (&b)[4], int s, int k) {  // k = 2 ky + dy
+        acc[k & 1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wreg[((k >> 1) * 3 + s % 3) * KH + s / 3], b[(k >> 1) + (k & 1)], acc[k & 1], 4,
+                                                                    4, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+      };
+      // The four reads of step s + 1 are issued behind the first four MFMAs of step s, into the other register set: an
+      // MFMA waits only for the read it consumes (counted lgkmcnt) and that read is five MFMAs old.  The instruction
+      // scheduler would sink every read to just before its use again: the scheduling barriers keep this order.
+      v8i b[2][4];
 #pragma unroll
-      for (int kh = 0; kh < KH; kh++) {
-        const uint4 *__restrict__ P = &plane[i][kh * 2 + h][2 * rp * WIN + x];
+      for (int y = 0; y < 4; y++) read(b[0][y], 0, y);
 #pragma unroll
-        for (int kx = 0; kx < 3; kx++) {
-          v8i b[4];  // input rows 2rp .. 2rp + 3 at column x + kx
+      for (int s = 0; s < NS; s++)
 #pragma unroll
-          for (int y = 0; y < 4; y++) {
-            const uint4 v = P[y * WIN + kx];
-            b[y] = v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
-          }
-#pragma unroll
-          for (int ky = 0; ky < 3; ky++)
-#pragma unroll
-            for (int dy = 0; dy < 2; dy++)
-              acc[dy] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wreg[(ky * 3 + kx) * KH + kh], b[ky + dy], acc[dy], 4, 4, 0,
-                                                                         0x7F7F7F7F, 0, 0x7F7F7F7F);
+        for (int k = 0; k < 6; k++) {
+          __builtin_amdgcn_sched_barrier(0);
+          mfma(b[s & 1], s, k);
+          if (s + 1 < NS && k < 4) read(b[(s + 1) & 1][k], s + 1, k);
         }
-      }
+      __builtin_amdgcn_sched_barrier(0);
       const bool valid = t0 + c < nitems;
       const size_t img = (size_t)(img0 + i);
       if constexpr (POOL) {

@@ -26,7 +26,9 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_last_act_noise_seeds", "bnn_mi355x_act_noise_mask", "bnn_mi355x_enumerate_input_faults",
        "bnn_mi355x_input_fault_sweep", "bnn_mi355x_last_input_sweep_stages", "bnn_mi355x_input_noise_campaigns",
        "bnn_mi355x_last_input_noise_counts", "bnn_mi355x_last_input_noise_seeds", "bnn_mi355x_input_noise_mask",
-       "bnn_mi355x_sweep_profile", "bnn_mi355x_last_sweep_profile"]
+       "bnn_mi355x_sweep_profile", "bnn_mi355x_last_sweep_profile", "bnn_mi355x_mem_noise_campaigns",
+       "bnn_mi355x_last_mem_noise_counts", "bnn_mi355x_last_mem_noise_seeds", "bnn_mi355x_mem_noise_mask",
+       "bnn_mi355x_mem_noise_params"]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -117,6 +119,16 @@ def declare_extensions(L):
         L.bnn_mi355x_sweep_profile.argtypes = [C.c_int]
         L.bnn_mi355x_last_sweep_profile.argtypes = [C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_long, ip]
         L.bnn_mi355x_last_sweep_profile.restype = C.c_long
+    if hasattr(L, "bnn_mi355x_mem_noise_campaigns"):  # (likewise)
+        up = C.POINTER(C.c_uint)
+        L.bnn_mi355x_mem_noise_campaigns.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_ulonglong, up, up, C.c_int, ip, fp]
+        L.bnn_mi355x_mem_noise_campaigns.restype = ip
+        L.bnn_mi355x_last_mem_noise_counts.argtypes = [C.POINTER(C.c_long), C.c_int]
+        L.bnn_mi355x_last_mem_noise_seeds.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+        L.bnn_mi355x_mem_noise_mask.argtypes = [C.c_ulonglong, C.c_int, C.c_int, C.c_uint, C.c_long, ip, C.c_int]
+        L.bnn_mi355x_mem_noise_mask.restype = C.c_long
+        L.bnn_mi355x_mem_noise_params.argtypes = [C.c_ulonglong, up, up, C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_mem_noise_params.restype = C.c_size_t
     L.bnn_mi355x_pack_params_faulty.argtypes = [C.c_char_p, ip, C.c_int, C.c_void_p, C.c_size_t]
     L.bnn_mi355x_pack_params_faulty.restype = C.c_size_t
     L.bnn_mi355x_debug_stage_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]

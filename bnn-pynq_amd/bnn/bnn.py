@@ -332,6 +332,45 @@ class PynqBNN:
         self.usecPerImage = usec.value
         return result, np.array(counts[:k], np.int64).reshape(num_runs, -1)
 
+    # extension: memory upset-rate campaigns (every bit of the weight / threshold memories upset with probability p)
+    def mem_noise_rates(self, rates, thresholds=False):
+        """rates as probabilities in [0, 1) -- a scalar for every layer (thresholds: every layer that has threshold memory),
+        or one per layer -- -> uint32 array of floor(p * 2^32), the unit of bnn_mi355x_mem_noise_campaigns"""
+        cnv = self.interface.bnn_mi355x_network().startswith(b"cnv")
+        layers = 9 if cnv else 4
+        p = np.full(layers, float(rates)) if np.isscalar(rates) else np.asarray(list(rates), np.float64)
+        if np.isscalar(rates) and thresholds and cnv:
+            p[8] = 0.0  # (CNV layer 8 passes its accumulators through: no threshold memory)
+        if p.shape != (layers,) or (p < 0).any() or (p >= 1).any():
+            raise ValueError("rates: a probability in [0, 1) for each of the {} layers".format(layers))
+        return np.floor(p * 4294967296.0).astype(np.uint64).astype(np.uint32)
+
+    def inference_multiple_mem_noise(self, path, num_runs, rates_w, rates_t, seed=0):
+        """num_runs independent runs over the images of `path`, every bit of layer L's weight memory flipped with
+        probability rates_w[L] and every bit of its threshold memory with rates_t[L] (mem_noise_rates), in place from the
+        first image on; run r draws with seed + r (seed 0: every run's seed from std::random_device, then in
+        self.mem_noise_seeds).  -> (classes int32 (num_runs, n), counts int64 (num_runs, layers, 2): the flips actually
+        applied per run, layer and memory kind (0 weights, 1 thresholds)).  The loaded parameters are not changed.
+        usecPerImage: device time of the call / (num_runs * n)."""
+        lib = self.interface
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_mem_noise_campaigns(path.encode(), len(self.classes), num_runs, seed, qw.ctypes.data_as(up),
+                                                 qt.ctypes.data_as(up), len(qw), ctypes.byref(size), ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("memory noise campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_mem_noise_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_mem_noise_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_mem_noise_seeds(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2)
+
     # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
     def enumerate_input_faults(self):
         """-> int32 array (image_bytes * 8, 2): every bit of the input image as records {byte, bit} in site order (byte in
@@ -605,6 +644,15 @@ class CnvClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
+    # extension: memory upset-rate campaigns (PynqBNN.inference_multiple_mem_noise)
+    def classify_images_mem_noise(self, imgs, num_runs, rates_w, rates_t, seed=0):
+        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_mem_noise(p, num_runs, rates_w, rates_t, seed))
+
+    def classify_cifars_mem_noise(self, path, num_runs, rates_w, rates_t, seed=0):
+        result = self.bnn.inference_multiple_mem_noise(path, num_runs, rates_w, rates_t, seed)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
     # extension: input-buffer faults (PynqBNN.input_fault_sweep, PynqBNN.inference_multiple_input_noise)
     def classify_images_input_fault_sweep(self, imgs, records, max_diffs=None):
         return self._with_tmp(imgs, lambda p: self.bnn.input_fault_sweep(p, records, max_diffs))
@@ -694,6 +742,11 @@ class LfcClassifier:
 
     def classify_mnists_act_noise(self, mnist_format_file, num_runs, rates, seed=0):
         result = self.bnn.inference_multiple_act_noise(mnist_format_file, num_runs, rates, seed)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_mnists_mem_noise(self, mnist_format_file, num_runs, rates_w, rates_t, seed=0):
+        result = self.bnn.inference_multiple_mem_noise(mnist_format_file, num_runs, rates_w, rates_t, seed)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

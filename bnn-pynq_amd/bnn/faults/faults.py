@@ -24,6 +24,10 @@ single activation of a layer's output, moved to another level while one image pa
 every activation of the chosen layers' outputs upset with probability p, independently per run, image and site
 (``PynqBNN.inference_multiple_act_noise``), with the spread over the runs and the rate the runs actually saw.
 
+``FaultTest.run_memory_noise_test`` / ``NetworkTest.memory_upset_rate_curve`` give the same curve for the parameter
+memories: every bit of the weight / threshold memories flipped with probability p per run, in place from the first image
+on (``PynqBNN.inference_multiple_mem_noise``), per memory kind and layer set.
+
 ``FaultTest.input_sensitivity`` / ``NetworkTest.input_sensitivity_map`` and ``FaultTest.run_input_noise_test`` /
 ``NetworkTest.input_upset_rate_curve`` are their twins for the image buffer every classification starts from: every
 single bit of the input image flipped alone (``PynqBNN.input_fault_sweep``), and every bit flipped with probability p
@@ -213,6 +217,22 @@ class FaultTest:
         print("Accuracies:", accuracies)
         print()
         return accuracies
+
+    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0):
+        """num_runs independent runs with every bit of layer L's weight memory flipped with probability rates_w[L] and
+        every bit of its threshold memory with rates_t[L] (scalars: every layer; thresholds: every layer that has any), in
+        place from the first image on -> (accuracy per run in percent, flips applied [run, layer, 2: weights,
+        thresholds]).  Run r draws with seed + r (0: std::random_device).  Left behind: self.mem_noise_results (classes,
+        [run, image]), self.mem_noise_counts and self.mem_noise_usec (device time per image of every run)."""
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        print("{}-{}: {} run(s) in one call, memory upset rate(s) weights {} thresholds {}".format(
+            self.network, self.dataset, num_runs, rates_w, rates_t))
+        results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed)
+        self.mem_noise_results, self.mem_noise_counts, self.mem_noise_usec = results, counts, classifier.usecPerImage
+        accuracies = [util.calculate_accuracy(row.tolist(), self.labels) for row in results]
+        print("Accuracies:", accuracies)
+        print()
+        return accuracies, counts
 
     def input_sensitivity(self, records=None):
         """Single input-bit faults: each record {byte, bit} (None: every bit of the image, in site order) flipped alone
@@ -473,6 +493,44 @@ class NetworkTest:
                 out = "{}/{}_{}_rate{:g}_stats".format(folder, ft.network, ft.dataset, p)
                 out += ".json" if len(which) == nl else "_layer{}.json".format(which)
                 util.write_dict_to_file(out, stats)
+
+    def memory_upset_rate_curve(self, output_folder, num_runs, rates, layers=(), targets=("weights", "thresholds"), seed=0):
+        """The accuracy-versus-upset-rate curve of the parameter memories (FaultTest.run_memory_noise_test), per memory
+        kind.  `layers`: layer sets -- each a list of layers whose memories are upset, or one layer number; empty: one set,
+        every layer (thresholds: every layer that has threshold memory).  Per target one file in the format of
+        upset_rate_curve, output_folder/<network>/<dataset>/memory-upsets/<network>_<dataset>_<target>_stats.json, with
+        one result per (layer set, rate p): the runs' accuracies with min / max / average and the effective runs, plus
+        "stddev accuracy", the nominal "rate", the "effective rate" the runs actually saw (flips applied / bits exposed)
+        and the flips per layer summed over the runs."""
+        ft = self.fault_test
+        folder = "{}/{}/{}/memory-upsets/".format(output_folder, ft.network, ft.dataset)
+        if self.control is None:  # (rate 0: the fault-free classes)
+            self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
+        classifier = ft.classifier_cls(ft.network, ft.dataset, ft.runtime)
+        nl = len(classifier.bnn.mem_noise_rates(0.0))
+        for target in targets:
+            t = {"weights": 0, "thresholds": 1}[target]
+            bits = np.array([len(classifier.bnn.enumerate_faults(l, t, 1)) for l in range(nl)])
+            have = [l for l in range(nl) if bits[l]]
+            sets = [[int(l)] if np.isscalar(l) else [int(x) for x in l] for l in layers] or [have]
+            raw = []
+            extra = {}
+            for which in sets:
+                for p in rates:
+                    per_layer = [float(p) if l in which else 0.0 for l in range(nl)]
+                    zeros = [0.0] * nl
+                    accuracies, counts = ft.run_memory_noise_test(num_runs, zeros if t else per_layer, per_layer if t else zeros, seed)
+                    name = "{} upset rate {:g}".format(target, p) + ("" if which == have else " layer{}".format(which))
+                    raw.append(self._raw(name, num_runs, 0, which, accuracies))
+                    exposed = float(bits[which].sum()) * num_runs
+                    extra[name] = {"stddev accuracy": float(np.std(accuracies)), "rate": float(p), "layers": which,
+                                   "effective rate": float(counts[:, which, t].sum()) / exposed if exposed else 0.0,
+                                   "flips per layer": [int(c) for c in counts[:, :, t].sum(axis=0)]}
+            stats = self._stats(util.dict_of_dicts_merge(*raw))
+            stats["layers"] = sorted({l for which in sets for l in which})
+            for name, e in extra.items():
+                stats["results"][name].update(e)
+            util.write_dict_to_file("{}/{}_{}_{}_stats.json".format(folder, ft.network, ft.dataset, target), stats)
 
     def input_sensitivity_map(self, output_folder):
         """The input-bit sweep (FaultTest.input_sensitivity) over every bit of the image, next to sensitivity_map's files:

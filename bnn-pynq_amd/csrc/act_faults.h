@@ -34,11 +34,14 @@ std::string check_act_fault(const NetSpec &net, const ActSite &s);
 //   u = philox4x32_10(counter {i, L, s >> 2, 0}, key {k & 0xffffffff, k >> 32})[s & 3];  upset iff u < rate,
 // with shift 1 + (u & 1) for 2-bit activations, 1 for 1-bit ones.  The host (act_noise_mask) and the kernel that
 // applies the upsets (kernels.hip, k_act_noise) both call act_noise_block: one block serves four consecutive sites.
+// `tag` is the fourth counter word: 0 for the activation and the input draws, 1 for the parameter memories' (mem_faults.h),
+// whose first three words are (layer, target, block) -- so the models never share a stream.
 #ifndef BNN_HD
 #define BNN_HD
 #endif
-BNN_HD inline void act_noise_block(uint32_t key0, uint32_t key1, uint32_t image, uint32_t layer, uint32_t block, uint32_t out[4]) {
-  uint32_t c0 = image, c1 = layer, c2 = block, c3 = 0;
+BNN_HD inline void act_noise_block(uint32_t key0, uint32_t key1, uint32_t image, uint32_t layer, uint32_t block, uint32_t out[4],
+                                   uint32_t tag = 0) {
+  uint32_t c0 = image, c1 = layer, c2 = block, c3 = tag;
 #pragma unroll
   for (int r = 0; r < 10; r++) {  // Philox4x32-10 (Salmon et al., SC'11)
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;

@@ -199,4 +199,20 @@ hipError_t input_seed(const uint8_t *images, int image_bytes, const MultiSeg *se
 hipError_t input_noise(const uint8_t *images, int image_bytes, unsigned long long pair0, int npairs, int n, const unsigned long long *seeds,
                        uint32_t rate_q32, unsigned long long *counts, uint8_t *staged, hipStream_t s);
 
+// Random upsets of the parameter memories (bnn_mi355x_mem_noise_campaigns; the model: mem_faults.h).  All three work in
+// place on `runs` copies of the blob, run q at copies + q * stride (a multiple of 256), on one layer whose weight
+// elements are not int8 and whose threshold elements are 16 bits wide: `offset` ... `kw` as the blob's header has them,
+// `pe` / `tmem` the layer's fold (row n lies in PE n % pe, at fold n / pe), `layer` its index.  Nothing is launched
+// for rate 0.  counts: [run][nlayers][2: weights, thresholds], += the sites flipped.
+struct MemNoiseLayer { uint32_t offset, row_dwords, rows, kw, pe, tmem, layer; };
+// weights: every site of the layer's rows flipped where the draw of (seeds[run], layer, 0, site) says so; two_bit: AR_TT
+// rows (three planes and a flag dword, set where a word now holds a -2)
+hipError_t mem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
+                       uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
+// AR_TT rows: every row's flag dword recomputed from its "weight is -2" plane (a flip can also remove a -2)
+hipError_t mem_noise_flags(uint8_t *copies, size_t stride, int runs, const MemNoiseLayer &L, hipStream_t s);
+// thresholds: raw[n * nthr + i] is the low 16 bits of neuron n's i-th threshold word in the loaded memories (device)
+hipError_t mem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
+                       bool signed_bb, const uint16_t *raw, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
+
 }  // namespace bnn

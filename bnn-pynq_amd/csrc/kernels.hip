@@ -45,6 +45,7 @@
 #include "act_faults.h"
 #include "input_faults.h"
 #include "kernels.h"
+#include "mem_faults.h"
 #include "packed_params.h"
 static_assert(bnn::kL0TileOffset == (int)bnn::kL0MfmaTileOffset && bnn::kL0BigBytes == (int)bnn::kL0MfmaBigBytes,
               "k_conv0_tile's operand offsets must be the ones packed_params.cpp writes the layer-0 table by");
@@ -2959,6 +2960,116 @@ __global__ __launch_bounds__(kBlock) void k_input_noise(const uint8_t *__restric
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + run, (unsigned long long)c);
 }
 
+// Random upsets of the parameter memories (bnn_mi355x_mem_noise_campaigns): in place on the runs' copies of the blob,
+// run blockIdx.y `stride` bytes behind run 0.  The draw is mem_faults.h's: act_noise_block of (seed, layer, target,
+// site >> 2) with the tag in the fourth counter word.  A neuron's weights are one contiguous run of MW * wbits sites
+// from ((n % PE) * TMEM + n / PE) * MW * wbits on (its SF memory words follow each other, fill_row), MW = 64 * kw.
+// k_mem_noise_w: a lane per 64-column word of one (run, row).  1-bit weights: 64 sites = 16 Philox blocks, the mask
+// XORed into the stored u64 (the plane's polarity does not matter to a flip).  2-bit weights (AR_TT): 128 sites = 32
+// blocks, site 2j the low and 2j + 1 the high bit of column j's ap_int<2> field (0 -> 0, 1 -> +1, 2 -> -2, 3 -> -1);
+// the field is read back from the three planes (high = sign, low = non-zero without "is -2"), flipped, and the planes
+// rebuilt the way fill_row derives them; a word that now holds a -2 sets the row's flag dword.  A lane without a flip
+// stores nothing; the wave's flips go to counts[run][layer][0] with one atomic (no lane has left).  No LDS.
+template <bool TWO_BIT>
+__global__ __launch_bounds__(kBlock) void k_mem_noise_w(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L,
+                                                        const unsigned long long *__restrict__ seeds, unsigned rate,
+                                                        unsigned long long *__restrict__ counts, unsigned nlayers) {
+  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
+  unsigned c = 0;
+  if (t < L.rows * L.kw) {
+    const unsigned n = t / L.kw, k = t - n * L.kw;
+    const unsigned long long seed = seeds[run];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    constexpr unsigned kSites = TWO_BIT ? 128 : 64;
+    const uint32_t block0 = (((n % L.pe) * L.tmem + n / L.pe) * L.kw + k) * (kSites / 4);
+    uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
+    if constexpr (!TWO_BIT) {
+      uint64_t m = 0;
+#pragma unroll
+      for (int b = 0; b < 16; b++) {
+        uint32_t u[4];
+        act_noise_block(k0, k1, L.layer, 0u, block0 + b, u, kMemNoiseTag);
+#pragma unroll
+        for (int e = 0; e < 4; e++) m |= (uint64_t)(u[e] < rate ? 1u : 0u) << (4 * b + e);
+      }
+      if (m) {
+        uint64_t *const w = reinterpret_cast<uint64_t *>(row + 2) + k;
+        *w ^= m;
+      }
+      c = __popcll(m);
+    } else {
+      uint64_t mlo = 0, mhi = 0;
+#pragma unroll
+      for (int b = 0; b < 32; b++) {
+        uint32_t u[4];
+        act_noise_block(k0, k1, L.layer, 0u, block0 + b, u, kMemNoiseTag);
+        mlo |= (uint64_t)((u[0] < rate ? 1u : 0u) | (u[2] < rate ? 2u : 0u)) << (2 * b);
+        mhi |= (uint64_t)((u[1] < rate ? 1u : 0u) | (u[3] < rate ? 2u : 0u)) << (2 * b);
+      }
+      if (mlo | mhi) {
+        uint64_t *const wq = reinterpret_cast<uint64_t *>(row + 2);
+        const uint64_t neg = wq[2 * k], nz = wq[2 * k + 1], two = wq[2 * L.kw + k];
+        const uint64_t hi = neg ^ mhi, lo = (nz & ~two) ^ mlo, two2 = hi & ~lo;
+        wq[2 * k] = hi;
+        wq[2 * k + 1] = hi | lo;
+        wq[2 * L.kw + k] = two2;
+        if (two2) atomicOr(row + 2 + 6 * L.kw, 1u);
+      }
+      c = __popcll(mlo) + __popcll(mhi);
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + ((size_t)run * nlayers + L.layer) * 2, (unsigned long long)c);
+}
+
+// A flip can also remove a -2 the call started with: then every (run, row)'s flag is recomputed from its "is -2" plane
+// behind k_mem_noise_w, a lane per row.
+__global__ __launch_bounds__(kBlock) void k_mem_noise_flags(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L) {
+  const unsigned run = blockIdx.y, n = blockIdx.x * kBlock + threadIdx.x;
+  if (n >= L.rows) return;
+  uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
+  const uint64_t *const two = reinterpret_cast<const uint64_t *>(row + 2) + 2 * L.kw;
+  uint64_t any = 0;
+  for (unsigned k = 0; k < L.kw; k++) any |= two[k];
+  row[2 + 6 * L.kw] = any ? 1u : 0u;
+}
+
+// k_mem_noise_t: thresholds of the layers whose elements are 16 bits wide.  A lane per (run, neuron n, threshold i): the
+// word's 16 sites from (((n % PE) * TMEM + n / PE) * nthr + i) * 16 on = 4 blocks.  On a hit the raw 16-bit word
+// (raw[n * nthr + i], from the loaded memories) is XORed with the mask, sign-extended and stored as the row's dword t_i
+// through fill_row's own transform (both dwords for a layer with one threshold).  Counts to counts[run][layer][1].
+__global__ __launch_bounds__(kBlock) void k_mem_noise_t(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L, unsigned nthr,
+                                                        Arith arith, bool signed_bb, const uint16_t *__restrict__ raw,
+                                                        const unsigned long long *__restrict__ seeds, unsigned rate,
+                                                        unsigned long long *__restrict__ counts, unsigned nlayers) {
+  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t m = 0;
+  if (t < L.rows * nthr) {
+    const unsigned n = t / nthr, i = t - n * nthr;
+    const unsigned long long seed = seeds[run];
+    const uint32_t block0 = (((n % L.pe) * L.tmem + n / L.pe) * nthr + i) * 4;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      uint32_t u[4];
+      act_noise_block((uint32_t)seed, (uint32_t)(seed >> 32), L.layer, 1u, block0 + b, u, kMemNoiseTag);
+#pragma unroll
+      for (int e = 0; e < 4; e++) m |= (u[e] < rate ? 1u : 0u) << (4 * b + e);
+    }
+    if (m) {
+      uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
+      const int32_t T = (int16_t)(uint16_t)(raw[t] ^ m);
+      const uint32_t v = (uint32_t)packed_threshold(arith, signed_bb, 64 * (int)L.kw, T);
+      row[i] = v;
+      if (nthr == 1) row[1] = v;
+    }
+  }
+  unsigned c = __popc(m);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + ((size_t)run * nlayers + L.layer) * 2 + 1, (unsigned long long)c);
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -3702,5 +3813,36 @@ hipError_t input_noise(const uint8_t *images, int image_bytes, unsigned long lon
   hipLaunchKernelGGL(k_input_noise, g, dim3(kBlock), 0, s, images, staged, units, upp, pair0, (unsigned)npairs, (unsigned)n, seeds, rate_q32, counts);
   return hipGetLastError();
 }
+
+hipError_t mem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
+                       uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s) {
+  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
+  if (runs > 65535 || L.kw == 0 || L.rows == 0 || stride % 256 || L.offset % 8 || L.row_dwords % 2 ||
+      L.row_dwords < (two_bit ? 4 + 6 * L.kw : 2 + 2 * L.kw))
+    return hipErrorInvalidValue;
+  const dim3 g((L.rows * L.kw + kBlock - 1) / kBlock, (unsigned)runs);
+  if (two_bit) hipLaunchKernelGGL(k_mem_noise_w<true>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, seeds, rate_q32, counts, (unsigned)nlayers);
+  else hipLaunchKernelGGL(k_mem_noise_w<false>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, seeds, rate_q32, counts, (unsigned)nlayers);
+  return hipGetLastError();
+}
+
+hipError_t mem_noise_flags(uint8_t *copies, size_t stride, int runs, const MemNoiseLayer &L, hipStream_t s) {
+  if (runs <= 0) return hipSuccess;
+  if (runs > 65535 || L.kw == 0 || L.rows == 0 || stride % 256 || L.offset % 8 || L.row_dwords < 4 + 6 * L.kw) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_mem_noise_flags, dim3((L.rows + kBlock - 1) / kBlock, (unsigned)runs), dim3(kBlock), 0, s, copies, (unsigned long long)stride, L);
+  return hipGetLastError();
+}
+
+hipError_t mem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
+                       bool signed_bb, const uint16_t *raw, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s) {
+  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
+  if (runs > 65535 || L.rows == 0 || stride % 256 || L.offset % 4 || nthr < 1 || nthr > 2 || L.row_dwords < 2 || arith == AR_INT8 || !raw)
+    return hipErrorInvalidValue;
+  const dim3 g((L.rows * (unsigned)nthr + kBlock - 1) / kBlock, (unsigned)runs);
+  hipLaunchKernelGGL(k_mem_noise_t, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)nthr, arith, signed_bb, raw, seeds, rate_q32,
+                     counts, (unsigned)nlayers);
+  return hipGetLastError();
+}
+
 
 }  // namespace bnn

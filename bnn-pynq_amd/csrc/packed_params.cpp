@@ -58,13 +58,7 @@ void fill_row(const LayerSpec &L, const LayerView &F, int n, uint32_t *row, uint
   int32_t T[2] = {0, 0};
   for (int i = 0; i < L.nthr && i < 2; i++) T[i] = F.threshold(n, i);
   if (L.nthr == 1) T[1] = T[0];
-  for (int i = 0; i < 2; i++) {
-    int32_t t;
-    if (L.arith == AR_INT8) t = floor_div2(T[i]);
-    else if (L.arith == AR_XNOR) t = L.signed_bb ? floor_div2(MW - T[i] + 1) : (MW - T[i]);
-    else t = T[i];
-    row[i] = (uint32_t)t;
-  }
+  for (int i = 0; i < 2; i++) row[i] = (uint32_t)packed_threshold(L.arith, L.signed_bb, MW, T[i]);
   if (L.arith == AR_INT8) {
     // tap tau = 3*(c*3+ky) + kx  <->  reference column (ky*3+kx)*3 + c
     for (int c = 0; c < 3; c++)
@@ -266,6 +260,21 @@ void repack_row(const NetSpec &net, const RawParams &raw, int l, int n, std::vec
     *offset = h.layer[0].offset;
     *bytes = (size_t)h.l0_mfma_offset + kL0MfmaBytes - h.layer[0].offset;
   }
+}
+
+void repack_row_only(const NetSpec &net, const RawParams &raw, int l, int n, std::vector<uint8_t> &blob) {
+  PackedHeader h;
+  std::memcpy(&h, blob.data(), sizeof(h));
+  const LayerSpec &L = net.L[l];
+  const LayerView F{&L, &raw.w[l], &raw.t[l]};
+  const uint32_t rd = h.layer[l].row_dwords;
+  fill_row(L, F, n, reinterpret_cast<uint32_t *>(blob.data() + h.layer[l].offset + (size_t)n * rd * 4), rd);
+}
+
+void repack_l0_tables(const NetSpec &net, const RawParams &raw, std::vector<uint8_t> &blob) {
+  PackedHeader h;
+  std::memcpy(&h, blob.data(), sizeof(h));
+  if (h.l0_mfma_offset) fill_l0_mfma(net, raw, blob.data() + h.l0_mfma_offset);
 }
 
 std::string pack_params_from_dir(const NetSpec &net, const std::string &dir, std::vector<uint8_t> &blob) {

@@ -86,6 +86,17 @@ static_assert(sizeof(PackedHeader) == 32 + 9 * 16, "blob header layout");
 
 uint32_t row_dwords_for(const LayerSpec &L);
 
+// Dword t_i of a row from the threshold T_i as the files hold it (the table above): what fill_row stores, and what the
+// kernel that upsets threshold words in place (kernels.hip, k_mem_noise_t) stores again from the upset word.
+#ifndef BNN_HD
+#define BNN_HD
+#endif
+BNN_HD inline int32_t packed_threshold(Arith arith, bool signed_bb, int mw, int32_t T) {
+  if (arith == AR_INT8) return T >> 1;  // floor(T / 2): an arithmetic shift
+  if (arith == AR_XNOR) return signed_bb ? (mw - T + 1) >> 1 : mw - T;
+  return T;
+}
+
 // The reference's PE memories exactly as the files hold them (what DoMemInit / DoMemRead see,
 // top.cpp:78-178): per layer, per PE, WMEM weight words and TMEM*nThr threshold words.  Kept on the
 // host next to the blob so that single words can be modified (fault injection,
@@ -100,6 +111,10 @@ void pack_blob(const NetSpec &net, const RawParams &raw, std::vector<uint8_t> &b
 // rebuild row n of layer l inside an existing blob; returns the byte offset and size of that row
 void repack_row(const NetSpec &net, const RawParams &raw, int l, int n, std::vector<uint8_t> &blob, size_t *offset,
                 size_t *bytes);
+// The two halves of repack_row for a caller that rebuilds many layer-0 rows of a CNV net at once: the row alone, and the
+// matrix-pipe tables behind the rows (which repack_row rebuilds after every layer-0 row), once at the end.
+void repack_row_only(const NetSpec &net, const RawParams &raw, int l, int n, std::vector<uint8_t> &blob);
+void repack_l0_tables(const NetSpec &net, const RawParams &raw, std::vector<uint8_t> &blob);
 
 // Reads the param directory and fills `blob`.  Returns "" on success, else the
 // error text (missing file: the reference throws "Could not open file",

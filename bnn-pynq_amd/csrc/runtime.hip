@@ -46,6 +46,7 @@
 #include "faults.h"
 #include "act_faults.h"
 #include "input_faults.h"
+#include "mem_faults.h"
 #include "kernels.h"
 #include "preprocess.h"
 #include "resample.h"
@@ -276,6 +277,10 @@ struct Runtime {
   size_t in_stage_cap = 0;
   std::vector<long> input_sweep_pairs, input_noise_counts;
   std::vector<unsigned long long> input_noise_seeds;
+  // bnn_mi355x_mem_noise_campaigns (the runs' blob copies: d_copies; patches and threshold tables: d_camp; seeds and counters:
+  // d_noise): the [run][layer][2] flips and the seeds of the last such call
+  std::vector<long> mem_noise_counts;
+  std::vector<unsigned long long> mem_noise_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -3172,6 +3177,351 @@ long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigne
     }
   }
   return total;
+}
+
+// ---- memory upset-rate campaigns (the model: mem_faults.h) ---------------------------------------------------------------
+
+// the argument checks of both entry points, then what every parameter-fault entry point refuses; nothing touches a device
+// before they have passed (ready() is the first thing that may)
+static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  if (!rate_w_q32 || !rate_t_q32 || n_rates != net.nlayers)
+    return fail(std::string(who) + ": bad arguments (a rate array missing, or n_rates is not " + std::to_string(net.nlayers) + ": one rate per layer)");
+  for (int l = 0; l < net.nlayers; l++)
+    if (rate_t_q32[l] != 0 && net.L[l].nthr == 0)
+      return fail(std::string(who) + ": layer " + std::to_string(l) + " has no threshold memory (its threshold rate must be 0)");
+#ifdef BNN_VARIANT
+  return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+#endif
+  if (!ready()) return -1;
+  if (r.raw.empty()) return fail("fault injection needs the parameter files (load_parameters), not an imported blob");
+  if (r.l1_mfma || r.l1_literal)
+    return fail("fault injection is not wired to the BNN_MI355X_L1 comparison forms (the matrix-pipe table is not patched)");
+  return 0;
+}
+
+// What the host prepares for the runs' copies: the patches of layer 0 of the CNV nets (int8 taps, 24-bit thresholds that
+// apply_fault reads back as their integer part, three table forms: drawn and applied here, fault_campaigns' way) and the raw
+// 16-bit threshold words of the layers whose threshold rate is not 0, for k_mem_noise_t.
+struct MemNoiseJob {
+  size_t stride = 0, spans_off = 0, tab_off[9] = {};
+  int nspans = 0;
+  std::vector<uint8_t> upload;                  // patch bytes | patch spans | threshold tables
+  std::vector<unsigned long long> host_counts;  // [run][layer][2]: the flips the host applied
+};
+
+static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, MemNoiseJob &job) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  const int R = (int)seeds.size(), S = net.nlayers;
+  PackedHeader h;
+  std::memcpy(&h, r.blob.data(), sizeof(h));
+  job.stride = (r.blob.size() + 255) & ~(size_t)255;
+  job.host_counts.assign((size_t)R * S * 2, 0);
+  std::vector<uint8_t> staging;
+  std::vector<PatchSpan> spans;
+  if (net.L[0].arith == AR_INT8 && (rw[0] || rth[0])) {
+    // ONE working copy of layer 0's memories and of the blob: a run's flips applied in order, the rebuilt rows and tables
+    // recorded as its patches, then both restored
+    RawParams raw;  // (layer 0's memories alone: nothing else is read here)
+    raw.w[0] = r.raw.w[0];
+    raw.t[0] = r.raw.t[0];
+    std::vector<uint8_t> blob = r.blob;
+    const size_t rb = (size_t)h.layer[0].row_dwords * 4, rows_bytes = rb * h.layer[0].rows;
+    std::vector<Fault> flips;
+    std::vector<char> touched(h.layer[0].rows);
+    for (int q = 0; q < R; q++) {
+      flips.clear();
+      for (int target = 0; target < 2; target++) {
+        const uint32_t rate = target ? rth[0] : rw[0];
+        const long k = mem_noise_mask(net, seeds[(size_t)q], 0, target, rate, 0, nullptr, 0);
+        const size_t at = flips.size();
+        flips.resize(at + (size_t)k);
+        mem_noise_mask(net, seeds[(size_t)q], 0, target, rate, 0, flips.data() + at, k);
+        job.host_counts[((size_t)q * S + 0) * 2 + target] = (unsigned long long)k;
+      }
+      if (flips.empty()) continue;
+      std::fill(touched.begin(), touched.end(), 0);
+      for (const Fault &f : flips) {
+        const int row = apply_fault(net, raw, f);
+        if (row < 0 || row >= (int)h.layer[0].rows) return fail("internal: mem_noise flip outside layer 0");
+        touched[(size_t)row] = 1;
+      }
+      auto add_span = [&](size_t off, size_t bytes) {
+        spans.push_back(PatchSpan{(uint64_t)q * job.stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
+        staging.insert(staging.end(), blob.begin() + off, blob.begin() + off + bytes);
+      };
+      for (uint32_t n = 0; n < h.layer[0].rows; n++) {
+        if (!touched[n]) continue;
+        repack_row_only(net, raw, 0, (int)n, blob);
+        add_span(h.layer[0].offset + (size_t)n * rb, rb);
+      }
+      if (h.l0_mfma_offset) {  // (once per run, not once per row as repack_row would)
+        repack_l0_tables(net, raw, blob);
+        add_span(h.l0_mfma_offset, kL0MfmaBytes);
+      }
+      raw.w[0] = r.raw.w[0];
+      raw.t[0] = r.raw.t[0];
+      std::memcpy(blob.data() + h.layer[0].offset, r.blob.data() + h.layer[0].offset, rows_bytes);
+      if (h.l0_mfma_offset) std::memcpy(blob.data() + h.l0_mfma_offset, r.blob.data() + h.l0_mfma_offset, kL0MfmaBytes);
+      if (staging.size() > 0xFFFF0000u) return fail("mem_noise: too many layer-0 patches for one call (staging above 4 GB)");
+    }
+  }
+  job.nspans = (int)spans.size();
+  job.spans_off = (staging.size() + 255) & ~(size_t)255;
+  size_t end = job.spans_off + spans.size() * sizeof(PatchSpan);
+  for (int l = 0; l < S; l++) {
+    const LayerSpec &L = net.L[l];
+    if (!rth[l] || L.thr24) continue;
+    end = (end + 255) & ~(size_t)255;
+    job.tab_off[l] = end;
+    end += (size_t)L.mh() * L.nthr * sizeof(uint16_t);
+  }
+  job.upload.assign(end, 0);
+  if (!staging.empty()) std::memcpy(job.upload.data(), staging.data(), staging.size());
+  if (!spans.empty()) std::memcpy(job.upload.data() + job.spans_off, spans.data(), spans.size() * sizeof(PatchSpan));
+  for (int l = 0; l < S; l++) {
+    const LayerSpec &L = net.L[l];
+    if (!rth[l] || L.thr24) continue;
+    uint16_t *tab = reinterpret_cast<uint16_t *>(job.upload.data() + job.tab_off[l]);
+    for (int n = 0; n < L.mh(); n++)
+      for (int i = 0; i < L.nthr; i++)
+        tab[(size_t)n * L.nthr + i] = (uint16_t)(r.raw.t[l][(size_t)(n % L.fold.pe)][(size_t)(n / L.fold.pe) * L.nthr + i] & 0xFFFF);
+  }
+  return 0;
+}
+
+// Enqueues on r.stream: one copy of the loaded blob per seed in r.d_copies (replicated by doubling), the host's layer-0
+// patches scattered over them, then the upset kernels layer by layer, weights before thresholds.  d_noise holds the seeds
+// and, at counts_off, the zeroed [run][layer][2] counters.  `seeds` and `job` must outlive the stream's work.
+static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, const MemNoiseJob &job,
+                             size_t counts_off) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  const int R = (int)seeds.size(), S = net.nlayers;
+  PackedHeader h;
+  std::memcpy(&h, r.blob.data(), sizeof(h));
+  const size_t stride = job.stride;
+  if (grow(r.d_copies, r.copies_cap, (size_t)R * stride) || grow(r.d_camp, r.camp_cap, job.upload.size() + 256) ||
+      grow(r.d_noise, r.noise_cap, counts_off + (size_t)R * S * 2 * 8))
+    return -1;
+  const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+  unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
+  HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
+  HIP_OK(hipMemsetAsync(d_counts, 0, (size_t)R * S * 2 * 8, r.stream));
+  HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, r.blob.size(), hipMemcpyDeviceToDevice, r.stream));
+  for (size_t have = 1; have < (size_t)R; have *= 2) {  // replicate by doubling
+    const size_t c = std::min(have, (size_t)R - have);
+    HIP_OK(hipMemcpyAsync(r.d_copies + have * stride, r.d_copies, c * stride, hipMemcpyDeviceToDevice, r.stream));
+  }
+  if (!job.upload.empty()) HIP_OK(hipMemcpyAsync(r.d_camp, job.upload.data(), job.upload.size(), hipMemcpyHostToDevice, r.stream));
+  hipError_t e = scatter_patches(r.d_camp, reinterpret_cast<const PatchSpan *>(r.d_camp + job.spans_off), job.nspans, r.d_copies, r.stream);
+  for (int l = 0; l < S && e == hipSuccess; l++) {
+    const LayerSpec &L = net.L[l];
+    if (L.arith == AR_INT8) continue;  // (the host's part)
+    const MemNoiseLayer ml{h.layer[l].offset, h.layer[l].row_dwords, h.layer[l].rows, h.layer[l].kw, (uint32_t)L.fold.pe, (uint32_t)L.fold.tmem, (uint32_t)l};
+    e = mem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, rw[l], d_counts, S, r.stream);
+    // the loaded parameters hold -2 rows already: a flip may have removed the last -2 of a row
+    if (e == hipSuccess && L.arith == AR_TT && rw[l] && r.two_rows > 0) e = mem_noise_flags(r.d_copies, stride, R, ml, r.stream);
+    if (e == hipSuccess && rth[l])
+      e = mem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
+                      rth[l], d_counts, S, r.stream);
+  }
+  if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// Random upsets of the parameter memories, many runs in one call.  Every run gets a copy of the loaded blob in HBM with its
+// upsets applied in place (mem_noise_enqueue); the (run, image) pairs then go in run-major order, in groups of at most one
+// activation workspace, through the multi-run stages with the copy stride: act_noise_campaigns' grouping with
+// fault_campaigns' copies.  kMaxRuns copies are what fault_campaigns holds as well, so a call's runs always fit.
+int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                    const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
+                                    float *usecPerImage) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  r.mem_noise_counts.clear();
+  r.mem_noise_seeds.clear();
+  const int S = net.nlayers;
+  if (!path) {
+    fail("mem_noise_campaigns: bad arguments (path missing)");
+    return nullptr;
+  }
+  if (num_runs < 1 || num_runs > kMaxRuns) {
+    fail("mem_noise_campaigns: num_runs must be 1 ... " + std::to_string(kMaxRuns));
+    return nullptr;
+  }
+  const int R = num_runs;
+  if (seed != 0 && 0ull - (uint64_t)seed < (uint64_t)R) {
+    fail("mem_noise_campaigns: seed + run wraps to 0 for a run (0 seeds from std::random_device)");
+    return nullptr;
+  }
+  if (mem_noise_check("mem_noise_campaigns", rate_w_q32, rate_t_q32, n_rates)) return nullptr;
+  ImageFile f;
+  if (open_image_file(path, f)) return nullptr;
+  const int n = (int)f.n;
+  const size_t total = (size_t)R * n;
+  const bool cnv = net.is_cnv;
+  std::vector<unsigned long long> seeds((size_t)R);
+  {
+    std::random_device rd;
+    for (int q = 0; q < R; q++) {
+      unsigned long long k = seed ? seed + (unsigned long long)q : 0;  // (seed 0: every run from std::random_device, never 0)
+      while (k == 0) k = ((unsigned long long)rd() << 32) | rd();
+      seeds[(size_t)q] = k;
+    }
+  }
+  bool any = false, tt = false;
+  for (int l = 0; l < S; l++) {
+    any = any || rate_w_q32[l] || rate_t_q32[l];
+    tt = tt || (rate_w_q32[l] && net.L[l].arith == AR_TT);
+  }
+  int *result = new (std::nothrow) int[total + 1];
+  if (!result) { fail("out of memory"); return nullptr; }
+  std::vector<unsigned long long> counts((size_t)R * S * 2, 0);
+  MemNoiseJob job;
+  double device_us = 0.0;
+  auto run = [&]() -> int {
+    if (n == 0) return 0;
+    if (any && mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job)) return -1;
+    size_t cap = std::min<size_t>(kMaxChunk, total);  // pairs per group: the activation workspace
+    if (const char *e = std::getenv("BNN_MI355X_NOISE_GROUP")) {  // tests: many small groups
+      const long long v = std::atoll(e);
+      if (v > 0) cap = std::min<size_t>(cap, (size_t)v);
+    }
+    // the records of every group: a run's images, cut at the group's end
+    struct Group { size_t seg0; int nsegs, max_len, total; };
+    std::vector<MultiSeg> segs;
+    std::vector<Group> groups;
+    for (size_t p0 = 0; p0 < total; p0 += cap) {
+      const size_t p1 = std::min(total, p0 + cap);
+      Group g{segs.size(), 0, 0, 0};
+      for (size_t p = p0; p < p1;) {
+        const int q = (int)(p / (size_t)n), i = (int)(p % (size_t)n), m = (int)std::min<size_t>((size_t)(n - i), p1 - p);
+        segs.push_back(MultiSeg{q, i, g.total, m});
+        g.nsegs++;
+        g.total += m;
+        g.max_len = std::max(g.max_len, m);
+        p += (size_t)m;
+      }
+      groups.push_back(g);
+    }
+    PackedHeader h;
+    std::memcpy(&h, r.blob.data(), sizeof(h));
+    const bool tab = h.l0_mfma_offset && r.l0_mfma;
+    const size_t counts_off = ((size_t)R * 8 + 255) & ~(size_t)255;
+    if (load_file_resident(f, n) || reserve((int)cap)) return -1;
+    if (grow(r.d_sw_segs, r.sw_segs_cap, segs.size() * sizeof(MultiSeg)) ||
+        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+      return -1;
+    std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
+    if (!cnv) w.resize(total);
+    DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+    if (settle_handover(r.stream)) return -1;
+    while (r.time_events.size() < 2) {
+      hipEvent_t e;
+      HIP_OK(hipEventCreateWithFlags(&e, kTimeEventFlags));
+      r.time_events.push_back(e);
+    }
+    // -- all of it on one stream, one wait at the end
+    HIP_OK(hipEventRecord(r.time_events[0], r.stream));
+    if (any && mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off)) return -1;
+    // (all rates 0: no copy is made, every run reads the loaded blob)
+    const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
+    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
+    HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
+    for (const Group &g : groups) {
+      MultiLaunch a{};
+      a.images = r.d_all;
+      a.segs = d_segs + g.seg0;
+      a.nsegs = g.nsegs; a.max_len = g.max_len; a.total = g.total; a.n = n;
+      a.buf0 = r.buf0; a.buf1 = r.buf1;
+      for (int k = 0; k < S; k++) a.rows[k] = reinterpret_cast<const uint32_t *>(base + h.layer[k].offset);
+      a.l0_mfma = tab ? base + h.l0_mfma_offset : nullptr;
+      a.stride = any ? job.stride : 0;
+      // (reading the flags back only to decide this would cost a host wait: the -2-aware instantiations are exact on rows without)
+      a.has_two = r.two_rows > 0 || tt;
+      a.classes = reinterpret_cast<int32_t *>(r.d_camp_res);
+      a.words = reinterpret_cast<uint64_t *>(r.d_camp_res);
+      a.number_class = number_class;
+      a.stream = r.stream;
+      const hipError_t e = cnv ? run_cnv_multi(net.id, a) : run_lfc_multi(net.id, a);
+      if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+    }
+    HIP_OK(hipEventRecord(r.time_events[1], r.stream));
+    if (any) HIP_OK(hipMemcpyAsync(counts.data(), r.d_noise + counts_off, counts.size() * 8, hipMemcpyDeviceToHost, r.stream));
+    if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    for (size_t i = 0; !cnv && i < total; i++) result[i] = lfc_class_batched(w[i], number_class);
+    for (size_t i = 0; i < job.host_counts.size(); i++) counts[i] += job.host_counts[i];
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, r.time_events[0], r.time_events[1]));
+    drain.ok();
+    device_us = ms * 1000.0;
+    return 0;
+  };
+  if (run() < 0) {
+    delete[] result;
+    return nullptr;
+  }
+  r.mem_noise_counts.assign(counts.begin(), counts.end());
+  r.mem_noise_seeds = std::move(seeds);
+  if (image_number) *image_number = n;
+  if (usecPerImage) *usecPerImage = total ? (float)(device_us / (double)total) : 0.f;
+  return result;
+}
+
+int bnn_mi355x_last_mem_noise_counts(long *flips, int cap) {
+  const std::vector<long> &c = rt().mem_noise_counts;
+  for (int i = 0; flips && i < cap && i < (int)c.size(); i++) flips[i] = c[(size_t)i];
+  return (int)c.size();
+}
+
+int bnn_mi355x_last_mem_noise_seeds(unsigned long long *seeds, int cap) {
+  const std::vector<unsigned long long> &k = rt().mem_noise_seeds;
+  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
+  return (int)k.size();
+}
+
+long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int target, unsigned int rate_q32, long first, int *records,
+                               int cap_records) {
+  const NetSpec &net = rt().spec;
+  if (mem_noise_sites(net, layer, target) < 0 || first < 0)
+    return fail("mem_noise_mask: bad layer (0 ... " + std::to_string(net.nlayers - 1) + "), target (0 weights, 1 thresholds) or first");
+  const long total = mem_noise_mask(net, run_seed, layer, target, rate_q32, 0, nullptr, 0);
+  if (records && cap_records > 0 && first < total) {
+    std::vector<Fault> v((size_t)std::min<long>(cap_records, total - first));
+    mem_noise_mask(net, run_seed, layer, target, rate_q32, first, v.data(), (long)v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      const Fault &f = v[i];
+      const int w[8] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
+      std::memcpy(records + i * 8, w, sizeof w);
+    }
+  }
+  return total;
+}
+
+size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                   void *dst, size_t cap) {
+  Runtime &r = rt();
+  if (mem_noise_check("mem_noise_params", rate_w_q32, rate_t_q32, n_rates)) return 0;
+  if (!dst) return r.blob.size();
+  if (cap < r.blob.size()) { fail("mem_noise_params: destination too small"); return 0; }
+  const std::vector<unsigned long long> seeds(1, run_seed);
+  MemNoiseJob job;
+  auto run = [&]() -> int {
+    if (mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job)) return -1;
+    DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+    if (settle_handover(r.stream)) return -1;
+    if (mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, 256)) return -1;
+    HIP_OK(hipMemcpyAsync(dst, r.d_copies, r.blob.size(), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    return 0;
+  };
+  return run() < 0 ? 0 : r.blob.size();
 }
 
 void free_results(int *result) { delete[] result; }

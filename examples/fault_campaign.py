@@ -2,7 +2,8 @@
 """A fault-injection campaign with the reference's `bnn.faults` drivers (the flow of the fork's fault
 notebooks) on an MI355X: 2 000 synthetic CIFAR-10-shaped images whose "labels" are the fault-free
 classes (control accuracy 100 %), three runs for each of {50, 500} upsets x {weight bit, threshold word}, then the
-datapath's accuracy-versus-upset-rate curve: every activation upset with probability 2^-14 ... 2^-6, ten runs each; and
+datapath's accuracy-versus-upset-rate curve: every activation upset with probability 2^-14 ... 2^-6, ten runs each; the
+same curve for the parameter memories (every weight / threshold bit upset with that probability, per memory kind); and
 the same two questions of the image buffer: the curve for input-bit upsets, and which bit positions of a pixel matter
 (every bit of the image flipped alone, on the first 200 images).
 
@@ -45,6 +46,15 @@ for p in rates:
     e = stats["results"]["upset rate %g" % p]
     print("upset rate %-12g (effective %.3g) accuracy min %.2f avg %.2f max %.2f stddev %.2f"
           % (p, e["effective rate"], e["min accuracy"], e["avg accuracy"], e["max accuracy"], e["stddev accuracy"]))
+
+# the parameter memories: every bit of the weight (then: threshold) memories upset with probability p, in place from image 0
+net.memory_upset_rate_curve(out, 10, rates, seed=1)
+for target in ("weights", "thresholds"):
+    stats = json.load(open(os.path.join(out, "cnvW1A1", "cifar10", "memory-upsets", "cnvW1A1_cifar10_%s_stats.json" % target)))
+    for p in rates:
+        e = stats["results"]["%s upset rate %g" % (target, p)]
+        print("%-10s upset rate %-12g (effective %.3g) accuracy min %.2f avg %.2f max %.2f stddev %.2f"
+              % (target, p, e["effective rate"], e["min accuracy"], e["avg accuracy"], e["max accuracy"], e["stddev accuracy"]))
 
 # the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
 net.input_upset_rate_curve(out, 10, rates, seed=1)

@@ -360,6 +360,52 @@ int bnn_mi355x_last_input_noise_seeds(unsigned long long *seeds, int cap);
 long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigned int rate_q32, long first, int *records,
                                  int cap_records);
 
+/* Memory upset-rate campaigns: the accuracy when EVERY bit of the weight / threshold memories is upset with probability
+ * p (cross-section x fluence), independently per bit -- the random, many-at-once form of the parameter faults of
+ * bnn_mi355x_fault_sweep.  The sites of layer L and target (0 weights, 1 thresholds) are the records
+ * bnn_mi355x_enumerate_faults(L, target, word_size 1, ...) lists; site s is a record's index in that list:
+ *     weights     s = (mem * WMEM + ind) * (SIMD * wbits) + bit
+ *     thresholds  s = ((mem * TMEM + ind) * nthr + thresh) * ebits + bit        (ebits 24 for layer 0 of the CNV nets, else 16)
+ * (pad bits of the 64-bit file words are no sites; pad columns inside a memory word's SIMD bits are).  For run seed k
+ *     u = philox4x32_10(counter {L, target, s >> 2, 1}, key {k & 0xffffffff, k >> 32})[s & 3]
+ * and the site is flipped iff u < rate (units of 2^-32: rate_w_q32[L], rate_t_q32[L], one entry per layer).  The
+ * activation and input draws have 0 in the fourth counter word: the three models never share a stream.  The parameters
+ * of a run are what bnn_mi355x_pack_params_faulty builds from the loaded parameters with every flipped site applied as a
+ * word_size-1 record, layer-major, per layer weights then thresholds, in site order; they are in place from the first
+ * image to the last (the memory state after the exposure).  Results depend on (seed, run, rates) and the loaded
+ * parameters alone, not on batch size, grouping or chunking.  The reference has no rate-based injection: parity is
+ * unpinned, the mechanism of a single flip is the pinned one.
+ * mem_noise_campaigns: num_runs (1 ... 4096) independent runs over the images of `path`, run r with seed + r (refused if
+ * that is 0 mod 2^64 for a run; seed == 0: every run's seed from std::random_device, read them back with
+ * last_mem_noise_seeds).  Returns a new int[num_runs * n] of classes, run-major (free_results).  n_rates must be the
+ * number of layers; a non-zero threshold rate for a layer without threshold memory is refused.  All rates 0: the
+ * fault-free classes once per run, no upset kernel is launched.  The loaded parameters, params_crc, last_faults,
+ * last_campaign_faults and every last_*sweep* state are unchanged.  Refused (NULL + last_error) before any device work:
+ * bad arguments, the hardened variants ("not modelled"), an imported blob (no raw memories), the BNN_MI355X_L1
+ * comparison forms.  usecPerImage: device time / (num_runs * n).  Every run has its own copy of the blob in HBM; the
+ * upsets are drawn and applied there by the GPU (layer 0 of the CNV nets by the host), and the (run, image) pairs run the
+ * integer-pipe kernels of the fault paths in groups bounded by the activation workspace (BNN_MI355X_NOISE_GROUP=<pairs>
+ * makes them smaller: tests).
+ * last_mem_noise_counts: of the last such call, the flips actually applied per [run][layer][2: weights, thresholds],
+ * counted by the code that applies them; returns runs * layers * 2 (0 before the first call).
+ * last_mem_noise_seeds: the runs' seeds of the last call; returns their number.
+ * mem_noise_mask: host only, touches no GPU.  The flipped sites of one (run seed, layer, target) at `rate_q32` as 8-int
+ * fault records (image 0, word_size 1) in site order: writes records [first, first + cap_records) and returns the total
+ * (records may be NULL); 0 for the thresholds of a layer without any; -1 + last_error for a bad layer or target or a
+ * negative first.
+ * mem_noise_params: the packed blob a run with this seed classifies with, made on the device by the kernels and patches
+ * the campaign uses (one copy) and read back: import it elsewhere, diff it.  dst NULL queries the size.  0 + last_error
+ * for what the campaign refuses, or a destination too small. */
+int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                    const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                    int *image_number, float *usecPerImage);
+int bnn_mi355x_last_mem_noise_counts(long *flips, int cap);
+int bnn_mi355x_last_mem_noise_seeds(unsigned long long *seeds, int cap);
+long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int target, unsigned int rate_q32, long first,
+                               int *records, int cap_records);
+size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                   const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap);
+
 /* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
  * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column
  * l = the output of layer l, l = 0 ... 7 (layers 1 and 3: after the max-pool); LFC column l = the output of layer l,

@@ -711,7 +711,7 @@ __global__ __launch_bounds__(256, 2) void k_l1_mfma(const uint32_t *__restrict__
 //     column ahead, behind the MFMAs of the column before, into a second register set: every wait inside a tile is a
 //     counted lgkmcnt for a read that is five MFMAs old (tests/test_conv_matrix_duty_build.py).
 //   * No pool (layer 2): lane half h stores output row 2rp + h (after the half swap both halves hold the word).
-//     Pool (layers 1, 3): vertical max = v_max_f32 of the two rows' accumulators, horizontal = AND of !fire with lane
+//     Pool (layers 1, 3): vertical max = AND of the two rows' accumulator bits (sign only), horizontal = AND of !fire with lane
 //     c ^ 1 (DPP; items per image and per row are even, so x and x ^ 1 of a row pair sit in lanes c and c ^ 1).
 // Items past the last image repeat the last valid one (their results are dropped).  Outputs are the XNOR kernels'
 // bit-packed HWC words, byte for byte.
@@ -817,9 +817,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
       const bool valid = t0 + c < nitems;
       const size_t img = (size_t)(img0 + i);
       if constexpr (POOL) {
+        // Vertical pool: only the sign of the row pair's maximum is used (sign bit = neither row fires), and the sign bit
+        // of the AND of the two bit patterns is exactly "both negative" -- one v_and_b32 where fmaxf costs three
+        // instructions (it canonicalises both operands first).  No NaN can arise (finite seeds, +-1 products, |sum| <=
+        // 1152 + 1154), and the sign bit of a zero means the same to both forms: the maximum of -0 and -0 is -0, of +0
+        // and anything negative (-0 too) +0.  (Here a zero arises only by cancellation and is +0: it fires.)
         int v[16];
 #pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = __float_as_int(fmaxf(acc[0][k], acc[1][k]));
+        for (int k = 0; k < 16; k++) v[k] = __float_as_int(acc[0][k]) & __float_as_int(acc[1][k]);
         const uint32_t nf = or_halves(sign_nibbles(v, h));
         const uint32_t pooled = nf & (uint32_t)__builtin_amdgcn_mov_dpp((int)nf, 0xB1, 0xF, 0xF, true);  // & lane c ^ 1
         if (valid && h == 0 && !(x & 1)) out[(img * (RP * RP) + rp * RP + (x >> 1)) * NT + mt] = ~pooled;

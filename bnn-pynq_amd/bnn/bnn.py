@@ -345,13 +345,16 @@ class PynqBNN:
             raise ValueError("rates: a probability in [0, 1) for each of the {} layers".format(layers))
         return np.floor(p * 4294967296.0).astype(np.uint64).astype(np.uint32)
 
-    def inference_multiple_mem_noise(self, path, num_runs, rates_w, rates_t, seed=0):
-        """num_runs independent runs over the images of `path`, every bit of layer L's weight memory flipped with
+    def inference_multiple_mem_noise(self, path, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
+        """scheme (0 none, 1 TMR, 2 interleaved, 3 resilient-interleaved) or burst > 1: the hardened form,
+        inference_multiple_hardened_mem_noise.  Else num_runs independent runs over the images of `path`, every bit of layer L's weight memory flipped with
         probability rates_w[L] and every bit of its threshold memory with rates_t[L] (mem_noise_rates), in place from the
         first image on; run r draws with seed + r (seed 0: every run's seed from std::random_device, then in
         self.mem_noise_seeds).  -> (classes int32 (num_runs, n), counts int64 (num_runs, layers, 2): the flips actually
         applied per run, layer and memory kind (0 weights, 1 thresholds)).  The loaded parameters are not changed.
         usecPerImage: device time of the call / (num_runs * n)."""
+        if scheme is not None or burst != 1:
+            return self.inference_multiple_hardened_mem_noise(path, num_runs, rates_w, rates_t, scheme or 0, burst, seed)
         lib = self.interface
         qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
         qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
@@ -370,6 +373,45 @@ class PynqBNN:
         self.mem_noise_seeds = list(seeds)
         self.usecPerImage = usec.value
         return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2)
+
+    # extension: hardened memory schemes in the memory upset campaigns (TMR, interleaved thresholds; bursts)
+    def hardening_layout(self, scheme):
+        """-> int array (layers, 3): weight modules, threshold modules, threshold interleave (0 / 2 / 3) per layer of this
+        network under `scheme`; RuntimeError with the reason for a (network, scheme) pair that is not modelled"""
+        lib = self.interface
+        out = (ctypes.c_int * 3)()
+        rows = []
+        for layer in range(len(self.mem_noise_rates(0.0))):
+            if lib.bnn_mi355x_hardening_layout(scheme, layer, out) != 0:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            rows.append(list(out))
+        return np.array(rows, np.int32)
+
+    def inference_multiple_hardened_mem_noise(self, path, num_runs, rates_w, rates_t, scheme, burst=1, seed=0):
+        """inference_multiple_mem_noise on the PHYSICAL memories of a hardened overlay: `scheme` 0 none, 1 TMR (three
+        modules of layer 0's weights and of the thresholds of layers 0-4, bitwise majority), 2 / 3 (resilient-)interleaved
+        threshold lines; an event flips `burst` (1 ... 16) adjacent physical bits of one memory word of one module, with
+        probability rates_w[L] / rates_t[L] per aligned group.  -> (classes int32 (num_runs, n), counts int64 (num_runs,
+        layers, 2: weights, thresholds, 2: physical bits flipped, logical bits that differ after voting and
+        de-interleaving)).  The seeds are left in self.mem_noise_seeds."""
+        lib = self.interface
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_hardened_mem_noise_campaigns(path.encode(), len(self.classes), scheme, burst, num_runs, seed, qw.ctypes.data_as(up),
+                                                          qt.ctypes.data_as(up), len(qw), ctypes.byref(size), ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("hardened memory noise campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_hardened_mem_noise_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_hardened_mem_noise_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_hardened_mem_noise_seeds(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2, 2)
 
     # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
     def enumerate_input_faults(self):
@@ -645,11 +687,11 @@ class CnvClassifier:
         return result
 
     # extension: memory upset-rate campaigns (PynqBNN.inference_multiple_mem_noise)
-    def classify_images_mem_noise(self, imgs, num_runs, rates_w, rates_t, seed=0):
-        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_mem_noise(p, num_runs, rates_w, rates_t, seed))
+    def classify_images_mem_noise(self, imgs, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
+        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_mem_noise(p, num_runs, rates_w, rates_t, seed, scheme, burst))
 
-    def classify_cifars_mem_noise(self, path, num_runs, rates_w, rates_t, seed=0):
-        result = self.bnn.inference_multiple_mem_noise(path, num_runs, rates_w, rates_t, seed)
+    def classify_cifars_mem_noise(self, path, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
+        result = self.bnn.inference_multiple_mem_noise(path, num_runs, rates_w, rates_t, seed, scheme, burst)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
@@ -745,8 +787,8 @@ class LfcClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
-    def classify_mnists_mem_noise(self, mnist_format_file, num_runs, rates_w, rates_t, seed=0):
-        result = self.bnn.inference_multiple_mem_noise(mnist_format_file, num_runs, rates_w, rates_t, seed)
+    def classify_mnists_mem_noise(self, mnist_format_file, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
+        result = self.bnn.inference_multiple_mem_noise(mnist_format_file, num_runs, rates_w, rates_t, seed, scheme, burst)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

@@ -26,7 +26,10 @@ every activation of the chosen layers' outputs upset with probability p, indepen
 
 ``FaultTest.run_memory_noise_test`` / ``NetworkTest.memory_upset_rate_curve`` give the same curve for the parameter
 memories: every bit of the weight / threshold memories flipped with probability p per run, in place from the first image
-on (``PynqBNN.inference_multiple_mem_noise``), per memory kind and layer set.
+on (``PynqBNN.inference_multiple_mem_noise``), per memory kind and layer set.  With ``scheme=`` / ``burst=`` the upsets
+hit the PHYSICAL memories of one of the fork's hardened overlays -- three voted modules (TMR), bit-interleaved threshold
+lines -- in bursts of adjacent bits; ``NetworkTest.hardening_curve`` compares the schemes at the same rates, the figure a
+hardening study reports.  ``hardening_of`` maps an overlay's name to (base network, scheme).
 
 ``FaultTest.input_sensitivity`` / ``NetworkTest.input_sensitivity_map`` and ``FaultTest.run_input_noise_test`` /
 ``NetworkTest.input_upset_rate_curve`` are their twins for the image buffer every classification starts from: every
@@ -57,6 +60,18 @@ def propagation_curves(alive, flipped, n_images, first=0):
     live = alive > 0
     size = np.where(live, flipped / np.maximum(alive, 1), 0.0).sum(axis=0) / np.maximum(live.sum(axis=0), 1)
     return [float(x) for x in share], [float(x) for x in size]
+
+
+# the memory organisations of the fork's hardened overlays (csrc/mem_org.h), by the scheme number the C ABI takes
+HARDENING_SCHEMES = ("none", "TMR", "interleaved", "resilient-interleaved")
+
+
+def hardening_of(overlay):
+    """an overlay's name -> (base network, scheme): "cnvW1A1-TMR" -> ("cnvW1A1", 1), "cnvW2A2" -> ("cnvW2A2", 0)"""
+    base, _, suffix = overlay.partition("-")
+    if suffix and suffix not in HARDENING_SCHEMES[1:]:
+        raise ValueError("unknown hardened overlay: " + overlay)
+    return base, HARDENING_SCHEMES.index(suffix) if suffix else 0
 
 
 class FaultTest:
@@ -218,8 +233,10 @@ class FaultTest:
         print()
         return accuracies
 
-    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0):
-        """num_runs independent runs with every bit of layer L's weight memory flipped with probability rates_w[L] and
+    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
+        """scheme (0 ... 3, HARDENING_SCHEMES) or burst > 1: the upsets hit the physical memories of that hardened
+        organisation in bursts of `burst` adjacent bits, and the counts are [run, layer, 2, 2: physical bits flipped,
+        logical bits that differ after voting and de-interleaving].  Else (today's path, unchanged) num_runs independent runs with every bit of layer L's weight memory flipped with probability rates_w[L] and
         every bit of its threshold memory with rates_t[L] (scalars: every layer; thresholds: every layer that has any), in
         place from the first image on -> (accuracy per run in percent, flips applied [run, layer, 2: weights,
         thresholds]).  Run r draws with seed + r (0: std::random_device).  Left behind: self.mem_noise_results (classes,
@@ -227,7 +244,11 @@ class FaultTest:
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, memory upset rate(s) weights {} thresholds {}".format(
             self.network, self.dataset, num_runs, rates_w, rates_t))
-        results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed)
+        if scheme is not None or burst != 1:
+            print("  memory organisation: {}, bursts of {}".format(HARDENING_SCHEMES[scheme or 0], burst))
+            results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed, scheme or 0, burst)
+        else:
+            results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed)
         self.mem_noise_results, self.mem_noise_counts, self.mem_noise_usec = results, counts, classifier.usecPerImage
         accuracies = [util.calculate_accuracy(row.tolist(), self.labels) for row in results]
         print("Accuracies:", accuracies)
@@ -494,8 +515,10 @@ class NetworkTest:
                 out += ".json" if len(which) == nl else "_layer{}.json".format(which)
                 util.write_dict_to_file(out, stats)
 
-    def memory_upset_rate_curve(self, output_folder, num_runs, rates, layers=(), targets=("weights", "thresholds"), seed=0):
-        """The accuracy-versus-upset-rate curve of the parameter memories (FaultTest.run_memory_noise_test), per memory
+    def memory_upset_rate_curve(self, output_folder, num_runs, rates, layers=(), targets=("weights", "thresholds"), seed=0, scheme=None,
+                                burst=1):
+        """scheme / burst: as run_memory_noise_test takes them (None and 1: today's path); the flips counted are then the
+        physical bits.  The accuracy-versus-upset-rate curve of the parameter memories (FaultTest.run_memory_noise_test), per memory
         kind.  `layers`: layer sets -- each a list of layers whose memories are upset, or one layer number; empty: one set,
         every layer (thresholds: every layer that has threshold memory).  Per target one file in the format of
         upset_rate_curve, output_folder/<network>/<dataset>/memory-upsets/<network>_<dataset>_<target>_stats.json, with
@@ -519,7 +542,9 @@ class NetworkTest:
                 for p in rates:
                     per_layer = [float(p) if l in which else 0.0 for l in range(nl)]
                     zeros = [0.0] * nl
-                    accuracies, counts = ft.run_memory_noise_test(num_runs, zeros if t else per_layer, per_layer if t else zeros, seed)
+                    accuracies, counts = ft.run_memory_noise_test(num_runs, zeros if t else per_layer, per_layer if t else zeros, seed, scheme, burst)
+                    if counts.ndim == 4:
+                        counts = counts[..., 0]
                     name = "{} upset rate {:g}".format(target, p) + ("" if which == have else " layer{}".format(which))
                     raw.append(self._raw(name, num_runs, 0, which, accuracies))
                     exposed = float(bits[which].sum()) * num_runs
@@ -531,6 +556,31 @@ class NetworkTest:
             for name, e in extra.items():
                 stats["results"][name].update(e)
             util.write_dict_to_file("{}/{}_{}_{}_stats.json".format(folder, ft.network, ft.dataset, target), stats)
+
+    def hardening_curve(self, output_folder, num_runs, rates, schemes, bursts=(1,), seed=0):
+        """What a hardened memory organisation buys: the accuracy at upset rate p of every weight and threshold memory, per
+        (scheme, burst, rate), the same seeds for every scheme.  One file in the format of upset_rate_curve,
+        output_folder/<network>/<dataset>/hardening/<network>_<dataset>_hardening_stats.json, with one result
+        "<scheme name> burst <b> upset rate <p>" per combination: the runs' accuracies with min / max / average, plus
+        "stddev accuracy", "scheme", "burst", "rate" and the "physical bits" flipped and "logical bits" that differ after
+        voting and de-interleaving, summed over the runs."""
+        ft = self.fault_test
+        folder = "{}/{}/{}/hardening/".format(output_folder, ft.network, ft.dataset)
+        if self.control is None:  # (rate 0: the fault-free classes)
+            self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
+        raw, extra = [], {}
+        for scheme in schemes:
+            for burst in bursts:
+                for p in rates:
+                    accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, scheme, burst)
+                    name = "{} burst {} upset rate {:g}".format(HARDENING_SCHEMES[scheme], burst, p)
+                    raw.append(self._raw(name, num_runs, 0, [], accuracies))
+                    extra[name] = {"stddev accuracy": float(np.std(accuracies)), "scheme": int(scheme), "burst": int(burst), "rate": float(p),
+                                   "physical bits": int(counts[..., 0].sum()), "logical bits": int(counts[..., 1].sum())}
+        stats = self._stats(util.dict_of_dicts_merge(*raw))
+        for name, e in extra.items():
+            stats["results"][name].update(e)
+        util.write_dict_to_file("{}/{}_{}_hardening_stats.json".format(folder, ft.network, ft.dataset), stats)
 
     def input_sensitivity_map(self, output_folder):
         """The input-bit sweep (FaultTest.input_sensitivity) over every bit of the image, next to sensitivity_map's files:

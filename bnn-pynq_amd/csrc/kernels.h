@@ -215,4 +215,15 @@ hipError_t mem_noise_flags(uint8_t *copies, size_t stride, int runs, const MemNo
 hipError_t mem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
                        bool signed_bb, const uint16_t *raw, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
 
+// The same upsets for a hardened memory organisation and bursts (bnn_mi355x_hardened_mem_noise_campaigns; the model:
+// mem_org.h), scheme 0 with burst 1 included.  counts: [run][nlayers][2: weights, thresholds][2], += the physical bits
+// flipped (before voting) and the logical bits that differ (after voting and de-interleaving).
+// weights of a layer >= 1 (one module, not interleaved): ebits = SIMD * wbits bits per memory word (a divisor of 64)
+hipError_t hmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
+                        int ebits, int burst, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
+// 16-bit thresholds: `modules` 1 or 3 (bitwise majority), `interleave` 0, 2 or 3; raw as for mem_noise_t
+hipError_t hmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
+                        bool signed_bb, const uint16_t *raw, int modules, int interleave, int burst, uint32_t rate_q32,
+                        unsigned long long *counts, int nlayers, hipStream_t s);
+
 }  // namespace bnn

@@ -46,6 +46,7 @@
 #include "input_faults.h"
 #include "kernels.h"
 #include "mem_faults.h"
+#include "mem_org.h"
 #include "packed_params.h"
 static_assert(bnn::kL0TileOffset == (int)bnn::kL0MfmaTileOffset && bnn::kL0BigBytes == (int)bnn::kL0MfmaBigBytes,
               "k_conv0_tile's operand offsets must be the ones packed_params.cpp writes the layer-0 table by");
@@ -3075,6 +3076,131 @@ __global__ __launch_bounds__(kBlock) void k_mem_noise_t(uint8_t *__restrict__ co
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + ((size_t)run * nlayers + L.layer) * 2 + 1, (unsigned long long)c);
 }
 
+// The upsets of a hardened memory organisation, with bursts (bnn_mi355x_hardened_mem_noise_campaigns; the model and the
+// draw: mem_org.h).  The copies hold the LOGICAL parameters, so these kernels flip a logical bit where the physical state
+// -- interleaved words, one copy per module -- says so after voting and de-interleaving.
+// k_hmem_noise_w: weights of a layer >= 1, which no scheme replicates or interleaves: k_mem_noise_w's lanes, sites and
+// stores; what changes is the draw.  Site s is bit s % ebits of memory word s / ebits and lies in that word's group
+// (s % ebits) / burst: event e = (s / ebits) * per + group, per = ceil(ebits / burst).  e never decreases along a
+// lane's sites, so a lane computes each Philox block once, and the bits of one group share a word of it.
+template <bool TWO_BIT>
+__global__ __launch_bounds__(kBlock) void k_hmem_noise_w(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L,
+                                                         unsigned ebits, unsigned burst, const unsigned long long *__restrict__ seeds,
+                                                         unsigned rate, unsigned long long *__restrict__ counts, unsigned nlayers) {
+  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
+  unsigned c = 0;
+  if (t < L.rows * L.kw) {
+    const unsigned n = t / L.kw, k = t - n * L.kw;
+    const unsigned long long seed = seeds[run];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), word = hardened_draw_word(0, 0, (int)burst);
+    constexpr unsigned kSites = TWO_BIT ? 128 : 64;
+    const unsigned per = (ebits + burst - 1) / burst;
+    const unsigned site0 = (((n % L.pe) * L.tmem + n / L.pe) * L.kw + k) * kSites;
+    unsigned element = site0 / ebits, bit = site0 - element * ebits, e = element * per + bit / burst, in_group = bit % burst;
+    uint32_t u[4], have = ~0u;
+    uint64_t mlo = 0, mhi = 0;  // (1-bit weights: mlo alone)
+    for (unsigned j = 0; j < kSites; j++) {
+      if ((e >> 2) != have) {
+        have = e >> 2;
+        act_noise_block(k0, k1, L.layer, word, have, u, kMemNoiseTag);
+      }
+      const uint32_t ue = (e & 2) ? ((e & 1) ? u[3] : u[2]) : ((e & 1) ? u[1] : u[0]);
+      const uint64_t hit = ue < rate ? 1ull : 0ull;
+      if (!TWO_BIT) mlo |= hit << j;
+      else if (j & 1) mhi |= hit << (j >> 1);
+      else mlo |= hit << (j >> 1);
+      if (++bit == ebits) {
+        bit = 0; in_group = 0;
+        e = ++element * per;
+      } else if (++in_group == burst) {
+        in_group = 0;
+        e++;
+      }
+    }
+    uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
+    if constexpr (!TWO_BIT) {
+      if (mlo) {
+        uint64_t *const w = reinterpret_cast<uint64_t *>(row + 2) + k;
+        *w ^= mlo;
+      }
+    } else if (mlo | mhi) {
+      uint64_t *const wq = reinterpret_cast<uint64_t *>(row + 2);
+      const uint64_t neg = wq[2 * k], nz = wq[2 * k + 1], two = wq[2 * L.kw + k];
+      const uint64_t hi = neg ^ mhi, lo = (nz & ~two) ^ mlo, two2 = hi & ~lo;
+      wq[2 * k] = hi;
+      wq[2 * k + 1] = hi | lo;
+      wq[2 * L.kw + k] = two2;
+      if (two2) atomicOr(row + 2 + 6 * L.kw, 1u);
+    }
+    c = __popcll(mlo) + __popcll(mhi);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+  if ((threadIdx.x & 63) == 0 && c) {  // one module, no permutation: the physical flips are the logical ones
+    unsigned long long *const at = counts + ((size_t)run * nlayers + L.layer) * 4;
+    atomicAdd(at, (unsigned long long)c);
+    atomicAdd(at + 1, (unsigned long long)c);
+  }
+}
+
+// k_hmem_noise_t: thresholds of the layers whose elements are 16 bits wide.  A lane per (run, neuron n, threshold i), as
+// k_mem_noise_t.  Logical bit k of the word lives at physical (line, bit) = interleave_site(...) of the neuron's PE: its
+// own line without interleave, else its own or the partner line's word.  That physical bit's event index follows from
+// its word and group, one draw per module; mask bit k = the hit, or the majority of the three modules' hits (the voter
+// is bitwise and the stored words equal before the upsets, so the majority of the words flips exactly those bits).  The
+// word is rebuilt from the pristine raw table through packed_threshold.  A lane reads raw and writes its own row dwords
+// alone; every physical bit is counted by the lane that owns its logical image.
+__global__ __launch_bounds__(kBlock) void k_hmem_noise_t(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L, unsigned nthr,
+                                                         Arith arith, bool signed_bb, const uint16_t *__restrict__ raw, unsigned modules,
+                                                         unsigned interleave, unsigned burst, const unsigned long long *__restrict__ seeds,
+                                                         unsigned rate, unsigned long long *__restrict__ counts, unsigned nlayers) {
+  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t m = 0;
+  unsigned phys = 0;
+  if (t < L.rows * nthr) {
+    const unsigned n = t / nthr, i = t - n * nthr, mem = n % L.pe, ind = n / L.pe;
+    const unsigned long long seed = seeds[run];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const unsigned per = (16 + burst - 1) / burst;
+    uint32_t hits[3] = {0, 0, 0}, u[3][4], have[3] = {~0u, ~0u, ~0u};  // (a module's last Philox block: bits of one line share it)
+    for (int k = 0; k < 16; k++) {
+      int p_ind, p_bit;
+      interleave_site((int)interleave, 16, (int)L.tmem, (int)ind, k, &p_ind, &p_bit);
+      const uint32_t e = ((mem * L.tmem + (unsigned)p_ind) * nthr + i) * per + (unsigned)p_bit / burst;
+#pragma unroll
+      for (unsigned md = 0; md < 3; md++) {
+        if (md >= modules) break;
+        if ((e >> 2) != have[md]) {
+          have[md] = e >> 2;
+          act_noise_block(k0, k1, L.layer, hardened_draw_word(1, (int)md, (int)burst), have[md], u[md], kMemNoiseTag);
+        }
+        const uint32_t ue = (e & 2) ? ((e & 1) ? u[md][3] : u[md][2]) : ((e & 1) ? u[md][1] : u[md][0]);
+        hits[md] |= (ue < rate ? 1u : 0u) << k;
+      }
+    }
+    phys = __popc(hits[0]) + __popc(hits[1]) + __popc(hits[2]);
+    m = modules == 3 ? ((hits[0] & hits[1]) | (hits[0] & hits[2]) | (hits[1] & hits[2])) : hits[0];
+    if (m) {
+      uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
+      const int32_t T = (int16_t)(uint16_t)(raw[t] ^ m);
+      const uint32_t v = (uint32_t)packed_threshold(arith, signed_bb, 64 * (int)L.kw, T);
+      row[i] = v;
+      if (nthr == 1) row[1] = v;
+    }
+  }
+  unsigned c = __popc(m);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    c += __shfl_xor(c, d, 64);
+    phys += __shfl_xor(phys, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && phys) {
+    unsigned long long *const at = counts + ((size_t)run * nlayers + L.layer) * 4 + 2;
+    atomicAdd(at, (unsigned long long)phys);
+    if (c) atomicAdd(at + 1, (unsigned long long)c);
+  }
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -3849,5 +3975,34 @@ hipError_t mem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned 
   return hipGetLastError();
 }
 
+hipError_t hmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
+                        int ebits, int burst, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s) {
+  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
+  if (runs > 65535 || L.kw == 0 || L.rows == 0 || stride % 256 || L.offset % 8 || L.row_dwords % 2 ||
+      L.row_dwords < (two_bit ? 4 + 6 * L.kw : 2 + 2 * L.kw) || ebits < 1 || ebits > 64 || 64 % ebits || burst < 1 || burst > kMaxBurst)
+    return hipErrorInvalidValue;
+  const dim3 g((L.rows * L.kw + kBlock - 1) / kBlock, (unsigned)runs);
+  if (two_bit)
+    hipLaunchKernelGGL(k_hmem_noise_w<true>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)ebits, (unsigned)burst, seeds,
+                       rate_q32, counts, (unsigned)nlayers);
+  else
+    hipLaunchKernelGGL(k_hmem_noise_w<false>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)ebits, (unsigned)burst, seeds,
+                       rate_q32, counts, (unsigned)nlayers);
+  return hipGetLastError();
+}
+
+hipError_t hmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
+                        bool signed_bb, const uint16_t *raw, int modules, int interleave, int burst, uint32_t rate_q32,
+                        unsigned long long *counts, int nlayers, hipStream_t s) {
+  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
+  if (runs > 65535 || L.rows == 0 || stride % 256 || L.offset % 4 || nthr < 1 || nthr > 2 || L.row_dwords < 2 || arith == AR_INT8 || !raw ||
+      (modules != 1 && modules != 3) || (interleave != 0 && interleave != HS_INTERLEAVED && interleave != HS_RESILIENT) || burst < 1 ||
+      burst > kMaxBurst || L.pe == 0 || L.rows != L.pe * L.tmem)
+    return hipErrorInvalidValue;
+  const dim3 g((L.rows * (unsigned)nthr + kBlock - 1) / kBlock, (unsigned)runs);
+  hipLaunchKernelGGL(k_hmem_noise_t, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)nthr, arith, signed_bb, raw,
+                     (unsigned)modules, (unsigned)interleave, (unsigned)burst, seeds, rate_q32, counts, (unsigned)nlayers);
+  return hipGetLastError();
+}
 
 }  // namespace bnn

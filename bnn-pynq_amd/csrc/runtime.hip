@@ -47,6 +47,7 @@
 #include "act_faults.h"
 #include "input_faults.h"
 #include "mem_faults.h"
+#include "mem_org.h"
 #include "kernels.h"
 #include "preprocess.h"
 #include "resample.h"
@@ -58,8 +59,9 @@
 #error "compile with -DBNN_NETWORK=NET_CNVW1A1 (or another bnn::NetId)"
 #endif
 // BNN_VARIANT: the library is built under the name of one of the fork's hardened overlays
-// (cnvW1A1-TMR, ...-interleaved, ...): same compute as BNN_NETWORK, same parameter files; their
-// fault model (replicated / bit-interleaved parameter memories) is not modelled.
+// (cnvW1A1-TMR, ...-interleaved, ...): same compute as BNN_NETWORK, same parameter files; the fault
+// entry points it shares with the base network refuse.  The hardened memory upset campaigns (mem_org.h)
+// take the scheme as an argument and carry no BNN_VARIANT guard.
 
 namespace bnn {
 namespace {
@@ -281,6 +283,9 @@ struct Runtime {
   // d_noise): the [run][layer][2] flips and the seeds of the last such call
   std::vector<long> mem_noise_counts;
   std::vector<unsigned long long> mem_noise_seeds;
+  // bnn_mi355x_hardened_mem_noise_campaigns (the same buffers): [run][layer][2][2: physical, logical] and the seeds
+  std::vector<long> hmem_noise_counts;
+  std::vector<unsigned long long> hmem_noise_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -3183,16 +3188,26 @@ long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigne
 
 // the argument checks of both entry points, then what every parameter-fault entry point refuses; nothing touches a device
 // before they have passed (ready() is the first thing that may)
-static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates) {
+// hz: the hardened entry points (mem_org.h) -- the scheme is an argument there, so they are the same in a variant's library
+struct Hardening { int scheme, burst; };
+
+static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                           const Hardening *hz = nullptr) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
+  if (hz) {
+    if (hz->burst < 1 || hz->burst > kMaxBurst) return fail(std::string(who) + ": burst must be 1 ... " + std::to_string(kMaxBurst));
+    MemOrg org;
+    const std::string e = hardening_layout(net, hz->scheme, 0, org);
+    if (!e.empty()) return fail(std::string(who) + ": " + e);
+  }
   if (!rate_w_q32 || !rate_t_q32 || n_rates != net.nlayers)
     return fail(std::string(who) + ": bad arguments (a rate array missing, or n_rates is not " + std::to_string(net.nlayers) + ": one rate per layer)");
   for (int l = 0; l < net.nlayers; l++)
     if (rate_t_q32[l] != 0 && net.L[l].nthr == 0)
       return fail(std::string(who) + ": layer " + std::to_string(l) + " has no threshold memory (its threshold rate must be 0)");
 #ifdef BNN_VARIANT
-  return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+  if (!hz) return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
 #endif
   if (!ready()) return -1;
   if (r.raw.empty()) return fail("fault injection needs the parameter files (load_parameters), not an imported blob");
@@ -3208,17 +3223,68 @@ struct MemNoiseJob {
   size_t stride = 0, spans_off = 0, tab_off[9] = {};
   int nspans = 0;
   std::vector<uint8_t> upload;                  // patch bytes | patch spans | threshold tables
-  std::vector<unsigned long long> host_counts;  // [run][layer][2]: the flips the host applied
+  std::vector<unsigned long long> host_counts;  // [run][layer][2]: the flips the host applied ([2][2] with a Hardening)
 };
 
-static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, MemNoiseJob &job) {
+// Layer 0 of one run through the physical model (mem_org.h): the events of every module applied to `phys` in order, the
+// logical memories voted and de-interleaved into raw.w[0] / raw.t[0], the rows whose words now differ from the loaded ones
+// marked.  counts: [2: weights, thresholds][2: physical bits flipped, logical bits that differ].  `phys` comes back as loaded.
+static int hardened_layer0(const Hardening &hz, unsigned long long seed, const unsigned int rate[2], const PhysParams &loaded, PhysParams &phys,
+                           RawParams &raw, std::vector<char> &touched, unsigned long long counts[4]) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  const LayerSpec &L = net.L[0];
+  MemOrg org;
+  hardening_layout(net, hz.scheme, 0, org);
+  std::vector<PhysFault> ev;
+  bool any = false;
+  for (int target = 0; target < 2; target++) {
+    const int ebits = mem_element_bits(L, target);
+    for (int m = 0; m < (target ? org.t_modules : org.w_modules); m++) {
+      const long k = hardened_mem_noise_mask(net, hz.scheme, hz.burst, seed, 0, target, m, rate[target], 0, nullptr, 0);
+      if (k < 0) return fail("internal: hardened layer-0 draw");
+      ev.resize((size_t)k);
+      hardened_mem_noise_mask(net, hz.scheme, hz.burst, seed, 0, target, m, rate[target], 0, ev.data(), k);
+      for (const PhysFault &pf : ev) {
+        if (phys_apply(net, hz.scheme, phys, pf) < 0) return fail("internal: hardened layer-0 event outside the memories");
+        counts[2 * target] += (unsigned long long)event_width(ebits, hz.burst, pf.f.bit);
+        any = true;
+      }
+    }
+  }
+  std::fill(touched.begin(), touched.end(), 0);
+  if (!any) return 0;
+  phys_logical(net, hz.scheme, phys, raw);
+  for (int target = 0; target < 2; target++) {
+    const int ebits = mem_element_bits(L, target);
+    const uint64_t emask = (1ull << ebits) - 1;
+    const auto &now = target ? raw.t[0] : raw.w[0];
+    const auto &was = target ? r.raw.t[0] : r.raw.w[0];
+    for (size_t pe = 0; pe < now.size(); pe++)
+      for (size_t i = 0; i < now[pe].size(); i++) {
+        const uint64_t d = (now[pe][i] ^ was[pe][i]) & emask;
+        if (!d) continue;
+        counts[2 * target + 1] += (unsigned long long)__builtin_popcountll(d);
+        const size_t ind = target ? i / (size_t)L.nthr : i;  // (apply_fault's row formula)
+        touched[(target ? ind : ind / (size_t)(L.fold.wmem / L.fold.tmem)) * (size_t)L.fold.pe + pe] = 1;
+      }
+  }
+  for (int m = 0; m < 3; m++) {
+    phys.mod[m].w[0] = loaded.mod[m].w[0];
+    phys.mod[m].t[0] = loaded.mod[m].t[0];
+  }
+  return 0;
+}
+
+static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, MemNoiseJob &job,
+                             const Hardening *hz = nullptr) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const int R = (int)seeds.size(), S = net.nlayers;
   PackedHeader h;
   std::memcpy(&h, r.blob.data(), sizeof(h));
   job.stride = (r.blob.size() + 255) & ~(size_t)255;
-  job.host_counts.assign((size_t)R * S * 2, 0);
+  job.host_counts.assign((size_t)R * S * (hz ? 4 : 2), 0);
   std::vector<uint8_t> staging;
   std::vector<PatchSpan> spans;
   if (net.L[0].arith == AR_INT8 && (rw[0] || rth[0])) {
@@ -3231,9 +3297,20 @@ static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const
     const size_t rb = (size_t)h.layer[0].row_dwords * 4, rows_bytes = rb * h.layer[0].rows;
     std::vector<Fault> flips;
     std::vector<char> touched(h.layer[0].rows);
+    PhysParams loaded, phys;
+    if (hz) {
+      phys_load(net, hz->scheme, r.raw, 0, 1, loaded);
+      phys = loaded;
+    }
     for (int q = 0; q < R; q++) {
       flips.clear();
-      for (int target = 0; target < 2; target++) {
+      bool changed = false;
+      if (hz) {
+        const unsigned int rate[2] = {rw[0], rth[0]};
+        if (hardened_layer0(*hz, seeds[(size_t)q], rate, loaded, phys, raw, touched, &job.host_counts[(size_t)q * S * 4])) return -1;
+        for (char c : touched) changed = changed || c;
+      }
+      for (int target = 0; target < 2 && !hz; target++) {
         const uint32_t rate = target ? rth[0] : rw[0];
         const long k = mem_noise_mask(net, seeds[(size_t)q], 0, target, rate, 0, nullptr, 0);
         const size_t at = flips.size();
@@ -3241,8 +3318,8 @@ static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const
         mem_noise_mask(net, seeds[(size_t)q], 0, target, rate, 0, flips.data() + at, k);
         job.host_counts[((size_t)q * S + 0) * 2 + target] = (unsigned long long)k;
       }
-      if (flips.empty()) continue;
-      std::fill(touched.begin(), touched.end(), 0);
+      if (hz ? !changed : flips.empty()) continue;
+      if (!hz) std::fill(touched.begin(), touched.end(), 0);
       for (const Fault &f : flips) {
         const int row = apply_fault(net, raw, f);
         if (row < 0 || row >= (int)h.layer[0].rows) return fail("internal: mem_noise flip outside layer 0");
@@ -3296,7 +3373,7 @@ static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const
 // patches scattered over them, then the upset kernels layer by layer, weights before thresholds.  d_noise holds the seeds
 // and, at counts_off, the zeroed [run][layer][2] counters.  `seeds` and `job` must outlive the stream's work.
 static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, const MemNoiseJob &job,
-                             size_t counts_off) {
+                             size_t counts_off, const Hardening *hz = nullptr) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const int R = (int)seeds.size(), S = net.nlayers;
@@ -3304,12 +3381,12 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
   std::memcpy(&h, r.blob.data(), sizeof(h));
   const size_t stride = job.stride;
   if (grow(r.d_copies, r.copies_cap, (size_t)R * stride) || grow(r.d_camp, r.camp_cap, job.upload.size() + 256) ||
-      grow(r.d_noise, r.noise_cap, counts_off + (size_t)R * S * 2 * 8))
+      grow(r.d_noise, r.noise_cap, counts_off + (size_t)R * S * (hz ? 4 : 2) * 8))
     return -1;
   const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
   unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
   HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
-  HIP_OK(hipMemsetAsync(d_counts, 0, (size_t)R * S * 2 * 8, r.stream));
+  HIP_OK(hipMemsetAsync(d_counts, 0, (size_t)R * S * (hz ? 4 : 2) * 8, r.stream));
   HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, r.blob.size(), hipMemcpyDeviceToDevice, r.stream));
   for (size_t have = 1; have < (size_t)R; have *= 2) {  // replicate by doubling
     const size_t c = std::min(have, (size_t)R - have);
@@ -3321,12 +3398,17 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
     const LayerSpec &L = net.L[l];
     if (L.arith == AR_INT8) continue;  // (the host's part)
     const MemNoiseLayer ml{h.layer[l].offset, h.layer[l].row_dwords, h.layer[l].rows, h.layer[l].kw, (uint32_t)L.fold.pe, (uint32_t)L.fold.tmem, (uint32_t)l};
-    e = mem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, rw[l], d_counts, S, r.stream);
+    MemOrg org{1, 1, 0};
+    if (hz) hardening_layout(net, hz->scheme, l, org);  // (checked by mem_noise_check; weights of a layer >= 1 have one module)
+    e = hz ? hmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz->burst, rw[l], d_counts, S, r.stream)
+           : mem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, rw[l], d_counts, S, r.stream);
     // the loaded parameters hold -2 rows already: a flip may have removed the last -2 of a row
     if (e == hipSuccess && L.arith == AR_TT && rw[l] && r.two_rows > 0) e = mem_noise_flags(r.d_copies, stride, R, ml, r.stream);
+    const uint16_t *const tab = reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]);
     if (e == hipSuccess && rth[l])
-      e = mem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
-                      rth[l], d_counts, S, r.stream);
+      e = hz ? hmem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, tab, org.t_modules, org.t_interleave, hz->burst,
+                            rth[l], d_counts, S, r.stream)
+             : mem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, tab, rth[l], d_counts, S, r.stream);
   }
   if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
   return 0;
@@ -3336,28 +3418,31 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
 // upsets applied in place (mem_noise_enqueue); the (run, image) pairs then go in run-major order, in groups of at most one
 // activation workspace, through the multi-run stages with the copy stride: act_noise_campaigns' grouping with
 // fault_campaigns' copies.  kMaxRuns copies are what fault_campaigns holds as well, so a call's runs always fit.
-int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
-                                    const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
-                                    float *usecPerImage) {
+// hz null: bnn_mi355x_mem_noise_campaigns; else the hardened form, whose counters have two entries per (layer, target).
+static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const char *path, int number_class, int num_runs, unsigned long long seed,
+                                     const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
+                                     float *usecPerImage) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  r.mem_noise_counts.clear();
-  r.mem_noise_seeds.clear();
+  std::vector<long> &last_counts = hz ? r.hmem_noise_counts : r.mem_noise_counts;
+  std::vector<unsigned long long> &last_seeds = hz ? r.hmem_noise_seeds : r.mem_noise_seeds;
+  last_counts.clear();
+  last_seeds.clear();
   const int S = net.nlayers;
   if (!path) {
-    fail("mem_noise_campaigns: bad arguments (path missing)");
+    fail(std::string(who) + ": bad arguments (path missing)");
     return nullptr;
   }
   if (num_runs < 1 || num_runs > kMaxRuns) {
-    fail("mem_noise_campaigns: num_runs must be 1 ... " + std::to_string(kMaxRuns));
+    fail(std::string(who) + ": num_runs must be 1 ... " + std::to_string(kMaxRuns));
     return nullptr;
   }
   const int R = num_runs;
   if (seed != 0 && 0ull - (uint64_t)seed < (uint64_t)R) {
-    fail("mem_noise_campaigns: seed + run wraps to 0 for a run (0 seeds from std::random_device)");
+    fail(std::string(who) + ": seed + run wraps to 0 for a run (0 seeds from std::random_device)");
     return nullptr;
   }
-  if (mem_noise_check("mem_noise_campaigns", rate_w_q32, rate_t_q32, n_rates)) return nullptr;
+  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz)) return nullptr;
   ImageFile f;
   if (open_image_file(path, f)) return nullptr;
   const int n = (int)f.n;
@@ -3379,12 +3464,12 @@ int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_
   }
   int *result = new (std::nothrow) int[total + 1];
   if (!result) { fail("out of memory"); return nullptr; }
-  std::vector<unsigned long long> counts((size_t)R * S * 2, 0);
+  std::vector<unsigned long long> counts((size_t)R * S * (hz ? 4 : 2), 0);
   MemNoiseJob job;
   double device_us = 0.0;
   auto run = [&]() -> int {
     if (n == 0) return 0;
-    if (any && mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job)) return -1;
+    if (any && mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job, hz)) return -1;
     size_t cap = std::min<size_t>(kMaxChunk, total);  // pairs per group: the activation workspace
     if (const char *e = std::getenv("BNN_MI355X_NOISE_GROUP")) {  // tests: many small groups
       const long long v = std::atoll(e);
@@ -3426,7 +3511,7 @@ int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_
     }
     // -- all of it on one stream, one wait at the end
     HIP_OK(hipEventRecord(r.time_events[0], r.stream));
-    if (any && mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off)) return -1;
+    if (any && mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off, hz)) return -1;
     // (all rates 0: no copy is made, every run reads the loaded blob)
     const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
     const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
@@ -3466,11 +3551,18 @@ int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_
     delete[] result;
     return nullptr;
   }
-  r.mem_noise_counts.assign(counts.begin(), counts.end());
-  r.mem_noise_seeds = std::move(seeds);
+  last_counts.assign(counts.begin(), counts.end());
+  last_seeds = std::move(seeds);
   if (image_number) *image_number = n;
   if (usecPerImage) *usecPerImage = total ? (float)(device_us / (double)total) : 0.f;
   return result;
+}
+
+int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
+                                    const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
+                                    float *usecPerImage) {
+  return mem_noise_campaigns_impl("mem_noise_campaigns", nullptr, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number,
+                                  usecPerImage);
 }
 
 int bnn_mi355x_last_mem_noise_counts(long *flips, int cap) {
@@ -3503,25 +3595,131 @@ long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int targe
   return total;
 }
 
-size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
-                                   void *dst, size_t cap) {
+static size_t mem_noise_params_impl(const char *who, const Hardening *hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                    const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap) {
   Runtime &r = rt();
-  if (mem_noise_check("mem_noise_params", rate_w_q32, rate_t_q32, n_rates)) return 0;
+  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz)) return 0;
   if (!dst) return r.blob.size();
-  if (cap < r.blob.size()) { fail("mem_noise_params: destination too small"); return 0; }
+  if (cap < r.blob.size()) { fail(std::string(who) + ": destination too small"); return 0; }
   const std::vector<unsigned long long> seeds(1, run_seed);
   MemNoiseJob job;
   auto run = [&]() -> int {
-    if (mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job)) return -1;
+    if (mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job, hz)) return -1;
     DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
     if (settle_handover(r.stream)) return -1;
-    if (mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, 256)) return -1;
+    if (mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, 256, hz)) return -1;
     HIP_OK(hipMemcpyAsync(dst, r.d_copies, r.blob.size(), hipMemcpyDeviceToHost, r.stream));
     HIP_OK(hipStreamSynchronize(r.stream));
     drain.ok();
     return 0;
   };
   return run() < 0 ? 0 : r.blob.size();
+}
+
+size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                   void *dst, size_t cap) {
+  return mem_noise_params_impl("mem_noise_params", nullptr, run_seed, rate_w_q32, rate_t_q32, n_rates, dst, cap);
+}
+
+// ---- hardened memory schemes in the memory upset campaigns (the model: mem_org.h) ------------------------------------------
+
+int bnn_mi355x_hardening_scheme(void) { return hardening_scheme_of(bnn_mi355x_network()); }
+
+int bnn_mi355x_hardening_layout(int scheme, int layer, int out[3]) {
+  MemOrg org;
+  const std::string e = hardening_layout(rt().spec, scheme, layer, org);
+  if (!e.empty()) return fail("hardening_layout: " + e);
+  if (out) { out[0] = org.w_modules; out[1] = org.t_modules; out[2] = org.t_interleave; }
+  return 0;
+}
+
+int bnn_mi355x_hardened_site(int scheme, int layer, int target, int ind, int bit, int *p_ind, int *p_bit) {
+  const NetSpec &net = rt().spec;
+  MemOrg org;
+  const std::string e = hardening_layout(net, scheme, layer, org);
+  if (!e.empty()) return fail("hardened_site: " + e);
+  const LayerSpec &L = net.L[layer];
+  const int ebits = (target == 0 || target == 1) ? mem_element_bits(L, target) : 0;
+  if (ebits == 0 || ind < 0 || ind >= (target ? L.fold.tmem : L.fold.wmem) || bit < 0 || bit >= ebits)
+    return fail("hardened_site: target (0 weights, 1 thresholds of a layer that has some), ind or bit outside the memory");
+  int pi = ind, pb = bit;
+  if (target == 1) interleave_site(org.t_interleave, ebits, L.fold.tmem, ind, bit, &pi, &pb);
+  if (p_ind) *p_ind = pi;
+  if (p_bit) *p_bit = pb;
+  return 0;
+}
+
+long bnn_mi355x_hardened_mem_noise_mask(int scheme, int burst, unsigned long long run_seed, int layer, int target, int module,
+                                        unsigned int rate_q32, long first, int *records, int cap_records) {
+  const NetSpec &net = rt().spec;
+  MemOrg org;
+  const std::string e = hardening_layout(net, scheme, layer, org);
+  if (!e.empty()) return fail("hardened_mem_noise_mask: " + e);
+  const long total = first < 0 ? -1 : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0);
+  if (total < 0)
+    return fail("hardened_mem_noise_mask: bad burst (1 ... " + std::to_string(kMaxBurst) + "), target (0 weights, 1 thresholds), module (of those "
+                "the memory has) or first");
+  if (records && cap_records > 0 && first < total) {
+    std::vector<PhysFault> v((size_t)std::min<long>(cap_records, total - first));
+    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size());
+    for (size_t i = 0; i < v.size(); i++) {
+      const Fault &f = v[i].f;
+      const int w[9] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size, v[i].module};
+      std::memcpy(records + i * 9, w, sizeof w);
+    }
+  }
+  return total;
+}
+
+size_t bnn_mi355x_pack_params_hardened(const char *path, int scheme, const int *records, int n_faults, void *dst, size_t cap) {
+  const NetSpec &net = rt().spec;
+  MemOrg org;
+  const std::string le = hardening_layout(net, scheme, 0, org);
+  if (!le.empty()) { fail("pack_params_hardened: " + le); return 0; }
+  RawParams raw;
+  const std::string e = read_raw_params(net, path ? path : "", raw);
+  if (!e.empty()) { fail(e); return 0; }
+  PhysParams phys;
+  phys_load(net, scheme, raw, 0, net.nlayers, phys);
+  for (int i = 0; i < n_faults; i++) {
+    const int *v = records + i * 9;
+    const PhysFault pf{Fault{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}, v[8]};
+    if (phys_apply(net, scheme, phys, pf) < 0) { fail("pack_params_hardened: fault record out of range (or a module the memory does not have)"); return 0; }
+  }
+  phys_logical(net, scheme, phys, raw);
+  std::vector<uint8_t> blob;
+  pack_blob(net, raw, blob);
+  if (dst) {
+    if (cap < blob.size()) { fail("pack_params_hardened: destination too small"); return 0; }
+    std::memcpy(dst, blob.data(), blob.size());
+  }
+  return blob.size();
+}
+
+int *bnn_mi355x_hardened_mem_noise_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs, unsigned long long seed,
+                                             const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
+                                             float *usecPerImage) {
+  const Hardening hz{scheme, burst};
+  return mem_noise_campaigns_impl("hardened_mem_noise_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates,
+                                  image_number, usecPerImage);
+}
+
+size_t bnn_mi355x_hardened_mem_noise_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                            const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap) {
+  const Hardening hz{scheme, burst};
+  return mem_noise_params_impl("hardened_mem_noise_params", &hz, run_seed, rate_w_q32, rate_t_q32, n_rates, dst, cap);
+}
+
+int bnn_mi355x_last_hardened_mem_noise_counts(long *counts, int cap) {
+  const std::vector<long> &c = rt().hmem_noise_counts;
+  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
+  return (int)c.size();
+}
+
+int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap) {
+  const std::vector<unsigned long long> &k = rt().hmem_noise_seeds;
+  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
+  return (int)k.size();
 }
 
 void free_results(int *result) { delete[] result; }

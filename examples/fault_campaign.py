@@ -3,7 +3,8 @@
 notebooks) on an MI355X: 2 000 synthetic CIFAR-10-shaped images whose "labels" are the fault-free
 classes (control accuracy 100 %), three runs for each of {50, 500} upsets x {weight bit, threshold word}, then the
 datapath's accuracy-versus-upset-rate curve: every activation upset with probability 2^-14 ... 2^-6, ten runs each; the
-same curve for the parameter memories (every weight / threshold bit upset with that probability, per memory kind); and
+same curve for the parameter memories (every weight / threshold bit upset with that probability, per memory kind);
+what TMR and threshold interleaving buy at the three highest rates, for single bits and bursts of four; and
 the same two questions of the image buffer: the curve for input-bit upsets, and which bit positions of a pixel matter
 (every bit of the image flipped alone, on the first 200 images).
 
@@ -55,6 +56,19 @@ for target in ("weights", "thresholds"):
         e = stats["results"]["%s upset rate %g" % (target, p)]
         print("%-10s upset rate %-12g (effective %.3g) accuracy min %.2f avg %.2f max %.2f stddev %.2f"
               % (target, p, e["effective rate"], e["min accuracy"], e["avg accuracy"], e["max accuracy"], e["stddev accuracy"]))
+
+# what hardening buys: the same upsets on the PHYSICAL memories of the fork's hardened overlays (three voted modules under
+# TMR, bit-interleaved threshold lines), single bits and bursts of four, the same seeds for every scheme
+schemes = [0, 1, 2, 3]
+net.hardening_curve(out, 10, rates[-3:], schemes, bursts=(1, 4), seed=1)
+stats = json.load(open(os.path.join(out, "cnvW1A1", "cifar10", "hardening", "cnvW1A1_cifar10_hardening_stats.json")))
+for scheme in schemes:
+    for burst in (1, 4):
+        for p in rates[-3:]:
+            e = stats["results"]["%s burst %d upset rate %g" % (bnn.faults.HARDENING_SCHEMES[scheme], burst, p)]
+            print("%-22s burst %d upset rate %-10g accuracy min %.2f avg %.2f max %.2f  (%d physical bits, %d logical)"
+                  % (bnn.faults.HARDENING_SCHEMES[scheme], burst, p, e["min accuracy"], e["avg accuracy"], e["max accuracy"],
+                     e["physical bits"], e["logical bits"]))
 
 # the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
 net.input_upset_rate_curve(out, 10, rates, seed=1)

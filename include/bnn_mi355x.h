@@ -406,6 +406,63 @@ long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int targe
 size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32,
                                    const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap);
 
+/* Hardened memory schemes in the memory upset campaigns: what TMR or threshold interleaving buys at an upset rate.  The
+ * entry points above keep their meaning (and the variant libraries their refusals); these take the scheme as an argument
+ * and are the same code in every library: 0 none, 1 TMR, 2 interleaved, 3 resilient-interleaved.
+ * The storage side is the reference's, restated from its host code (csrc/mem_org.h has the tables and the formula):
+ *   TMR          three modules for the weight memory of layer 0 and the threshold memories of layers 0-4, else one;
+ *   interleaved  (2, 3) the threshold memory of every layer that has one: lines ind (even) and ind + 1 of a PE are stored
+ *                as one bit-interleaved pair, by the default pattern (2) or the resilient variants' pattern with the
+ *                second element reversed (3); weights are not interleaved; an odd last line is stored as is.
+ * Supported: cnvW1A1 and cnvW1A2 with 1, 2, 3; cnvW2A2 with 1 and 3; scheme 0 everywhere.  Refused with the reason in
+ * last_error: cnvW2A2 with scheme 2 (the reference interleaves its 64-bit weight elements with a 64-bit pattern for 128
+ * positions and reads past the second element: no defined layout) and every LFC library with a scheme other than 0 (the
+ * one LFC overlay interleaves 24-bit elements into 16-bit words; its hardware is not in the reference).
+ * The PHYSICAL state is what the loader hands the memories: interleaved words, one copy per module.  A physical fault
+ * record is 9 ints {image, target, layer, mem, ind, thresh, bit, word_size, module}: inject_fault's read-modify-write on
+ * that module's physical word (the layer-0 integer-part quirk included, as is).  The parameters the network computes with
+ * are de-interleave(vote(modules)).  The de-interleaver is the inverse permutation (forced: a fault-free hardened overlay
+ * computes the base network).  The voter is THE PROJECT'S OWN choice, the reference's being in a fork that is not in its
+ * tree: the bitwise majority of the low `ebits` of the three stored words.  Any voter agrees with it while at most one
+ * module of a word is hit; where two are hit voters could differ, and such results are this model's alone.
+ * The upset model: per-layer rates as above plus a burst width b (1 ... 16).  An event flips b adjacent physical bits of
+ * one element of one module: the aligned group g of enumerate_faults(L, target, word_size b), per = ceil(ebits / b)
+ * groups per element, the last one clipped to the element.  With e = element * per + g (element as above) and module m
+ *     u = philox4x32_10(counter {L, target | m << 1 | (b - 1) << 8, e >> 2, 1}, key {k & 0xffffffff, k >> 32})[e & 3]
+ * and the event happens iff u < rate.  m = 0, b = 1 is mem_noise_mask's draw: scheme 0 with burst 1 reproduces
+ * mem_noise_campaigns bit for bit.  Events apply layer-major, weights then thresholds, module-major, in event order.
+ * hardening_scheme: the scheme this library's name implies (0 for a base network).  Host only.
+ * hardening_layout: out = {weight modules, threshold modules, threshold interleave 0 / 2 / 3} of a layer; -1 + last_error
+ * for a refused (network, scheme) pair or a bad layer.  Host only.
+ * hardened_site: logical -> physical: bit `bit` of line `ind` (of one PE) of the layer's weight (0) or threshold (1)
+ * memory is stored in line *p_ind at bit *p_bit.  -1 + last_error for a refused pair or a position outside.  Host only.
+ * hardened_mem_noise_mask: the events of one (run seed, layer, target, module) as 9-int physical records (image 0,
+ * word_size b, bit = g * b), paged like mem_noise_mask; -1 + last_error for a bad argument.  Host only.
+ * pack_params_hardened: the blob after n physical faults applied in the order given (dst NULL queries the size); scheme 0
+ * with module 0 is pack_params_faulty.  Host only.
+ * hardened_mem_noise_campaigns: mem_noise_campaigns with (scheme, burst): its conventions, refusals (but the variants':
+ * the scheme is the argument), grouping and BNN_MI355X_NOISE_GROUP; also refused: burst outside 1 ... 16, a bad scheme or
+ * refused pair.  Always runs its own kernels (k_hmem_noise_w / k_hmem_noise_t; layer 0 of the CNV nets on the host through
+ * the physical model), scheme 0 included.  All rates 0: the fault-free classes, no upset kernel is launched.
+ * hardened_mem_noise_params: the blob one run classifies with, made by those kernels and read back.
+ * last_hardened_mem_noise_counts: per [run][layer][2: weights, thresholds] two longs: the physical bits flipped (before
+ * voting) and the logical bits that differ (after voting and de-interleaving); returns runs * layers * 4.
+ * last_hardened_mem_noise_seeds: the runs' seeds of the last such call. */
+int bnn_mi355x_hardening_scheme(void);
+int bnn_mi355x_hardening_layout(int scheme, int layer, int out[3]);
+int bnn_mi355x_hardened_site(int scheme, int layer, int target, int ind, int bit, int *p_ind, int *p_bit);
+long bnn_mi355x_hardened_mem_noise_mask(int scheme, int burst, unsigned long long run_seed, int layer, int target, int module,
+                                        unsigned int rate_q32, long first, int *records, int cap_records);
+size_t bnn_mi355x_pack_params_hardened(const char *path, int scheme, const int *records, int n_faults, void *dst, size_t cap);
+int *bnn_mi355x_hardened_mem_noise_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs,
+                                             unsigned long long seed, const unsigned int *rate_w_q32,
+                                             const unsigned int *rate_t_q32, int n_rates, int *image_number,
+                                             float *usecPerImage);
+size_t bnn_mi355x_hardened_mem_noise_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                            const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap);
+int bnn_mi355x_last_hardened_mem_noise_counts(long *counts, int cap);
+int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap);
+
 /* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
  * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column
  * l = the output of layer l, l = 0 ... 7 (layers 1 and 3: after the max-pool); LFC column l = the output of layer l,

@@ -1,0 +1,24 @@
+"""CPU: the memory-organisation model (csrc/mem_org.cpp: the hardened overlays' physical parameter memories, the voter, the
+de-interleaver, the burst draw) under AddressSanitizer + UBSan, from a stand-alone program of its own."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import gpu_lib as gl
+
+CSRC = os.path.join(gl.ROOT, "bnn-pynq_amd", "csrc")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_mem_org_under_asan_ubsan(tmp_path):
+    exe = str(tmp_path / "mem_org_sanitize")
+    srcs = [os.path.join(gl.ROOT, "tests", "host_sanitize_mem_org", "main.cpp")] + \
+           [os.path.join(CSRC, f) for f in ("topology.cpp", "packed_params.cpp", "faults.cpp", "mem_org.cpp")]
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, "-o", exe] + srcs,
+                   check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    out = subprocess.run([exe, os.path.join(gl.ROOT, "bnn-pynq_amd", "bnn", "params")], capture_output=True, text=True, env=env)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "mem_org sanitize run ok" in out.stdout

@@ -714,8 +714,9 @@ __global__ __launch_bounds__(256, 2) void k_l1_mfma(const uint32_t *__restrict__
 //   * No pool (layer 2): lane half h stores output row 2rp + h (after the half swap both halves hold the word).
 //     Pool (layers 1, 3): vertical max = AND of the two rows' accumulator bits (sign only), horizontal = AND of !fire with lane
 //     c ^ 1 (DPP; items per image and per row are even, so x and x ^ 1 of a row pair sit in lanes c and c ^ 1).
-// Items past the last image repeat the last valid one (their results are dropped).  Outputs are the XNOR kernels'
-// bit-packed HWC words, byte for byte.
+//   * Item arithmetic: carried from tile to tile, no division in the tile loop (below).
+// Lanes past the group's last item read some item of the block's planes (their results are dropped).  Outputs are the
+// XNOR kernels' bit-packed HWC words, byte for byte.
 // ---------------------------------------------------------------------------
 // Row stride of an LDS plane, in pixels: the smallest one >= win for which the step from the last column of a row pair
 // to the first column of the next keeps the 16-byte slots of a tile's consecutive items consecutive modulo 16 (the 16
@@ -745,7 +746,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
   static_assert(WOUT % 2 == 0 && IPI % 2 == 0 && (NT == 2 || NT == 4), "tile geometry");
   __shared__ uint4 plane[G * IMGS];  // [image][32-channel block q][row][column], strides IMGS, PIXS, WS, 1
   __shared__ uint32_t lut[256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mt = wave % NT, c = lane & 31, h = lane >> 5;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), mt = wave % NT, c = lane & 31, h = lane >> 5;
   lut[tid] = fp4_pm1((uint32_t)tid);
   // weights [k step = tap * KH + kh][neuron tile][lane] x 16 bytes, then the seeds [tile][h][16] floats
   const uint4 *__restrict__ wt = reinterpret_cast<const uint4 *>(tab);
@@ -771,9 +772,21 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
     const int i = d / DWI, e = d - i * DWI, pix = e / CD, q = e % CD;
     return i * IMGS + q * PIXS + (WS == WIN ? pix : pix / WIN * WS + pix % WIN);
   };
+  // A wave's tiles are STEP items apart, and its first tile of a group starts at the same item in every group: the
+  // item's column, row pair, plane slot (without the half's PIXS) and, where there is no pool, output byte offset in
+  // the group are carried per lane and advanced behind each tile -- no division in the tile loop.  Lanes past the
+  // group's last item go on advancing (they store nothing); where G images do not fill whole tiles (layers 1 and 3)
+  // PS_LAST, the slot of the planes' last item, keeps their reads inside the block's planes.
+  constexpr int STEP = 32 * STREAMS, DR = STEP / WOUT, DX = STEP % WOUT, PS_LAST = (G - 1) * IMGS + 2 * (RP - 1) * WS + WOUT - 1;
+  constexpr bool RAGGED = (G * IPI) % 32 != 0;
+  static_assert(DX % 2 == 0 && DR + 1 <= RP, "a lane's column keeps its parity; one row-pair wrap and one image wrap per step");
+  const int item0 = (wave / NT) * 32 + c, i0 = item0 / IPI, rem0 = item0 - i0 * IPI, rp0 = rem0 / WOUT, x0 = rem0 - rp0 * WOUT;
+  const int ps0 = i0 * IMGS + 2 * rp0 * WS + x0;
+  const uint32_t ob0 = (uint32_t)((i0 * (WOUT * WOUT) + (2 * rp0 + h) * WOUT + x0) * NT + mt) * 4;
   if (blockIdx.x < ngroups) fetch(blockIdx.x);
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int img0 = grp * G, nimg = min(G, n_images - img0), nitems = nimg * IPI;
+    uint32_t *__restrict__ gout = out + (size_t)img0 * (POOL ? RP * RP : WOUT * WOUT) * NT;  // the group's outputs: wave-uniform
     __syncthreads();  // the previous group's planes are no longer read
 #pragma unroll
     for (int j = 0; j < NPF; j++) {  // one source dword (32 channels of a pixel) per iteration
@@ -785,11 +798,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
     }
     if (grp + (int)gridDim.x < ngroups) fetch(grp + gridDim.x);
     __syncthreads();
-    for (int t0 = (wave / NT) * 32; t0 < nitems; t0 += 32 * STREAMS) {
-      const int item = min(t0 + c, nitems - 1);
-      const int i = item / IPI, rem = item - i * IPI, rp = rem / WOUT, x = rem - rp * WOUT;
+    int x = x0, rp = rp0, ps = ps0;
+    [[maybe_unused]] uint32_t ob = ob0;
+    for (int t0 = (wave / NT) * 32; t0 < nitems; t0 += STEP) {
       v16f acc[2] = {seed, seed};  // output rows 2rp, 2rp + 1
-      const uint4 *__restrict__ P = &plane[i * IMGS + h * PIXS + 2 * rp * WS + x];
+      const uint4 *__restrict__ P = &plane[(RAGGED ? min(ps, PS_LAST) : ps) + h * PIXS];
       // step s = 3 kh + kx: input rows 2rp .. 2rp + 3 at column x + kx of channel block 2 kh + h (4 ds_read_b128), then the
       // 6 MFMAs of output rows 2rp, 2rp + 1 x ky
       auto read = [&](v8i &b, int s, int y) {  // input row 2rp + y
@@ -816,7 +829,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
         }
       __builtin_amdgcn_sched_barrier(0);
       const bool valid = t0 + c < nitems;
-      const size_t img = (size_t)(img0 + i);
       if constexpr (POOL) {
         // Vertical pool: only the sign of the row pair's maximum is used (sign bit = neither row fires), and the sign bit
         // of the AND of the two bit patterns is exactly "both negative" -- one v_and_b32 where fmaxf costs three
@@ -828,7 +840,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
         for (int k = 0; k < 16; k++) v[k] = __float_as_int(acc[0][k]) & __float_as_int(acc[1][k]);
         const uint32_t nf = or_halves(sign_nibbles(v, h));
         const uint32_t pooled = nf & (uint32_t)__builtin_amdgcn_mov_dpp((int)nf, 0xB1, 0xF, 0xF, true);  // & lane c ^ 1
-        if (valid && h == 0 && !(x & 1)) out[(img * (RP * RP) + rp * RP + (x >> 1)) * NT + mt] = ~pooled;
+        // the pooled pixel of an even item is item / 2 of the group (RP * RP = IPI / 2 per image, WOUT / 2 = RP per row pair)
+        if (valid && h == 0 && !(c & 1)) gout[(size_t)(t0 >> 1) * NT + (c >> 1) * NT + mt] = ~pooled;
       } else {
         uint32_t nf[2];
 #pragma unroll
@@ -836,10 +849,23 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
           int v[16];
 #pragma unroll
           for (int k = 0; k < 16; k++) v[k] = __float_as_int(acc[dy][k]);
-          nf[dy] = or_halves(sign_nibbles(v, h));
+          nf[dy] = sign_nibbles(v, h);  // this half's 16 neurons of output row 2rp + dy
         }
-        if (valid) out[(img * (WOUT * WOUT) + (2 * rp + h) * WOUT + x) * NT + mt] = ~(h ? nf[1] : nf[0]);
+        // half h stores row 2rp + h: one swap hands half 0's row-1 bits to half 1 and half 1's row-0 bits to half 0, so the
+        // OR of the pair is row h's whole word in half h (or_halves per row would be two swaps and a select)
+        const auto sw = __builtin_amdgcn_permlane32_swap(nf[0], nf[1], false, false);
+        if (valid) *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(gout) + ob) = ~(sw[0] | sw[1]);
       }
+      // the next tile of this wave: STEP items on = DR row pairs and DX columns, then at most one row-pair wrap and one
+      // image wrap (DR + 1 <= RP).  A row-pair wrap moves the unpooled output by one more row (2 WOUT - WOUT), an image
+      // wrap by nothing (2 RP rows are an image's WOUT).
+      x += DX, rp += DR, ps += 2 * DR * WS + DX;
+      if constexpr (!POOL) ob += (2 * DR * WOUT + DX) * NT * 4;
+      if (x >= WOUT) {
+        x -= WOUT, rp += 1, ps += 2 * WS - WOUT;
+        if constexpr (!POOL) ob += WOUT * NT * 4;
+      }
+      if (rp >= RP) rp -= RP, ps += IMGS - 2 * RP * WS;
     }
   }
 }

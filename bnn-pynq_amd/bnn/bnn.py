@@ -413,6 +413,35 @@ class PynqBNN:
         self.usecPerImage = usec.value
         return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2, 2)
 
+    # extension: exposure campaigns (upsets that accumulate over epochs of images, with scrubbing)
+    def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0):
+        """inference_multiple_hardened_mem_noise spread over time: the run is cut into epochs of `epoch_images` images, the
+        rates are per epoch, an epoch's upsets XOR onto the physical state the earlier ones left, and before every epoch
+        t > 0 with t % scrub_every == 0 (0: never) all memories are rewritten from the loaded parameters.  -> (classes
+        int32 (num_runs, n), counts int64 (num_runs, epochs, layers, 2: weights, thresholds, 2: physical bits flipped in
+        the epoch, logical bits that differ from the loaded parameters after it)).  The seeds are left in
+        self.mem_noise_seeds."""
+        lib = self.interface
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_exposure_campaigns(path.encode(), len(self.classes), scheme, burst, num_runs, seed, qw.ctypes.data_as(up),
+                                                qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every, ctypes.byref(size),
+                                                ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_exposure_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_exposure_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_exposure_seeds(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        epochs = -(-size.value // epoch_images)
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 2, 2)
+
     # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
     def enumerate_input_faults(self):
         """-> int32 array (image_bytes * 8, 2): every bit of the input image as records {byte, bit} in site order (byte in
@@ -695,6 +724,15 @@ class CnvClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
+    # extension: exposure campaigns (PynqBNN.inference_multiple_exposure)
+    def classify_images_exposure(self, imgs, *args):
+        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_exposure(p, *args))
+
+    def classify_cifars_exposure(self, path, *args):
+        result = self.bnn.inference_multiple_exposure(path, *args)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
     # extension: input-buffer faults (PynqBNN.input_fault_sweep, PynqBNN.inference_multiple_input_noise)
     def classify_images_input_fault_sweep(self, imgs, records, max_diffs=None):
         return self._with_tmp(imgs, lambda p: self.bnn.input_fault_sweep(p, records, max_diffs))
@@ -789,6 +827,11 @@ class LfcClassifier:
 
     def classify_mnists_mem_noise(self, mnist_format_file, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
         result = self.bnn.inference_multiple_mem_noise(mnist_format_file, num_runs, rates_w, rates_t, seed, scheme, burst)
+        self.usecPerImage = self.bnn.usecPerImage
+        return result
+
+    def classify_mnists_exposure(self, mnist_format_file, *args):
+        result = self.bnn.inference_multiple_exposure(mnist_format_file, *args)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

@@ -31,6 +31,10 @@ hit the PHYSICAL memories of one of the fork's hardened overlays -- three voted 
 lines -- in bursts of adjacent bits; ``NetworkTest.hardening_curve`` compares the schemes at the same rates, the figure a
 hardening study reports.  ``hardening_of`` maps an overlay's name to (base network, scheme).
 
+``FaultTest.run_exposure_test`` / ``NetworkTest.scrubbing_curve`` let those upsets ACCUMULATE while the run goes on: the
+images are cut into epochs, the rates are per epoch, and the memories are rewritten every ``scrub_every`` epochs
+(``PynqBNN.inference_multiple_exposure``) -- the accuracy per epoch tells how often a hardened memory must be scrubbed.
+
 ``FaultTest.input_sensitivity`` / ``NetworkTest.input_sensitivity_map`` and ``FaultTest.run_input_noise_test`` /
 ``NetworkTest.input_upset_rate_curve`` are their twins for the image buffer every classification starts from: every
 single bit of the input image flipped alone (``PynqBNN.input_fault_sweep``), and every bit flipped with probability p
@@ -252,6 +256,26 @@ class FaultTest:
         self.mem_noise_results, self.mem_noise_counts, self.mem_noise_usec = results, counts, classifier.usecPerImage
         accuracies = [util.calculate_accuracy(row.tolist(), self.labels) for row in results]
         print("Accuracies:", accuracies)
+        print()
+        return accuracies, counts
+
+    def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0):
+        """Upsets that accumulate while the run goes on: the images are cut into epochs of `epoch_images`, rates_w[L] /
+        rates_t[L] are the probability of an event PER EPOCH (scalars: every layer), an epoch's upsets XOR onto the physical
+        state of the hardened organisation `scheme` (None: 0) the earlier epochs left, and every `scrub_every` epochs (0:
+        never) the memories are rewritten.  -> (accuracy in percent [run][epoch], over the epoch's images; counts [run,
+        epoch, layer, 2: weights, thresholds, 2: physical bits flipped in the epoch, logical bits that differ after it]).
+        Left behind: self.exposure_results (classes, [run, image]), self.exposure_counts, self.exposure_usec."""
+        classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
+        print("{}-{}: {} run(s) in one call, epochs of {} images, upset rate(s) per epoch weights {} thresholds {}, {}, bursts of {}, "
+              "scrub every {}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t, HARDENING_SCHEMES[scheme or 0],
+                                      burst, scrub_every or "never"))
+        results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst,
+                                         seed)
+        self.exposure_results, self.exposure_counts, self.exposure_usec = results, counts, classifier.usecPerImage
+        accuracies = [[util.calculate_accuracy(row[i: i + epoch_images].tolist(), self.labels[i: i + epoch_images])
+                       for i in range(0, results.shape[1], epoch_images)] for row in results]
+        print("Accuracies per epoch:", accuracies)
         print()
         return accuracies, counts
 
@@ -581,6 +605,36 @@ class NetworkTest:
         for name, e in extra.items():
             stats["results"][name].update(e)
         util.write_dict_to_file("{}/{}_{}_hardening_stats.json".format(folder, ft.network, ft.dataset), stats)
+
+    def scrubbing_curve(self, output_folder, num_runs, rates, scrub_intervals, schemes, epoch_images, bursts=(1,), seed=0):
+        """How often must the memories be rewritten: the accuracy per epoch while upsets accumulate at rate p per epoch in
+        every weight and threshold memory, per (scheme, burst, rate, scrub interval), the same seeds everywhere.  One file
+        in the style of hardening_curve, output_folder/<network>/<dataset>/scrubbing/<network>_<dataset>_scrubbing_stats.json,
+        with one result "<scheme name> burst <b> upset rate <p> scrub every <S>" per combination: the runs' accuracies over
+        ALL images with min / max / average, plus "mean accuracy per epoch" (over the runs), "scheme", "burst", "rate",
+        "scrub every", "epoch images" and the "physical bits" flipped (summed over runs and epochs) and "logical bits per
+        epoch" that differ after each epoch (summed over the runs)."""
+        ft = self.fault_test
+        folder = "{}/{}/{}/scrubbing/".format(output_folder, ft.network, ft.dataset)
+        if self.control is None:  # (rate 0: the fault-free classes)
+            self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
+        raw, extra = [], {}
+        for scheme in schemes:
+            for burst in bursts:
+                for p in rates:
+                    for every in scrub_intervals:
+                        per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed)
+                        accuracies = [util.calculate_accuracy(row.tolist(), ft.labels) for row in ft.exposure_results]
+                        name = "{} burst {} upset rate {:g} scrub every {}".format(HARDENING_SCHEMES[scheme], burst, p, every)
+                        raw.append(self._raw(name, num_runs, 0, [], accuracies))
+                        extra[name] = {"mean accuracy per epoch": [float(x) for x in np.mean(np.array(per_epoch, float), axis=0)],
+                                       "scheme": int(scheme), "burst": int(burst), "rate": float(p), "scrub every": int(every),
+                                       "epoch images": int(epoch_images), "physical bits": int(counts[..., 0].sum()),
+                                       "logical bits per epoch": [int(x) for x in counts[..., 1].sum(axis=(0, 2, 3))]}
+        stats = self._stats(util.dict_of_dicts_merge(*raw))
+        for name, e in extra.items():
+            stats["results"][name].update(e)
+        util.write_dict_to_file("{}/{}_{}_scrubbing_stats.json".format(folder, ft.network, ft.dataset), stats)
 
     def input_sensitivity_map(self, output_folder):
         """The input-bit sweep (FaultTest.input_sensitivity) over every bit of the image, next to sensitivity_map's files:

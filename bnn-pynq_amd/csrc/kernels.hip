@@ -3227,6 +3227,146 @@ __global__ __launch_bounds__(kBlock) void k_hmem_noise_t(uint8_t *__restrict__ c
   }
 }
 
+// Exposure campaigns (bnn_mi355x_exposure_campaigns; the model: mem_org.h): the upsets of EPOCH `epoch` XORed onto the
+// physical state the earlier epochs left.  counts: this epoch's [layer][2: weights, thresholds][2] entries of run 0, run
+// q's `run_stride` longs behind; [0] += the physical bits this epoch flipped, [1] += the logical bits that now differ
+// from the loaded parameters, over ALL lanes (the caller zeroes them: every epoch has entries of its own).
+// k_xmem_noise_w: weights of a layer >= 1.  One module, no interleave: the copy itself is the state.  k_hmem_noise_w's
+// lanes, sites and stores with the epoch in the draw; the logical count compares the lane's word with the loaded blob's
+// at the same offset (2-bit weights: the (sign, low) fields).
+template <bool TWO_BIT>
+__global__ __launch_bounds__(kBlock) void k_xmem_noise_w(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L,
+                                                         unsigned ebits, unsigned burst, const unsigned long long *__restrict__ seeds,
+                                                         unsigned rate, unsigned epoch, const uint8_t *__restrict__ loaded,
+                                                         unsigned long long *__restrict__ counts, unsigned long long run_stride) {
+  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
+  unsigned c = 0, d = 0;
+  if (t < L.rows * L.kw) {
+    const unsigned n = t / L.kw, k = t - n * L.kw;
+    const unsigned long long seed = seeds[run];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), word = hardened_draw_word(0, 0, (int)burst), tag = exposure_tag(epoch);
+    constexpr unsigned kSites = TWO_BIT ? 128 : 64;
+    const unsigned per = (ebits + burst - 1) / burst;
+    const unsigned site0 = (((n % L.pe) * L.tmem + n / L.pe) * L.kw + k) * kSites;
+    unsigned element = site0 / ebits, bit = site0 - element * ebits, e = element * per + bit / burst, in_group = bit % burst;
+    uint32_t u[4], have = ~0u;
+    uint64_t mlo = 0, mhi = 0;  // (1-bit weights: mlo alone)
+    for (unsigned j = 0; j < kSites; j++) {
+      if ((e >> 2) != have) {
+        have = e >> 2;
+        act_noise_block(k0, k1, L.layer, word, have, u, tag);
+      }
+      const uint32_t ue = (e & 2) ? ((e & 1) ? u[3] : u[2]) : ((e & 1) ? u[1] : u[0]);
+      const uint64_t hit = ue < rate ? 1ull : 0ull;
+      if (!TWO_BIT) mlo |= hit << j;
+      else if (j & 1) mhi |= hit << (j >> 1);
+      else mlo |= hit << (j >> 1);
+      if (++bit == ebits) {
+        bit = 0; in_group = 0;
+        e = ++element * per;
+      } else if (++in_group == burst) {
+        in_group = 0;
+        e++;
+      }
+    }
+    const size_t at = (size_t)L.offset + (size_t)n * L.row_dwords * 4 + 8;  // (the row's planes, behind its two threshold dwords)
+    uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
+    const uint64_t *const was = reinterpret_cast<const uint64_t *>(loaded + at);
+    if constexpr (!TWO_BIT) {
+      uint64_t *const w = reinterpret_cast<uint64_t *>(row + 2) + k;
+      const uint64_t now = *w ^ mlo;
+      if (mlo) *w = now;
+      d = __popcll(now ^ was[k]);
+    } else {
+      uint64_t *const wq = reinterpret_cast<uint64_t *>(row + 2);
+      const uint64_t neg = wq[2 * k], nz = wq[2 * k + 1], two = wq[2 * L.kw + k];
+      const uint64_t hi = neg ^ mhi, lo = (nz & ~two) ^ mlo, two2 = hi & ~lo;
+      if (mlo | mhi) {
+        wq[2 * k] = hi;
+        wq[2 * k + 1] = hi | lo;
+        wq[2 * L.kw + k] = two2;
+        if (two2) atomicOr(row + 2 + 6 * L.kw, 1u);
+      }
+      d = __popcll(hi ^ was[2 * k]) + __popcll(lo ^ (was[2 * k + 1] & ~was[2 * L.kw + k]));
+    }
+    c = __popcll(mlo) + __popcll(mhi);
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    c += __shfl_xor(c, s, 64);
+    d += __shfl_xor(d, s, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && (c | d)) {
+    unsigned long long *const at = counts + (size_t)run * run_stride + (size_t)L.layer * 4;
+    if (c) atomicAdd(at, (unsigned long long)c);
+    if (d) atomicAdd(at + 1, (unsigned long long)d);
+  }
+}
+
+// k_xmem_noise_t: thresholds of the layers whose elements are 16 bits wide; k_hmem_noise_t's lane per (run, neuron n,
+// threshold i).  state[run * rows * nthr + lane] holds the accumulated hit masks of the (up to three) modules, 16 bits
+// each, in logical-image order as hits[md] there: bit k is the physical bit interleave_site gives for logical bit k -- so
+// no lane depends on another's state.  The lane draws the epoch's hits, XORs them into the state (stored only when
+// something changed), votes, and where the voted mask differs from the one before rebuilds its row dword(s) from the
+// pristine raw table.  A scrub zeroes the state and restores the copies.
+__global__ __launch_bounds__(kBlock) void k_xmem_noise_t(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L, unsigned nthr,
+                                                         Arith arith, bool signed_bb, const uint16_t *__restrict__ raw, unsigned modules,
+                                                         unsigned interleave, unsigned burst, const unsigned long long *__restrict__ seeds,
+                                                         unsigned rate, unsigned epoch, unsigned long long *__restrict__ state,
+                                                         unsigned long long *__restrict__ counts, unsigned long long run_stride) {
+  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t m = 0;
+  unsigned phys = 0;
+  if (t < L.rows * nthr) {
+    const unsigned n = t / nthr, i = t - n * nthr, mem = n % L.pe, ind = n / L.pe;
+    const unsigned long long seed = seeds[run];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), tag = exposure_tag(epoch);
+    const unsigned per = (16 + burst - 1) / burst;
+    uint32_t hits[3] = {0, 0, 0}, u[3][4], have[3] = {~0u, ~0u, ~0u};  // (a module's last Philox block: bits of one line share it)
+    for (int k = 0; k < 16; k++) {
+      int p_ind, p_bit;
+      interleave_site((int)interleave, 16, (int)L.tmem, (int)ind, k, &p_ind, &p_bit);
+      const uint32_t e = ((mem * L.tmem + (unsigned)p_ind) * nthr + i) * per + (unsigned)p_bit / burst;
+#pragma unroll
+      for (unsigned md = 0; md < 3; md++) {
+        if (md >= modules) break;
+        if ((e >> 2) != have[md]) {
+          have[md] = e >> 2;
+          act_noise_block(k0, k1, L.layer, hardened_draw_word(1, (int)md, (int)burst), have[md], u[md], tag);
+        }
+        const uint32_t ue = (e & 2) ? ((e & 1) ? u[md][3] : u[md][2]) : ((e & 1) ? u[md][1] : u[md][0]);
+        hits[md] |= (ue < rate ? 1u : 0u) << k;
+      }
+    }
+    phys = __popc(hits[0]) + __popc(hits[1]) + __popc(hits[2]);
+    unsigned long long *const st = state + (size_t)run * L.rows * nthr + t;
+    const unsigned long long before = *st;
+    const uint32_t b0 = (uint32_t)before & 0xFFFFu, b1 = (uint32_t)(before >> 16) & 0xFFFFu, b2 = (uint32_t)(before >> 32) & 0xFFFFu;
+    const uint32_t a0 = b0 ^ hits[0], a1 = b1 ^ hits[1], a2 = b2 ^ hits[2];
+    if (phys) *st = (unsigned long long)a0 | (unsigned long long)a1 << 16 | (unsigned long long)a2 << 32;
+    const uint32_t m_before = modules == 3 ? ((b0 & b1) | (b0 & b2) | (b1 & b2)) : b0;
+    m = modules == 3 ? ((a0 & a1) | (a0 & a2) | (a1 & a2)) : a0;
+    if (m != m_before) {
+      uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
+      const int32_t T = (int16_t)(uint16_t)(raw[t] ^ m);
+      const uint32_t v = (uint32_t)packed_threshold(arith, signed_bb, 64 * (int)L.kw, T);
+      row[i] = v;
+      if (nthr == 1) row[1] = v;
+    }
+  }
+  unsigned c = __popc(m);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    c += __shfl_xor(c, d, 64);
+    phys += __shfl_xor(phys, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && (phys | c)) {
+    unsigned long long *const at = counts + (size_t)run * run_stride + (size_t)L.layer * 4 + 2;
+    if (phys) atomicAdd(at, (unsigned long long)phys);
+    if (c) atomicAdd(at + 1, (unsigned long long)c);
+  }
+}
+
 // images: up to here lfcW1A1 runs as one k_lfc_block_s launch.  Round 2 (oldest-wave-first arbitration left to itself)
 // it lost to the staged kernels beyond ~40 000 images; with the per-layer wave priorities it wins over the whole range
 // of one pass (profiles/r03_lfc_block_priorities.txt, us per batch, block vs staged): 32 768 images 161 vs 175,
@@ -4028,6 +4168,39 @@ hipError_t hmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned
   const dim3 g((L.rows * (unsigned)nthr + kBlock - 1) / kBlock, (unsigned)runs);
   hipLaunchKernelGGL(k_hmem_noise_t, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)nthr, arith, signed_bb, raw,
                      (unsigned)modules, (unsigned)interleave, (unsigned)burst, seeds, rate_q32, counts, (unsigned)nlayers);
+  return hipGetLastError();
+}
+
+hipError_t xmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
+                        int ebits, int burst, uint32_t rate_q32, int epoch, const uint8_t *loaded, unsigned long long *counts, size_t run_stride,
+                        hipStream_t s) {
+  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
+  if (runs > 65535 || L.kw == 0 || L.rows == 0 || stride % 256 || L.offset % 8 || L.row_dwords % 2 ||
+      L.row_dwords < (two_bit ? 4 + 6 * L.kw : 2 + 2 * L.kw) || ebits < 1 || ebits > 64 || 64 % ebits || burst < 1 || burst > kMaxBurst ||
+      epoch < 0 || epoch >= kMaxEpochs || !loaded || (uintptr_t)loaded % 8 || !counts)
+    return hipErrorInvalidValue;
+  const dim3 g((L.rows * L.kw + kBlock - 1) / kBlock, (unsigned)runs);
+  if (two_bit)
+    hipLaunchKernelGGL(k_xmem_noise_w<true>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)ebits, (unsigned)burst, seeds,
+                       rate_q32, (unsigned)epoch, loaded, counts, (unsigned long long)run_stride);
+  else
+    hipLaunchKernelGGL(k_xmem_noise_w<false>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)ebits, (unsigned)burst, seeds,
+                       rate_q32, (unsigned)epoch, loaded, counts, (unsigned long long)run_stride);
+  return hipGetLastError();
+}
+
+hipError_t xmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
+                        bool signed_bb, const uint16_t *raw, int modules, int interleave, int burst, uint32_t rate_q32, int epoch,
+                        unsigned long long *state, unsigned long long *counts, size_t run_stride, hipStream_t s) {
+  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
+  if (runs > 65535 || L.rows == 0 || stride % 256 || L.offset % 4 || nthr < 1 || nthr > 2 || L.row_dwords < 2 || arith == AR_INT8 || !raw ||
+      (modules != 1 && modules != 3) || (interleave != 0 && interleave != HS_INTERLEAVED && interleave != HS_RESILIENT) || burst < 1 ||
+      burst > kMaxBurst || L.pe == 0 || L.rows != L.pe * L.tmem || epoch < 0 || epoch >= kMaxEpochs || !state || (uintptr_t)state % 8 || !counts)
+    return hipErrorInvalidValue;
+  const dim3 g((L.rows * (unsigned)nthr + kBlock - 1) / kBlock, (unsigned)runs);
+  hipLaunchKernelGGL(k_xmem_noise_t, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)nthr, arith, signed_bb, raw,
+                     (unsigned)modules, (unsigned)interleave, (unsigned)burst, seeds, rate_q32, (unsigned)epoch, state, counts,
+                     (unsigned long long)run_stride);
   return hipGetLastError();
 }
 

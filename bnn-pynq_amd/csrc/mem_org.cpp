@@ -133,8 +133,8 @@ void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams
 }
 
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap) {
-  if (burst < 1 || burst > kMaxBurst) return -1;
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch) {
+  if (burst < 1 || burst > kMaxBurst || epoch < 0 || epoch >= kMaxEpochs) return -1;
   MemOrg org{1, 1, 0};
   if (!hardening_layout(net, scheme, layer, org).empty()) return -1;
   const long events = enumerate_faults(net, layer, target, burst, 0, nullptr, 0);
@@ -144,13 +144,14 @@ long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t
   const uint32_t word = hardened_draw_word(target, module, burst);
   for (long b = 0; 4 * b < events; b++) {
     uint32_t u[4];
-    act_noise_block((uint32_t)run_seed, (uint32_t)(run_seed >> 32), (uint32_t)layer, word, (uint32_t)b, u, kMemNoiseTag);
+    act_noise_block((uint32_t)run_seed, (uint32_t)(run_seed >> 32), (uint32_t)layer, word, (uint32_t)b, u, exposure_tag((uint32_t)epoch));
     for (int e = 0; e < 4 && 4 * b + e < events; e++) {
       if (u[e] >= rate_q32) continue;
       if (out && total >= first && total - first < cap) {
         PhysFault &pf = out[total - first];
         enumerate_faults(net, layer, target, burst, 4 * b + e, &pf.f, 1);
         pf.module = module;
+        pf.f.image = epoch;
       }
       total++;
     }

@@ -110,6 +110,24 @@ BNN_HD inline void interleave_source(int il, int T, int lines, int p_ind, int p_
   }
 }
 
+// ---- exposure campaigns (bnn_mi355x_exposure_campaigns): upsets that accumulate, with scrubbing ---------------------------
+// A run over n images is cut into EPOCHS of `epoch_images` images: epoch t holds images [t * epoch_images,
+// min(n, (t + 1) * epoch_images)), the last one may be short, E = ceil(n / epoch_images) <= kMaxEpochs.  Rates are per
+// epoch.  The events of epoch t are the draw above with the epoch in the fourth counter word,
+//     u = philox4x32_10(counter {L, target | m << 1 | (b - 1) << 8, e >> 2, 1 + (t << 8)}, key {seed})[e & 3],
+// so t = 0 is hardened_mem_noise_mask's draw, and the low byte 1 still keeps the stream apart from the activation and
+// input draws (0 there).  An epoch's upsets XOR onto whatever the PHYSICAL state holds, before the epoch's images are
+// classified; the order inside an epoch is the one above, across epochs epoch-major (it matters for the layer-0
+// integer-part quirk of apply_fault alone).  scrub_every = S > 0: before the upsets of every epoch t > 0 with t % S == 0
+// all physical memories return to the loaded parameters (a full rewrite; a voter-driven repair is not modelled); S = 0
+// never.  The logical parameters of an epoch are de-interleave(vote(modules)) of the state.  On the host: the blob of
+// (run, epoch t) is pack_params_hardened of the masks of epochs (last scrub epoch <= t) ... t, concatenated.
+// The epoch granularity, the full-rewrite scrub and the voter are the project's own choices: parity unpinned.
+constexpr int kMaxEpochs = 1 << 16;  // (the epoch shares its counter word with the tag byte: below 2^24)
+BNN_HD inline uint32_t exposure_tag(uint32_t epoch) { return 1u + (epoch << 8); }  // (kMemNoiseTag in the low byte)
+// the last epoch <= t whose upsets met freshly written memories
+inline int exposure_first_epoch(int t, int scrub_every) { return scrub_every > 0 ? t - t % scrub_every : 0; }
+
 // ---- host only from here ---------------------------------------------------------------------------------------------
 
 struct PhysFault { Fault f; int module; };
@@ -135,8 +153,9 @@ inline int event_width(int ebits, int burst, int bit) { return ebits - bit < bur
 
 // the events of one (run seed, layer, target, module) in event order as physical faults (image 0, word_size burst);
 // returns their number (0: thresholds of a layer without any), -1 for a bad scheme, burst, layer, target or module;
-// writes events first .. first + cap - 1 to out (which may be null)
+// writes events first .. first + cap - 1 to out (which may be null).  epoch: the exposure campaigns' (above); the
+// records' image field holds it
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap);
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch = 0);
 
 }  // namespace bnn

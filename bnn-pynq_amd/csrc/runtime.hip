@@ -286,6 +286,10 @@ struct Runtime {
   // bnn_mi355x_hardened_mem_noise_campaigns (the same buffers): [run][layer][2][2: physical, logical] and the seeds
   std::vector<long> hmem_noise_counts;
   std::vector<unsigned long long> hmem_noise_seeds;
+  // bnn_mi355x_exposure_campaigns (the same buffers; the threshold state behind the tables in d_camp):
+  // [run][epoch][layer][2][2: physical bits of the epoch, logical bits after it] and the seeds
+  std::vector<long> xmem_counts;
+  std::vector<unsigned long long> xmem_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -3224,28 +3228,40 @@ struct MemNoiseJob {
   int nspans = 0;
   std::vector<uint8_t> upload;                  // patch bytes | patch spans | threshold tables
   std::vector<unsigned long long> host_counts;  // [run][layer][2]: the flips the host applied ([2][2] with a Hardening)
+  // exposure campaigns: host_counts is [run][epoch][layer][2][2]; the spans are ordered by epoch, epoch t's being
+  // span_first[t] ... span_first[t + 1] - 1; k_xmem_noise_t's state of layer l (runs * rows * nthr words) lies at
+  // state_off[l] of d_camp, all of them in [state_begin, state_begin + state_bytes)
+  std::vector<int> span_first;
+  size_t state_off[9] = {}, state_begin = 0, state_bytes = 0;
 };
 
 // Layer 0 of one run through the physical model (mem_org.h): the events of every module applied to `phys` in order, the
 // logical memories voted and de-interleaved into raw.w[0] / raw.t[0], the rows whose words now differ from the loaded ones
 // marked.  counts: [2: weights, thresholds][2: physical bits flipped, logical bits that differ].  `phys` comes back as loaded.
+// The exposure campaigns step one state through their epochs: the events are those of `epoch`, and with `keep` phys
+// stays as the events left it.  Without an event nothing but `touched` (cleared) is written: the logical state is the
+// one phys had, which the caller knows.
 static int hardened_layer0(const Hardening &hz, unsigned long long seed, const unsigned int rate[2], const PhysParams &loaded, PhysParams &phys,
-                           RawParams &raw, std::vector<char> &touched, unsigned long long counts[4]) {
+                           RawParams &raw, std::vector<char> &touched, unsigned long long counts[4], int epoch = 0, bool keep = false) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const LayerSpec &L = net.L[0];
   MemOrg org;
   hardening_layout(net, hz.scheme, 0, org);
-  std::vector<PhysFault> ev;
+  std::vector<PhysFault> ev(256);
   bool any = false;
   for (int target = 0; target < 2; target++) {
     const int ebits = mem_element_bits(L, target);
     for (int m = 0; m < (target ? org.t_modules : org.w_modules); m++) {
-      const long k = hardened_mem_noise_mask(net, hz.scheme, hz.burst, seed, 0, target, m, rate[target], 0, nullptr, 0);
+      // (one draw where the events fit the buffer: an exposure campaign comes here runs x epochs x modules times)
+      const long k = hardened_mem_noise_mask(net, hz.scheme, hz.burst, seed, 0, target, m, rate[target], 0, ev.data(), (long)ev.size(), epoch);
       if (k < 0) return fail("internal: hardened layer-0 draw");
-      ev.resize((size_t)k);
-      hardened_mem_noise_mask(net, hz.scheme, hz.burst, seed, 0, target, m, rate[target], 0, ev.data(), k);
-      for (const PhysFault &pf : ev) {
+      if ((size_t)k > ev.size()) {
+        ev.resize((size_t)k);
+        hardened_mem_noise_mask(net, hz.scheme, hz.burst, seed, 0, target, m, rate[target], 0, ev.data(), k, epoch);
+      }
+      for (long i = 0; i < k; i++) {
+        const PhysFault &pf = ev[(size_t)i];
         if (phys_apply(net, hz.scheme, phys, pf) < 0) return fail("internal: hardened layer-0 event outside the memories");
         counts[2 * target] += (unsigned long long)event_width(ebits, hz.burst, pf.f.bit);
         any = true;
@@ -3269,12 +3285,14 @@ static int hardened_layer0(const Hardening &hz, unsigned long long seed, const u
         touched[(target ? ind : ind / (size_t)(L.fold.wmem / L.fold.tmem)) * (size_t)L.fold.pe + pe] = 1;
       }
   }
-  for (int m = 0; m < 3; m++) {
+  for (int m = 0; m < 3 && !keep; m++) {
     phys.mod[m].w[0] = loaded.mod[m].w[0];
     phys.mod[m].t[0] = loaded.mod[m].t[0];
   }
   return 0;
 }
+
+static void mem_noise_upload(const std::vector<uint8_t> &staging, const std::vector<PatchSpan> &spans, const unsigned int *rth, MemNoiseJob &job);
 
 static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, MemNoiseJob &job,
                              const Hardening *hz = nullptr) {
@@ -3345,6 +3363,15 @@ static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const
       if (staging.size() > 0xFFFF0000u) return fail("mem_noise: too many layer-0 patches for one call (staging above 4 GB)");
     }
   }
+  mem_noise_upload(staging, spans, rth, job);
+  return 0;
+}
+
+// the upload of a job: patch bytes | patch spans | the raw 16-bit threshold tables of the layers with a threshold rate
+static void mem_noise_upload(const std::vector<uint8_t> &staging, const std::vector<PatchSpan> &spans, const unsigned int *rth, MemNoiseJob &job) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  const int S = net.nlayers;
   job.nspans = (int)spans.size();
   job.spans_off = (staging.size() + 255) & ~(size_t)255;
   size_t end = job.spans_off + spans.size() * sizeof(PatchSpan);
@@ -3365,6 +3392,16 @@ static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const
     for (int n = 0; n < L.mh(); n++)
       for (int i = 0; i < L.nthr; i++)
         tab[(size_t)n * L.nthr + i] = (uint16_t)(r.raw.t[l][(size_t)(n % L.fold.pe)][(size_t)(n / L.fold.pe) * L.nthr + i] & 0xFFFF);
+  }
+}
+
+// R copies of the loaded blob in r.d_copies, `stride` apart, on r.stream
+static int replicate_blob(int R, size_t stride) {
+  Runtime &r = rt();
+  HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, r.blob.size(), hipMemcpyDeviceToDevice, r.stream));
+  for (size_t have = 1; have < (size_t)R; have *= 2) {  // replicate by doubling
+    const size_t c = std::min(have, (size_t)R - have);
+    HIP_OK(hipMemcpyAsync(r.d_copies + have * stride, r.d_copies, c * stride, hipMemcpyDeviceToDevice, r.stream));
   }
   return 0;
 }
@@ -3387,11 +3424,7 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
   unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
   HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
   HIP_OK(hipMemsetAsync(d_counts, 0, (size_t)R * S * (hz ? 4 : 2) * 8, r.stream));
-  HIP_OK(hipMemcpyAsync(r.d_copies, r.d_blob, r.blob.size(), hipMemcpyDeviceToDevice, r.stream));
-  for (size_t have = 1; have < (size_t)R; have *= 2) {  // replicate by doubling
-    const size_t c = std::min(have, (size_t)R - have);
-    HIP_OK(hipMemcpyAsync(r.d_copies + have * stride, r.d_copies, c * stride, hipMemcpyDeviceToDevice, r.stream));
-  }
+  if (replicate_blob(R, stride)) return -1;
   if (!job.upload.empty()) HIP_OK(hipMemcpyAsync(r.d_camp, job.upload.data(), job.upload.size(), hipMemcpyHostToDevice, r.stream));
   hipError_t e = scatter_patches(r.d_camp, reinterpret_cast<const PatchSpan *>(r.d_camp + job.spans_off), job.nspans, r.d_copies, r.stream);
   for (int l = 0; l < S && e == hipSuccess; l++) {
@@ -3414,21 +3447,173 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
   return 0;
 }
 
+// ---- exposure campaigns: upsets that accumulate over epochs, with scrubbing (the model: mem_org.h) -------------------------
+
+struct Exposure { int epoch_images, scrub_every; };
+
+static bool exposure_scrubs(const Exposure &ex, int t) { return t > 0 && ex.scrub_every > 0 && t % ex.scrub_every == 0; }
+
+// What the host prepares for E epochs.  Layer 0 of the CNV nets: one persistent physical working state per run is stepped
+// through the epochs by hardened_layer0, scrubs included (the draw is deterministic, so all of it is known before anything
+// is enqueued); the rows and tables an epoch changes become that epoch's patches.  A row is rebuilt where its words differ from the loaded
+// ones now or did so after the epoch before (it may have returned to them).  Then mem_noise_prepare's tables, and the
+// layout of the threshold state.
+static int exposure_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, int E,
+                            const Exposure &ex, const Hardening &hz, MemNoiseJob &job) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  const int R = (int)seeds.size(), S = net.nlayers;
+  PackedHeader h;
+  std::memcpy(&h, r.blob.data(), sizeof(h));
+  job.stride = (r.blob.size() + 255) & ~(size_t)255;
+  job.host_counts.assign((size_t)R * E * S * 4, 0);
+  std::vector<uint8_t> staging;
+  std::vector<std::vector<PatchSpan>> by_epoch((size_t)E);
+  if (net.L[0].arith == AR_INT8 && (rw[0] || rth[0])) {
+    RawParams raw;  // (layer 0's memories alone: nothing else is read here)
+    raw.w[0] = r.raw.w[0];
+    raw.t[0] = r.raw.t[0];
+    // the rows and tables are packed into a working blob and copied out: every span is rebuilt from `raw` in full, so what
+    // an earlier epoch or run left in the blob is never uploaded
+    std::vector<uint8_t> blob = r.blob;
+    const size_t rb = (size_t)h.layer[0].row_dwords * 4;
+    std::vector<char> touched(h.layer[0].rows), before(h.layer[0].rows);
+    PhysParams loaded, phys;
+    phys_load(net, hz.scheme, r.raw, 0, 1, loaded);
+    const unsigned int rate[2] = {rw[0], rth[0]};
+    for (int q = 0; q < R; q++) {
+      phys = loaded;
+      std::fill(before.begin(), before.end(), 0);
+      for (int t = 0; t < E; t++) {
+        unsigned long long *const counts = &job.host_counts[(((size_t)q * E + t) * S + 0) * 4];
+        const bool scrub = exposure_scrubs(ex, t);
+        if (scrub) {  // (the copies on the device return to the loaded blob as well)
+          phys = loaded;
+          std::fill(before.begin(), before.end(), 0);
+        }
+        if (hardened_layer0(hz, seeds[(size_t)q], rate, loaded, phys, raw, touched, counts, t, true)) return -1;
+        if (counts[0] + counts[2] == 0) {  // no event: nothing to patch; without a scrub the logical state is the last epoch's
+          if (!scrub && t > 0) {
+            counts[1] = counts[1 - S * 4];
+            counts[3] = counts[3 - S * 4];
+          }
+          continue;
+        }
+        auto add_span = [&](size_t off, size_t bytes) {
+          by_epoch[(size_t)t].push_back(PatchSpan{(uint64_t)q * job.stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
+          staging.insert(staging.end(), blob.begin() + off, blob.begin() + off + bytes);
+        };
+        bool rebuilt = false;
+        for (uint32_t n = 0; n < h.layer[0].rows; n++) {
+          if (!touched[n] && !before[n]) continue;
+          repack_row_only(net, raw, 0, (int)n, blob);
+          add_span(h.layer[0].offset + (size_t)n * rb, rb);
+          rebuilt = true;
+        }
+        if (rebuilt && h.l0_mfma_offset) {  // (once per epoch, not once per row as repack_row would)
+          repack_l0_tables(net, raw, blob);
+          add_span(h.l0_mfma_offset, kL0MfmaBytes);
+        }
+        before = touched;
+        if (staging.size() > 0xFFFF0000u) return fail("exposure: too many layer-0 patches for one call (staging above 4 GB)");
+      }
+    }
+  }
+  std::vector<PatchSpan> spans;
+  job.span_first.assign((size_t)E + 1, 0);
+  for (int t = 0; t < E; t++) {
+    spans.insert(spans.end(), by_epoch[(size_t)t].begin(), by_epoch[(size_t)t].end());
+    job.span_first[(size_t)t + 1] = (int)spans.size();
+  }
+  mem_noise_upload(staging, spans, rth, job);
+  size_t end = (job.upload.size() + 255) & ~(size_t)255;
+  job.state_begin = end;
+  for (int l = 0; l < S; l++) {
+    const LayerSpec &L = net.L[l];
+    if (!rth[l] || L.thr24) continue;
+    job.state_off[l] = end;
+    end += (((size_t)R * L.mh() * L.nthr * 8) + 255) & ~(size_t)255;
+  }
+  job.state_bytes = end - job.state_begin;
+  return 0;
+}
+
+// Enqueues on r.stream what comes before epoch 0: the seeds, the zeroed [run][epoch][layer][2][2] counters at counts_off of
+// d_noise, the runs' copies of the loaded blob, the job's upload and the zeroed threshold state.
+static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, int E) {
+  Runtime &r = rt();
+  const int R = (int)seeds.size(), S = r.spec.nlayers;
+  const size_t counts_bytes = (size_t)R * E * S * 4 * 8;
+  if (grow(r.d_copies, r.copies_cap, (size_t)R * job.stride) || grow(r.d_camp, r.camp_cap, job.state_begin + job.state_bytes + 256) ||
+      grow(r.d_noise, r.noise_cap, counts_off + counts_bytes))
+    return -1;
+  HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
+  HIP_OK(hipMemsetAsync(r.d_noise + counts_off, 0, counts_bytes, r.stream));
+  if (replicate_blob(R, job.stride)) return -1;
+  if (!job.upload.empty()) HIP_OK(hipMemcpyAsync(r.d_camp, job.upload.data(), job.upload.size(), hipMemcpyHostToDevice, r.stream));
+  if (job.state_bytes) HIP_OK(hipMemsetAsync(r.d_camp + job.state_begin, 0, job.state_bytes, r.stream));
+  return 0;
+}
+
+// Enqueues epoch t: the scrub where one is due (the copies restored by the same doubling copy, the state cleared), the
+// host's layer-0 patches of the epoch, then the upset kernels layer by layer, weights before thresholds.
+static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned int *rth, const MemNoiseJob &job, size_t counts_off, int E,
+                          const Exposure &ex, const Hardening &hz) {
+  Runtime &r = rt();
+  const NetSpec &net = r.spec;
+  const int S = net.nlayers;
+  PackedHeader h;
+  std::memcpy(&h, r.blob.data(), sizeof(h));
+  const size_t stride = job.stride;
+  const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+  unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)t * S * 4;
+  const size_t run_stride = (size_t)E * S * 4;
+  if (exposure_scrubs(ex, t)) {
+    if (replicate_blob(R, stride)) return -1;
+    if (job.state_bytes) HIP_OK(hipMemsetAsync(r.d_camp + job.state_begin, 0, job.state_bytes, r.stream));
+  }
+  const int s0 = job.span_first[(size_t)t], s1 = job.span_first[(size_t)t + 1];
+  hipError_t e = scatter_patches(r.d_camp, reinterpret_cast<const PatchSpan *>(r.d_camp + job.spans_off) + s0, s1 - s0, r.d_copies, r.stream);
+  for (int l = 0; l < S && e == hipSuccess; l++) {
+    const LayerSpec &L = net.L[l];
+    if (L.arith == AR_INT8) continue;  // (the host's part)
+    const MemNoiseLayer ml{h.layer[l].offset, h.layer[l].row_dwords, h.layer[l].rows, h.layer[l].kw, (uint32_t)L.fold.pe, (uint32_t)L.fold.tmem, (uint32_t)l};
+    MemOrg org{1, 1, 0};
+    hardening_layout(net, hz.scheme, l, org);  // (checked by mem_noise_check; weights of a layer >= 1 have one module)
+    e = xmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
+                     static_cast<const uint8_t *>(r.d_blob), d_counts, run_stride, r.stream);
+    // a flip may have removed the last -2 of a row (the loaded parameters may hold -2 rows, and so may an earlier epoch's state)
+    if (e == hipSuccess && L.arith == AR_TT && rw[l] && (r.two_rows > 0 || t > 0)) e = mem_noise_flags(r.d_copies, stride, R, ml, r.stream);
+    if (e == hipSuccess && rth[l])
+      e = xmem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
+                       org.t_modules, org.t_interleave, hz.burst, rth[l], t, reinterpret_cast<unsigned long long *>(r.d_camp + job.state_off[l]),
+                       d_counts, run_stride, r.stream);
+  }
+  if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+  return 0;
+}
+
 // Random upsets of the parameter memories, many runs in one call.  Every run gets a copy of the loaded blob in HBM with its
 // upsets applied in place (mem_noise_enqueue); the (run, image) pairs then go in run-major order, in groups of at most one
 // activation workspace, through the multi-run stages with the copy stride: act_noise_campaigns' grouping with
 // fault_campaigns' copies.  kMaxRuns copies are what fault_campaigns holds as well, so a call's runs always fit.
 // hz null: bnn_mi355x_mem_noise_campaigns; else the hardened form, whose counters have two entries per (layer, target).
+// ex (with hz): bnn_mi355x_exposure_campaigns -- the images go epoch by epoch, each epoch's scrub and upsets enqueued in
+// front of its pairs (exposure_epoch), and the counters have one [layer][2][2] block per (run, epoch).
 static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const char *path, int number_class, int num_runs, unsigned long long seed,
                                      const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
-                                     float *usecPerImage) {
+                                     float *usecPerImage, const Exposure *ex = nullptr) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  std::vector<long> &last_counts = hz ? r.hmem_noise_counts : r.mem_noise_counts;
-  std::vector<unsigned long long> &last_seeds = hz ? r.hmem_noise_seeds : r.mem_noise_seeds;
+  std::vector<long> &last_counts = ex ? r.xmem_counts : (hz ? r.hmem_noise_counts : r.mem_noise_counts);
+  std::vector<unsigned long long> &last_seeds = ex ? r.xmem_seeds : (hz ? r.hmem_noise_seeds : r.mem_noise_seeds);
   last_counts.clear();
   last_seeds.clear();
   const int S = net.nlayers;
+  if (ex && (ex->epoch_images < 1 || ex->scrub_every < 0)) {
+    fail(std::string(who) + ": epoch_images must be at least 1 and scrub_every must not be negative (0: never scrub)");
+    return nullptr;
+  }
   if (!path) {
     fail(std::string(who) + ": bad arguments (path missing)");
     return nullptr;
@@ -3448,6 +3633,14 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
   const int n = (int)f.n;
   const size_t total = (size_t)R * n;
   const bool cnv = net.is_cnv;
+  const int ei = ex ? ex->epoch_images : std::max(n, 1);  // images per epoch; without ex the call is one epoch
+  const long long epochs = ((long long)n + ei - 1) / ei;
+  if (ex && (epochs > kMaxEpochs || (unsigned long long)R * (unsigned long long)epochs * S * 4 > 0x7FFFFFFFull)) {
+    fail(std::string(who) + ": " + std::to_string(epochs) + " epochs: at most " + std::to_string(kMaxEpochs) +
+         ", and num_runs * epochs * layers * 4 counters must stay below 2^31");
+    return nullptr;
+  }
+  const int E = (int)epochs;
   std::vector<unsigned long long> seeds((size_t)R);
   {
     std::random_device rd;
@@ -3464,33 +3657,38 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
   }
   int *result = new (std::nothrow) int[total + 1];
   if (!result) { fail("out of memory"); return nullptr; }
-  std::vector<unsigned long long> counts((size_t)R * S * (hz ? 4 : 2), 0);
+  std::vector<unsigned long long> counts((size_t)R * (ex ? E : 1) * S * (hz ? 4 : 2), 0);
   MemNoiseJob job;
   double device_us = 0.0;
   auto run = [&]() -> int {
     if (n == 0) return 0;
-    if (any && mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job, hz)) return -1;
+    if (any && (ex ? exposure_prepare(seeds, rate_w_q32, rate_t_q32, E, *ex, *hz, job) : mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job, hz)))
+      return -1;
     size_t cap = std::min<size_t>(kMaxChunk, total);  // pairs per group: the activation workspace
     if (const char *e = std::getenv("BNN_MI355X_NOISE_GROUP")) {  // tests: many small groups
       const long long v = std::atoll(e);
       if (v > 0) cap = std::min<size_t>(cap, (size_t)v);
     }
-    // the records of every group: a run's images, cut at the group's end
-    struct Group { size_t seg0; int nsegs, max_len, total; };
+    // the records of every group: a run's images of one epoch, cut at the group's end; the epochs one after the other
+    struct Group { size_t seg0; int nsegs, max_len, total, epoch; };
     std::vector<MultiSeg> segs;
     std::vector<Group> groups;
-    for (size_t p0 = 0; p0 < total; p0 += cap) {
-      const size_t p1 = std::min(total, p0 + cap);
-      Group g{segs.size(), 0, 0, 0};
-      for (size_t p = p0; p < p1;) {
-        const int q = (int)(p / (size_t)n), i = (int)(p % (size_t)n), m = (int)std::min<size_t>((size_t)(n - i), p1 - p);
-        segs.push_back(MultiSeg{q, i, g.total, m});
-        g.nsegs++;
-        g.total += m;
-        g.max_len = std::max(g.max_len, m);
-        p += (size_t)m;
+    for (int t = 0; t < E; t++) {
+      const int i0 = t * ei, len = std::min(n, i0 + ei) - i0;  // (t * ei < n)
+      const size_t pairs = (size_t)R * len;
+      for (size_t p0 = 0; p0 < pairs; p0 += cap) {
+        const size_t p1 = std::min(pairs, p0 + cap);
+        Group g{segs.size(), 0, 0, 0, t};
+        for (size_t p = p0; p < p1;) {
+          const int q = (int)(p / (size_t)len), i = (int)(p % (size_t)len), m = (int)std::min<size_t>((size_t)(len - i), p1 - p);
+          segs.push_back(MultiSeg{q, i0 + i, g.total, m});
+          g.nsegs++;
+          g.total += m;
+          g.max_len = std::max(g.max_len, m);
+          p += (size_t)m;
+        }
+        groups.push_back(g);
       }
-      groups.push_back(g);
     }
     PackedHeader h;
     std::memcpy(&h, r.blob.data(), sizeof(h));
@@ -3511,12 +3709,15 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     }
     // -- all of it on one stream, one wait at the end
     HIP_OK(hipEventRecord(r.time_events[0], r.stream));
-    if (any && mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off, hz)) return -1;
+    if (any && (ex ? exposure_begin(seeds, job, counts_off, E) : mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off, hz))) return -1;
     // (all rates 0: no copy is made, every run reads the loaded blob)
     const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
     const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
     HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
+    int entered = -1;  // (exposure) the last epoch whose scrub and upsets are in the stream
     for (const Group &g : groups) {
+      for (; ex && any && entered < g.epoch; entered++)
+        if (exposure_epoch(entered + 1, R, rate_w_q32, rate_t_q32, job, counts_off, E, *ex, *hz)) return -1;
       MultiLaunch a{};
       a.images = r.d_all;
       a.segs = d_segs + g.seg0;
@@ -3718,6 +3919,82 @@ int bnn_mi355x_last_hardened_mem_noise_counts(long *counts, int cap) {
 
 int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap) {
   const std::vector<unsigned long long> &k = rt().hmem_noise_seeds;
+  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
+  return (int)k.size();
+}
+
+// ---- exposure campaigns (the model: mem_org.h) ------------------------------------------------------------------------------
+
+long bnn_mi355x_exposure_mask(int scheme, int burst, unsigned long long run_seed, int epoch, int layer, int target, int module,
+                              unsigned int rate_q32, long first, int *records, int cap_records) {
+  const NetSpec &net = rt().spec;
+  MemOrg org;
+  const std::string e = hardening_layout(net, scheme, layer, org);
+  if (!e.empty()) return fail("exposure_mask: " + e);
+  const long total = first < 0 ? -1 : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0, epoch);
+  if (total < 0)
+    return fail("exposure_mask: bad burst (1 ... " + std::to_string(kMaxBurst) + "), epoch (0 ... " + std::to_string(kMaxEpochs - 1) +
+                "), target (0 weights, 1 thresholds), module (of those the memory has) or first");
+  if (records && cap_records > 0 && first < total) {
+    std::vector<PhysFault> v((size_t)std::min<long>(cap_records, total - first));
+    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size(), epoch);
+    for (size_t i = 0; i < v.size(); i++) {
+      const Fault &f = v[i].f;
+      const int w[9] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size, v[i].module};
+      std::memcpy(records + i * 9, w, sizeof w);
+    }
+  }
+  return total;
+}
+
+int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs, unsigned long long seed,
+                                   const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch_images, int scrub_every,
+                                   int *image_number, float *usecPerImage) {
+  const Hardening hz{scheme, burst};
+  const Exposure ex{epoch_images, scrub_every};
+  return mem_noise_campaigns_impl("exposure_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number,
+                                  usecPerImage, &ex);
+}
+
+// One copy stepped through epochs 0 ... epoch by the campaign's own steps (exposure_begin, exposure_epoch), then read back.
+size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                  const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
+  Runtime &r = rt();
+  const Hardening hz{scheme, burst};
+  const Exposure ex{1, scrub_every};
+  if (epoch < 0 || epoch >= kMaxEpochs || scrub_every < 0) {
+    fail("exposure_params: epoch must be 0 ... " + std::to_string(kMaxEpochs - 1) + " and scrub_every must not be negative (0: never scrub)");
+    return 0;
+  }
+  if (mem_noise_check("exposure_params", rate_w_q32, rate_t_q32, n_rates, &hz)) return 0;
+  if (!dst) return r.blob.size();
+  if (cap < r.blob.size()) { fail("exposure_params: destination too small"); return 0; }
+  const std::vector<unsigned long long> seeds(1, run_seed);
+  const int E = epoch + 1;
+  MemNoiseJob job;
+  auto run = [&]() -> int {
+    if (exposure_prepare(seeds, rate_w_q32, rate_t_q32, E, ex, hz, job)) return -1;
+    DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+    if (settle_handover(r.stream)) return -1;
+    if (exposure_begin(seeds, job, 256, E)) return -1;
+    for (int t = 0; t < E; t++)
+      if (exposure_epoch(t, 1, rate_w_q32, rate_t_q32, job, 256, E, ex, hz)) return -1;
+    HIP_OK(hipMemcpyAsync(dst, r.d_copies, r.blob.size(), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    return 0;
+  };
+  return run() < 0 ? 0 : r.blob.size();
+}
+
+int bnn_mi355x_last_exposure_counts(long *counts, int cap) {
+  const std::vector<long> &c = rt().xmem_counts;
+  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
+  return (int)c.size();
+}
+
+int bnn_mi355x_last_exposure_seeds(unsigned long long *seeds, int cap) {
+  const std::vector<unsigned long long> &k = rt().xmem_seeds;
   for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
   return (int)k.size();
 }

@@ -70,6 +70,16 @@ for scheme in schemes:
                   % (bnn.faults.HARDENING_SCHEMES[scheme], burst, p, e["min accuracy"], e["avg accuracy"], e["max accuracy"],
                      e["physical bits"], e["logical bits"]))
 
+# how often the memories must be rewritten: the same upsets ACCUMULATE over 8 epochs of 250 images at a rate per epoch,
+# never scrubbed, scrubbed every other epoch and every epoch; unhardened and TMR
+net.scrubbing_curve(out, 10, [2.0 ** -10], [0, 2, 1], [0, 1], 250, seed=1)
+stats = json.load(open(os.path.join(out, "cnvW1A1", "cifar10", "scrubbing", "cnvW1A1_cifar10_scrubbing_stats.json")))
+for scheme in (0, 1):
+    for every in (0, 2, 1):
+        e = stats["results"]["%s burst 1 upset rate %g scrub every %d" % (bnn.faults.HARDENING_SCHEMES[scheme], 2.0 ** -10, every)]
+        print("%-6s scrub every %d: mean accuracy per epoch %s" % (bnn.faults.HARDENING_SCHEMES[scheme], every,
+                                                                  np.round(e["mean accuracy per epoch"], 2).tolist()))
+
 # the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
 net.input_upset_rate_curve(out, 10, rates, seed=1)
 for p in rates:

@@ -372,7 +372,8 @@ long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigne
  * activation and input draws have 0 in the fourth counter word: the three models never share a stream.  The parameters
  * of a run are what bnn_mi355x_pack_params_faulty builds from the loaded parameters with every flipped site applied as a
  * word_size-1 record, layer-major, per layer weights then thresholds, in site order; they are in place from the first
- * image to the last (the memory state after the exposure).  Results depend on (seed, run, rates) and the loaded
+ * image to the last (the memory state after the exposure; upsets that arrive while the run goes on: the exposure
+ * campaigns below).  Results depend on (seed, run, rates) and the loaded
  * parameters alone, not on batch size, grouping or chunking.  The reference has no rate-based injection: parity is
  * unpinned, the mechanism of a single flip is the pinned one.
  * mem_noise_campaigns: num_runs (1 ... 4096) independent runs over the images of `path`, run r with seed + r (refused if
@@ -462,6 +463,54 @@ size_t bnn_mi355x_hardened_mem_noise_params(int scheme, int burst, unsigned long
                                             const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap);
 int bnn_mi355x_last_hardened_mem_noise_counts(long *counts, int cap);
 int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap);
+
+/* Exposure campaigns: memory upsets that ACCUMULATE while a run goes on, with scrubbing -- how often must the memories
+ * be rewritten?  The campaigns above put every upset in place before the first image; here the physical state of the
+ * hardened model (scheme, burst, modules, interleave, voter: all as above) lives on the device between steps.
+ * Epochs: a run over n images is cut into epochs of `epoch_images` images; epoch t holds images [t * epoch_images,
+ * min(n, (t + 1) * epoch_images)), the last one may be short, E = ceil(n / epoch_images).  E is at most 65 536, and
+ * num_runs * E * layers * 4 must stay below 2^31 (the counters' index): refused beyond.
+ * Rates are PER EPOCH: rate_w_q32[L], rate_t_q32[L] in units of 2^-32, the probability of an event in one epoch.
+ * Draw: the events of epoch t are the hardened campaign's with the epoch in the fourth counter word,
+ *     u = philox4x32_10(counter {L, target | m << 1 | (b - 1) << 8, e >> 2, 1 + (t << 8)}, key {k & 0xffffffff, k >> 32})[e & 3]
+ * and the event happens iff u < rate.  t = 0 is exactly hardened_mem_noise_mask's draw; the activation and input draws
+ * have 0 in that word, so the low byte 1 keeps the streams apart.
+ * Order: an epoch's upsets apply to the PHYSICAL state before the epoch's images are classified, XORed onto whatever the
+ * state holds; inside an epoch layer-major, weights then thresholds, module-major, in event order; across epochs
+ * epoch-major (the order matters only for the layer-0 integer-part quirk, kept as is).
+ * Scrubbing: scrub_every = S.  0: never.  S > 0: before the upsets of every epoch t > 0 with t % S == 0 all physical
+ * memories return to the loaded parameters -- a full rewrite; a voter-driven repair scrub is not modelled.
+ * The logical parameters of an epoch are de-interleave(vote(modules)) of the physical state.  On the host: the blob of
+ * (run k, epoch t) is pack_params_hardened(dir, scheme, records), the records being the concatenation over epochs
+ * t' = (last scrub epoch <= t) ... t of exposure_mask's records of that epoch, each in the in-epoch order above.
+ * The voter, the epoch granularity and the full-rewrite scrub are the project's own choices (the reference injects at
+ * image times into unhardened memories and has no scrub): parity unpinned.
+ * exposure_mask: host only.  hardened_mem_noise_mask for one epoch (0 ... 65 535): the same 9-int physical records and
+ * paging, the record's image field holding the epoch; with epoch 0 every other field equals that function's.
+ * exposure_campaigns: returns int[num_runs * n], run-major (free_results); image j is classified with the state of epoch
+ * j / epoch_images.  Seeds, num_runs limits, usecPerImage, grouping (BNN_MI355X_NOISE_GROUP, inside an epoch) and what
+ * stays untouched (the loaded parameters, params_crc, the last_* state of every other entry point) follow
+ * hardened_mem_noise_campaigns, and so do the refusals: the same (network, scheme) pairs, an imported blob, the
+ * BNN_MI355X_L1 comparison forms, burst outside 1 ... 16; also epoch_images < 1, scrub_every < 0 and E beyond the cap.
+ * All before any device work, NULL + last_error.  All rates 0: the fault-free classes, no upset kernel or copy is
+ * launched.  With epoch_images >= n the call computes hardened_mem_noise_campaigns' classes and counts.
+ * exposure_params: the blob run `run_seed` classifies epoch `epoch` with, made on the device by the campaign's own
+ * kernels and scrub steps -- one copy stepped through epochs 0 ... epoch -- and read back.  dst NULL queries the size;
+ * 0 + last_error for what the campaign refuses, an epoch outside 0 ... 65 535 or a destination too small.
+ * last_exposure_counts: per [run][epoch][layer][2: weights, thresholds] two longs: the physical bits flipped IN that
+ * epoch, and the logical bits that differ from the loaded parameters AFTER that epoch's upsets; returns runs * E *
+ * layers * 4.
+ * last_exposure_seeds: the runs' seeds of the last such call. */
+long bnn_mi355x_exposure_mask(int scheme, int burst, unsigned long long run_seed, int epoch, int layer, int target,
+                              int module, unsigned int rate_q32, long first, int *records, int cap_records);
+int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs,
+                                   unsigned long long seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32,
+                                   int n_rates, int epoch_images, int scrub_every, int *image_number, float *usecPerImage);
+size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                  const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst,
+                                  size_t cap);
+int bnn_mi355x_last_exposure_counts(long *counts, int cap);
+int bnn_mi355x_last_exposure_seeds(unsigned long long *seeds, int cap);
 
 /* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
  * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column

@@ -414,13 +414,15 @@ class PynqBNN:
         return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2, 2)
 
     # extension: exposure campaigns (upsets that accumulate over epochs of images, with scrubbing)
-    def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0):
+    def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0, code=0):
         """inference_multiple_hardened_mem_noise spread over time: the run is cut into epochs of `epoch_images` images, the
         rates are per epoch, an epoch's upsets XOR onto the physical state the earlier ones left, and before every epoch
         t > 0 with t % scrub_every == 0 (0: never) all memories are rewritten from the loaded parameters.  -> (classes
         int32 (num_runs, n), counts int64 (num_runs, epochs, layers, 2: weights, thresholds, 2: physical bits flipped in
         the epoch, logical bits that differ from the loaded parameters after it)).  The seeds are left in
-        self.mem_noise_seeds."""
+        self.mem_noise_seeds.  code 1 (SEC-DED coded 16-bit threshold memories): inference_multiple_ecc_exposure."""
+        if code:
+            return self.inference_multiple_ecc_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme, code, burst, seed)
         lib = self.interface
         qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
         qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
@@ -441,6 +443,35 @@ class PynqBNN:
         self.usecPerImage = usec.value
         epochs = -(-size.value // epoch_images)
         return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 2, 2)
+
+    # extension: SEC-DED coded threshold memories in the exposure campaigns
+    def inference_multiple_ecc_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, code=1, burst=1, seed=0):
+        """inference_multiple_exposure with the 16-bit threshold memories protected by a SEC-DED code (`code` 1; 0: none):
+        Hamming(21,16) plus an overall parity bit, the 6 check bits of an element in a check memory of their own that takes
+        upsets at the threshold rate; `scheme` 0 or 2 (interleaved: a burst becomes single errors of two code words).
+        Weights and the 24-bit thresholds of CNV layer 0 are not coded.  -> (classes int32 (num_runs, n), counts int64
+        (num_runs, epochs, layers, 6: weights physical, logical; thresholds physical (data plus check), logical (after
+        decoding); threshold words corrected; detected as uncorrectable)).  The seeds are left in self.mem_noise_seeds."""
+        lib = self.interface
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_ecc_exposure_campaigns(path.encode(), len(self.classes), scheme, code, burst, num_runs, seed, qw.ctypes.data_as(up),
+                                                    qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every, ctypes.byref(size),
+                                                    ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("ecc exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_ecc_exposure_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_ecc_exposure_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_ecc_exposure_seeds(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        epochs = -(-size.value // epoch_images)
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 6)
 
     # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
     def enumerate_input_faults(self):

@@ -68,6 +68,17 @@ def propagation_curves(alive, flipped, n_images, first=0):
 
 # the memory organisations of the fork's hardened overlays (csrc/mem_org.h), by the scheme number the C ABI takes
 HARDENING_SCHEMES = ("none", "TMR", "interleaved", "resilient-interleaved")
+# the codes of the 16-bit threshold memories (csrc/ecc.h), by the code number the C ABI takes; the project's own model
+ECC_CODES = ("", "SEC-DED")
+
+
+def scheme_and_code(entry):
+    """an entry of hardening_curve's / scrubbing_curve's `schemes`: a plain scheme, or a (scheme, code) pair"""
+    return (int(entry[0]), int(entry[1])) if isinstance(entry, (tuple, list)) else (int(entry), 0)
+
+
+def organisation_name(scheme, code=0):
+    return HARDENING_SCHEMES[scheme] + (" + " + ECC_CODES[code] if code else "")
 
 
 def hardening_of(overlay):
@@ -237,8 +248,9 @@ class FaultTest:
         print()
         return accuracies
 
-    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
-        """scheme (0 ... 3, HARDENING_SCHEMES) or burst > 1: the upsets hit the physical memories of that hardened
+    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1, code=0):
+        """code 1 (SEC-DED coded threshold memories, csrc/ecc.h; scheme 0 or 2): the exposure campaign with one epoch, which
+        is the one-shot campaign; the counts are then [run, layer, 6] as run_exposure_test's.  scheme (0 ... 3, HARDENING_SCHEMES) or burst > 1: the upsets hit the physical memories of that hardened
         organisation in bursts of `burst` adjacent bits, and the counts are [run, layer, 2, 2: physical bits flipped,
         logical bits that differ after voting and de-interleaving].  Else (today's path, unchanged) num_runs independent runs with every bit of layer L's weight memory flipped with probability rates_w[L] and
         every bit of its threshold memory with rates_t[L] (scalars: every layer; thresholds: every layer that has any), in
@@ -248,7 +260,11 @@ class FaultTest:
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, memory upset rate(s) weights {} thresholds {}".format(
             self.network, self.dataset, num_runs, rates_w, rates_t))
-        if scheme is not None or burst != 1:
+        if code:
+            print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code), burst))
+            results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, 1 << 30, 0, scheme or 0, burst, seed, code)
+            counts = counts[:, 0]
+        elif scheme is not None or burst != 1:
             print("  memory organisation: {}, bursts of {}".format(HARDENING_SCHEMES[scheme or 0], burst))
             results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed, scheme or 0, burst)
         else:
@@ -259,19 +275,22 @@ class FaultTest:
         print()
         return accuracies, counts
 
-    def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0):
+    def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0, code=0):
         """Upsets that accumulate while the run goes on: the images are cut into epochs of `epoch_images`, rates_w[L] /
         rates_t[L] are the probability of an event PER EPOCH (scalars: every layer), an epoch's upsets XOR onto the physical
         state of the hardened organisation `scheme` (None: 0) the earlier epochs left, and every `scrub_every` epochs (0:
         never) the memories are rewritten.  -> (accuracy in percent [run][epoch], over the epoch's images; counts [run,
         epoch, layer, 2: weights, thresholds, 2: physical bits flipped in the epoch, logical bits that differ after it]).
+        code 1: the 16-bit threshold memories carry a SEC-DED code (csrc/ecc.h; scheme 0 or 2; weights and CNV layer 0 are
+        not coded) and the counts are [run, epoch, layer, 6: weights physical, logical; thresholds physical (data plus check
+        bits), logical (after decoding); threshold words corrected; detected as uncorrectable].
         Left behind: self.exposure_results (classes, [run, image]), self.exposure_counts, self.exposure_usec."""
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, epochs of {} images, upset rate(s) per epoch weights {} thresholds {}, {}, bursts of {}, "
-              "scrub every {}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t, HARDENING_SCHEMES[scheme or 0],
-                                      burst, scrub_every or "never"))
-        results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst,
-                                         seed)
+              "scrub every {}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t,
+                                      organisation_name(scheme or 0, code), burst, scrub_every or "never"))
+        args = (num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst, seed)
+        results, counts = self._classify(classifier, "_exposure", *(args + (code,) if code else args))
         self.exposure_results, self.exposure_counts, self.exposure_usec = results, counts, classifier.usecPerImage
         accuracies = [[util.calculate_accuracy(row[i: i + epoch_images].tolist(), self.labels[i: i + epoch_images])
                        for i in range(0, results.shape[1], epoch_images)] for row in results]
@@ -587,20 +606,27 @@ class NetworkTest:
         output_folder/<network>/<dataset>/hardening/<network>_<dataset>_hardening_stats.json, with one result
         "<scheme name> burst <b> upset rate <p>" per combination: the runs' accuracies with min / max / average, plus
         "stddev accuracy", "scheme", "burst", "rate" and the "physical bits" flipped and "logical bits" that differ after
-        voting and de-interleaving, summed over the runs."""
+        voting and de-interleaving, summed over the runs.  An entry of `schemes` may be a (scheme, code) pair (code 1: SEC-DED
+        coded threshold memories): its name is "<scheme name> + SEC-DED", and it also writes "code", "corrected words" and
+        "detected words"."""
         ft = self.fault_test
         folder = "{}/{}/{}/hardening/".format(output_folder, ft.network, ft.dataset)
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme in schemes:
+        for scheme, code in map(scheme_and_code, schemes):
             for burst in bursts:
                 for p in rates:
-                    accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, scheme, burst)
-                    name = "{} burst {} upset rate {:g}".format(HARDENING_SCHEMES[scheme], burst, p)
+                    accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, scheme, burst, code)
+                    name = "{} burst {} upset rate {:g}".format(organisation_name(scheme, code), burst, p)
                     raw.append(self._raw(name, num_runs, 0, [], accuracies))
-                    extra[name] = {"stddev accuracy": float(np.std(accuracies)), "scheme": int(scheme), "burst": int(burst), "rate": float(p),
-                                   "physical bits": int(counts[..., 0].sum()), "logical bits": int(counts[..., 1].sum())}
+                    extra[name] = {"stddev accuracy": float(np.std(accuracies)), "scheme": int(scheme), "burst": int(burst), "rate": float(p)}
+                    if code:  # [run, layer, 6]
+                        extra[name].update({"code": int(code), "physical bits": int(counts[..., [0, 2]].sum()),
+                                            "logical bits": int(counts[..., [1, 3]].sum()), "corrected words": int(counts[..., 4].sum()),
+                                            "detected words": int(counts[..., 5].sum())})
+                    else:
+                        extra[name].update({"physical bits": int(counts[..., 0].sum()), "logical bits": int(counts[..., 1].sum())})
         stats = self._stats(util.dict_of_dicts_merge(*raw))
         for name, e in extra.items():
             stats["results"][name].update(e)
@@ -613,24 +639,32 @@ class NetworkTest:
         with one result "<scheme name> burst <b> upset rate <p> scrub every <S>" per combination: the runs' accuracies over
         ALL images with min / max / average, plus "mean accuracy per epoch" (over the runs), "scheme", "burst", "rate",
         "scrub every", "epoch images" and the "physical bits" flipped (summed over runs and epochs) and "logical bits per
-        epoch" that differ after each epoch (summed over the runs)."""
+        epoch" that differ after each epoch (summed over the runs).  An entry of `schemes` may be a (scheme, code) pair (code 1:
+        SEC-DED coded threshold memories): its name is "<scheme name> + SEC-DED", and it also writes "code" and the
+        "corrected words per epoch" and "detected words per epoch" (summed over the runs)."""
         ft = self.fault_test
         folder = "{}/{}/{}/scrubbing/".format(output_folder, ft.network, ft.dataset)
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme in schemes:
+        for scheme, code in map(scheme_and_code, schemes):
             for burst in bursts:
                 for p in rates:
                     for every in scrub_intervals:
-                        per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed)
+                        per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed, code)
                         accuracies = [util.calculate_accuracy(row.tolist(), ft.labels) for row in ft.exposure_results]
-                        name = "{} burst {} upset rate {:g} scrub every {}".format(HARDENING_SCHEMES[scheme], burst, p, every)
+                        name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(scheme, code), burst, p, every)
+                        status = {}
+                        if code:  # [run, epoch, layer, 6] -> the four counters in the uncoded shape, and the decode status
+                            status = {"code": int(code), "corrected words per epoch": [int(x) for x in counts[..., 4].sum(axis=(0, 2))],
+                                      "detected words per epoch": [int(x) for x in counts[..., 5].sum(axis=(0, 2))]}
+                            counts = counts[..., :4].reshape(counts.shape[:3] + (2, 2))
                         raw.append(self._raw(name, num_runs, 0, [], accuracies))
                         extra[name] = {"mean accuracy per epoch": [float(x) for x in np.mean(np.array(per_epoch, float), axis=0)],
                                        "scheme": int(scheme), "burst": int(burst), "rate": float(p), "scrub every": int(every),
                                        "epoch images": int(epoch_images), "physical bits": int(counts[..., 0].sum()),
                                        "logical bits per epoch": [int(x) for x in counts[..., 1].sum(axis=(0, 2, 3))]}
+                        extra[name].update(status)
         stats = self._stats(util.dict_of_dicts_merge(*raw))
         for name, e in extra.items():
             stats["results"][name].update(e)

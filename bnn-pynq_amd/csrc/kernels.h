@@ -239,5 +239,11 @@ hipError_t xmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned
 hipError_t xmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
                         bool signed_bb, const uint16_t *raw, int modules, int interleave, int burst, uint32_t rate_q32, int epoch,
                         unsigned long long *state, unsigned long long *counts, size_t run_stride, hipStream_t s);
+// 16-bit thresholds of a coded layer (SEC-DED: ecc.h), in xmem_noise_t's place: a state word holds the accumulated hit
+// masks of the element's 16 data bits (low 16) and 6 check bits (bits 16 ... 21); interleave 0 or 2.  ecc: this epoch's
+// [layer][2: words with decode status 1, 2] of run 0, run q's ecc_stride longs behind
+hipError_t emem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
+                        bool signed_bb, const uint16_t *raw, int interleave, int burst, uint32_t rate_q32, int epoch, unsigned long long *state,
+                        unsigned long long *counts, size_t run_stride, unsigned long long *ecc, size_t ecc_stride, hipStream_t s);
 
 }  // namespace bnn

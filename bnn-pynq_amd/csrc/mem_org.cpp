@@ -43,46 +43,92 @@ std::string hardening_layout(const NetSpec &net, int scheme, int layer, MemOrg &
   return "";
 }
 
-void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out) {
+std::string ecc_layout(const NetSpec &net, int scheme, int code, int layer, EccOrg &out) {
+  out.check_bits = 0;
+  const std::string e = hardening_layout(net, scheme, layer, out.org);
+  if (!e.empty()) return e;
+  if (code < EC_NONE || code > EC_SECDED) return "code must be 0 (none) or 1 (SEC-DED)";
+  if (code == EC_NONE) return "";
+  if (scheme == HS_TMR) return "code 1 with scheme 1 (TMR): TMR plus a code is not modelled";
+  if (scheme == HS_RESILIENT)
+    return "code 1 with scheme 3 (resilient-interleaved): the resilient patterns are defined for 32 and 48 positions only, not for the 12 of a "
+           "pair of check words";
+  const LayerSpec &L = net.L[layer];
+  if (L.nthr > 0 && !L.thr24) {  // (the 24-bit thresholds of CNV layer 0 are not coded: ecc.h)
+    out.check_bits = kEccCheckBits;
+    out.org.t_modules = 2;
+  }
+  return "";
+}
+
+namespace {
+// the threshold words of one layer with the pairs of lines (ind, ind + 1) of every PE interleaved (forward) or
+// de-interleaved at element width T; an odd last line stays as it is
+void permute_pairs(const LayerSpec &L, int il, int T, bool forward, std::vector<std::vector<uint64_t>> &t) {
+  const int lines = L.fold.tmem;
+  const uint64_t emask = (1ull << T) - 1;
+  for (size_t pe = 0; pe < t.size(); pe++)
+    for (int ind = 0; ind + 1 < lines; ind += 2)
+      for (int i = 0; i < L.nthr; i++) {
+        uint64_t *const at[2] = {&t[pe][(size_t)ind * L.nthr + i], &t[pe][(size_t)(ind + 1) * L.nthr + i]};
+        uint64_t w[2] = {0, 0};
+        for (int half = 0; half < 2; half++)
+          for (int bit = 0; bit < T; bit++) {
+            int oi, ob;
+            if (forward) interleave_site(il, T, lines, ind + half, bit, &oi, &ob);
+            else interleave_source(il, T, lines, ind + half, bit, &oi, &ob);
+            w[oi - ind] |= ((*at[half] >> bit) & 1) << ob;
+          }
+        *at[0] = w[0] & emask;
+        *at[1] = w[1] & emask;
+      }
+}
+}  // namespace
+
+void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code) {
   out.l0 = l0;
   out.l1 = l1;
   for (int l = l0; l < l1; l++) {
     const LayerSpec &L = net.L[l];
-    MemOrg org{1, 1, 0};
-    hardening_layout(net, scheme, l, org);
+    EccOrg eo{MemOrg{1, 1, 0}, 0};
+    ecc_layout(net, scheme, code, l, eo);
+    const MemOrg &org = eo.org;
     for (int m = 0; m < 3; m++) {
       out.mod[m].w[l].clear();
       out.mod[m].t[l].clear();
     }
     for (int m = 0; m < org.w_modules; m++) out.mod[m].w[l] = raw.w[l];
     std::vector<std::vector<uint64_t>> t = raw.t[l];
-    if (org.t_interleave) {
-      const int T = mem_element_bits(L, 1), lines = L.fold.tmem;
-      const uint64_t emask = (1ull << T) - 1;
-      for (size_t pe = 0; pe < t.size(); pe++)
-        for (int ind = 0; ind + 1 < lines; ind += 2)  // (an odd last line stays as the file has it)
-          for (int i = 0; i < L.nthr; i++) {
-            uint64_t w[2] = {0, 0};
-            for (int half = 0; half < 2; half++)
-              for (int bit = 0; bit < T; bit++) {
-                int pi, pb;
-                interleave_site(org.t_interleave, T, lines, ind + half, bit, &pi, &pb);
-                w[pi - ind] |= ((raw.t[l][pe][(size_t)(ind + half) * L.nthr + i] >> bit) & 1) << pb;
-              }
-            t[pe][(size_t)ind * L.nthr + i] = w[0] & emask;
-            t[pe][(size_t)(ind + 1) * L.nthr + i] = w[1] & emask;
-          }
+    if (org.t_interleave) permute_pairs(L, org.t_interleave, mem_element_bits(L, 1), true, t);
+    if (eo.check_bits) {  // data in module 0, the check words of the LOGICAL elements in module 1
+      std::vector<std::vector<uint64_t>> c = raw.t[l];
+      for (auto &pe : c)
+        for (uint64_t &w : pe) w = ecc_encode((uint32_t)w);
+      if (org.t_interleave) permute_pairs(L, org.t_interleave, kEccCheckBits, true, c);
+      out.mod[0].t[l] = t;
+      out.mod[1].t[l] = c;
+      continue;
     }
     for (int m = 0; m < org.t_modules; m++) out.mod[m].t[l] = t;
   }
 }
 
-int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf) {
+int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf, int code) {
   const Fault &f = pf.f;
   if (f.layer < p.l0 || f.layer >= p.l1 || (f.target != 0 && f.target != 1)) return -1;
-  MemOrg org{1, 1, 0};
-  if (!hardening_layout(net, scheme, f.layer, org).empty()) return -1;
-  if (pf.module < 0 || pf.module >= (f.target == 0 ? org.w_modules : org.t_modules)) return -1;
+  EccOrg eo{MemOrg{1, 1, 0}, 0};
+  if (!ecc_layout(net, scheme, code, f.layer, eo).empty()) return -1;
+  if (pf.module < 0 || pf.module >= (f.target == 0 ? eo.org.w_modules : eo.org.t_modules)) return -1;
+  if (f.target == 1 && eo.check_bits && pf.module == 1) {
+    const LayerSpec &L = net.L[f.layer];
+    if (f.word_size < 1 || f.word_size > 64 || f.mem < 0 || f.mem >= L.fold.pe || f.ind < 0 || f.ind >= L.fold.tmem || f.thresh < 0 ||
+        f.thresh >= L.nthr || f.bit < 0 || f.bit >= kEccCheckBits)
+      return -1;
+    const int at = (f.bit / f.word_size) * f.word_size;  // (apply_fault's alignment)
+    const uint64_t flip = ((1ull << event_width(kEccCheckBits, f.word_size, at)) - 1) << at;
+    p.mod[1].t[f.layer][(size_t)f.mem][(size_t)f.ind * L.nthr + f.thresh] ^= flip;
+    return f.ind * L.fold.pe + f.mem;
+  }
   return apply_fault(net, p.mod[pf.module], f);
 }
 
@@ -101,43 +147,46 @@ void vote(const RawParams *mod, bool thresholds, int l, int modules, int ebits, 
 }
 }  // namespace
 
-void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out) {
+void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code, long (*status)[2]) {
   for (int l = p.l0; l < p.l1; l++) {
     const LayerSpec &L = net.L[l];
-    MemOrg org{1, 1, 0};
-    hardening_layout(net, scheme, l, org);
+    EccOrg eo{MemOrg{1, 1, 0}, 0};
+    ecc_layout(net, scheme, code, l, eo);
+    const MemOrg &org = eo.org;
+    if (status) status[l][0] = status[l][1] = 0;
     vote(p.mod, false, l, org.w_modules, mem_element_bits(L, 0), out.w[l]);
     if (L.nthr == 0) {
       out.t[l] = p.mod[0].t[l];
       continue;
     }
     std::vector<std::vector<uint64_t>> v;
-    vote(p.mod, true, l, org.t_modules, mem_element_bits(L, 1), v);
-    out.t[l] = v;
-    if (!org.t_interleave) continue;
-    const int T = mem_element_bits(L, 1), lines = L.fold.tmem;
-    for (size_t pe = 0; pe < v.size(); pe++)
-      for (int ind = 0; ind + 1 < lines; ind += 2)
-        for (int i = 0; i < L.nthr; i++) {
-          uint64_t e[2] = {0, 0};
-          for (int half = 0; half < 2; half++)
-            for (int pb = 0; pb < T; pb++) {
-              int li, lb;
-              interleave_source(org.t_interleave, T, lines, ind + half, pb, &li, &lb);
-              e[li - ind] |= ((v[pe][(size_t)(ind + half) * L.nthr + i] >> pb) & 1) << lb;
-            }
-          out.t[l][pe][(size_t)ind * L.nthr + i] = e[0];
-          out.t[l][pe][(size_t)(ind + 1) * L.nthr + i] = e[1];
+    vote(p.mod, true, l, eo.check_bits ? 1 : org.t_modules, mem_element_bits(L, 1), v);
+    if (org.t_interleave) permute_pairs(L, org.t_interleave, mem_element_bits(L, 1), false, v);
+    if (eo.check_bits) {
+      std::vector<std::vector<uint64_t>> c = p.mod[1].t[l];
+      if (org.t_interleave) permute_pairs(L, org.t_interleave, kEccCheckBits, false, c);
+      for (size_t pe = 0; pe < v.size(); pe++)
+        for (size_t i = 0; i < v[pe].size(); i++) {
+          uint32_t d;
+          const int st = ecc_decode((uint32_t)v[pe][i], (uint32_t)c[pe][i], &d);
+          v[pe][i] = d;
+          if (status && st) status[l][st - 1]++;
         }
+    }
+    out.t[l] = v;
   }
 }
 
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch) {
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch, int code) {
   if (burst < 1 || burst > kMaxBurst || epoch < 0 || epoch >= kMaxEpochs) return -1;
-  MemOrg org{1, 1, 0};
-  if (!hardening_layout(net, scheme, layer, org).empty()) return -1;
-  const long events = enumerate_faults(net, layer, target, burst, 0, nullptr, 0);
+  EccOrg eo{MemOrg{1, 1, 0}, 0};
+  if (!ecc_layout(net, scheme, code, layer, eo).empty()) return -1;
+  const MemOrg &org = eo.org;
+  const bool check = target == 1 && module == 1 && eo.check_bits;  // the check memory: the same shape, 6 bits wide
+  const long per_c = (long)ecc_check_groups(burst);
+  const long events = check ? (long)net.L[layer].fold.pe * net.L[layer].fold.tmem * net.L[layer].nthr * per_c
+                            : enumerate_faults(net, layer, target, burst, 0, nullptr, 0);
   if (events < 0 || module < 0 || module >= (target == 0 ? org.w_modules : org.t_modules)) return -1;
   long total = 0;
   if (rate_q32 == 0) return 0;
@@ -149,7 +198,21 @@ long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t
       if (u[e] >= rate_q32) continue;
       if (out && total >= first && total - first < cap) {
         PhysFault &pf = out[total - first];
-        enumerate_faults(net, layer, target, burst, 4 * b + e, &pf.f, 1);
+        if (check) {
+          const LayerSpec &L = net.L[layer];
+          long el = (4 * b + e) / per_c;
+          pf.f = Fault{};
+          pf.f.bit = (int)((4 * b + e - el * per_c) * burst);
+          pf.f.thresh = (int)(el % L.nthr);
+          el /= L.nthr;
+          pf.f.ind = (int)(el % L.fold.tmem);
+          pf.f.mem = (int)(el / L.fold.tmem);
+          pf.f.layer = layer;
+          pf.f.target = 1;
+          pf.f.word_size = burst;
+        } else {
+          enumerate_faults(net, layer, target, burst, 4 * b + e, &pf.f, 1);
+        }
         pf.module = module;
         pf.f.image = epoch;
       }

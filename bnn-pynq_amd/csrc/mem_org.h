@@ -40,6 +40,7 @@
 
 #include <string>
 
+#include "ecc.h"
 #include "faults.h"
 #include "packed_params.h"
 #include "topology.h"
@@ -128,7 +129,33 @@ BNN_HD inline uint32_t exposure_tag(uint32_t epoch) { return 1u + (epoch << 8); 
 // the last epoch <= t whose upsets met freshly written memories
 inline int exposure_first_epoch(int t, int scrub_every) { return scrub_every > 0 ? t - t % scrub_every : 0; }
 
+// ---- coded threshold memories (bnn_mi355x_ecc_exposure_campaigns): the code of ecc.h on top of a scheme -----------------
+// `code` is 0 (none: everything above, unchanged) or 1 (SEC-DED).  Code 1 covers the 16-bit threshold memory of every
+// layer that has one -- the memories the interleaved schemes cover; weights and the 24-bit thresholds of CNV layer 0 are
+// not coded (ecc.h says why), and layer 0 keeps the uncoded host route.
+// Storage: the 6 check bits of a threshold element live in a CHECK MEMORY of their own, of the same (PE, line,
+// threshold) shape, addressed as module 1 of target 1 (the supported schemes give threshold memories one module).
+// Scheme 0 stores element and check word as they are.  Scheme 2 encodes the LOGICAL element, then interleaves the data
+// of lines ind, ind + 1 as above and their check words by the same construction at width 6 (interleave_site(2, 6, ...):
+// pattern 0x555, line ind holds positions 6 ... 11, line ind + 1 positions 0 ... 5); an odd last line is stored as is.
+// The logical parameters are decode(de-interleave(data), de-interleave(check)).
+// Supported: code 1 with scheme 0 (every network) and with scheme 2 (where scheme 2 is supported).  Refused: code 1 with
+// scheme 1 (TMR plus a code is not modelled) or 3 (the resilient patterns are defined for 32 and 48 positions only).
+// Upsets: the data memories draw as above (module 0); the check memory draws by the same construction at element width
+// 6 with module 1 in the counter word: per_c = ceil(6 / b) groups per element, e = element * per_c + g, an event a pure
+// XOR of bits [g * b, min(g * b + b, 6)) of the check word, at the layer's threshold rate.  Bursts do not cross from
+// the data memory into the check memory.  Order inside an epoch: module-major, data then check.
+// Counts per (run, epoch, layer), six: the four above (thresholds: physical = data plus check bits flipped, logical = data
+// bits that differ after decoding), then the threshold words whose decode status after the epoch is 1, and 2.
+// The storage in a check memory of its own, the draw, and the absence of a repair scrub are the project's own choices.
+BNN_HD inline uint32_t ecc_check_groups(int burst) { return (uint32_t)((kEccCheckBits + burst - 1) / burst); }
+
 // ---- host only from here ---------------------------------------------------------------------------------------------
+
+// hardening_layout plus the code: "" and the organisation, else why (network, scheme, code, layer) is refused.
+// check_bits: 6 where the layer's threshold memory is coded (then t_modules counts the check memory: 2), else 0
+struct EccOrg { MemOrg org; int check_bits; };
+std::string ecc_layout(const NetSpec &net, int scheme, int code, int layer, EccOrg &out);
 
 struct PhysFault { Fault f; int module; };
 
@@ -138,13 +165,17 @@ struct PhysParams {
   int l0 = 0, l1 = 0;
   RawParams mod[3];
 };
-// what the loader stores from the parameter files
-void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out);
-// one physical fault; returns apply_fault's result, -1 also for a module the memory does not have
-int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf);
+// what the loader stores from the parameter files.  code 1: the check memory of a coded layer in mod[1].t[l], filled
+// from the logical elements
+void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code = 0);
+// one physical fault; returns apply_fault's result, -1 also for a module the memory does not have.  A record of a check
+// memory (code 1, target 1, module 1) XORs bits [bit, min(bit + word_size, 6)) of the check word, bit aligned as there
+int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf, int code = 0);
 // de-interleave(vote(modules)) into out.w[l], out.t[l] for l in [l0, l1).  A memory with one module and no interleave
-// is copied word for word; a voted or de-interleaved word holds its element's bits alone.
-void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out);
+// is copied word for word; a voted or de-interleaved word holds its element's bits alone.  code 1: a coded layer's
+// words end with the decode (they hold the 16 delivered bits alone); status, where given, counts per layer the words
+// decoded with status 1 ([l][0]) and 2 ([l][1])
+void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code = 0, long (*status)[2] = nullptr);
 
 // element width in bits of a layer's weight (target 0) or threshold (target 1) memory; 0: no threshold memory
 int mem_element_bits(const LayerSpec &L, int target);
@@ -154,8 +185,8 @@ inline int event_width(int ebits, int burst, int bit) { return ebits - bit < bur
 // the events of one (run seed, layer, target, module) in event order as physical faults (image 0, word_size burst);
 // returns their number (0: thresholds of a layer without any), -1 for a bad scheme, burst, layer, target or module;
 // writes events first .. first + cap - 1 to out (which may be null).  epoch: the exposure campaigns' (above); the
-// records' image field holds it
+// records' image field holds it.  code 1: module 1 of a coded layer's thresholds lists the check memory's events
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch = 0);
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch = 0, int code = 0);
 
 }  // namespace bnn

@@ -290,6 +290,10 @@ struct Runtime {
   // [run][epoch][layer][2][2: physical bits of the epoch, logical bits after it] and the seeds
   std::vector<long> xmem_counts;
   std::vector<unsigned long long> xmem_seeds;
+  // bnn_mi355x_ecc_exposure_campaigns (the same buffers): [run][epoch][layer][6: the four above, then the threshold words
+  // decoded with status 1 and with status 2 after the epoch] and the seeds
+  std::vector<long> emem_counts;
+  std::vector<unsigned long long> emem_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -3193,7 +3197,8 @@ long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigne
 // the argument checks of both entry points, then what every parameter-fault entry point refuses; nothing touches a device
 // before they have passed (ready() is the first thing that may)
 // hz: the hardened entry points (mem_org.h) -- the scheme is an argument there, so they are the same in a variant's library
-struct Hardening { int scheme, burst; };
+// code: the SEC-DED axis of bnn_mi355x_ecc_exposure_campaigns (ecc.h); 0 everywhere else
+struct Hardening { int scheme, burst, code = 0; };
 
 static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
                            const Hardening *hz = nullptr) {
@@ -3201,8 +3206,8 @@ static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, cons
   const NetSpec &net = r.spec;
   if (hz) {
     if (hz->burst < 1 || hz->burst > kMaxBurst) return fail(std::string(who) + ": burst must be 1 ... " + std::to_string(kMaxBurst));
-    MemOrg org;
-    const std::string e = hardening_layout(net, hz->scheme, 0, org);
+    EccOrg org;
+    const std::string e = ecc_layout(net, hz->scheme, hz->code, 0, org);
     if (!e.empty()) return fail(std::string(who) + ": " + e);
   }
   if (!rate_w_q32 || !rate_t_q32 || n_rates != net.nlayers)
@@ -3449,7 +3454,9 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
 
 // ---- exposure campaigns: upsets that accumulate over epochs, with scrubbing (the model: mem_org.h) -------------------------
 
-struct Exposure { int epoch_images, scrub_every; };
+// longs: the counters per (run, epoch, layer) the caller is handed -- 4, or 6 on the coded route (the ecc entry points, with
+// code 0 as well), whose last_* state is its own
+struct Exposure { int epoch_images, scrub_every, longs = 4; };
 
 static bool exposure_scrubs(const Exposure &ex, int t) { return t > 0 && ex.scrub_every > 0 && t % ex.scrub_every == 0; }
 
@@ -3540,10 +3547,11 @@ static int exposure_prepare(const std::vector<unsigned long long> &seeds, const 
 
 // Enqueues on r.stream what comes before epoch 0: the seeds, the zeroed [run][epoch][layer][2][2] counters at counts_off of
 // d_noise, the runs' copies of the loaded blob, the job's upload and the zeroed threshold state.
-static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, int E) {
+// longs 6: the [run][epoch][layer][2] decode-status counters of k_emem_noise_t lie behind the others.
+static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, int E, int longs = 4) {
   Runtime &r = rt();
   const int R = (int)seeds.size(), S = r.spec.nlayers;
-  const size_t counts_bytes = (size_t)R * E * S * 4 * 8;
+  const size_t counts_bytes = (size_t)R * E * S * (size_t)longs * 8;
   if (grow(r.d_copies, r.copies_cap, (size_t)R * job.stride) || grow(r.d_camp, r.camp_cap, job.state_begin + job.state_bytes + 256) ||
       grow(r.d_noise, r.noise_cap, counts_off + counts_bytes))
     return -1;
@@ -3578,13 +3586,20 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
     const LayerSpec &L = net.L[l];
     if (L.arith == AR_INT8) continue;  // (the host's part)
     const MemNoiseLayer ml{h.layer[l].offset, h.layer[l].row_dwords, h.layer[l].rows, h.layer[l].kw, (uint32_t)L.fold.pe, (uint32_t)L.fold.tmem, (uint32_t)l};
-    MemOrg org{1, 1, 0};
-    hardening_layout(net, hz.scheme, l, org);  // (checked by mem_noise_check; weights of a layer >= 1 have one module)
+    EccOrg eo{MemOrg{1, 1, 0}, 0};
+    ecc_layout(net, hz.scheme, hz.code, l, eo);  // (checked by mem_noise_check; weights of a layer >= 1 have one module)
+    const MemOrg &org = eo.org;
     e = xmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
                      static_cast<const uint8_t *>(r.d_blob), d_counts, run_stride, r.stream);
     // a flip may have removed the last -2 of a row (the loaded parameters may hold -2 rows, and so may an earlier epoch's state)
     if (e == hipSuccess && L.arith == AR_TT && rw[l] && (r.two_rows > 0 || t > 0)) e = mem_noise_flags(r.d_copies, stride, R, ml, r.stream);
-    if (e == hipSuccess && rth[l])
+    if (e == hipSuccess && rth[l] && eo.check_bits) {
+      // a coded layer (code 1 comes by the 6-long route alone): the decode-status counters behind the [run][epoch][layer][4]
+      unsigned long long *const d_ecc = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * run_stride + (size_t)t * S * 2;
+      e = emem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
+                       org.t_interleave, hz.burst, rth[l], t, reinterpret_cast<unsigned long long *>(r.d_camp + job.state_off[l]), d_counts,
+                       run_stride, d_ecc, (size_t)E * S * 2, r.stream);
+    } else if (e == hipSuccess && rth[l])
       e = xmem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
                        org.t_modules, org.t_interleave, hz.burst, rth[l], t, reinterpret_cast<unsigned long long *>(r.d_camp + job.state_off[l]),
                        d_counts, run_stride, r.stream);
@@ -3605,8 +3620,9 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
                                      float *usecPerImage, const Exposure *ex = nullptr) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  std::vector<long> &last_counts = ex ? r.xmem_counts : (hz ? r.hmem_noise_counts : r.mem_noise_counts);
-  std::vector<unsigned long long> &last_seeds = ex ? r.xmem_seeds : (hz ? r.hmem_noise_seeds : r.mem_noise_seeds);
+  const bool six = ex && ex->longs == 6;  // the coded route: two decode-status counters behind the four
+  std::vector<long> &last_counts = six ? r.emem_counts : ex ? r.xmem_counts : (hz ? r.hmem_noise_counts : r.mem_noise_counts);
+  std::vector<unsigned long long> &last_seeds = six ? r.emem_seeds : ex ? r.xmem_seeds : (hz ? r.hmem_noise_seeds : r.mem_noise_seeds);
   last_counts.clear();
   last_seeds.clear();
   const int S = net.nlayers;
@@ -3635,9 +3651,9 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
   const bool cnv = net.is_cnv;
   const int ei = ex ? ex->epoch_images : std::max(n, 1);  // images per epoch; without ex the call is one epoch
   const long long epochs = ((long long)n + ei - 1) / ei;
-  if (ex && (epochs > kMaxEpochs || (unsigned long long)R * (unsigned long long)epochs * S * 4 > 0x7FFFFFFFull)) {
+  if (ex && (epochs > kMaxEpochs || (unsigned long long)R * (unsigned long long)epochs * S * (unsigned)ex->longs > 0x7FFFFFFFull)) {
     fail(std::string(who) + ": " + std::to_string(epochs) + " epochs: at most " + std::to_string(kMaxEpochs) +
-         ", and num_runs * epochs * layers * 4 counters must stay below 2^31");
+         ", and num_runs * epochs * layers * " + std::to_string(ex->longs) + " counters must stay below 2^31");
     return nullptr;
   }
   const int E = (int)epochs;
@@ -3658,6 +3674,7 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
   int *result = new (std::nothrow) int[total + 1];
   if (!result) { fail("out of memory"); return nullptr; }
   std::vector<unsigned long long> counts((size_t)R * (ex ? E : 1) * S * (hz ? 4 : 2), 0);
+  std::vector<unsigned long long> status(six ? (size_t)R * E * S * 2 : 0, 0);  // (the coded route: [run][epoch][layer][2])
   MemNoiseJob job;
   double device_us = 0.0;
   auto run = [&]() -> int {
@@ -3709,7 +3726,7 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     }
     // -- all of it on one stream, one wait at the end
     HIP_OK(hipEventRecord(r.time_events[0], r.stream));
-    if (any && (ex ? exposure_begin(seeds, job, counts_off, E) : mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off, hz))) return -1;
+    if (any && (ex ? exposure_begin(seeds, job, counts_off, E, ex->longs) : mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off, hz))) return -1;
     // (all rates 0: no copy is made, every run reads the loaded blob)
     const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
     const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
@@ -3737,6 +3754,7 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     }
     HIP_OK(hipEventRecord(r.time_events[1], r.stream));
     if (any) HIP_OK(hipMemcpyAsync(counts.data(), r.d_noise + counts_off, counts.size() * 8, hipMemcpyDeviceToHost, r.stream));
+    if (any && six) HIP_OK(hipMemcpyAsync(status.data(), r.d_noise + counts_off + counts.size() * 8, status.size() * 8, hipMemcpyDeviceToHost, r.stream));
     if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
     else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
     HIP_OK(hipStreamSynchronize(r.stream));
@@ -3752,7 +3770,15 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     delete[] result;
     return nullptr;
   }
-  last_counts.assign(counts.begin(), counts.end());
+  if (six) {  // [run][epoch][layer]: the four counters, then the two decode-status counters
+    last_counts.resize(counts.size() / 4 * 6);
+    for (size_t b = 0; b < counts.size() / 4; b++) {
+      for (int j = 0; j < 4; j++) last_counts[b * 6 + j] = (long)counts[b * 4 + j];
+      for (int j = 0; j < 2; j++) last_counts[b * 6 + 4 + j] = (long)status[b * 2 + j];
+    }
+  } else {
+    last_counts.assign(counts.begin(), counts.end());
+  }
   last_seeds = std::move(seeds);
   if (image_number) *image_number = n;
   if (usecPerImage) *usecPerImage = total ? (float)(device_us / (double)total) : 0.f;
@@ -3957,18 +3983,17 @@ int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int schem
 }
 
 // One copy stepped through epochs 0 ... epoch by the campaign's own steps (exposure_begin, exposure_epoch), then read back.
-size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
-                                  const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
+static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                   const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
   Runtime &r = rt();
-  const Hardening hz{scheme, burst};
-  const Exposure ex{1, scrub_every};
+  const Exposure ex{1, scrub_every, 6};  // (room for the decode-status counters of a coded layer; nothing reads them here)
   if (epoch < 0 || epoch >= kMaxEpochs || scrub_every < 0) {
-    fail("exposure_params: epoch must be 0 ... " + std::to_string(kMaxEpochs - 1) + " and scrub_every must not be negative (0: never scrub)");
+    fail(std::string(who) + ": epoch must be 0 ... " + std::to_string(kMaxEpochs - 1) + " and scrub_every must not be negative (0: never scrub)");
     return 0;
   }
-  if (mem_noise_check("exposure_params", rate_w_q32, rate_t_q32, n_rates, &hz)) return 0;
+  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, &hz)) return 0;
   if (!dst) return r.blob.size();
-  if (cap < r.blob.size()) { fail("exposure_params: destination too small"); return 0; }
+  if (cap < r.blob.size()) { fail(std::string(who) + ": destination too small"); return 0; }
   const std::vector<unsigned long long> seeds(1, run_seed);
   const int E = epoch + 1;
   MemNoiseJob job;
@@ -3976,7 +4001,7 @@ size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_
     if (exposure_prepare(seeds, rate_w_q32, rate_t_q32, E, ex, hz, job)) return -1;
     DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
     if (settle_handover(r.stream)) return -1;
-    if (exposure_begin(seeds, job, 256, E)) return -1;
+    if (exposure_begin(seeds, job, 256, E, ex.longs)) return -1;
     for (int t = 0; t < E; t++)
       if (exposure_epoch(t, 1, rate_w_q32, rate_t_q32, job, 256, E, ex, hz)) return -1;
     HIP_OK(hipMemcpyAsync(dst, r.d_copies, r.blob.size(), hipMemcpyDeviceToHost, r.stream));
@@ -3987,6 +4012,11 @@ size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_
   return run() < 0 ? 0 : r.blob.size();
 }
 
+size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                  const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
+  return exposure_params_impl("exposure_params", Hardening{scheme, burst}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch, scrub_every, dst, cap);
+}
+
 int bnn_mi355x_last_exposure_counts(long *counts, int cap) {
   const std::vector<long> &c = rt().xmem_counts;
   for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
@@ -3995,6 +4025,115 @@ int bnn_mi355x_last_exposure_counts(long *counts, int cap) {
 
 int bnn_mi355x_last_exposure_seeds(unsigned long long *seeds, int cap) {
   const std::vector<unsigned long long> &k = rt().xmem_seeds;
+  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
+  return (int)k.size();
+}
+
+// ---- coded threshold memories in the exposure campaigns (the code: ecc.h; storage and upsets: mem_org.h) -----------------
+
+unsigned int bnn_mi355x_ecc_encode(unsigned int data) { return ecc_encode(data); }
+
+int bnn_mi355x_ecc_decode(unsigned int data, unsigned int check, unsigned int *out_data) {
+  uint32_t d;
+  const int status = ecc_decode(data, check, &d);
+  if (out_data) *out_data = d;
+  return status;
+}
+
+int bnn_mi355x_ecc_layout(int scheme, int code, int layer, int out[4]) {
+  EccOrg eo;
+  const std::string e = ecc_layout(rt().spec, scheme, code, layer, eo);
+  if (!e.empty()) return fail("ecc_layout: " + e);
+  if (out) { out[0] = eo.org.w_modules; out[1] = eo.org.t_modules; out[2] = eo.org.t_interleave; out[3] = eo.check_bits; }
+  return 0;
+}
+
+int bnn_mi355x_ecc_check_site(int scheme, int code, int layer, int ind, int bit, int *p_ind, int *p_bit) {
+  const NetSpec &net = rt().spec;
+  EccOrg eo;
+  const std::string e = ecc_layout(net, scheme, code, layer, eo);
+  if (!e.empty()) return fail("ecc_check_site: " + e);
+  if (!eo.check_bits) return fail("ecc_check_site: layer " + std::to_string(layer) + " has no check memory (code 0, no thresholds, or 24-bit ones)");
+  const LayerSpec &L = net.L[layer];
+  if (ind < 0 || ind >= L.fold.tmem || bit < 0 || bit >= eo.check_bits) return fail("ecc_check_site: ind or bit outside the check memory");
+  int pi, pb;
+  interleave_site(eo.org.t_interleave, eo.check_bits, L.fold.tmem, ind, bit, &pi, &pb);
+  if (p_ind) *p_ind = pi;
+  if (p_bit) *p_bit = pb;
+  return 0;
+}
+
+long bnn_mi355x_ecc_exposure_mask(int scheme, int code, int burst, unsigned long long run_seed, int epoch, int layer, int target, int module,
+                                  unsigned int rate_q32, long first, int *records, int cap_records) {
+  const NetSpec &net = rt().spec;
+  EccOrg eo;
+  const std::string e = ecc_layout(net, scheme, code, layer, eo);
+  if (!e.empty()) return fail("ecc_exposure_mask: " + e);
+  const long total =
+      first < 0 ? -1 : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0, epoch, code);
+  if (total < 0)
+    return fail("ecc_exposure_mask: bad burst (1 ... " + std::to_string(kMaxBurst) + "), epoch (0 ... " + std::to_string(kMaxEpochs - 1) +
+                "), target (0 weights, 1 thresholds), module (of those the memory has) or first");
+  if (records && cap_records > 0 && first < total) {
+    std::vector<PhysFault> v((size_t)std::min<long>(cap_records, total - first));
+    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size(), epoch, code);
+    for (size_t i = 0; i < v.size(); i++) {
+      const Fault &f = v[i].f;
+      const int w[9] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size, v[i].module};
+      std::memcpy(records + i * 9, w, sizeof w);
+    }
+  }
+  return total;
+}
+
+size_t bnn_mi355x_pack_params_ecc(const char *path, int scheme, int code, const int *records, int n_faults, void *dst, size_t cap) {
+  const NetSpec &net = rt().spec;
+  EccOrg eo;
+  const std::string le = ecc_layout(net, scheme, code, 0, eo);
+  if (!le.empty()) { fail("pack_params_ecc: " + le); return 0; }
+  RawParams raw;
+  const std::string e = read_raw_params(net, path ? path : "", raw);
+  if (!e.empty()) { fail(e); return 0; }
+  PhysParams phys;
+  phys_load(net, scheme, raw, 0, net.nlayers, phys, code);
+  for (int i = 0; i < n_faults; i++) {
+    const int *v = records + i * 9;
+    const PhysFault pf{Fault{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}, v[8]};
+    if (phys_apply(net, scheme, phys, pf, code) < 0) { fail("pack_params_ecc: fault record out of range (or a module the memory does not have)"); return 0; }
+  }
+  phys_logical(net, scheme, phys, raw, code);
+  std::vector<uint8_t> blob;
+  pack_blob(net, raw, blob);
+  if (dst) {
+    if (cap < blob.size()) { fail("pack_params_ecc: destination too small"); return 0; }
+    std::memcpy(dst, blob.data(), blob.size());
+  }
+  return blob.size();
+}
+
+int *bnn_mi355x_ecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst, int num_runs, unsigned long long seed,
+                                       const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch_images,
+                                       int scrub_every, int *image_number, float *usecPerImage) {
+  const Hardening hz{scheme, burst, code};
+  const Exposure ex{epoch_images, scrub_every, 6};
+  return mem_noise_campaigns_impl("ecc_exposure_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number,
+                                  usecPerImage, &ex);
+}
+
+size_t bnn_mi355x_ecc_exposure_params(int scheme, int code, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                      const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
+  return exposure_params_impl("ecc_exposure_params", Hardening{scheme, burst, code}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch, scrub_every,
+                              dst, cap);
+}
+
+int bnn_mi355x_last_ecc_exposure_counts(long *counts, int cap) {
+  const std::vector<long> &c = rt().emem_counts;
+  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
+  return (int)c.size();
+}
+
+int bnn_mi355x_last_ecc_exposure_seeds(unsigned long long *seeds, int cap) {
+  const std::vector<unsigned long long> &k = rt().emem_seeds;
   for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
   return (int)k.size();
 }

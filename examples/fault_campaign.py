@@ -79,6 +79,7 @@ for scheme in (0, 1):
         e = stats["results"]["%s burst 1 upset rate %g scrub every %d" % (bnn.faults.HARDENING_SCHEMES[scheme], 2.0 ** -10, every)]
         print("%-6s scrub every %d: mean accuracy per epoch %s" % (bnn.faults.HARDENING_SCHEMES[scheme], every,
                                                                   np.round(e["mean accuracy per epoch"], 2).tolist()))
+net.scrubbing_curve(os.path.join(out, "ecc"), 10, [2.0 ** -10], [0, 1], [(0, 1), (2, 1)], 250, bursts=(1, 2), seed=1)  # (scheme, code): SEC-DED coded thresholds
 
 # the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
 net.input_upset_rate_curve(out, 10, rates, seed=1)

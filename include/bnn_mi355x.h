@@ -512,6 +512,74 @@ size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_
 int bnn_mi355x_last_exposure_counts(long *counts, int cap);
 int bnn_mi355x_last_exposure_seeds(unsigned long long *seeds, int cap);
 
+/* Coded threshold memories in the exposure campaigns: a single-error-correcting, double-error-detecting code as an axis
+ * orthogonal to the scheme.  The code is the PROJECT'S OWN MODEL (the fork has none; parity unpinned, like the voter and
+ * the activation faults): Hamming(21,16) plus an overall parity bit, which is what block RAM ECC is.
+ * code: 0 none (every function below is then the exposure function of the same name), 1 SEC-DED.
+ * The code: a coded element is a 16-bit threshold word with 6 check bits.  Code word positions are 1 ... 21; positions 1,
+ * 2, 4, 8, 16 hold check bits c0 ... c4, the other positions in increasing order (3, 5, 6, 7, 9 ... 15, 17 ... 21) data
+ * bits 0 ... 15.  c_j = the XOR of the data bits whose position has bit j set; c5 = the XOR of all 16 data bits and
+ * c0 ... c4.  encode(0x0001) = 0x23, encode(0x8000) = 0x15, encode(0xFFFF) = 0x1E, encode(0x1234) = 0x19.
+ * Decode (stored data d, stored check c): s = (encode(d) ^ c) & 31, P = parity(d) ^ parity(c).  s = 0 and P = 0: status
+ * 0, data d.  P = 1 and s = 0 or a power of two: status 1 (corrected: a check bit was hit), data d.  P = 1 and s a data
+ * position: status 1, d with that data bit flipped.  P = 1 and s = 22 ... 31, or P = 0 and s != 0: status 2 (detected,
+ * uncorrectable), data d as stored.  Every single error of the 22 bits is restored, none of the 231 doubles is
+ * miscorrected, of the 1 540 triples 1 052 are accepted as a correction (the data then wrong) and 488 detected.
+ * Which memories: code 1 covers the 16-bit threshold memory of every layer that has one.  TWO LIMITS: weights are not
+ * coded (their memory words are SIMD * wbits = 1 ... 32 bits wide: no per-word code makes sense over them; the
+ * interleaved schemes leave them alone as well), and the 24-bit threshold memory of CNV layer 0 is not coded (a fault
+ * there passes through the reference's integer-part read-back, which rewrites the whole word: no code word survives
+ * that).  Layer 0 keeps the uncoded host route; a study that wants it out of the picture sets its rates to 0.
+ * Storage: the check bits of an element live in a check memory of their own, of the same (PE, line, threshold) shape, 6
+ * bits wide, addressed as MODULE 1 of target 1.  Scheme 0 stores element and check word as they are.  Scheme 2 encodes
+ * the logical element, interleaves the data of lines ind, ind + 1 as without a code, and their check words by the same
+ * construction at width 6 (pattern 0x555: line ind holds positions 6 ... 11, line ind + 1 positions 0 ... 5); an odd last
+ * line is stored as is.  The logical parameters are decode(de-interleave(data), de-interleave(check)).
+ * Pairs: code 1 with scheme 0 (every network) and with scheme 2 (cnvW1A1, cnvW1A2).  Refused with the reason: code 1
+ * with scheme 1 (TMR plus a code is not modelled) or 3 (the resilient patterns are defined for 32 and 48 positions
+ * only), everything the scheme alone refuses, code outside 0 ... 1.
+ * Upsets: the data memories draw as in the exposure campaigns (module 0).  The check memory draws by the same
+ * construction at element width 6: per_c = ceil(6 / b) groups per element, the last one clipped to 6, e = element *
+ * per_c + g,
+ *     u = philox4x32_10(counter {L, 1 | 1 << 1 | (b - 1) << 8, e >> 2, 1 + (t << 8)}, key {seed})[e & 3],
+ * an event iff u < rate_t_q32[L].  A check event is the 9-int physical record with target 1, module 1, bit = g * b and
+ * word_size b: a pure XOR of bits [bit, min(bit + b, 6)) of the check word.  Bursts do not cross from the data memory
+ * into the check memory.  Order inside an epoch: layer-major, weights then thresholds, module-major (data, then check),
+ * in event order.  Epochs, the scrub (a full rewrite, of data and check words) and the epoch cap are exposure_campaigns'
+ * own; a REPAIR scrub that writes the decoder's output back is not modelled.
+ * ecc_encode / ecc_decode: host only; the 6 check bits / the status, the delivered data in *out_data.
+ * ecc_layout: out = {weight modules, threshold modules (2 where coded: data plus check), interleave, check bits 0 / 6};
+ * -1 + last_error for a refused pair.
+ * ecc_check_site: logical -> physical for bit `bit` (0 ... 5) of the check word of line `ind` (hardened_site answers for
+ * data bits); -1 for a layer without a check memory.
+ * ecc_exposure_mask: exposure_mask with the code; code 1: module 1 of a coded layer's thresholds lists the check events.
+ * pack_params_ecc: load the physical state, apply the 9-int records in order, de-interleave, decode, pack.  Code 0:
+ * pack_params_hardened.
+ * ecc_exposure_campaigns: exposure_campaigns' conventions and refusals plus those above.  Code 0: its classes, counts
+ * (in the first four longs) and seeds bit for bit.  All rates 0: the fault-free classes, no upset kernel launched.  The
+ * last_* state is this entry point's own; num_runs * E * layers * 6 must stay below 2^31.
+ * ecc_exposure_params: the blob a run classifies epoch `epoch` with, made by the campaign's own kernels and read back.
+ * last_ecc_exposure_counts: per [run][epoch][layer] six longs: weights physical, logical; thresholds physical (data plus
+ * check bits flipped in the epoch), logical (data bits that differ after decoding); the threshold words whose decode
+ * status after the epoch is 1; those whose status is 2 (both 0 for an uncoded layer).  Returns runs * E * layers * 6. */
+unsigned int bnn_mi355x_ecc_encode(unsigned int data);
+int bnn_mi355x_ecc_decode(unsigned int data, unsigned int check, unsigned int *out_data);
+int bnn_mi355x_ecc_layout(int scheme, int code, int layer, int out[4]);
+int bnn_mi355x_ecc_check_site(int scheme, int code, int layer, int ind, int bit, int *p_ind, int *p_bit);
+long bnn_mi355x_ecc_exposure_mask(int scheme, int code, int burst, unsigned long long run_seed, int epoch, int layer,
+                                  int target, int module, unsigned int rate_q32, long first, int *records, int cap_records);
+size_t bnn_mi355x_pack_params_ecc(const char *path, int scheme, int code, const int *records, int n_faults, void *dst,
+                                  size_t cap);
+int *bnn_mi355x_ecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst, int num_runs,
+                                       unsigned long long seed, const unsigned int *rate_w_q32,
+                                       const unsigned int *rate_t_q32, int n_rates, int epoch_images, int scrub_every,
+                                       int *image_number, float *usecPerImage);
+size_t bnn_mi355x_ecc_exposure_params(int scheme, int code, int burst, unsigned long long run_seed,
+                                      const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch,
+                                      int scrub_every, void *dst, size_t cap);
+int bnn_mi355x_last_ecc_exposure_counts(long *counts, int cap);
+int bnn_mi355x_last_ecc_exposure_seeds(unsigned long long *seeds, int cap);
+
 /* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
  * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column
  * l = the output of layer l, l = 0 ... 7 (layers 1 and 3: after the max-pool); LFC column l = the output of layer l,

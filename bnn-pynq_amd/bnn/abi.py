@@ -35,7 +35,9 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_exposure_params", "bnn_mi355x_last_exposure_counts", "bnn_mi355x_last_exposure_seeds", "bnn_mi355x_ecc_encode",
        "bnn_mi355x_ecc_decode", "bnn_mi355x_ecc_layout", "bnn_mi355x_ecc_check_site", "bnn_mi355x_ecc_exposure_mask",
        "bnn_mi355x_pack_params_ecc", "bnn_mi355x_ecc_exposure_campaigns", "bnn_mi355x_ecc_exposure_params",
-       "bnn_mi355x_last_ecc_exposure_counts", "bnn_mi355x_last_ecc_exposure_seeds"]
+       "bnn_mi355x_last_ecc_exposure_counts", "bnn_mi355x_last_ecc_exposure_seeds", "bnn_mi355x_ecc_repair",
+       "bnn_mi355x_pack_params_repair", "bnn_mi355x_repair_exposure_campaigns", "bnn_mi355x_repair_exposure_params",
+       "bnn_mi355x_last_repair_exposure_counts", "bnn_mi355x_last_repair_exposure_seeds"]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -184,6 +186,19 @@ def declare_extensions(L):
         L.bnn_mi355x_ecc_exposure_params.restype = C.c_size_t
         L.bnn_mi355x_last_ecc_exposure_counts.argtypes = [C.POINTER(C.c_long), C.c_int]
         L.bnn_mi355x_last_ecc_exposure_seeds.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+    if hasattr(L, "bnn_mi355x_repair_exposure_campaigns"):  # (likewise)
+        up = C.POINTER(C.c_uint)
+        L.bnn_mi355x_ecc_repair.argtypes = [C.c_uint, C.c_uint, up, up]
+        L.bnn_mi355x_pack_params_repair.argtypes = [C.c_char_p, C.c_int, C.c_int, ip, C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_pack_params_repair.restype = C.c_size_t
+        L.bnn_mi355x_repair_exposure_campaigns.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, up, up,
+                                                           C.c_int, C.c_int, C.c_int, C.c_int, ip, fp]
+        L.bnn_mi355x_repair_exposure_campaigns.restype = ip
+        L.bnn_mi355x_repair_exposure_params.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ulonglong, up, up, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_repair_exposure_params.restype = C.c_size_t
+        L.bnn_mi355x_last_repair_exposure_counts.argtypes = [C.POINTER(C.c_long), C.c_int]
+        L.bnn_mi355x_last_repair_exposure_seeds.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     L.bnn_mi355x_pack_params_faulty.argtypes = [C.c_char_p, ip, C.c_int, C.c_void_p, C.c_size_t]
     L.bnn_mi355x_pack_params_faulty.restype = C.c_size_t
     L.bnn_mi355x_debug_stage_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]

@@ -414,13 +414,18 @@ class PynqBNN:
         return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2, 2)
 
     # extension: exposure campaigns (upsets that accumulate over epochs of images, with scrubbing)
-    def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0, code=0):
+    def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0, code=0,
+                                    repair_every=0):
         """inference_multiple_hardened_mem_noise spread over time: the run is cut into epochs of `epoch_images` images, the
         rates are per epoch, an epoch's upsets XOR onto the physical state the earlier ones left, and before every epoch
         t > 0 with t % scrub_every == 0 (0: never) all memories are rewritten from the loaded parameters.  -> (classes
         int32 (num_runs, n), counts int64 (num_runs, epochs, layers, 2: weights, thresholds, 2: physical bits flipped in
         the epoch, logical bits that differ from the loaded parameters after it)).  The seeds are left in
-        self.mem_noise_seeds.  code 1 (SEC-DED coded 16-bit threshold memories): inference_multiple_ecc_exposure."""
+        self.mem_noise_seeds.  code 1 (SEC-DED coded 16-bit threshold memories): inference_multiple_ecc_exposure;
+        repair_every > 0 (repair scrubs): inference_multiple_repair_exposure."""
+        if repair_every:
+            return self.inference_multiple_repair_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, repair_every, scheme, code,
+                                                           burst, seed)
         if code:
             return self.inference_multiple_ecc_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme, code, burst, seed)
         lib = self.interface
@@ -472,6 +477,38 @@ class PynqBNN:
         self.usecPerImage = usec.value
         epochs = -(-size.value // epoch_images)
         return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 6)
+
+    # extension: repair scrubs in the exposure campaigns
+    def inference_multiple_repair_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, repair_every=1, scheme=0, code=0,
+                                           burst=1, seed=0):
+        """inference_multiple_ecc_exposure with the scrub a TMR or coded memory really has: before every epoch t > 0 with
+        t % repair_every == 0 (0: never) that is no rewrite epoch (t % scrub_every == 0), every memory with redundancy is
+        read, voted (TMR: the bitwise majority written to all three modules) or decoded (SEC-DED: a status-1 word written
+        back with fresh check bits) and written back.  Memories without redundancy keep accumulating upsets, and what the
+        redundancy gets wrong (a bit hit in two modules, an accepted triple error) is locked in.  -> (classes int32
+        (num_runs, n), counts int64 (num_runs, epochs, layers, 8: the six of inference_multiple_ecc_exposure, the words
+        the epoch's repair rewrote, the words of the repaired memories still unlike the loaded ones after it)).  The seeds
+        are left in self.mem_noise_seeds."""
+        lib = self.interface
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_repair_exposure_campaigns(path.encode(), len(self.classes), scheme, code, burst, num_runs, seed,
+                                                       qw.ctypes.data_as(up), qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every,
+                                                       repair_every, ctypes.byref(size), ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("repair exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_repair_exposure_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_repair_exposure_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_repair_exposure_seeds(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        epochs = -(-size.value // epoch_images)
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 8)
 
     # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
     def enumerate_input_faults(self):

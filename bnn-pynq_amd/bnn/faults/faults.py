@@ -275,7 +275,7 @@ class FaultTest:
         print()
         return accuracies, counts
 
-    def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0, code=0):
+    def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0, code=0, repair_every=0):
         """Upsets that accumulate while the run goes on: the images are cut into epochs of `epoch_images`, rates_w[L] /
         rates_t[L] are the probability of an event PER EPOCH (scalars: every layer), an epoch's upsets XOR onto the physical
         state of the hardened organisation `scheme` (None: 0) the earlier epochs left, and every `scrub_every` epochs (0:
@@ -284,13 +284,18 @@ class FaultTest:
         code 1: the 16-bit threshold memories carry a SEC-DED code (csrc/ecc.h; scheme 0 or 2; weights and CNV layer 0 are
         not coded) and the counts are [run, epoch, layer, 6: weights physical, logical; thresholds physical (data plus check
         bits), logical (after decoding); threshold words corrected; detected as uncorrectable].
+        repair_every > 0: before every epoch t > 0 with t % repair_every == 0 that is no rewrite epoch the memories with
+        redundancy (TMR modules, coded thresholds) are repaired -- read, voted or decoded, written back -- which fixes only
+        what the redundancy covers and locks in what it gets wrong; the counts are then [run, epoch, layer, 8: the six
+        above, the words the epoch's repair rewrote, the words of the repaired memories still unlike the loaded ones].
         Left behind: self.exposure_results (classes, [run, image]), self.exposure_counts, self.exposure_usec."""
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, epochs of {} images, upset rate(s) per epoch weights {} thresholds {}, {}, bursts of {}, "
-              "scrub every {}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t,
-                                      organisation_name(scheme or 0, code), burst, scrub_every or "never"))
+              "scrub every {}{}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t,
+                                        organisation_name(scheme or 0, code), burst, scrub_every or "never",
+                                        ", repair every {}".format(repair_every) if repair_every else ""))
         args = (num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst, seed)
-        results, counts = self._classify(classifier, "_exposure", *(args + (code,) if code else args))
+        results, counts = self._classify(classifier, "_exposure", *(args + (code, repair_every) if repair_every else args + (code,) if code else args))
         self.exposure_results, self.exposure_counts, self.exposure_usec = results, counts, classifier.usecPerImage
         accuracies = [[util.calculate_accuracy(row[i: i + epoch_images].tolist(), self.labels[i: i + epoch_images])
                        for i in range(0, results.shape[1], epoch_images)] for row in results]
@@ -641,7 +646,10 @@ class NetworkTest:
         "scrub every", "epoch images" and the "physical bits" flipped (summed over runs and epochs) and "logical bits per
         epoch" that differ after each epoch (summed over the runs).  An entry of `schemes` may be a (scheme, code) pair (code 1:
         SEC-DED coded threshold memories): its name is "<scheme name> + SEC-DED", and it also writes "code" and the
-        "corrected words per epoch" and "detected words per epoch" (summed over the runs)."""
+        "corrected words per epoch" and "detected words per epoch" (summed over the runs).  An entry of `scrub_intervals`
+        may be a (scrub_every, repair_every) pair (run_exposure_test's repair scrub); with a non-zero repair_every the name
+        ends in " repair every <P>" and the result also holds "repair every", "repaired words per epoch" and "unrepaired
+        words per epoch" (summed over the runs)."""
         ft = self.fault_test
         folder = "{}/{}/{}/scrubbing/".format(output_folder, ft.network, ft.dataset)
         if self.control is None:  # (rate 0: the fault-free classes)
@@ -651,13 +659,22 @@ class NetworkTest:
             for burst in bursts:
                 for p in rates:
                     for every in scrub_intervals:
-                        per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed, code)
+                        every, repair = (int(every[0]), int(every[1])) if isinstance(every, (tuple, list)) else (every, 0)
+                        per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed, code,
+                                                                 *((repair,) if repair else ()))
                         accuracies = [util.calculate_accuracy(row.tolist(), ft.labels) for row in ft.exposure_results]
                         name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(scheme, code), burst, p, every)
                         status = {}
+                        if repair:  # [run, epoch, layer, 8]: the repair's two counters behind the coded shape
+                            name += " repair every {}".format(repair)
+                            status = {"repair every": repair, "repaired words per epoch": [int(x) for x in counts[..., 6].sum(axis=(0, 2))],
+                                      "unrepaired words per epoch": [int(x) for x in counts[..., 7].sum(axis=(0, 2))]}
+                            counts = counts[..., :6]
+                            if not code:
+                                counts = counts[..., :4].reshape(counts.shape[:3] + (2, 2))
                         if code:  # [run, epoch, layer, 6] -> the four counters in the uncoded shape, and the decode status
-                            status = {"code": int(code), "corrected words per epoch": [int(x) for x in counts[..., 4].sum(axis=(0, 2))],
-                                      "detected words per epoch": [int(x) for x in counts[..., 5].sum(axis=(0, 2))]}
+                            status.update({"code": int(code), "corrected words per epoch": [int(x) for x in counts[..., 4].sum(axis=(0, 2))],
+                                           "detected words per epoch": [int(x) for x in counts[..., 5].sum(axis=(0, 2))]})
                             counts = counts[..., :4].reshape(counts.shape[:3] + (2, 2))
                         raw.append(self._raw(name, num_runs, 0, [], accuracies))
                         extra[name] = {"mean accuracy per epoch": [float(x) for x in np.mean(np.array(per_epoch, float), axis=0)],

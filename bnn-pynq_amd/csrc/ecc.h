@@ -18,13 +18,20 @@
 // The code is linear: status and corrected bit depend on the error pattern (data mask dm, check mask cm) alone --
 //     decode(d ^ dm, encode(d) ^ cm) = (status of decode(dm, cm), d ^ data of decode(dm, cm)),
 // which is how the kernel (k_emem_noise_t) uses it: it decodes the accumulated hit masks, never a stored word.
+// A REPAIR (ecc_repair below; the exposure campaigns' repair scrub: mem_org.h, "repair scrubs") reads a stored word,
+// decodes it and, with status 1, writes the delivered data d' and encode(d') back; with status 0 or 2 it writes nothing.
+// By the same linearity that is a rule on error patterns, and the one k_repair_state applies to its hit masks:
+//     (dm, cm) -> (m, encode(m)) where decode(dm, cm) = (1, m), else (dm, cm) unchanged
+// -- a stored word d ^ dm, encode(d) ^ cm becomes d ^ m, encode(d ^ m) = encode(d) ^ encode(m).  The decoder flips exactly
+// one of the 22 positions, so what a status-1 repair stores is always a valid code word: a corrected single returns to
+// the loaded word (m = 0), an accepted triple becomes a clean-looking wrong one (m != 0, status 0 from then on) that no
+// later repair touches.  The delivered data is d' before and after.
 //
 // Two limits.  WEIGHTS are not coded: their memory words are SIMD * wbits wide (1 ... 32 bits in the fold tables) and
 // no per-word code makes sense over them -- as the interleaved schemes leave them alone.  The 24-bit threshold memory
 // of CNV LAYER 0 is not coded: a fault there passes through the reference's integer-part read-back (apply_fault), which
 // rewrites the whole word, and no code word survives that; layer 0 keeps the uncoded host route, and a study that wants
-// it out of the picture sets its rates to 0.  A scrub is a full rewrite (data and check words); a REPAIR scrub that
-// writes the decoder's output back is not modelled.
+// it out of the picture sets its rates to 0.  A scrub is a full rewrite (data and check words) or a repair (above).
 #pragma once
 #include <stdint.h>
 
@@ -60,6 +67,16 @@ BNN_HD inline int ecc_decode(uint32_t data, uint32_t check, uint32_t *out) {
   for (uint32_t t = s; t >>= 1;) hb++;
   *out = d ^ (1u << (s - hb - 2));
   return 1;
+}
+
+// what a repair leaves stored of (data, check), and the decode status: status 1 the delivered data and its check bits,
+// else the word as it was.  With an error pattern (dm, cm): the pattern that remains.
+BNN_HD inline int ecc_repair(uint32_t data, uint32_t check, uint32_t *out_data, uint32_t *out_check) {
+  uint32_t d;
+  const int status = ecc_decode(data, check, &d);
+  *out_data = status == 1 ? d : (data & 0xFFFFu);
+  *out_check = status == 1 ? ecc_encode(d) : (check & 0x3Fu);
+  return status;
 }
 
 }  // namespace bnn

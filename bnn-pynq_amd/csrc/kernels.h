@@ -246,4 +246,17 @@ hipError_t emem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned
                         bool signed_bb, const uint16_t *raw, int interleave, int burst, uint32_t rate_q32, int epoch, unsigned long long *state,
                         unsigned long long *counts, size_t run_stride, unsigned long long *ecc, size_t ecc_stride, hipStream_t s);
 
+// The repair scrub of the exposure campaigns (bnn_mi355x_repair_exposure_campaigns; the model: mem_org.h, "repair
+// scrubs"): ONE launch rewrites the state words of every layer that has redundancy, in place of a full rewrite's copy and
+// memset.  An entry per such layer: its state words (xmem_noise_t's or emem_noise_t's: runs * lanes of them) at
+// camp + state_off (8-byte aligned), lanes = rows * nthr, kind, and the layer's index for the counters.  TMR: the three
+// 16-bit hit masks become their bitwise majority; coded: (data mask, check mask) becomes ecc_repair's.  rep: this epoch's
+// [layer][2: words rewritten, words whose state still differs from the loaded one] of run 0, run q's rep_stride longs
+// behind.  The copies are not touched: a repair does not change the delivered parameters.
+enum : uint32_t { RK_SKIP = 0, RK_TMR = 1, RK_CODED = 2 };
+constexpr int kRepairEntries = 9;
+struct RepairEntry { unsigned long long state_off; uint32_t lanes, kind, layer, pad; };
+struct RepairTable { RepairEntry e[kRepairEntries]; };
+hipError_t repair_state(uint8_t *camp, const RepairTable &tab, int entries, int runs, unsigned long long *rep, size_t rep_stride, hipStream_t s);
+
 }  // namespace bnn

@@ -1,6 +1,7 @@
 // mem_org.cpp -- see mem_org.h (host only).
 #include "mem_org.h"
 
+#include <algorithm>
 #include <cstring>
 
 #include "act_faults.h"
@@ -175,6 +176,100 @@ void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams
     }
     out.t[l] = v;
   }
+}
+
+namespace {
+// the TMR repair of one memory: the low ebits of the three modules' words become their bitwise majority
+void repair_voted(RawParams *mod, const RawParams *loaded, bool thresholds, int l, int ebits, long *counts) {
+  auto mem = [&](RawParams &r) -> std::vector<std::vector<uint64_t>> & { return thresholds ? r.t[l] : r.w[l]; };
+  const uint64_t emask = ebits >= 64 ? ~0ull : (1ull << ebits) - 1;
+  for (size_t pe = 0; pe < mem(mod[0]).size(); pe++)
+    for (size_t i = 0; i < mem(mod[0])[pe].size(); i++) {
+      uint64_t *const w[3] = {&mem(mod[0])[pe][i], &mem(mod[1])[pe][i], &mem(mod[2])[pe][i]};
+      const uint64_t v = ((*w[0] & *w[1]) | (*w[0] & *w[2]) | (*w[1] & *w[2])) & emask;
+      bool wrote = false;
+      for (int m = 0; m < 3; m++) {
+        wrote = wrote || (*w[m] & emask) != v;
+        *w[m] = (*w[m] & ~emask) | v;
+      }
+      if (counts && wrote) counts[0]++;
+      if (counts && loaded && v != ((thresholds ? loaded[0].t[l] : loaded[0].w[l])[pe][i] & emask)) counts[1]++;
+    }
+}
+
+// the bits of the logical element (line ind, threshold i) of one PE, gathered from / scattered to its physical sites
+uint32_t gather(const LayerSpec &L, int il, int width, const std::vector<uint64_t> &pe, int ind, int i) {
+  uint32_t v = 0;
+  for (int k = 0; k < width; k++) {
+    int pi, pb;
+    interleave_site(il, width, L.fold.tmem, ind, k, &pi, &pb);
+    v |= (uint32_t)((pe[(size_t)pi * L.nthr + i] >> pb) & 1) << k;
+  }
+  return v;
+}
+void scatter(const LayerSpec &L, int il, int width, std::vector<uint64_t> &pe, int ind, int i, uint32_t v) {
+  for (int k = 0; k < width; k++) {
+    int pi, pb;
+    interleave_site(il, width, L.fold.tmem, ind, k, &pi, &pb);
+    uint64_t &w = pe[(size_t)pi * L.nthr + i];
+    w = (w & ~(1ull << pb)) | (uint64_t)((v >> k) & 1) << pb;
+  }
+}
+}  // namespace
+
+void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0, int l1, long (*counts)[2], const PhysParams *loaded) {
+  for (int l = std::max(l0, p.l0); l < l1 && l < p.l1; l++) {
+    const LayerSpec &L = net.L[l];
+    EccOrg eo{MemOrg{1, 1, 0}, 0};
+    if (counts) counts[l][0] = counts[l][1] = 0;
+    if (!ecc_layout(net, scheme, code, l, eo).empty()) continue;
+    if (eo.org.w_modules == 3) repair_voted(p.mod, loaded ? loaded->mod : nullptr, false, l, mem_element_bits(L, 0), counts ? counts[l] : nullptr);
+    if (L.nthr == 0) continue;
+    if (!eo.check_bits) {
+      if (eo.org.t_modules == 3) repair_voted(p.mod, loaded ? loaded->mod : nullptr, true, l, mem_element_bits(L, 1), counts ? counts[l] : nullptr);
+      continue;
+    }
+    // a coded memory, element by element: its 16 data and 6 check bits lie where interleave_site puts them, and no other
+    // element's do, so the order of the elements does not matter
+    const int il = eo.org.t_interleave;
+    for (size_t pe = 0; pe < p.mod[0].t[l].size(); pe++)
+      for (int ind = 0; ind < L.fold.tmem; ind++)
+        for (int i = 0; i < L.nthr; i++) {
+          const uint32_t d = gather(L, il, kEccDataBits, p.mod[0].t[l][pe], ind, i), c = gather(L, il, kEccCheckBits, p.mod[1].t[l][pe], ind, i);
+          uint32_t rd, rc;
+          const int st = ecc_repair(d, c, &rd, &rc);
+          if (st == 1) {
+            scatter(L, il, kEccDataBits, p.mod[0].t[l][pe], ind, i, rd);
+            scatter(L, il, kEccCheckBits, p.mod[1].t[l][pe], ind, i, rc);
+            if (counts) counts[l][0]++;
+          }
+          if (counts && loaded &&
+              (rd != gather(L, il, kEccDataBits, loaded->mod[0].t[l][pe], ind, i) || rc != gather(L, il, kEccCheckBits, loaded->mod[1].t[l][pe], ind, i)))
+            counts[l][1]++;
+        }
+  }
+}
+
+std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n) {
+  for (int i = 0; i < n; i++) {
+    const int layer = records[(size_t)i * 9 + 2];
+    if (layer < 0 && layer != kMarkRepair && layer != kMarkRewrite)
+      return "record " + std::to_string(i) + ": layer " + std::to_string(layer) +
+             " is no marker (-1: repair all memories now, -2: rewrite all memories from the loaded parameters now)";
+  }
+  for (int i = 0; i < n; i++) {
+    const int *v = records + (size_t)i * 9;
+    if (v[2] == kMarkRepair) {
+      phys_repair(net, scheme, code, p, p.l0, p.l1, nullptr);
+    } else if (v[2] == kMarkRewrite) {
+      p = loaded;
+    } else {
+      const PhysFault pf{Fault{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}, v[8]};
+      if (phys_apply(net, scheme, p, pf, code) < 0)
+        return "record " + std::to_string(i) + ": fault record out of range (or a module the memory does not have)";
+    }
+  }
+  return "";
 }
 
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,

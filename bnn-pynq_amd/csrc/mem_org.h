@@ -120,8 +120,8 @@ BNN_HD inline void interleave_source(int il, int T, int lines, int p_ind, int p_
 // input draws (0 there).  An epoch's upsets XOR onto whatever the PHYSICAL state holds, before the epoch's images are
 // classified; the order inside an epoch is the one above, across epochs epoch-major (it matters for the layer-0
 // integer-part quirk of apply_fault alone).  scrub_every = S > 0: before the upsets of every epoch t > 0 with t % S == 0
-// all physical memories return to the loaded parameters (a full rewrite; a voter-driven repair is not modelled); S = 0
-// never.  The logical parameters of an epoch are de-interleave(vote(modules)) of the state.  On the host: the blob of
+// all physical memories return to the loaded parameters (a full rewrite; the repair that reads, votes or decodes and
+// writes back: "repair scrubs" below); S = 0 never.  The logical parameters of an epoch are de-interleave(vote(modules)) of the state.  On the host: the blob of
 // (run, epoch t) is pack_params_hardened of the masks of epochs (last scrub epoch <= t) ... t, concatenated.
 // The epoch granularity, the full-rewrite scrub and the voter are the project's own choices: parity unpinned.
 constexpr int kMaxEpochs = 1 << 16;  // (the epoch shares its counter word with the tag byte: below 2^24)
@@ -147,8 +147,42 @@ inline int exposure_first_epoch(int t, int scrub_every) { return scrub_every > 0
 // the data memory into the check memory.  Order inside an epoch: module-major, data then check.
 // Counts per (run, epoch, layer), six: the four above (thresholds: physical = data plus check bits flipped, logical = data
 // bits that differ after decoding), then the threshold words whose decode status after the epoch is 1, and 2.
-// The storage in a check memory of its own, the draw, and the absence of a repair scrub are the project's own choices.
+// The storage in a check memory of its own and the draw are the project's own choices.
 BNN_HD inline uint32_t ecc_check_groups(int burst) { return (uint32_t)((kEccCheckBits + burst - 1) / burst); }
+
+// ---- repair scrubs (bnn_mi355x_repair_exposure_campaigns): read, vote or decode, write back ---------------------------
+// The full rewrite above needs the golden copy; a system that flies TMR or a code scrubs by reading a word, voting or
+// decoding it and writing the result back.  repair_every = P >= 0 goes next to scrub_every = S: before the upsets of epoch
+// t > 0 a full rewrite happens if S > 0 and t % S == 0 (as above, and then there is no repair in that epoch); otherwise a
+// REPAIR happens if P > 0 and t % P == 0.  A repair visits every physical memory that has redundancy:
+//   TMR memories (three modules: layer 0's weights, the thresholds of layers 0-4 under scheme 1): for every word, v is
+//     the bitwise majority of the low `ebits` of the three stored words -- the voter of phys_logical -- and the low
+//     `ebits` of all three modules become v.
+//   Coded threshold memories (code 1), per LOGICAL element: with (d, c) the de-interleaved data and check words and
+//     st = ecc_decode(d, c, &d'): st = 1, data d' and check ecc_encode(d') are stored (scheme 2: re-interleaved; only the
+//     element's own bits of the two physical lines change); st = 0 or 2, nothing is written (ecc_repair, ecc.h).
+//   Every other memory is untouched: the weights of layers >= 1, single-module thresholds (layers 5-7 under TMR),
+//     uncoded memories, CNV layer 0 under code 1 included.
+// So a repair fixes only what the redundancy covers, and it locks in what the redundancy gets wrong: a TMR bit hit in two
+// modules, a triple error the decoder accepts as a correction -- valid stored states that no later repair touches.  In
+// error-pattern terms (what k_repair_state applies to the state words of k_xmem_noise_t / k_emem_noise_t):
+//     TMR    (m0, m1, m2) -> (v, v, v), v = maj(m0, m1, m2)
+//     coded  (dm, cm) -> (m, ecc_encode(m)) when ecc_decode(dm, cm, &m) is 1, else unchanged (the code is linear: ecc.h)
+// The logical parameters are the same before and after a repair: it changes only what later upsets meet.
+// Counts per (run, epoch, layer), eight: the six above, then [6] the logical words the repair of that epoch rewrote (TMR:
+// words where some module differed from the vote, counted once; coded: status-1 words) and [7] the words of the layer's
+// repaired memories whose stored state still differs from the loaded one after the repair (TMR: vote != loaded; coded:
+// left at status 2, or a wrong code word -- one this repair wrote or an earlier one locked in).  Both 0 in an epoch
+// without a repair and for a layer without redundancy; CNV layer 0 counts weights and thresholds together.
+// On the host: MARKER records among the 9-int records (bnn_mi355x_pack_params_repair), layer -1 "repair all memories
+// now", layer -2 "rewrite all memories from the loaded parameters now"; the blob of (run, epoch t) is that of the
+// concatenation over epochs 0 ... t of [the epoch's marker, if one is due] + the epoch's records in the in-epoch order.
+// TMR plus a code stays refused.  Like the voter and the code, the repair is the project's own model: parity unpinned.
+enum : int { kMarkRepair = -1, kMarkRewrite = -2 };
+inline bool exposure_rewrites(int t, int scrub_every) { return t > 0 && scrub_every > 0 && t % scrub_every == 0; }
+inline bool exposure_repairs(int t, int scrub_every, int repair_every) {
+  return t > 0 && repair_every > 0 && t % repair_every == 0 && !exposure_rewrites(t, scrub_every);
+}
 
 // ---- host only from here ---------------------------------------------------------------------------------------------
 
@@ -176,6 +210,15 @@ int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &p
 // words end with the decode (they hold the 16 delivered bits alone); status, where given, counts per layer the words
 // decoded with status 1 ([l][0]) and 2 ([l][1])
 void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code = 0, long (*status)[2] = nullptr);
+// one repair ("repair scrubs" above) of the memories of layers [l0, l1) that have redundancy, in place.  counts, where
+// given, receives per layer [l][0] the words rewritten and, with `loaded` (phys_load's result for the same arguments),
+// [l][1] the words of the repaired memories whose stored state still differs from the loaded one afterwards
+void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0, int l1, long (*counts)[2],
+                 const PhysParams *loaded = nullptr);
+// the records of bnn_mi355x_pack_params_repair, 9 ints each, applied to p in order: a fault record through phys_apply, a
+// marker (layer kMarkRepair / kMarkRewrite) as a repair of all memories / a return to `loaded`.  "" or why a record is
+// refused, naming it; every layer field is checked before anything is applied
+std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n);
 
 // element width in bits of a layer's weight (target 0) or threshold (target 1) memory; 0: no threshold memory
 int mem_element_bits(const LayerSpec &L, int target);

@@ -294,6 +294,10 @@ struct Runtime {
   // decoded with status 1 and with status 2 after the epoch] and the seeds
   std::vector<long> emem_counts;
   std::vector<unsigned long long> emem_seeds;
+  // bnn_mi355x_repair_exposure_campaigns (the same buffers): [run][epoch][layer][8: the six above, then the words the
+  // epoch's repair rewrote and the words of the repaired memories still unlike the loaded ones after it] and the seeds
+  std::vector<long> rmem_counts;
+  std::vector<unsigned long long> rmem_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -3238,6 +3242,8 @@ struct MemNoiseJob {
   // state_off[l] of d_camp, all of them in [state_begin, state_begin + state_bytes)
   std::vector<int> span_first;
   size_t state_off[9] = {}, state_begin = 0, state_bytes = 0;
+  // the repair route: [run][epoch][layer][2] of the host's layer-0 repairs (words rewritten, words still unlike the loaded ones)
+  std::vector<unsigned long long> host_repairs;
 };
 
 // Layer 0 of one run through the physical model (mem_org.h): the events of every module applied to `phys` in order, the
@@ -3455,10 +3461,12 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
 // ---- exposure campaigns: upsets that accumulate over epochs, with scrubbing (the model: mem_org.h) -------------------------
 
 // longs: the counters per (run, epoch, layer) the caller is handed -- 4, or 6 on the coded route (the ecc entry points, with
-// code 0 as well), whose last_* state is its own
-struct Exposure { int epoch_images, scrub_every, longs = 4; };
+// code 0 as well), whose last_* state is its own, or 8 on the repair route (likewise its own; with repair_every 0 as well)
+// repair_every: the repair scrub of mem_org.h ("repair scrubs"); 0 never
+struct Exposure { int epoch_images, scrub_every, longs = 4, repair_every = 0; };
 
-static bool exposure_scrubs(const Exposure &ex, int t) { return t > 0 && ex.scrub_every > 0 && t % ex.scrub_every == 0; }
+static bool exposure_scrubs(const Exposure &ex, int t) { return exposure_rewrites(t, ex.scrub_every); }
+static bool exposure_repairs(const Exposure &ex, int t) { return exposure_repairs(t, ex.scrub_every, ex.repair_every); }
 
 // What the host prepares for E epochs.  Layer 0 of the CNV nets: one persistent physical working state per run is stepped
 // through the epochs by hardened_layer0, scrubs included (the draw is deterministic, so all of it is known before anything
@@ -3474,6 +3482,7 @@ static int exposure_prepare(const std::vector<unsigned long long> &seeds, const 
   std::memcpy(&h, r.blob.data(), sizeof(h));
   job.stride = (r.blob.size() + 255) & ~(size_t)255;
   job.host_counts.assign((size_t)R * E * S * 4, 0);
+  job.host_repairs.assign(ex.longs == 8 ? (size_t)R * E * S * 2 : 0, 0);
   std::vector<uint8_t> staging;
   std::vector<std::vector<PatchSpan>> by_epoch((size_t)E);
   if (net.L[0].arith == AR_INT8 && (rw[0] || rth[0])) {
@@ -3497,6 +3506,12 @@ static int exposure_prepare(const std::vector<unsigned long long> &seeds, const 
         if (scrub) {  // (the copies on the device return to the loaded blob as well)
           phys = loaded;
           std::fill(before.begin(), before.end(), 0);
+        } else if (exposure_repairs(ex, t)) {
+          // a repair: the modules of layer 0 voted and written back.  The delivered rows do not change: no patch
+          long rc[1][2];
+          phys_repair(net, hz.scheme, hz.code, phys, 0, 1, rc, &loaded);
+          job.host_repairs[(((size_t)q * E + t) * S + 0) * 2] = (unsigned long long)rc[0][0];
+          job.host_repairs[(((size_t)q * E + t) * S + 0) * 2 + 1] = (unsigned long long)rc[0][1];
         }
         if (hardened_layer0(hz, seeds[(size_t)q], rate, loaded, phys, raw, touched, counts, t, true)) return -1;
         if (counts[0] + counts[2] == 0) {  // no event: nothing to patch; without a scrub the logical state is the last epoch's
@@ -3547,7 +3562,8 @@ static int exposure_prepare(const std::vector<unsigned long long> &seeds, const 
 
 // Enqueues on r.stream what comes before epoch 0: the seeds, the zeroed [run][epoch][layer][2][2] counters at counts_off of
 // d_noise, the runs' copies of the loaded blob, the job's upload and the zeroed threshold state.
-// longs 6: the [run][epoch][layer][2] decode-status counters of k_emem_noise_t lie behind the others.
+// longs 6: the [run][epoch][layer][2] decode-status counters of k_emem_noise_t lie behind the others; longs 8: behind
+// those, the [run][epoch][layer][2] counters of k_repair_state.
 static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, int E, int longs = 4) {
   Runtime &r = rt();
   const int R = (int)seeds.size(), S = r.spec.nlayers;
@@ -3563,7 +3579,8 @@ static int exposure_begin(const std::vector<unsigned long long> &seeds, const Me
   return 0;
 }
 
-// Enqueues epoch t: the scrub where one is due (the copies restored by the same doubling copy, the state cleared), the
+// Enqueues epoch t: the scrub where one is due (the copies restored by the same doubling copy, the state cleared) or
+// else the repair where one is due (ONE launch of k_repair_state over the state of every layer with redundancy), the
 // host's layer-0 patches of the epoch, then the upset kernels layer by layer, weights before thresholds.
 static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned int *rth, const MemNoiseJob &job, size_t counts_off, int E,
                           const Exposure &ex, const Hardening &hz) {
@@ -3579,6 +3596,21 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
   if (exposure_scrubs(ex, t)) {
     if (replicate_blob(R, stride)) return -1;
     if (job.state_bytes) HIP_OK(hipMemsetAsync(r.d_camp + job.state_begin, 0, job.state_bytes, r.stream));
+  } else if (exposure_repairs(ex, t) && ex.longs == 8 && job.state_bytes) {
+    RepairTable tab{};
+    int entries = 0;
+    for (int l = 0; l < S; l++) {
+      const LayerSpec &L = net.L[l];
+      if (!rth[l] || L.thr24 || L.arith == AR_INT8) continue;  // (no state: nothing to repair)
+      EccOrg eo{MemOrg{1, 1, 0}, 0};
+      ecc_layout(net, hz.scheme, hz.code, l, eo);
+      const uint32_t kind = eo.check_bits ? RK_CODED : eo.org.t_modules == 3 ? RK_TMR : RK_SKIP;
+      if (kind != RK_SKIP) tab.e[entries++] = RepairEntry{(unsigned long long)job.state_off[l], h.layer[l].rows * (uint32_t)L.nthr, kind, (uint32_t)l, 0};
+    }
+    // the repair counters behind the [run][epoch][layer][4] and the [run][epoch][layer][2] decode-status counters
+    unsigned long long *const d_rep = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * run_stride / 4 * 6 + (size_t)t * S * 2;
+    const hipError_t re = repair_state(r.d_camp, tab, entries, R, d_rep, (size_t)E * S * 2, r.stream);
+    if (re != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(re));
   }
   const int s0 = job.span_first[(size_t)t], s1 = job.span_first[(size_t)t + 1];
   hipError_t e = scatter_patches(r.d_camp, reinterpret_cast<const PatchSpan *>(r.d_camp + job.spans_off) + s0, s1 - s0, r.d_copies, r.stream);
@@ -3620,14 +3652,19 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
                                      float *usecPerImage, const Exposure *ex = nullptr) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  const bool six = ex && ex->longs == 6;  // the coded route: two decode-status counters behind the four
-  std::vector<long> &last_counts = six ? r.emem_counts : ex ? r.xmem_counts : (hz ? r.hmem_noise_counts : r.mem_noise_counts);
-  std::vector<unsigned long long> &last_seeds = six ? r.emem_seeds : ex ? r.xmem_seeds : (hz ? r.hmem_noise_seeds : r.mem_noise_seeds);
+  const bool eight = ex && ex->longs == 8;       // the repair route: two repair counters behind the six
+  const bool six = eight || (ex && ex->longs == 6);  // the coded route: two decode-status counters behind the four
+  std::vector<long> &last_counts = eight ? r.rmem_counts : six ? r.emem_counts : ex ? r.xmem_counts : (hz ? r.hmem_noise_counts : r.mem_noise_counts);
+  std::vector<unsigned long long> &last_seeds = eight ? r.rmem_seeds : six ? r.emem_seeds : ex ? r.xmem_seeds : (hz ? r.hmem_noise_seeds : r.mem_noise_seeds);
   last_counts.clear();
   last_seeds.clear();
   const int S = net.nlayers;
   if (ex && (ex->epoch_images < 1 || ex->scrub_every < 0)) {
     fail(std::string(who) + ": epoch_images must be at least 1 and scrub_every must not be negative (0: never scrub)");
+    return nullptr;
+  }
+  if (ex && ex->repair_every < 0) {
+    fail(std::string(who) + ": repair_every must not be negative (0: never repair)");
     return nullptr;
   }
   if (!path) {
@@ -3643,19 +3680,26 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     fail(std::string(who) + ": seed + run wraps to 0 for a run (0 seeds from std::random_device)");
     return nullptr;
   }
-  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz)) return nullptr;
   ImageFile f;
-  if (open_image_file(path, f)) return nullptr;
+  // the epochs a file implies, refused where they or their counters are too many; `false` once that is known not to be so
+  auto too_many_epochs = [&]() -> bool {
+    const long long images = (long long)f.n, per = ex ? ex->epoch_images : std::max<long long>(images, 1), epochs = (images + per - 1) / per;
+    if (!ex || (epochs <= kMaxEpochs && (unsigned long long)R * (unsigned long long)epochs * S * (unsigned)ex->longs <= 0x7FFFFFFFull)) return false;
+    fail(std::string(who) + ": " + std::to_string(epochs) + " epochs: at most " + std::to_string(kMaxEpochs) +
+         ", and num_runs * epochs * layers * " + std::to_string(ex->longs) + " counters must stay below 2^31");
+    return true;
+  };
+  // (the repair route refuses every argument before a device is looked for -- mem_noise_check ends with ready(), the first
+  // thing that may touch one -- and the file's size is known without a device; the other routes keep the order they had)
+  if (eight && (open_image_file(path, f) || too_many_epochs())) return nullptr;
+  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz)) return nullptr;
+  if (!eight && open_image_file(path, f)) return nullptr;
   const int n = (int)f.n;
   const size_t total = (size_t)R * n;
   const bool cnv = net.is_cnv;
   const int ei = ex ? ex->epoch_images : std::max(n, 1);  // images per epoch; without ex the call is one epoch
   const long long epochs = ((long long)n + ei - 1) / ei;
-  if (ex && (epochs > kMaxEpochs || (unsigned long long)R * (unsigned long long)epochs * S * (unsigned)ex->longs > 0x7FFFFFFFull)) {
-    fail(std::string(who) + ": " + std::to_string(epochs) + " epochs: at most " + std::to_string(kMaxEpochs) +
-         ", and num_runs * epochs * layers * " + std::to_string(ex->longs) + " counters must stay below 2^31");
-    return nullptr;
-  }
+  if (!eight && too_many_epochs()) return nullptr;  // (the repair route: checked above)
   const int E = (int)epochs;
   std::vector<unsigned long long> seeds((size_t)R);
   {
@@ -3675,6 +3719,7 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
   if (!result) { fail("out of memory"); return nullptr; }
   std::vector<unsigned long long> counts((size_t)R * (ex ? E : 1) * S * (hz ? 4 : 2), 0);
   std::vector<unsigned long long> status(six ? (size_t)R * E * S * 2 : 0, 0);  // (the coded route: [run][epoch][layer][2])
+  std::vector<unsigned long long> repairs(eight ? (size_t)R * E * S * 2 : 0, 0);  // (the repair route: likewise)
   MemNoiseJob job;
   double device_us = 0.0;
   auto run = [&]() -> int {
@@ -3755,11 +3800,15 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     HIP_OK(hipEventRecord(r.time_events[1], r.stream));
     if (any) HIP_OK(hipMemcpyAsync(counts.data(), r.d_noise + counts_off, counts.size() * 8, hipMemcpyDeviceToHost, r.stream));
     if (any && six) HIP_OK(hipMemcpyAsync(status.data(), r.d_noise + counts_off + counts.size() * 8, status.size() * 8, hipMemcpyDeviceToHost, r.stream));
+    if (any && eight)
+      HIP_OK(hipMemcpyAsync(repairs.data(), r.d_noise + counts_off + (counts.size() + status.size()) * 8, repairs.size() * 8, hipMemcpyDeviceToHost,
+                            r.stream));
     if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
     else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
     HIP_OK(hipStreamSynchronize(r.stream));
     for (size_t i = 0; !cnv && i < total; i++) result[i] = lfc_class_batched(w[i], number_class);
     for (size_t i = 0; i < job.host_counts.size(); i++) counts[i] += job.host_counts[i];
+    for (size_t i = 0; i < job.host_repairs.size(); i++) repairs[i] += job.host_repairs[i];
     float ms = 0.f;
     HIP_OK(hipEventElapsedTime(&ms, r.time_events[0], r.time_events[1]));
     drain.ok();
@@ -3770,11 +3819,13 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     delete[] result;
     return nullptr;
   }
-  if (six) {  // [run][epoch][layer]: the four counters, then the two decode-status counters
-    last_counts.resize(counts.size() / 4 * 6);
+  if (six) {  // [run][epoch][layer]: the four counters, then the two decode-status counters, then (eight) the two repair counters
+    const size_t k = eight ? 8 : 6;
+    last_counts.resize(counts.size() / 4 * k);
     for (size_t b = 0; b < counts.size() / 4; b++) {
-      for (int j = 0; j < 4; j++) last_counts[b * 6 + j] = (long)counts[b * 4 + j];
-      for (int j = 0; j < 2; j++) last_counts[b * 6 + 4 + j] = (long)status[b * 2 + j];
+      for (int j = 0; j < 4; j++) last_counts[b * k + j] = (long)counts[b * 4 + j];
+      for (int j = 0; j < 2; j++) last_counts[b * k + 4 + j] = (long)status[b * 2 + j];
+      for (int j = 0; j < 2 && eight; j++) last_counts[b * k + 6 + j] = (long)repairs[b * 2 + j];
     }
   } else {
     last_counts.assign(counts.begin(), counts.end());
@@ -3984,9 +4035,12 @@ int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int schem
 
 // One copy stepped through epochs 0 ... epoch by the campaign's own steps (exposure_begin, exposure_epoch), then read back.
 static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
-                                   const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
+                                   const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap,
+                                   int repair_every = -1) {
   Runtime &r = rt();
-  const Exposure ex{1, scrub_every, 6};  // (room for the decode-status counters of a coded layer; nothing reads them here)
+  // (room for the decode-status counters of a coded layer, and on the repair route -- repair_every >= 0 -- for the repair
+  // counters; nothing reads them here)
+  const Exposure ex{1, scrub_every, repair_every < 0 ? 6 : 8, std::max(repair_every, 0)};
   if (epoch < 0 || epoch >= kMaxEpochs || scrub_every < 0) {
     fail(std::string(who) + ": epoch must be 0 ... " + std::to_string(kMaxEpochs - 1) + " and scrub_every must not be negative (0: never scrub)");
     return 0;
@@ -4134,6 +4188,71 @@ int bnn_mi355x_last_ecc_exposure_counts(long *counts, int cap) {
 
 int bnn_mi355x_last_ecc_exposure_seeds(unsigned long long *seeds, int cap) {
   const std::vector<unsigned long long> &k = rt().emem_seeds;
+  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
+  return (int)k.size();
+}
+
+// ---- repair scrubs in the exposure campaigns (the model: mem_org.h, "repair scrubs"; the rule on a code word: ecc.h) -------
+
+int bnn_mi355x_ecc_repair(unsigned int data, unsigned int check, unsigned int *out_data, unsigned int *out_check) {
+  uint32_t d, c;
+  const int status = ecc_repair(data, check, &d, &c);
+  if (out_data) *out_data = d;
+  if (out_check) *out_check = c;
+  return status;
+}
+
+size_t bnn_mi355x_pack_params_repair(const char *path, int scheme, int code, const int *records, int n_faults, void *dst, size_t cap) {
+  const NetSpec &net = rt().spec;
+  EccOrg eo;
+  const std::string le = ecc_layout(net, scheme, code, 0, eo);
+  if (!le.empty()) { fail("pack_params_repair: " + le); return 0; }
+  RawParams raw;
+  const std::string e = read_raw_params(net, path ? path : "", raw);
+  if (!e.empty()) { fail(e); return 0; }
+  PhysParams loaded;
+  phys_load(net, scheme, raw, 0, net.nlayers, loaded, code);
+  PhysParams phys = loaded;
+  const std::string re = phys_replay(net, scheme, code, loaded, phys, records, n_faults);
+  if (!re.empty()) { fail("pack_params_repair: " + re); return 0; }
+  phys_logical(net, scheme, phys, raw, code);
+  std::vector<uint8_t> blob;
+  pack_blob(net, raw, blob);
+  if (dst) {
+    if (cap < blob.size()) { fail("pack_params_repair: destination too small"); return 0; }
+    std::memcpy(dst, blob.data(), blob.size());
+  }
+  return blob.size();
+}
+
+int *bnn_mi355x_repair_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst, int num_runs, unsigned long long seed,
+                                          const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch_images,
+                                          int scrub_every, int repair_every, int *image_number, float *usecPerImage) {
+  const Hardening hz{scheme, burst, code};
+  const Exposure ex{epoch_images, scrub_every, 8, repair_every};
+  return mem_noise_campaigns_impl("repair_exposure_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates,
+                                  image_number, usecPerImage, &ex);
+}
+
+size_t bnn_mi355x_repair_exposure_params(int scheme, int code, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                         const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, int repair_every, void *dst,
+                                         size_t cap) {
+  if (repair_every < 0) {
+    fail("repair_exposure_params: repair_every must not be negative (0: never repair)");
+    return 0;
+  }
+  return exposure_params_impl("repair_exposure_params", Hardening{scheme, burst, code}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch,
+                              scrub_every, dst, cap, repair_every);
+}
+
+int bnn_mi355x_last_repair_exposure_counts(long *counts, int cap) {
+  const std::vector<long> &c = rt().rmem_counts;
+  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
+  return (int)c.size();
+}
+
+int bnn_mi355x_last_repair_exposure_seeds(unsigned long long *seeds, int cap) {
+  const std::vector<unsigned long long> &k = rt().rmem_seeds;
   for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
   return (int)k.size();
 }

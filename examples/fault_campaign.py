@@ -81,6 +81,18 @@ for scheme in (0, 1):
                                                                   np.round(e["mean accuracy per epoch"], 2).tolist()))
 net.scrubbing_curve(os.path.join(out, "ecc"), 10, [2.0 ** -10], [0, 1], [(0, 1), (2, 1)], 250, bursts=(1, 2), seed=1)  # (scheme, code): SEC-DED coded thresholds
 
+# the scrub such memories really have: a REPAIR reads a word, votes or decodes it and writes it back -- it fixes only what the
+# redundancy covers and locks in what it gets wrong.  (scrub_every, repair_every): rewrite every epoch / repair every epoch /
+# repair every epoch + rewrite every 10 / never; 20 epochs of 100 images, TMR and interleaved + SEC-DED
+intervals = [(1, 0), (0, 1), (10, 1), (0, 0)]
+net.scrubbing_curve(os.path.join(out, "repair"), 10, [2.0 ** -10], intervals, [1, (2, 1)], 100, seed=1)
+stats = json.load(open(os.path.join(out, "repair", "cnvW1A1", "cifar10", "scrubbing", "cnvW1A1_cifar10_scrubbing_stats.json")))
+for name in ("TMR", "interleaved + SEC-DED"):
+    for every, repair in intervals:
+        e = stats["results"]["%s burst 1 upset rate %g scrub every %d" % (name, 2.0 ** -10, every) + (" repair every %d" % repair if repair else "")]
+        print("%-21s rewrite every %2d repair every %d: avg accuracy %.2f, last epoch %.2f, words repaired %d"
+              % (name, every, repair, e["avg accuracy"], e["mean accuracy per epoch"][-1], sum(e.get("repaired words per epoch", [0]))))
+
 # the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
 net.input_upset_rate_curve(out, 10, rates, seed=1)
 for p in rates:

@@ -479,7 +479,7 @@ int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap)
  * state holds; inside an epoch layer-major, weights then thresholds, module-major, in event order; across epochs
  * epoch-major (the order matters only for the layer-0 integer-part quirk, kept as is).
  * Scrubbing: scrub_every = S.  0: never.  S > 0: before the upsets of every epoch t > 0 with t % S == 0 all physical
- * memories return to the loaded parameters -- a full rewrite; a voter-driven repair scrub is not modelled.
+ * memories return to the loaded parameters -- a full rewrite; the voter-driven repair scrub: repair_exposure_campaigns.
  * The logical parameters of an epoch are de-interleave(vote(modules)) of the physical state.  On the host: the blob of
  * (run k, epoch t) is pack_params_hardened(dir, scheme, records), the records being the concatenation over epochs
  * t' = (last scrub epoch <= t) ... t of exposure_mask's records of that epoch, each in the in-epoch order above.
@@ -546,7 +546,7 @@ int bnn_mi355x_last_exposure_seeds(unsigned long long *seeds, int cap);
  * word_size b: a pure XOR of bits [bit, min(bit + b, 6)) of the check word.  Bursts do not cross from the data memory
  * into the check memory.  Order inside an epoch: layer-major, weights then thresholds, module-major (data, then check),
  * in event order.  Epochs, the scrub (a full rewrite, of data and check words) and the epoch cap are exposure_campaigns'
- * own; a REPAIR scrub that writes the decoder's output back is not modelled.
+ * own; the REPAIR scrub that writes the decoder's output back: repair_exposure_campaigns below.
  * ecc_encode / ecc_decode: host only; the 6 check bits / the status, the delivered data in *out_data.
  * ecc_layout: out = {weight modules, threshold modules (2 where coded: data plus check), interleave, check bits 0 / 6};
  * -1 + last_error for a refused pair.
@@ -579,6 +579,51 @@ size_t bnn_mi355x_ecc_exposure_params(int scheme, int code, int burst, unsigned 
                                       int scrub_every, void *dst, size_t cap);
 int bnn_mi355x_last_ecc_exposure_counts(long *counts, int cap);
 int bnn_mi355x_last_ecc_exposure_seeds(unsigned long long *seeds, int cap);
+
+/* Repair scrubs in the exposure campaigns: the scrub a system that flies TMR or a code really has.  scrub_every's full
+ * rewrite needs the golden copy; a REPAIR reads a word, votes or decodes it, and writes the result back.  Like the voter
+ * and the code it is this project's own model (csrc/mem_org.h "repair scrubs", csrc/ecc.h): parity unpinned.
+ * repair_every = P >= 0 goes next to scrub_every = S: before the upsets of epoch t > 0 a full rewrite happens if S > 0 and
+ * t % S == 0 (and then no repair in that epoch); otherwise a repair happens if P > 0 and t % P == 0.  A repair visits
+ * every physical memory that has redundancy:
+ *   TMR memories (layer 0's weights, the thresholds of layers 0-4 under scheme 1): the low `ebits` of all three modules'
+ *     words become their bitwise majority (the voter);
+ *   coded threshold memories (code 1), per logical element: with (d, c) the de-interleaved data and check words and
+ *     st = ecc_decode(d, c, &d'): st = 1, d' and ecc_encode(d') are stored (scheme 2: re-interleaved; only the element's
+ *     own bits of the two physical lines change); st = 0 or 2, nothing is written;
+ *   every other memory is untouched: the weights of layers >= 1, single-module thresholds, uncoded memories (CNV layer 0
+ *     under code 1 included).
+ * So it fixes only what the redundancy covers, and locks in what the redundancy gets wrong (a TMR bit hit in two
+ * modules; a triple error the decoder accepts: a status-1 result is always a valid code word).  The delivered parameters
+ * are the same before and after a repair.
+ * ecc_repair: host only; the decode status, and in *out_data / *out_check what a repair leaves stored of (data, check).
+ * pack_params_repair: pack_params_ecc with two MARKER records among the 9-int records, told by their layer field: -1
+ * repair all memories now, -2 rewrite all memories from the loaded parameters now (the other eight ints are not read).
+ * Without markers it is pack_params_ecc byte for byte; any other negative layer is refused, naming the record.  The
+ * blob of (run, epoch t) is pack_params_repair of the concatenation over epochs 0 ... t of [the epoch's marker, if one is
+ * due] + ecc_exposure_mask's records of that epoch in the in-epoch order.  Host only.
+ * repair_exposure_campaigns: ecc_exposure_campaigns' conventions and refusals, plus repair_every < 0 and num_runs * E *
+ * layers * 8 >= 2^31; TMR plus a code stays refused.  repair_every 0: that function's classes, six counts, seeds and
+ * blobs bit for bit.  The last_* state is this entry point's own.
+ * repair_exposure_params: the blob a run classifies epoch `epoch` with, made by the campaign's own steps and read back.
+ * last_repair_exposure_counts: per [run][epoch][layer] eight longs: the six of last_ecc_exposure_counts, then [6] the
+ * logical words the repair of that epoch rewrote (TMR: words where some module differed from the vote, counted once;
+ * coded: status-1 words) and [7] the words of the layer's repaired memories whose stored state still differs from the
+ * loaded one after the repair (TMR: vote != loaded; coded: left at status 2, or a wrong code word, written now or locked
+ * in earlier).  Both 0 in an epoch without a repair and for a layer without redundancy; CNV layer 0 counts weights and
+ * thresholds together, the other layers thresholds.  Returns runs * E * layers * 8. */
+int bnn_mi355x_ecc_repair(unsigned int data, unsigned int check, unsigned int *out_data, unsigned int *out_check);
+size_t bnn_mi355x_pack_params_repair(const char *path, int scheme, int code, const int *records, int n_faults, void *dst,
+                                     size_t cap);
+int *bnn_mi355x_repair_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst,
+                                          int num_runs, unsigned long long seed, const unsigned int *rate_w_q32,
+                                          const unsigned int *rate_t_q32, int n_rates, int epoch_images, int scrub_every,
+                                          int repair_every, int *image_number, float *usecPerImage);
+size_t bnn_mi355x_repair_exposure_params(int scheme, int code, int burst, unsigned long long run_seed,
+                                         const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                         int epoch, int scrub_every, int repair_every, void *dst, size_t cap);
+int bnn_mi355x_last_repair_exposure_counts(long *counts, int cap);
+int bnn_mi355x_last_repair_exposure_seeds(unsigned long long *seeds, int cap);
 
 /* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
  * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column

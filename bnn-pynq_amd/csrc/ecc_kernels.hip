@@ -1,8 +1,8 @@
 // ecc_kernels.hip -- the upset kernel of the coded (SEC-DED) threshold memories in the exposure campaigns
 // (bnn_mi355x_ecc_exposure_campaigns; the code: ecc.h, the storage and the draw: mem_org.h; declared in kernels.h).
 // A translation unit of its own, for one reason: interleave_site is called here at widths 16 AND 6, and in kernels.hip
-// -- where every caller passes 16 -- that would change what the compiler makes of k_hmem_noise_t and k_xmem_noise_t
-// (measured: DESIGN.md 9).  Kept apart, every kernel body of kernels.hip is what it was.
+// -- where every caller passes 16 -- that would change what the compiler makes of k_xmem_noise_t (measured: DESIGN.md
+// 9).  Kept apart, every kernel body of kernels.hip is what it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -215,27 +215,20 @@ hipError_t mem_noise_flags(uint8_t *copies, size_t stride, int runs, const MemNo
 hipError_t mem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
                        bool signed_bb, const uint16_t *raw, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
 
-// The same upsets for a hardened memory organisation and bursts (bnn_mi355x_hardened_mem_noise_campaigns; the model:
-// mem_org.h), scheme 0 with burst 1 included.  counts: [run][nlayers][2: weights, thresholds][2], += the physical bits
-// flipped (before voting) and the logical bits that differ (after voting and de-interleaving).
-// weights of a layer >= 1 (one module, not interleaved): ebits = SIMD * wbits bits per memory word (a divisor of 64)
-hipError_t hmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
-                        int ebits, int burst, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s);
-// 16-bit thresholds: `modules` 1 or 3 (bitwise majority), `interleave` 0, 2 or 3; raw as for mem_noise_t
-hipError_t hmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
-                        bool signed_bb, const uint16_t *raw, int modules, int interleave, int burst, uint32_t rate_q32,
-                        unsigned long long *counts, int nlayers, hipStream_t s);
-
-// The same upsets spread over time (bnn_mi355x_exposure_campaigns; the model: mem_org.h): the events of `epoch` XORed
-// onto the state the earlier epochs left in the copies.  counts: this epoch's [nlayers][2][2] entries of run 0 (zeroed by
-// the caller), run q's `run_stride` longs behind: [0] += the physical bits flipped in this epoch, [1] += the logical bits
-// that differ from the loaded parameters after it, over all of the memory.
-// weights of a layer >= 1: `loaded` the loaded blob in HBM (8-byte aligned), compared word for word at the copy's offsets
+// The upsets of a memory organisation, with bursts, over epochs (bnn_mi355x_hardened_mem_noise_campaigns and the
+// *_exposure_* entry points; the model: mem_org.h), scheme 0 with burst 1 included: the events of `epoch` (bursts of `burst`
+// physical bits) XORed onto the state the earlier epochs left in the copies; a one-shot campaign is epoch 0 on zeroed
+// state.  counts: this epoch's [nlayers][2: weights, thresholds][2] entries of run 0 (zeroed by the caller), run q's
+// `run_stride` longs behind: [0] += the physical bits flipped in this epoch (before voting), [1] += the logical bits that
+// differ from the loaded parameters after it (after voting and de-interleaving), over all of the memory.
+// weights of a layer >= 1 (one module, not interleaved): ebits = SIMD * wbits bits per memory word (a divisor of 64);
+// `loaded` the loaded blob in HBM (8-byte aligned), compared word for word at the copy's offsets
 hipError_t xmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
                         int ebits, int burst, uint32_t rate_q32, int epoch, const uint8_t *loaded, unsigned long long *counts, size_t run_stride,
                         hipStream_t s);
-// 16-bit thresholds: state holds runs * rows * nthr words (run-major, lane n * nthr + i), the accumulated hit masks of the
-// modules, 16 bits each; zero where the copies hold the loaded parameters
+// 16-bit thresholds: `modules` 1 or 3 (bitwise majority), `interleave` 0, 2 or 3; raw as for mem_noise_t; state holds
+// runs * rows * nthr words (run-major, lane n * nthr + i), the accumulated hit masks of the modules, 16 bits each; zero
+// where the copies hold the loaded parameters
 hipError_t xmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
                         bool signed_bb, const uint16_t *raw, int modules, int interleave, int burst, uint32_t rate_q32, int epoch,
                         unsigned long long *state, unsigned long long *counts, size_t run_stride, hipStream_t s);

@@ -3102,138 +3102,32 @@ __global__ __launch_bounds__(kBlock) void k_mem_noise_t(uint8_t *__restrict__ co
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + ((size_t)run * nlayers + L.layer) * 2 + 1, (unsigned long long)c);
 }
 
-// The upsets of a hardened memory organisation, with bursts (bnn_mi355x_hardened_mem_noise_campaigns; the model and the
-// draw: mem_org.h).  The copies hold the LOGICAL parameters, so these kernels flip a logical bit where the physical state
-// -- interleaved words, one copy per module -- says so after voting and de-interleaving.
-// k_hmem_noise_w: weights of a layer >= 1, which no scheme replicates or interleaves: k_mem_noise_w's lanes, sites and
-// stores; what changes is the draw.  Site s is bit s % ebits of memory word s / ebits and lies in that word's group
-// (s % ebits) / burst: event e = (s / ebits) * per + group, per = ceil(ebits / burst).  e never decreases along a
-// lane's sites, so a lane computes each Philox block once, and the bits of one group share a word of it.
-template <bool TWO_BIT>
-__global__ __launch_bounds__(kBlock) void k_hmem_noise_w(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L,
-                                                         unsigned ebits, unsigned burst, const unsigned long long *__restrict__ seeds,
-                                                         unsigned rate, unsigned long long *__restrict__ counts, unsigned nlayers) {
-  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
-  unsigned c = 0;
-  if (t < L.rows * L.kw) {
-    const unsigned n = t / L.kw, k = t - n * L.kw;
-    const unsigned long long seed = seeds[run];
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), word = hardened_draw_word(0, 0, (int)burst);
-    constexpr unsigned kSites = TWO_BIT ? 128 : 64;
-    const unsigned per = (ebits + burst - 1) / burst;
-    const unsigned site0 = (((n % L.pe) * L.tmem + n / L.pe) * L.kw + k) * kSites;
-    unsigned element = site0 / ebits, bit = site0 - element * ebits, e = element * per + bit / burst, in_group = bit % burst;
-    uint32_t u[4], have = ~0u;
-    uint64_t mlo = 0, mhi = 0;  // (1-bit weights: mlo alone)
-    for (unsigned j = 0; j < kSites; j++) {
-      if ((e >> 2) != have) {
-        have = e >> 2;
-        act_noise_block(k0, k1, L.layer, word, have, u, kMemNoiseTag);
-      }
-      const uint32_t ue = (e & 2) ? ((e & 1) ? u[3] : u[2]) : ((e & 1) ? u[1] : u[0]);
-      const uint64_t hit = ue < rate ? 1ull : 0ull;
-      if (!TWO_BIT) mlo |= hit << j;
-      else if (j & 1) mhi |= hit << (j >> 1);
-      else mlo |= hit << (j >> 1);
-      if (++bit == ebits) {
-        bit = 0; in_group = 0;
-        e = ++element * per;
-      } else if (++in_group == burst) {
-        in_group = 0;
-        e++;
-      }
-    }
-    uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
-    if constexpr (!TWO_BIT) {
-      if (mlo) {
-        uint64_t *const w = reinterpret_cast<uint64_t *>(row + 2) + k;
-        *w ^= mlo;
-      }
-    } else if (mlo | mhi) {
-      uint64_t *const wq = reinterpret_cast<uint64_t *>(row + 2);
-      const uint64_t neg = wq[2 * k], nz = wq[2 * k + 1], two = wq[2 * L.kw + k];
-      const uint64_t hi = neg ^ mhi, lo = (nz & ~two) ^ mlo, two2 = hi & ~lo;
-      wq[2 * k] = hi;
-      wq[2 * k + 1] = hi | lo;
-      wq[2 * L.kw + k] = two2;
-      if (two2) atomicOr(row + 2 + 6 * L.kw, 1u);
-    }
-    c = __popcll(mlo) + __popcll(mhi);
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-  if ((threadIdx.x & 63) == 0 && c) {  // one module, no permutation: the physical flips are the logical ones
-    unsigned long long *const at = counts + ((size_t)run * nlayers + L.layer) * 4;
-    atomicAdd(at, (unsigned long long)c);
-    atomicAdd(at + 1, (unsigned long long)c);
-  }
-}
-
-// k_hmem_noise_t: thresholds of the layers whose elements are 16 bits wide.  A lane per (run, neuron n, threshold i), as
-// k_mem_noise_t.  Logical bit k of the word lives at physical (line, bit) = interleave_site(...) of the neuron's PE: its
-// own line without interleave, else its own or the partner line's word.  That physical bit's event index follows from
-// its word and group, one draw per module; mask bit k = the hit, or the majority of the three modules' hits (the voter
-// is bitwise and the stored words equal before the upsets, so the majority of the words flips exactly those bits).  The
-// word is rebuilt from the pristine raw table through packed_threshold.  A lane reads raw and writes its own row dwords
-// alone; every physical bit is counted by the lane that owns its logical image.
-__global__ __launch_bounds__(kBlock) void k_hmem_noise_t(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L, unsigned nthr,
-                                                         Arith arith, bool signed_bb, const uint16_t *__restrict__ raw, unsigned modules,
-                                                         unsigned interleave, unsigned burst, const unsigned long long *__restrict__ seeds,
-                                                         unsigned rate, unsigned long long *__restrict__ counts, unsigned nlayers) {
-  const unsigned run = blockIdx.y, t = blockIdx.x * kBlock + threadIdx.x;
-  uint32_t m = 0;
-  unsigned phys = 0;
-  if (t < L.rows * nthr) {
-    const unsigned n = t / nthr, i = t - n * nthr, mem = n % L.pe, ind = n / L.pe;
-    const unsigned long long seed = seeds[run];
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const unsigned per = (16 + burst - 1) / burst;
-    uint32_t hits[3] = {0, 0, 0}, u[3][4], have[3] = {~0u, ~0u, ~0u};  // (a module's last Philox block: bits of one line share it)
-    for (int k = 0; k < 16; k++) {
-      int p_ind, p_bit;
-      interleave_site((int)interleave, 16, (int)L.tmem, (int)ind, k, &p_ind, &p_bit);
-      const uint32_t e = ((mem * L.tmem + (unsigned)p_ind) * nthr + i) * per + (unsigned)p_bit / burst;
-#pragma unroll
-      for (unsigned md = 0; md < 3; md++) {
-        if (md >= modules) break;
-        if ((e >> 2) != have[md]) {
-          have[md] = e >> 2;
-          act_noise_block(k0, k1, L.layer, hardened_draw_word(1, (int)md, (int)burst), have[md], u[md], kMemNoiseTag);
-        }
-        const uint32_t ue = (e & 2) ? ((e & 1) ? u[md][3] : u[md][2]) : ((e & 1) ? u[md][1] : u[md][0]);
-        hits[md] |= (ue < rate ? 1u : 0u) << k;
-      }
-    }
-    phys = __popc(hits[0]) + __popc(hits[1]) + __popc(hits[2]);
-    m = modules == 3 ? ((hits[0] & hits[1]) | (hits[0] & hits[2]) | (hits[1] & hits[2])) : hits[0];
-    if (m) {
-      uint32_t *const row = reinterpret_cast<uint32_t *>(copies + (size_t)run * stride + L.offset) + (size_t)n * L.row_dwords;
-      const int32_t T = (int16_t)(uint16_t)(raw[t] ^ m);
-      const uint32_t v = (uint32_t)packed_threshold(arith, signed_bb, 64 * (int)L.kw, T);
-      row[i] = v;
-      if (nthr == 1) row[1] = v;
-    }
-  }
-  unsigned c = __popc(m);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    c += __shfl_xor(c, d, 64);
-    phys += __shfl_xor(phys, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0 && phys) {
-    unsigned long long *const at = counts + ((size_t)run * nlayers + L.layer) * 4 + 2;
-    atomicAdd(at, (unsigned long long)phys);
-    if (c) atomicAdd(at + 1, (unsigned long long)c);
-  }
-}
-
-// Exposure campaigns (bnn_mi355x_exposure_campaigns; the model: mem_org.h): the upsets of EPOCH `epoch` XORed onto the
-// physical state the earlier epochs left.  counts: this epoch's [layer][2: weights, thresholds][2] entries of run 0, run
-// q's `run_stride` longs behind; [0] += the physical bits this epoch flipped, [1] += the logical bits that now differ
-// from the loaded parameters, over ALL lanes (the caller zeroes them: every epoch has entries of its own).
-// k_xmem_noise_w: weights of a layer >= 1.  One module, no interleave: the copy itself is the state.  k_hmem_noise_w's
-// lanes, sites and stores with the epoch in the draw; the logical count compares the lane's word with the loaded blob's
-// at the same offset (2-bit weights: the (sign, low) fields).
+// The upsets of a memory ORGANISATION, with bursts, over epochs (bnn_mi355x_hardened_mem_noise_campaigns and the
+// *_exposure_* entry points; the model: mem_org.h).  The copies hold the LOGICAL parameters; the upsets are drawn on the
+// PHYSICAL state -- interleaved words, one copy per module -- and a logical bit changes where that state says so after
+// voting and de-interleaving.  A one-shot campaign is epoch 0 on zeroed state.
+// The draw: element x of a memory (words of `ebits` bits, numbered as mem_faults.h numbers them) has per = ceil(ebits /
+// burst) aligned groups of `burst` bits, the last one clipped; EVENT e = x * per + g flips group g of module m iff
+// act_noise_block(seed, layer, hardened_draw_word(target, m, burst), e >> 2, exposure_tag(epoch))[e & 3] < rate.  With
+// burst 1, e is mem_faults.h's site s = x * ebits + bit, and with module 0 and epoch 0 the counter words are the plain
+// kernels' above.  The upsets of `epoch` XOR onto what the earlier epochs left.
+// counts: this epoch's [layer][2: weights, thresholds][2] entries of run 0, run q's `run_stride` longs behind;
+// [0] += the physical bits this epoch flipped (before voting), [1] += the logical bits that now differ from the loaded
+// parameters, over ALL lanes (the caller zeroes them: every epoch has entries of its own).  A wave adds its sums with
+// one atomic per entry (no lane has left before the reduction).  No LDS.
+//
+// k_xmem_noise_w: weights of a layer >= 1, which no scheme replicates or interleaves: the copy itself is the state.  A
+// lane per 64-column word k of one (run, row n).  A neuron's weights are one contiguous run of MW * wbits sites from
+// ((n % PE) * TMEM + n / PE) * MW * wbits on (its SF memory words follow each other, fill_row), MW = 64 * kw, so the
+// lane owns sites site0 ... site0 + kSites - 1: bit s % ebits of element s / ebits, in group (s % ebits) / burst.  e
+// never decreases along them, so each Philox block is computed once and the bits of one group share a word of it.
+// 1-bit weights: 64 sites, the mask XORed into the stored u64 (the plane's polarity does not matter to a flip).  2-bit
+// weights (AR_TT): 128 sites, site 2j the low and 2j + 1 the high bit of column j's ap_int<2> field (0 -> 0, 1 -> +1,
+// 2 -> -2, 3 -> -1).  The row stores three planes -- neg (the high bit), nz (high | low) and two ("is -2": high & ~low)
+// -- so the field is read back as (neg, nz & ~two), flipped, and the planes rebuilt the way fill_row derives them; a
+// word that now holds a -2 sets the row's flag dword (k_mem_noise_flags clears it where none is left).  A lane without
+// a hit stores nothing.  The logical count compares the lane's word with the loaded blob's at the same offset (2-bit
+// weights: the (high, low) fields); one module, no permutation, so the physical flips are the hits themselves.
 template <bool TWO_BIT>
 __global__ __launch_bounds__(kBlock) void k_xmem_noise_w(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L,
                                                          unsigned ebits, unsigned burst, const unsigned long long *__restrict__ seeds,
@@ -3303,12 +3197,21 @@ __global__ __launch_bounds__(kBlock) void k_xmem_noise_w(uint8_t *__restrict__ c
   }
 }
 
-// k_xmem_noise_t: thresholds of the layers whose elements are 16 bits wide; k_hmem_noise_t's lane per (run, neuron n,
-// threshold i).  state[run * rows * nthr + lane] holds the accumulated hit masks of the (up to three) modules, 16 bits
-// each, in logical-image order as hits[md] there: bit k is the physical bit interleave_site gives for logical bit k -- so
-// no lane depends on another's state.  The lane draws the epoch's hits, XORs them into the state (stored only when
-// something changed), votes, and where the voted mask differs from the one before rebuilds its row dword(s) from the
-// pristine raw table.  A scrub zeroes the state and restores the copies.
+// k_xmem_noise_t: thresholds of the layers whose elements are 16 bits wide.  A lane per (run, neuron n, threshold i),
+// element x = ((n % PE) * TMEM + n / PE) * nthr + i.  Logical bit k of the word lives at physical (line, bit) =
+// interleave_site(...) of the neuron's PE: its own line without interleave, else its own or the partner line's word;
+// that physical bit's event index follows from its word and group, one draw per module (a module's last Philox block
+// is kept: bits of one line share it).  Every physical bit is drawn and counted by the lane that owns its logical image.
+// The STATE WORD state[run * rows * nthr + lane] holds the accumulated hit masks of the (up to three) modules, 16 bits
+// each from bit 0, 16 and 32, in logical-image order: bit k of a mask is the physical bit interleave_site gives for
+// logical bit k -- so no lane depends on another's state.  Zero means the loaded parameters: what the caller's memset
+// leaves before epoch 0 and at a scrub, which also restores the copies.  The lane XORs the epoch's hits into the state
+// (stored only when something was hit) and takes the logical mask: module 0's, or with three modules their bitwise
+// majority (the voter is bitwise and the modules are loaded equal, so the majority of the words flips exactly those
+// bits).  Where that mask differs from the one before, the raw 16-bit word (raw[n * nthr + i], from the loaded
+// memories) is XORed with it, sign-extended and stored as the row's dword t_i through packed_threshold, fill_row's own
+// transform (both dwords for a layer with one threshold).  A lane reads raw and writes its own state word and row
+// dwords alone.
 __global__ __launch_bounds__(kBlock) void k_xmem_noise_t(uint8_t *__restrict__ copies, unsigned long long stride, MemNoiseLayer L, unsigned nthr,
                                                          Arith arith, bool signed_bb, const uint16_t *__restrict__ raw, unsigned modules,
                                                          unsigned interleave, unsigned burst, const unsigned long long *__restrict__ seeds,
@@ -4138,36 +4041,6 @@ hipError_t mem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned 
   const dim3 g((L.rows * (unsigned)nthr + kBlock - 1) / kBlock, (unsigned)runs);
   hipLaunchKernelGGL(k_mem_noise_t, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)nthr, arith, signed_bb, raw, seeds, rate_q32,
                      counts, (unsigned)nlayers);
-  return hipGetLastError();
-}
-
-hipError_t hmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
-                        int ebits, int burst, uint32_t rate_q32, unsigned long long *counts, int nlayers, hipStream_t s) {
-  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
-  if (runs > 65535 || L.kw == 0 || L.rows == 0 || stride % 256 || L.offset % 8 || L.row_dwords % 2 ||
-      L.row_dwords < (two_bit ? 4 + 6 * L.kw : 2 + 2 * L.kw) || ebits < 1 || ebits > 64 || 64 % ebits || burst < 1 || burst > kMaxBurst)
-    return hipErrorInvalidValue;
-  const dim3 g((L.rows * L.kw + kBlock - 1) / kBlock, (unsigned)runs);
-  if (two_bit)
-    hipLaunchKernelGGL(k_hmem_noise_w<true>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)ebits, (unsigned)burst, seeds,
-                       rate_q32, counts, (unsigned)nlayers);
-  else
-    hipLaunchKernelGGL(k_hmem_noise_w<false>, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)ebits, (unsigned)burst, seeds,
-                       rate_q32, counts, (unsigned)nlayers);
-  return hipGetLastError();
-}
-
-hipError_t hmem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, int nthr, Arith arith,
-                        bool signed_bb, const uint16_t *raw, int modules, int interleave, int burst, uint32_t rate_q32,
-                        unsigned long long *counts, int nlayers, hipStream_t s) {
-  if (runs <= 0 || rate_q32 == 0) return hipSuccess;
-  if (runs > 65535 || L.rows == 0 || stride % 256 || L.offset % 4 || nthr < 1 || nthr > 2 || L.row_dwords < 2 || arith == AR_INT8 || !raw ||
-      (modules != 1 && modules != 3) || (interleave != 0 && interleave != HS_INTERLEAVED && interleave != HS_RESILIENT) || burst < 1 ||
-      burst > kMaxBurst || L.pe == 0 || L.rows != L.pe * L.tmem)
-    return hipErrorInvalidValue;
-  const dim3 g((L.rows * (unsigned)nthr + kBlock - 1) / kBlock, (unsigned)runs);
-  hipLaunchKernelGGL(k_hmem_noise_t, g, dim3(kBlock), 0, s, copies, (unsigned long long)stride, L, (unsigned)nthr, arith, signed_bb, raw,
-                     (unsigned)modules, (unsigned)interleave, (unsigned)burst, seeds, rate_q32, counts, (unsigned)nlayers);
   return hipGetLastError();
 }
 

@@ -73,7 +73,7 @@ BNN_HD inline uint32_t hardened_draw_word(int target, int module, int burst) {
 }
 
 // Logical -> physical: bit `bit` of the T-bit element in line `ind` (of `lines` lines of one PE) is stored in line
-// *p_ind at bit *p_bit.  il 0: the identity.  Shared by the host model and the kernel (k_hmem_noise_t).
+// *p_ind at bit *p_bit.  il 0: the identity.  Shared by the host model and the kernels (k_xmem_noise_t, k_emem_noise_t).
 BNN_HD inline void interleave_site(int il, int T, int lines, int ind, int bit, int *p_ind, int *p_bit) {
   const int a = ind & ~1;
   if (il == 0 || a + 1 >= lines) {

@@ -87,7 +87,7 @@ static_assert(sizeof(PackedHeader) == 32 + 9 * 16, "blob header layout");
 uint32_t row_dwords_for(const LayerSpec &L);
 
 // Dword t_i of a row from the threshold T_i as the files hold it (the table above): what fill_row stores, and what the
-// kernel that upsets threshold words in place (kernels.hip, k_mem_noise_t) stores again from the upset word.
+// kernels that upset threshold words in place (kernels.hip, k_mem_noise_t, k_xmem_noise_t) store again from the upset word.
 #ifndef BNN_HD
 #define BNN_HD
 #endif

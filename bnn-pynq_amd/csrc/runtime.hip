@@ -1766,6 +1766,13 @@ int *classify_host(const uint8_t *imgs, int n, int ncls, float *usec, int enable
                        enable_detail);
 }
 
+// a bnn_mi355x_last_* getter: the first `cap` values into the caller's array (which may be null); returns how many there are
+template <class T>
+int copy_out(const std::vector<T> &v, T *out, int cap) {
+  for (int i = 0; out && i < cap && i < (int)v.size(); i++) out[i] = v[(size_t)i];
+  return (int)v.size();
+}
+
 }  // namespace
 }  // namespace bnn
 
@@ -3200,27 +3207,27 @@ long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigne
 
 // the argument checks of both entry points, then what every parameter-fault entry point refuses; nothing touches a device
 // before they have passed (ready() is the first thing that may)
-// hz: the hardened entry points (mem_org.h) -- the scheme is an argument there, so they are the same in a variant's library
+// hz: the memory organisation (mem_org.h) -- the plain entry points pass scheme 0 with burst 1, which every network has
 // code: the SEC-DED axis of bnn_mi355x_ecc_exposure_campaigns (ecc.h); 0 everywhere else
+// base_only: a variant's library refuses the entry point (the plain ones: the organisation is the variant's there, not
+// an argument; where the scheme is an argument the call is the same in a variant's library)
 struct Hardening { int scheme, burst, code = 0; };
 
-static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
-                           const Hardening *hz = nullptr) {
+static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, const Hardening &hz,
+                           bool base_only) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  if (hz) {
-    if (hz->burst < 1 || hz->burst > kMaxBurst) return fail(std::string(who) + ": burst must be 1 ... " + std::to_string(kMaxBurst));
-    EccOrg org;
-    const std::string e = ecc_layout(net, hz->scheme, hz->code, 0, org);
-    if (!e.empty()) return fail(std::string(who) + ": " + e);
-  }
+  if (hz.burst < 1 || hz.burst > kMaxBurst) return fail(std::string(who) + ": burst must be 1 ... " + std::to_string(kMaxBurst));
+  EccOrg org;
+  const std::string e = ecc_layout(net, hz.scheme, hz.code, 0, org);
+  if (!e.empty()) return fail(std::string(who) + ": " + e);
   if (!rate_w_q32 || !rate_t_q32 || n_rates != net.nlayers)
     return fail(std::string(who) + ": bad arguments (a rate array missing, or n_rates is not " + std::to_string(net.nlayers) + ": one rate per layer)");
   for (int l = 0; l < net.nlayers; l++)
     if (rate_t_q32[l] != 0 && net.L[l].nthr == 0)
       return fail(std::string(who) + ": layer " + std::to_string(l) + " has no threshold memory (its threshold rate must be 0)");
 #ifdef BNN_VARIANT
-  if (!hz) return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
+  if (base_only) return fail("fault injection is not modelled for " BNN_VARIANT " (replicated / interleaved parameter memories); use the base network");
 #endif
   if (!ready()) return -1;
   if (r.raw.empty()) return fail("fault injection needs the parameter files (load_parameters), not an imported blob");
@@ -3231,13 +3238,13 @@ static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, cons
 
 // What the host prepares for the runs' copies: the patches of layer 0 of the CNV nets (int8 taps, 24-bit thresholds that
 // apply_fault reads back as their integer part, three table forms: drawn and applied here, fault_campaigns' way) and the raw
-// 16-bit threshold words of the layers whose threshold rate is not 0, for k_mem_noise_t.
+// 16-bit threshold words of the layers whose threshold rate is not 0, for the threshold kernels.
 struct MemNoiseJob {
   size_t stride = 0, spans_off = 0, tab_off[9] = {};
   int nspans = 0;
   std::vector<uint8_t> upload;                  // patch bytes | patch spans | threshold tables
-  std::vector<unsigned long long> host_counts;  // [run][layer][2]: the flips the host applied ([2][2] with a Hardening)
-  // exposure campaigns: host_counts is [run][epoch][layer][2][2]; the spans are ordered by epoch, epoch t's being
+  std::vector<unsigned long long> host_counts;  // [run][layer][2]: the flips the host applied (the plain route)
+  // the exposure path: host_counts is [run][epoch][layer][2][2]; the spans are ordered by epoch, epoch t's being
   // span_first[t] ... span_first[t + 1] - 1; k_xmem_noise_t's state of layer l (runs * rows * nthr words) lies at
   // state_off[l] of d_camp, all of them in [state_begin, state_begin + state_bytes)
   std::vector<int> span_first;
@@ -3248,12 +3255,11 @@ struct MemNoiseJob {
 
 // Layer 0 of one run through the physical model (mem_org.h): the events of every module applied to `phys` in order, the
 // logical memories voted and de-interleaved into raw.w[0] / raw.t[0], the rows whose words now differ from the loaded ones
-// marked.  counts: [2: weights, thresholds][2: physical bits flipped, logical bits that differ].  `phys` comes back as loaded.
-// The exposure campaigns step one state through their epochs: the events are those of `epoch`, and with `keep` phys
-// stays as the events left it.  Without an event nothing but `touched` (cleared) is written: the logical state is the
-// one phys had, which the caller knows.
-static int hardened_layer0(const Hardening &hz, unsigned long long seed, const unsigned int rate[2], const PhysParams &loaded, PhysParams &phys,
-                           RawParams &raw, std::vector<char> &touched, unsigned long long counts[4], int epoch = 0, bool keep = false) {
+// marked.  counts: [2: weights, thresholds][2: physical bits flipped, logical bits that differ].
+// One state is stepped through the epochs: the events are those of `epoch`, and phys stays as they left it.  Without an
+// event nothing but `touched` (cleared) is written: the logical state is the one phys had, which the caller knows.
+static int hardened_layer0(const Hardening &hz, unsigned long long seed, const unsigned int rate[2], PhysParams &phys, RawParams &raw,
+                           std::vector<char> &touched, unsigned long long counts[4], int epoch) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const LayerSpec &L = net.L[0];
@@ -3296,24 +3302,21 @@ static int hardened_layer0(const Hardening &hz, unsigned long long seed, const u
         touched[(target ? ind : ind / (size_t)(L.fold.wmem / L.fold.tmem)) * (size_t)L.fold.pe + pe] = 1;
       }
   }
-  for (int m = 0; m < 3 && !keep; m++) {
-    phys.mod[m].w[0] = loaded.mod[m].w[0];
-    phys.mod[m].t[0] = loaded.mod[m].t[0];
-  }
   return 0;
 }
 
 static void mem_noise_upload(const std::vector<uint8_t> &staging, const std::vector<PatchSpan> &spans, const unsigned int *rth, MemNoiseJob &job);
 
-static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, MemNoiseJob &job,
-                             const Hardening *hz = nullptr) {
+// The plain route (bnn_mi355x_mem_noise_campaigns, _mem_noise_params): independent single-bit flips of the memories as
+// loaded, all of them in place before the first image.  Layer 0 of the CNV nets: mem_noise_mask's flips through apply_fault.
+static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, MemNoiseJob &job) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const int R = (int)seeds.size(), S = net.nlayers;
   PackedHeader h;
   std::memcpy(&h, r.blob.data(), sizeof(h));
   job.stride = (r.blob.size() + 255) & ~(size_t)255;
-  job.host_counts.assign((size_t)R * S * (hz ? 4 : 2), 0);
+  job.host_counts.assign((size_t)R * S * 2, 0);
   std::vector<uint8_t> staging;
   std::vector<PatchSpan> spans;
   if (net.L[0].arith == AR_INT8 && (rw[0] || rth[0])) {
@@ -3326,20 +3329,9 @@ static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const
     const size_t rb = (size_t)h.layer[0].row_dwords * 4, rows_bytes = rb * h.layer[0].rows;
     std::vector<Fault> flips;
     std::vector<char> touched(h.layer[0].rows);
-    PhysParams loaded, phys;
-    if (hz) {
-      phys_load(net, hz->scheme, r.raw, 0, 1, loaded);
-      phys = loaded;
-    }
     for (int q = 0; q < R; q++) {
       flips.clear();
-      bool changed = false;
-      if (hz) {
-        const unsigned int rate[2] = {rw[0], rth[0]};
-        if (hardened_layer0(*hz, seeds[(size_t)q], rate, loaded, phys, raw, touched, &job.host_counts[(size_t)q * S * 4])) return -1;
-        for (char c : touched) changed = changed || c;
-      }
-      for (int target = 0; target < 2 && !hz; target++) {
+      for (int target = 0; target < 2; target++) {
         const uint32_t rate = target ? rth[0] : rw[0];
         const long k = mem_noise_mask(net, seeds[(size_t)q], 0, target, rate, 0, nullptr, 0);
         const size_t at = flips.size();
@@ -3347,8 +3339,8 @@ static int mem_noise_prepare(const std::vector<unsigned long long> &seeds, const
         mem_noise_mask(net, seeds[(size_t)q], 0, target, rate, 0, flips.data() + at, k);
         job.host_counts[((size_t)q * S + 0) * 2 + target] = (unsigned long long)k;
       }
-      if (hz ? !changed : flips.empty()) continue;
-      if (!hz) std::fill(touched.begin(), touched.end(), 0);
+      if (flips.empty()) continue;
+      std::fill(touched.begin(), touched.end(), 0);
       for (const Fault &f : flips) {
         const int row = apply_fault(net, raw, f);
         if (row < 0 || row >= (int)h.layer[0].rows) return fail("internal: mem_noise flip outside layer 0");
@@ -3417,11 +3409,11 @@ static int replicate_blob(int R, size_t stride) {
   return 0;
 }
 
-// Enqueues on r.stream: one copy of the loaded blob per seed in r.d_copies (replicated by doubling), the host's layer-0
-// patches scattered over them, then the upset kernels layer by layer, weights before thresholds.  d_noise holds the seeds
-// and, at counts_off, the zeroed [run][layer][2] counters.  `seeds` and `job` must outlive the stream's work.
+// The plain route, enqueued on r.stream: one copy of the loaded blob per seed in r.d_copies (replicated by doubling), the
+// host's layer-0 patches scattered over them, then the upset kernels layer by layer, weights before thresholds.  d_noise
+// holds the seeds and, at counts_off, the zeroed [run][layer][2] counters.  `seeds` and `job` must outlive the stream's work.
 static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, const MemNoiseJob &job,
-                             size_t counts_off, const Hardening *hz = nullptr) {
+                             size_t counts_off) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const int R = (int)seeds.size(), S = net.nlayers;
@@ -3429,12 +3421,12 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
   std::memcpy(&h, r.blob.data(), sizeof(h));
   const size_t stride = job.stride;
   if (grow(r.d_copies, r.copies_cap, (size_t)R * stride) || grow(r.d_camp, r.camp_cap, job.upload.size() + 256) ||
-      grow(r.d_noise, r.noise_cap, counts_off + (size_t)R * S * (hz ? 4 : 2) * 8))
+      grow(r.d_noise, r.noise_cap, counts_off + (size_t)R * S * 2 * 8))
     return -1;
   const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
   unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
   HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
-  HIP_OK(hipMemsetAsync(d_counts, 0, (size_t)R * S * (hz ? 4 : 2) * 8, r.stream));
+  HIP_OK(hipMemsetAsync(d_counts, 0, (size_t)R * S * 2 * 8, r.stream));
   if (replicate_blob(R, stride)) return -1;
   if (!job.upload.empty()) HIP_OK(hipMemcpyAsync(r.d_camp, job.upload.data(), job.upload.size(), hipMemcpyHostToDevice, r.stream));
   hipError_t e = scatter_patches(r.d_camp, reinterpret_cast<const PatchSpan *>(r.d_camp + job.spans_off), job.nspans, r.d_copies, r.stream);
@@ -3442,26 +3434,23 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
     const LayerSpec &L = net.L[l];
     if (L.arith == AR_INT8) continue;  // (the host's part)
     const MemNoiseLayer ml{h.layer[l].offset, h.layer[l].row_dwords, h.layer[l].rows, h.layer[l].kw, (uint32_t)L.fold.pe, (uint32_t)L.fold.tmem, (uint32_t)l};
-    MemOrg org{1, 1, 0};
-    if (hz) hardening_layout(net, hz->scheme, l, org);  // (checked by mem_noise_check; weights of a layer >= 1 have one module)
-    e = hz ? hmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz->burst, rw[l], d_counts, S, r.stream)
-           : mem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, rw[l], d_counts, S, r.stream);
+    e = mem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, rw[l], d_counts, S, r.stream);
     // the loaded parameters hold -2 rows already: a flip may have removed the last -2 of a row
     if (e == hipSuccess && L.arith == AR_TT && rw[l] && r.two_rows > 0) e = mem_noise_flags(r.d_copies, stride, R, ml, r.stream);
-    const uint16_t *const tab = reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]);
     if (e == hipSuccess && rth[l])
-      e = hz ? hmem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, tab, org.t_modules, org.t_interleave, hz->burst,
-                            rth[l], d_counts, S, r.stream)
-             : mem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, tab, rth[l], d_counts, S, r.stream);
+      e = mem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
+                      rth[l], d_counts, S, r.stream);
   }
   if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
   return 0;
 }
 
-// ---- exposure campaigns: upsets that accumulate over epochs, with scrubbing (the model: mem_org.h) -------------------------
+// ---- the exposure path: upsets of a memory organisation that accumulate over epochs, with scrubbing (the model: mem_org.h) --
+// The hardened one-shot campaign (bnn_mi355x_hardened_mem_noise_campaigns) is one epoch that is never scrubbed: epoch 0's
+// tag is kMemNoiseTag, and its upsets meet zeroed state.
 
-// longs: the counters per (run, epoch, layer) the caller is handed -- 4, or 6 on the coded route (the ecc entry points, with
-// code 0 as well), whose last_* state is its own, or 8 on the repair route (likewise its own; with repair_every 0 as well)
+// longs: the counters per (run, epoch, layer) on the device -- 4, or 6 on the coded route (the ecc entry points, with
+// code 0 as well), or 8 on the repair route (with repair_every 0 as well)
 // repair_every: the repair scrub of mem_org.h ("repair scrubs"); 0 never
 struct Exposure { int epoch_images, scrub_every, longs = 4, repair_every = 0; };
 
@@ -3471,9 +3460,9 @@ static bool exposure_repairs(const Exposure &ex, int t) { return exposure_repair
 // What the host prepares for E epochs.  Layer 0 of the CNV nets: one persistent physical working state per run is stepped
 // through the epochs by hardened_layer0, scrubs included (the draw is deterministic, so all of it is known before anything
 // is enqueued); the rows and tables an epoch changes become that epoch's patches.  A row is rebuilt where its words differ from the loaded
-// ones now or did so after the epoch before (it may have returned to them).  Then mem_noise_prepare's tables, and the
-// layout of the threshold state.
-static int exposure_prepare(const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, int E,
+// ones now or did so after the epoch before (it may have returned to them).  Then the threshold tables (mem_noise_upload),
+// and the layout of the threshold state.
+static int exposure_prepare(const char *who, const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, int E,
                             const Exposure &ex, const Hardening &hz, MemNoiseJob &job) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
@@ -3513,7 +3502,7 @@ static int exposure_prepare(const std::vector<unsigned long long> &seeds, const 
           job.host_repairs[(((size_t)q * E + t) * S + 0) * 2] = (unsigned long long)rc[0][0];
           job.host_repairs[(((size_t)q * E + t) * S + 0) * 2 + 1] = (unsigned long long)rc[0][1];
         }
-        if (hardened_layer0(hz, seeds[(size_t)q], rate, loaded, phys, raw, touched, counts, t, true)) return -1;
+        if (hardened_layer0(hz, seeds[(size_t)q], rate, phys, raw, touched, counts, t)) return -1;
         if (counts[0] + counts[2] == 0) {  // no event: nothing to patch; without a scrub the logical state is the last epoch's
           if (!scrub && t > 0) {
             counts[1] = counts[1 - S * 4];
@@ -3537,7 +3526,7 @@ static int exposure_prepare(const std::vector<unsigned long long> &seeds, const 
           add_span(h.l0_mfma_offset, kL0MfmaBytes);
         }
         before = touched;
-        if (staging.size() > 0xFFFF0000u) return fail("exposure: too many layer-0 patches for one call (staging above 4 GB)");
+        if (staging.size() > 0xFFFF0000u) return fail(std::string(who) + ": too many layer-0 patches for one call (staging above 4 GB)");
       }
     }
   }
@@ -3564,7 +3553,7 @@ static int exposure_prepare(const std::vector<unsigned long long> &seeds, const 
 // d_noise, the runs' copies of the loaded blob, the job's upload and the zeroed threshold state.
 // longs 6: the [run][epoch][layer][2] decode-status counters of k_emem_noise_t lie behind the others; longs 8: behind
 // those, the [run][epoch][layer][2] counters of k_repair_state.
-static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, int E, int longs = 4) {
+static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, int E, int longs) {
   Runtime &r = rt();
   const int R = (int)seeds.size(), S = r.spec.nlayers;
   const size_t counts_bytes = (size_t)R * E * S * (size_t)longs * 8;
@@ -3640,30 +3629,42 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
   return 0;
 }
 
-// Random upsets of the parameter memories, many runs in one call.  Every run gets a copy of the loaded blob in HBM with its
-// upsets applied in place (mem_noise_enqueue); the (run, image) pairs then go in run-major order, in groups of at most one
-// activation workspace, through the multi-run stages with the copy stride: act_noise_campaigns' grouping with
-// fault_campaigns' copies.  kMaxRuns copies are what fault_campaigns holds as well, so a call's runs always fit.
-// hz null: bnn_mi355x_mem_noise_campaigns; else the hardened form, whose counters have two entries per (layer, target).
-// ex (with hz): bnn_mi355x_exposure_campaigns -- the images go epoch by epoch, each epoch's scrub and upsets enqueued in
-// front of its pairs (exposure_epoch), and the counters have one [layer][2][2] block per (run, epoch).
-static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const char *path, int number_class, int num_runs, unsigned long long seed,
-                                     const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
-                                     float *usecPerImage, const Exposure *ex = nullptr) {
+// What is an entry point's own: everything else is the same call.
+struct MemNoiseEntry {
+  const char *who;                                  // its name in every refusal
+  std::vector<long> Runtime::*counts;               // its bnn_mi355x_last_*_counts
+  std::vector<unsigned long long> Runtime::*seeds;  // and bnn_mi355x_last_*_seeds
+  bool one_epoch = false;      // no epoch arguments: the whole file is ONE epoch (an empty file as well), never scrubbed
+  bool base_only = false;      // a variant's library refuses it (mem_noise_check)
+  bool plain = false;          // the plain route (mem_noise_prepare, mem_noise_enqueue): its counters are [run][layer][2]
+  bool file_first = false;     // the file is opened and its epochs are counted before mem_noise_check
+};
+
+// Random upsets of the parameter memories, many runs in one call.  Every run gets a copy of the loaded blob in HBM; the images
+// go epoch by epoch, each epoch's scrub and upsets enqueued in front of its pairs and applied to the copies in place
+// (exposure_epoch; the plain route: all of it in front of the one epoch's pairs, mem_noise_enqueue); an epoch's (run, image)
+// pairs go in run-major order, in groups of at most one activation workspace, through the multi-run stages with the copy
+// stride: act_noise_campaigns' grouping with fault_campaigns' copies.  kMaxRuns copies are what fault_campaigns holds as
+// well, so a call's runs always fit.  The counters have one [layer][2][2] block per (run, epoch), with ex.longs 6 / 8 two
+// decode-status / and two repair counters per (run, epoch, layer) behind them; the plain route's are [run][layer][2].
+static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &hz, const Exposure &ex, const char *path, int number_class,
+                                     int num_runs, unsigned long long seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32,
+                                     int n_rates, int *image_number, float *usecPerImage) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  const bool eight = ex && ex->longs == 8;       // the repair route: two repair counters behind the six
-  const bool six = eight || (ex && ex->longs == 6);  // the coded route: two decode-status counters behind the four
-  std::vector<long> &last_counts = eight ? r.rmem_counts : six ? r.emem_counts : ex ? r.xmem_counts : (hz ? r.hmem_noise_counts : r.mem_noise_counts);
-  std::vector<unsigned long long> &last_seeds = eight ? r.rmem_seeds : six ? r.emem_seeds : ex ? r.xmem_seeds : (hz ? r.hmem_noise_seeds : r.mem_noise_seeds);
+  const char *const who = en.who;
+  const bool eight = ex.longs == 8;        // the repair route: two repair counters behind the six
+  const bool six = eight || ex.longs == 6;  // the coded route: two decode-status counters behind the four
+  std::vector<long> &last_counts = r.*en.counts;
+  std::vector<unsigned long long> &last_seeds = r.*en.seeds;
   last_counts.clear();
   last_seeds.clear();
   const int S = net.nlayers;
-  if (ex && (ex->epoch_images < 1 || ex->scrub_every < 0)) {
+  if (!en.one_epoch && (ex.epoch_images < 1 || ex.scrub_every < 0)) {
     fail(std::string(who) + ": epoch_images must be at least 1 and scrub_every must not be negative (0: never scrub)");
     return nullptr;
   }
-  if (ex && ex->repair_every < 0) {
+  if (ex.repair_every < 0) {
     fail(std::string(who) + ": repair_every must not be negative (0: never repair)");
     return nullptr;
   }
@@ -3683,24 +3684,23 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
   ImageFile f;
   // the epochs a file implies, refused where they or their counters are too many; `false` once that is known not to be so
   auto too_many_epochs = [&]() -> bool {
-    const long long images = (long long)f.n, per = ex ? ex->epoch_images : std::max<long long>(images, 1), epochs = (images + per - 1) / per;
-    if (!ex || (epochs <= kMaxEpochs && (unsigned long long)R * (unsigned long long)epochs * S * (unsigned)ex->longs <= 0x7FFFFFFFull)) return false;
+    const long long epochs = en.one_epoch ? 1 : ((long long)f.n + ex.epoch_images - 1) / ex.epoch_images;
+    if (epochs <= kMaxEpochs && (unsigned long long)R * (unsigned long long)epochs * S * (unsigned)ex.longs <= 0x7FFFFFFFull) return false;
     fail(std::string(who) + ": " + std::to_string(epochs) + " epochs: at most " + std::to_string(kMaxEpochs) +
-         ", and num_runs * epochs * layers * " + std::to_string(ex->longs) + " counters must stay below 2^31");
+         ", and num_runs * epochs * layers * " + std::to_string(ex.longs) + " counters must stay below 2^31");
     return true;
   };
-  // (the repair route refuses every argument before a device is looked for -- mem_noise_check ends with ready(), the first
-  // thing that may touch one -- and the file's size is known without a device; the other routes keep the order they had)
-  if (eight && (open_image_file(path, f) || too_many_epochs())) return nullptr;
-  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz)) return nullptr;
-  if (!eight && open_image_file(path, f)) return nullptr;
+  // (file_first, the repair entry point: every argument is refused before a device is looked for -- mem_noise_check ends with
+  // ready(), the first thing that may touch one -- and the file's size is known without a device; the others keep the order they had)
+  if (en.file_first && (open_image_file(path, f) || too_many_epochs())) return nullptr;
+  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz, en.base_only)) return nullptr;
+  if (!en.file_first && open_image_file(path, f)) return nullptr;
   const int n = (int)f.n;
   const size_t total = (size_t)R * n;
   const bool cnv = net.is_cnv;
-  const int ei = ex ? ex->epoch_images : std::max(n, 1);  // images per epoch; without ex the call is one epoch
-  const long long epochs = ((long long)n + ei - 1) / ei;
-  if (!eight && too_many_epochs()) return nullptr;  // (the repair route: checked above)
-  const int E = (int)epochs;
+  const int ei = en.one_epoch ? std::max(n, 1) : ex.epoch_images;  // images per epoch
+  if (!en.file_first && too_many_epochs()) return nullptr;
+  const int E = en.one_epoch ? 1 : (int)(((long long)n + ei - 1) / ei);
   std::vector<unsigned long long> seeds((size_t)R);
   {
     std::random_device rd;
@@ -3717,14 +3717,14 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
   }
   int *result = new (std::nothrow) int[total + 1];
   if (!result) { fail("out of memory"); return nullptr; }
-  std::vector<unsigned long long> counts((size_t)R * (ex ? E : 1) * S * (hz ? 4 : 2), 0);
+  std::vector<unsigned long long> counts((size_t)R * E * S * (en.plain ? 2 : 4), 0);
   std::vector<unsigned long long> status(six ? (size_t)R * E * S * 2 : 0, 0);  // (the coded route: [run][epoch][layer][2])
   std::vector<unsigned long long> repairs(eight ? (size_t)R * E * S * 2 : 0, 0);  // (the repair route: likewise)
   MemNoiseJob job;
   double device_us = 0.0;
   auto run = [&]() -> int {
     if (n == 0) return 0;
-    if (any && (ex ? exposure_prepare(seeds, rate_w_q32, rate_t_q32, E, *ex, *hz, job) : mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job, hz)))
+    if (any && (en.plain ? mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job) : exposure_prepare(who, seeds, rate_w_q32, rate_t_q32, E, ex, hz, job)))
       return -1;
     size_t cap = std::min<size_t>(kMaxChunk, total);  // pairs per group: the activation workspace
     if (const char *e = std::getenv("BNN_MI355X_NOISE_GROUP")) {  // tests: many small groups
@@ -3771,15 +3771,16 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
     }
     // -- all of it on one stream, one wait at the end
     HIP_OK(hipEventRecord(r.time_events[0], r.stream));
-    if (any && (ex ? exposure_begin(seeds, job, counts_off, E, ex->longs) : mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off, hz))) return -1;
+    if (any && (en.plain ? mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off) : exposure_begin(seeds, job, counts_off, E, ex.longs)))
+      return -1;
     // (all rates 0: no copy is made, every run reads the loaded blob)
     const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
     const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
     HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
-    int entered = -1;  // (exposure) the last epoch whose scrub and upsets are in the stream
+    int entered = -1;  // the last epoch whose scrub and upsets are in the stream
     for (const Group &g : groups) {
-      for (; ex && any && entered < g.epoch; entered++)
-        if (exposure_epoch(entered + 1, R, rate_w_q32, rate_t_q32, job, counts_off, E, *ex, *hz)) return -1;
+      for (; !en.plain && any && entered < g.epoch; entered++)
+        if (exposure_epoch(entered + 1, R, rate_w_q32, rate_t_q32, job, counts_off, E, ex, hz)) return -1;
       MultiLaunch a{};
       a.images = r.d_all;
       a.segs = d_segs + g.seg0;
@@ -3839,21 +3840,15 @@ static int *mem_noise_campaigns_impl(const char *who, const Hardening *hz, const
 int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_runs, unsigned long long seed,
                                     const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
                                     float *usecPerImage) {
-  return mem_noise_campaigns_impl("mem_noise_campaigns", nullptr, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number,
-                                  usecPerImage);
+  // independent single-bit flips of the memories as loaded (no scheme, burst 1), by the plain route
+  const MemNoiseEntry en{"mem_noise_campaigns", &Runtime::mem_noise_counts, &Runtime::mem_noise_seeds, true, true, true};
+  return mem_noise_campaigns_impl(en, Hardening{HS_NONE, 1}, Exposure{0, 0}, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates,
+                                  image_number, usecPerImage);
 }
 
-int bnn_mi355x_last_mem_noise_counts(long *flips, int cap) {
-  const std::vector<long> &c = rt().mem_noise_counts;
-  for (int i = 0; flips && i < cap && i < (int)c.size(); i++) flips[i] = c[(size_t)i];
-  return (int)c.size();
-}
+int bnn_mi355x_last_mem_noise_counts(long *flips, int cap) { return copy_out(rt().mem_noise_counts, flips, cap); }
 
-int bnn_mi355x_last_mem_noise_seeds(unsigned long long *seeds, int cap) {
-  const std::vector<unsigned long long> &k = rt().mem_noise_seeds;
-  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
-  return (int)k.size();
-}
+int bnn_mi355x_last_mem_noise_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().mem_noise_seeds, seeds, cap); }
 
 long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int target, unsigned int rate_q32, long first, int *records,
                                int cap_records) {
@@ -3873,30 +3868,26 @@ long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int targe
   return total;
 }
 
-static size_t mem_noise_params_impl(const char *who, const Hardening *hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
-                                    const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap) {
+size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                   void *dst, size_t cap) {
+  const char *const who = "mem_noise_params";
   Runtime &r = rt();
-  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz)) return 0;
+  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, Hardening{HS_NONE, 1}, true)) return 0;
   if (!dst) return r.blob.size();
   if (cap < r.blob.size()) { fail(std::string(who) + ": destination too small"); return 0; }
   const std::vector<unsigned long long> seeds(1, run_seed);
   MemNoiseJob job;
   auto run = [&]() -> int {
-    if (mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job, hz)) return -1;
+    if (mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job)) return -1;
     DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
     if (settle_handover(r.stream)) return -1;
-    if (mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, 256, hz)) return -1;
+    if (mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, 256)) return -1;
     HIP_OK(hipMemcpyAsync(dst, r.d_copies, r.blob.size(), hipMemcpyDeviceToHost, r.stream));
     HIP_OK(hipStreamSynchronize(r.stream));
     drain.ok();
     return 0;
   };
   return run() < 0 ? 0 : r.blob.size();
-}
-
-size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
-                                   void *dst, size_t cap) {
-  return mem_noise_params_impl("mem_noise_params", nullptr, run_seed, rate_w_q32, rate_t_q32, n_rates, dst, cap);
 }
 
 // ---- hardened memory schemes in the memory upset campaigns (the model: mem_org.h) ------------------------------------------
@@ -3977,28 +3968,24 @@ size_t bnn_mi355x_pack_params_hardened(const char *path, int scheme, const int *
 int *bnn_mi355x_hardened_mem_noise_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs, unsigned long long seed,
                                              const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int *image_number,
                                              float *usecPerImage) {
-  const Hardening hz{scheme, burst};
-  return mem_noise_campaigns_impl("hardened_mem_noise_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates,
-                                  image_number, usecPerImage);
+  const MemNoiseEntry en{"hardened_mem_noise_campaigns", &Runtime::hmem_noise_counts, &Runtime::hmem_noise_seeds, true};
+  return mem_noise_campaigns_impl(en, Hardening{scheme, burst}, Exposure{0, 0}, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32,
+                                  n_rates, image_number, usecPerImage);
 }
 
+static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                   const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap,
+                                   int repair_every = -1);
+
+// (epoch 0 of a state that is never scrubbed)
 size_t bnn_mi355x_hardened_mem_noise_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
                                             const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap) {
-  const Hardening hz{scheme, burst};
-  return mem_noise_params_impl("hardened_mem_noise_params", &hz, run_seed, rate_w_q32, rate_t_q32, n_rates, dst, cap);
+  return exposure_params_impl("hardened_mem_noise_params", Hardening{scheme, burst}, run_seed, rate_w_q32, rate_t_q32, n_rates, 0, 0, dst, cap);
 }
 
-int bnn_mi355x_last_hardened_mem_noise_counts(long *counts, int cap) {
-  const std::vector<long> &c = rt().hmem_noise_counts;
-  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
-  return (int)c.size();
-}
+int bnn_mi355x_last_hardened_mem_noise_counts(long *counts, int cap) { return copy_out(rt().hmem_noise_counts, counts, cap); }
 
-int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap) {
-  const std::vector<unsigned long long> &k = rt().hmem_noise_seeds;
-  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
-  return (int)k.size();
-}
+int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().hmem_noise_seeds, seeds, cap); }
 
 // ---- exposure campaigns (the model: mem_org.h) ------------------------------------------------------------------------------
 
@@ -4027,16 +4014,15 @@ long bnn_mi355x_exposure_mask(int scheme, int burst, unsigned long long run_seed
 int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs, unsigned long long seed,
                                    const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch_images, int scrub_every,
                                    int *image_number, float *usecPerImage) {
-  const Hardening hz{scheme, burst};
-  const Exposure ex{epoch_images, scrub_every};
-  return mem_noise_campaigns_impl("exposure_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number,
-                                  usecPerImage, &ex);
+  const MemNoiseEntry en{"exposure_campaigns", &Runtime::xmem_counts, &Runtime::xmem_seeds};
+  return mem_noise_campaigns_impl(en, Hardening{scheme, burst}, Exposure{epoch_images, scrub_every}, path, number_class, num_runs, seed,
+                                  rate_w_q32, rate_t_q32, n_rates, image_number, usecPerImage);
 }
 
 // One copy stepped through epochs 0 ... epoch by the campaign's own steps (exposure_begin, exposure_epoch), then read back.
 static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
                                    const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap,
-                                   int repair_every = -1) {
+                                   int repair_every) {
   Runtime &r = rt();
   // (room for the decode-status counters of a coded layer, and on the repair route -- repair_every >= 0 -- for the repair
   // counters; nothing reads them here)
@@ -4045,14 +4031,14 @@ static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigne
     fail(std::string(who) + ": epoch must be 0 ... " + std::to_string(kMaxEpochs - 1) + " and scrub_every must not be negative (0: never scrub)");
     return 0;
   }
-  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, &hz)) return 0;
+  if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz, false)) return 0;
   if (!dst) return r.blob.size();
   if (cap < r.blob.size()) { fail(std::string(who) + ": destination too small"); return 0; }
   const std::vector<unsigned long long> seeds(1, run_seed);
   const int E = epoch + 1;
   MemNoiseJob job;
   auto run = [&]() -> int {
-    if (exposure_prepare(seeds, rate_w_q32, rate_t_q32, E, ex, hz, job)) return -1;
+    if (exposure_prepare(who, seeds, rate_w_q32, rate_t_q32, E, ex, hz, job)) return -1;
     DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
     if (settle_handover(r.stream)) return -1;
     if (exposure_begin(seeds, job, 256, E, ex.longs)) return -1;
@@ -4071,17 +4057,9 @@ size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_
   return exposure_params_impl("exposure_params", Hardening{scheme, burst}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch, scrub_every, dst, cap);
 }
 
-int bnn_mi355x_last_exposure_counts(long *counts, int cap) {
-  const std::vector<long> &c = rt().xmem_counts;
-  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
-  return (int)c.size();
-}
+int bnn_mi355x_last_exposure_counts(long *counts, int cap) { return copy_out(rt().xmem_counts, counts, cap); }
 
-int bnn_mi355x_last_exposure_seeds(unsigned long long *seeds, int cap) {
-  const std::vector<unsigned long long> &k = rt().xmem_seeds;
-  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
-  return (int)k.size();
-}
+int bnn_mi355x_last_exposure_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().xmem_seeds, seeds, cap); }
 
 // ---- coded threshold memories in the exposure campaigns (the code: ecc.h; storage and upsets: mem_org.h) -----------------
 
@@ -4168,10 +4146,9 @@ size_t bnn_mi355x_pack_params_ecc(const char *path, int scheme, int code, const 
 int *bnn_mi355x_ecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst, int num_runs, unsigned long long seed,
                                        const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch_images,
                                        int scrub_every, int *image_number, float *usecPerImage) {
-  const Hardening hz{scheme, burst, code};
-  const Exposure ex{epoch_images, scrub_every, 6};
-  return mem_noise_campaigns_impl("ecc_exposure_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number,
-                                  usecPerImage, &ex);
+  const MemNoiseEntry en{"ecc_exposure_campaigns", &Runtime::emem_counts, &Runtime::emem_seeds};
+  return mem_noise_campaigns_impl(en, Hardening{scheme, burst, code}, Exposure{epoch_images, scrub_every, 6}, path, number_class, num_runs, seed,
+                                  rate_w_q32, rate_t_q32, n_rates, image_number, usecPerImage);
 }
 
 size_t bnn_mi355x_ecc_exposure_params(int scheme, int code, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
@@ -4180,17 +4157,9 @@ size_t bnn_mi355x_ecc_exposure_params(int scheme, int code, int burst, unsigned 
                               dst, cap);
 }
 
-int bnn_mi355x_last_ecc_exposure_counts(long *counts, int cap) {
-  const std::vector<long> &c = rt().emem_counts;
-  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
-  return (int)c.size();
-}
+int bnn_mi355x_last_ecc_exposure_counts(long *counts, int cap) { return copy_out(rt().emem_counts, counts, cap); }
 
-int bnn_mi355x_last_ecc_exposure_seeds(unsigned long long *seeds, int cap) {
-  const std::vector<unsigned long long> &k = rt().emem_seeds;
-  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
-  return (int)k.size();
-}
+int bnn_mi355x_last_ecc_exposure_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().emem_seeds, seeds, cap); }
 
 // ---- repair scrubs in the exposure campaigns (the model: mem_org.h, "repair scrubs"; the rule on a code word: ecc.h) -------
 
@@ -4228,10 +4197,9 @@ size_t bnn_mi355x_pack_params_repair(const char *path, int scheme, int code, con
 int *bnn_mi355x_repair_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst, int num_runs, unsigned long long seed,
                                           const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch_images,
                                           int scrub_every, int repair_every, int *image_number, float *usecPerImage) {
-  const Hardening hz{scheme, burst, code};
-  const Exposure ex{epoch_images, scrub_every, 8, repair_every};
-  return mem_noise_campaigns_impl("repair_exposure_campaigns", &hz, path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates,
-                                  image_number, usecPerImage, &ex);
+  const MemNoiseEntry en{"repair_exposure_campaigns", &Runtime::rmem_counts, &Runtime::rmem_seeds, false, false, false, true};
+  return mem_noise_campaigns_impl(en, Hardening{scheme, burst, code}, Exposure{epoch_images, scrub_every, 8, repair_every}, path, number_class,
+                                  num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number, usecPerImage);
 }
 
 size_t bnn_mi355x_repair_exposure_params(int scheme, int code, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
@@ -4245,17 +4213,9 @@ size_t bnn_mi355x_repair_exposure_params(int scheme, int code, int burst, unsign
                               scrub_every, dst, cap, repair_every);
 }
 
-int bnn_mi355x_last_repair_exposure_counts(long *counts, int cap) {
-  const std::vector<long> &c = rt().rmem_counts;
-  for (int i = 0; counts && i < cap && i < (int)c.size(); i++) counts[i] = c[(size_t)i];
-  return (int)c.size();
-}
+int bnn_mi355x_last_repair_exposure_counts(long *counts, int cap) { return copy_out(rt().rmem_counts, counts, cap); }
 
-int bnn_mi355x_last_repair_exposure_seeds(unsigned long long *seeds, int cap) {
-  const std::vector<unsigned long long> &k = rt().rmem_seeds;
-  for (int i = 0; seeds && i < cap && i < (int)k.size(); i++) seeds[i] = k[(size_t)i];
-  return (int)k.size();
-}
+int bnn_mi355x_last_repair_exposure_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().rmem_seeds, seeds, cap); }
 
 void free_results(int *result) { delete[] result; }
 

@@ -443,9 +443,10 @@ size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned i
  * with module 0 is pack_params_faulty.  Host only.
  * hardened_mem_noise_campaigns: mem_noise_campaigns with (scheme, burst): its conventions, refusals (but the variants':
  * the scheme is the argument), grouping and BNN_MI355X_NOISE_GROUP; also refused: burst outside 1 ... 16, a bad scheme or
- * refused pair.  Always runs its own kernels (k_hmem_noise_w / k_hmem_noise_t; layer 0 of the CNV nets on the host through
- * the physical model), scheme 0 included.  All rates 0: the fault-free classes, no upset kernel is launched.
- * hardened_mem_noise_params: the blob one run classifies with, made by those kernels and read back.
+ * refused pair.  Runs the exposure campaigns' device path (k_xmem_noise_w / k_xmem_noise_t at epoch 0 on zeroed state;
+ * layer 0 of the CNV nets on the host through the physical model), scheme 0 included: exposure_campaigns with the whole
+ * file as one epoch.  All rates 0: the fault-free classes, no upset kernel is launched.
+ * hardened_mem_noise_params: the blob one run classifies with, made by that path and read back.
  * last_hardened_mem_noise_counts: per [run][layer][2: weights, thresholds] two longs: the physical bits flipped (before
  * voting) and the logical bits that differ (after voting and de-interleaving); returns runs * layers * 4.
  * last_hardened_mem_noise_seeds: the runs' seeds of the last such call. */

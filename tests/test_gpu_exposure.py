@@ -129,7 +129,8 @@ def assert_accumulation_preconditions(network, scheme, burst, per_epoch, epochs,
 @pytest.mark.parametrize("network,scheme", [(n, 0) for n, _ in mm.NETS] + PAIRS, ids=str)
 def test_one_epoch_is_the_hardened_campaign(network, scheme, tmp_path, monkeypatch):
     """epoch_images >= n, bursts 1 and 4, both rates: classes, seeds, counts and the blob of epoch 0 equal
-    hardened_mem_noise_campaigns / _params bit for bit (scrub_every has nothing to act on)"""
+    hardened_mem_noise_campaigns / _params bit for bit (scrub_every has nothing to act on).  Both entry points run the same
+    device path: this pins the hardened entry point's argument mapping (the whole file as one epoch, never scrubbed)"""
     L, pdir = gm.load(network, DATASET[network])
     path = sw.write_images(network, sw.images(network, N, seed=17), tmp_path)
     monkeypatch.setenv("BNN_MI355X_NOISE_GROUP", "37")

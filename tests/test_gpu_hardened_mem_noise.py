@@ -125,8 +125,9 @@ def rates_of(network, p):
 
 @pytest.mark.parametrize("network,dataset", mm.NETS, ids=lambda x: x)
 def test_scheme_0_burst_1_is_mem_noise_campaigns(network, dataset, tmp_path, monkeypatch):
-    """the new kernels against the old entry points, all five nets, both rates: classes, blob and counts are equal (the
-    logical count equals the physical one wherever a bit is a bit: every memory but layer 0's thresholds of a CNV net)"""
+    """the exposure path at epoch 0 (k_xmem_noise_w / _t, which the hardened entry point runs) against the plain route's own
+    kernels, all five nets, both rates: classes, blob and counts are equal (the logical count equals the physical one
+    wherever a bit is a bit: every memory but layer 0's thresholds of a CNV net)"""
     L, pdir = gm.load(network, dataset)
     path = sw.write_images(network, sw.images(network, N, seed=17), tmp_path)
     monkeypatch.setenv("BNN_MI355X_NOISE_GROUP", "37")

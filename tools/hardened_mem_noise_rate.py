@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Hardened memory schemes in the memory upset campaigns (bnn_mi355x_hardened_mem_noise_campaigns): RUNS runs over N random
 images of cnvW1A1, every weight and threshold rate 2^-6.  Configurations, alternating in one process: mem_noise_campaigns at
-the same rates (the baseline: independent single-bit flips, the kernels the new ones sit next to), then each supported
+the same rates (the baseline: independent single-bit flips, by the plain route's own kernels), then each supported
 scheme (0 none, 1 TMR, 2 interleaved, 3 resilient-interleaved) at burst 1 and 4.  Per configuration: wall and device time
 (best of three calls), the ratio to the baseline's device time, the physical bits flipped and the logical bits that differ
 after voting and de-interleaving, and the mean accuracy against the fault-free classes.

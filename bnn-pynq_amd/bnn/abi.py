@@ -37,7 +37,10 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_pack_params_ecc", "bnn_mi355x_ecc_exposure_campaigns", "bnn_mi355x_ecc_exposure_params",
        "bnn_mi355x_last_ecc_exposure_counts", "bnn_mi355x_last_ecc_exposure_seeds", "bnn_mi355x_ecc_repair",
        "bnn_mi355x_pack_params_repair", "bnn_mi355x_repair_exposure_campaigns", "bnn_mi355x_repair_exposure_params",
-       "bnn_mi355x_last_repair_exposure_counts", "bnn_mi355x_last_repair_exposure_seeds"]
+       "bnn_mi355x_last_repair_exposure_counts", "bnn_mi355x_last_repair_exposure_seeds", "bnn_mi355x_wecc_encode",
+       "bnn_mi355x_wecc_decode", "bnn_mi355x_wecc_repair", "bnn_mi355x_wecc_layout", "bnn_mi355x_wecc_exposure_mask",
+       "bnn_mi355x_pack_params_wecc", "bnn_mi355x_wecc_exposure_campaigns", "bnn_mi355x_wecc_exposure_params",
+       "bnn_mi355x_last_wecc_exposure_counts", "bnn_mi355x_last_wecc_exposure_seeds"]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -199,6 +202,27 @@ def declare_extensions(L):
         L.bnn_mi355x_repair_exposure_params.restype = C.c_size_t
         L.bnn_mi355x_last_repair_exposure_counts.argtypes = [C.POINTER(C.c_long), C.c_int]
         L.bnn_mi355x_last_repair_exposure_seeds.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+    if hasattr(L, "bnn_mi355x_wecc_exposure_campaigns"):  # (likewise)
+        up = C.POINTER(C.c_uint)
+        ullp = C.POINTER(C.c_ulonglong)
+        L.bnn_mi355x_wecc_encode.argtypes = [C.c_ulonglong]
+        L.bnn_mi355x_wecc_encode.restype = C.c_uint
+        L.bnn_mi355x_wecc_decode.argtypes = [C.c_ulonglong, C.c_uint, ullp]
+        L.bnn_mi355x_wecc_repair.argtypes = [C.c_ulonglong, C.c_uint, ullp, up]
+        L.bnn_mi355x_wecc_layout.argtypes = [C.c_int, C.c_int, ip]
+        L.bnn_mi355x_wecc_exposure_mask.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_uint, C.c_long, ip, C.c_int]
+        L.bnn_mi355x_wecc_exposure_mask.restype = C.c_long
+        L.bnn_mi355x_pack_params_wecc.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_pack_params_wecc.restype = C.c_size_t
+        L.bnn_mi355x_wecc_exposure_campaigns.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, up,
+                                                         up, C.c_int, C.c_int, C.c_int, C.c_int, ip, fp]
+        L.bnn_mi355x_wecc_exposure_campaigns.restype = ip
+        L.bnn_mi355x_wecc_exposure_params.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, up, up, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_wecc_exposure_params.restype = C.c_size_t
+        L.bnn_mi355x_last_wecc_exposure_counts.argtypes = [C.POINTER(C.c_long), C.c_int]
+        L.bnn_mi355x_last_wecc_exposure_seeds.argtypes = [ullp, C.c_int]
     L.bnn_mi355x_pack_params_faulty.argtypes = [C.c_char_p, ip, C.c_int, C.c_void_p, C.c_size_t]
     L.bnn_mi355x_pack_params_faulty.restype = C.c_size_t
     L.bnn_mi355x_debug_stage_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]

@@ -415,14 +415,18 @@ class PynqBNN:
 
     # extension: exposure campaigns (upsets that accumulate over epochs of images, with scrubbing)
     def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0, code=0,
-                                    repair_every=0):
+                                    repair_every=0, weight_code=0):
         """inference_multiple_hardened_mem_noise spread over time: the run is cut into epochs of `epoch_images` images, the
         rates are per epoch, an epoch's upsets XOR onto the physical state the earlier ones left, and before every epoch
         t > 0 with t % scrub_every == 0 (0: never) all memories are rewritten from the loaded parameters.  -> (classes
         int32 (num_runs, n), counts int64 (num_runs, epochs, layers, 2: weights, thresholds, 2: physical bits flipped in
         the epoch, logical bits that differ from the loaded parameters after it)).  The seeds are left in
         self.mem_noise_seeds.  code 1 (SEC-DED coded 16-bit threshold memories): inference_multiple_ecc_exposure;
-        repair_every > 0 (repair scrubs): inference_multiple_repair_exposure."""
+        repair_every > 0 (repair scrubs): inference_multiple_repair_exposure; weight_code 1 (SEC-DED (72,64) coded weight
+        memories): inference_multiple_wecc_exposure."""
+        if weight_code:
+            return self.inference_multiple_wecc_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, repair_every, scheme, code,
+                                                         weight_code, burst, seed)
         if repair_every:
             return self.inference_multiple_repair_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, repair_every, scheme, code,
                                                            burst, seed)
@@ -509,6 +513,38 @@ class PynqBNN:
         self.usecPerImage = usec.value
         epochs = -(-size.value // epoch_images)
         return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 8)
+
+    # extension: SEC-DED (72,64) coded weight memories in the exposure campaigns
+    def inference_multiple_wecc_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, repair_every=0, scheme=0, code=0,
+                                         weight_code=1, burst=1, seed=0):
+        """inference_multiple_repair_exposure with the weight memories of every layer but CNV layer 0 protected by a SEC-DED
+        code (`weight_code` 1; 0: none): Hamming(71,64) plus an overall parity bit over every 64 sites of the memory, the 8
+        check bits of a code word in a check memory of the layer's own that takes upsets at the weight rate.  A repair epoch
+        also rewrites the status-1 code words.  Goes with every (scheme, code) the repair campaign accepts, TMR included.
+        -> (classes int32 (num_runs, n), counts int64 (num_runs, epochs, layers, 12: the eight of
+        inference_multiple_repair_exposure -- weights physical counts data plus check bits, weights logical the data bits
+        that differ after decoding -- then the weight code words corrected, detected as uncorrectable, rewritten by the
+        epoch's repair, still unlike the loaded ones after it)).  The seeds are left in self.mem_noise_seeds."""
+        lib = self.interface
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_wecc_exposure_campaigns(path.encode(), len(self.classes), scheme, code, weight_code, burst, num_runs, seed,
+                                                     qw.ctypes.data_as(up), qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every,
+                                                     repair_every, ctypes.byref(size), ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("wecc exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_wecc_exposure_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_wecc_exposure_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_wecc_exposure_seeds(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        epochs = -(-size.value // epoch_images)
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 12)
 
     # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
     def enumerate_input_faults(self):

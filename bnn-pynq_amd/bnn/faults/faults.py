@@ -70,6 +70,8 @@ def propagation_curves(alive, flipped, n_images, first=0):
 HARDENING_SCHEMES = ("none", "TMR", "interleaved", "resilient-interleaved")
 # the codes of the 16-bit threshold memories (csrc/ecc.h), by the code number the C ABI takes; the project's own model
 ECC_CODES = ("", "SEC-DED")
+# the codes of the weight memories of the layers >= 1 (csrc/wecc.h), by the weight_code number; the project's own model
+WEIGHT_CODES = ("", "SEC-DED weights")
 
 
 def scheme_and_code(entry):
@@ -77,8 +79,13 @@ def scheme_and_code(entry):
     return (int(entry[0]), int(entry[1])) if isinstance(entry, (tuple, list)) else (int(entry), 0)
 
 
-def organisation_name(scheme, code=0):
-    return HARDENING_SCHEMES[scheme] + (" + " + ECC_CODES[code] if code else "")
+def scheme_code_and_weight_code(entry):
+    """likewise, a (scheme, code, weight_code) triple as well"""
+    return scheme_and_code(entry) + ((int(entry[2]),) if isinstance(entry, (tuple, list)) and len(entry) > 2 else (0,))
+
+
+def organisation_name(scheme, code=0, weight_code=0):
+    return HARDENING_SCHEMES[scheme] + (" + " + ECC_CODES[code] if code else "") + (" + " + WEIGHT_CODES[weight_code] if weight_code else "")
 
 
 def hardening_of(overlay):
@@ -248,8 +255,9 @@ class FaultTest:
         print()
         return accuracies
 
-    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1, code=0):
-        """code 1 (SEC-DED coded threshold memories, csrc/ecc.h; scheme 0 or 2): the exposure campaign with one epoch, which
+    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1, code=0, weight_code=0):
+        """weight_code 1 (SEC-DED (72,64) coded weight memories of the layers >= 1, csrc/wecc.h; any scheme and code): likewise
+        one epoch of the exposure campaign, the counts [run, layer, 12] as run_exposure_test's.  code 1 (SEC-DED coded threshold memories, csrc/ecc.h; scheme 0 or 2): the exposure campaign with one epoch, which
         is the one-shot campaign; the counts are then [run, layer, 6] as run_exposure_test's.  scheme (0 ... 3, HARDENING_SCHEMES) or burst > 1: the upsets hit the physical memories of that hardened
         organisation in bursts of `burst` adjacent bits, and the counts are [run, layer, 2, 2: physical bits flipped,
         logical bits that differ after voting and de-interleaving].  Else (today's path, unchanged) num_runs independent runs with every bit of layer L's weight memory flipped with probability rates_w[L] and
@@ -260,7 +268,12 @@ class FaultTest:
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, memory upset rate(s) weights {} thresholds {}".format(
             self.network, self.dataset, num_runs, rates_w, rates_t))
-        if code:
+        if weight_code:
+            print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code, weight_code), burst))
+            results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, 1 << 30, 0, scheme or 0, burst, seed, code, 0,
+                                             weight_code)
+            counts = counts[:, 0]
+        elif code:
             print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code), burst))
             results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, 1 << 30, 0, scheme or 0, burst, seed, code)
             counts = counts[:, 0]
@@ -275,7 +288,8 @@ class FaultTest:
         print()
         return accuracies, counts
 
-    def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0, code=0, repair_every=0):
+    def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0, code=0, repair_every=0,
+                          weight_code=0):
         """Upsets that accumulate while the run goes on: the images are cut into epochs of `epoch_images`, rates_w[L] /
         rates_t[L] are the probability of an event PER EPOCH (scalars: every layer), an epoch's upsets XOR onto the physical
         state of the hardened organisation `scheme` (None: 0) the earlier epochs left, and every `scrub_every` epochs (0:
@@ -288,14 +302,19 @@ class FaultTest:
         redundancy (TMR modules, coded thresholds) are repaired -- read, voted or decoded, written back -- which fixes only
         what the redundancy covers and locks in what it gets wrong; the counts are then [run, epoch, layer, 8: the six
         above, the words the epoch's repair rewrote, the words of the repaired memories still unlike the loaded ones].
+        weight_code 1: the weight memories of every layer but CNV layer 0 carry a SEC-DED (72,64) code (csrc/wecc.h; any
+        scheme, code and repair_every; a repair also rewrites status-1 weight code words) and the counts are [run, epoch,
+        layer, 12: the eight above, weight code words corrected, detected as uncorrectable, rewritten by the epoch's
+        repair, still unlike the loaded ones after it].
         Left behind: self.exposure_results (classes, [run, image]), self.exposure_counts, self.exposure_usec."""
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, epochs of {} images, upset rate(s) per epoch weights {} thresholds {}, {}, bursts of {}, "
               "scrub every {}{}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t,
-                                        organisation_name(scheme or 0, code), burst, scrub_every or "never",
+                                        organisation_name(scheme or 0, code, weight_code), burst, scrub_every or "never",
                                         ", repair every {}".format(repair_every) if repair_every else ""))
         args = (num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst, seed)
-        results, counts = self._classify(classifier, "_exposure", *(args + (code, repair_every) if repair_every else args + (code,) if code else args))
+        results, counts = self._classify(classifier, "_exposure", *(args + (code, repair_every, weight_code) if weight_code else
+                                                                    args + (code, repair_every) if repair_every else args + (code,) if code else args))
         self.exposure_results, self.exposure_counts, self.exposure_usec = results, counts, classifier.usecPerImage
         accuracies = [[util.calculate_accuracy(row[i: i + epoch_images].tolist(), self.labels[i: i + epoch_images])
                        for i in range(0, results.shape[1], epoch_images)] for row in results]
@@ -613,19 +632,26 @@ class NetworkTest:
         "stddev accuracy", "scheme", "burst", "rate" and the "physical bits" flipped and "logical bits" that differ after
         voting and de-interleaving, summed over the runs.  An entry of `schemes` may be a (scheme, code) pair (code 1: SEC-DED
         coded threshold memories): its name is "<scheme name> + SEC-DED", and it also writes "code", "corrected words" and
-        "detected words"."""
+        "detected words".  A (scheme, code, weight_code) triple (weight_code 1: SEC-DED (72,64) coded weight memories):
+        the name holds " + SEC-DED weights", and it also writes "weight code", "corrected weight words" and "detected weight
+        words"."""
         ft = self.fault_test
         folder = "{}/{}/{}/hardening/".format(output_folder, ft.network, ft.dataset)
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme, code in map(scheme_and_code, schemes):
+        for scheme, code, weight_code in map(scheme_code_and_weight_code, schemes):
             for burst in bursts:
                 for p in rates:
-                    accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, scheme, burst, code)
-                    name = "{} burst {} upset rate {:g}".format(organisation_name(scheme, code), burst, p)
+                    accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, scheme, burst, code,
+                                                                  *((weight_code,) if weight_code else ()))
+                    name = "{} burst {} upset rate {:g}".format(organisation_name(scheme, code, weight_code), burst, p)
                     raw.append(self._raw(name, num_runs, 0, [], accuracies))
                     extra[name] = {"stddev accuracy": float(np.std(accuracies)), "scheme": int(scheme), "burst": int(burst), "rate": float(p)}
+                    if weight_code:  # [run, layer, 12]
+                        extra[name].update({"weight code": int(weight_code), "corrected weight words": int(counts[..., 8].sum()),
+                                            "detected weight words": int(counts[..., 9].sum())})
+                        counts = counts[..., :6] if code else counts[..., :4].reshape(counts.shape[:2] + (2, 2))
                     if code:  # [run, layer, 6]
                         extra[name].update({"code": int(code), "physical bits": int(counts[..., [0, 2]].sum()),
                                             "logical bits": int(counts[..., [1, 3]].sum()), "corrected words": int(counts[..., 4].sum()),
@@ -649,26 +675,37 @@ class NetworkTest:
         "corrected words per epoch" and "detected words per epoch" (summed over the runs).  An entry of `scrub_intervals`
         may be a (scrub_every, repair_every) pair (run_exposure_test's repair scrub); with a non-zero repair_every the name
         ends in " repair every <P>" and the result also holds "repair every", "repaired words per epoch" and "unrepaired
-        words per epoch" (summed over the runs)."""
+        words per epoch" (summed over the runs).  An entry of `schemes` may also be a (scheme, code, weight_code) triple
+        (weight_code 1: SEC-DED (72,64) coded weight memories of the layers >= 1): the name holds " + SEC-DED weights", and the
+        result also holds "weight code" and the "corrected / detected / repaired / unrepaired weight words per epoch"."""
         ft = self.fault_test
         folder = "{}/{}/{}/scrubbing/".format(output_folder, ft.network, ft.dataset)
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme, code in map(scheme_and_code, schemes):
+        for scheme, code, weight_code in map(scheme_code_and_weight_code, schemes):
             for burst in bursts:
                 for p in rates:
                     for every in scrub_intervals:
                         every, repair = (int(every[0]), int(every[1])) if isinstance(every, (tuple, list)) else (every, 0)
                         per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed, code,
-                                                                 *((repair,) if repair else ()))
+                                                                 *((repair, weight_code) if weight_code else (repair,) if repair else ()))
                         accuracies = [util.calculate_accuracy(row.tolist(), ft.labels) for row in ft.exposure_results]
-                        name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(scheme, code), burst, p, every)
+                        name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(scheme, code, weight_code), burst, p, every)
                         status = {}
+                        if weight_code:  # [run, epoch, layer, 12]: the weight code words' four counters behind the repair shape
+                            status = {"weight code": int(weight_code),
+                                      "corrected weight words per epoch": [int(x) for x in counts[..., 8].sum(axis=(0, 2))],
+                                      "detected weight words per epoch": [int(x) for x in counts[..., 9].sum(axis=(0, 2))],
+                                      "repaired weight words per epoch": [int(x) for x in counts[..., 10].sum(axis=(0, 2))],
+                                      "unrepaired weight words per epoch": [int(x) for x in counts[..., 11].sum(axis=(0, 2))]}
+                            counts = counts[..., :8]
+                            if not repair:
+                                counts = counts[..., :6] if code else counts[..., :4].reshape(counts.shape[:3] + (2, 2))
                         if repair:  # [run, epoch, layer, 8]: the repair's two counters behind the coded shape
                             name += " repair every {}".format(repair)
-                            status = {"repair every": repair, "repaired words per epoch": [int(x) for x in counts[..., 6].sum(axis=(0, 2))],
-                                      "unrepaired words per epoch": [int(x) for x in counts[..., 7].sum(axis=(0, 2))]}
+                            status.update({"repair every": repair, "repaired words per epoch": [int(x) for x in counts[..., 6].sum(axis=(0, 2))],
+                                           "unrepaired words per epoch": [int(x) for x in counts[..., 7].sum(axis=(0, 2))]})
                             counts = counts[..., :6]
                             if not code:
                                 counts = counts[..., :4].reshape(counts.shape[:3] + (2, 2))

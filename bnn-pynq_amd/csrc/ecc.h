@@ -27,8 +27,9 @@
 // the loaded word (m = 0), an accepted triple becomes a clean-looking wrong one (m != 0, status 0 from then on) that no
 // later repair touches.  The delivered data is d' before and after.
 //
-// Two limits.  WEIGHTS are not coded: their memory words are SIMD * wbits wide (1 ... 32 bits in the fold tables) and
-// no per-word code makes sense over them -- as the interleaved schemes leave them alone.  The 24-bit threshold memory
+// Two limits.  WEIGHTS are not coded BY THIS CODE: their memory words are SIMD * wbits wide (1 ... 64 bits in the fold
+// tables) and no per-word code makes sense over them; the code over them is the one that lies over the memory 64 data
+// bits at a time, whatever the word width -- wecc.h, a `weight_code` axis of its own.  The 24-bit threshold memory
 // of CNV LAYER 0 is not coded: a fault there passes through the reference's integer-part read-back (apply_fault), which
 // rewrites the whole word, and no code word survives that; layer 0 keeps the uncoded host route, and a study that wants
 // it out of the picture sets its rates to 0.  A scrub is a full rewrite (data and check words) or a repair (above).

@@ -252,4 +252,19 @@ struct RepairEntry { unsigned long long state_off; uint32_t lanes, kind, layer, 
 struct RepairTable { RepairEntry e[kRepairEntries]; };
 hipError_t repair_state(uint8_t *camp, const RepairTable &tab, int entries, int runs, unsigned long long *rep, size_t rep_stride, hipStream_t s);
 
+// Coded weight memories (SEC-DED (72,64): wecc.h; bnn_mi355x_wecc_exposure_campaigns; the model: mem_org.h, "coded weight
+// memories"), wecc_kernels.hip.  wmem_noise_w goes in xmem_noise_w's place for a coded layer, same geometry and
+// arguments; state holds runs * rows * kw * (two_bit ? 2 : 1) code words (run-major, lane-major, a lane's code words
+// one after the other), each a pair of longs: the accumulated hit mask of the 64 data sites, and of the 8 check bits;
+// zero where the copies hold the loaded parameters.  counts[0] += the data and check bits flipped, [1] += the data bits
+// that differ after decoding.  wst: this epoch's [layer][4: code words at status 1, at status 2, rewritten by the
+// epoch's repair, still unlike the loaded ones after it] of run 0, run q's wst_stride longs behind.
+hipError_t wmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
+                        int ebits, int burst, uint32_t rate_q32, int epoch, const uint8_t *loaded, unsigned long long *state,
+                        unsigned long long *counts, size_t run_stride, unsigned long long *wst, size_t wst_stride, hipStream_t s);
+// The repair of the coded weight memories: ONE launch over (code word, run, coded layer) applies wecc_repair to the state
+// pairs; entries as for repair_state (state_off the layer's pairs, lanes its code words per run; kind RK_CODED).  The
+// copies are not touched.
+hipError_t wrepair_state(uint8_t *camp, const RepairTable &tab, int entries, int runs, unsigned long long *wst, size_t wst_stride, hipStream_t s);
+
 }  // namespace bnn

@@ -62,6 +62,36 @@ std::string ecc_layout(const NetSpec &net, int scheme, int code, int layer, EccO
   return "";
 }
 
+std::string wecc_check(int weight_code) {
+  if (weight_code < WC_NONE || weight_code > WC_SECDED) return "weight_code must be 0 (none) or 1 (SEC-DED (72,64) over the weights of layers >= 1)";
+  return "";
+}
+
+int wecc_words_per_pe(const NetSpec &net, int weight_code, int layer) {
+  if (weight_code != WC_SECDED || layer < 0 || layer >= net.nlayers) return 0;
+  const LayerSpec &L = net.L[layer];
+  const int ebits = mem_element_bits(L, 0);
+  // (CNV layer 0: int8 taps, 3 or 6 bits per element -- not coded: wecc.h)
+  if (L.arith == AR_INT8 || ebits < 1 || 64 % ebits || ((long)L.fold.wmem * ebits) % 64) return 0;
+  return (int)((long)L.fold.wmem * ebits / 64);
+}
+
+namespace {
+// code word cw of one PE's weight memory: its 64 data bits gathered from / scattered to the 64 / ebits elements it covers
+uint64_t wecc_gather(const std::vector<uint64_t> &pe, int ebits, int cw) {
+  const int n = 64 / ebits;
+  const uint64_t emask = ebits >= 64 ? ~0ull : (1ull << ebits) - 1;
+  uint64_t d = 0;
+  for (int i = 0; i < n; i++) d |= (pe[(size_t)cw * n + i] & emask) << (i * ebits);
+  return d;
+}
+void wecc_scatter(std::vector<uint64_t> &pe, int ebits, int cw, uint64_t d) {
+  const int n = 64 / ebits;
+  const uint64_t emask = ebits >= 64 ? ~0ull : (1ull << ebits) - 1;
+  for (int i = 0; i < n; i++) pe[(size_t)cw * n + i] = (d >> (i * ebits)) & emask;
+}
+}  // namespace
+
 namespace {
 // the threshold words of one layer with the pairs of lines (ind, ind + 1) of every PE interleaved (forward) or
 // de-interleaved at element width T; an odd last line stays as it is
@@ -86,7 +116,7 @@ void permute_pairs(const LayerSpec &L, int il, int T, bool forward, std::vector<
 }
 }  // namespace
 
-void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code) {
+void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code, int weight_code) {
   out.l0 = l0;
   out.l1 = l1;
   for (int l = l0; l < l1; l++) {
@@ -99,6 +129,12 @@ void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int
       out.mod[m].t[l].clear();
     }
     for (int m = 0; m < org.w_modules; m++) out.mod[m].w[l] = raw.w[l];
+    if (const int cwpp = wecc_words_per_pe(net, weight_code, l)) {  // the check words of the loaded code words in module 1
+      const int ebits = mem_element_bits(L, 0);
+      out.mod[1].w[l].assign(raw.w[l].size(), std::vector<uint64_t>((size_t)cwpp));
+      for (size_t pe = 0; pe < raw.w[l].size(); pe++)
+        for (int cw = 0; cw < cwpp; cw++) out.mod[1].w[l][pe][(size_t)cw] = wecc_encode(wecc_gather(raw.w[l][pe], ebits, cw));
+    }
     std::vector<std::vector<uint64_t>> t = raw.t[l];
     if (org.t_interleave) permute_pairs(L, org.t_interleave, mem_element_bits(L, 1), true, t);
     if (eo.check_bits) {  // data in module 0, the check words of the LOGICAL elements in module 1
@@ -114,11 +150,21 @@ void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int
   }
 }
 
-int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf, int code) {
+int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf, int code, int weight_code) {
   const Fault &f = pf.f;
   if (f.layer < p.l0 || f.layer >= p.l1 || (f.target != 0 && f.target != 1)) return -1;
   EccOrg eo{MemOrg{1, 1, 0}, 0};
   if (!ecc_layout(net, scheme, code, f.layer, eo).empty()) return -1;
+  const int cwpp = f.target == 0 ? wecc_words_per_pe(net, weight_code, f.layer) : 0;
+  if (cwpp && pf.module == 1) {  // the weight check memory
+    const LayerSpec &L = net.L[f.layer];
+    if (f.word_size < 1 || f.word_size > 64 || f.mem < 0 || f.mem >= L.fold.pe || f.ind < 0 || f.ind >= cwpp || f.bit < 0 || f.bit >= kWeccCheckBits)
+      return -1;
+    const int at = (f.bit / f.word_size) * f.word_size;  // (apply_fault's alignment)
+    const uint64_t flip = ((1ull << event_width(kWeccCheckBits, f.word_size, at)) - 1) << at;
+    p.mod[1].w[f.layer][(size_t)f.mem][(size_t)f.ind] ^= flip;
+    return (int)(((long)f.ind * 64 / mem_element_bits(L, 0)) / (L.fold.wmem / L.fold.tmem)) * L.fold.pe + f.mem;
+  }
   if (pf.module < 0 || pf.module >= (f.target == 0 ? eo.org.w_modules : eo.org.t_modules)) return -1;
   if (f.target == 1 && eo.check_bits && pf.module == 1) {
     const LayerSpec &L = net.L[f.layer];
@@ -148,7 +194,8 @@ void vote(const RawParams *mod, bool thresholds, int l, int modules, int ebits, 
 }
 }  // namespace
 
-void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code, long (*status)[2]) {
+void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code, long (*status)[2], int weight_code,
+                  long (*wstatus)[2]) {
   for (int l = p.l0; l < p.l1; l++) {
     const LayerSpec &L = net.L[l];
     EccOrg eo{MemOrg{1, 1, 0}, 0};
@@ -156,6 +203,17 @@ void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams
     const MemOrg &org = eo.org;
     if (status) status[l][0] = status[l][1] = 0;
     vote(p.mod, false, l, org.w_modules, mem_element_bits(L, 0), out.w[l]);
+    if (wstatus) wstatus[l][0] = wstatus[l][1] = 0;
+    if (const int cwpp = wecc_words_per_pe(net, weight_code, l)) {
+      const int ebits = mem_element_bits(L, 0);
+      for (size_t pe = 0; pe < out.w[l].size(); pe++)
+        for (int cw = 0; cw < cwpp; cw++) {
+          uint64_t d;
+          const int st = wecc_decode(wecc_gather(out.w[l][pe], ebits, cw), (uint32_t)p.mod[1].w[l][pe][(size_t)cw], &d);
+          if (st == 1) wecc_scatter(out.w[l][pe], ebits, cw, d);
+          if (wstatus && st) wstatus[l][st - 1]++;
+        }
+    }
     if (L.nthr == 0) {
       out.t[l] = p.mod[0].t[l];
       continue;
@@ -217,12 +275,30 @@ void scatter(const LayerSpec &L, int il, int width, std::vector<uint64_t> &pe, i
 }
 }  // namespace
 
-void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0, int l1, long (*counts)[2], const PhysParams *loaded) {
+void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0, int l1, long (*counts)[2], const PhysParams *loaded,
+                 int weight_code, long (*wcounts)[2]) {
   for (int l = std::max(l0, p.l0); l < l1 && l < p.l1; l++) {
     const LayerSpec &L = net.L[l];
     EccOrg eo{MemOrg{1, 1, 0}, 0};
     if (counts) counts[l][0] = counts[l][1] = 0;
+    if (wcounts) wcounts[l][0] = wcounts[l][1] = 0;
     if (!ecc_layout(net, scheme, code, l, eo).empty()) continue;
+    if (const int cwpp = wecc_words_per_pe(net, weight_code, l)) {  // a coded weight memory, code word by code word
+      const int ebits = mem_element_bits(L, 0);
+      for (size_t pe = 0; pe < p.mod[0].w[l].size(); pe++)
+        for (int cw = 0; cw < cwpp; cw++) {
+          uint64_t rd;
+          uint32_t rc;
+          const int st = wecc_repair(wecc_gather(p.mod[0].w[l][pe], ebits, cw), (uint32_t)p.mod[1].w[l][pe][(size_t)cw], &rd, &rc);
+          if (st == 1) {
+            wecc_scatter(p.mod[0].w[l][pe], ebits, cw, rd);
+            p.mod[1].w[l][pe][(size_t)cw] = rc;
+            if (wcounts) wcounts[l][0]++;
+          }
+          if (wcounts && loaded && (rd != wecc_gather(loaded->mod[0].w[l][pe], ebits, cw) || rc != (uint32_t)loaded->mod[1].w[l][pe][(size_t)cw]))
+            wcounts[l][1]++;
+        }
+    }
     if (eo.org.w_modules == 3) repair_voted(p.mod, loaded ? loaded->mod : nullptr, false, l, mem_element_bits(L, 0), counts ? counts[l] : nullptr);
     if (L.nthr == 0) continue;
     if (!eo.check_bits) {
@@ -250,7 +326,8 @@ void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0
   }
 }
 
-std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n) {
+std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n,
+                        int weight_code) {
   for (int i = 0; i < n; i++) {
     const int layer = records[(size_t)i * 9 + 2];
     if (layer < 0 && layer != kMarkRepair && layer != kMarkRewrite)
@@ -260,12 +337,12 @@ std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysPara
   for (int i = 0; i < n; i++) {
     const int *v = records + (size_t)i * 9;
     if (v[2] == kMarkRepair) {
-      phys_repair(net, scheme, code, p, p.l0, p.l1, nullptr);
+      phys_repair(net, scheme, code, p, p.l0, p.l1, nullptr, nullptr, weight_code);
     } else if (v[2] == kMarkRewrite) {
       p = loaded;
     } else {
       const PhysFault pf{Fault{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}, v[8]};
-      if (phys_apply(net, scheme, p, pf, code) < 0)
+      if (phys_apply(net, scheme, p, pf, code, weight_code) < 0)
         return "record " + std::to_string(i) + ": fault record out of range (or a module the memory does not have)";
     }
   }
@@ -273,16 +350,19 @@ std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysPara
 }
 
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch, int code) {
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch, int code, int weight_code) {
   if (burst < 1 || burst > kMaxBurst || epoch < 0 || epoch >= kMaxEpochs) return -1;
   EccOrg eo{MemOrg{1, 1, 0}, 0};
   if (!ecc_layout(net, scheme, code, layer, eo).empty()) return -1;
   const MemOrg &org = eo.org;
   const bool check = target == 1 && module == 1 && eo.check_bits;  // the check memory: the same shape, 6 bits wide
-  const long per_c = (long)ecc_check_groups(burst);
-  const long events = check ? (long)net.L[layer].fold.pe * net.L[layer].fold.tmem * net.L[layer].nthr * per_c
-                            : enumerate_faults(net, layer, target, burst, 0, nullptr, 0);
-  if (events < 0 || module < 0 || module >= (target == 0 ? org.w_modules : org.t_modules)) return -1;
+  const int cwpp = target == 0 ? wecc_words_per_pe(net, weight_code, layer) : 0;
+  const bool wcheck = cwpp && module == 1;  // the weight check memory: (PE, code word) shaped, 8 bits wide
+  const long per_c = wcheck ? (long)wecc_check_groups(burst) : (long)ecc_check_groups(burst);
+  const long events = wcheck  ? (long)net.L[layer].fold.pe * cwpp * per_c
+                      : check ? (long)net.L[layer].fold.pe * net.L[layer].fold.tmem * net.L[layer].nthr * per_c
+                              : enumerate_faults(net, layer, target, burst, 0, nullptr, 0);
+  if (events < 0 || module < 0 || (!wcheck && module >= (target == 0 ? org.w_modules : org.t_modules))) return -1;
   long total = 0;
   if (rate_q32 == 0) return 0;
   const uint32_t word = hardened_draw_word(target, module, burst);
@@ -293,7 +373,16 @@ long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t
       if (u[e] >= rate_q32) continue;
       if (out && total >= first && total - first < cap) {
         PhysFault &pf = out[total - first];
-        if (check) {
+        if (wcheck) {
+          const long el = (4 * b + e) / per_c;
+          pf.f = Fault{};
+          pf.f.bit = (int)((4 * b + e - el * per_c) * burst);
+          pf.f.ind = (int)(el % cwpp);
+          pf.f.mem = (int)(el / cwpp);
+          pf.f.layer = layer;
+          pf.f.target = 0;
+          pf.f.word_size = burst;
+        } else if (check) {
           const LayerSpec &L = net.L[layer];
           long el = (4 * b + e) / per_c;
           pf.f = Fault{};

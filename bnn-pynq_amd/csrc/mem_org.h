@@ -41,6 +41,7 @@
 #include <string>
 
 #include "ecc.h"
+#include "wecc.h"
 #include "faults.h"
 #include "packed_params.h"
 #include "topology.h"
@@ -184,12 +185,44 @@ inline bool exposure_repairs(int t, int scrub_every, int repair_every) {
   return t > 0 && repair_every > 0 && t % repair_every == 0 && !exposure_rewrites(t, scrub_every);
 }
 
+// ---- coded weight memories (bnn_mi355x_wecc_exposure_campaigns): the code of wecc.h over the weights of layers >= 1 -----
+// `weight_code` is a third axis next to scheme and code: 0 (none: everything above, unchanged) or 1 (SEC-DED (72,64)).
+// Weight code 1 covers the weight memory of every layer but CNV layer 0 -- every layer >= 1 of the CNV nets, all four of
+// the LFC nets (their layer 0 runs on the device path).  CNV layer 0 is not coded: its element width (3 or 6 bits) does
+// not divide 64, it lives on the host route, and TMR already replicates it; it is treated as the threshold code treats it.
+// CODE WORD q of a layer is sites [64 q, 64 q + 64) of its weight memory in the PE-major site order of enumerate_faults
+// and k_xmem_noise_w (site = element * ebits + bit, element = pe * WMEM + ind; ebits divides 64, and a PE holds a
+// multiple of 64 sites, so no code word straddles PEs): 64 / ebits whole elements.  For 2-bit weights a site is one bit
+// of an ap_int<2> field, so a code word covers 32 columns.
+// Storage: the 8 check bits of code word q are element q of a CHECK MEMORY of the layer's own -- (PE, code word of the
+// PE) shaped, WMEM * ebits / 64 words per PE -- addressed as module 1 of target 0 (no scheme gives the weights of these
+// layers a second module).  The logical weights are decode(data, check).
+// Upsets: the data memory draws exactly as above (module 0: the uncoded campaign's records, same counter words, same
+// order); the check memory draws by the same construction at element width 8 with module 1 in the counter word: per_c =
+// ceil(8 / b) groups per element, e = q * per_c + g, an event a pure XOR of bits [g * b, min(g * b + b, 8)) of the check
+// word, at the layer's weight rate.  Bursts do not cross elements, so they cross neither code words nor from one memory
+// into the other.  Order inside an epoch: module-major, data then check.
+// Repair (a repair epoch), per code word: status 1 stores the delivered data and its wecc_encode, status 0 or 2 writes
+// nothing; a full rewrite clears the weight state like every other memory.  weight_code 1 goes with every (scheme, code,
+// repair_every) combination the repair route accepts, TMR included.
+// Counts per (run, epoch, layer), twelve: the eight above (weights physical = data plus check bits flipped, weights
+// logical = data bits that differ after decoding), then [8] / [9] the weight code words whose decode status after the
+// epoch is 1 / 2, [10] the code words the epoch's repair rewrote (status 1) and [11] those whose stored state still
+// differs from the loaded one after the repair; [10] and [11] are 0 in an epoch without a repair.
+// A check-memory record: target 0, module 1, mem the PE, ind the code word of the PE, bit g * b, word_size b.
+// Like the voter, the threshold code and the repair this is the project's own model: parity unpinned.
+BNN_HD inline uint32_t wecc_check_groups(int burst) { return (uint32_t)((kWeccCheckBits + burst - 1) / burst); }
+
 // ---- host only from here ---------------------------------------------------------------------------------------------
 
 // hardening_layout plus the code: "" and the organisation, else why (network, scheme, code, layer) is refused.
 // check_bits: 6 where the layer's threshold memory is coded (then t_modules counts the check memory: 2), else 0
 struct EccOrg { MemOrg org; int check_bits; };
 std::string ecc_layout(const NetSpec &net, int scheme, int code, int layer, EccOrg &out);
+// the code words per PE of a layer's weight memory where weight_code covers it, else 0 (weight_code 0, CNV layer 0)
+int wecc_words_per_pe(const NetSpec &net, int weight_code, int layer);
+// "" or why the weight code is refused
+std::string wecc_check(int weight_code);
 
 struct PhysFault { Fault f; int module; };
 
@@ -201,24 +234,30 @@ struct PhysParams {
 };
 // what the loader stores from the parameter files.  code 1: the check memory of a coded layer in mod[1].t[l], filled
 // from the logical elements
-void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code = 0);
+// weight_code 1: the check memory of a coded layer's weights in mod[1].w[l] ([pe][code word of the PE])
+void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code = 0, int weight_code = 0);
 // one physical fault; returns apply_fault's result, -1 also for a module the memory does not have.  A record of a check
 // memory (code 1, target 1, module 1) XORs bits [bit, min(bit + word_size, 6)) of the check word, bit aligned as there
-int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf, int code = 0);
+// weight_code 1: a record of a weight check memory (target 0, module 1) likewise at width 8
+int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &pf, int code = 0, int weight_code = 0);
 // de-interleave(vote(modules)) into out.w[l], out.t[l] for l in [l0, l1).  A memory with one module and no interleave
 // is copied word for word; a voted or de-interleaved word holds its element's bits alone.  code 1: a coded layer's
 // words end with the decode (they hold the 16 delivered bits alone); status, where given, counts per layer the words
 // decoded with status 1 ([l][0]) and 2 ([l][1])
-void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code = 0, long (*status)[2] = nullptr);
+// weight_code 1: a coded layer's weight words end with the decode of their code words; wstatus the same counts for them
+void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code = 0, long (*status)[2] = nullptr,
+                  int weight_code = 0, long (*wstatus)[2] = nullptr);
 // one repair ("repair scrubs" above) of the memories of layers [l0, l1) that have redundancy, in place.  counts, where
 // given, receives per layer [l][0] the words rewritten and, with `loaded` (phys_load's result for the same arguments),
-// [l][1] the words of the repaired memories whose stored state still differs from the loaded one afterwards
+// [l][1] the words of the repaired memories whose stored state still differs from the loaded one afterwards.
+// weight_code 1: the coded weight memories are repaired too, counted apart in wcounts (code words)
 void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0, int l1, long (*counts)[2],
-                 const PhysParams *loaded = nullptr);
+                 const PhysParams *loaded = nullptr, int weight_code = 0, long (*wcounts)[2] = nullptr);
 // the records of bnn_mi355x_pack_params_repair, 9 ints each, applied to p in order: a fault record through phys_apply, a
 // marker (layer kMarkRepair / kMarkRewrite) as a repair of all memories / a return to `loaded`.  "" or why a record is
 // refused, naming it; every layer field is checked before anything is applied
-std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n);
+std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n,
+                        int weight_code = 0);
 
 // element width in bits of a layer's weight (target 0) or threshold (target 1) memory; 0: no threshold memory
 int mem_element_bits(const LayerSpec &L, int target);
@@ -228,8 +267,9 @@ inline int event_width(int ebits, int burst, int bit) { return ebits - bit < bur
 // the events of one (run seed, layer, target, module) in event order as physical faults (image 0, word_size burst);
 // returns their number (0: thresholds of a layer without any), -1 for a bad scheme, burst, layer, target or module;
 // writes events first .. first + cap - 1 to out (which may be null).  epoch: the exposure campaigns' (above); the
-// records' image field holds it.  code 1: module 1 of a coded layer's thresholds lists the check memory's events
+// records' image field holds it.  code 1: module 1 of a coded layer's thresholds lists the check memory's events;
+// weight_code 1: module 1 of a coded layer's weights likewise
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch = 0, int code = 0);
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch = 0, int code = 0, int weight_code = 0);
 
 }  // namespace bnn

@@ -298,6 +298,11 @@ struct Runtime {
   // epoch's repair rewrote and the words of the repaired memories still unlike the loaded ones after it] and the seeds
   std::vector<long> rmem_counts;
   std::vector<unsigned long long> rmem_seeds;
+  // bnn_mi355x_wecc_exposure_campaigns (the same buffers; the weight state behind the threshold state in d_camp):
+  // [run][epoch][layer][12: the eight above, then the weight code words at decode status 1 and 2 after the epoch, those the
+  // epoch's repair rewrote and those still unlike the loaded ones after it] and the seeds
+  std::vector<long> wmem_counts;
+  std::vector<unsigned long long> wmem_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -3211,7 +3216,8 @@ long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigne
 // code: the SEC-DED axis of bnn_mi355x_ecc_exposure_campaigns (ecc.h); 0 everywhere else
 // base_only: a variant's library refuses the entry point (the plain ones: the organisation is the variant's there, not
 // an argument; where the scheme is an argument the call is the same in a variant's library)
-struct Hardening { int scheme, burst, code = 0; };
+// weight_code: the SEC-DED axis of bnn_mi355x_wecc_exposure_campaigns over the weights of layers >= 1 (wecc.h); 0 everywhere else
+struct Hardening { int scheme, burst, code = 0, weight_code = 0; };
 
 static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, const Hardening &hz,
                            bool base_only) {
@@ -3249,6 +3255,10 @@ struct MemNoiseJob {
   // state_off[l] of d_camp, all of them in [state_begin, state_begin + state_bytes)
   std::vector<int> span_first;
   size_t state_off[9] = {}, state_begin = 0, state_bytes = 0;
+  // the coded weight route: k_wmem_noise_w's state pairs of layer l (runs * code words of them) at wstate_off[l], inside the
+  // same [state_begin, state_begin + state_bytes), so that a full rewrite clears them with the threshold state
+  size_t wstate_off[9] = {};
+  uint32_t wstate_words[9] = {};  // code words of layer l per run; 0: not coded (or a weight rate of 0)
   // the repair route: [run][epoch][layer][2] of the host's layer-0 repairs (words rewritten, words still unlike the loaded ones)
   std::vector<unsigned long long> host_repairs;
 };
@@ -3471,7 +3481,7 @@ static int exposure_prepare(const char *who, const std::vector<unsigned long lon
   std::memcpy(&h, r.blob.data(), sizeof(h));
   job.stride = (r.blob.size() + 255) & ~(size_t)255;
   job.host_counts.assign((size_t)R * E * S * 4, 0);
-  job.host_repairs.assign(ex.longs == 8 ? (size_t)R * E * S * 2 : 0, 0);
+  job.host_repairs.assign(ex.longs >= 8 ? (size_t)R * E * S * 2 : 0, 0);
   std::vector<uint8_t> staging;
   std::vector<std::vector<PatchSpan>> by_epoch((size_t)E);
   if (net.L[0].arith == AR_INT8 && (rw[0] || rth[0])) {
@@ -3545,6 +3555,13 @@ static int exposure_prepare(const char *who, const std::vector<unsigned long lon
     job.state_off[l] = end;
     end += (((size_t)R * L.mh() * L.nthr * 8) + 255) & ~(size_t)255;
   }
+  for (int l = 0; l < S; l++) {  // (the coded weight memories: a pair of longs per code word)
+    const int cwpp = wecc_words_per_pe(net, hz.weight_code, l);
+    if (!rw[l] || !cwpp) continue;
+    job.wstate_off[l] = end;
+    job.wstate_words[l] = (uint32_t)cwpp * (uint32_t)net.L[l].fold.pe;
+    end += (((size_t)R * job.wstate_words[l] * 16) + 255) & ~(size_t)255;
+  }
   job.state_bytes = end - job.state_begin;
   return 0;
 }
@@ -3585,7 +3602,7 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
   if (exposure_scrubs(ex, t)) {
     if (replicate_blob(R, stride)) return -1;
     if (job.state_bytes) HIP_OK(hipMemsetAsync(r.d_camp + job.state_begin, 0, job.state_bytes, r.stream));
-  } else if (exposure_repairs(ex, t) && ex.longs == 8 && job.state_bytes) {
+  } else if (exposure_repairs(ex, t) && ex.longs >= 8 && job.state_bytes) {
     RepairTable tab{};
     int entries = 0;
     for (int l = 0; l < S; l++) {
@@ -3600,6 +3617,16 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
     unsigned long long *const d_rep = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * run_stride / 4 * 6 + (size_t)t * S * 2;
     const hipError_t re = repair_state(r.d_camp, tab, entries, R, d_rep, (size_t)E * S * 2, r.stream);
     if (re != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(re));
+    // the coded weight memories: one more launch over their state pairs, its counters behind all of those above
+    RepairTable wtab{};
+    int wentries = 0;
+    for (int l = 0; l < S; l++)
+      if (job.wstate_words[l]) wtab.e[wentries++] = RepairEntry{(unsigned long long)job.wstate_off[l], job.wstate_words[l], RK_CODED, (uint32_t)l, 0};
+    if (wentries) {
+      unsigned long long *const d_wst = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * E * S * 8 + (size_t)t * S * 4;
+      const hipError_t we = wrepair_state(r.d_camp, wtab, wentries, R, d_wst, (size_t)E * S * 4, r.stream);
+      if (we != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(we));
+    }
   }
   const int s0 = job.span_first[(size_t)t], s1 = job.span_first[(size_t)t + 1];
   hipError_t e = scatter_patches(r.d_camp, reinterpret_cast<const PatchSpan *>(r.d_camp + job.spans_off) + s0, s1 - s0, r.d_copies, r.stream);
@@ -3610,8 +3637,15 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
     EccOrg eo{MemOrg{1, 1, 0}, 0};
     ecc_layout(net, hz.scheme, hz.code, l, eo);  // (checked by mem_noise_check; weights of a layer >= 1 have one module)
     const MemOrg &org = eo.org;
-    e = xmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
-                     static_cast<const uint8_t *>(r.d_blob), d_counts, run_stride, r.stream);
+    if (job.wstate_words[l]) {
+      // a coded weight memory (weight_code 1 comes by the 12-long route alone): its status counters behind the eight
+      unsigned long long *const d_wst = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * E * S * 8 + (size_t)t * S * 4;
+      e = wmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
+                       static_cast<const uint8_t *>(r.d_blob), reinterpret_cast<unsigned long long *>(r.d_camp + job.wstate_off[l]), d_counts,
+                       run_stride, d_wst, (size_t)E * S * 4, r.stream);
+    } else
+      e = xmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
+                       static_cast<const uint8_t *>(r.d_blob), d_counts, run_stride, r.stream);
     // a flip may have removed the last -2 of a row (the loaded parameters may hold -2 rows, and so may an earlier epoch's state)
     if (e == hipSuccess && L.arith == AR_TT && rw[l] && (r.two_rows > 0 || t > 0)) e = mem_noise_flags(r.d_copies, stride, R, ml, r.stream);
     if (e == hipSuccess && rth[l] && eo.check_bits) {
@@ -3653,7 +3687,8 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const char *const who = en.who;
-  const bool eight = ex.longs == 8;        // the repair route: two repair counters behind the six
+  const bool twelve = ex.longs == 12;      // the coded weight route: four weight code word counters behind the eight
+  const bool eight = ex.longs >= 8;        // the repair route: two repair counters behind the six
   const bool six = eight || ex.longs == 6;  // the coded route: two decode-status counters behind the four
   std::vector<long> &last_counts = r.*en.counts;
   std::vector<unsigned long long> &last_seeds = r.*en.seeds;
@@ -3720,6 +3755,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
   std::vector<unsigned long long> counts((size_t)R * E * S * (en.plain ? 2 : 4), 0);
   std::vector<unsigned long long> status(six ? (size_t)R * E * S * 2 : 0, 0);  // (the coded route: [run][epoch][layer][2])
   std::vector<unsigned long long> repairs(eight ? (size_t)R * E * S * 2 : 0, 0);  // (the repair route: likewise)
+  std::vector<unsigned long long> wstatus(twelve ? (size_t)R * E * S * 4 : 0, 0);  // (the coded weight route: [run][epoch][layer][4])
   MemNoiseJob job;
   double device_us = 0.0;
   auto run = [&]() -> int {
@@ -3804,6 +3840,9 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     if (any && eight)
       HIP_OK(hipMemcpyAsync(repairs.data(), r.d_noise + counts_off + (counts.size() + status.size()) * 8, repairs.size() * 8, hipMemcpyDeviceToHost,
                             r.stream));
+    if (any && twelve)
+      HIP_OK(hipMemcpyAsync(wstatus.data(), r.d_noise + counts_off + (counts.size() + status.size() + repairs.size()) * 8, wstatus.size() * 8,
+                            hipMemcpyDeviceToHost, r.stream));
     if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
     else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
     HIP_OK(hipStreamSynchronize(r.stream));
@@ -3821,12 +3860,13 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     return nullptr;
   }
   if (six) {  // [run][epoch][layer]: the four counters, then the two decode-status counters, then (eight) the two repair counters
-    const size_t k = eight ? 8 : 6;
+    const size_t k = twelve ? 12 : eight ? 8 : 6;
     last_counts.resize(counts.size() / 4 * k);
     for (size_t b = 0; b < counts.size() / 4; b++) {
       for (int j = 0; j < 4; j++) last_counts[b * k + j] = (long)counts[b * 4 + j];
       for (int j = 0; j < 2; j++) last_counts[b * k + 4 + j] = (long)status[b * 2 + j];
       for (int j = 0; j < 2 && eight; j++) last_counts[b * k + 6 + j] = (long)repairs[b * 2 + j];
+      for (int j = 0; j < 4 && twelve; j++) last_counts[b * k + 8 + j] = (long)wstatus[b * 4 + j];
     }
   } else {
     last_counts.assign(counts.begin(), counts.end());
@@ -3975,7 +4015,7 @@ int *bnn_mi355x_hardened_mem_noise_campaigns(const char *path, int number_class,
 
 static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
                                    const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap,
-                                   int repair_every = -1);
+                                   int repair_every = -1, bool twelve = false);
 
 // (epoch 0 of a state that is never scrubbed)
 size_t bnn_mi355x_hardened_mem_noise_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
@@ -4022,11 +4062,11 @@ int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int schem
 // One copy stepped through epochs 0 ... epoch by the campaign's own steps (exposure_begin, exposure_epoch), then read back.
 static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
                                    const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap,
-                                   int repair_every) {
+                                   int repair_every, bool twelve) {
   Runtime &r = rt();
   // (room for the decode-status counters of a coded layer, and on the repair route -- repair_every >= 0 -- for the repair
   // counters; nothing reads them here)
-  const Exposure ex{1, scrub_every, repair_every < 0 ? 6 : 8, std::max(repair_every, 0)};
+  const Exposure ex{1, scrub_every, twelve ? 12 : repair_every < 0 ? 6 : 8, std::max(repair_every, 0)};
   if (epoch < 0 || epoch >= kMaxEpochs || scrub_every < 0) {
     fail(std::string(who) + ": epoch must be 0 ... " + std::to_string(kMaxEpochs - 1) + " and scrub_every must not be negative (0: never scrub)");
     return 0;
@@ -4095,20 +4135,22 @@ int bnn_mi355x_ecc_check_site(int scheme, int code, int layer, int ind, int bit,
   return 0;
 }
 
-long bnn_mi355x_ecc_exposure_mask(int scheme, int code, int burst, unsigned long long run_seed, int epoch, int layer, int target, int module,
-                                  unsigned int rate_q32, long first, int *records, int cap_records) {
+// (bnn_mi355x_ecc_exposure_mask, and with a weight code bnn_mi355x_wecc_exposure_mask)
+static long coded_exposure_mask(const std::string &who, int scheme, int code, int weight_code, int burst, unsigned long long run_seed, int epoch,
+                                int layer, int target, int module, unsigned int rate_q32, long first, int *records, int cap_records) {
   const NetSpec &net = rt().spec;
   EccOrg eo;
   const std::string e = ecc_layout(net, scheme, code, layer, eo);
-  if (!e.empty()) return fail("ecc_exposure_mask: " + e);
-  const long total =
-      first < 0 ? -1 : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0, epoch, code);
+  if (!e.empty()) return fail(who + ": " + e);
+  const long total = first < 0 ? -1
+                               : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0, epoch, code,
+                                                         weight_code);
   if (total < 0)
-    return fail("ecc_exposure_mask: bad burst (1 ... " + std::to_string(kMaxBurst) + "), epoch (0 ... " + std::to_string(kMaxEpochs - 1) +
+    return fail(who + ": bad burst (1 ... " + std::to_string(kMaxBurst) + "), epoch (0 ... " + std::to_string(kMaxEpochs - 1) +
                 "), target (0 weights, 1 thresholds), module (of those the memory has) or first");
   if (records && cap_records > 0 && first < total) {
     std::vector<PhysFault> v((size_t)std::min<long>(cap_records, total - first));
-    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size(), epoch, code);
+    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size(), epoch, code, weight_code);
     for (size_t i = 0; i < v.size(); i++) {
       const Fault &f = v[i].f;
       const int w[9] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size, v[i].module};
@@ -4116,6 +4158,12 @@ long bnn_mi355x_ecc_exposure_mask(int scheme, int code, int burst, unsigned long
     }
   }
   return total;
+}
+
+long bnn_mi355x_ecc_exposure_mask(int scheme, int code, int burst, unsigned long long run_seed, int epoch, int layer, int target, int module,
+                                  unsigned int rate_q32, long first, int *records, int cap_records) {
+  return coded_exposure_mask("ecc_exposure_mask", scheme, code, WC_NONE, burst, run_seed, epoch, layer, target, module, rate_q32, first, records,
+                             cap_records);
 }
 
 size_t bnn_mi355x_pack_params_ecc(const char *path, int scheme, int code, const int *records, int n_faults, void *dst, size_t cap) {
@@ -4171,27 +4219,33 @@ int bnn_mi355x_ecc_repair(unsigned int data, unsigned int check, unsigned int *o
   return status;
 }
 
-size_t bnn_mi355x_pack_params_repair(const char *path, int scheme, int code, const int *records, int n_faults, void *dst, size_t cap) {
+// (bnn_mi355x_pack_params_repair, and with a weight code bnn_mi355x_pack_params_wecc)
+static size_t pack_params_replayed(const std::string &who, const char *path, int scheme, int code, int weight_code, const int *records, int n_faults,
+                                   void *dst, size_t cap) {
   const NetSpec &net = rt().spec;
   EccOrg eo;
   const std::string le = ecc_layout(net, scheme, code, 0, eo);
-  if (!le.empty()) { fail("pack_params_repair: " + le); return 0; }
+  if (!le.empty()) { fail(who + ": " + le); return 0; }
   RawParams raw;
   const std::string e = read_raw_params(net, path ? path : "", raw);
   if (!e.empty()) { fail(e); return 0; }
   PhysParams loaded;
-  phys_load(net, scheme, raw, 0, net.nlayers, loaded, code);
+  phys_load(net, scheme, raw, 0, net.nlayers, loaded, code, weight_code);
   PhysParams phys = loaded;
-  const std::string re = phys_replay(net, scheme, code, loaded, phys, records, n_faults);
-  if (!re.empty()) { fail("pack_params_repair: " + re); return 0; }
-  phys_logical(net, scheme, phys, raw, code);
+  const std::string re = phys_replay(net, scheme, code, loaded, phys, records, n_faults, weight_code);
+  if (!re.empty()) { fail(who + ": " + re); return 0; }
+  phys_logical(net, scheme, phys, raw, code, nullptr, weight_code);
   std::vector<uint8_t> blob;
   pack_blob(net, raw, blob);
   if (dst) {
-    if (cap < blob.size()) { fail("pack_params_repair: destination too small"); return 0; }
+    if (cap < blob.size()) { fail(who + ": destination too small"); return 0; }
     std::memcpy(dst, blob.data(), blob.size());
   }
   return blob.size();
+}
+
+size_t bnn_mi355x_pack_params_repair(const char *path, int scheme, int code, const int *records, int n_faults, void *dst, size_t cap) {
+  return pack_params_replayed("pack_params_repair", path, scheme, code, WC_NONE, records, n_faults, dst, cap);
 }
 
 int *bnn_mi355x_repair_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst, int num_runs, unsigned long long seed,
@@ -4216,6 +4270,80 @@ size_t bnn_mi355x_repair_exposure_params(int scheme, int code, int burst, unsign
 int bnn_mi355x_last_repair_exposure_counts(long *counts, int cap) { return copy_out(rt().rmem_counts, counts, cap); }
 
 int bnn_mi355x_last_repair_exposure_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().rmem_seeds, seeds, cap); }
+
+// ---- coded weight memories in the exposure campaigns (the code: wecc.h; storage and upsets: mem_org.h) -------------------
+
+unsigned int bnn_mi355x_wecc_encode(unsigned long long data) { return wecc_encode(data); }
+
+int bnn_mi355x_wecc_decode(unsigned long long data, unsigned int check, unsigned long long *out_data) {
+  uint64_t d;
+  const int status = wecc_decode(data, check, &d);
+  if (out_data) *out_data = d;
+  return status;
+}
+
+int bnn_mi355x_wecc_repair(unsigned long long data, unsigned int check, unsigned long long *out_data, unsigned int *out_check) {
+  uint64_t d;
+  uint32_t c;
+  const int status = wecc_repair(data, check, &d, &c);
+  if (out_data) *out_data = d;
+  if (out_check) *out_check = c;
+  return status;
+}
+
+int bnn_mi355x_wecc_layout(int weight_code, int layer, int out[3]) {
+  const NetSpec &net = rt().spec;
+  const std::string e = wecc_check(weight_code);
+  if (!e.empty()) return fail("wecc_layout: " + e);
+  if (layer < 0 || layer >= net.nlayers) return fail("wecc_layout: layer must be 0 ... " + std::to_string(net.nlayers - 1));
+  const int cwpp = wecc_words_per_pe(net, weight_code, layer);
+  if (out) { out[0] = cwpp ? 1 : 0; out[1] = cwpp; out[2] = cwpp ? kWeccCheckBits : 0; }
+  return 0;
+}
+
+long bnn_mi355x_wecc_exposure_mask(int scheme, int code, int weight_code, int burst, unsigned long long run_seed, int epoch, int layer, int target,
+                                   int module, unsigned int rate_q32, long first, int *records, int cap_records) {
+  const std::string e = wecc_check(weight_code);
+  if (!e.empty()) return fail("wecc_exposure_mask: " + e);
+  return coded_exposure_mask("wecc_exposure_mask", scheme, code, weight_code, burst, run_seed, epoch, layer, target, module, rate_q32, first, records,
+                             cap_records);
+}
+
+size_t bnn_mi355x_pack_params_wecc(const char *path, int scheme, int code, int weight_code, const int *records, int n_faults, void *dst, size_t cap) {
+  const std::string e = wecc_check(weight_code);
+  if (!e.empty()) { fail("pack_params_wecc: " + e); return 0; }
+  return pack_params_replayed("pack_params_wecc", path, scheme, code, weight_code, records, n_faults, dst, cap);
+}
+
+int *bnn_mi355x_wecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int weight_code, int burst, int num_runs,
+                                        unsigned long long seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                        int epoch_images, int scrub_every, int repair_every, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  r.wmem_counts.clear();
+  r.wmem_seeds.clear();
+  const std::string e = wecc_check(weight_code);  // (before a device is looked for, like every refusal of the repair entry point)
+  if (!e.empty()) { fail("wecc_exposure_campaigns: " + e); return nullptr; }
+  const MemNoiseEntry en{"wecc_exposure_campaigns", &Runtime::wmem_counts, &Runtime::wmem_seeds, false, false, false, true};
+  return mem_noise_campaigns_impl(en, Hardening{scheme, burst, code, weight_code}, Exposure{epoch_images, scrub_every, 12, repair_every}, path,
+                                  number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number, usecPerImage);
+}
+
+size_t bnn_mi355x_wecc_exposure_params(int scheme, int code, int weight_code, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                       const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, int repair_every, void *dst,
+                                       size_t cap) {
+  const std::string e = wecc_check(weight_code);
+  if (!e.empty()) { fail("wecc_exposure_params: " + e); return 0; }
+  if (repair_every < 0) {
+    fail("wecc_exposure_params: repair_every must not be negative (0: never repair)");
+    return 0;
+  }
+  return exposure_params_impl("wecc_exposure_params", Hardening{scheme, burst, code, weight_code}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch,
+                              scrub_every, dst, cap, repair_every, true);
+}
+
+int bnn_mi355x_last_wecc_exposure_counts(long *counts, int cap) { return copy_out(rt().wmem_counts, counts, cap); }
+
+int bnn_mi355x_last_wecc_exposure_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().wmem_seeds, seeds, cap); }
 
 void free_results(int *result) { delete[] result; }
 

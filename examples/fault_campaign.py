@@ -93,6 +93,16 @@ for name in ("TMR", "interleaved + SEC-DED"):
         print("%-21s rewrite every %2d repair every %d: avg accuracy %.2f, last epoch %.2f, words repaired %d"
               % (name, every, repair, e["avg accuracy"], e["mean accuracy per epoch"][-1], sum(e.get("repaired words per epoch", [0]))))
 
+# the last unprotected memories: SEC-DED (72,64) over the weights of the layers >= 1, a (scheme, code, weight_code) triple.  TMR
+# plus coded weights is the first organisation in which every memory has redundancy; the same four schedules
+net.scrubbing_curve(os.path.join(out, "wecc"), 10, [2.0 ** -10], intervals, [(1, 0, 1), (0, 1, 1)], 100, seed=1)
+stats = json.load(open(os.path.join(out, "wecc", "cnvW1A1", "cifar10", "scrubbing", "cnvW1A1_cifar10_scrubbing_stats.json")))
+for name in ("TMR + SEC-DED weights", "none + SEC-DED + SEC-DED weights"):
+    for every, repair in intervals:
+        e = stats["results"]["%s burst 1 upset rate %g scrub every %d" % (name, 2.0 ** -10, every) + (" repair every %d" % repair if repair else "")]
+        print("%-32s rewrite every %2d repair every %d: avg accuracy %.2f, last epoch %.2f, weight code words repaired %d"
+              % (name, every, repair, e["avg accuracy"], e["mean accuracy per epoch"][-1], sum(e["repaired weight words per epoch"])))
+
 # the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
 net.input_upset_rate_curve(out, 10, rates, seed=1)
 for p in rates:

@@ -626,6 +626,59 @@ size_t bnn_mi355x_repair_exposure_params(int scheme, int code, int burst, unsign
 int bnn_mi355x_last_repair_exposure_counts(long *counts, int cap);
 int bnn_mi355x_last_repair_exposure_seeds(unsigned long long *seeds, int cap);
 
+/* Coded WEIGHT memories in the exposure campaigns: a third axis `weight_code` next to `scheme` and `code`.  0 none; 1
+ * SEC-DED (72,64) -- Hamming(71,64) plus an overall parity bit, what block RAM ECC is -- over the weight memory of every
+ * layer but CNV layer 0 (every layer >= 1 of the CNV nets, all four of the LFC nets).  Like the voter, the threshold code
+ * and the repair it is this project's own model (csrc/wecc.h, csrc/mem_org.h "coded weight memories"): parity unpinned.
+ *   Code word positions are 1 ... 71; positions 1, 2, 4, ..., 64 hold check bits c0 ... c6, the others in increasing order
+ *   data bits 0 ... 63; c7 is the XOR of all data bits and c0 ... c6.  Decode, with s the syndrome and P the overall
+ *   parity: P = 0, s = 0: status 0; P = 1 and s = 0 or a power of two: status 1, data as stored; P = 1 and s a data
+ *   position: status 1, that bit flipped; P = 1 and s > 71, or P = 0 and s != 0: status 2, data as stored.
+ * Code word q of a layer is sites [64 q, 64 q + 64) of its weight memory in the PE-major site order of
+ * enumerate_faults (2-bit weights: a site is one bit of an ap_int<2> field, a code word covers 32 columns).  Its 8 check
+ * bits are element q of a check memory of the layer's own, (PE, code word of the PE) shaped, addressed as MODULE 1 of
+ * target 0.  The data memory's events are exactly the uncoded campaign's records; the check memory draws by the same
+ * construction at element width 8 with module 1 in the counter word, at the layer's weight rate: record fields mem = PE,
+ * ind = code word of the PE, bit = g * burst, word_size = burst, an event the XOR of bits [bit, min(bit + burst, 8)).
+ * The logical weights are decode(data, check).  A repair epoch stores, per code word at status 1, the delivered data
+ * and its check bits, and writes nothing at status 0 or 2; a full rewrite clears the weight memories like every other.
+ * CNV layer 0 is not coded (3- or 6-bit elements, the host route, replicated by TMR).  weight_code 1 goes with every
+ * (scheme, code, repair_every) combination repair_exposure_campaigns accepts, TMR included.
+ * wecc_encode / wecc_decode / wecc_repair: host only; the 8 check bits; the decode status and in *out_data the delivered
+ * data; the status and what a repair leaves stored of (data, check).
+ * wecc_layout: out[0] 1 where the layer's weight memory is coded, out[1] its code words per PE, out[2] its check bits (8
+ * or 0).  Returns 0, or -1 + last_error for a weight_code outside 0 ... 1 or a bad layer.  Host only.
+ * wecc_exposure_mask: ecc_exposure_mask plus weight_code; module 1 of target 0 lists a coded layer's check events.
+ * pack_params_wecc: pack_params_repair plus weight_code: the same 9-int records and -1 / -2 markers.  Host only.
+ * wecc_exposure_campaigns: repair_exposure_campaigns' arguments, conventions and refusals plus weight_code (outside
+ * 0 ... 1: refused before a device is looked for) and num_runs * E * layers * 12 >= 2^31.
+ * wecc_exposure_params: the blob a run classifies epoch `epoch` with.
+ * last_wecc_exposure_counts: per [run][epoch][layer] twelve longs: the eight of last_repair_exposure_counts (weights
+ * physical [0] now counts data plus check bits, weights logical [1] the data bits that differ after decoding), then the
+ * weight code words [8] at status 1 and [9] at status 2 after the epoch, [10] those the epoch's repair rewrote and [11]
+ * those whose stored state still differs from the loaded one after the repair.  Returns runs * E * layers * 12.
+ * With weight_code 0 every one of these returns its predecessor's result bit for bit ([8] ... [11] are 0); the last_*
+ * state is these entry points' own. */
+unsigned int bnn_mi355x_wecc_encode(unsigned long long data);
+int bnn_mi355x_wecc_decode(unsigned long long data, unsigned int check, unsigned long long *out_data);
+int bnn_mi355x_wecc_repair(unsigned long long data, unsigned int check, unsigned long long *out_data,
+                           unsigned int *out_check);
+int bnn_mi355x_wecc_layout(int weight_code, int layer, int out[3]);
+long bnn_mi355x_wecc_exposure_mask(int scheme, int code, int weight_code, int burst, unsigned long long run_seed,
+                                   int epoch, int layer, int target, int module, unsigned int rate_q32, long first,
+                                   int *records, int cap_records);
+size_t bnn_mi355x_pack_params_wecc(const char *path, int scheme, int code, int weight_code, const int *records,
+                                   int n_faults, void *dst, size_t cap);
+int *bnn_mi355x_wecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int weight_code,
+                                        int burst, int num_runs, unsigned long long seed, const unsigned int *rate_w_q32,
+                                        const unsigned int *rate_t_q32, int n_rates, int epoch_images, int scrub_every,
+                                        int repair_every, int *image_number, float *usecPerImage);
+size_t bnn_mi355x_wecc_exposure_params(int scheme, int code, int weight_code, int burst, unsigned long long run_seed,
+                                       const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                       int epoch, int scrub_every, int repair_every, void *dst, size_t cap);
+int bnn_mi355x_last_wecc_exposure_counts(long *counts, int cap);
+int bnn_mi355x_last_wecc_exposure_seeds(unsigned long long *seeds, int cap);
+
 /* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
  * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column
  * l = the output of layer l, l = 0 ... 7 (layers 1 and 3: after the max-pool); LFC column l = the output of layer l,

@@ -1,0 +1,216 @@
+"""Coded weight memories in the exposure campaigns, on the GPU (bnn_mi355x_wecc_exposure_campaigns; the model: csrc/mem_org.h
+"coded weight memories", csrc/wecc.h).  All checks are exact.
+
+The model is pinned on the host: bnn_mi355x_pack_params_wecc applies an ordered list of physical records with repair and
+rewrite markers (tests/test_wecc_pack.py, against the plain-Python route of tests/wecc_ref.py).  The blob of (run, epoch
+t) must be pack_params_wecc of the marker-and-mask stream of epochs 0 ... t; bnn_mi355x_wecc_exposure_params reads back
+the very blob the device classifies that epoch with, and the epoch's classes are compared with import_params(blob) +
+inference_buffer in a second library handle.  The twelve counts are what wecc_ref's stepped code words give.
+
+The shape (wecc_ref.GPU_*): 3 runs x 24 images, 4 epochs of 6, every rate 2^-7 per epoch (CNV layer 0's rates 0 in the
+coded-threshold cases), bursts 1 and 2, four schedules -- never, a repair every epoch, a repair every epoch with a rewrite
+before epoch 2, a rewrite every epoch.  What these seeds hold (status 1, status 2, accepted triples, repairs that lock in a
+wrong word) is asserted on the CPU (tests/test_wecc_pack.py, the coverage condition)."""
+import ctypes as C
+import faulthandler
+import struct
+
+import numpy as np
+import pytest
+
+import gpu_lib as gl
+import repair_ref as rr
+import test_gpu_act_fault_sweep as sw
+import test_gpu_mem_noise as gm
+import test_gpu_repair_exposure as gr
+import wecc_ref as wr
+
+pytestmark = pytest.mark.gpu
+RUNS, N, EI, E, SEED = wr.GPU_RUNS, wr.GPU_IMAGES, wr.GPU_EPOCH_IMAGES, wr.GPU_EPOCHS, wr.GPU_SEED
+CASES = [(n, s, c, b) for n, cases in sorted(wr.GPU_CASES.items()) for s, c, b in cases]
+
+
+@pytest.fixture(autouse=True)
+def _time_limit():
+    """every test runs in this process under a limit of its own (a case takes a few seconds): a device call that hangs
+    ends the process with a traceback, and nothing more is started on the card"""
+    faulthandler.dump_traceback_later(180, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+def wcampaign(L, path, scheme, code, weight_code, burst, runs, seed, rw, rt, epoch_images, scrub_every=0, repair_every=0, ncls=10):
+    """-> (classes [runs, n], counts [runs, epochs, layers, 12], seeds [runs])"""
+    up = C.c_uint * len(rw)
+    cnt, usec = C.c_int(0), C.c_float(0)
+    p = L.bnn_mi355x_wecc_exposure_campaigns(path.encode(), ncls, scheme, code, weight_code, burst, runs, seed, up(*rw), up(*rt), len(rw),
+                                             epoch_images, scrub_every, repair_every, C.byref(cnt), C.byref(usec))
+    assert p, L.bnn_mi355x_last_error().decode()
+    n = cnt.value
+    got = np.ctypeslib.as_array(p, shape=(max(runs * n, 1),))[: runs * n].copy().reshape(runs, n)
+    L.free_results(p)
+    epochs = -(-n // epoch_images)
+    k = L.bnn_mi355x_last_wecc_exposure_counts(None, 0)
+    assert k == runs * epochs * len(rw) * 12
+    c = (C.c_long * k)()
+    assert L.bnn_mi355x_last_wecc_exposure_counts(c, k) == k
+    s = (C.c_ulonglong * runs)()
+    assert L.bnn_mi355x_last_wecc_exposure_seeds(s, runs) == runs
+    return got, np.array(c[:], np.int64).reshape(runs, epochs, len(rw), 12), list(s)
+
+
+def wdevice_blob(L, scheme, code, weight_code, burst, seed, rw, rt, epoch, scrub_every=0, repair_every=0):
+    up = C.c_uint * len(rw)
+    size = L.bnn_mi355x_wecc_exposure_params(scheme, code, weight_code, burst, seed, up(*rw), up(*rt), len(rw), epoch, scrub_every, repair_every,
+                                             None, 0)
+    assert size > 0, L.bnn_mi355x_last_error().decode()
+    blob = np.zeros(size, np.uint8)
+    assert L.bnn_mi355x_wecc_exposure_params(scheme, code, weight_code, burst, seed, up(*rw), up(*rt), len(rw), epoch, scrub_every, repair_every,
+                                             blob.ctypes.data, size) == size
+    return blob
+
+
+def drawn_epochs(L, network, scheme, code, burst, seed, rw, rt):
+    """the library's masks of every epoch; the check memories' (thresholds and weights), layer 0's and every threshold
+    memory's restated in plain Python"""
+    out = []
+    for t in range(E):
+        recs = wr.lib_epoch_events(L, network, scheme, code, 1, burst, seed, t, rw, rt)
+        for key, mine in wr.epoch_events(network, scheme, code, 1, burst, seed, t, rw, rt, lambda l, target: target == 1 or l == 0).items():
+            assert mine.shape == recs[key].shape and (mine == recs[key]).all(), (t, key)
+        for l in wr.coded_layers(network, 1):
+            mine = wr.check_events(network, burst, seed, t, l, rw[l])
+            assert mine.shape == recs[(l, 0, 1)].shape and (mine == recs[(l, 0, 1)]).all(), (t, l)
+        out.append(recs)
+    return out
+
+
+def row_flags(blob, layer):
+    off, rd, rows, kw = struct.unpack_from("<4I", blob, 32 + 16 * layer)
+    return blob[off: off + rows * rd * 4].view(np.uint32).reshape(rows, rd)[:, 2 + 6 * kw]
+
+
+@pytest.mark.parametrize("network,scheme,code,burst", CASES, ids=str)
+def test_coded_weights(network, scheme, code, burst, tmp_path, monkeypatch):
+    """the four schedules: for every run and epoch the device's blob is pack_params_wecc of the marker-and-mask stream of
+    epochs 0 ... t, byte for byte; the epoch's classes are those of that blob in a second library handle; the twelve
+    counts are wecc_ref's"""
+    L, pdir = gm.load(network, wr.GPU_DATASET[network])
+    L2 = gl.load(network, "python_hw")  # a second handle: importing a blob drops the raw memories the campaign draws in
+    imgs = sw.images(network, N, seed=29)
+    path = sw.write_images(network, imgs, tmp_path)
+    clean_cls = gm.clean_classes(L, path)
+    crc = L.bnn_mi355x_params_crc()
+    rw, rt = wr.gpu_rates(network, code)
+    coded = wr.coded_layers(network, 1)
+    runs_epochs = [drawn_epochs(L, network, scheme, code, burst, SEED + r, rw, rt) for r in range(RUNS)]
+    monkeypatch.setenv("BNN_MI355X_NOISE_GROUP", "37")
+    changed = cleared = 0
+    for every, repair in wr.GPU_SCHEDULES:
+        what = "%s scheme %d code %d burst %d scrub every %d repair every %d" % (network, scheme, code, burst, every, repair)
+        ref = [wr.campaign_counts(network, scheme, code, 1, pdir, runs_epochs[r], every, repair) for r in range(RUNS)]
+        want_counts = np.array([c for c, _ in ref])
+        assert (want_counts[:, :, coded, 0] > 0).all() and want_counts[:, :, coded, 9].sum() > 0, what
+        if repair == 0:
+            assert (want_counts[..., 10:] == 0).all() and (want_counts[..., 6:8] == 0).all()
+        else:
+            assert (want_counts[:, 0, :, 10:] == 0).all() and want_counts[:, 1:, coded, 11].sum() > 0
+        not_coded = [l for l in range(want_counts.shape[2]) if l not in coded]
+        assert (want_counts[:, :, not_coded, 8:] == 0).all()
+        classes = []
+        for r in range(RUNS):
+            classes.append([])
+            before = None
+            for t in range(E):
+                blob = wr.lib_pack(L, pdir, scheme, code, 1, rr.stream(runs_epochs[r], t, every, repair))
+                gm.assert_same_bytes(wdevice_blob(L, scheme, code, 1, burst, SEED + r, rw, rt, t, every, repair), blob, what + " run %d epoch %d" % (r, t))
+                classes[-1].append(gm.classify_with_blob(L2, blob, imgs))
+                if network == "cnvW2A2":  # rows that lose their last -2 without a rewrite: the flag must go back to 0
+                    now = np.concatenate([row_flags(blob, l) for l in coded])
+                    if before is not None and not rr.rewrites(t, every):
+                        cleared += int(((before == 1) & (now == 0)).sum())
+                    before = now
+        got, counts, seeds = wcampaign(L, path, scheme, code, 1, burst, RUNS, SEED, rw, rt, EI, every, repair)
+        assert seeds == [SEED + r for r in range(RUNS)]
+        assert counts.tolist() == want_counts.tolist(), what
+        for r in range(RUNS):
+            for t in range(E):
+                want = classes[r][t][t * EI: (t + 1) * EI]
+                assert got[r, t * EI: (t + 1) * EI].tolist() == want.tolist(), what + " run %d epoch %d" % (r, t)
+                changed += int((want != clean_cls[t * EI: (t + 1) * EI]).sum())
+    if network == "cnvW2A2":
+        print("rows whose last -2 went away without a rewrite:", cleared)
+        assert cleared > 0
+    assert changed > 0 and L.bnn_mi355x_params_crc() == crc
+    assert gm.clean_classes(L, path).tolist() == clean_cls.tolist()
+
+
+@pytest.mark.parametrize("network,scheme,code", [("cnvW1A1", 1, 0), ("cnvW1A1", 2, 1), ("cnvW2A2", 0, 1), ("lfcW1A1", 0, 1), ("lfcW1A2", 0, 0)], ids=str)
+def test_weight_code_0_is_the_repair_exposure_campaign(network, scheme, code, tmp_path, monkeypatch):
+    """burst 2, scrub every 3, repair every 1: classes, seeds, the eight counts and the blob of every epoch equal
+    repair_exposure_campaigns' / repair_exposure_params' bit for bit; counts 8 ... 11 are 0; the repair entry point's last_*
+    state is not this one's"""
+    L, pdir = gm.load(network, wr.GPU_DATASET[network])
+    path = sw.write_images(network, sw.images(network, N, seed=17), tmp_path)
+    monkeypatch.setenv("BNN_MI355X_NOISE_GROUP", "37")
+    rw, rt = wr.gpu_rates(network, 0)
+    want, wcounts, wseeds = gr.rcampaign(L, path, scheme, code, 2, RUNS, SEED, rw, rt, EI, 3, 1)
+    got, counts, seeds = wcampaign(L, path, scheme, code, 0, 2, RUNS, SEED + 1, rw, rt, EI, 3, 1)  # (another seed: the states are apart)
+    s = (C.c_ulonglong * RUNS)()
+    L.bnn_mi355x_last_repair_exposure_seeds(s, RUNS)
+    assert list(s) == wseeds and seeds == [SEED + 1 + r for r in range(RUNS)]
+    got, counts, seeds = wcampaign(L, path, scheme, code, 0, 2, RUNS, SEED, rw, rt, EI, 3, 1)
+    assert seeds == wseeds and got.tolist() == want.tolist()
+    assert counts[..., :8].tolist() == wcounts.tolist() and (counts[..., 8:] == 0).all()
+    assert wcounts[..., 0].sum() > 0 and (want != gm.clean_classes(L, path)[None]).any()
+    for r in range(RUNS):
+        for t in range(E):
+            gm.assert_same_bytes(wdevice_blob(L, scheme, code, 0, 2, SEED + r, rw, rt, t, 3, 1), gr.rdevice_blob(L, scheme, code, 2, SEED + r, rw, rt, t, 3, 1),
+                                 "%s scheme %d code %d run %d epoch %d" % (network, scheme, code, r, t))
+
+
+def test_rate_0_and_refusals(tmp_path):
+    """all rates 0: the fault-free classes once per run, all counts 0; a weight rate of 0 in one coded layer leaves that
+    layer's counts 0; refusals with a device present return NULL / 0 with a reason and leave no counts"""
+    network = "cnvW1A1"
+    L, pdir = gm.load(network, "cifar10")
+    path = sw.write_images(network, sw.images(network, N, seed=4), tmp_path)
+    clean = gm.clean_classes(L, path)
+    z = [0] * 9
+    got, counts, _ = wcampaign(L, path, 1, 0, 1, 1, RUNS, 5, z, z, EI, 0, 1)
+    assert (got == clean[None]).all() and (counts == 0).all()
+    assert (wdevice_blob(L, 1, 0, 1, 1, 5, z, z, 3, 0, 1) == gl.pack_params(network, pdir)).all()
+    rw, rt = wr.gpu_rates(network, 0)
+    rw[4] = 0
+    got, counts, _ = wcampaign(L, path, 0, 0, 1, 1, RUNS, 5, rw, rt, EI, 0, 1)
+    assert (counts[:, :, 4, [0, 1, 8, 9, 10, 11]] == 0).all() and (counts[:, :, 3, 0] > 0).all()
+    up = C.c_uint * 9
+    for wc in (-1, 2):
+        assert not L.bnn_mi355x_wecc_exposure_campaigns(path.encode(), 10, 0, 0, wc, 1, 1, 1, up(*rw), up(*rt), 9, EI, 0, 1, None, None)
+        assert b"wecc_exposure_campaigns: weight_code must be 0 (none) or 1" in L.bnn_mi355x_last_error()
+        assert L.bnn_mi355x_last_wecc_exposure_counts(None, 0) == 0 and L.bnn_mi355x_last_wecc_exposure_seeds(None, 0) == 0
+        assert L.bnn_mi355x_wecc_exposure_params(0, 0, wc, 1, 1, up(*rw), up(*rt), 9, 1, 0, 1, None, 0) == 0
+        assert b"wecc_exposure_params: weight_code must be" in L.bnn_mi355x_last_error()
+    assert not L.bnn_mi355x_wecc_exposure_campaigns(path.encode(), 10, 1, 1, 1, 1, 1, 1, up(*rw), up(*rt), 9, EI, 0, 1, None, None)
+    assert b"TMR plus a code is not modelled" in L.bnn_mi355x_last_error()
+    assert gm.clean_classes(L, path).tolist() == clean.tolist()
+
+
+def test_python_interface(tmp_path):
+    """FaultTest.run_exposure_test(..., weight_code=1) returns what the C call returns; with weight_code 0 it keeps its entry
+    points"""
+    from bnn.faults import faults
+    network, dataset = "cnvW1A1", "cifar10"
+    L, pdir = gm.load(network, dataset)
+    n, runs, seed, ei = 20, 2, 77, 8
+    imgs = sw.images(network, n, seed=21)
+    path = sw.write_images(network, imgs, tmp_path, network)
+    labels = gm.clean_classes(L, path).tolist()
+    ft = faults.CNVFaultTest(network, dataset, path, labels)
+    rw, rt = gm.rates(network, 2.0 ** -7, 2.0 ** -7)
+    acc, cnts = ft.run_exposure_test(runs, 2.0 ** -7, 2.0 ** -7, ei, scrub_every=0, scheme=1, burst=1, seed=seed, repair_every=1, weight_code=1)
+    got, counts, _ = wcampaign(L, path, 1, 0, 1, 1, runs, seed, rw, rt, ei, 0, 1)
+    assert ft.exposure_results.tolist() == got.tolist() and cnts.tolist() == counts.tolist() and cnts.shape == (runs, 3, 9, 12)
+    assert cnts[:, 1:, 1:, 10].sum() > 0
+    _, eight = ft.run_exposure_test(runs, 2.0 ** -7, 2.0 ** -7, ei, scrub_every=0, scheme=1, burst=1, seed=seed, repair_every=1)
+    assert eight.shape == (runs, 3, 9, 8) and eight.tolist() == gr.rcampaign(L, path, 1, 0, 1, runs, seed, rw, rt, ei, 0, 1)[1].tolist()

@@ -40,7 +40,9 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_last_repair_exposure_counts", "bnn_mi355x_last_repair_exposure_seeds", "bnn_mi355x_wecc_encode",
        "bnn_mi355x_wecc_decode", "bnn_mi355x_wecc_repair", "bnn_mi355x_wecc_layout", "bnn_mi355x_wecc_exposure_mask",
        "bnn_mi355x_pack_params_wecc", "bnn_mi355x_wecc_exposure_campaigns", "bnn_mi355x_wecc_exposure_params",
-       "bnn_mi355x_last_wecc_exposure_counts", "bnn_mi355x_last_wecc_exposure_seeds"]
+       "bnn_mi355x_last_wecc_exposure_counts", "bnn_mi355x_last_wecc_exposure_seeds", "bnn_mi355x_iwecc_layout",
+       "bnn_mi355x_iwecc_site", "bnn_mi355x_pack_params_iwecc", "bnn_mi355x_iwecc_exposure_campaigns",
+       "bnn_mi355x_iwecc_exposure_params", "bnn_mi355x_last_iwecc_exposure_counts", "bnn_mi355x_last_iwecc_exposure_seeds"]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -223,6 +225,20 @@ def declare_extensions(L):
         L.bnn_mi355x_wecc_exposure_params.restype = C.c_size_t
         L.bnn_mi355x_last_wecc_exposure_counts.argtypes = [C.POINTER(C.c_long), C.c_int]
         L.bnn_mi355x_last_wecc_exposure_seeds.argtypes = [ullp, C.c_int]
+    if hasattr(L, "bnn_mi355x_iwecc_exposure_campaigns"):  # (likewise)
+        up = C.POINTER(C.c_uint)
+        L.bnn_mi355x_iwecc_layout.argtypes = [C.c_int, C.c_int, C.c_int, ip]
+        L.bnn_mi355x_iwecc_site.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.POINTER(C.c_long)]
+        L.bnn_mi355x_pack_params_iwecc.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_pack_params_iwecc.restype = C.c_size_t
+        L.bnn_mi355x_iwecc_exposure_campaigns.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
+                                                          up, up, C.c_int, C.c_int, C.c_int, C.c_int, ip, fp]
+        L.bnn_mi355x_iwecc_exposure_campaigns.restype = ip
+        L.bnn_mi355x_iwecc_exposure_params.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, up, up, C.c_int, C.c_int,
+                                                       C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_iwecc_exposure_params.restype = C.c_size_t
+        L.bnn_mi355x_last_iwecc_exposure_counts.argtypes = [C.POINTER(C.c_long), C.c_int]
+        L.bnn_mi355x_last_iwecc_exposure_seeds.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     L.bnn_mi355x_pack_params_faulty.argtypes = [C.c_char_p, ip, C.c_int, C.c_void_p, C.c_size_t]
     L.bnn_mi355x_pack_params_faulty.restype = C.c_size_t
     L.bnn_mi355x_debug_stage_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]

@@ -415,7 +415,7 @@ class PynqBNN:
 
     # extension: exposure campaigns (upsets that accumulate over epochs of images, with scrubbing)
     def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0, code=0,
-                                    repair_every=0, weight_code=0):
+                                    repair_every=0, weight_code=0, weight_interleave=0):
         """inference_multiple_hardened_mem_noise spread over time: the run is cut into epochs of `epoch_images` images, the
         rates are per epoch, an epoch's upsets XOR onto the physical state the earlier ones left, and before every epoch
         t > 0 with t % scrub_every == 0 (0: never) all memories are rewritten from the loaded parameters.  -> (classes
@@ -423,7 +423,11 @@ class PynqBNN:
         the epoch, logical bits that differ from the loaded parameters after it)).  The seeds are left in
         self.mem_noise_seeds.  code 1 (SEC-DED coded 16-bit threshold memories): inference_multiple_ecc_exposure;
         repair_every > 0 (repair scrubs): inference_multiple_repair_exposure; weight_code 1 (SEC-DED (72,64) coded weight
-        memories): inference_multiple_wecc_exposure."""
+        memories): inference_multiple_wecc_exposure; weight_interleave 1 (their code words column-interleaved):
+        inference_multiple_iwecc_exposure."""
+        if weight_interleave:
+            return self.inference_multiple_iwecc_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, repair_every, scheme, code,
+                                                          weight_code, weight_interleave, burst, seed)
         if weight_code:
             return self.inference_multiple_wecc_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, repair_every, scheme, code,
                                                          weight_code, burst, seed)
@@ -541,6 +545,38 @@ class PynqBNN:
         lib.bnn_mi355x_last_wecc_exposure_counts(counts, k)
         seeds = (ctypes.c_ulonglong * num_runs)()
         lib.bnn_mi355x_last_wecc_exposure_seeds(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        epochs = -(-size.value // epoch_images)
+        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 12)
+
+    # extension: column-interleaved code words over the coded weight memories
+    def inference_multiple_iwecc_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, repair_every=0, scheme=0, code=0,
+                                          weight_code=1, weight_interleave=1, burst=1, seed=0):
+        """inference_multiple_wecc_exposure with the (72,64) code words of a layer's weight memory COLUMN-INTERLEAVED
+        (`weight_interleave` 1; 0: not, and then this is inference_multiple_wecc_exposure's result): at depth D = gcd(16,
+        code words per PE) adjacent columns of a memory word lie in D different code words, so a burst of up to D bits
+        is D single errors, each corrected -- where without it an aligned burst of 2 is a double error of one code word
+        and nothing is corrected.  The weights stay where they were and the upsets are the same events; only which code
+        word a bit belongs to changes.  Needs weight_code 1.  -> (classes int32 (num_runs, n), counts int64 (num_runs,
+        epochs, layers, 12) as inference_multiple_wecc_exposure, the code words counted after gathering).  The seeds are
+        left in self.mem_noise_seeds."""
+        lib = self.interface
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_iwecc_exposure_campaigns(path.encode(), len(self.classes), scheme, code, weight_code, weight_interleave, burst,
+                                                      num_runs, seed, qw.ctypes.data_as(up), qt.ctypes.data_as(up), len(qw), epoch_images,
+                                                      scrub_every, repair_every, ctypes.byref(size), ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError("iwecc exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        k = lib.bnn_mi355x_last_iwecc_exposure_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        lib.bnn_mi355x_last_iwecc_exposure_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        lib.bnn_mi355x_last_iwecc_exposure_seeds(seeds, num_runs)
         self.mem_noise_seeds = list(seeds)
         self.usecPerImage = usec.value
         epochs = -(-size.value // epoch_images)

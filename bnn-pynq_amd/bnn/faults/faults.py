@@ -72,6 +72,8 @@ HARDENING_SCHEMES = ("none", "TMR", "interleaved", "resilient-interleaved")
 ECC_CODES = ("", "SEC-DED")
 # the codes of the weight memories of the layers >= 1 (csrc/wecc.h), by the weight_code number; the project's own model
 WEIGHT_CODES = ("", "SEC-DED weights")
+# the column interleave of those code words (csrc/mem_org.h, "column-interleaved code words"), by the weight_interleave number
+WEIGHT_INTERLEAVES = ("", "column-interleaved")
 
 
 def scheme_and_code(entry):
@@ -84,8 +86,14 @@ def scheme_code_and_weight_code(entry):
     return scheme_and_code(entry) + ((int(entry[2]),) if isinstance(entry, (tuple, list)) and len(entry) > 2 else (0,))
 
 
-def organisation_name(scheme, code=0, weight_code=0):
-    return HARDENING_SCHEMES[scheme] + (" + " + ECC_CODES[code] if code else "") + (" + " + WEIGHT_CODES[weight_code] if weight_code else "")
+def scheme_codes_and_interleave(entry):
+    """likewise, a (scheme, code, weight_code, weight_interleave) 4-tuple as well"""
+    return scheme_code_and_weight_code(entry) + ((int(entry[3]),) if isinstance(entry, (tuple, list)) and len(entry) > 3 else (0,))
+
+
+def organisation_name(scheme, code=0, weight_code=0, weight_interleave=0):
+    return HARDENING_SCHEMES[scheme] + (" + " + ECC_CODES[code] if code else "") + (" + " + WEIGHT_CODES[weight_code] if weight_code else "") + \
+        (" " + WEIGHT_INTERLEAVES[weight_interleave] if weight_interleave else "")
 
 
 def hardening_of(overlay):
@@ -255,8 +263,9 @@ class FaultTest:
         print()
         return accuracies
 
-    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1, code=0, weight_code=0):
-        """weight_code 1 (SEC-DED (72,64) coded weight memories of the layers >= 1, csrc/wecc.h; any scheme and code): likewise
+    def run_memory_noise_test(self, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1, code=0, weight_code=0, weight_interleave=0):
+        """weight_interleave 1 (with weight_code 1: the code words column-interleaved, csrc/mem_org.h): the same through
+        inference_multiple_iwecc_exposure.  weight_code 1 (SEC-DED (72,64) coded weight memories of the layers >= 1, csrc/wecc.h; any scheme and code): likewise
         one epoch of the exposure campaign, the counts [run, layer, 12] as run_exposure_test's.  code 1 (SEC-DED coded threshold memories, csrc/ecc.h; scheme 0 or 2): the exposure campaign with one epoch, which
         is the one-shot campaign; the counts are then [run, layer, 6] as run_exposure_test's.  scheme (0 ... 3, HARDENING_SCHEMES) or burst > 1: the upsets hit the physical memories of that hardened
         organisation in bursts of `burst` adjacent bits, and the counts are [run, layer, 2, 2: physical bits flipped,
@@ -268,10 +277,12 @@ class FaultTest:
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, memory upset rate(s) weights {} thresholds {}".format(
             self.network, self.dataset, num_runs, rates_w, rates_t))
+        if weight_interleave and not weight_code:
+            raise ValueError("run_memory_noise_test: weight_interleave 1 needs weight_code 1")
         if weight_code:
-            print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code, weight_code), burst))
+            print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code, weight_code, weight_interleave), burst))
             results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, 1 << 30, 0, scheme or 0, burst, seed, code, 0,
-                                             weight_code)
+                                             weight_code, *((weight_interleave,) if weight_interleave else ()))
             counts = counts[:, 0]
         elif code:
             print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code), burst))
@@ -289,7 +300,7 @@ class FaultTest:
         return accuracies, counts
 
     def run_exposure_test(self, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=None, burst=1, seed=0, code=0, repair_every=0,
-                          weight_code=0):
+                          weight_code=0, weight_interleave=0):
         """Upsets that accumulate while the run goes on: the images are cut into epochs of `epoch_images`, rates_w[L] /
         rates_t[L] are the probability of an event PER EPOCH (scalars: every layer), an epoch's upsets XOR onto the physical
         state of the hardened organisation `scheme` (None: 0) the earlier epochs left, and every `scrub_every` epochs (0:
@@ -310,10 +321,11 @@ class FaultTest:
         classifier = self.classifier_cls(self.network, self.dataset, self.runtime)
         print("{}-{}: {} run(s) in one call, epochs of {} images, upset rate(s) per epoch weights {} thresholds {}, {}, bursts of {}, "
               "scrub every {}{}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t,
-                                        organisation_name(scheme or 0, code, weight_code), burst, scrub_every or "never",
+                                        organisation_name(scheme or 0, code, weight_code, weight_interleave), burst, scrub_every or "never",
                                         ", repair every {}".format(repair_every) if repair_every else ""))
         args = (num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst, seed)
-        results, counts = self._classify(classifier, "_exposure", *(args + (code, repair_every, weight_code) if weight_code else
+        results, counts = self._classify(classifier, "_exposure", *(args + (code, repair_every, weight_code, weight_interleave) if weight_interleave else
+                                                                    args + (code, repair_every, weight_code) if weight_code else
                                                                     args + (code, repair_every) if repair_every else args + (code,) if code else args))
         self.exposure_results, self.exposure_counts, self.exposure_usec = results, counts, classifier.usecPerImage
         accuracies = [[util.calculate_accuracy(row[i: i + epoch_images].tolist(), self.labels[i: i + epoch_images])
@@ -634,21 +646,25 @@ class NetworkTest:
         coded threshold memories): its name is "<scheme name> + SEC-DED", and it also writes "code", "corrected words" and
         "detected words".  A (scheme, code, weight_code) triple (weight_code 1: SEC-DED (72,64) coded weight memories):
         the name holds " + SEC-DED weights", and it also writes "weight code", "corrected weight words" and "detected weight
-        words"."""
+        words".  A (scheme, code, weight_code, weight_interleave) 4-tuple (weight_interleave 1: those code words
+        column-interleaved): the name ends in " column-interleaved", and it also writes "weight interleave"."""
         ft = self.fault_test
         folder = "{}/{}/{}/hardening/".format(output_folder, ft.network, ft.dataset)
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme, code, weight_code in map(scheme_code_and_weight_code, schemes):
+        for scheme, code, weight_code, weight_interleave in map(scheme_codes_and_interleave, schemes):
             for burst in bursts:
                 for p in rates:
                     accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, scheme, burst, code,
-                                                                  *((weight_code,) if weight_code else ()))
-                    name = "{} burst {} upset rate {:g}".format(organisation_name(scheme, code, weight_code), burst, p)
+                                                                  *((weight_code, weight_interleave) if weight_interleave else
+                                                                    (weight_code,) if weight_code else ()))
+                    name = "{} burst {} upset rate {:g}".format(organisation_name(scheme, code, weight_code, weight_interleave), burst, p)
                     raw.append(self._raw(name, num_runs, 0, [], accuracies))
                     extra[name] = {"stddev accuracy": float(np.std(accuracies)), "scheme": int(scheme), "burst": int(burst), "rate": float(p)}
                     if weight_code:  # [run, layer, 12]
+                        if weight_interleave:
+                            extra[name]["weight interleave"] = int(weight_interleave)
                         extra[name].update({"weight code": int(weight_code), "corrected weight words": int(counts[..., 8].sum()),
                                             "detected weight words": int(counts[..., 9].sum())})
                         counts = counts[..., :6] if code else counts[..., :4].reshape(counts.shape[:2] + (2, 2))
@@ -677,24 +693,28 @@ class NetworkTest:
         ends in " repair every <P>" and the result also holds "repair every", "repaired words per epoch" and "unrepaired
         words per epoch" (summed over the runs).  An entry of `schemes` may also be a (scheme, code, weight_code) triple
         (weight_code 1: SEC-DED (72,64) coded weight memories of the layers >= 1): the name holds " + SEC-DED weights", and the
-        result also holds "weight code" and the "corrected / detected / repaired / unrepaired weight words per epoch"."""
+        result also holds "weight code" and the "corrected / detected / repaired / unrepaired weight words per epoch"; a
+        (scheme, code, weight_code, weight_interleave) 4-tuple (weight_interleave 1: those code words column-interleaved)
+        adds " column-interleaved" to the name and "weight interleave" to the result."""
         ft = self.fault_test
         folder = "{}/{}/{}/scrubbing/".format(output_folder, ft.network, ft.dataset)
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme, code, weight_code in map(scheme_code_and_weight_code, schemes):
+        for scheme, code, weight_code, weight_interleave in map(scheme_codes_and_interleave, schemes):
             for burst in bursts:
                 for p in rates:
                     for every in scrub_intervals:
                         every, repair = (int(every[0]), int(every[1])) if isinstance(every, (tuple, list)) else (every, 0)
                         per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed, code,
-                                                                 *((repair, weight_code) if weight_code else (repair,) if repair else ()))
+                                                                 *((repair, weight_code, weight_interleave) if weight_interleave else
+                                                                   (repair, weight_code) if weight_code else (repair,) if repair else ()))
                         accuracies = [util.calculate_accuracy(row.tolist(), ft.labels) for row in ft.exposure_results]
-                        name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(scheme, code, weight_code), burst, p, every)
+                        name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(scheme, code, weight_code, weight_interleave), burst,
+                                                                                   p, every)
                         status = {}
                         if weight_code:  # [run, epoch, layer, 12]: the weight code words' four counters behind the repair shape
-                            status = {"weight code": int(weight_code),
+                            status = {**({"weight interleave": int(weight_interleave)} if weight_interleave else {}), "weight code": int(weight_code),
                                       "corrected weight words per epoch": [int(x) for x in counts[..., 8].sum(axis=(0, 2))],
                                       "detected weight words per epoch": [int(x) for x in counts[..., 9].sum(axis=(0, 2))],
                                       "repaired weight words per epoch": [int(x) for x in counts[..., 10].sum(axis=(0, 2))],

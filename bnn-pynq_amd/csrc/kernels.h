@@ -248,7 +248,7 @@ hipError_t emem_noise_t(uint8_t *copies, size_t stride, int runs, const unsigned
 // behind.  The copies are not touched: a repair does not change the delivered parameters.
 enum : uint32_t { RK_SKIP = 0, RK_TMR = 1, RK_CODED = 2 };
 constexpr int kRepairEntries = 9;
-struct RepairEntry { unsigned long long state_off; uint32_t lanes, kind, layer, pad; };
+struct RepairEntry { unsigned long long state_off; uint32_t lanes, kind, layer, depth; };  // (depth: iwrepair_state's alone, else 0)
 struct RepairTable { RepairEntry e[kRepairEntries]; };
 hipError_t repair_state(uint8_t *camp, const RepairTable &tab, int entries, int runs, unsigned long long *rep, size_t rep_stride, hipStream_t s);
 
@@ -266,5 +266,20 @@ hipError_t wmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned
 // pairs; entries as for repair_state (state_off the layer's pairs, lanes its code words per run; kind RK_CODED).  The
 // copies are not touched.
 hipError_t wrepair_state(uint8_t *camp, const RepairTable &tab, int entries, int runs, unsigned long long *wst, size_t wst_stride, hipStream_t s);
+
+// Column-interleaved coded weight memories (bnn_mi355x_iwecc_exposure_campaigns; the model: mem_org.h, "column-interleaved
+// code words"), iwecc_kernels.hip.  iwmem_noise_w goes in wmem_noise_w's place for a layer of interleave depth `depth`
+// (1, 2, 4, 8 or 16; 1: the same result as wmem_noise_w): same arguments, same state size and place, but a lane per CODE
+// WORD'S WORTH of storage numbered in SITE order (lane q: sites [64 q, 64 q + 64) and check element q), and a state pair
+// means the accumulated PHYSICAL hit masks of those 64 sites and that check element; the depth adjacent lanes of a group
+// exchange them into code word patterns, decode, and exchange the remaining errors back.  The code words per run must be
+// a multiple of 64 (a wave is whole or absent): hipErrorInvalidValue otherwise.  counts and wst as for wmem_noise_w, the
+// status counters per code word after gathering.
+hipError_t iwmem_noise_w(uint8_t *copies, size_t stride, int runs, const unsigned long long *seeds, const MemNoiseLayer &L, bool two_bit,
+                         int ebits, int burst, int depth, uint32_t rate_q32, int epoch, const uint8_t *loaded, unsigned long long *state,
+                         unsigned long long *counts, size_t run_stride, unsigned long long *wst, size_t wst_stride, hipStream_t s);
+// The repair of interleaved coded weight memories, in wrepair_state's place (not next to it): entries as there, with the
+// layer's depth in RepairEntry::depth and lanes a multiple of 64.
+hipError_t iwrepair_state(uint8_t *camp, const RepairTable &tab, int entries, int runs, unsigned long long *wst, size_t wst_stride, hipStream_t s);
 
 }  // namespace bnn

@@ -76,6 +76,45 @@ int wecc_words_per_pe(const NetSpec &net, int weight_code, int layer) {
   return (int)((long)L.fold.wmem * ebits / 64);
 }
 
+std::string iwecc_check(int weight_code, int weight_interleave) {
+  const std::string e = wecc_check(weight_code);
+  if (!e.empty()) return e;
+  if (weight_interleave < WI_NONE || weight_interleave > WI_COLUMNS) return "weight_interleave must be 0 (none) or 1 (column-interleaved code words)";
+  if (weight_interleave == WI_COLUMNS && weight_code != WC_SECDED) return "weight_interleave 1 needs weight_code 1";
+  return "";
+}
+
+int wecc_depth(const NetSpec &net, int weight_code, int weight_interleave, int layer) {
+  const int cwpp = wecc_words_per_pe(net, weight_code, layer);
+  if (!cwpp) return 0;
+  if (weight_interleave != WI_COLUMNS) return 1;
+  int d = kMaxBurst;
+  while (cwpp % d) d >>= 1;  // (kMaxBurst is a power of two: the gcd is the largest power of two <= 16 that divides)
+  return d;
+}
+
+bool iwecc_site(const NetSpec &net, int weight_code, int weight_interleave, int layer, int module, long index, long *word, int *bit) {
+  const int D = wecc_depth(net, weight_code, weight_interleave, layer);
+  if (!D || (module != 0 && module != 1) || index < 0) return false;
+  const long per = module == 0 ? kWeccDataBits : kWeccCheckBits;  // bits of a code word in this memory
+  const long words = (long)net.L[layer].fold.pe * wecc_words_per_pe(net, weight_code, layer);
+  if (index >= words * per) return false;
+  const long G = index / (per * D);
+  int w, b;
+  iwecc_member(D, (int)(index - G * per * D), &w, &b);
+  *word = G * D + w;
+  *bit = b;
+  return true;
+}
+
+long iwecc_site_of(const NetSpec &net, int weight_code, int weight_interleave, int layer, int module, long word, int bit) {
+  const int D = wecc_depth(net, weight_code, weight_interleave, layer);
+  if (!D || (module != 0 && module != 1) || word < 0) return -1;
+  const long per = module == 0 ? kWeccDataBits : kWeccCheckBits;
+  if (word >= (long)net.L[layer].fold.pe * wecc_words_per_pe(net, weight_code, layer) || bit < 0 || bit >= per) return -1;
+  return word / D * (per * D) + iwecc_offset(D, (int)(word % D), bit);
+}
+
 namespace {
 // code word cw of one PE's weight memory: its 64 data bits gathered from / scattered to the 64 / ebits elements it covers
 uint64_t wecc_gather(const std::vector<uint64_t> &pe, int ebits, int cw) {
@@ -89,6 +128,43 @@ void wecc_scatter(std::vector<uint64_t> &pe, int ebits, int cw, uint64_t d) {
   const int n = 64 / ebits;
   const uint64_t emask = ebits >= 64 ? ~0ull : (1ull << ebits) - 1;
   for (int i = 0; i < n; i++) pe[(size_t)cw * n + i] = (d >> (i * ebits)) & emask;
+}
+
+// the same at interleave depth D ("column-interleaved code words", mem_org.h), bit by bit: `width` bits of code word cw of
+// one PE's memory of ebits-wide elements -- the data memory (width 64) or the check memory (width 8, ebits 8).  Depth 1 is
+// wecc_gather / wecc_scatter and the check element itself
+uint64_t iwecc_gather(const std::vector<uint64_t> &pe, int ebits, int width, int D, int cw) {
+  const long base = (long)(cw / D) * width * D;
+  uint64_t d = 0;
+  for (int b = 0; b < width; b++) {
+    const long site = base + iwecc_offset(D, cw % D, b);
+    d |= ((pe[(size_t)(site / ebits)] >> (site % ebits)) & 1) << b;
+  }
+  return d;
+}
+void iwecc_scatter(std::vector<uint64_t> &pe, int ebits, int width, int D, int cw, uint64_t d) {
+  const long base = (long)(cw / D) * width * D;
+  for (int b = 0; b < width; b++) {
+    const long site = base + iwecc_offset(D, cw % D, b);
+    uint64_t &w = pe[(size_t)(site / ebits)];
+    w = (w & ~(1ull << (site % ebits))) | ((d >> b) & 1) << (site % ebits);
+  }
+}
+// code word cw of one PE at depth D: its data bits in the weight memory `pe`, its check bits in the check memory `pe`
+// (D <= 1: the whole-element route that was there before the interleave)
+uint64_t code_data(const std::vector<uint64_t> &pe, int ebits, int D, int cw) {
+  return D <= 1 ? wecc_gather(pe, ebits, cw) : iwecc_gather(pe, ebits, kWeccDataBits, D, cw);
+}
+uint32_t code_check(const std::vector<uint64_t> &pe, int D, int cw) {
+  return D <= 1 ? (uint32_t)pe[(size_t)cw] : (uint32_t)iwecc_gather(pe, kWeccCheckBits, kWeccCheckBits, D, cw);
+}
+void store_data(std::vector<uint64_t> &pe, int ebits, int D, int cw, uint64_t d) {
+  if (D <= 1) wecc_scatter(pe, ebits, cw, d);
+  else iwecc_scatter(pe, ebits, kWeccDataBits, D, cw, d);
+}
+void store_check(std::vector<uint64_t> &pe, int D, int cw, uint32_t c) {
+  if (D <= 1) pe[(size_t)cw] = c;
+  else iwecc_scatter(pe, kWeccCheckBits, kWeccCheckBits, D, cw, c);
 }
 }  // namespace
 
@@ -116,7 +192,8 @@ void permute_pairs(const LayerSpec &L, int il, int T, bool forward, std::vector<
 }
 }  // namespace
 
-void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code, int weight_code) {
+void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code, int weight_code,
+               int weight_interleave) {
   out.l0 = l0;
   out.l1 = l1;
   for (int l = l0; l < l1; l++) {
@@ -132,8 +209,9 @@ void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int
     if (const int cwpp = wecc_words_per_pe(net, weight_code, l)) {  // the check words of the loaded code words in module 1
       const int ebits = mem_element_bits(L, 0);
       out.mod[1].w[l].assign(raw.w[l].size(), std::vector<uint64_t>((size_t)cwpp));
+      const int D = wecc_depth(net, weight_code, weight_interleave, l);
       for (size_t pe = 0; pe < raw.w[l].size(); pe++)
-        for (int cw = 0; cw < cwpp; cw++) out.mod[1].w[l][pe][(size_t)cw] = wecc_encode(wecc_gather(raw.w[l][pe], ebits, cw));
+        for (int cw = 0; cw < cwpp; cw++) store_check(out.mod[1].w[l][pe], D, cw, wecc_encode(code_data(raw.w[l][pe], ebits, D, cw)));
     }
     std::vector<std::vector<uint64_t>> t = raw.t[l];
     if (org.t_interleave) permute_pairs(L, org.t_interleave, mem_element_bits(L, 1), true, t);
@@ -195,7 +273,7 @@ void vote(const RawParams *mod, bool thresholds, int l, int modules, int ebits, 
 }  // namespace
 
 void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code, long (*status)[2], int weight_code,
-                  long (*wstatus)[2]) {
+                  long (*wstatus)[2], int weight_interleave) {
   for (int l = p.l0; l < p.l1; l++) {
     const LayerSpec &L = net.L[l];
     EccOrg eo{MemOrg{1, 1, 0}, 0};
@@ -206,11 +284,13 @@ void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams
     if (wstatus) wstatus[l][0] = wstatus[l][1] = 0;
     if (const int cwpp = wecc_words_per_pe(net, weight_code, l)) {
       const int ebits = mem_element_bits(L, 0);
+      const int D = wecc_depth(net, weight_code, weight_interleave, l);
       for (size_t pe = 0; pe < out.w[l].size(); pe++)
         for (int cw = 0; cw < cwpp; cw++) {
+          // (a correction changes bits of this code word alone, so the code words of a group do not depend on the order)
           uint64_t d;
-          const int st = wecc_decode(wecc_gather(out.w[l][pe], ebits, cw), (uint32_t)p.mod[1].w[l][pe][(size_t)cw], &d);
-          if (st == 1) wecc_scatter(out.w[l][pe], ebits, cw, d);
+          const int st = wecc_decode(code_data(out.w[l][pe], ebits, D, cw), code_check(p.mod[1].w[l][pe], D, cw), &d);
+          if (st == 1) store_data(out.w[l][pe], ebits, D, cw, d);
           if (wstatus && st) wstatus[l][st - 1]++;
         }
     }
@@ -276,7 +356,7 @@ void scatter(const LayerSpec &L, int il, int width, std::vector<uint64_t> &pe, i
 }  // namespace
 
 void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0, int l1, long (*counts)[2], const PhysParams *loaded,
-                 int weight_code, long (*wcounts)[2]) {
+                 int weight_code, long (*wcounts)[2], int weight_interleave) {
   for (int l = std::max(l0, p.l0); l < l1 && l < p.l1; l++) {
     const LayerSpec &L = net.L[l];
     EccOrg eo{MemOrg{1, 1, 0}, 0};
@@ -285,17 +365,18 @@ void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0
     if (!ecc_layout(net, scheme, code, l, eo).empty()) continue;
     if (const int cwpp = wecc_words_per_pe(net, weight_code, l)) {  // a coded weight memory, code word by code word
       const int ebits = mem_element_bits(L, 0);
+      const int D = wecc_depth(net, weight_code, weight_interleave, l);
       for (size_t pe = 0; pe < p.mod[0].w[l].size(); pe++)
         for (int cw = 0; cw < cwpp; cw++) {
           uint64_t rd;
           uint32_t rc;
-          const int st = wecc_repair(wecc_gather(p.mod[0].w[l][pe], ebits, cw), (uint32_t)p.mod[1].w[l][pe][(size_t)cw], &rd, &rc);
+          const int st = wecc_repair(code_data(p.mod[0].w[l][pe], ebits, D, cw), code_check(p.mod[1].w[l][pe], D, cw), &rd, &rc);
           if (st == 1) {
-            wecc_scatter(p.mod[0].w[l][pe], ebits, cw, rd);
-            p.mod[1].w[l][pe][(size_t)cw] = rc;
+            store_data(p.mod[0].w[l][pe], ebits, D, cw, rd);
+            store_check(p.mod[1].w[l][pe], D, cw, rc);
             if (wcounts) wcounts[l][0]++;
           }
-          if (wcounts && loaded && (rd != wecc_gather(loaded->mod[0].w[l][pe], ebits, cw) || rc != (uint32_t)loaded->mod[1].w[l][pe][(size_t)cw]))
+          if (wcounts && loaded && (rd != code_data(loaded->mod[0].w[l][pe], ebits, D, cw) || rc != code_check(loaded->mod[1].w[l][pe], D, cw)))
             wcounts[l][1]++;
         }
     }
@@ -327,7 +408,7 @@ void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0
 }
 
 std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n,
-                        int weight_code) {
+                        int weight_code, int weight_interleave) {
   for (int i = 0; i < n; i++) {
     const int layer = records[(size_t)i * 9 + 2];
     if (layer < 0 && layer != kMarkRepair && layer != kMarkRewrite)
@@ -337,7 +418,7 @@ std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysPara
   for (int i = 0; i < n; i++) {
     const int *v = records + (size_t)i * 9;
     if (v[2] == kMarkRepair) {
-      phys_repair(net, scheme, code, p, p.l0, p.l1, nullptr, nullptr, weight_code);
+      phys_repair(net, scheme, code, p, p.l0, p.l1, nullptr, nullptr, weight_code, nullptr, weight_interleave);
     } else if (v[2] == kMarkRewrite) {
       p = loaded;
     } else {
@@ -350,8 +431,10 @@ std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysPara
 }
 
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch, int code, int weight_code) {
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch, int code, int weight_code,
+                             int weight_interleave) {
   if (burst < 1 || burst > kMaxBurst || epoch < 0 || epoch >= kMaxEpochs) return -1;
+  if (weight_interleave != WI_NONE && !iwecc_check(weight_code, weight_interleave).empty()) return -1;
   EccOrg eo{MemOrg{1, 1, 0}, 0};
   if (!ecc_layout(net, scheme, code, layer, eo).empty()) return -1;
   const MemOrg &org = eo.org;

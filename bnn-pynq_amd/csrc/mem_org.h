@@ -212,6 +212,37 @@ inline bool exposure_repairs(int t, int scrub_every, int repair_every) {
 // A check-memory record: target 0, module 1, mem the PE, ind the code word of the PE, bit g * b, word_size b.
 // Like the voter, the threshold code and the repair this is the project's own model: parity unpinned.
 BNN_HD inline uint32_t wecc_check_groups(int burst) { return (uint32_t)((kWeccCheckBits + burst - 1) / burst); }
+//
+// COLUMN-INTERLEAVED code words (bnn_mi355x_iwecc_exposure_campaigns): a fourth axis `weight_interleave`, 0 (none:
+// everything above, unchanged) or 1; it needs weight_code 1 and covers exactly the layers weight_code 1 covers.  Why: a
+// burst stays inside one element, and above its bits all land in one code word -- an aligned burst of 2 in an even-width
+// element always flips an even number of bits of it, so the overall parity never fires and nothing is corrected.  Real
+// block RAM ECC stripes adjacent columns over different code words; this is that.
+// Depth: per layer D = gcd(kMaxBurst = 16, code words per PE (wecc_words_per_pe)); an odd count gives D = 1, coded and not
+// interleaved (in the five nets every coded layer's count is even: D is 2, 8 or 16).  D divides the code words per PE, so
+// no group straddles PEs.
+// GROUP G of a layer is D consecutive code words' worth of storage in the site order above: its data memory is sites
+// [64 D G, 64 D (G + 1)), its check memory elements [D G, D (G + 1)), 8 bits each.  Only the MEMBERSHIP changes:
+//   data   the site at offset p of the group (0 <= p < 64 D) is data bit p / D of code word p % D of the group
+//   check  the bit at offset r = 8 * element + bit of the group's check elements (0 <= r < 8 D) is check bit r / D of code
+//          word r % D of the group
+// so columns adjacent in a memory word lie in different code words, as far apart as D allows.  The weights stay where
+// they were (site s is the same weight), and so does every upset: the events of both memories are exactly weight_code
+// 1's records (bnn_mi355x_wecc_exposure_mask lists them).  A burst of b bits lands in min(b, D) different code words.
+// Delivery is wecc_decode per code word over the gathered bits, the corrected bit scattered back to its site; a repair is
+// wecc_repair per code word, status 1 writing the delivered data and fresh check bits to their scattered places; a full
+// rewrite clears everything.  Orthogonal to (scheme, code, repair_every).  The twelve counts keep their meaning; [8] ...
+// [11] count CODE WORDS AFTER GATHERING, not physical 64-site words; [0] is weight_code 1's, the events being the same.
+// Consequences: one event of any width <= D leaves every code word at status <= 1 and the delivered weights the loaded
+// ones; an aligned burst of 2 D in an element that wide puts two flipped bits into each of the D code words (status 2 for
+// all, nothing corrected): the depth's limit.  The project's own model, like the code it lays out: parity unpinned.
+enum : int { WI_NONE = 0, WI_COLUMNS = 1 };
+// data: offset p in [0, 64 D) of a group <-> (code word of the group, data bit); check likewise with r in [0, 8 D)
+BNN_HD inline void iwecc_member(int depth, int offset, int *word, int *bit) {
+  *word = offset % depth;
+  *bit = offset / depth;
+}
+BNN_HD inline int iwecc_offset(int depth, int word, int bit) { return bit * depth + word; }
 
 // ---- host only from here ---------------------------------------------------------------------------------------------
 
@@ -223,6 +254,16 @@ std::string ecc_layout(const NetSpec &net, int scheme, int code, int layer, EccO
 int wecc_words_per_pe(const NetSpec &net, int weight_code, int layer);
 // "" or why the weight code is refused
 std::string wecc_check(int weight_code);
+// "" or why the pair is refused (wecc_check's reasons first)
+std::string iwecc_check(int weight_code, int weight_interleave);
+// the interleave depth of a layer's coded weight memory: 0 not coded, 1 coded and not interleaved (weight_interleave 0, or
+// an odd count of code words per PE), else gcd(kMaxBurst, code words per PE)
+int wecc_depth(const NetSpec &net, int weight_code, int weight_interleave, int layer);
+// the code word of the layer (PE-major) and the bit of it that a site holds: module 0 a data site of the weight memory
+// (bit 0 ... 63), module 1 a bit 8 * element + bit of the check memory (bit 0 ... 7); false for a layer that is not coded
+// or an index outside the memory.  iwecc_site_of is the inverse: the site (or check bit index) of (code word, bit)
+bool iwecc_site(const NetSpec &net, int weight_code, int weight_interleave, int layer, int module, long index, long *word, int *bit);
+long iwecc_site_of(const NetSpec &net, int weight_code, int weight_interleave, int layer, int module, long word, int bit);
 
 struct PhysFault { Fault f; int module; };
 
@@ -235,7 +276,9 @@ struct PhysParams {
 // what the loader stores from the parameter files.  code 1: the check memory of a coded layer in mod[1].t[l], filled
 // from the logical elements
 // weight_code 1: the check memory of a coded layer's weights in mod[1].w[l] ([pe][code word of the PE])
-void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code = 0, int weight_code = 0);
+// weight_interleave 1: the check bits at their interleaved places (element [pe][D G + i] of the PE's groups)
+void phys_load(const NetSpec &net, int scheme, const RawParams &raw, int l0, int l1, PhysParams &out, int code = 0, int weight_code = 0,
+               int weight_interleave = 0);
 // one physical fault; returns apply_fault's result, -1 also for a module the memory does not have.  A record of a check
 // memory (code 1, target 1, module 1) XORs bits [bit, min(bit + word_size, 6)) of the check word, bit aligned as there
 // weight_code 1: a record of a weight check memory (target 0, module 1) likewise at width 8
@@ -246,18 +289,18 @@ int phys_apply(const NetSpec &net, int scheme, PhysParams &p, const PhysFault &p
 // decoded with status 1 ([l][0]) and 2 ([l][1])
 // weight_code 1: a coded layer's weight words end with the decode of their code words; wstatus the same counts for them
 void phys_logical(const NetSpec &net, int scheme, const PhysParams &p, RawParams &out, int code = 0, long (*status)[2] = nullptr,
-                  int weight_code = 0, long (*wstatus)[2] = nullptr);
+                  int weight_code = 0, long (*wstatus)[2] = nullptr, int weight_interleave = 0);
 // one repair ("repair scrubs" above) of the memories of layers [l0, l1) that have redundancy, in place.  counts, where
 // given, receives per layer [l][0] the words rewritten and, with `loaded` (phys_load's result for the same arguments),
 // [l][1] the words of the repaired memories whose stored state still differs from the loaded one afterwards.
 // weight_code 1: the coded weight memories are repaired too, counted apart in wcounts (code words)
 void phys_repair(const NetSpec &net, int scheme, int code, PhysParams &p, int l0, int l1, long (*counts)[2],
-                 const PhysParams *loaded = nullptr, int weight_code = 0, long (*wcounts)[2] = nullptr);
+                 const PhysParams *loaded = nullptr, int weight_code = 0, long (*wcounts)[2] = nullptr, int weight_interleave = 0);
 // the records of bnn_mi355x_pack_params_repair, 9 ints each, applied to p in order: a fault record through phys_apply, a
 // marker (layer kMarkRepair / kMarkRewrite) as a repair of all memories / a return to `loaded`.  "" or why a record is
 // refused, naming it; every layer field is checked before anything is applied
 std::string phys_replay(const NetSpec &net, int scheme, int code, const PhysParams &loaded, PhysParams &p, const int *records, int n,
-                        int weight_code = 0);
+                        int weight_code = 0, int weight_interleave = 0);
 
 // element width in bits of a layer's weight (target 0) or threshold (target 1) memory; 0: no threshold memory
 int mem_element_bits(const LayerSpec &L, int target);
@@ -268,8 +311,10 @@ inline int event_width(int ebits, int burst, int bit) { return ebits - bit < bur
 // returns their number (0: thresholds of a layer without any), -1 for a bad scheme, burst, layer, target or module;
 // writes events first .. first + cap - 1 to out (which may be null).  epoch: the exposure campaigns' (above); the
 // records' image field holds it.  code 1: module 1 of a coded layer's thresholds lists the check memory's events;
-// weight_code 1: module 1 of a coded layer's weights likewise
+// weight_code 1: module 1 of a coded layer's weights likewise.  weight_interleave changes no event (only which code word
+// a bit belongs to): it is checked (-1 for a pair iwecc_check refuses) and otherwise without effect
 long hardened_mem_noise_mask(const NetSpec &net, int scheme, int burst, uint64_t run_seed, int layer, int target, int module,
-                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch = 0, int code = 0, int weight_code = 0);
+                             uint32_t rate_q32, long first, PhysFault *out, long cap, int epoch = 0, int code = 0, int weight_code = 0,
+                             int weight_interleave = 0);
 
 }  // namespace bnn

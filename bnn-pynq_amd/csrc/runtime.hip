@@ -303,6 +303,9 @@ struct Runtime {
   // epoch's repair rewrote and those still unlike the loaded ones after it] and the seeds
   std::vector<long> wmem_counts;
   std::vector<unsigned long long> wmem_seeds;
+  // bnn_mi355x_iwecc_exposure_campaigns (the same twelve, the code words counted after gathering) and the seeds
+  std::vector<long> iwmem_counts;
+  std::vector<unsigned long long> iwmem_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
@@ -3217,7 +3220,8 @@ long bnn_mi355x_input_noise_mask(unsigned long long run_seed, int image, unsigne
 // base_only: a variant's library refuses the entry point (the plain ones: the organisation is the variant's there, not
 // an argument; where the scheme is an argument the call is the same in a variant's library)
 // weight_code: the SEC-DED axis of bnn_mi355x_wecc_exposure_campaigns over the weights of layers >= 1 (wecc.h); 0 everywhere else
-struct Hardening { int scheme, burst, code = 0, weight_code = 0; };
+// weight_interleave: the column interleave of those code words (bnn_mi355x_iwecc_exposure_campaigns; mem_org.h); 0 everywhere else
+struct Hardening { int scheme, burst, code = 0, weight_code = 0, weight_interleave = 0; };
 
 static int mem_noise_check(const char *who, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, const Hardening &hz,
                            bool base_only) {
@@ -3259,6 +3263,8 @@ struct MemNoiseJob {
   // same [state_begin, state_begin + state_bytes), so that a full rewrite clears them with the threshold state
   size_t wstate_off[9] = {};
   uint32_t wstate_words[9] = {};  // code words of layer l per run; 0: not coded (or a weight rate of 0)
+  // weight_interleave 1: the layer's interleave depth (k_iwmem_noise_w's pairs are physical, in site order); else 0
+  uint32_t wdepth[9] = {};
   // the repair route: [run][epoch][layer][2] of the host's layer-0 repairs (words rewritten, words still unlike the loaded ones)
   std::vector<unsigned long long> host_repairs;
 };
@@ -3560,6 +3566,7 @@ static int exposure_prepare(const char *who, const std::vector<unsigned long lon
     if (!rw[l] || !cwpp) continue;
     job.wstate_off[l] = end;
     job.wstate_words[l] = (uint32_t)cwpp * (uint32_t)net.L[l].fold.pe;
+    if (hz.weight_interleave) job.wdepth[l] = (uint32_t)wecc_depth(net, hz.weight_code, hz.weight_interleave, l);
     end += (((size_t)R * job.wstate_words[l] * 16) + 255) & ~(size_t)255;
   }
   job.state_bytes = end - job.state_begin;
@@ -3621,10 +3628,13 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
     RepairTable wtab{};
     int wentries = 0;
     for (int l = 0; l < S; l++)
-      if (job.wstate_words[l]) wtab.e[wentries++] = RepairEntry{(unsigned long long)job.wstate_off[l], job.wstate_words[l], RK_CODED, (uint32_t)l, 0};
+      if (job.wstate_words[l])
+        wtab.e[wentries++] = RepairEntry{(unsigned long long)job.wstate_off[l], job.wstate_words[l], RK_CODED, (uint32_t)l, job.wdepth[l]};
     if (wentries) {
       unsigned long long *const d_wst = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * E * S * 8 + (size_t)t * S * 4;
-      const hipError_t we = wrepair_state(r.d_camp, wtab, wentries, R, d_wst, (size_t)E * S * 4, r.stream);
+      // (weight_interleave 1: every coded layer's pairs are physical ones, so the interleaved repair goes INSTEAD)
+      const hipError_t we = hz.weight_interleave ? iwrepair_state(r.d_camp, wtab, wentries, R, d_wst, (size_t)E * S * 4, r.stream)
+                                                 : wrepair_state(r.d_camp, wtab, wentries, R, d_wst, (size_t)E * S * 4, r.stream);
       if (we != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(we));
     }
   }
@@ -3640,9 +3650,14 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
     if (job.wstate_words[l]) {
       // a coded weight memory (weight_code 1 comes by the 12-long route alone): its status counters behind the eight
       unsigned long long *const d_wst = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * E * S * 8 + (size_t)t * S * 4;
-      e = wmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
-                       static_cast<const uint8_t *>(r.d_blob), reinterpret_cast<unsigned long long *>(r.d_camp + job.wstate_off[l]), d_counts,
-                       run_stride, d_wst, (size_t)E * S * 4, r.stream);
+      if (job.wdepth[l])
+        e = iwmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, (int)job.wdepth[l], rw[l], t,
+                          static_cast<const uint8_t *>(r.d_blob), reinterpret_cast<unsigned long long *>(r.d_camp + job.wstate_off[l]), d_counts,
+                          run_stride, d_wst, (size_t)E * S * 4, r.stream);
+      else
+        e = wmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
+                         static_cast<const uint8_t *>(r.d_blob), reinterpret_cast<unsigned long long *>(r.d_camp + job.wstate_off[l]), d_counts,
+                         run_stride, d_wst, (size_t)E * S * 4, r.stream);
     } else
       e = xmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
                        static_cast<const uint8_t *>(r.d_blob), d_counts, run_stride, r.stream);
@@ -4221,7 +4236,7 @@ int bnn_mi355x_ecc_repair(unsigned int data, unsigned int check, unsigned int *o
 
 // (bnn_mi355x_pack_params_repair, and with a weight code bnn_mi355x_pack_params_wecc)
 static size_t pack_params_replayed(const std::string &who, const char *path, int scheme, int code, int weight_code, const int *records, int n_faults,
-                                   void *dst, size_t cap) {
+                                   void *dst, size_t cap, int weight_interleave = 0) {
   const NetSpec &net = rt().spec;
   EccOrg eo;
   const std::string le = ecc_layout(net, scheme, code, 0, eo);
@@ -4230,11 +4245,11 @@ static size_t pack_params_replayed(const std::string &who, const char *path, int
   const std::string e = read_raw_params(net, path ? path : "", raw);
   if (!e.empty()) { fail(e); return 0; }
   PhysParams loaded;
-  phys_load(net, scheme, raw, 0, net.nlayers, loaded, code, weight_code);
+  phys_load(net, scheme, raw, 0, net.nlayers, loaded, code, weight_code, weight_interleave);
   PhysParams phys = loaded;
-  const std::string re = phys_replay(net, scheme, code, loaded, phys, records, n_faults, weight_code);
+  const std::string re = phys_replay(net, scheme, code, loaded, phys, records, n_faults, weight_code, weight_interleave);
   if (!re.empty()) { fail(who + ": " + re); return 0; }
-  phys_logical(net, scheme, phys, raw, code, nullptr, weight_code);
+  phys_logical(net, scheme, phys, raw, code, nullptr, weight_code, nullptr, weight_interleave);
   std::vector<uint8_t> blob;
   pack_blob(net, raw, blob);
   if (dst) {
@@ -4344,6 +4359,77 @@ size_t bnn_mi355x_wecc_exposure_params(int scheme, int code, int weight_code, in
 int bnn_mi355x_last_wecc_exposure_counts(long *counts, int cap) { return copy_out(rt().wmem_counts, counts, cap); }
 
 int bnn_mi355x_last_wecc_exposure_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().wmem_seeds, seeds, cap); }
+
+// ---- column-interleaved code words over the coded weight memories (mem_org.h, "column-interleaved code words") -------------
+
+int bnn_mi355x_iwecc_layout(int weight_code, int weight_interleave, int layer, int out[4]) {
+  const NetSpec &net = rt().spec;
+  const std::string e = iwecc_check(weight_code, weight_interleave);
+  if (!e.empty()) return fail("iwecc_layout: " + e);
+  if (layer < 0 || layer >= net.nlayers) return fail("iwecc_layout: layer must be 0 ... " + std::to_string(net.nlayers - 1));
+  const int cwpp = wecc_words_per_pe(net, weight_code, layer);
+  if (out) {
+    out[0] = cwpp ? 1 : 0;
+    out[1] = cwpp;
+    out[2] = cwpp ? kWeccCheckBits : 0;
+    out[3] = wecc_depth(net, weight_code, weight_interleave, layer);
+  }
+  return 0;
+}
+
+int bnn_mi355x_iwecc_site(int weight_code, int weight_interleave, int layer, int module, long index, long out[2]) {
+  const NetSpec &net = rt().spec;
+  const std::string e = iwecc_check(weight_code, weight_interleave);
+  if (!e.empty()) return fail("iwecc_site: " + e);
+  if (layer < 0 || layer >= net.nlayers) return fail("iwecc_site: layer must be 0 ... " + std::to_string(net.nlayers - 1));
+  if (module != 0 && module != 1) return fail("iwecc_site: module must be 0 (a data site of the weight memory) or 1 (a bit of the check memory)");
+  if (!wecc_depth(net, weight_code, weight_interleave, layer))
+    return fail("iwecc_site: the weight memory of layer " + std::to_string(layer) + " is not coded (weight_code 0, or CNV layer 0)");
+  long word;
+  int bit;
+  if (!iwecc_site(net, weight_code, weight_interleave, layer, module, index, &word, &bit))
+    return fail("iwecc_site: index must be 0 ... " +
+                std::to_string((long)net.L[layer].fold.pe * wecc_words_per_pe(net, weight_code, layer) * (module ? kWeccCheckBits : kWeccDataBits) - 1));
+  if (out) { out[0] = word; out[1] = bit; }
+  return 0;
+}
+
+size_t bnn_mi355x_pack_params_iwecc(const char *path, int scheme, int code, int weight_code, int weight_interleave, const int *records, int n_faults,
+                                    void *dst, size_t cap) {
+  const std::string e = iwecc_check(weight_code, weight_interleave);
+  if (!e.empty()) { fail("pack_params_iwecc: " + e); return 0; }
+  return pack_params_replayed("pack_params_iwecc", path, scheme, code, weight_code, records, n_faults, dst, cap, weight_interleave);
+}
+
+int *bnn_mi355x_iwecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int weight_code, int weight_interleave, int burst,
+                                         int num_runs, unsigned long long seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32,
+                                         int n_rates, int epoch_images, int scrub_every, int repair_every, int *image_number, float *usecPerImage) {
+  Runtime &r = rt();
+  r.iwmem_counts.clear();
+  r.iwmem_seeds.clear();
+  const std::string e = iwecc_check(weight_code, weight_interleave);  // (before a device is looked for, like every refusal of the family)
+  if (!e.empty()) { fail("iwecc_exposure_campaigns: " + e); return nullptr; }
+  const MemNoiseEntry en{"iwecc_exposure_campaigns", &Runtime::iwmem_counts, &Runtime::iwmem_seeds, false, false, false, true};
+  return mem_noise_campaigns_impl(en, Hardening{scheme, burst, code, weight_code, weight_interleave}, Exposure{epoch_images, scrub_every, 12, repair_every},
+                                  path, number_class, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, image_number, usecPerImage);
+}
+
+size_t bnn_mi355x_iwecc_exposure_params(int scheme, int code, int weight_code, int weight_interleave, int burst, unsigned long long run_seed,
+                                        const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every,
+                                        int repair_every, void *dst, size_t cap) {
+  const std::string e = iwecc_check(weight_code, weight_interleave);
+  if (!e.empty()) { fail("iwecc_exposure_params: " + e); return 0; }
+  if (repair_every < 0) {
+    fail("iwecc_exposure_params: repair_every must not be negative (0: never repair)");
+    return 0;
+  }
+  return exposure_params_impl("iwecc_exposure_params", Hardening{scheme, burst, code, weight_code, weight_interleave}, run_seed, rate_w_q32, rate_t_q32,
+                              n_rates, epoch, scrub_every, dst, cap, repair_every, true);
+}
+
+int bnn_mi355x_last_iwecc_exposure_counts(long *counts, int cap) { return copy_out(rt().iwmem_counts, counts, cap); }
+
+int bnn_mi355x_last_iwecc_exposure_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().iwmem_seeds, seeds, cap); }
 
 void free_results(int *result) { delete[] result; }
 

@@ -103,6 +103,16 @@ for name in ("TMR + SEC-DED weights", "none + SEC-DED + SEC-DED weights"):
         print("%-32s rewrite every %2d repair every %d: avg accuracy %.2f, last epoch %.2f, weight code words repaired %d"
               % (name, every, repair, e["avg accuracy"], e["mean accuracy per epoch"][-1], sum(e["repaired weight words per epoch"])))
 
+# bursts: with the coded weights alone an aligned burst of 2 is a double error of one code word and nothing is corrected;
+# column-interleaved (a (scheme, code, weight_code, weight_interleave) 4-tuple) its two bits lie in two code words, both corrected
+net.scrubbing_curve(os.path.join(out, "iwecc"), 10, [2.0 ** -10], [(0, 1)], [(1, 0, 1), (1, 0, 1, 1)], 100, bursts=(2,), seed=1)
+stats = json.load(open(os.path.join(out, "iwecc", "cnvW1A1", "cifar10", "scrubbing", "cnvW1A1_cifar10_scrubbing_stats.json")))
+for name in ("TMR + SEC-DED weights", "TMR + SEC-DED weights column-interleaved"):
+    e = stats["results"]["%s burst 2 upset rate %g scrub every 0 repair every 1" % (name, 2.0 ** -10)]
+    print("%-42s burst 2, repair every epoch: avg accuracy %.2f, last epoch %.2f, weight code words corrected %d, detected %d"
+          % (name, e["avg accuracy"], e["mean accuracy per epoch"][-1], sum(e["corrected weight words per epoch"]),
+             sum(e["detected weight words per epoch"])))
+
 # the image buffer: upset-rate curve, then the per-bit sensitivity map (24 576 sites x 200 images)
 net.input_upset_rate_curve(out, 10, rates, seed=1)
 for p in rates:

@@ -679,6 +679,47 @@ size_t bnn_mi355x_wecc_exposure_params(int scheme, int code, int weight_code, in
 int bnn_mi355x_last_wecc_exposure_counts(long *counts, int cap);
 int bnn_mi355x_last_wecc_exposure_seeds(unsigned long long *seeds, int cap);
 
+/* COLUMN-INTERLEAVED code words over the coded weight memories: a fourth axis `weight_interleave`.  0 none (everything
+ * above, unchanged); 1 column-interleaved.  It needs weight_code 1 and covers exactly the layers weight_code 1 covers.
+ * Why: a burst stays inside one element, and with weight_code 1 alone all its bits land in one code word -- an aligned
+ * burst of 2 in an even-width element flips an even number of bits of it, the overall parity never fires and nothing is
+ * corrected.  Real block RAM ECC stripes adjacent columns over different code words.  The project's own model
+ * (csrc/mem_org.h "column-interleaved code words"), like the code it lays out: parity unpinned.
+ *   Depth, per layer: D = gcd(16, code words per PE) (16 the widest burst); an odd count gives D = 1, coded and not
+ *   interleaved.  Group G of a layer is D consecutive code words' worth of storage in the site order: data sites
+ *   [64 D G, 64 D (G + 1)), check elements [D G, D (G + 1)).  The site at offset p of the group is data bit p / D of code
+ *   word p % D of the group; the check bit at offset r = 8 * element + bit is check bit r / D of code word r % D.  The
+ *   weights stay where they were and the upsets are unchanged: the events of both memories are weight_code 1's records,
+ *   which wecc_exposure_mask lists (there is no mask entry point of this family).  A burst of b bits lands in min(b, D)
+ *   code words.  Delivery, repair and rewrite are weight_code 1's, per code word over the gathered bits.
+ * iwecc_layout: out[0 ... 2] are wecc_layout's, out[3] the depth (0 where the layer is not coded, 1 where coded and not
+ * interleaved).  Returns 0, or -1 + last_error.  Host only.
+ * iwecc_site: module 0: index a data site of the layer's weight memory; module 1: index a check bit, 8 * element + bit.
+ * out[0] the code word of the layer (PE-major), out[1] the bit of the code word (0 ... 63, or 0 ... 7).  Returns 0, or -1 +
+ * last_error for a bad argument or a layer that is not coded.  Host only.
+ * pack_params_iwecc: pack_params_wecc plus weight_interleave.  Host only.
+ * iwecc_exposure_campaigns / _params: wecc_exposure_campaigns / _params plus weight_interleave behind weight_code.
+ * Refused before a device is looked for: weight_interleave outside 0 ... 1, and weight_interleave 1 without weight_code 1.
+ * last_iwecc_exposure_counts: the twelve longs of last_wecc_exposure_counts; [8] ... [11] count code words after
+ * gathering, not physical 64-site words; [0] is weight_code 1's, the events being the same.
+ * With weight_interleave 0 every one of these returns its wecc predecessor's result bit for bit; the last_* state is
+ * these entry points' own. */
+int bnn_mi355x_iwecc_layout(int weight_code, int weight_interleave, int layer, int out[4]);
+int bnn_mi355x_iwecc_site(int weight_code, int weight_interleave, int layer, int module, long index, long out[2]);
+size_t bnn_mi355x_pack_params_iwecc(const char *path, int scheme, int code, int weight_code, int weight_interleave,
+                                    const int *records, int n_faults, void *dst, size_t cap);
+int *bnn_mi355x_iwecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int weight_code,
+                                         int weight_interleave, int burst, int num_runs, unsigned long long seed,
+                                         const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates,
+                                         int epoch_images, int scrub_every, int repair_every, int *image_number,
+                                         float *usecPerImage);
+size_t bnn_mi355x_iwecc_exposure_params(int scheme, int code, int weight_code, int weight_interleave, int burst,
+                                        unsigned long long run_seed, const unsigned int *rate_w_q32,
+                                        const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every,
+                                        int repair_every, void *dst, size_t cap);
+int bnn_mi355x_last_iwecc_exposure_counts(long *counts, int cap);
+int bnn_mi355x_last_iwecc_exposure_seeds(unsigned long long *seeds, int cap);
+
 /* Propagation profiles of the single-fault sweeps: where a fault is masked.  With S the network's layers a profile has
  * S - 1 columns, one per layer with an output map -- the maps bnn_mi355x_enumerate_act_faults has sites in: CNV column
  * l = the output of layer l, l = 0 ... 7 (layers 1 and 3: after the max-pool); LFC column l = the output of layer l,

@@ -42,7 +42,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_pack_params_wecc", "bnn_mi355x_wecc_exposure_campaigns", "bnn_mi355x_wecc_exposure_params",
        "bnn_mi355x_last_wecc_exposure_counts", "bnn_mi355x_last_wecc_exposure_seeds", "bnn_mi355x_iwecc_layout",
        "bnn_mi355x_iwecc_site", "bnn_mi355x_pack_params_iwecc", "bnn_mi355x_iwecc_exposure_campaigns",
-       "bnn_mi355x_iwecc_exposure_params", "bnn_mi355x_last_iwecc_exposure_counts", "bnn_mi355x_last_iwecc_exposure_seeds"]
+       "bnn_mi355x_iwecc_exposure_params", "bnn_mi355x_last_iwecc_exposure_counts", "bnn_mi355x_last_iwecc_exposure_seeds",
+       "bnn_mi355x_tile_boxes", "bnn_mi355x_windows_to_cifar", "bnn_mi355x_classify_windows"]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -249,6 +250,13 @@ def declare_extensions(L):
     L.bnn_mi355x_stage_name.restype = C.c_char_p
     L.bnn_mi355x_thumbnail_size.argtypes = [C.c_int, C.c_int, ip, ip]
     L.bnn_mi355x_images_to_cifar.argtypes = [C.POINTER(C.c_void_p), ip, ip, ip, C.POINTER(C.c_long), C.c_int, C.c_void_p]
+    if hasattr(L, "bnn_mi355x_classify_windows"):  # (an older build of the same ABI under BNN_MI355X_LIBDIR lacks them)
+        L.bnn_mi355x_tile_boxes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long]
+        L.bnn_mi355x_tile_boxes.restype = C.c_long
+        L.bnn_mi355x_windows_to_cifar.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_void_p]
+        L.bnn_mi355x_classify_windows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, fp, fp,
+                                                  C.c_int]
+        L.bnn_mi355x_classify_windows.restype = ip
 
 
 _cache = {}

@@ -901,6 +901,106 @@ class CnvClassifier:
     def classify_paths(self, paths):
         return self.classify_images([Image.open(p) for p in paths])
 
+    # -- extension: every window of one scene in one call (CNV-BNN_Road-Signs.ipynb cells 13-16) ----------
+    def tile_boxes(self, size, sizes=(64, 96)):
+        """the notebook's tiling of a picture of ``size`` = (width, height): for each window size in ``sizes`` (size-major,
+        like cell 13) windows every ``s // 4`` pixels, rows outer, columns inner, kept when ``right <= width and lower <
+        height`` -> list of (left, upper, right, lower), what ``Image.crop`` takes"""
+        width, height = size
+        lib = self.bnn.interface
+        bounds = []
+        for s in sizes:
+            if hasattr(lib, "bnn_mi355x_tile_boxes"):
+                n = lib.bnn_mi355x_tile_boxes(width, height, s, None, 0)
+                if n < 0:
+                    raise ValueError(lib.bnn_mi355x_last_error().decode())
+                out = np.zeros((n, 4), np.int32)
+                lib.bnn_mi355x_tile_boxes(width, height, s, out.ctypes.data, n)
+                bounds += [tuple(int(v) for v in b) for b in out]
+            else:  # a library without the symbol: cell 13 as it stands
+                stride = s // 4
+                for j in range(height // stride):
+                    for i in range(width // stride):
+                        b = (stride * i, stride * j, stride * i + s, stride * j + s)
+                        if b[2] <= width and b[3] < height:
+                            bounds.append(b)
+        return bounds
+
+    def _scene(self, img):
+        """(uint8 array for the device route or None for the PIL route, PIL image or None)"""
+        if isinstance(img, np.ndarray):
+            if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))):
+                raise ValueError("pictures given as arrays must be uint8 [H, W, 3] (RGB), [H, W, 4] (RGBA) or [H, W] (L)")
+            return np.ascontiguousarray(img), None
+        if img.mode in ("RGB", "RGBA", "L"):
+            return np.ascontiguousarray(np.asarray(img)), img
+        return None, img
+
+    @staticmethod
+    def _boxes(boxes):
+        b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+        return b
+
+    def windows_to_cifar(self, img, boxes):
+        """CIFAR-10 records (uint8 array [n, 3073]) of the windows ``boxes`` (left, upper, right, lower) of ONE picture
+        (a PIL image or a uint8 array, as in :meth:`images_to_cifar`): the same bytes as :meth:`image_to_cifar` writes
+        for ``img.crop(box)``, made on the GPU from one upload of the picture (``bnn_mi355x_windows_to_cifar``).  Modes
+        other than RGB, RGBA and L, and a library without the entry point, take :meth:`images_to_cifar` on the crops.
+        The caller's image is left as it is."""
+        lib = self.bnn.interface
+        a, pil = self._scene(img)
+        b = self._boxes(boxes)
+        if a is None or not hasattr(lib, "bnn_mi355x_windows_to_cifar"):
+            pil = pil if pil is not None else Image.fromarray(a)
+            return self.images_to_cifar([pil.crop(tuple(int(v) for v in box)) for box in b])
+        recs = np.empty((len(b), 3073), dtype=np.uint8)
+        bands = 1 if a.ndim == 2 else a.shape[2]
+        if lib.bnn_mi355x_windows_to_cifar(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, b.ctypes.data, len(b), recs.ctypes.data) != 0:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        return recs
+
+    def _classify_windows(self, img, boxes, detail):
+        lib = self.bnn.interface
+        a, pil = self._scene(img)
+        b = self._boxes(boxes)
+        if a is None or not hasattr(lib, "bnn_mi355x_classify_windows"):
+            pil = pil if pil is not None else Image.fromarray(a)
+            crops = [pil.crop(tuple(int(v) for v in box)) for box in b]
+            return self.classify_images_details(crops) if detail else self.classify_images(crops)
+        bands = 1 if a.ndim == 2 else a.shape[2]
+        usec, pre = ctypes.c_float(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_classify_windows(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, b.ctypes.data, len(b), len(self.classes),
+                                              ctypes.byref(usec), ctypes.byref(pre), 1 if detail else 0)
+        if not ptr:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        result = self.bnn._collect(ptr, len(b) * (len(self.classes) if detail else 1))
+        self.usecPerImage = self.bnn.usecPerImage = usec.value
+        self.usecPreprocess = pre.value
+        return result
+
+    def classify_windows(self, img, boxes):
+        """what :meth:`classify_images` returns for ``[img.crop(b) for b in boxes]``; the picture goes to the GPU once
+        and the records never leave it (``bnn_mi355x_classify_windows``)"""
+        return self._classify_windows(img, boxes, False)
+
+    def classify_windows_details(self, img, boxes):
+        """what :meth:`classify_images_details` returns for the crops: ``len(classes)`` scores per window"""
+        return self._classify_windows(img, boxes, True)
+
+    def locate(self, img, class_index, sizes=(64, 96), min_score=None):
+        """cells 14 and 16: the windows of the notebook's tiling (:meth:`tile_boxes`) whose class is ``class_index`` -- or,
+        with ``min_score``, those whose score for ``class_index`` exceeds it -> list of (left, upper, right, lower)"""
+        size = (img.shape[1], img.shape[0]) if isinstance(img, np.ndarray) else img.size
+        bounds = self.tile_boxes(size, sizes)
+        if not bounds:
+            return []
+        if min_score is None:
+            hit = np.asarray(self.classify_windows(img, bounds)) == class_index
+        else:
+            scores = np.asarray(self.classify_windows_details(img, bounds)).reshape(len(bounds), len(self.classes))
+            hit = scores[:, class_index] > min_score
+        return [b for b, h in zip(bounds, hit) if h]
+
     # extension
     def classify_array(self, images, detail=False):
         result = self.bnn.inference_array(images, detail)

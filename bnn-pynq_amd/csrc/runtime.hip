@@ -51,6 +51,8 @@
 #include "kernels.h"
 #include "preprocess.h"
 #include "resample.h"
+#include "window_kernels.h"
+#include "windows.h"
 #include "packed_params.h"
 #include "pack_inputs.h"
 #include "topology.h"
@@ -311,6 +313,12 @@ struct Runtime {
   size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
   uint8_t *d_pp_src = nullptr, *d_pp_tmp = nullptr, *d_pp_rec = nullptr;
   int32_t *d_pp_coef = nullptr;
+  // windows of one scene -> records / classes (bnn_mi355x_windows_to_cifar, bnn_mi355x_classify_windows): the scene, the
+  // boxes + grouped order + coefficient tables (one upload), the 3072-byte bodies; upload / kernels / pass time stamps
+  size_t win_scene_cap = 0, win_meta_cap = 0, win_body_cap = 0;
+  uint8_t *d_win_scene = nullptr, *d_win_body = nullptr;
+  int32_t *d_win_meta = nullptr;
+  hipEvent_t win_ev[3] = {nullptr, nullptr, nullptr};
   // optional per-stage profiling (bnn_mi355x_profile): one event set per enqueued chunk
   bool profiling = false;
   std::vector<std::vector<hipEvent_t>> prof_sets;
@@ -463,7 +471,7 @@ int upload_blob() {
 
 void free_workspace() {
   Runtime &r = rt();
-  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.file_cap && !r.all_cap && !r.h_io &&
+  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.file_cap && !r.all_cap && !r.h_io &&
       !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
       !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.sw_prof_cap && !r.noise_cap && !r.in_stage_cap)
     return;
@@ -511,6 +519,10 @@ void free_workspace() {
   r.d_pp_src = r.d_pp_tmp = r.d_pp_rec = nullptr;
   r.d_pp_coef = nullptr;
   r.pp_src_cap = r.pp_tmp_cap = r.pp_coef_cap = r.pp_rec_cap = 0;
+  (void)hipFree(r.d_win_scene); (void)hipFree(r.d_win_body); (void)hipFree(r.d_win_meta);
+  r.d_win_scene = r.d_win_body = nullptr;
+  r.d_win_meta = nullptr;
+  r.win_scene_cap = r.win_meta_cap = r.win_body_cap = 0;
 }
 
 // grow-only device buffer (contents are not preserved)
@@ -4829,6 +4841,164 @@ int bnn_mi355x_inference_device(const void *d_images, int n_images, int number_c
     if (rc) r.err = why;
   }
   return rc;
+}
+
+long bnn_mi355x_tile_boxes(int width, int height, int size, int *boxes, long cap) {
+  if (!rt().spec.is_cnv) return fail("tile_boxes: windows become CIFAR-10 records, the input of the CNV networks only");
+  const long n = tile_boxes(width, height, size, boxes, cap < 0 ? 0 : cap);
+  if (n < 0) return fail("tile_boxes: need a window size of 4 or more (stride = size / 4) and a picture of 1 x 1 pixels or more");
+  return n;
+}
+
+}  // extern "C"
+
+namespace bnn {
+namespace {
+
+static_assert(kWindowMidBytes == BNN_MI355X_WINDOW_LDS_BYTES && kWindowLdsBytes <= 65536, "the header states the window kernel's LDS bound");
+
+// Enqueues, on r.stream: the scene's upload, one upload of boxes + order + tables, the window kernels (one launch per
+// size group; the groups of the one-by-one route through launch_image_to_cifar on a packed copy of each window).
+// Record i goes to out + i * pitch: 3073-byte records (`label`) or 16-byte aligned 3072-byte bodies.  The caller has
+// validated the arguments, bound the device and syncs the stream before `plan` and the caller's pixels go away.
+int enqueue_windows(const char *what, const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes, int n,
+                    const WindowPlan &plan, std::vector<int32_t> &meta, uint8_t *out, long pitch, int label) {
+  Runtime &r = rt();
+  const size_t row_bytes = (size_t)width * bands;
+  // one buffer: boxes (16-byte aligned, the kernel reads them as int4) | order | tables
+  const size_t off_order = (size_t)n * 4, off_coef = off_order + (((size_t)n + 3) & ~(size_t)3);
+  meta.assign(off_coef + plan.coef.size(), 0);
+  std::memcpy(meta.data(), boxes, (size_t)n * 4 * sizeof(int32_t));
+  std::memcpy(meta.data() + off_order, plan.order.data(), (size_t)n * sizeof(int32_t));
+  if (!plan.coef.empty()) std::memcpy(meta.data() + off_coef, plan.coef.data(), plan.coef.size() * sizeof(int32_t));
+  if (grow(r.d_win_scene, r.win_scene_cap, row_bytes * height) || grow(r.d_win_meta, r.win_meta_cap, meta.size())) return -1;
+  for (const WindowGroup &g : plan.groups)
+    if (!g.fused && (grow(r.d_pp_src, r.pp_src_cap, (size_t)g.w * g.h * bands) || grow(r.d_pp_rec, r.pp_rec_cap, 3073) ||
+                     grow(r.d_pp_tmp, r.pp_tmp_cap, (size_t)(g.h > g.w ? g.h : g.w) * 32 * 4 + 4096)))
+      return -1;
+  if (row_stride == 0 || (size_t)row_stride == row_bytes)
+    HIP_OK(hipMemcpyAsync(r.d_win_scene, pixels, row_bytes * height, hipMemcpyHostToDevice, r.stream));
+  else
+    HIP_OK(hipMemcpy2DAsync(r.d_win_scene, row_bytes, pixels, (size_t)row_stride, row_bytes, (size_t)height, hipMemcpyHostToDevice, r.stream));
+  HIP_OK(hipMemcpyAsync(r.d_win_meta, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  const int32_t *d_coef = r.d_win_meta + off_coef;
+  for (const WindowGroup &g : plan.groups) {
+    if (g.fused) {
+      if (g.horizontal && (size_t)g.h * g.out_w * bands > (size_t)kWindowMidBytes) return fail(std::string(what) + ": internal: a fused group exceeds the LDS budget");
+      WindowLaunch a{};
+      a.scene = r.d_win_scene; a.stride = (long)row_bytes; a.bands = bands;
+      a.boxes = r.d_win_meta; a.order = r.d_win_meta + off_order + g.first;
+      a.w = g.w; a.h = g.h; a.out_w = g.out_w; a.out_h = g.out_h;
+      a.horizontal = g.horizontal ? 1 : 0; a.vertical = g.vertical ? 1 : 0;
+      a.kh = d_coef + g.off_kh; a.bh = d_coef + g.off_bh; a.ksize_h = g.ksize_h;
+      a.kv = d_coef + g.off_kv; a.bv = d_coef + g.off_bv; a.ksize_v = g.ksize_v;
+      a.out = out; a.out_pitch = pitch; a.label = label;
+      const hipError_t e = launch_windows_to_cifar(a, g.count, r.stream);
+      if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+      continue;
+    }
+    // one by one: a packed device-to-device copy of the window (RGBA: premultiplied in place there, never in the scene),
+    // then exactly what images_to_cifar runs for a picture of that size
+    for (int k = g.first; k < g.first + g.count; k++) {
+      const int i = plan.order[(size_t)k];
+      const int *b = boxes + 4 * (size_t)i;
+      const size_t wrow = (size_t)g.w * bands;
+      HIP_OK(hipMemcpy2DAsync(r.d_pp_src, wrow, r.d_win_scene + (size_t)b[1] * row_bytes + (size_t)b[0] * bands, row_bytes, wrow, (size_t)g.h,
+                              hipMemcpyDeviceToDevice, r.stream));
+      ResampleJob j{};
+      j.src = r.d_pp_src; j.w = g.w; j.h = g.h; j.bands = bands; j.stride = (long)wrow;
+      j.out_w = g.out_w; j.out_h = g.out_h;
+      j.vertical_first = vertical_pass_first(g.w, g.h, g.out_h);
+      j.kh = d_coef + g.off_kh; j.bh = d_coef + g.off_bh; j.ksize_h = g.ksize_h;
+      j.kv = d_coef + g.off_kv; j.bv = d_coef + g.off_bv; j.ksize_v = g.ksize_v;
+      j.tmp = r.d_pp_tmp;
+      j.record = label ? out + (size_t)i * pitch : r.d_pp_rec;
+      const hipError_t e = launch_image_to_cifar(j, r.stream);
+      if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+      if (!label) HIP_OK(hipMemcpyAsync(out + (size_t)i * pitch, r.d_pp_rec + 1, 3072, hipMemcpyDeviceToDevice, r.stream));
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_windows_to_cifar(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes,
+                                int n_windows, uint8_t *records) {
+  Runtime &r = rt();
+  if (!r.spec.is_cnv) return fail("windows_to_cifar: CIFAR-10 records are the input of the CNV networks only");
+  const std::string bad = validate_windows("windows_to_cifar", pixels, width, height, bands, row_stride, boxes, n_windows, records);
+  if (!bad.empty()) return fail(bad);
+  if (n_windows == 0) return 0;
+  if (bind_device()) return -1;
+  WindowPlan plan;
+  std::vector<int32_t> meta;  // (outlives its asynchronous upload, like `plan`: declared before `drain`)
+  plan_windows(boxes, n_windows, bands, plan);
+  if (grow(r.d_pp_rec, r.pp_rec_cap, (size_t)n_windows * 3073)) return -1;
+  DrainOnFailure drain;
+  if (enqueue_windows("windows_to_cifar", pixels, width, height, bands, row_stride, boxes, n_windows, plan, meta, r.d_pp_rec, 3073, 1)) return -1;
+  HIP_OK(hipMemcpyAsync(records, r.d_pp_rec, (size_t)n_windows * 3073, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  return 0;
+}
+
+int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes,
+                                 int n_windows, int number_class, float *usecPerImage, float *usecPreprocess, int enable_detail) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (!r.spec.is_cnv) { fail("classify_windows: CIFAR-10 records are the input of the CNV networks only"); return nullptr; }
+  // (no output buffer of the caller's to check: the result array is the call's own)
+  const std::string bad = validate_windows("classify_windows", pixels, width, height, bands, row_stride, boxes, n_windows, pixels);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  const int n = n_windows;
+  if (n > 0 && !ready()) return nullptr;
+  const size_t count = (size_t)n * (enable_detail ? number_class : 1);
+  int *result = new (std::nothrow) int[count ? count : 1];
+  if (!result) { fail("out of memory"); return nullptr; }
+  if (n == 0) return result;
+  // everything that can fail from here on frees `result`
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    WindowPlan plan;
+    std::vector<int32_t> meta;
+    std::vector<int16_t> scores;
+    plan_windows(boxes, n, bands, plan);
+    // the pass's workspaces first (they synchronise when they grow), so that nothing is allocated between the kernels
+    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n) || grow(r.d_win_body, r.win_body_cap, (size_t)n * 3072)) return -1;
+    for (hipEvent_t &e : r.win_ev)
+      if (!e) HIP_OK(hipEventCreate(&e));
+    if (enable_detail) scores.resize((size_t)n * 64);
+    DrainOnFailure drain;
+    HIP_OK(hipEventRecord(r.win_ev[0], r.stream));
+    if (enqueue_windows("classify_windows", pixels, width, height, bands, row_stride, boxes, n, plan, meta, r.d_win_body, 3072, 0)) return -1;
+    HIP_OK(hipEventRecord(r.win_ev[1], r.stream));
+    // the pass bnn_mi355x_inference_device enqueues, on the same stream, on bodies that never left the device
+    if (bnn_mi355x_inference_device(r.d_win_body, n, number_class, enable_detail ? nullptr : r.d_classes, enable_detail ? r.d_scores : nullptr,
+                                    nullptr, r.stream))
+      return -1;
+    HIP_OK(hipEventRecord(r.win_ev[2], r.stream));
+    if (enable_detail) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, (size_t)n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    if (enable_detail)
+      for (int i = 0; i < n; i++)
+        for (int j = 0; j < number_class; j++) result[(size_t)i * number_class + j] = scores[(size_t)i * 64 + j];
+    float pre = 0.f, pass = 0.f;
+    HIP_OK(hipEventElapsedTime(&pre, r.win_ev[0], r.win_ev[1]));
+    HIP_OK(hipEventElapsedTime(&pass, r.win_ev[1], r.win_ev[2]));
+    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
+    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
+    return 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  return result;
 }
 
 }  // extern "C"

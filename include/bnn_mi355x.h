@@ -761,6 +761,41 @@ int bnn_mi355x_thumbnail_size(int width, int height, int *out_w, int *out_h);
 int bnn_mi355x_images_to_cifar(const uint8_t *const *pixels, const int *widths, const int *heights, const int *bands,
                                const long *row_strides, int n_images, uint8_t *records);
 
+/* Locate objects in a scene (CNV-BNN_Road-Signs.ipynb cells 13-16): every window of ONE picture becomes a CIFAR-10
+ * record -- and, with classify_windows, a class -- in one call.  The notebook tiles a street picture into overlapping
+ * windows, crops each one (im.crop(bound)) and classifies the crops; here the picture goes to the device once, all
+ * windows of one size share one pair of coefficient tables and one kernel launch (csrc/window_kernels.hip), and
+ * classify_windows never brings the records back.  CNV libraries only (-1 / NULL + last_error on an LFC library).
+ *   pixels, width, height, bands, row_stride: the picture, as one picture of images_to_cifar (bands 1 = "L", 3 = "RGB",
+ *              4 = "RGBA"; row_stride 0 = packed rows).  It is not modified.
+ *   boxes:     n_windows x 4 ints (left, upper, right, lower), exactly what Image.crop takes.
+ * tile_boxes: the notebook's tiling rule for ONE window size; host only, touches no GPU.  stride = size / 4, x_tiles =
+ *       width / stride, y_tiles = height / stride; rows are the outer loop, columns the inner one; a box is kept when
+ *       right <= width && lower < height.  The notebook is strict on the height and not on the width (a window may
+ *       touch the right edge of the picture but not the lower one); that is reproduced as it is.  Returns the number of
+ *       boxes of that size and writes at most `cap` of them (boxes may be NULL); -1 + last_error for size < 4.  A
+ *       640 x 480 picture gives 962 boxes of 64 and 368 of 96: the 1 330 the notebook prints.
+ * windows_to_cifar: record i (3073 bytes, host) is byte-identical to what image_to_cifar writes for
+ *       Image.fromarray(pixels).crop(boxes[i]); records come in the caller's order whatever grouping runs inside.
+ * classify_windows: the same records, but their 3072-byte bodies stay in HBM and the pass bnn_mi355x_inference_device
+ *       enqueues runs on them on the same stream; the classes (or, with enable_detail, number_class scores per window)
+ *       come back in one copy.  Return convention and ownership as bnn_mi355x_inference_buffer (free with
+ *       free_results).  usecPerImage: the device time of the classification pass per window, as in the other entry
+ *       points; usecPreprocess (may be NULL): the device time of the uploads and the window kernels, per window.
+ * Refused, before anything touches the GPU, with -1 / NULL + last_error naming the first offending box: a box with
+ * right <= left or lower <= upper; a box that leaves the picture (Pillow would pad it with zeros; the notebook filters
+ * such boxes out, so they are not modelled); bands other than 1, 3, 4; a row stride shorter than a row; null pointers
+ * with n_windows > 0.  n_windows == 0 succeeds.
+ * Windows whose horizontal-pass output (height x out_w x bands bytes) exceeds BNN_MI355X_WINDOW_LDS_BYTES, and windows
+ * Pillow resamples vertical pass first (height > 100 x width), go one by one through the kernels of images_to_cifar. */
+#define BNN_MI355X_WINDOW_LDS_BYTES 32768
+long bnn_mi355x_tile_boxes(int width, int height, int size, int *boxes, long cap);
+int bnn_mi355x_windows_to_cifar(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes,
+                                int n_windows, uint8_t *records);
+int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes,
+                                 int n_windows, int number_class, float *usecPerImage, float *usecPreprocess,
+                                 int enable_detail);
+
 /* Test hook: run the stages 0..stage on n host images (n <= 32768) and copy that stage's output,
  * exactly as it sits in HBM (bit-packed activation layout), to dst.  CNV: stage L =
  * layer L (0..7, after the max-pool where there is one); LFC: stage 0 = binarised input, stage

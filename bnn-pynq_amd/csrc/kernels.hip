@@ -431,18 +431,15 @@ __device__ __forceinline__ uint32_t sign_bits16(const v16i &acc) {
   for (int i = 15; i >= 0; i--) x = shift_in_sign(x, acc[i]);
   return x;
 }
-// lanes 0..31 contribute `a`, lanes 32..63 `b`; lane (r, h): (a of lane r | a of lane r + 32) for h = 0, the same of b for h = 1
-__device__ __forceinline__ uint32_t merge_halves(uint32_t a, uint32_t b) {
+// 16-bit words: lanes 0..31 contribute `a`, lanes 32..63 `b`; lane (r, h): (a of lane r | a of lane r + 32 << 16) for
+// h = 0, the same of b for h = 1 -- the words go in unshifted: one v_permlane32_swap, one shift, one or
+__device__ __forceinline__ uint32_t merge_halves16(uint32_t a, uint32_t b) {
   const auto sw = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-  return sw[0] | sw[1];
+  return sw[0] | (sw[1] << 16);
 }
-// the 4 bytes at LDS byte address base + OFF (OFF a multiple of 4, base any alignment): two aligned dwords (one
-// ds_read2_b32) and a v_alignbyte -- an unaligned ds_read_b32 is legal on gfx950 but executes lane by lane
-// (measured: the first version of this kernel, one unaligned read per run, took 1.98 ms against 0.78 ms)
-template <int OFF>
-__device__ __forceinline__ uint32_t lds_run(const uint32_t *aligned, uint32_t shift) {
-  return __builtin_amdgcn_alignbyte(aligned[OFF / 4 + 1], aligned[OFF / 4], shift);
-}
+// (A run's 4 bytes at any alignment are fetched as the two aligned dwords around them -- one ds_read2_b32 -- and a
+// v_alignbyte: an unaligned ds_read_b32 is legal on gfx950 but executes lane by lane.  Measured: the first version of
+// k_conv0_tile, one unaligned read per run, took 1.98 ms against 0.78 ms)
 
 template <bool OUT2, bool MULTI = false>
 __global__ __launch_bounds__(kBlock, 2) void k_conv0_tile(const uint8_t *__restrict__ imgs, uint32_t *__restrict__ out,
@@ -460,12 +457,16 @@ __global__ __launch_bounds__(kBlock, 2) void k_conv0_tile(const uint8_t *__restr
     out += (size_t)sg.slot * 900 * (OUT2 ? 4 : 2);
   }
   const int cnt = __builtin_amdgcn_readfirstlane(min(kL0Imgs, n_images - img0));  // >= 1 by the grid size
-  const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(imgs + (size_t)img0 * 3072);
-  for (int i = tid; i < cnt * 192; i += kBlock) {
-    uint4 v = src[i];
+  // a wave stages one channel plane per pass, a lane 16 bytes of it: plane p of the block (image p / 3, channel p % 3) is
+  // 1 024 contiguous bytes of the input and, kL0Image being 3 * kL0Plane, starts at LDS byte p * kL0Plane -- the pass
+  // costs two VALU instructions of addressing (15 when a thread walked the pieces of the block and divided by 192)
+  static_assert(kL0Image == 3 * kL0Plane && kL0Plane % 16 == 0, "the planes of a block follow each other at one stride");
+  const uint8_t *__restrict__ src = imgs + (size_t)img0 * 3072;
+#pragma clang loop unroll(disable) interleave(disable) vectorize(disable)
+  for (int p = wave; p < cnt * 3; p += kBlock / 64) {
+    uint4 v = *reinterpret_cast<const uint4 *>(src + (size_t)p * 1024 + (uint32_t)lane * 16);
     v.x = quantise4(v.x); v.y = quantise4(v.y); v.z = quantise4(v.z); v.w = quantise4(v.w);
-    const int g = i / 192, j = i - g * 192;                       // image, 16-byte piece of it
-    q4[(g * kL0Image + (j >> 6) * kL0Plane + (j & 63) * 16) >> 4] = v;  // 64 pieces per channel plane
+    q4[p * (kL0Plane / 16) + lane] = v;
   }
   // A operands (loop-invariant): 16 + 8 (+ 8) bytes per lane and neuron tile
   const uint8_t *__restrict__ tab = l0tab + kL0TileOffset;
@@ -483,26 +484,56 @@ __global__ __launch_bounds__(kBlock, 2) void k_conv0_tile(const uint8_t *__restr
   // A tile is one output ROW: 30 of the 32 pixel lanes carry a pixel (the other two compute on the bytes behind the row
   // and store nothing), 30 tiles per image instead of 29 -- and everything a lane needs to find its bytes and its output
   // word is a wave-uniform term plus a constant of the lane, where tiles of 32 consecutive pixels of the flattened map
-  // (29 per image, the first form) cost thirteen VALU instructions of divide-by-30 arithmetic per tile against six now.
+  // (29 per image, the first form) cost thirteen VALU instructions of divide-by-30 arithmetic per tile against six (round 3; two now, below).
   // Measured gain: 2 % of the stage only (0.502 -> 0.491 ms, profiles/r03_layer0_row_tiles_ab.txt): the instructions
   // saved are the cheap full-rate kind and there are 3.4 % more tiles
+  //
+  // The tile loop (round 24): 42 VALU instructions per tile where there were 50.  The LDS addresses of
+  // a tile are two lane constants (al_lane, al2_lane: the `& ~3` applies to the lane part alone, the tile term
+  // gi * kL0Image + 32 * oy being a multiple of 4) plus the tile term, which the scalar unit forms: two v_add per tile,
+  // the run offsets in the reads' immediate offsets.  The output address is a scalar row pointer plus a lane constant
+  // (no VALU).  Lane half 1's constant operand 0x00004001 is written ONCE, before the loop: the v_alignbyte that
+  // forms run (2,1) executes with the upper 32 lanes masked off and leaves it standing (no v_cndmask).  The two
+  // 16-bit sign words are merged unshifted (one swap, a shift and the or-not).  The next tile's five fetches are issued
+  // behind this tile's first MFMAs, before its sign chains, into a second register set: the chains run with the reads in flight.
+  constexpr int W = OUT2 ? 4 : 2;  // output dwords per pixel
   const uint32_t lane_byte = (uint32_t)(r + h * kL0Plane);
+  // this lane's runs: h = 0: (c,ky) = (0,0) (0,1) (0,2) (2,0) and, for the K = 16 product, (2,1);
+  //                   h = 1: (1,0) (1,1) (1,2) (2,2) and the constants 1, 64
+  const uint32_t al_lane = lane_byte & ~3u;  // shift: (lane_byte & 3) in both halves (kL0Plane % 4 == 0)
+  uint32_t al2_lane = al_lane + 2 * kL0Plane - h * (kL0Plane - 64);  // run (2,0) / (2,2): two rows apart
+  uint32_t lane_out = (uint32_t)(r * W + h) * 4;                     // bytes into the output row
+  // (opaque to the optimiser, which otherwise takes the constant 2 * kL0Plane back out of al2_lane and adds it per tile
+  // and per run, and turns the row pointer into a carried 64-bit vector add)
+  asm("" : "+v"(al2_lane), "+v"(lane_out));
   const bool live = r < 30;
-  for (int T = wave; T < cnt * 30; T += kBlock / 64) {
-    const int gi = T / 30, oy = T - gi * 30;            // wave-uniform
-    const size_t pix = (size_t)(img0 + gi) * 900 + (size_t)(oy * 30) + r;
-    const uint32_t byte = (uint32_t)(gi * kL0Image + 32 * oy) + lane_byte;
-    // this lane's runs: h = 0: (c,ky) = (0,0) (0,1) (0,2) (2,0) and, for the K = 16 product, (2,1);
-    //                   h = 1: (1,0) (1,1) (1,2) (2,2) and the constants 1, 64
-    const uint32_t *al = reinterpret_cast<const uint32_t *>(qb + (byte & ~3u));  // shift: (byte & 3) in both halves (kL0Plane % 4 == 0)
-    const uint32_t *al2 = reinterpret_cast<const uint32_t *>(qb + ((byte & ~3u) - h * (kL0Plane - 64)));  // run (2,0) / (2,2): two rows apart
+  const int tiles = cnt * 30;
+  uint32_t lo[5], hi[5];  // the two aligned dwords around each run
+  const auto fetch = [&](int T) {
+    const int gi = T / 30, oy = T - gi * 30;  // wave-uniform
+    const uint32_t tile = (uint32_t)(gi * kL0Image + 32 * oy);
+    const uint32_t *al = reinterpret_cast<const uint32_t *>(qb + (al_lane + tile));
+    const uint32_t *al2 = reinterpret_cast<const uint32_t *>(qb + (al2_lane + tile));
+#pragma unroll
+    for (int i = 0; i < 3; i++) lo[i] = al[8 * i], hi[i] = al[8 * i + 1];
+#pragma unroll
+    for (int i = 0; i < 2; i++) lo[3 + i] = al2[8 * i], hi[3 + i] = al2[8 * i + 1];
+  };
+  uint32_t bs_lo = 0x00004001u;  // lane half 1 keeps this through the loop
+  fetch(wave);
+  for (int T = wave; T < tiles; T += kBlock / 64) {
+    uint8_t *orow = reinterpret_cast<uint8_t *>(out + ((size_t)img0 * 900 + (size_t)T * 30) * W);  // (T * 30 = gi * 900 + oy * 30)
+    asm volatile("" : "+v"(lane_out));  // (keeps the row pointer scalar: the store is SGPR base + this lane constant)
     v4i bb;
-    bb[0] = (int)lds_run<0>(al, byte);
-    bb[1] = (int)lds_run<32>(al, byte);
-    bb[2] = (int)lds_run<64>(al, byte);
-    bb[3] = (int)lds_run<2 * kL0Plane>(al2, byte);
-    const uint32_t mid = lds_run<2 * kL0Plane + 32>(al2, byte);  // run (2,1) where h = 0
-    const long bs = (long)(uint64_t)(h ? 0x00004001u : mid);
+#pragma unroll
+    for (int i = 0; i < 4; i++) bb[i] = (int)__builtin_amdgcn_alignbyte(hi[i], lo[i], lane_byte);
+    {  // run (2,1) where h = 0; lanes 32..63 are masked off and keep their constant
+      uint64_t saved;
+      asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, 0xffffffff\n\tv_alignbyte_b32 %0, %2, %3, %4\n\ts_mov_b64 exec, %1"
+                   : "+v"(bs_lo), "=&s"(saved)
+                   : "v"(hi[4]), "v"(lo[4]), "v"(lane_byte));
+    }
+    const long bs = (long)(uint64_t)bs_lo;
     uint32_t x[2], y[2];
     // both neuron tiles' products are issued before either is read: the second chain covers the first one's latency
     v16i big[2], d0[2], d1[2];
@@ -513,24 +544,25 @@ __global__ __launch_bounds__(kBlock, 2) void k_conv0_tile(const uint8_t *__restr
       d0[ct] = __builtin_amdgcn_mfma_i32_32x32x16_i8(asm0[ct], bs, big[ct], 0, 0, 0);  // dot - t0 - 1: sign = !fire
       if constexpr (OUT2) d1[ct] = __builtin_amdgcn_mfma_i32_32x32x16_i8(asm1[ct], bs, big[ct], 0, 0, 0);  // second threshold
     }
+    fetch(min(T + kBlock / 64, tiles - 1));  // the next tile's (behind the last one: a staged row again, unused)
 #pragma unroll
     for (int ct = 0; ct < 2; ct++) {
       if constexpr (!OUT2) {
-        x[ct] = sign_bits16(d0[ct]) << (16 * h);
+        x[ct] = sign_bits16(d0[ct]);
       } else {
         const uint32_t n0 = sign_bits16(d0[ct]), n1 = sign_bits16(d1[ct]);
-        x[ct] = (n0 & n1) << (16 * h);  // sign plane: neither fired
-        y[ct] = (n0 ^ n1) << (16 * h);  // inverted non-zero plane
+        x[ct] = n0 & n1;  // sign plane: neither fired
+        y[ct] = n0 ^ n1;  // inverted non-zero plane
       }
     }
     if constexpr (!OUT2) {
-      const uint32_t w = ~merge_halves(x[0], x[1]);  // collected !fire
-      if (live) out[pix * 2 + h] = w;
+      const uint32_t w = ~merge_halves16(x[0], x[1]);  // collected !fire
+      if (live) *reinterpret_cast<uint32_t *>(orow + lane_out) = w;
     } else {  // [pixel][C/64 = 1][plane][half]
-      const uint32_t sg = merge_halves(x[0], x[1]), nz = ~merge_halves(y[0], y[1]);
+      const uint32_t sg = merge_halves16(x[0], x[1]), nz = ~merge_halves16(y[0], y[1]);
       if (live) {
-        out[pix * 4 + h] = sg;
-        out[pix * 4 + 2 + h] = nz;
+        *reinterpret_cast<uint32_t *>(orow + lane_out) = sg;
+        *reinterpret_cast<uint32_t *>(orow + lane_out + 8) = nz;
       }
     }
   }
@@ -1160,7 +1192,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void k_tail_mfma(const std::
     }
     if (grp + (int)gridDim.x < ngroups) fetch(grp + gridDim.x);
     __syncthreads();
-#pragma unroll 1
+#pragma clang loop unroll(disable) interleave(disable) vectorize(disable)
     for (int t0 = 0; t0 < nitems; t0 += 32) {
       const int item = min(t0 + c, nitems - 1);
       int base;
@@ -3294,7 +3326,9 @@ inline long long lfc_block_max() {
 }
 
 // images: from here on layer 0 runs in its LDS-staged tile form (k_conv0_tile) -- measured (tools/stage_times.py): 2 048
-// images 28.6 vs 18.2 us for the lane-per-pixel form, 8 192 44.7 vs 47.0, 131 072 516 vs 785; BNN_MI355X_L0_TILE_MIN overrides
+// images 28.6 vs 18.2 us for the lane-per-pixel form, 8 192 44.7 vs 47.0, 131 072 516 vs 785; BNN_MI355X_L0_TILE_MIN overrides.
+// With the 42-instruction tile loop (profiles/r24_l0_valu_ab.txt): 2 048 23.9 vs 18.4, 4 096 25.9 vs 26.4, 8 192 38.6 vs 45.3 --
+// no win outside the noise below 8 192: the edge stays
 inline long long l0_tile_min() {
   static const long long v = [] {
     const char *e = std::getenv("BNN_MI355X_L0_TILE_MIN");

@@ -345,6 +345,40 @@ class PynqBNN:
             raise ValueError("rates: a probability in [0, 1) for each of the {} layers".format(layers))
         return np.floor(p * 4294967296.0).astype(np.uint64).astype(np.uint32)
 
+    # the families of parameter-memory upset campaigns, by the stem of bnn_mi355x_<stem>_campaigns and
+    # bnn_mi355x_last_<stem>_counts / _seeds: the words of the family's error, the last axes of its counts per layer
+    _UPSET_FAMILIES = {"mem_noise": ("memory noise", (2,)), "hardened_mem_noise": ("hardened memory noise", (2, 2)),
+                       "exposure": ("exposure", (2, 2)), "ecc_exposure": ("ecc exposure", (6,)), "repair_exposure": ("repair exposure", (8,)),
+                       "wecc_exposure": ("wecc exposure", (12,)), "iwecc_exposure": ("iwecc exposure", (12,))}
+
+    def _upset_campaign(self, family, path, num_runs, rates_w, rates_t, seed, lead_args=(), tail_args=()):
+        """One call of bnn_mi355x_<family>_campaigns, whose arguments are (path, classes, *lead_args: the memory
+        organisation, num_runs, seed, the two rate arrays, their length, *tail_args: epoch_images first where the family
+        has epochs, image_number, usecPerImage).  -> (classes int32 (num_runs, n), counts int64 (num_runs, [epochs,]
+        layers) + the family's last axes); the seeds go to self.mem_noise_seeds, the time to self.usecPerImage."""
+        lib = self.interface
+        words, counts_tail = self._UPSET_FAMILIES[family]
+        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
+        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
+        up = ctypes.POINTER(ctypes.c_uint)
+        size, usec = ctypes.c_int(0), ctypes.c_float(0)
+        ptr = getattr(lib, "bnn_mi355x_{}_campaigns".format(family))(
+            path.encode(), len(self.classes), *lead_args, num_runs, seed, qw.ctypes.data_as(up), qt.ctypes.data_as(up), len(qw), *tail_args,
+            ctypes.byref(size), ctypes.byref(usec))
+        if not ptr:
+            raise RuntimeError(words + " campaigns failed: " + lib.bnn_mi355x_last_error().decode())
+        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
+        last_counts = getattr(lib, "bnn_mi355x_last_{}_counts".format(family))
+        k = last_counts(None, 0)
+        counts = (ctypes.c_long * max(k, 1))()
+        last_counts(counts, k)
+        seeds = (ctypes.c_ulonglong * num_runs)()
+        getattr(lib, "bnn_mi355x_last_{}_seeds".format(family))(seeds, num_runs)
+        self.mem_noise_seeds = list(seeds)
+        self.usecPerImage = usec.value
+        epochs = (-(-size.value // tail_args[0]),) if tail_args else ()  # (the last epoch may be short)
+        return result, np.array(counts[:k], np.int64).reshape((num_runs,) + epochs + (len(qw),) + counts_tail)
+
     def inference_multiple_mem_noise(self, path, num_runs, rates_w, rates_t, seed=0, scheme=None, burst=1):
         """scheme (0 none, 1 TMR, 2 interleaved, 3 resilient-interleaved) or burst > 1: the hardened form,
         inference_multiple_hardened_mem_noise.  Else num_runs independent runs over the images of `path`, every bit of layer L's weight memory flipped with
@@ -355,24 +389,7 @@ class PynqBNN:
         usecPerImage: device time of the call / (num_runs * n)."""
         if scheme is not None or burst != 1:
             return self.inference_multiple_hardened_mem_noise(path, num_runs, rates_w, rates_t, scheme or 0, burst, seed)
-        lib = self.interface
-        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
-        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
-        up = ctypes.POINTER(ctypes.c_uint)
-        size, usec = ctypes.c_int(0), ctypes.c_float(0)
-        ptr = lib.bnn_mi355x_mem_noise_campaigns(path.encode(), len(self.classes), num_runs, seed, qw.ctypes.data_as(up),
-                                                 qt.ctypes.data_as(up), len(qw), ctypes.byref(size), ctypes.byref(usec))
-        if not ptr:
-            raise RuntimeError("memory noise campaigns failed: " + lib.bnn_mi355x_last_error().decode())
-        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
-        k = lib.bnn_mi355x_last_mem_noise_counts(None, 0)
-        counts = (ctypes.c_long * max(k, 1))()
-        lib.bnn_mi355x_last_mem_noise_counts(counts, k)
-        seeds = (ctypes.c_ulonglong * num_runs)()
-        lib.bnn_mi355x_last_mem_noise_seeds(seeds, num_runs)
-        self.mem_noise_seeds = list(seeds)
-        self.usecPerImage = usec.value
-        return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2)
+        return self._upset_campaign("mem_noise", path, num_runs, rates_w, rates_t, seed)
 
     # extension: hardened memory schemes in the memory upset campaigns (TMR, interleaved thresholds; bursts)
     def hardening_layout(self, scheme):
@@ -394,24 +411,7 @@ class PynqBNN:
         probability rates_w[L] / rates_t[L] per aligned group.  -> (classes int32 (num_runs, n), counts int64 (num_runs,
         layers, 2: weights, thresholds, 2: physical bits flipped, logical bits that differ after voting and
         de-interleaving)).  The seeds are left in self.mem_noise_seeds."""
-        lib = self.interface
-        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
-        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
-        up = ctypes.POINTER(ctypes.c_uint)
-        size, usec = ctypes.c_int(0), ctypes.c_float(0)
-        ptr = lib.bnn_mi355x_hardened_mem_noise_campaigns(path.encode(), len(self.classes), scheme, burst, num_runs, seed, qw.ctypes.data_as(up),
-                                                          qt.ctypes.data_as(up), len(qw), ctypes.byref(size), ctypes.byref(usec))
-        if not ptr:
-            raise RuntimeError("hardened memory noise campaigns failed: " + lib.bnn_mi355x_last_error().decode())
-        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
-        k = lib.bnn_mi355x_last_hardened_mem_noise_counts(None, 0)
-        counts = (ctypes.c_long * max(k, 1))()
-        lib.bnn_mi355x_last_hardened_mem_noise_counts(counts, k)
-        seeds = (ctypes.c_ulonglong * num_runs)()
-        lib.bnn_mi355x_last_hardened_mem_noise_seeds(seeds, num_runs)
-        self.mem_noise_seeds = list(seeds)
-        self.usecPerImage = usec.value
-        return result, np.array(counts[:k], np.int64).reshape(num_runs, -1, 2, 2)
+        return self._upset_campaign("hardened_mem_noise", path, num_runs, rates_w, rates_t, seed, (scheme, burst))
 
     # extension: exposure campaigns (upsets that accumulate over epochs of images, with scrubbing)
     def inference_multiple_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, burst=1, seed=0, code=0,
@@ -436,26 +436,7 @@ class PynqBNN:
                                                            burst, seed)
         if code:
             return self.inference_multiple_ecc_exposure(path, num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme, code, burst, seed)
-        lib = self.interface
-        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
-        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
-        up = ctypes.POINTER(ctypes.c_uint)
-        size, usec = ctypes.c_int(0), ctypes.c_float(0)
-        ptr = lib.bnn_mi355x_exposure_campaigns(path.encode(), len(self.classes), scheme, burst, num_runs, seed, qw.ctypes.data_as(up),
-                                                qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every, ctypes.byref(size),
-                                                ctypes.byref(usec))
-        if not ptr:
-            raise RuntimeError("exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
-        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
-        k = lib.bnn_mi355x_last_exposure_counts(None, 0)
-        counts = (ctypes.c_long * max(k, 1))()
-        lib.bnn_mi355x_last_exposure_counts(counts, k)
-        seeds = (ctypes.c_ulonglong * num_runs)()
-        lib.bnn_mi355x_last_exposure_seeds(seeds, num_runs)
-        self.mem_noise_seeds = list(seeds)
-        self.usecPerImage = usec.value
-        epochs = -(-size.value // epoch_images)
-        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 2, 2)
+        return self._upset_campaign("exposure", path, num_runs, rates_w, rates_t, seed, (scheme, burst), (epoch_images, scrub_every))
 
     # extension: SEC-DED coded threshold memories in the exposure campaigns
     def inference_multiple_ecc_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, scheme=0, code=1, burst=1, seed=0):
@@ -465,26 +446,7 @@ class PynqBNN:
         Weights and the 24-bit thresholds of CNV layer 0 are not coded.  -> (classes int32 (num_runs, n), counts int64
         (num_runs, epochs, layers, 6: weights physical, logical; thresholds physical (data plus check), logical (after
         decoding); threshold words corrected; detected as uncorrectable)).  The seeds are left in self.mem_noise_seeds."""
-        lib = self.interface
-        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
-        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
-        up = ctypes.POINTER(ctypes.c_uint)
-        size, usec = ctypes.c_int(0), ctypes.c_float(0)
-        ptr = lib.bnn_mi355x_ecc_exposure_campaigns(path.encode(), len(self.classes), scheme, code, burst, num_runs, seed, qw.ctypes.data_as(up),
-                                                    qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every, ctypes.byref(size),
-                                                    ctypes.byref(usec))
-        if not ptr:
-            raise RuntimeError("ecc exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
-        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
-        k = lib.bnn_mi355x_last_ecc_exposure_counts(None, 0)
-        counts = (ctypes.c_long * max(k, 1))()
-        lib.bnn_mi355x_last_ecc_exposure_counts(counts, k)
-        seeds = (ctypes.c_ulonglong * num_runs)()
-        lib.bnn_mi355x_last_ecc_exposure_seeds(seeds, num_runs)
-        self.mem_noise_seeds = list(seeds)
-        self.usecPerImage = usec.value
-        epochs = -(-size.value // epoch_images)
-        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 6)
+        return self._upset_campaign("ecc_exposure", path, num_runs, rates_w, rates_t, seed, (scheme, code, burst), (epoch_images, scrub_every))
 
     # extension: repair scrubs in the exposure campaigns
     def inference_multiple_repair_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, repair_every=1, scheme=0, code=0,
@@ -497,26 +459,8 @@ class PynqBNN:
         (num_runs, n), counts int64 (num_runs, epochs, layers, 8: the six of inference_multiple_ecc_exposure, the words
         the epoch's repair rewrote, the words of the repaired memories still unlike the loaded ones after it)).  The seeds
         are left in self.mem_noise_seeds."""
-        lib = self.interface
-        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
-        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
-        up = ctypes.POINTER(ctypes.c_uint)
-        size, usec = ctypes.c_int(0), ctypes.c_float(0)
-        ptr = lib.bnn_mi355x_repair_exposure_campaigns(path.encode(), len(self.classes), scheme, code, burst, num_runs, seed,
-                                                       qw.ctypes.data_as(up), qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every,
-                                                       repair_every, ctypes.byref(size), ctypes.byref(usec))
-        if not ptr:
-            raise RuntimeError("repair exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
-        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
-        k = lib.bnn_mi355x_last_repair_exposure_counts(None, 0)
-        counts = (ctypes.c_long * max(k, 1))()
-        lib.bnn_mi355x_last_repair_exposure_counts(counts, k)
-        seeds = (ctypes.c_ulonglong * num_runs)()
-        lib.bnn_mi355x_last_repair_exposure_seeds(seeds, num_runs)
-        self.mem_noise_seeds = list(seeds)
-        self.usecPerImage = usec.value
-        epochs = -(-size.value // epoch_images)
-        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 8)
+        return self._upset_campaign("repair_exposure", path, num_runs, rates_w, rates_t, seed, (scheme, code, burst),
+                                    (epoch_images, scrub_every, repair_every))
 
     # extension: SEC-DED (72,64) coded weight memories in the exposure campaigns
     def inference_multiple_wecc_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, repair_every=0, scheme=0, code=0,
@@ -529,26 +473,8 @@ class PynqBNN:
         inference_multiple_repair_exposure -- weights physical counts data plus check bits, weights logical the data bits
         that differ after decoding -- then the weight code words corrected, detected as uncorrectable, rewritten by the
         epoch's repair, still unlike the loaded ones after it)).  The seeds are left in self.mem_noise_seeds."""
-        lib = self.interface
-        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
-        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
-        up = ctypes.POINTER(ctypes.c_uint)
-        size, usec = ctypes.c_int(0), ctypes.c_float(0)
-        ptr = lib.bnn_mi355x_wecc_exposure_campaigns(path.encode(), len(self.classes), scheme, code, weight_code, burst, num_runs, seed,
-                                                     qw.ctypes.data_as(up), qt.ctypes.data_as(up), len(qw), epoch_images, scrub_every,
-                                                     repair_every, ctypes.byref(size), ctypes.byref(usec))
-        if not ptr:
-            raise RuntimeError("wecc exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
-        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
-        k = lib.bnn_mi355x_last_wecc_exposure_counts(None, 0)
-        counts = (ctypes.c_long * max(k, 1))()
-        lib.bnn_mi355x_last_wecc_exposure_counts(counts, k)
-        seeds = (ctypes.c_ulonglong * num_runs)()
-        lib.bnn_mi355x_last_wecc_exposure_seeds(seeds, num_runs)
-        self.mem_noise_seeds = list(seeds)
-        self.usecPerImage = usec.value
-        epochs = -(-size.value // epoch_images)
-        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 12)
+        return self._upset_campaign("wecc_exposure", path, num_runs, rates_w, rates_t, seed, (scheme, code, weight_code, burst),
+                                    (epoch_images, scrub_every, repair_every))
 
     # extension: column-interleaved code words over the coded weight memories
     def inference_multiple_iwecc_exposure(self, path, num_runs, rates_w, rates_t, epoch_images, scrub_every=0, repair_every=0, scheme=0, code=0,
@@ -561,26 +487,8 @@ class PynqBNN:
         word a bit belongs to changes.  Needs weight_code 1.  -> (classes int32 (num_runs, n), counts int64 (num_runs,
         epochs, layers, 12) as inference_multiple_wecc_exposure, the code words counted after gathering).  The seeds are
         left in self.mem_noise_seeds."""
-        lib = self.interface
-        qw = np.ascontiguousarray(self.mem_noise_rates(rates_w), np.uint32)
-        qt = np.ascontiguousarray(self.mem_noise_rates(rates_t, thresholds=True), np.uint32)
-        up = ctypes.POINTER(ctypes.c_uint)
-        size, usec = ctypes.c_int(0), ctypes.c_float(0)
-        ptr = lib.bnn_mi355x_iwecc_exposure_campaigns(path.encode(), len(self.classes), scheme, code, weight_code, weight_interleave, burst,
-                                                      num_runs, seed, qw.ctypes.data_as(up), qt.ctypes.data_as(up), len(qw), epoch_images,
-                                                      scrub_every, repair_every, ctypes.byref(size), ctypes.byref(usec))
-        if not ptr:
-            raise RuntimeError("iwecc exposure campaigns failed: " + lib.bnn_mi355x_last_error().decode())
-        result = self._collect(ptr, num_runs * size.value).reshape(num_runs, size.value)
-        k = lib.bnn_mi355x_last_iwecc_exposure_counts(None, 0)
-        counts = (ctypes.c_long * max(k, 1))()
-        lib.bnn_mi355x_last_iwecc_exposure_counts(counts, k)
-        seeds = (ctypes.c_ulonglong * num_runs)()
-        lib.bnn_mi355x_last_iwecc_exposure_seeds(seeds, num_runs)
-        self.mem_noise_seeds = list(seeds)
-        self.usecPerImage = usec.value
-        epochs = -(-size.value // epoch_images)
-        return result, np.array(counts[:k], np.int64).reshape(num_runs, epochs, len(qw), 12)
+        return self._upset_campaign("iwecc_exposure", path, num_runs, rates_w, rates_t, seed, (scheme, code, weight_code, weight_interleave, burst),
+                                    (epoch_images, scrub_every, repair_every))
 
     # extension: input-buffer faults (which pixel bits matter; the accuracy at input-buffer upset rate p)
     def enumerate_input_faults(self):
@@ -865,11 +773,11 @@ class CnvClassifier:
         return result
 
     # extension: exposure campaigns (PynqBNN.inference_multiple_exposure)
-    def classify_images_exposure(self, imgs, *args):
-        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_exposure(p, *args))
+    def classify_images_exposure(self, imgs, *args, **kwargs):
+        return self._with_tmp(imgs, lambda p: self.bnn.inference_multiple_exposure(p, *args, **kwargs))
 
-    def classify_cifars_exposure(self, path, *args):
-        result = self.bnn.inference_multiple_exposure(path, *args)
+    def classify_cifars_exposure(self, path, *args, **kwargs):
+        result = self.bnn.inference_multiple_exposure(path, *args, **kwargs)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
@@ -1070,8 +978,8 @@ class LfcClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
-    def classify_mnists_exposure(self, mnist_format_file, *args):
-        result = self.bnn.inference_multiple_exposure(mnist_format_file, *args)
+    def classify_mnists_exposure(self, mnist_format_file, *args, **kwargs):
+        result = self.bnn.inference_multiple_exposure(mnist_format_file, *args, **kwargs)
         self.usecPerImage = self.bnn.usecPerImage
         return result
 

@@ -44,6 +44,8 @@ single bit of the input image flipped alone (``PynqBNN.input_fault_sweep``), and
 sweeps with ``PynqBNN.sweep_profile`` on, which adds per fault and layer the images and the activations that differ from
 the fault-free ones; ``propagation_curves`` reduces the two arrays to a masking curve and a mean error size per layer.
 """
+from collections import namedtuple
+
 import numpy as np
 
 from .. import bnn as _bnn
@@ -76,19 +78,41 @@ WEIGHT_CODES = ("", "SEC-DED weights")
 WEIGHT_INTERLEAVES = ("", "column-interleaved")
 
 
-def scheme_and_code(entry):
-    """an entry of hardening_curve's / scrubbing_curve's `schemes`: a plain scheme, or a (scheme, code) pair"""
-    return (int(entry[0]), int(entry[1])) if isinstance(entry, (tuple, list)) else (int(entry), 0)
+# a memory organisation of the exposure campaigns: the numbers the C ABI takes, by HARDENING_SCHEMES, ECC_CODES, WEIGHT_CODES
+# and WEIGHT_INTERLEAVES
+Organisation = namedtuple("Organisation", "scheme code weight_code weight_interleave")
 
 
-def scheme_code_and_weight_code(entry):
-    """likewise, a (scheme, code, weight_code) triple as well"""
-    return scheme_and_code(entry) + ((int(entry[2]),) if isinstance(entry, (tuple, list)) and len(entry) > 2 else (0,))
+def organisation(entry):
+    """an entry of hardening_curve's / scrubbing_curve's `schemes` -> Organisation: a plain scheme, or a (scheme, code), (scheme,
+    code, weight_code) or (scheme, code, weight_code, weight_interleave) tuple; what an entry leaves out is 0"""
+    parts = tuple(entry) if isinstance(entry, (tuple, list)) else (entry,)
+    return Organisation(*(int(x) for x in parts + (0,) * (4 - len(parts))))
 
 
-def scheme_codes_and_interleave(entry):
-    """likewise, a (scheme, code, weight_code, weight_interleave) 4-tuple as well"""
-    return scheme_code_and_weight_code(entry) + ((int(entry[3]),) if isinstance(entry, (tuple, list)) and len(entry) > 3 else (0,))
+UpsetCounts = namedtuple("UpsetCounts", "weights_physical weights_logical thresholds_physical thresholds_logical corrected detected "
+                                        "repaired unrepaired weight_corrected weight_detected weight_repaired weight_unrepaired")
+
+
+def upset_counts(counts):
+    """The counts of a hardened or exposure campaign, [run, (epoch,) layer] + the family's last axes, by name: an
+    UpsetCounts of arrays [run, (epoch,) layer], None for the blocks the family does not count.  The columns:
+
+        last axes   column    field
+        (2, 2)...   0, 1      weights_physical (bits flipped; with a weight code data plus check bits), weights_logical (bits
+                              that differ after voting, de-interleaving and decoding)
+                    2, 3      thresholds_physical (with a code data plus check bits), thresholds_logical
+        6 ...       4, 5      corrected, detected: threshold words the SEC-DED decoder corrected / found uncorrectable
+        8 ...       6, 7      repaired, unrepaired: words the epoch's repair rewrote / of the repaired memories still unlike
+                              the loaded ones after it
+        12          8 ... 11  weight_corrected, weight_detected, weight_repaired, weight_unrepaired: the same four of the
+                              weight code words
+
+    (2, 2) is [weights, thresholds][physical, logical]: columns 0 ... 3 of the wider forms."""
+    counts = np.asarray(counts)
+    if counts.shape[-1] == 2:
+        counts = counts.reshape(counts.shape[:-2] + (4,))
+    return UpsetCounts(*(counts[..., i] if i < counts.shape[-1] else None for i in range(len(UpsetCounts._fields))))
 
 
 def organisation_name(scheme, code=0, weight_code=0, weight_interleave=0):
@@ -183,10 +207,10 @@ class FaultTest:
         return (results, times, accuracies)
 
 
-    def _classify(self, classifier, method, *args):
-        """classifier.classify_<set>_<method>(input, *args) for this test's input set"""
+    def _classify(self, classifier, method, *args, **kwargs):
+        """classifier.classify_<set>_<method>(input, *args, **kwargs) for this test's input set"""
         kind = {"cifar10": "cifars", "mnist": "mnists"}.get(self.dataset, "images")
-        return getattr(classifier, "classify_{}{}".format(kind, method))(self.input_file, *args)
+        return getattr(classifier, "classify_{}{}".format(kind, method))(self.input_file, *args, **kwargs)
 
     def sensitivity(self, layers, target_type=0, word_size=1):
         """Every distinct single fault of `layers` (target_type 0 weights / 1 thresholds, word_size adjacent bits),
@@ -279,20 +303,15 @@ class FaultTest:
             self.network, self.dataset, num_runs, rates_w, rates_t))
         if weight_interleave and not weight_code:
             raise ValueError("run_memory_noise_test: weight_interleave 1 needs weight_code 1")
-        if weight_code:
+        if weight_code or code:
             print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code, weight_code, weight_interleave), burst))
-            results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, 1 << 30, 0, scheme or 0, burst, seed, code, 0,
-                                             weight_code, *((weight_interleave,) if weight_interleave else ()))
-            counts = counts[:, 0]
-        elif code:
-            print("  memory organisation: {}, bursts of {}".format(organisation_name(scheme or 0, code), burst))
-            results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, 1 << 30, 0, scheme or 0, burst, seed, code)
-            counts = counts[:, 0]
-        elif scheme is not None or burst != 1:
-            print("  memory organisation: {}, bursts of {}".format(HARDENING_SCHEMES[scheme or 0], burst))
-            results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed, scheme or 0, burst)
+            results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, 1 << 30, 0, scheme or 0, burst, seed, code=code,
+                                             repair_every=0, weight_code=weight_code, weight_interleave=weight_interleave)
+            counts = counts[:, 0]  # (the one epoch)
         else:
-            results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed)
+            if scheme is not None or burst != 1:
+                print("  memory organisation: {}, bursts of {}".format(HARDENING_SCHEMES[scheme or 0], burst))
+            results, counts = self._classify(classifier, "_mem_noise", num_runs, rates_w, rates_t, seed, scheme, burst)
         self.mem_noise_results, self.mem_noise_counts, self.mem_noise_usec = results, counts, classifier.usecPerImage
         accuracies = [util.calculate_accuracy(row.tolist(), self.labels) for row in results]
         print("Accuracies:", accuracies)
@@ -323,10 +342,8 @@ class FaultTest:
               "scrub every {}{}".format(self.network, self.dataset, num_runs, epoch_images, rates_w, rates_t,
                                         organisation_name(scheme or 0, code, weight_code, weight_interleave), burst, scrub_every or "never",
                                         ", repair every {}".format(repair_every) if repair_every else ""))
-        args = (num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst, seed)
-        results, counts = self._classify(classifier, "_exposure", *(args + (code, repair_every, weight_code, weight_interleave) if weight_interleave else
-                                                                    args + (code, repair_every, weight_code) if weight_code else
-                                                                    args + (code, repair_every) if repair_every else args + (code,) if code else args))
+        results, counts = self._classify(classifier, "_exposure", num_runs, rates_w, rates_t, epoch_images, scrub_every, scheme or 0, burst, seed,
+                                         code=code, repair_every=repair_every, weight_code=weight_code, weight_interleave=weight_interleave)
         self.exposure_results, self.exposure_counts, self.exposure_usec = results, counts, classifier.usecPerImage
         accuracies = [[util.calculate_accuracy(row[i: i + epoch_images].tolist(), self.labels[i: i + epoch_images])
                        for i in range(0, results.shape[1], epoch_images)] for row in results]
@@ -653,27 +670,26 @@ class NetworkTest:
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme, code, weight_code, weight_interleave in map(scheme_codes_and_interleave, schemes):
+        for org in map(organisation, schemes):
             for burst in bursts:
                 for p in rates:
-                    accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, scheme, burst, code,
-                                                                  *((weight_code, weight_interleave) if weight_interleave else
-                                                                    (weight_code,) if weight_code else ()))
-                    name = "{} burst {} upset rate {:g}".format(organisation_name(scheme, code, weight_code, weight_interleave), burst, p)
+                    accuracies, counts = ft.run_memory_noise_test(num_runs, float(p), float(p), seed, org.scheme, burst, code=org.code,
+                                                                  weight_code=org.weight_code, weight_interleave=org.weight_interleave)
+                    c = upset_counts(counts)
+                    name = "{} burst {} upset rate {:g}".format(organisation_name(*org), burst, p)
                     raw.append(self._raw(name, num_runs, 0, [], accuracies))
-                    extra[name] = {"stddev accuracy": float(np.std(accuracies)), "scheme": int(scheme), "burst": int(burst), "rate": float(p)}
-                    if weight_code:  # [run, layer, 12]
-                        if weight_interleave:
-                            extra[name]["weight interleave"] = int(weight_interleave)
-                        extra[name].update({"weight code": int(weight_code), "corrected weight words": int(counts[..., 8].sum()),
-                                            "detected weight words": int(counts[..., 9].sum())})
-                        counts = counts[..., :6] if code else counts[..., :4].reshape(counts.shape[:2] + (2, 2))
-                    if code:  # [run, layer, 6]
-                        extra[name].update({"code": int(code), "physical bits": int(counts[..., [0, 2]].sum()),
-                                            "logical bits": int(counts[..., [1, 3]].sum()), "corrected words": int(counts[..., 4].sum()),
-                                            "detected words": int(counts[..., 5].sum())})
-                    else:
-                        extra[name].update({"physical bits": int(counts[..., 0].sum()), "logical bits": int(counts[..., 1].sum())})
+                    e = extra[name] = {"stddev accuracy": float(np.std(accuracies)), "scheme": org.scheme, "burst": int(burst), "rate": float(p)}
+                    if org.weight_interleave:
+                        e["weight interleave"] = org.weight_interleave
+                    if org.weight_code:
+                        e.update({"weight code": org.weight_code, "corrected weight words": int(c.weight_corrected.sum()),
+                                  "detected weight words": int(c.weight_detected.sum())})
+                    if org.code:
+                        e["code"] = org.code
+                    e.update({"physical bits": int(c.weights_physical.sum() + c.thresholds_physical.sum()),
+                              "logical bits": int(c.weights_logical.sum() + c.thresholds_logical.sum())})
+                    if org.code:
+                        e.update({"corrected words": int(c.corrected.sum()), "detected words": int(c.detected.sum())})
         stats = self._stats(util.dict_of_dicts_merge(*raw))
         for name, e in extra.items():
             stats["results"][name].update(e)
@@ -701,44 +717,41 @@ class NetworkTest:
         if self.control is None:  # (rate 0: the fault-free classes)
             self.control = ft.run_memory_noise_test(1, 0.0, 0.0, seed or 1)[0][0]
         raw, extra = [], {}
-        for scheme, code, weight_code, weight_interleave in map(scheme_codes_and_interleave, schemes):
+        def per_epoch_sum(a):
+            return [int(x) for x in a.sum(axis=(0, 2))]  # (over the runs and the layers)
+
+        for org in map(organisation, schemes):
             for burst in bursts:
                 for p in rates:
                     for every in scrub_intervals:
                         every, repair = (int(every[0]), int(every[1])) if isinstance(every, (tuple, list)) else (every, 0)
-                        per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, scheme, burst, seed, code,
-                                                                 *((repair, weight_code, weight_interleave) if weight_interleave else
-                                                                   (repair, weight_code) if weight_code else (repair,) if repair else ()))
+                        per_epoch, counts = ft.run_exposure_test(num_runs, float(p), float(p), epoch_images, every, org.scheme, burst, seed,
+                                                                 code=org.code, repair_every=repair, weight_code=org.weight_code,
+                                                                 weight_interleave=org.weight_interleave)
+                        c = upset_counts(counts)
                         accuracies = [util.calculate_accuracy(row.tolist(), ft.labels) for row in ft.exposure_results]
-                        name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(scheme, code, weight_code, weight_interleave), burst,
-                                                                                   p, every)
-                        status = {}
-                        if weight_code:  # [run, epoch, layer, 12]: the weight code words' four counters behind the repair shape
-                            status = {**({"weight interleave": int(weight_interleave)} if weight_interleave else {}), "weight code": int(weight_code),
-                                      "corrected weight words per epoch": [int(x) for x in counts[..., 8].sum(axis=(0, 2))],
-                                      "detected weight words per epoch": [int(x) for x in counts[..., 9].sum(axis=(0, 2))],
-                                      "repaired weight words per epoch": [int(x) for x in counts[..., 10].sum(axis=(0, 2))],
-                                      "unrepaired weight words per epoch": [int(x) for x in counts[..., 11].sum(axis=(0, 2))]}
-                            counts = counts[..., :8]
-                            if not repair:
-                                counts = counts[..., :6] if code else counts[..., :4].reshape(counts.shape[:3] + (2, 2))
-                        if repair:  # [run, epoch, layer, 8]: the repair's two counters behind the coded shape
+                        name = "{} burst {} upset rate {:g} scrub every {}".format(organisation_name(*org), burst, p, every)
+                        if repair:
                             name += " repair every {}".format(repair)
-                            status.update({"repair every": repair, "repaired words per epoch": [int(x) for x in counts[..., 6].sum(axis=(0, 2))],
-                                           "unrepaired words per epoch": [int(x) for x in counts[..., 7].sum(axis=(0, 2))]})
-                            counts = counts[..., :6]
-                            if not code:
-                                counts = counts[..., :4].reshape(counts.shape[:3] + (2, 2))
-                        if code:  # [run, epoch, layer, 6] -> the four counters in the uncoded shape, and the decode status
-                            status.update({"code": int(code), "corrected words per epoch": [int(x) for x in counts[..., 4].sum(axis=(0, 2))],
-                                           "detected words per epoch": [int(x) for x in counts[..., 5].sum(axis=(0, 2))]})
-                            counts = counts[..., :4].reshape(counts.shape[:3] + (2, 2))
                         raw.append(self._raw(name, num_runs, 0, [], accuracies))
-                        extra[name] = {"mean accuracy per epoch": [float(x) for x in np.mean(np.array(per_epoch, float), axis=0)],
-                                       "scheme": int(scheme), "burst": int(burst), "rate": float(p), "scrub every": int(every),
-                                       "epoch images": int(epoch_images), "physical bits": int(counts[..., 0].sum()),
-                                       "logical bits per epoch": [int(x) for x in counts[..., 1].sum(axis=(0, 2, 3))]}
-                        extra[name].update(status)
+                        e = extra[name] = {"mean accuracy per epoch": [float(x) for x in np.mean(np.array(per_epoch, float), axis=0)],
+                                           "scheme": org.scheme, "burst": int(burst), "rate": float(p), "scrub every": int(every),
+                                           "epoch images": int(epoch_images),
+                                           "physical bits": int(c.weights_physical.sum() + c.thresholds_physical.sum()),
+                                           "logical bits per epoch": per_epoch_sum(c.weights_logical + c.thresholds_logical)}
+                        if org.weight_interleave:
+                            e["weight interleave"] = org.weight_interleave
+                        if org.weight_code:
+                            e.update({"weight code": org.weight_code, "corrected weight words per epoch": per_epoch_sum(c.weight_corrected),
+                                      "detected weight words per epoch": per_epoch_sum(c.weight_detected),
+                                      "repaired weight words per epoch": per_epoch_sum(c.weight_repaired),
+                                      "unrepaired weight words per epoch": per_epoch_sum(c.weight_unrepaired)})
+                        if repair:
+                            e.update({"repair every": repair, "repaired words per epoch": per_epoch_sum(c.repaired),
+                                      "unrepaired words per epoch": per_epoch_sum(c.unrepaired)})
+                        if org.code:
+                            e.update({"code": org.code, "corrected words per epoch": per_epoch_sum(c.corrected),
+                                      "detected words per epoch": per_epoch_sum(c.detected)})
         stats = self._stats(util.dict_of_dicts_merge(*raw))
         for name, e in extra.items():
             stats["results"][name].update(e)

@@ -2199,13 +2199,36 @@ int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs
   return result;
 }
 
+// The fault records of the C ABI: 8 ints {image, target, layer, mem, ind, thresh, bit, word_size}; a physical fault's
+// (mem_org.h) have the module as a ninth.
+static void put_record(const Fault &f, int *w) {
+  const int v[8] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
+  std::memcpy(w, v, sizeof v);
+}
+static void put_record(const PhysFault &pf, int *w) {
+  put_record(pf.f, w);
+  w[8] = pf.module;
+}
+static Fault fault_record(const int *v) { return Fault{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}; }
+static PhysFault phys_fault_record(const int *v) { return PhysFault{fault_record(v), v[8]}; }
+
+// the tail of every pack_params_* entry point: the memories packed as load_parameters packs them, copied out where dst is given
+static size_t pack_params_out(const std::string &who, const RawParams &raw, void *dst, size_t cap) {
+  std::vector<uint8_t> blob;
+  pack_blob(rt().spec, raw, blob);
+  if (dst) {
+    if (cap < blob.size()) { fail(who + ": destination too small"); return 0; }
+    std::memcpy(dst, blob.data(), blob.size());
+  }
+  return blob.size();
+}
+
 int bnn_mi355x_last_campaign_faults(int *records, int cap_records) {
   Runtime &r = rt();
   const int n = (int)r.camp_faults.size();
   for (int i = 0; i < n && i < cap_records && records; i++) {
-    const Fault &f = r.camp_faults[(size_t)i];
-    const int v[9] = {r.camp_run[(size_t)i], f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
-    for (int j = 0; j < 9; j++) records[i * 9 + j] = v[j];
+    records[i * 9] = r.camp_run[(size_t)i];
+    put_record(r.camp_faults[(size_t)i], records + i * 9 + 1);
   }
   return n;
 }
@@ -2217,11 +2240,7 @@ long bnn_mi355x_enumerate_faults(int layer, int target, int word_size, long firs
   if (records && cap_records > 0 && first < total) {
     std::vector<Fault> v((size_t)std::min<long>(cap_records, total - first));
     enumerate_faults(net, layer, target, word_size, first, v.data(), (long)v.size());
-    for (size_t i = 0; i < v.size(); i++) {
-      const Fault &f = v[i];
-      const int w[8] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
-      std::memcpy(records + i * 8, w, sizeof w);
-    }
+    for (size_t i = 0; i < v.size(); i++) put_record(v[i], records + i * 8);
   }
   return total;
 }
@@ -2770,8 +2789,8 @@ long bnn_mi355x_fault_sweep(const char *path, int number_class, const int *recor
   const NetSpec &net = r.spec;
   std::vector<Fault> faults((size_t)n_faults);
   for (int i = 0; i < n_faults; i++) {
-    const int *v = records + (size_t)i * 8;
-    faults[(size_t)i] = Fault{0, v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    faults[(size_t)i] = fault_record(records + (size_t)i * 8);
+    faults[(size_t)i].image = 0;  // (whatever the record's first int holds)
     const std::string e = check_fault(net, faults[(size_t)i]);
     if (!e.empty()) return fail("fault_sweep: record " + std::to_string(i) + ": " + e);
   }
@@ -3477,10 +3496,36 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
 // The hardened one-shot campaign (bnn_mi355x_hardened_mem_noise_campaigns) is one epoch that is never scrubbed: epoch 0's
 // tag is kMemNoiseTag, and its upsets meet zeroed state.
 
-// longs: the counters per (run, epoch, layer) on the device -- 4, or 6 on the coded route (the ecc entry points, with
-// code 0 as well), or 8 on the repair route (with repair_every 0 as well)
+// longs: the counters per (run, epoch, layer) -- 4, or 6 on the coded route (the ecc entry points, with code 0 as well), 8
+// on the repair route (with repair_every 0 as well), 12 on the coded weight routes: which blocks ExposureCounters has
 // repair_every: the repair scrub of mem_org.h ("repair scrubs"); 0 never
 struct Exposure { int epoch_images, scrub_every, longs = 4, repair_every = 0; };
+
+// The counter region of the exposure path, on the device (from counts_off of d_noise on) and read back: up to four blocks
+// one behind the other, each [run][epoch][layer][width(b)] longs.  A family with `longs` counters has the blocks whose
+// columns lie below that; bnn_mi355x_last_*_counts hands out [run][epoch][layer][longs], block b from column(b) on.
+struct ExposureCounters {
+  enum Block {
+    COUNTS,   // [2: weights, thresholds][2: physical bits flipped, logical bits that differ]: the upset kernels' and the host's
+    STATUS,   // threshold words corrected, detected as uncorrectable (k_emem_noise_t)
+    REPAIRS,  // words a repair rewrote, words still unlike the loaded ones after it (k_repair_state and the host)
+    WSTATUS,  // weight code words corrected, detected, rewritten, still unlike (k_wmem_noise_w / k_iwmem_noise_w, k_wrepair_state / k_iwrepair_state)
+    BLOCKS
+  };
+  size_t R, E, S;
+  int longs;
+  static size_t width(int b) { return b == STATUS || b == REPAIRS ? 2 : 4; }
+  static size_t column(int b) { return b == COUNTS ? 0 : b == STATUS ? 4 : b == REPAIRS ? 6 : 8; }
+  bool has(int b) const { return (size_t)longs > column(b); }
+  size_t cells() const { return R * E * S; }
+  size_t offset(int b) const { return cells() * column(b); }    // of the block, in longs
+  size_t run_stride(int b) const { return E * S * width(b); }  // from a run's counters to the next run's, in longs
+  size_t bytes() const { return cells() * (size_t)longs * 8; }
+  // epoch t of run 0 in block b of the region at `region`; nullptr for a block the family has not
+  unsigned long long *epoch(uint8_t *region, int b, int t) const {
+    return has(b) ? reinterpret_cast<unsigned long long *>(region) + offset(b) + (size_t)t * S * width(b) : nullptr;
+  }
+};
 
 static bool exposure_scrubs(const Exposure &ex, int t) { return exposure_rewrites(t, ex.scrub_every); }
 static bool exposure_repairs(const Exposure &ex, int t) { return exposure_repairs(t, ex.scrub_every, ex.repair_every); }
@@ -3490,16 +3535,16 @@ static bool exposure_repairs(const Exposure &ex, int t) { return exposure_repair
 // is enqueued); the rows and tables an epoch changes become that epoch's patches.  A row is rebuilt where its words differ from the loaded
 // ones now or did so after the epoch before (it may have returned to them).  Then the threshold tables (mem_noise_upload),
 // and the layout of the threshold state.
-static int exposure_prepare(const char *who, const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth, int E,
-                            const Exposure &ex, const Hardening &hz, MemNoiseJob &job) {
+static int exposure_prepare(const char *who, const std::vector<unsigned long long> &seeds, const unsigned int *rw, const unsigned int *rth,
+                            const ExposureCounters &cl, const Exposure &ex, const Hardening &hz, MemNoiseJob &job) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  const int R = (int)seeds.size(), S = net.nlayers;
+  const int R = (int)seeds.size(), E = (int)cl.E, S = net.nlayers;
   PackedHeader h;
   std::memcpy(&h, r.blob.data(), sizeof(h));
   job.stride = (r.blob.size() + 255) & ~(size_t)255;
-  job.host_counts.assign((size_t)R * E * S * 4, 0);
-  job.host_repairs.assign(ex.longs >= 8 ? (size_t)R * E * S * 2 : 0, 0);
+  job.host_counts.assign(cl.cells() * cl.width(cl.COUNTS), 0);
+  job.host_repairs.assign(cl.has(cl.REPAIRS) ? cl.cells() * cl.width(cl.REPAIRS) : 0, 0);
   std::vector<uint8_t> staging;
   std::vector<std::vector<PatchSpan>> by_epoch((size_t)E);
   if (net.L[0].arith == AR_INT8 && (rw[0] || rth[0])) {
@@ -3585,19 +3630,16 @@ static int exposure_prepare(const char *who, const std::vector<unsigned long lon
   return 0;
 }
 
-// Enqueues on r.stream what comes before epoch 0: the seeds, the zeroed [run][epoch][layer][2][2] counters at counts_off of
-// d_noise, the runs' copies of the loaded blob, the job's upload and the zeroed threshold state.
-// longs 6: the [run][epoch][layer][2] decode-status counters of k_emem_noise_t lie behind the others; longs 8: behind
-// those, the [run][epoch][layer][2] counters of k_repair_state.
-static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, int E, int longs) {
+// Enqueues on r.stream what comes before epoch 0: the seeds, the zeroed counter region `cl` at counts_off of d_noise, the
+// runs' copies of the loaded blob, the job's upload and the zeroed threshold state.
+static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, const ExposureCounters &cl) {
   Runtime &r = rt();
-  const int R = (int)seeds.size(), S = r.spec.nlayers;
-  const size_t counts_bytes = (size_t)R * E * S * (size_t)longs * 8;
+  const int R = (int)seeds.size();
   if (grow(r.d_copies, r.copies_cap, (size_t)R * job.stride) || grow(r.d_camp, r.camp_cap, job.state_begin + job.state_bytes + 256) ||
-      grow(r.d_noise, r.noise_cap, counts_off + counts_bytes))
+      grow(r.d_noise, r.noise_cap, counts_off + cl.bytes()))
     return -1;
   HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
-  HIP_OK(hipMemsetAsync(r.d_noise + counts_off, 0, counts_bytes, r.stream));
+  HIP_OK(hipMemsetAsync(r.d_noise + counts_off, 0, cl.bytes(), r.stream));
   if (replicate_blob(R, job.stride)) return -1;
   if (!job.upload.empty()) HIP_OK(hipMemcpyAsync(r.d_camp, job.upload.data(), job.upload.size(), hipMemcpyHostToDevice, r.stream));
   if (job.state_bytes) HIP_OK(hipMemsetAsync(r.d_camp + job.state_begin, 0, job.state_bytes, r.stream));
@@ -3607,21 +3649,24 @@ static int exposure_begin(const std::vector<unsigned long long> &seeds, const Me
 // Enqueues epoch t: the scrub where one is due (the copies restored by the same doubling copy, the state cleared) or
 // else the repair where one is due (ONE launch of k_repair_state over the state of every layer with redundancy), the
 // host's layer-0 patches of the epoch, then the upset kernels layer by layer, weights before thresholds.
-static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned int *rth, const MemNoiseJob &job, size_t counts_off, int E,
-                          const Exposure &ex, const Hardening &hz) {
+static int exposure_epoch(int t, const unsigned int *rw, const unsigned int *rth, const MemNoiseJob &job, size_t counts_off,
+                          const ExposureCounters &cl, const Exposure &ex, const Hardening &hz) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
-  const int S = net.nlayers;
+  const int R = (int)cl.R, S = net.nlayers;
   PackedHeader h;
   std::memcpy(&h, r.blob.data(), sizeof(h));
   const size_t stride = job.stride;
   const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
-  unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)t * S * 4;
-  const size_t run_stride = (size_t)E * S * 4;
+  // epoch t of every block (a kernel whose block the family has not is never launched)
+  uint8_t *const region = r.d_noise + counts_off;
+  unsigned long long *const d_counts = cl.epoch(region, cl.COUNTS, t), *const d_ecc = cl.epoch(region, cl.STATUS, t),
+                           *const d_rep = cl.epoch(region, cl.REPAIRS, t), *const d_wst = cl.epoch(region, cl.WSTATUS, t);
+  const size_t run_stride = cl.run_stride(cl.COUNTS);
   if (exposure_scrubs(ex, t)) {
     if (replicate_blob(R, stride)) return -1;
     if (job.state_bytes) HIP_OK(hipMemsetAsync(r.d_camp + job.state_begin, 0, job.state_bytes, r.stream));
-  } else if (exposure_repairs(ex, t) && ex.longs >= 8 && job.state_bytes) {
+  } else if (exposure_repairs(ex, t) && cl.has(cl.REPAIRS) && job.state_bytes) {
     RepairTable tab{};
     int entries = 0;
     for (int l = 0; l < S; l++) {
@@ -3632,21 +3677,18 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
       const uint32_t kind = eo.check_bits ? RK_CODED : eo.org.t_modules == 3 ? RK_TMR : RK_SKIP;
       if (kind != RK_SKIP) tab.e[entries++] = RepairEntry{(unsigned long long)job.state_off[l], h.layer[l].rows * (uint32_t)L.nthr, kind, (uint32_t)l, 0};
     }
-    // the repair counters behind the [run][epoch][layer][4] and the [run][epoch][layer][2] decode-status counters
-    unsigned long long *const d_rep = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * run_stride / 4 * 6 + (size_t)t * S * 2;
-    const hipError_t re = repair_state(r.d_camp, tab, entries, R, d_rep, (size_t)E * S * 2, r.stream);
+    const hipError_t re = repair_state(r.d_camp, tab, entries, R, d_rep, cl.run_stride(cl.REPAIRS), r.stream);
     if (re != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(re));
-    // the coded weight memories: one more launch over their state pairs, its counters behind all of those above
+    // the coded weight memories: one more launch over their state pairs
     RepairTable wtab{};
     int wentries = 0;
     for (int l = 0; l < S; l++)
       if (job.wstate_words[l])
         wtab.e[wentries++] = RepairEntry{(unsigned long long)job.wstate_off[l], job.wstate_words[l], RK_CODED, (uint32_t)l, job.wdepth[l]};
     if (wentries) {
-      unsigned long long *const d_wst = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * E * S * 8 + (size_t)t * S * 4;
       // (weight_interleave 1: every coded layer's pairs are physical ones, so the interleaved repair goes INSTEAD)
-      const hipError_t we = hz.weight_interleave ? iwrepair_state(r.d_camp, wtab, wentries, R, d_wst, (size_t)E * S * 4, r.stream)
-                                                 : wrepair_state(r.d_camp, wtab, wentries, R, d_wst, (size_t)E * S * 4, r.stream);
+      const hipError_t we = hz.weight_interleave ? iwrepair_state(r.d_camp, wtab, wentries, R, d_wst, cl.run_stride(cl.WSTATUS), r.stream)
+                                                 : wrepair_state(r.d_camp, wtab, wentries, R, d_wst, cl.run_stride(cl.WSTATUS), r.stream);
       if (we != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(we));
     }
   }
@@ -3660,27 +3702,25 @@ static int exposure_epoch(int t, int R, const unsigned int *rw, const unsigned i
     ecc_layout(net, hz.scheme, hz.code, l, eo);  // (checked by mem_noise_check; weights of a layer >= 1 have one module)
     const MemOrg &org = eo.org;
     if (job.wstate_words[l]) {
-      // a coded weight memory (weight_code 1 comes by the 12-long route alone): its status counters behind the eight
-      unsigned long long *const d_wst = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * E * S * 8 + (size_t)t * S * 4;
+      // a coded weight memory (weight_code 1 comes by the 12-long route alone, which has the WSTATUS block)
       if (job.wdepth[l])
         e = iwmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, (int)job.wdepth[l], rw[l], t,
                           static_cast<const uint8_t *>(r.d_blob), reinterpret_cast<unsigned long long *>(r.d_camp + job.wstate_off[l]), d_counts,
-                          run_stride, d_wst, (size_t)E * S * 4, r.stream);
+                          run_stride, d_wst, cl.run_stride(cl.WSTATUS), r.stream);
       else
         e = wmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
                          static_cast<const uint8_t *>(r.d_blob), reinterpret_cast<unsigned long long *>(r.d_camp + job.wstate_off[l]), d_counts,
-                         run_stride, d_wst, (size_t)E * S * 4, r.stream);
+                         run_stride, d_wst, cl.run_stride(cl.WSTATUS), r.stream);
     } else
       e = xmem_noise_w(r.d_copies, stride, R, d_seeds, ml, L.arith == AR_TT, mem_element_bits(L, 0), hz.burst, rw[l], t,
                        static_cast<const uint8_t *>(r.d_blob), d_counts, run_stride, r.stream);
     // a flip may have removed the last -2 of a row (the loaded parameters may hold -2 rows, and so may an earlier epoch's state)
     if (e == hipSuccess && L.arith == AR_TT && rw[l] && (r.two_rows > 0 || t > 0)) e = mem_noise_flags(r.d_copies, stride, R, ml, r.stream);
     if (e == hipSuccess && rth[l] && eo.check_bits) {
-      // a coded layer (code 1 comes by the 6-long route alone): the decode-status counters behind the [run][epoch][layer][4]
-      unsigned long long *const d_ecc = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off) + (size_t)R * run_stride + (size_t)t * S * 2;
+      // a coded layer (code 1 comes by the routes of 6 longs and more alone, which have the STATUS block)
       e = emem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
                        org.t_interleave, hz.burst, rth[l], t, reinterpret_cast<unsigned long long *>(r.d_camp + job.state_off[l]), d_counts,
-                       run_stride, d_ecc, (size_t)E * S * 2, r.stream);
+                       run_stride, d_ecc, cl.run_stride(cl.STATUS), r.stream);
     } else if (e == hipSuccess && rth[l])
       e = xmem_noise_t(r.d_copies, stride, R, d_seeds, ml, L.nthr, L.arith, L.signed_bb, reinterpret_cast<const uint16_t *>(r.d_camp + job.tab_off[l]),
                        org.t_modules, org.t_interleave, hz.burst, rth[l], t, reinterpret_cast<unsigned long long *>(r.d_camp + job.state_off[l]),
@@ -3706,17 +3746,13 @@ struct MemNoiseEntry {
 // (exposure_epoch; the plain route: all of it in front of the one epoch's pairs, mem_noise_enqueue); an epoch's (run, image)
 // pairs go in run-major order, in groups of at most one activation workspace, through the multi-run stages with the copy
 // stride: act_noise_campaigns' grouping with fault_campaigns' copies.  kMaxRuns copies are what fault_campaigns holds as
-// well, so a call's runs always fit.  The counters have one [layer][2][2] block per (run, epoch), with ex.longs 6 / 8 two
-// decode-status / and two repair counters per (run, epoch, layer) behind them; the plain route's are [run][layer][2].
+// well, so a call's runs always fit.  The counters are ExposureCounters' blocks; the plain route's are [run][layer][2].
 static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &hz, const Exposure &ex, const char *path, int number_class,
                                      int num_runs, unsigned long long seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32,
                                      int n_rates, int *image_number, float *usecPerImage) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const char *const who = en.who;
-  const bool twelve = ex.longs == 12;      // the coded weight route: four weight code word counters behind the eight
-  const bool eight = ex.longs >= 8;        // the repair route: two repair counters behind the six
-  const bool six = eight || ex.longs == 6;  // the coded route: two decode-status counters behind the four
   std::vector<long> &last_counts = r.*en.counts;
   std::vector<unsigned long long> &last_seeds = r.*en.seeds;
   last_counts.clear();
@@ -3779,15 +3815,13 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
   }
   int *result = new (std::nothrow) int[total + 1];
   if (!result) { fail("out of memory"); return nullptr; }
-  std::vector<unsigned long long> counts((size_t)R * E * S * (en.plain ? 2 : 4), 0);
-  std::vector<unsigned long long> status(six ? (size_t)R * E * S * 2 : 0, 0);  // (the coded route: [run][epoch][layer][2])
-  std::vector<unsigned long long> repairs(eight ? (size_t)R * E * S * 2 : 0, 0);  // (the repair route: likewise)
-  std::vector<unsigned long long> wstatus(twelve ? (size_t)R * E * S * 4 : 0, 0);  // (the coded weight route: [run][epoch][layer][4])
+  const ExposureCounters cl{(size_t)R, (size_t)E, (size_t)S, ex.longs};
+  std::vector<unsigned long long> counts(en.plain ? (size_t)R * S * 2 : cl.bytes() / 8, 0);  // the counters as the device holds them
   MemNoiseJob job;
   double device_us = 0.0;
   auto run = [&]() -> int {
     if (n == 0) return 0;
-    if (any && (en.plain ? mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job) : exposure_prepare(who, seeds, rate_w_q32, rate_t_q32, E, ex, hz, job)))
+    if (any && (en.plain ? mem_noise_prepare(seeds, rate_w_q32, rate_t_q32, job) : exposure_prepare(who, seeds, rate_w_q32, rate_t_q32, cl, ex, hz, job)))
       return -1;
     size_t cap = std::min<size_t>(kMaxChunk, total);  // pairs per group: the activation workspace
     if (const char *e = std::getenv("BNN_MI355X_NOISE_GROUP")) {  // tests: many small groups
@@ -3834,7 +3868,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     }
     // -- all of it on one stream, one wait at the end
     HIP_OK(hipEventRecord(r.time_events[0], r.stream));
-    if (any && (en.plain ? mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off) : exposure_begin(seeds, job, counts_off, E, ex.longs)))
+    if (any && (en.plain ? mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off) : exposure_begin(seeds, job, counts_off, cl)))
       return -1;
     // (all rates 0: no copy is made, every run reads the loaded blob)
     const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
@@ -3843,7 +3877,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     int entered = -1;  // the last epoch whose scrub and upsets are in the stream
     for (const Group &g : groups) {
       for (; !en.plain && any && entered < g.epoch; entered++)
-        if (exposure_epoch(entered + 1, R, rate_w_q32, rate_t_q32, job, counts_off, E, ex, hz)) return -1;
+        if (exposure_epoch(entered + 1, rate_w_q32, rate_t_q32, job, counts_off, cl, ex, hz)) return -1;
       MultiLaunch a{};
       a.images = r.d_all;
       a.segs = d_segs + g.seg0;
@@ -3863,19 +3897,13 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     }
     HIP_OK(hipEventRecord(r.time_events[1], r.stream));
     if (any) HIP_OK(hipMemcpyAsync(counts.data(), r.d_noise + counts_off, counts.size() * 8, hipMemcpyDeviceToHost, r.stream));
-    if (any && six) HIP_OK(hipMemcpyAsync(status.data(), r.d_noise + counts_off + counts.size() * 8, status.size() * 8, hipMemcpyDeviceToHost, r.stream));
-    if (any && eight)
-      HIP_OK(hipMemcpyAsync(repairs.data(), r.d_noise + counts_off + (counts.size() + status.size()) * 8, repairs.size() * 8, hipMemcpyDeviceToHost,
-                            r.stream));
-    if (any && twelve)
-      HIP_OK(hipMemcpyAsync(wstatus.data(), r.d_noise + counts_off + (counts.size() + status.size() + repairs.size()) * 8, wstatus.size() * 8,
-                            hipMemcpyDeviceToHost, r.stream));
     if (cnv) HIP_OK(hipMemcpyAsync(result, r.d_camp_res, total * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
     else HIP_OK(hipMemcpyAsync(w.data(), r.d_camp_res, total * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
     HIP_OK(hipStreamSynchronize(r.stream));
     for (size_t i = 0; !cnv && i < total; i++) result[i] = lfc_class_batched(w[i], number_class);
+    // (the host's layer-0 part, in the shape of the block it goes to)
     for (size_t i = 0; i < job.host_counts.size(); i++) counts[i] += job.host_counts[i];
-    for (size_t i = 0; i < job.host_repairs.size(); i++) repairs[i] += job.host_repairs[i];
+    for (size_t i = 0; i < job.host_repairs.size(); i++) counts[cl.offset(cl.REPAIRS) + i] += job.host_repairs[i];
     float ms = 0.f;
     HIP_OK(hipEventElapsedTime(&ms, r.time_events[0], r.time_events[1]));
     drain.ok();
@@ -3886,17 +3914,17 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     delete[] result;
     return nullptr;
   }
-  if (six) {  // [run][epoch][layer]: the four counters, then the two decode-status counters, then (eight) the two repair counters
-    const size_t k = twelve ? 12 : eight ? 8 : 6;
-    last_counts.resize(counts.size() / 4 * k);
-    for (size_t b = 0; b < counts.size() / 4; b++) {
-      for (int j = 0; j < 4; j++) last_counts[b * k + j] = (long)counts[b * 4 + j];
-      for (int j = 0; j < 2; j++) last_counts[b * k + 4 + j] = (long)status[b * 2 + j];
-      for (int j = 0; j < 2 && eight; j++) last_counts[b * k + 6 + j] = (long)repairs[b * 2 + j];
-      for (int j = 0; j < 4 && twelve; j++) last_counts[b * k + 8 + j] = (long)wstatus[b * 4 + j];
-    }
-  } else {
+  // the plain route's [run][layer][2] as they are; else the blocks side by side, [run][epoch][layer][longs]
+  if (en.plain) {
     last_counts.assign(counts.begin(), counts.end());
+  } else {
+    last_counts.resize(counts.size());
+    long *out = last_counts.data();  // (one pass in the order it is written: a cell's blocks follow each other by column)
+    for (size_t c = 0; c < cl.cells(); c++)
+      for (int b = 0; b < cl.BLOCKS && cl.has(b); b++) {
+        const unsigned long long *const from = counts.data() + cl.offset(b) + c * cl.width(b);
+        for (size_t j = 0; j < cl.width(b); j++) *out++ = (long)from[j];
+      }
   }
   last_seeds = std::move(seeds);
   if (image_number) *image_number = n;
@@ -3926,11 +3954,7 @@ long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int targe
   if (records && cap_records > 0 && first < total) {
     std::vector<Fault> v((size_t)std::min<long>(cap_records, total - first));
     mem_noise_mask(net, run_seed, layer, target, rate_q32, first, v.data(), (long)v.size());
-    for (size_t i = 0; i < v.size(); i++) {
-      const Fault &f = v[i];
-      const int w[8] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
-      std::memcpy(records + i * 8, w, sizeof w);
-    }
+    for (size_t i = 0; i < v.size(); i++) put_record(v[i], records + i * 8);
   }
   return total;
 }
@@ -3985,51 +4009,67 @@ int bnn_mi355x_hardened_site(int scheme, int layer, int target, int ind, int bit
   return 0;
 }
 
-long bnn_mi355x_hardened_mem_noise_mask(int scheme, int burst, unsigned long long run_seed, int layer, int target, int module,
-                                        unsigned int rate_q32, long first, int *records, int cap_records) {
+// The mask entry points of the physical organisations: the layout checked, the events of one (run seed, epoch, layer, target,
+// module) counted, those from `first` on drawn and written as 9-int records.  epochs false: an entry point without epochs
+// passes epoch 0, and its refusal does not speak of one.
+static long phys_noise_mask(const std::string &who, const Hardening &hz, unsigned long long run_seed, bool epochs, int epoch, int layer, int target,
+                            int module, unsigned int rate_q32, long first, int *records, int cap_records) {
   const NetSpec &net = rt().spec;
-  MemOrg org;
-  const std::string e = hardening_layout(net, scheme, layer, org);
-  if (!e.empty()) return fail("hardened_mem_noise_mask: " + e);
-  const long total = first < 0 ? -1 : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0);
+  EccOrg eo;
+  const std::string e = ecc_layout(net, hz.scheme, hz.code, layer, eo);
+  if (!e.empty()) return fail(who + ": " + e);
+  const long total = first < 0 ? -1
+                               : hardened_mem_noise_mask(net, hz.scheme, hz.burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0, epoch, hz.code,
+                                                         hz.weight_code);
   if (total < 0)
-    return fail("hardened_mem_noise_mask: bad burst (1 ... " + std::to_string(kMaxBurst) + "), target (0 weights, 1 thresholds), module (of those "
-                "the memory has) or first");
+    return fail(who + ": bad burst (1 ... " + std::to_string(kMaxBurst) + "), " +
+                (epochs ? "epoch (0 ... " + std::to_string(kMaxEpochs - 1) + "), " : std::string()) +
+                "target (0 weights, 1 thresholds), module (of those the memory has) or first");
   if (records && cap_records > 0 && first < total) {
     std::vector<PhysFault> v((size_t)std::min<long>(cap_records, total - first));
-    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size());
-    for (size_t i = 0; i < v.size(); i++) {
-      const Fault &f = v[i].f;
-      const int w[9] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size, v[i].module};
-      std::memcpy(records + i * 9, w, sizeof w);
-    }
+    hardened_mem_noise_mask(net, hz.scheme, hz.burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size(), epoch, hz.code,
+                            hz.weight_code);
+    for (size_t i = 0; i < v.size(); i++) put_record(v[i], records + i * 9);
   }
   return total;
 }
 
-size_t bnn_mi355x_pack_params_hardened(const char *path, int scheme, const int *records, int n_faults, void *dst, size_t cap) {
+long bnn_mi355x_hardened_mem_noise_mask(int scheme, int burst, unsigned long long run_seed, int layer, int target, int module,
+                                        unsigned int rate_q32, long first, int *records, int cap_records) {
+  return phys_noise_mask("hardened_mem_noise_mask", Hardening{scheme, burst}, run_seed, false, 0, layer, target, module, rate_q32, first, records,
+                         cap_records);
+}
+
+// the head of the pack_params_* entry points of the physical organisations: the organisation checked, the parameter files read
+static bool pack_params_read(const std::string &who, const char *path, int scheme, int code, RawParams &raw) {
+  EccOrg eo;
+  const std::string le = ecc_layout(rt().spec, scheme, code, 0, eo);
+  if (!le.empty()) { fail(who + ": " + le); return false; }
+  const std::string e = read_raw_params(rt().spec, path ? path : "", raw);
+  if (!e.empty()) { fail(e); return false; }
+  return true;
+}
+
+// (bnn_mi355x_pack_params_hardened: code 0, and bnn_mi355x_pack_params_ecc) the 9-int fault records applied to the physical
+// memories in order, then what the datapath is delivered
+static size_t pack_params_phys(const std::string &who, const char *path, int scheme, int code, const int *records, int n_faults, void *dst,
+                               size_t cap) {
   const NetSpec &net = rt().spec;
-  MemOrg org;
-  const std::string le = hardening_layout(net, scheme, 0, org);
-  if (!le.empty()) { fail("pack_params_hardened: " + le); return 0; }
   RawParams raw;
-  const std::string e = read_raw_params(net, path ? path : "", raw);
-  if (!e.empty()) { fail(e); return 0; }
+  if (!pack_params_read(who, path, scheme, code, raw)) return 0;
   PhysParams phys;
-  phys_load(net, scheme, raw, 0, net.nlayers, phys);
-  for (int i = 0; i < n_faults; i++) {
-    const int *v = records + i * 9;
-    const PhysFault pf{Fault{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}, v[8]};
-    if (phys_apply(net, scheme, phys, pf) < 0) { fail("pack_params_hardened: fault record out of range (or a module the memory does not have)"); return 0; }
-  }
-  phys_logical(net, scheme, phys, raw);
-  std::vector<uint8_t> blob;
-  pack_blob(net, raw, blob);
-  if (dst) {
-    if (cap < blob.size()) { fail("pack_params_hardened: destination too small"); return 0; }
-    std::memcpy(dst, blob.data(), blob.size());
-  }
-  return blob.size();
+  phys_load(net, scheme, raw, 0, net.nlayers, phys, code);
+  for (int i = 0; i < n_faults; i++)
+    if (phys_apply(net, scheme, phys, phys_fault_record(records + i * 9), code) < 0) {
+      fail(who + ": fault record out of range (or a module the memory does not have)");
+      return 0;
+    }
+  phys_logical(net, scheme, phys, raw, code);
+  return pack_params_out(who, raw, dst, cap);
+}
+
+size_t bnn_mi355x_pack_params_hardened(const char *path, int scheme, const int *records, int n_faults, void *dst, size_t cap) {
+  return pack_params_phys("pack_params_hardened", path, scheme, EC_NONE, records, n_faults, dst, cap);
 }
 
 int *bnn_mi355x_hardened_mem_noise_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs, unsigned long long seed,
@@ -4040,14 +4080,15 @@ int *bnn_mi355x_hardened_mem_noise_campaigns(const char *path, int number_class,
                                   n_rates, image_number, usecPerImage);
 }
 
-static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
-                                   const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap,
-                                   int repair_every = -1, bool twelve = false);
+// ex: scrub_every and repair_every, and the longs of the caller's family (epoch_images is not read: one copy, no images)
+static size_t exposure_params_impl(const char *who, const Hardening &hz, const Exposure &ex, unsigned long long run_seed,
+                                   const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch, void *dst, size_t cap);
 
 // (epoch 0 of a state that is never scrubbed)
 size_t bnn_mi355x_hardened_mem_noise_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
                                             const unsigned int *rate_t_q32, int n_rates, void *dst, size_t cap) {
-  return exposure_params_impl("hardened_mem_noise_params", Hardening{scheme, burst}, run_seed, rate_w_q32, rate_t_q32, n_rates, 0, 0, dst, cap);
+  return exposure_params_impl("hardened_mem_noise_params", Hardening{scheme, burst}, Exposure{1, 0}, run_seed, rate_w_q32, rate_t_q32, n_rates, 0, dst,
+                              cap);
 }
 
 int bnn_mi355x_last_hardened_mem_noise_counts(long *counts, int cap) { return copy_out(rt().hmem_noise_counts, counts, cap); }
@@ -4058,24 +4099,8 @@ int bnn_mi355x_last_hardened_mem_noise_seeds(unsigned long long *seeds, int cap)
 
 long bnn_mi355x_exposure_mask(int scheme, int burst, unsigned long long run_seed, int epoch, int layer, int target, int module,
                               unsigned int rate_q32, long first, int *records, int cap_records) {
-  const NetSpec &net = rt().spec;
-  MemOrg org;
-  const std::string e = hardening_layout(net, scheme, layer, org);
-  if (!e.empty()) return fail("exposure_mask: " + e);
-  const long total = first < 0 ? -1 : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0, epoch);
-  if (total < 0)
-    return fail("exposure_mask: bad burst (1 ... " + std::to_string(kMaxBurst) + "), epoch (0 ... " + std::to_string(kMaxEpochs - 1) +
-                "), target (0 weights, 1 thresholds), module (of those the memory has) or first");
-  if (records && cap_records > 0 && first < total) {
-    std::vector<PhysFault> v((size_t)std::min<long>(cap_records, total - first));
-    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size(), epoch);
-    for (size_t i = 0; i < v.size(); i++) {
-      const Fault &f = v[i].f;
-      const int w[9] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size, v[i].module};
-      std::memcpy(records + i * 9, w, sizeof w);
-    }
-  }
-  return total;
+  return phys_noise_mask("exposure_mask", Hardening{scheme, burst}, run_seed, true, epoch, layer, target, module, rate_q32, first, records,
+                         cap_records);
 }
 
 int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int scheme, int burst, int num_runs, unsigned long long seed,
@@ -4087,14 +4112,10 @@ int *bnn_mi355x_exposure_campaigns(const char *path, int number_class, int schem
 }
 
 // One copy stepped through epochs 0 ... epoch by the campaign's own steps (exposure_begin, exposure_epoch), then read back.
-static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigned long long run_seed, const unsigned int *rate_w_q32,
-                                   const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap,
-                                   int repair_every, bool twelve) {
+static size_t exposure_params_impl(const char *who, const Hardening &hz, const Exposure &ex, unsigned long long run_seed,
+                                   const unsigned int *rate_w_q32, const unsigned int *rate_t_q32, int n_rates, int epoch, void *dst, size_t cap) {
   Runtime &r = rt();
-  // (room for the decode-status counters of a coded layer, and on the repair route -- repair_every >= 0 -- for the repair
-  // counters; nothing reads them here)
-  const Exposure ex{1, scrub_every, twelve ? 12 : repair_every < 0 ? 6 : 8, std::max(repair_every, 0)};
-  if (epoch < 0 || epoch >= kMaxEpochs || scrub_every < 0) {
+  if (epoch < 0 || epoch >= kMaxEpochs || ex.scrub_every < 0) {
     fail(std::string(who) + ": epoch must be 0 ... " + std::to_string(kMaxEpochs - 1) + " and scrub_every must not be negative (0: never scrub)");
     return 0;
   }
@@ -4103,14 +4124,15 @@ static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigne
   if (cap < r.blob.size()) { fail(std::string(who) + ": destination too small"); return 0; }
   const std::vector<unsigned long long> seeds(1, run_seed);
   const int E = epoch + 1;
+  const ExposureCounters cl{1, (size_t)E, (size_t)r.spec.nlayers, ex.longs};  // (the kernels count; nothing reads the counters here)
   MemNoiseJob job;
   auto run = [&]() -> int {
-    if (exposure_prepare(who, seeds, rate_w_q32, rate_t_q32, E, ex, hz, job)) return -1;
+    if (exposure_prepare(who, seeds, rate_w_q32, rate_t_q32, cl, ex, hz, job)) return -1;
     DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
     if (settle_handover(r.stream)) return -1;
-    if (exposure_begin(seeds, job, 256, E, ex.longs)) return -1;
+    if (exposure_begin(seeds, job, 256, cl)) return -1;
     for (int t = 0; t < E; t++)
-      if (exposure_epoch(t, 1, rate_w_q32, rate_t_q32, job, 256, E, ex, hz)) return -1;
+      if (exposure_epoch(t, rate_w_q32, rate_t_q32, job, 256, cl, ex, hz)) return -1;
     HIP_OK(hipMemcpyAsync(dst, r.d_copies, r.blob.size(), hipMemcpyDeviceToHost, r.stream));
     HIP_OK(hipStreamSynchronize(r.stream));
     drain.ok();
@@ -4121,7 +4143,8 @@ static size_t exposure_params_impl(const char *who, const Hardening &hz, unsigne
 
 size_t bnn_mi355x_exposure_params(int scheme, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
                                   const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
-  return exposure_params_impl("exposure_params", Hardening{scheme, burst}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch, scrub_every, dst, cap);
+  return exposure_params_impl("exposure_params", Hardening{scheme, burst}, Exposure{1, scrub_every}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch,
+                              dst, cap);
 }
 
 int bnn_mi355x_last_exposure_counts(long *counts, int cap) { return copy_out(rt().xmem_counts, counts, cap); }
@@ -4162,60 +4185,14 @@ int bnn_mi355x_ecc_check_site(int scheme, int code, int layer, int ind, int bit,
   return 0;
 }
 
-// (bnn_mi355x_ecc_exposure_mask, and with a weight code bnn_mi355x_wecc_exposure_mask)
-static long coded_exposure_mask(const std::string &who, int scheme, int code, int weight_code, int burst, unsigned long long run_seed, int epoch,
-                                int layer, int target, int module, unsigned int rate_q32, long first, int *records, int cap_records) {
-  const NetSpec &net = rt().spec;
-  EccOrg eo;
-  const std::string e = ecc_layout(net, scheme, code, layer, eo);
-  if (!e.empty()) return fail(who + ": " + e);
-  const long total = first < 0 ? -1
-                               : hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, 0, nullptr, 0, epoch, code,
-                                                         weight_code);
-  if (total < 0)
-    return fail(who + ": bad burst (1 ... " + std::to_string(kMaxBurst) + "), epoch (0 ... " + std::to_string(kMaxEpochs - 1) +
-                "), target (0 weights, 1 thresholds), module (of those the memory has) or first");
-  if (records && cap_records > 0 && first < total) {
-    std::vector<PhysFault> v((size_t)std::min<long>(cap_records, total - first));
-    hardened_mem_noise_mask(net, scheme, burst, run_seed, layer, target, module, rate_q32, first, v.data(), (long)v.size(), epoch, code, weight_code);
-    for (size_t i = 0; i < v.size(); i++) {
-      const Fault &f = v[i].f;
-      const int w[9] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size, v[i].module};
-      std::memcpy(records + i * 9, w, sizeof w);
-    }
-  }
-  return total;
-}
-
 long bnn_mi355x_ecc_exposure_mask(int scheme, int code, int burst, unsigned long long run_seed, int epoch, int layer, int target, int module,
                                   unsigned int rate_q32, long first, int *records, int cap_records) {
-  return coded_exposure_mask("ecc_exposure_mask", scheme, code, WC_NONE, burst, run_seed, epoch, layer, target, module, rate_q32, first, records,
-                             cap_records);
+  return phys_noise_mask("ecc_exposure_mask", Hardening{scheme, burst, code}, run_seed, true, epoch, layer, target, module, rate_q32, first, records,
+                         cap_records);
 }
 
 size_t bnn_mi355x_pack_params_ecc(const char *path, int scheme, int code, const int *records, int n_faults, void *dst, size_t cap) {
-  const NetSpec &net = rt().spec;
-  EccOrg eo;
-  const std::string le = ecc_layout(net, scheme, code, 0, eo);
-  if (!le.empty()) { fail("pack_params_ecc: " + le); return 0; }
-  RawParams raw;
-  const std::string e = read_raw_params(net, path ? path : "", raw);
-  if (!e.empty()) { fail(e); return 0; }
-  PhysParams phys;
-  phys_load(net, scheme, raw, 0, net.nlayers, phys, code);
-  for (int i = 0; i < n_faults; i++) {
-    const int *v = records + i * 9;
-    const PhysFault pf{Fault{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]}, v[8]};
-    if (phys_apply(net, scheme, phys, pf, code) < 0) { fail("pack_params_ecc: fault record out of range (or a module the memory does not have)"); return 0; }
-  }
-  phys_logical(net, scheme, phys, raw, code);
-  std::vector<uint8_t> blob;
-  pack_blob(net, raw, blob);
-  if (dst) {
-    if (cap < blob.size()) { fail("pack_params_ecc: destination too small"); return 0; }
-    std::memcpy(dst, blob.data(), blob.size());
-  }
-  return blob.size();
+  return pack_params_phys("pack_params_ecc", path, scheme, code, records, n_faults, dst, cap);
 }
 
 int *bnn_mi355x_ecc_exposure_campaigns(const char *path, int number_class, int scheme, int code, int burst, int num_runs, unsigned long long seed,
@@ -4228,8 +4205,8 @@ int *bnn_mi355x_ecc_exposure_campaigns(const char *path, int number_class, int s
 
 size_t bnn_mi355x_ecc_exposure_params(int scheme, int code, int burst, unsigned long long run_seed, const unsigned int *rate_w_q32,
                                       const unsigned int *rate_t_q32, int n_rates, int epoch, int scrub_every, void *dst, size_t cap) {
-  return exposure_params_impl("ecc_exposure_params", Hardening{scheme, burst, code}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch, scrub_every,
-                              dst, cap);
+  return exposure_params_impl("ecc_exposure_params", Hardening{scheme, burst, code}, Exposure{1, scrub_every, 6}, run_seed, rate_w_q32, rate_t_q32,
+                              n_rates, epoch, dst, cap);
 }
 
 int bnn_mi355x_last_ecc_exposure_counts(long *counts, int cap) { return copy_out(rt().emem_counts, counts, cap); }
@@ -4250,25 +4227,15 @@ int bnn_mi355x_ecc_repair(unsigned int data, unsigned int check, unsigned int *o
 static size_t pack_params_replayed(const std::string &who, const char *path, int scheme, int code, int weight_code, const int *records, int n_faults,
                                    void *dst, size_t cap, int weight_interleave = 0) {
   const NetSpec &net = rt().spec;
-  EccOrg eo;
-  const std::string le = ecc_layout(net, scheme, code, 0, eo);
-  if (!le.empty()) { fail(who + ": " + le); return 0; }
   RawParams raw;
-  const std::string e = read_raw_params(net, path ? path : "", raw);
-  if (!e.empty()) { fail(e); return 0; }
+  if (!pack_params_read(who, path, scheme, code, raw)) return 0;
   PhysParams loaded;
   phys_load(net, scheme, raw, 0, net.nlayers, loaded, code, weight_code, weight_interleave);
   PhysParams phys = loaded;
   const std::string re = phys_replay(net, scheme, code, loaded, phys, records, n_faults, weight_code, weight_interleave);
   if (!re.empty()) { fail(who + ": " + re); return 0; }
   phys_logical(net, scheme, phys, raw, code, nullptr, weight_code, nullptr, weight_interleave);
-  std::vector<uint8_t> blob;
-  pack_blob(net, raw, blob);
-  if (dst) {
-    if (cap < blob.size()) { fail(who + ": destination too small"); return 0; }
-    std::memcpy(dst, blob.data(), blob.size());
-  }
-  return blob.size();
+  return pack_params_out(who, raw, dst, cap);
 }
 
 size_t bnn_mi355x_pack_params_repair(const char *path, int scheme, int code, const int *records, int n_faults, void *dst, size_t cap) {
@@ -4290,8 +4257,8 @@ size_t bnn_mi355x_repair_exposure_params(int scheme, int code, int burst, unsign
     fail("repair_exposure_params: repair_every must not be negative (0: never repair)");
     return 0;
   }
-  return exposure_params_impl("repair_exposure_params", Hardening{scheme, burst, code}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch,
-                              scrub_every, dst, cap, repair_every);
+  return exposure_params_impl("repair_exposure_params", Hardening{scheme, burst, code}, Exposure{1, scrub_every, 8, repair_every}, run_seed, rate_w_q32,
+                              rate_t_q32, n_rates, epoch, dst, cap);
 }
 
 int bnn_mi355x_last_repair_exposure_counts(long *counts, int cap) { return copy_out(rt().rmem_counts, counts, cap); }
@@ -4332,8 +4299,8 @@ long bnn_mi355x_wecc_exposure_mask(int scheme, int code, int weight_code, int bu
                                    int module, unsigned int rate_q32, long first, int *records, int cap_records) {
   const std::string e = wecc_check(weight_code);
   if (!e.empty()) return fail("wecc_exposure_mask: " + e);
-  return coded_exposure_mask("wecc_exposure_mask", scheme, code, weight_code, burst, run_seed, epoch, layer, target, module, rate_q32, first, records,
-                             cap_records);
+  return phys_noise_mask("wecc_exposure_mask", Hardening{scheme, burst, code, weight_code}, run_seed, true, epoch, layer, target, module, rate_q32,
+                         first, records, cap_records);
 }
 
 size_t bnn_mi355x_pack_params_wecc(const char *path, int scheme, int code, int weight_code, const int *records, int n_faults, void *dst, size_t cap) {
@@ -4364,8 +4331,8 @@ size_t bnn_mi355x_wecc_exposure_params(int scheme, int code, int weight_code, in
     fail("wecc_exposure_params: repair_every must not be negative (0: never repair)");
     return 0;
   }
-  return exposure_params_impl("wecc_exposure_params", Hardening{scheme, burst, code, weight_code}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch,
-                              scrub_every, dst, cap, repair_every, true);
+  return exposure_params_impl("wecc_exposure_params", Hardening{scheme, burst, code, weight_code}, Exposure{1, scrub_every, 12, repair_every}, run_seed,
+                              rate_w_q32, rate_t_q32, n_rates, epoch, dst, cap);
 }
 
 int bnn_mi355x_last_wecc_exposure_counts(long *counts, int cap) { return copy_out(rt().wmem_counts, counts, cap); }
@@ -4435,8 +4402,8 @@ size_t bnn_mi355x_iwecc_exposure_params(int scheme, int code, int weight_code, i
     fail("iwecc_exposure_params: repair_every must not be negative (0: never repair)");
     return 0;
   }
-  return exposure_params_impl("iwecc_exposure_params", Hardening{scheme, burst, code, weight_code, weight_interleave}, run_seed, rate_w_q32, rate_t_q32,
-                              n_rates, epoch, scrub_every, dst, cap, repair_every, true);
+  return exposure_params_impl("iwecc_exposure_params", Hardening{scheme, burst, code, weight_code, weight_interleave},
+                              Exposure{1, scrub_every, 12, repair_every}, run_seed, rate_w_q32, rate_t_q32, n_rates, epoch, dst, cap);
 }
 
 int bnn_mi355x_last_iwecc_exposure_counts(long *counts, int cap) { return copy_out(rt().iwmem_counts, counts, cap); }
@@ -4625,11 +4592,7 @@ int bnn_mi355x_plan_faults(unsigned long long seed, int num_images, unsigned int
   std::vector<Fault> plan;
   const std::string pe = plan_faults(rt().spec, seed, num_images, flip_count, word_size, target, target_layers, num_targets, plan);
   if (!pe.empty()) return fail(pe);
-  for (size_t i = 0; i < plan.size() && (int)i < cap_records; i++) {
-    const Fault &f = plan[i];
-    const int v[8] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
-    for (int j = 0; j < 8; j++) records[i * 8 + j] = v[j];
-  }
+  for (size_t i = 0; i < plan.size() && (int)i < cap_records; i++) put_record(plan[i], records + i * 8);
   return (int)plan.size();
 }
 
@@ -4637,18 +4600,9 @@ size_t bnn_mi355x_pack_params_faulty(const char *path, const int *records, int n
   RawParams raw;
   const std::string e = read_raw_params(rt().spec, path ? path : "", raw);
   if (!e.empty()) { fail(e); return 0; }
-  for (int i = 0; i < n_faults; i++) {
-    const int *v = records + i * 8;
-    const Fault f{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
-    if (apply_fault(rt().spec, raw, f) < 0) { fail("pack_params_faulty: fault record out of range"); return 0; }
-  }
-  std::vector<uint8_t> blob;
-  pack_blob(rt().spec, raw, blob);
-  if (dst) {
-    if (cap < blob.size()) { fail("pack_params_faulty: destination too small"); return 0; }
-    std::memcpy(dst, blob.data(), blob.size());
-  }
-  return blob.size();
+  for (int i = 0; i < n_faults; i++)
+    if (apply_fault(rt().spec, raw, fault_record(records + i * 8)) < 0) { fail("pack_params_faulty: fault record out of range"); return 0; }
+  return pack_params_out("pack_params_faulty", raw, dst, cap);
 }
 
 int bnn_mi355x_set_fault_seed(unsigned long long seed) {
@@ -4659,11 +4613,7 @@ int bnn_mi355x_set_fault_seed(unsigned long long seed) {
 int bnn_mi355x_last_faults(int *records, int cap_records) {
   Runtime &r = rt();
   const int n = (int)r.last_faults.size();
-  for (int i = 0; i < n && i < cap_records; i++) {
-    const Fault &f = r.last_faults[i];
-    const int v[8] = {f.image, f.target, f.layer, f.mem, f.ind, f.thresh, f.bit, f.word_size};
-    for (int j = 0; j < 8; j++) records[i * 8 + j] = v[j];
-  }
+  for (int i = 0; i < n && i < cap_records; i++) put_record(r.last_faults[i], records + i * 8);
   return n;
 }
 

@@ -43,7 +43,14 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_last_wecc_exposure_counts", "bnn_mi355x_last_wecc_exposure_seeds", "bnn_mi355x_iwecc_layout",
        "bnn_mi355x_iwecc_site", "bnn_mi355x_pack_params_iwecc", "bnn_mi355x_iwecc_exposure_campaigns",
        "bnn_mi355x_iwecc_exposure_params", "bnn_mi355x_last_iwecc_exposure_counts", "bnn_mi355x_last_iwecc_exposure_seeds",
-       "bnn_mi355x_tile_boxes", "bnn_mi355x_windows_to_cifar", "bnn_mi355x_classify_windows"]
+       "bnn_mi355x_tile_boxes", "bnn_mi355x_windows_to_cifar", "bnn_mi355x_classify_windows", "bnn_mi355x_glyph_fit",
+       "bnn_mi355x_resample_coeffs", "bnn_mi355x_enhance_picture", "bnn_mi355x_glyphs_to_mnist", "bnn_mi355x_classify_glyphs"]
+
+
+class GlyphOpts(C.Structure):
+    """``bnn_mi355x_glyph_opts``"""
+    _fields_ = [("contrast", C.c_float), ("brightness", C.c_float), ("threshold", C.c_int), ("filter", C.c_int),
+                ("square_blank", C.c_int)]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -257,6 +264,16 @@ def declare_extensions(L):
         L.bnn_mi355x_classify_windows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, fp, fp,
                                                   C.c_int]
         L.bnn_mi355x_classify_windows.restype = ip
+    if hasattr(L, "bnn_mi355x_classify_glyphs"):  # (likewise)
+        op = C.POINTER(GlyphOpts)
+        L.bnn_mi355x_glyph_fit.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.bnn_mi355x_resample_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.bnn_mi355x_enhance_picture.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, op, C.c_void_p, ip]
+        L.bnn_mi355x_glyphs_to_mnist.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, op, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+        L.bnn_mi355x_classify_glyphs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, op, C.c_int, fp, fp,
+                                                 C.c_void_p]
+        L.bnn_mi355x_classify_glyphs.restype = ip
 
 
 _cache = {}

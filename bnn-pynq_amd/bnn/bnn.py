@@ -998,5 +998,170 @@ class LfcClassifier:
         self.usecPerImage = self.bnn.usecPerImage
         return result
 
+    # -- extension: from a picture to MNIST-format records and classes (LFC-BNN_MNIST_Webcam.ipynb and
+    #    LFC-BNN_Chars_Webcam.ipynb, cells 9-13) ------------------------------------------------------------
+    GLYPH_PRESETS = {"mnist": (3, 4.0, None), "chars": (5, 2.0, 180)}  # contrast, brightness, threshold of the two notebooks
+
+    @classmethod
+    def _glyph_opts(cls, preset="mnist", contrast=None, brightness=None, threshold=None, filter=3, square_blank=False):
+        """the notebooks' knobs -> ``bnn_mi355x_glyph_opts``.  ``preset``: "mnist" (contrast 3, brightness 4.0, no
+        threshold) or "chars" (5, 2.0, 180); each knob given by name overrides it.  ``filter``: 3 (BICUBIC, what
+        ``Image.resize`` takes by default) or 0 (NEAREST, the default of the notebooks' 2018 Pillow).  ``square_blank``:
+        reproduce the notebooks' blank record for a square ink box (they forget the paste)."""
+        if preset not in cls.GLYPH_PRESETS:
+            raise ValueError("preset must be one of %s" % sorted(cls.GLYPH_PRESETS))
+        c, b, t = cls.GLYPH_PRESETS[preset]
+        c = c if contrast is None else contrast
+        b = b if brightness is None else brightness
+        t = t if threshold is None else threshold
+        return abi.GlyphOpts(float(c), float(b), -1 if t is None else int(t), int(filter), 1 if square_blank else 0)
+
+    @staticmethod
+    def _picture(img):
+        """(uint8 array [H, W] / [H, W, 3] / [H, W, 4], bands); other PIL modes are made "L" as the notebooks do"""
+        if isinstance(img, np.ndarray):
+            if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))):
+                raise ValueError("pictures given as arrays must be uint8 [H, W, 3] (RGB), [H, W, 4] (RGBA) or [H, W] (L)")
+            a = np.ascontiguousarray(img)
+        else:
+            a = np.ascontiguousarray(np.asarray(img if img.mode in ("RGB", "RGBA", "L") else img.convert("L")))
+        return a, (1 if a.ndim == 2 else a.shape[2])
+
+    @staticmethod
+    def _glyph_boxes(boxes):
+        if boxes is None:
+            return None, 0
+        b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+        if len(b) == 0:
+            raise ValueError("no boxes (boxes=None takes the whole picture)")
+        return b, len(b)
+
+    def _on_device(self):
+        # a library with only the reference's six symbols (the reference's own .so) has no such entry points
+        return hasattr(self.bnn.interface, "bnn_mi355x_classify_glyphs")
+
+    @staticmethod
+    def _enhance_host(a, o):
+        """cells 9 of the notebooks in PIL: the enhanced "L" picture"""
+        from PIL import ImageEnhance
+        img = Image.fromarray(a).convert("L")
+        img = ImageEnhance.Contrast(img).enhance(o.contrast)
+        img = ImageEnhance.Brightness(img).enhance(o.brightness)
+        if o.threshold >= 0:
+            img = img.point(lambda p: 255 if p > o.threshold else 0)
+        return img
+
+    def _glyphs_host(self, a, b, o):
+        """cells 9-13 in PIL, per box: (records, ink boxes, status)"""
+        from PIL import ImageOps
+        plane = self._enhance_host(a, o)
+        boxes = [(0, 0) + plane.size] if b is None else [tuple(int(v) for v in box) for box in b]
+        recs = np.zeros((len(boxes), 784), np.uint8)
+        ink = np.zeros((len(boxes), 4), np.int32)
+        status = np.zeros(len(boxes), np.int32)
+        for i, box in enumerate(boxes):
+            crop = plane.crop(box)
+            found = ImageOps.invert(crop).getbbox()
+            if found is None:
+                found, status[i] = (0, 0) + crop.size, 1
+            glyph = crop.crop(found)
+            ink[i] = (box[0] + found[0], box[1] + found[1], box[0] + found[2], box[1] + found[3])
+            width, height = glyph.size
+            ratio = min((28. / height), (28. / width))
+            size = (28, 28) if height == width else (int(width * ratio), 28) if height > width else (28, int(height * ratio))
+            if 0 in size:
+                status[i] = 2
+                continue
+            background = Image.new("L", (28, 28), 255)
+            if not (o.square_blank and height == width):
+                glyph = glyph.resize(size, o.filter)
+                background.paste(glyph, (int((28 - glyph.size[0]) / 2), int((28 - glyph.size[1]) / 2)))
+            recs[i] = np.where(np.asarray(background).reshape(-1) == 0, 255, 1)
+        return recs, ink, status
+
+    def enhance(self, img, **opts):
+        """the picture after greyscale, contrast, brightness and threshold (see :meth:`_glyph_opts` for the knobs) as a
+        PIL "L" image: what the notebooks display before they crop.  Made on the GPU (``bnn_mi355x_enhance_picture``)."""
+        o = self._glyph_opts(**opts)
+        a, bands = self._picture(img)
+        if not self._on_device():
+            return self._enhance_host(a, o)
+        lib = self.bnn.interface
+        out = np.empty(a.shape[:2], np.uint8)
+        if lib.bnn_mi355x_enhance_picture(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, ctypes.byref(o), out.ctypes.data, None) != 0:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        return Image.fromarray(out)
+
+    def glyphs_to_mnist(self, img, boxes=None, details=False, **opts):
+        """MNIST-format records (uint8 array [n, 784]) of the glyphs in the ``boxes`` (left, upper, right, lower) of ONE
+        picture -- ``boxes=None``: the whole picture holds one glyph.  Per box what the notebooks do to a camera frame:
+        enhance, bounding box of the ink, resize into 28 x 28 keeping the aspect ratio, paste centred on white, 255 / 1
+        per pixel; on the GPU from one upload of the picture (``bnn_mi355x_glyphs_to_mnist``).  ``details=True``:
+        (records, ink boxes [n, 4] in picture coordinates, status [n]: 0 fine, 1 no ink in the box, 2 ink more than 28
+        times as long as wide, where Pillow raises -- that record is all zero).  The caller's image is left as it is."""
+        o = self._glyph_opts(**opts)
+        a, bands = self._picture(img)
+        b, n = self._glyph_boxes(boxes)
+        if not self._on_device():
+            recs, ink, status = self._glyphs_host(a, b, o)
+        else:
+            lib = self.bnn.interface
+            m = max(n, 1)
+            recs, ink, status = np.zeros((m, 784), np.uint8), np.zeros((m, 4), np.int32), np.zeros(m, np.int32)
+            if lib.bnn_mi355x_glyphs_to_mnist(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, None if b is None else b.ctypes.data, n,
+                                              ctypes.byref(o), recs.ctypes.data, ink.ctypes.data, status.ctypes.data) != 0:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        return (recs, ink, status) if details else recs
+
+    def image_to_mnist(self, img, fp, **opts):
+        """write the idx3 header for one image and the record of the one glyph in ``img`` (cell 13's file, what
+        :meth:`classify_mnist` takes).  Raises ``ValueError`` where Pillow does: ink more than 28 times as long as wide."""
+        recs, _, status = self.glyphs_to_mnist(img, None, details=True, **opts)
+        if status[0] == 2:
+            raise ValueError("height and width must be > 0")
+        fp.write(bytes([0, 0, 8, 3, 0, 0, 0, 1, 0, 0, 0, 28, 0, 0, 0, 28]))
+        fp.write(recs[0].tobytes())
+
+    def classify_glyphs(self, img, boxes=None, **opts):
+        """the classes of the glyphs in ``boxes`` (see :meth:`glyphs_to_mnist`): what :meth:`classify_mnists` returns for
+        an idx file of their records, -1 for a glyph of status 2.  The picture goes to the GPU once and the records never
+        leave it (``bnn_mi355x_classify_glyphs``).  ``self.glyph_status`` holds the status per glyph."""
+        o = self._glyph_opts(**opts)
+        a, bands = self._picture(img)
+        b, n = self._glyph_boxes(boxes)
+        if not self._on_device():
+            recs, _, status = self._glyphs_host(a, b, o)
+            with tempfile.NamedTemporaryFile() as tmp:
+                tmp.write(bytes([0, 0, 8, 3]) + len(recs).to_bytes(4, "big") + bytes([0, 0, 0, 28, 0, 0, 0, 28]) + recs.tobytes())
+                tmp.flush()
+                result = self.classify_mnists(tmp.name)
+            result[status == 2] = -1
+            self.glyph_status = status
+            return result
+        lib = self.bnn.interface
+        m = max(n, 1)
+        status = np.zeros(m, np.int32)
+        usec, pre = ctypes.c_float(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_classify_glyphs(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, None if b is None else b.ctypes.data, n,
+                                             ctypes.byref(o), len(self.classes), ctypes.byref(usec), ctypes.byref(pre), status.ctypes.data)
+        if not ptr:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        result = self.bnn._collect(ptr, m)
+        self.usecPerImage = self.bnn.usecPerImage = usec.value
+        self.usecPreprocess = pre.value
+        self.glyph_status = status
+        return result
+
+    def classify_image(self, img, **opts):
+        """the class of the one glyph in ``img`` (a PIL image or a uint8 array): the notebooks, from the camera frame to
+        the class, in one call.  Raises ``ValueError`` where Pillow does (see :meth:`image_to_mnist`)."""
+        result = self.classify_glyphs(img, None, **opts)
+        if self.glyph_status[0] == 2:
+            raise ValueError("height and width must be > 0")
+        return int(result[0])
+
+    def classify_path(self, path, **opts):
+        return self.classify_image(Image.open(path), **opts)
+
     def class_name(self, index):
         return self.bnn.classes[index]

@@ -29,4 +29,13 @@ inline bool vertical_pass_first(int w, int h, int out_h) { return (long)h > (lon
 // out_size pairs {first input index, tap count}.  Returns ksize.
 int lanczos_coeffs(int in_size, int out_size, std::vector<int32_t> &kk, std::vector<int32_t> &bounds);
 
+// The same tables for the two filters Image.resize takes in the LFC notebooks' glyph fit (glyphs.h), numbered as Pillow
+// numbers them.  kFilterBicubic (3, the default of current Pillow): a = -0.5, support 2, the filter scale clamped to 1
+// when the axis is enlarged.  kFilterNearest (0, the default of the notebooks' 2018 Pillow): one tap of weight 2^22 per
+// output at int(xo), xo starting at 0.5 * (in / out) and growing by REPEATED ADDITION of in / out, as Pillow's affine
+// scaler walks it; an index that lands outside the axis gets no tap (Pillow leaves such a pixel 0).  Same layout and
+// return value as lanczos_coeffs; 0 (and empty tables) for another filter or sizes below 1.
+constexpr int kFilterNearest = 0, kFilterBicubic = 3;
+int resample_coeffs(int filter, int in_size, int out_size, std::vector<int32_t> &kk, std::vector<int32_t> &bounds);
+
 }  // namespace bnn

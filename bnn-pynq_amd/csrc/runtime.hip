@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -53,6 +54,8 @@
 #include "resample.h"
 #include "window_kernels.h"
 #include "windows.h"
+#include "glyph_kernels.h"
+#include "glyphs.h"
 #include "packed_params.h"
 #include "pack_inputs.h"
 #include "topology.h"
@@ -319,6 +322,14 @@ struct Runtime {
   uint8_t *d_win_scene = nullptr, *d_win_body = nullptr;
   int32_t *d_win_meta = nullptr;
   hipEvent_t win_ev[3] = {nullptr, nullptr, nullptr};
+  // one picture and N boxes -> MNIST-format records / classes (bnn_mi355x_enhance_picture, bnn_mi355x_glyphs_to_mnist,
+  // bnn_mi355x_classify_glyphs; LFC): the picture, its L plane, boxes + found ink boxes, descriptors + tables, the global
+  // temporary of glyphs past the LDS budget, the 784-byte records, the plane's pixel sum; time stamps as win_ev
+  size_t gl_src_cap = 0, gl_plane_cap = 0, gl_box_cap = 0, gl_plan_cap = 0, gl_tmp_cap = 0, gl_rec_cap = 0, gl_sum_cap = 0;
+  uint8_t *d_gl_src = nullptr, *d_gl_plane = nullptr, *d_gl_tmp = nullptr, *d_gl_rec = nullptr;
+  int32_t *d_gl_box = nullptr, *d_gl_plan = nullptr;
+  unsigned long long *d_gl_sum = nullptr;
+  hipEvent_t gl_ev[3] = {nullptr, nullptr, nullptr};
   // optional per-stage profiling (bnn_mi355x_profile): one event set per enqueued chunk
   bool profiling = false;
   std::vector<std::vector<hipEvent_t>> prof_sets;
@@ -471,7 +482,7 @@ int upload_blob() {
 
 void free_workspace() {
   Runtime &r = rt();
-  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.file_cap && !r.all_cap && !r.h_io &&
+  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.gl_src_cap && !r.gl_plane_cap && !r.gl_box_cap && !r.gl_plan_cap && !r.gl_tmp_cap && !r.gl_rec_cap && !r.gl_sum_cap && !r.file_cap && !r.all_cap && !r.h_io &&
       !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
       !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.sw_prof_cap && !r.noise_cap && !r.in_stage_cap)
     return;
@@ -523,6 +534,12 @@ void free_workspace() {
   r.d_win_scene = r.d_win_body = nullptr;
   r.d_win_meta = nullptr;
   r.win_scene_cap = r.win_meta_cap = r.win_body_cap = 0;
+  (void)hipFree(r.d_gl_src); (void)hipFree(r.d_gl_plane); (void)hipFree(r.d_gl_tmp); (void)hipFree(r.d_gl_rec);
+  (void)hipFree(r.d_gl_box); (void)hipFree(r.d_gl_plan); (void)hipFree(r.d_gl_sum);
+  r.d_gl_src = r.d_gl_plane = r.d_gl_tmp = r.d_gl_rec = nullptr;
+  r.d_gl_box = r.d_gl_plan = nullptr;
+  r.d_gl_sum = nullptr;
+  r.gl_src_cap = r.gl_plane_cap = r.gl_box_cap = r.gl_plan_cap = r.gl_tmp_cap = r.gl_rec_cap = r.gl_sum_cap = 0;
 }
 
 // grow-only device buffer (contents are not preserved)
@@ -4943,6 +4960,220 @@ int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, i
     float pre = 0.f, pass = 0.f;
     HIP_OK(hipEventElapsedTime(&pre, r.win_ev[0], r.win_ev[1]));
     HIP_OK(hipEventElapsedTime(&pass, r.win_ev[1], r.win_ev[2]));
+    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
+    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
+    return 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  return result;
+}
+
+}  // extern "C"
+
+// ---- one picture and N boxes -> MNIST-format records / classes (LFC; glyphs.h) ----------------------------------
+namespace bnn {
+namespace {
+
+static_assert(sizeof(GlyphDesc) == 16 * sizeof(int32_t), "the record kernel reads a glyph's descriptor as 16 ints");
+static_assert(kGlyphMidBytes == BNN_MI355X_GLYPH_LDS_BYTES && kGlyphMidBytes + kGlyphRecord <= 65536, "the header states the record kernel's LDS bound");
+static_assert(kGlyphRecord % 16 == 0, "records are written with 16-byte stores");
+
+GlyphOpts glyph_opts(const bnn_mi355x_glyph_opts *o) {
+  GlyphOpts g;
+  if (o) { g.contrast = o->contrast; g.brightness = o->brightness; g.threshold = o->threshold; g.filter = o->filter; g.square_blank = o->square_blank; }
+  return g;
+}
+
+// Enqueues, on r.stream: the picture's upload (rows padded to whole 16-pixel lanes), k_glyph_luma and -- when a step is
+// not the identity -- k_glyph_enhance.  Afterwards p.plane is the enhanced L plane and *p.sum the pixel sum of the plane
+// before the enhancement.  The caller has validated the arguments and bound the device.
+int enqueue_glyph_plane(const char *what, const uint8_t *pixels, int width, int height, int bands, long row_stride, const GlyphOpts &o,
+                        GlyphPicture &p) {
+  Runtime &r = rt();
+  const long pitch = glyph_plane_pitch(width);
+  const size_t src_pitch = (size_t)pitch * bands, row_bytes = (size_t)width * bands;
+  if (grow(r.d_gl_src, r.gl_src_cap, src_pitch * height) || grow(r.d_gl_plane, r.gl_plane_cap, (size_t)pitch * height) ||
+      grow(r.d_gl_sum, r.gl_sum_cap, 1))
+    return -1;
+  HIP_OK(hipMemcpy2DAsync(r.d_gl_src, src_pitch, pixels, row_stride ? (size_t)row_stride : row_bytes, row_bytes, (size_t)height, hipMemcpyHostToDevice,
+                          r.stream));
+  HIP_OK(hipMemsetAsync(r.d_gl_sum, 0, sizeof(unsigned long long), r.stream));
+  p = GlyphPicture{};
+  p.src = r.d_gl_src; p.plane = r.d_gl_plane; p.width = width; p.height = height; p.bands = bands; p.plane_pitch = pitch; p.sum = r.d_gl_sum;
+  hipError_t e = launch_glyph_luma(p, r.stream);
+  if (e == hipSuccess && (o.contrast != 1.0f || o.brightness != 1.0f || o.threshold >= 0))
+    e = launch_glyph_enhance(p, o.contrast, o.brightness, o.threshold, r.stream);
+  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  return 0;
+}
+
+// Behind enqueue_glyph_plane: one upload of the boxes, k_glyph_bbox, the call's ONE host round trip (the n x 4 ink boxes
+// come back, the fit and the tables are made from them, descriptors and tables go up in one upload), k_glyph_record.
+// Record i lands at r.d_gl_rec + i * 784; `plan` holds status and ink boxes.  `meta` outlives its uploads.
+int enqueue_glyph_records(const char *what, const GlyphPicture &p, const int *boxes, int n, const GlyphOpts &o, GlyphPlan &plan,
+                          std::vector<int32_t> &meta) {
+  Runtime &r = rt();
+  const size_t off_found = (size_t)n * 4;
+  meta.assign((size_t)n * 8, 0);
+  std::memcpy(meta.data(), boxes, (size_t)n * 4 * sizeof(int32_t));
+  int tallest = 1;
+  for (int i = 0; i < n; i++) {
+    int32_t *f = meta.data() + off_found + 4 * (size_t)i;
+    f[0] = f[1] = INT_MAX;
+    f[2] = f[3] = -1;
+    tallest = std::max(tallest, boxes[4 * (size_t)i + 3] - boxes[4 * (size_t)i + 1]);
+  }
+  if (grow(r.d_gl_box, r.gl_box_cap, meta.size()) || grow(r.d_gl_rec, r.gl_rec_cap, (size_t)n * kGlyphRecord) ||
+      grow(r.d_gl_plan, r.gl_plan_cap, (size_t)n * 16 + 4096))
+    return -1;
+  HIP_OK(hipMemcpyAsync(r.d_gl_box, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  hipError_t e = launch_glyph_bbox(p, r.d_gl_box, r.d_gl_box + off_found, n, tallest, r.stream);
+  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  std::vector<int32_t> found((size_t)n * 4);
+  HIP_OK(hipMemcpyAsync(found.data(), r.d_gl_box + off_found, found.size() * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  const std::string bad = plan_glyphs(boxes, found.data(), n, o.filter, o.square_blank, plan);
+  if (!bad.empty()) return fail(std::string(what) + ": " + bad);
+  const size_t off_coef = (size_t)n * 16;
+  meta.assign(off_coef + plan.coef.size(), 0);
+  std::memcpy(meta.data(), plan.desc.data(), (size_t)n * sizeof(GlyphDesc));
+  if (!plan.coef.empty()) std::memcpy(meta.data() + off_coef, plan.coef.data(), plan.coef.size() * sizeof(int32_t));
+  // (the stream is idle here: growing costs no second wait)
+  if (grow(r.d_gl_plan, r.gl_plan_cap, meta.size()) || (plan.tmp_bytes && grow(r.d_gl_tmp, r.gl_tmp_cap, plan.tmp_bytes))) return -1;
+  HIP_OK(hipMemcpyAsync(r.d_gl_plan, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  e = launch_glyph_record(p, reinterpret_cast<const GlyphDesc *>(r.d_gl_plan), r.d_gl_plan + off_coef, plan.tmp_bytes ? r.d_gl_tmp : nullptr,
+                          r.d_gl_rec, n, r.stream);
+  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  return 0;
+}
+
+const char kGlyphsLfcOnly[] = ": MNIST-format records are the input of the LFC networks only";
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_glyph_fit(int width, int height, int out[5]) {
+  const GlyphFit f = glyph_fit(width, height);
+  if (out) { out[0] = f.out_w; out[1] = f.out_h; out[2] = f.off_x; out[3] = f.off_y; out[4] = f.status; }
+  return f.status;
+}
+
+int bnn_mi355x_resample_coeffs(int filter, int in_size, int out_size, int *kk, int *bounds, int cap_kk) {
+  std::vector<int32_t> k, b;
+  const int ksize = resample_coeffs(filter, in_size, out_size, k, b);
+  if (ksize <= 0) return fail("resample_coeffs: need filter 0 (NEAREST) or 3 (BICUBIC) and sizes of 1 or more");
+  if (kk && cap_kk > 0 && (size_t)cap_kk >= k.size()) std::memcpy(kk, k.data(), k.size() * sizeof(int32_t));
+  if (bounds) std::memcpy(bounds, b.data(), b.size() * sizeof(int32_t));
+  return ksize;
+}
+
+int bnn_mi355x_enhance_picture(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
+                               uint8_t *out_L, int *out_mean) {
+  Runtime &r = rt();
+  if (r.spec.is_cnv) return fail(std::string("enhance_picture") + kGlyphsLfcOnly);
+  const GlyphOpts o = glyph_opts(opts);
+  const std::string bad = validate_glyphs("enhance_picture", pixels, width, height, bands, row_stride, nullptr, 0, opts ? &o : nullptr, out_L);
+  if (!bad.empty()) return fail(bad);
+  if (bind_device()) return -1;
+  DrainOnFailure drain;
+  GlyphPicture p;
+  if (enqueue_glyph_plane("enhance_picture", pixels, width, height, bands, row_stride, o, p)) return -1;
+  unsigned long long sum = 0;
+  HIP_OK(hipMemcpy2DAsync(out_L, (size_t)width, p.plane, (size_t)p.plane_pitch, (size_t)width, (size_t)height, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipMemcpyAsync(&sum, p.sum, sizeof sum, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  const unsigned long long n = (unsigned long long)width * (unsigned long long)height;
+  if (out_mean) *out_mean = (int)((2 * sum + n) / (2 * n));
+  return 0;
+}
+
+int bnn_mi355x_glyphs_to_mnist(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes, int n_boxes,
+                               const bnn_mi355x_glyph_opts *opts, uint8_t *records, int *ink_boxes, int *status) {
+  Runtime &r = rt();
+  if (r.spec.is_cnv) return fail(std::string("glyphs_to_mnist") + kGlyphsLfcOnly);
+  const GlyphOpts o = glyph_opts(opts);
+  const std::string bad = validate_glyphs("glyphs_to_mnist", pixels, width, height, bands, row_stride, boxes, n_boxes, opts ? &o : nullptr, records);
+  if (!bad.empty()) return fail(bad);
+  const int whole[4] = {0, 0, width, height};
+  if (!boxes || n_boxes == 0) { boxes = whole; n_boxes = 1; }
+  const int n = n_boxes;
+  if (bind_device()) return -1;
+  GlyphPlan plan;
+  std::vector<int32_t> meta;
+  std::vector<uint8_t> staged((size_t)n * kGlyphRecord);
+  DrainOnFailure drain;
+  GlyphPicture p;
+  if (enqueue_glyph_plane("glyphs_to_mnist", pixels, width, height, bands, row_stride, o, p) ||
+      enqueue_glyph_records("glyphs_to_mnist", p, boxes, n, o, plan, meta))
+    return -1;
+  HIP_OK(hipMemcpyAsync(staged.data(), r.d_gl_rec, staged.size(), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  for (int i = 0; i < n; i++) {
+    // a status-2 glyph's record stays as the caller left it
+    if (plan.status[(size_t)i] != kGlyphTooThin) std::memcpy(records + (size_t)i * kGlyphRecord, staged.data() + (size_t)i * kGlyphRecord, kGlyphRecord);
+    if (status) status[i] = plan.status[(size_t)i];
+  }
+  if (ink_boxes) std::memcpy(ink_boxes, plan.ink_boxes.data(), (size_t)n * 4 * sizeof(int32_t));
+  return 0;
+}
+
+int *bnn_mi355x_classify_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes, int n_boxes,
+                                const bnn_mi355x_glyph_opts *opts, int number_class, float *usecPerImage, float *usecPreprocess, int *status) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (r.spec.is_cnv) { fail(std::string("classify_glyphs") + kGlyphsLfcOnly); return nullptr; }
+  const GlyphOpts o = glyph_opts(opts);
+  // (no output buffer of the caller's to check: the result array is the call's own)
+  const std::string bad = validate_glyphs("classify_glyphs", pixels, width, height, bands, row_stride, boxes, n_boxes, opts ? &o : nullptr, pixels);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  const int whole[4] = {0, 0, width, height};
+  if (!boxes || n_boxes == 0) { boxes = whole; n_boxes = 1; }
+  const int n = n_boxes;
+  if (!ready()) return nullptr;
+  int *result = new (std::nothrow) int[(size_t)n];
+  if (!result) { fail("out of memory"); return nullptr; }
+  // everything that can fail from here on frees `result`
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    GlyphPlan plan;
+    std::vector<int32_t> meta;
+    std::vector<uint64_t> words;
+    // the pass's workspaces first (they synchronise when they grow), so that nothing is allocated between the kernels
+    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n)) return -1;
+    for (hipEvent_t &e : r.gl_ev)
+      if (!e) HIP_OK(hipEventCreate(&e));
+    // up to 47 classes the last stage decodes on the device; beyond, the words come back and libm decodes them, as the
+    // reference does (bnn_mi355x_inference_device)
+    const bool on_device = number_class <= 47;
+    if (!on_device) words.resize((size_t)n);
+    DrainOnFailure drain;
+    GlyphPicture p;
+    HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
+    if (enqueue_glyph_plane("classify_glyphs", pixels, width, height, bands, row_stride, o, p) ||
+        enqueue_glyph_records("classify_glyphs", p, boxes, n, o, plan, meta))
+      return -1;
+    HIP_OK(hipEventRecord(r.gl_ev[1], r.stream));
+    // the pass bnn_mi355x_inference_device enqueues, on the same stream, on records that never left the device
+    if (bnn_mi355x_inference_device(r.d_gl_rec, n, number_class, on_device ? r.d_classes : nullptr, nullptr, r.d_words, r.stream)) return -1;
+    HIP_OK(hipEventRecord(r.gl_ev[2], r.stream));
+    if (on_device) HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(words.data(), r.d_words, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    for (int i = 0; i < n; i++) {
+      if (!on_device) result[i] = lfc_class_batched(words[(size_t)i], number_class);
+      if (plan.status[(size_t)i] == kGlyphTooThin) result[i] = -1;  // its record was never written
+      if (status) status[i] = plan.status[(size_t)i];
+    }
+    float pre = 0.f, pass = 0.f;
+    HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
+    HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));
     if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
     if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
     return 0;

@@ -796,6 +796,62 @@ int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, i
                                  int n_windows, int number_class, float *usecPerImage, float *usecPreprocess,
                                  int enable_detail);
 
+/* Read handwriting (LFC-BNN_MNIST_Webcam.ipynb and LFC-BNN_Chars_Webcam.ipynb, cells 9-13): ONE picture and N boxes
+ * become N MNIST-format records (28 x 28 bytes) -- and, with classify_glyphs, N classes -- in one call.  The notebooks
+ * do this by hand with PIL for one camera frame, through two temporary files; here the picture goes to the device once
+ * (csrc/glyph_kernels.hip) and classify_glyphs never brings the records back.  LFC libraries only (-1 / NULL +
+ * last_error on a CNV library).  Every step is Pillow's arithmetic, bit for bit (Pillow 12):
+ *   1 greyscale   L = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16; alpha is ignored, L pictures are taken as they are
+ *   2 contrast    m = (2 sum(L) + n) / (2 n) over the WHOLE picture of n pixels (int(ImageStat.mean + 0.5)); v = blend(m,
+ *                 v, contrast)
+ *   3 brightness  v = blend(0, v, brightness).  blend(a, b, f) = float(a) + f * float(b - a) in single precision, the
+ *                 multiply and the add rounded separately; 0 for t <= 0, 255 for t >= 255, else truncated.  A factor
+ *                 of exactly 1.0 leaves the plane alone.
+ *   4 threshold   v = v > threshold ? 255 : 0 (the chars notebook's 180); -1: none
+ *   5 ink box     inside a box, the bounding box of the pixels != 255 (getbbox of the inverse; the notebooks' 80-pixel
+ *                 white border only shifts it).  No ink at all: the whole box, status 1, a record with no ink.
+ *   6 fit         (w, h) the ink box, ratio = min(28. / h, 28. / w): square -> (28, 28), taller -> (int(w ratio), 28),
+ *                 wider -> (28, int(h ratio)); Image.resize of the crop with `filter` 3 (BICUBIC, Pillow's default) or
+ *                 0 (NEAREST, the default of the notebooks' 2018 Pillow).  An output dimension of 0 (aspect above 28)
+ *                 is status 2, where Pillow raises ValueError: the record is not written, the class is -1.
+ *   7 paste       at (int((28 - w') / 2), int((28 - h') / 2)) on white.  The notebooks forget the paste for a SQUARE
+ *                 ink box and hand the net a blank record; square_blank = 1 reproduces that, 0 pastes it.
+ *   8 record      784 bytes, row-major: 255 where the pasted pixel is exactly 0, 1 everywhere else.
+ *   pixels, width, height, bands, row_stride: the picture, as for windows_to_cifar.  It is not modified.
+ *   boxes:     n_boxes x 4 ints (left, upper, right, lower) as Image.crop takes them; n_boxes == 0 or boxes == NULL:
+ *              the whole picture is the one box (and one record / class comes back).
+ *   opts:      the notebooks' values are {3, 4.0, -1, 3, 0} (MNIST) and {5, 2.0, 180, 3, 0} (chars).
+ * enhance_picture: steps 1-4; out_L: height x width bytes (host), what the notebooks display; out_mean (may be NULL): m.
+ * glyphs_to_mnist: records: n x 784 bytes (host); ink_boxes (may be NULL): n x 4 ints, the ink boxes in picture
+ *       coordinates; status (may be NULL): n ints, 0 / 1 / 2 as above.
+ * classify_glyphs: the same records stay in HBM and the pass bnn_mi355x_inference_device enqueues runs on them on the
+ *       same stream; the classes come back in one copy (with number_class > 47 the words do, and are decoded on the
+ *       host like everywhere else).  Return convention, ownership and the two times as classify_windows.
+ * Refused before anything touches the GPU, worded like the window entry points: bad boxes (the first one is named), bands,
+ * row stride, picture size, null pointers; factors that are not finite or are negative; a threshold outside -1..255; a
+ * filter other than 0 / 3.
+ * Ink boxes whose horizontal-pass output (height x w' bytes) exceeds BNN_MI355X_GLYPH_LDS_BYTES keep it in a global
+ * temporary instead of LDS.
+ * glyph_fit, resample_coeffs: host only, touch no GPU (tests).  glyph_fit: step 6 and 7 for a (width, height) ink box,
+ *       out (may be NULL) = {w', h', paste x, paste y, status}; returns the status (0 or 2).  resample_coeffs: Pillow's
+ *       8-bit fixed-point coefficient table of one axis (k = round(2^22 w), `ksize` ints per output, zero padded) and
+ *       its bounds (first input index, tap count per output); returns ksize, -1 for another filter or a size below 1;
+ *       kk is written when cap_kk >= out_size x ksize ints, bounds (2 x out_size ints) when it is not NULL. */
+#define BNN_MI355X_GLYPH_LDS_BYTES 32768
+typedef struct {
+  float contrast, brightness;
+  int threshold, filter, square_blank;
+} bnn_mi355x_glyph_opts;
+int bnn_mi355x_glyph_fit(int width, int height, int out[5]);
+int bnn_mi355x_resample_coeffs(int filter, int in_size, int out_size, int *kk, int *bounds, int cap_kk);
+int bnn_mi355x_enhance_picture(const uint8_t *pixels, int width, int height, int bands, long row_stride,
+                               const bnn_mi355x_glyph_opts *opts, uint8_t *out_L, int *out_mean);
+int bnn_mi355x_glyphs_to_mnist(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes,
+                               int n_boxes, const bnn_mi355x_glyph_opts *opts, uint8_t *records, int *ink_boxes, int *status);
+int *bnn_mi355x_classify_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *boxes,
+                                int n_boxes, const bnn_mi355x_glyph_opts *opts, int number_class, float *usecPerImage,
+                                float *usecPreprocess, int *status);
+
 /* Test hook: run the stages 0..stage on n host images (n <= 32768) and copy that stage's output,
  * exactly as it sits in HBM (bit-packed activation layout), to dst.  CNV: stage L =
  * layer L (0..7, after the max-pool where there is one); LFC: stage 0 = binarised input, stage

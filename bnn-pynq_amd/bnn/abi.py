@@ -44,13 +44,19 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_iwecc_site", "bnn_mi355x_pack_params_iwecc", "bnn_mi355x_iwecc_exposure_campaigns",
        "bnn_mi355x_iwecc_exposure_params", "bnn_mi355x_last_iwecc_exposure_counts", "bnn_mi355x_last_iwecc_exposure_seeds",
        "bnn_mi355x_tile_boxes", "bnn_mi355x_windows_to_cifar", "bnn_mi355x_classify_windows", "bnn_mi355x_glyph_fit",
-       "bnn_mi355x_resample_coeffs", "bnn_mi355x_enhance_picture", "bnn_mi355x_glyphs_to_mnist", "bnn_mi355x_classify_glyphs"]
+       "bnn_mi355x_resample_coeffs", "bnn_mi355x_enhance_picture", "bnn_mi355x_glyphs_to_mnist", "bnn_mi355x_classify_glyphs",
+       "bnn_mi355x_find_glyphs_host", "bnn_mi355x_find_glyphs", "bnn_mi355x_read_glyphs", "bnn_mi355x_last_find_usec"]
 
 
 class GlyphOpts(C.Structure):
     """``bnn_mi355x_glyph_opts``"""
     _fields_ = [("contrast", C.c_float), ("brightness", C.c_float), ("threshold", C.c_int), ("filter", C.c_int),
                 ("square_blank", C.c_int)]
+
+
+class FindOpts(C.Structure):
+    """``bnn_mi355x_find_opts``"""
+    _fields_ = [("ink_level", C.c_int), ("reach_x", C.c_int), ("reach_y", C.c_int), ("min_pixels", C.c_int), ("order", C.c_int)]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -274,6 +280,16 @@ def declare_extensions(L):
         L.bnn_mi355x_classify_glyphs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, op, C.c_int, fp, fp,
                                                  C.c_void_p]
         L.bnn_mi355x_classify_glyphs.restype = ip
+    if hasattr(L, "bnn_mi355x_read_glyphs"):  # (likewise)
+        op, fo = C.POINTER(GlyphOpts), C.POINTER(FindOpts)
+        L.bnn_mi355x_find_glyphs_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, fo, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.bnn_mi355x_find_glyphs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, op, fo, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int]
+        L.bnn_mi355x_read_glyphs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, op, fo, C.c_int, C.c_int, ip, C.c_void_p, fp, fp,
+                                             C.c_void_p]
+        L.bnn_mi355x_read_glyphs.restype = ip
+        L.bnn_mi355x_last_find_usec.argtypes = []
+        L.bnn_mi355x_last_find_usec.restype = C.c_float
 
 
 _cache = {}

@@ -1152,6 +1152,76 @@ class LfcClassifier:
         self.glyph_status = status
         return result
 
+    # -- extension: find the glyphs of a picture (connected components of its ink, on the GPU) and read them ----------
+    FIND_ORDERS = {"raster": 0, "left": 1}
+
+    def _find_entry(self, symbol):
+        lib = self.bnn.interface
+        if not hasattr(lib, symbol):  # no second implementation in Python
+            raise RuntimeError("the runtime library has no %s: rebuild it with `make -C bnn-pynq_amd`" % symbol)
+        return lib
+
+    @classmethod
+    def _find_opts(cls, reach, min_pixels, ink_level, order, max_glyphs):
+        if order not in cls.FIND_ORDERS:
+            raise ValueError("order must be one of %s" % sorted(cls.FIND_ORDERS))
+        rx, ry = reach
+        return abi.FindOpts(int(ink_level), int(rx), int(ry), int(min_pixels), cls.FIND_ORDERS[order]), int(max_glyphs)
+
+    def find_glyphs(self, img, reach=(1, 1), min_pixels=1, ink_level=255, order="left", max_glyphs=4096, details=False, **opts):
+        """the boxes (int32 array [n, 4]: left, upper, right, lower, as :meth:`classify_glyphs` takes them) of the glyphs of
+        ONE picture: the connected components of its ink, labelled on the GPU on the enhanced plane
+        (``bnn_mi355x_find_glyphs``; ``**opts``: the knobs of :meth:`_glyph_opts`).  A pixel is ink below ``ink_level``;
+        two ink pixels are adjacent within ``reach`` = (x, y) pixels -- (1, 1) is 8-connectivity, a larger y joins the dot
+        of an "i" to its stem; components of fewer than ``min_pixels`` pixels are dropped.  ``order``: "left" (by left
+        edge: the reading order of one line) or "raster" (by first pixel).  At most ``max_glyphs`` are returned.
+        ``details=True``: (boxes, pixel counts, total found, labels int32 [height, width]: the index of each pixel's glyph,
+        -1 for background, dropped glyphs and glyphs beyond ``max_glyphs``)."""
+        o = self._glyph_opts(**opts)
+        f, cap = self._find_opts(reach, min_pixels, ink_level, order, max_glyphs)
+        a, bands = self._picture(img)
+        lib = self._find_entry("bnn_mi355x_find_glyphs")
+        n = max(1, min(cap, ((a.shape[1] + 1) // 2) * ((a.shape[0] + 1) // 2)))  # never more glyphs than 2 x 2 cells
+        boxes, counts = np.zeros((n, 4), np.int32), np.zeros(n, np.int32)
+        labels = np.empty(a.shape[:2], np.int32) if details else None
+        total = lib.bnn_mi355x_find_glyphs(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, ctypes.byref(o), ctypes.byref(f), boxes.ctypes.data,
+                                           counts.ctypes.data, None if labels is None else labels.ctypes.data, cap)
+        if total < 0:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        self.glyphs_found = total
+        k = min(total, cap)
+        return (boxes[:k], counts[:k], total, labels) if details else boxes[:k]
+
+    def read_glyphs(self, img, reach=(1, 1), min_pixels=1, ink_level=255, order="left", max_glyphs=4096, **opts):
+        """(classes, boxes) of the glyphs of ONE picture, found as :meth:`find_glyphs` finds them and classified as
+        :meth:`classify_glyphs` classifies those boxes, in one call (``bnn_mi355x_read_glyphs``): the picture goes to the
+        GPU once, neither the plane nor the records come back.  ``self.glyph_status`` holds the status per glyph,
+        ``self.glyphs_found`` how many there were (it may exceed ``max_glyphs``)."""
+        o = self._glyph_opts(**opts)
+        f, cap = self._find_opts(reach, min_pixels, ink_level, order, max_glyphs)
+        a, bands = self._picture(img)
+        lib = self._find_entry("bnn_mi355x_read_glyphs")
+        n = max(1, min(cap, ((a.shape[1] + 1) // 2) * ((a.shape[0] + 1) // 2)))
+        boxes, status = np.zeros((n, 4), np.int32), np.zeros(n, np.int32)
+        usec, pre, found = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_int(0)
+        ptr = lib.bnn_mi355x_read_glyphs(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, ctypes.byref(o), ctypes.byref(f), len(self.classes), cap,
+                                         ctypes.byref(found), boxes.ctypes.data, ctypes.byref(usec), ctypes.byref(pre), status.ctypes.data)
+        if not ptr:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        k = min(found.value, cap)
+        result = np.ctypeslib.as_array(ptr, shape=(max(k, 1),))[:k].astype(np.int32, copy=True)
+        lib.free_results(ptr)
+        self.usecPerImage = self.bnn.usecPerImage = usec.value
+        self.usecPreprocess = pre.value
+        self.glyph_status = status[:k]
+        self.glyphs_found = found.value
+        return result, boxes[:k]
+
+    def read_text(self, img, **kwargs):
+        """what the picture says: the class names of :meth:`read_glyphs`' glyphs in order, "?" for a glyph of status 2"""
+        classes, _ = self.read_glyphs(img, **kwargs)
+        return "".join(self.class_name(c) if c >= 0 else "?" for c in classes)
+
     def classify_image(self, img, **opts):
         """the class of the one glyph in ``img`` (a PIL image or a uint8 array): the notebooks, from the camera frame to
         the class, in one call.  Raises ``ValueError`` where Pillow does (see :meth:`image_to_mnist`)."""

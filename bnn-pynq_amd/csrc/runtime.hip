@@ -54,6 +54,8 @@
 #include "resample.h"
 #include "window_kernels.h"
 #include "windows.h"
+#include "component_kernels.h"
+#include "components.h"
 #include "glyph_kernels.h"
 #include "glyphs.h"
 #include "packed_params.h"
@@ -330,6 +332,15 @@ struct Runtime {
   int32_t *d_gl_box = nullptr, *d_gl_plan = nullptr;
   unsigned long long *d_gl_sum = nullptr;
   hipEvent_t gl_ev[3] = {nullptr, nullptr, nullptr};
+  // the glyphs of a picture (bnn_mi355x_find_glyphs, bnn_mi355x_read_glyphs; components.h): ink words, the label plane, the
+  // components by root number, head + compacted list, and -- when the label map is asked for -- the index per root number
+  // and the relabelled plane; time stamps around the labelling launches and what they measured in the last call
+  size_t cc_bits_cap = 0, cc_label_cap = 0, cc_stat_cap = 0, cc_list_cap = 0, cc_index_cap = 0, cc_out_cap = 0;
+  uint64_t *d_cc_bits = nullptr;
+  int32_t *d_cc_label = nullptr, *d_cc_list = nullptr, *d_cc_index = nullptr, *d_cc_out = nullptr;
+  Component *d_cc_stat = nullptr;
+  hipEvent_t cc_ev[2] = {nullptr, nullptr};
+  float cc_usec = 0.f;
   // optional per-stage profiling (bnn_mi355x_profile): one event set per enqueued chunk
   bool profiling = false;
   std::vector<std::vector<hipEvent_t>> prof_sets;
@@ -482,7 +493,7 @@ int upload_blob() {
 
 void free_workspace() {
   Runtime &r = rt();
-  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.gl_src_cap && !r.gl_plane_cap && !r.gl_box_cap && !r.gl_plan_cap && !r.gl_tmp_cap && !r.gl_rec_cap && !r.gl_sum_cap && !r.file_cap && !r.all_cap && !r.h_io &&
+  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.gl_src_cap && !r.gl_plane_cap && !r.gl_box_cap && !r.gl_plan_cap && !r.gl_tmp_cap && !r.gl_rec_cap && !r.gl_sum_cap && !r.cc_bits_cap && !r.cc_label_cap && !r.cc_stat_cap && !r.cc_list_cap && !r.cc_index_cap && !r.cc_out_cap && !r.file_cap && !r.all_cap && !r.h_io &&
       !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
       !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.sw_prof_cap && !r.noise_cap && !r.in_stage_cap)
     return;
@@ -540,6 +551,12 @@ void free_workspace() {
   r.d_gl_box = r.d_gl_plan = nullptr;
   r.d_gl_sum = nullptr;
   r.gl_src_cap = r.gl_plane_cap = r.gl_box_cap = r.gl_plan_cap = r.gl_tmp_cap = r.gl_rec_cap = r.gl_sum_cap = 0;
+  (void)hipFree(r.d_cc_bits); (void)hipFree(r.d_cc_label); (void)hipFree(r.d_cc_stat); (void)hipFree(r.d_cc_list);
+  (void)hipFree(r.d_cc_index); (void)hipFree(r.d_cc_out);
+  r.d_cc_bits = nullptr;
+  r.d_cc_label = r.d_cc_list = r.d_cc_index = r.d_cc_out = nullptr;
+  r.d_cc_stat = nullptr;
+  r.cc_bits_cap = r.cc_label_cap = r.cc_stat_cap = r.cc_list_cap = r.cc_index_cap = r.cc_out_cap = 0;
 }
 
 // grow-only device buffer (contents are not preserved)
@@ -5171,6 +5188,206 @@ int *bnn_mi355x_classify_glyphs(const uint8_t *pixels, int width, int height, in
       if (plan.status[(size_t)i] == kGlyphTooThin) result[i] = -1;  // its record was never written
       if (status) status[i] = plan.status[(size_t)i];
     }
+    float pre = 0.f, pass = 0.f;
+    HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
+    HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));
+    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
+    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
+    return 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  return result;
+}
+
+}  // extern "C"
+
+// ---- the glyphs of a picture: connected components of its ink (LFC; components.h) ----------------------------------
+namespace bnn {
+namespace {
+
+static_assert(sizeof(Component) == 8 * sizeof(int32_t), "the kernels and the read-back take a component as 8 ints");
+static_assert(kMaxComponentPixels == BNN_MI355X_FIND_MAX_PIXELS && kMaxReach == BNN_MI355X_FIND_MAX_REACH, "the header states the model's limits");
+
+FindOpts find_opts(const bnn_mi355x_find_opts *f) {
+  FindOpts o;
+  if (f) { o.ink_level = f->ink_level; o.reach_x = f->reach_x; o.reach_y = f->reach_y; o.min_pixels = f->min_pixels; o.order = f->order; }
+  return o;
+}
+
+constexpr size_t kFirstReadBack = 4096;  // components that come back with the counters, in the call's one copy
+
+// The workspaces of a picture of width x height pixels, before anything is enqueued (growing synchronises).
+int reserve_components(int width, int height, bool labels) {
+  Runtime &r = rt();
+  const size_t n = (size_t)width * height, comps = max_components(width, height);
+  if (grow(r.d_cc_bits, r.cc_bits_cap, (size_t)height * cc_words_per_row(width)) || grow(r.d_cc_label, r.cc_label_cap, n) ||
+      grow(r.d_cc_stat, r.cc_stat_cap, comps) || grow(r.d_cc_list, r.cc_list_cap, kComponentHead + comps * 8) ||
+      (labels && (grow(r.d_cc_index, r.cc_index_cap, comps) || grow(r.d_cc_out, r.cc_out_cap, n))))
+    return -1;
+  for (hipEvent_t &e : r.cc_ev)
+    if (!e) HIP_OK(hipEventCreate(&e));
+  return 0;
+}
+
+// Behind enqueue_glyph_plane, on r.stream: the six labelling launches, the call's round trip for the component list
+// (the counters and the first kFirstReadBack components in one copy; a second copy only for more), select_components,
+// and -- when `labels` is not null -- the index map's upload, k_cc_relabel and the map's copy into `labels`, which the
+// caller waits for.  `chosen`: the returned components in order; `index` outlives its upload.
+int enqueue_components(const char *what, const GlyphPicture &p, const FindOpts &f, int cap, int32_t *labels, std::vector<Component> &chosen,
+                       long &total, std::vector<int32_t> &index) {
+  Runtime &r = rt();
+  const int comps = (int)max_components(p.width, p.height);
+  ComponentPlane c{};
+  c.plane = p.plane; c.plane_pitch = p.plane_pitch; c.width = p.width; c.height = p.height;
+  c.words_per_row = cc_words_per_row(p.width); c.bits = r.d_cc_bits; c.label = r.d_cc_label;
+  HIP_OK(hipEventRecord(r.cc_ev[0], r.stream));
+  hipError_t e = launch_cc_label(c, f.ink_level, f.reach_x, f.reach_y, r.stream);
+  if (e == hipSuccess) e = launch_cc_collect(c, r.d_cc_list, r.d_cc_stat, comps, f.min_pixels, r.stream);
+  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  HIP_OK(hipEventRecord(r.cc_ev[1], r.stream));
+  const size_t first = std::min((size_t)comps, kFirstReadBack);
+  std::vector<int32_t> back(kComponentHead + first * 8);
+  HIP_OK(hipMemcpyAsync(back.data(), r.d_cc_list, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  const long roots = back[0], kept = back[1];
+  if (roots < 0 || roots > comps || kept < 0 || kept > roots) return fail(std::string(what) + ": internal: the component counters are out of range");
+  if ((size_t)kept > first) {
+    back.resize(kComponentHead + (size_t)kept * 8);
+    HIP_OK(hipMemcpyAsync(back.data(), r.d_cc_list, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+  }
+  HIP_OK(hipEventElapsedTime(&r.cc_usec, r.cc_ev[0], r.cc_ev[1]));
+  r.cc_usec *= 1000.f;
+  std::vector<Component> all((size_t)kept);
+  if (kept) std::memcpy(all.data(), back.data() + kComponentHead, (size_t)kept * sizeof(Component));
+  for (const Component &k : all)
+    if (k.id < 0 || k.id >= roots || k.left < 0 || k.upper < 0 || k.right > p.width || k.lower > p.height || k.left >= k.right || k.upper >= k.lower)
+      return fail(std::string(what) + ": internal: a component's box leaves the picture");
+  total = select_components(all, f, cap, chosen);
+  if (labels) {
+    index.assign((size_t)std::max(roots, 1L), -1);
+    for (size_t k = 0; k < chosen.size(); k++) index[(size_t)chosen[k].id] = (int32_t)k;
+    HIP_OK(hipMemcpyAsync(r.d_cc_index, index.data(), index.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+    e = launch_cc_relabel(c, r.d_cc_index, r.d_cc_out, r.stream);
+    if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+    HIP_OK(hipMemcpyAsync(labels, r.d_cc_out, (size_t)p.width * p.height * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  }
+  return 0;
+}
+
+void boxes_of(const std::vector<Component> &chosen, int *boxes, int *pixel_counts) {
+  for (size_t k = 0; k < chosen.size(); k++) {
+    const Component &c = chosen[k];
+    boxes[4 * k] = c.left; boxes[4 * k + 1] = c.upper; boxes[4 * k + 2] = c.right; boxes[4 * k + 3] = c.lower;
+    if (pixel_counts) pixel_counts[k] = c.pixels;
+  }
+}
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_find_glyphs_host(const uint8_t *plane, int width, int height, long row_stride, const bnn_mi355x_find_opts *find, int *boxes,
+                                int *pixel_counts, int32_t *labels, int cap) {
+  const FindOpts f = find_opts(find);
+  const GlyphOpts o;
+  std::string bad = validate_glyphs("find_glyphs_host", plane, width, height, 1, row_stride, nullptr, 0, &o, boxes);
+  if (bad.empty()) bad = validate_find("find_glyphs_host", width, height, &f, boxes, cap);
+  if (!bad.empty()) return fail(bad);
+  const long total = find_components_host(plane, width, height, row_stride, f, boxes, pixel_counts, labels, cap);
+  return (int)total;
+}
+
+float bnn_mi355x_last_find_usec(void) { return rt().cc_usec; }
+
+int bnn_mi355x_find_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
+                           const bnn_mi355x_find_opts *find, int *boxes, int *pixel_counts, int32_t *labels, int cap) {
+  Runtime &r = rt();
+  if (r.spec.is_cnv) return fail(std::string("find_glyphs") + kGlyphsLfcOnly);
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  std::string bad = validate_glyphs("find_glyphs", pixels, width, height, bands, row_stride, nullptr, 0, opts ? &o : nullptr, boxes);
+  if (bad.empty()) bad = validate_find("find_glyphs", width, height, &f, boxes, cap);
+  if (!bad.empty()) return fail(bad);
+  if (bind_device()) return -1;
+  std::vector<Component> chosen;
+  std::vector<int32_t> index;
+  long total = 0;
+  if (reserve_components(width, height, labels != nullptr)) return -1;
+  DrainOnFailure drain;
+  GlyphPicture p;
+  if (enqueue_glyph_plane("find_glyphs", pixels, width, height, bands, row_stride, o, p) ||
+      enqueue_components("find_glyphs", p, f, cap, labels, chosen, total, index))
+    return -1;
+  if (labels) HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  boxes_of(chosen, boxes, pixel_counts);
+  return (int)total;
+}
+
+int *bnn_mi355x_read_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
+                            const bnn_mi355x_find_opts *find, int number_class, int cap, int *n_found, int *boxes, float *usecPerImage,
+                            float *usecPreprocess, int *status) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (r.spec.is_cnv) { fail(std::string("read_glyphs") + kGlyphsLfcOnly); return nullptr; }
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  std::string bad = validate_glyphs("read_glyphs", pixels, width, height, bands, row_stride, nullptr, 0, opts ? &o : nullptr, n_found);
+  if (bad.empty()) bad = validate_find("read_glyphs", width, height, &f, boxes, cap);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (!ready()) return nullptr;
+  int *result = nullptr;
+  // everything that can fail from here on frees `result`
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    std::vector<Component> chosen;
+    std::vector<int32_t> index, meta, found;
+    std::vector<uint64_t> words;
+    GlyphPlan plan;
+    long total = 0;
+    if (reserve_components(width, height, false)) return -1;
+    for (hipEvent_t &e : r.gl_ev)
+      if (!e) HIP_OK(hipEventCreate(&e));
+    const bool on_device = number_class <= 47;  // (as classify_glyphs)
+    DrainOnFailure drain;
+    GlyphPicture p;
+    HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
+    if (enqueue_glyph_plane("read_glyphs", pixels, width, height, bands, row_stride, o, p) ||
+        enqueue_components("read_glyphs", p, f, cap, nullptr, chosen, total, index))
+      return -1;
+    const int n = (int)chosen.size();
+    result = new (std::nothrow) int[(size_t)(n > 0 ? n : 1)];
+    if (!result) return fail("out of memory");
+    *n_found = (int)total;
+    if (n == 0) {  // nothing to read: a non-null, empty result
+      HIP_OK(hipStreamSynchronize(r.stream));
+      drain.ok();
+      return 0;
+    }
+    found.resize((size_t)n * 4);
+    boxes_of(chosen, found.data(), nullptr);
+    // the stream is idle after the component list's round trip: the pass's workspaces grow without a second wait
+    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n)) return -1;
+    if (!on_device) words.resize((size_t)n);
+    // the found boxes are boxes like any caller's: from here on this is classify_glyphs
+    if (enqueue_glyph_records("read_glyphs", p, found.data(), n, o, plan, meta)) return -1;
+    HIP_OK(hipEventRecord(r.gl_ev[1], r.stream));
+    if (bnn_mi355x_inference_device(r.d_gl_rec, n, number_class, on_device ? r.d_classes : nullptr, nullptr, r.d_words, r.stream)) return -1;
+    HIP_OK(hipEventRecord(r.gl_ev[2], r.stream));
+    if (on_device) HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(words.data(), r.d_words, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    for (int i = 0; i < n; i++) {
+      if (!on_device) result[i] = lfc_class_batched(words[(size_t)i], number_class);
+      if (plan.status[(size_t)i] == kGlyphTooThin) result[i] = -1;  // its record was never written
+      if (status) status[i] = plan.status[(size_t)i];
+    }
+    std::memcpy(boxes, found.data(), found.size() * sizeof(int));
     float pre = 0.f, pass = 0.f;
     HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
     HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));

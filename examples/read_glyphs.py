@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Read handwriting from a picture (the reference's notebooks/LFC-BNN_MNIST_Webcam.ipynb, cells 9-15) on an MI355X -- for
-a whole line of digits at once.  A few digits are drawn with Pillow's own font on an off-white sheet, the sheet is split
-into boxes where columns hold no ink, and every box goes through the notebook's procedure (contrast, brightness, bounding
-box of the ink, 28 x 28, invert) and the LFC network in ONE call: the picture goes to the GPU once, the records never
-come back.  The mnist parameters were trained on handwriting; Pillow's font is print, so expect misread digits (the
-host route through Pillow and classify_mnists reads the same ones): the example shows the path, not the accuracy.
+a whole line of digits at once: "here is a frame, what does it say".  A few digits are drawn with Pillow's own font on an
+off-white sheet and read_glyphs does the rest in ONE call: the picture goes to the GPU once, the glyphs are found there
+(the connected components of the ink of the enhanced plane, left to right), every glyph goes through the notebook's
+procedure (contrast, brightness, bounding box of the ink, 28 x 28, invert) and the LFC network, and neither the plane nor
+the records come back.  The column split this example used to find its boxes with stays as a cross-check: on one line of
+separate glyphs the found boxes have exactly its x-ranges.  The mnist parameters were trained on handwriting; Pillow's
+font is print, so expect misread digits (the host route through Pillow and classify_mnists reads the same ones): the
+example shows the path, not the accuracy.
 
     python examples/read_glyphs.py [digits [enhanced.png]]
 """
@@ -29,21 +32,24 @@ font = ImageFont.load_default(size=64)
 for i, ch in enumerate(digits):
     draw.text((30 + 50 * i, 12), ch, font=font, fill=(25, 25, 40))
 
-# cell 9: what the notebook displays
+# cells 9-15 for the whole sheet: find the glyphs, make their records, classify them
+classes, boxes = classifier.read_glyphs(sheet, order="left")
+n = len(boxes)
+print("%d glyphs found" % classifier.glyphs_found)
+if n:
+    print("%d glyphs: %.1f us upload + labelling + glyph kernels, %.1f us classification pass (device time)"
+          % (n, classifier.usecPreprocess * n, classifier.usecPerImage * n))
+print("drawn:", digits)
+print("read: ", "".join(classifier.class_name(c) if c >= 0 else "?" for c in classes))
+
+# the cross-check: cell 9's picture, split where columns hold no ink (what a caller without find_glyphs would do; it
+# fails for two lines, for glyphs whose columns overlap and for a speck of noise anywhere in a column)
 enhanced = classifier.enhance(sheet)
 if len(sys.argv) > 2:
     enhanced.save(sys.argv[2])
     print("enhanced:", sys.argv[2])
-
-# one box per run of columns that hold ink (finding the boxes is the caller's business: any segmentation will do)
 ink_columns = (np.asarray(enhanced) != 255).any(axis=0)
 edges = np.flatnonzero(np.diff(np.concatenate([[0], ink_columns.astype(np.int8), [0]])))
-boxes = [(int(a), 0, int(b), sheet.size[1]) for a, b in zip(edges[::2], edges[1::2])]
-print("%d boxes" % len(boxes))
-
-# cells 11-15 for all of them
-classes = classifier.classify_glyphs(sheet, boxes)
-print("%d glyphs: %.1f us upload + glyph kernels, %.1f us classification pass (device time)"
-      % (len(boxes), classifier.usecPreprocess * len(boxes), classifier.usecPerImage * len(boxes)))
-print("drawn:", digits)
-print("read: ", "".join(classifier.class_name(c) if c >= 0 else "?" for c in classes))
+split = [(int(a), int(b)) for a, b in zip(edges[::2], edges[1::2])]
+found = [(int(b[0]), int(b[2])) for b in boxes]
+print("x-ranges of the found boxes %s the column split's: %s" % ("equal" if found == split else "DIFFER from", found))

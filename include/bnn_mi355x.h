@@ -852,6 +852,53 @@ int *bnn_mi355x_classify_glyphs(const uint8_t *pixels, int width, int height, in
                                 int n_boxes, const bnn_mi355x_glyph_opts *opts, int number_class, float *usecPerImage,
                                 float *usecPreprocess, int *status);
 
+/* Find the glyphs of a picture: the connected components of its ink, labelled on the device on the enhanced L plane that
+ * the glyph entry points make there (csrc/component_kernels.hip), so that reading a frame is ONE call: upload, enhance,
+ * label, boxes, records, classes.  The reference has no segmentation; the model is this project's own (csrc/components.h):
+ *   ink        a pixel of the enhanced plane (steps 1-4 above) is ink iff its value is below ink_level (1..255; at 255
+ *              this is step 5's rule "!= 255")
+ *   adjacency  two different ink pixels are adjacent iff |dx| <= reach_x and |dy| <= reach_y (1..BNN_MI355X_FIND_MAX_REACH
+ *              each); the glyphs are the connected components.  Reach (1, 1) is 8-connectivity; a larger reach_y joins
+ *              the dot of an "i" to its stem and the bars of an "=".
+ *   component  its first pixel (smallest y * width + x), its box (left, upper, right, lower; right and lower exclusive,
+ *              as classify_glyphs takes boxes), its number of ink pixels
+ *   filter     components of fewer than min_pixels (>= 1) ink pixels are dropped
+ *   order      0: ascending first pixel (raster order); 1: ascending (left, upper, first pixel), the reading order of one
+ *              line
+ *   cap        (>= 1) the first min(cap, total) components in that order are returned; total is the return value and may
+ *              exceed cap
+ *   find:      NULL is {255, 1, 1, 1, 0}.
+ *   boxes:     cap x 4 ints; pixel_counts (may be NULL): cap ints; labels (may be NULL): height x width int32, the index
+ *              of the pixel's component in the returned order, -1 for background, for filtered components and for
+ *              components beyond the cap.
+ * find_glyphs_host: host only, touches no GPU, any library: the model's plain two-pass union-find statement on an L plane
+ *       the caller already has (rows row_stride bytes apart, 0: width).  Returns total, -1 + last_error.
+ * find_glyphs: picture -> enhanced plane (opts as for classify_glyphs) -> components, on the device.  Returns total.
+ * read_glyphs: the same, then the records of the found boxes and the LFC pass on the same stream: exactly the classes
+ *       and status classify_glyphs returns for the boxes find_glyphs returns (a glyph's record is the crop of its box: a
+ *       neighbour's ink inside the box is part of it).  Returns min(cap, total) classes -- ownership, return convention,
+ *       the two times and status (may be NULL, cap ints) as classify_glyphs -- and writes *n_found = total and the boxes.
+ *       With no component the result is non-null and empty.  Two host round trips: the component list, the ink boxes.
+ * find_glyphs and read_glyphs are LFC only.  Refused before anything touches the GPU: what the glyph entry points
+ * refuse; ink_level, a reach, min_pixels, order or cap out of range; a picture of more than BNN_MI355X_FIND_MAX_PIXELS
+ * pixels (an int32 label per pixel and 16 bytes of lists per pixel on the device).
+ * last_find_usec: device time of the labelling launches (ink words .. compacted list) of the last find_glyphs /
+ *       read_glyphs call, in microseconds. */
+#define BNN_MI355X_FIND_MAX_PIXELS 16777216
+#define BNN_MI355X_FIND_MAX_REACH 16
+typedef struct {
+  int ink_level, reach_x, reach_y, min_pixels, order;
+} bnn_mi355x_find_opts;
+int bnn_mi355x_find_glyphs_host(const uint8_t *plane, int width, int height, long row_stride, const bnn_mi355x_find_opts *find,
+                                int *boxes, int *pixel_counts, int32_t *labels, int cap);
+int bnn_mi355x_find_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride,
+                           const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find, int *boxes, int *pixel_counts,
+                           int32_t *labels, int cap);
+int *bnn_mi355x_read_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride,
+                            const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find, int number_class, int cap,
+                            int *n_found, int *boxes, float *usecPerImage, float *usecPreprocess, int *status);
+float bnn_mi355x_last_find_usec(void);
+
 /* Test hook: run the stages 0..stage on n host images (n <= 32768) and copy that stage's output,
  * exactly as it sits in HBM (bit-packed activation layout), to dst.  CNV: stage L =
  * layer L (0..7, after the max-pool where there is one); LFC: stage 0 = binarised input, stage

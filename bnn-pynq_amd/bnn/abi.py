@@ -45,7 +45,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_iwecc_exposure_params", "bnn_mi355x_last_iwecc_exposure_counts", "bnn_mi355x_last_iwecc_exposure_seeds",
        "bnn_mi355x_tile_boxes", "bnn_mi355x_windows_to_cifar", "bnn_mi355x_classify_windows", "bnn_mi355x_glyph_fit",
        "bnn_mi355x_resample_coeffs", "bnn_mi355x_enhance_picture", "bnn_mi355x_glyphs_to_mnist", "bnn_mi355x_classify_glyphs",
-       "bnn_mi355x_find_glyphs_host", "bnn_mi355x_find_glyphs", "bnn_mi355x_read_glyphs", "bnn_mi355x_last_find_usec"]
+       "bnn_mi355x_find_glyphs_host", "bnn_mi355x_find_glyphs", "bnn_mi355x_read_glyphs", "bnn_mi355x_last_find_usec",
+       "bnn_mi355x_order_lines", "bnn_mi355x_page_to_mnist", "bnn_mi355x_read_page"]
 
 
 class GlyphOpts(C.Structure):
@@ -57,6 +58,11 @@ class GlyphOpts(C.Structure):
 class FindOpts(C.Structure):
     """``bnn_mi355x_find_opts``"""
     _fields_ = [("ink_level", C.c_int), ("reach_x", C.c_int), ("reach_y", C.c_int), ("min_pixels", C.c_int), ("order", C.c_int)]
+
+
+class PageOpts(C.Structure):
+    """``bnn_mi355x_page_opts``"""
+    _fields_ = [("mask", C.c_int), ("line_order", C.c_int), ("word_gap", C.c_int)]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -290,6 +296,14 @@ def declare_extensions(L):
         L.bnn_mi355x_read_glyphs.restype = ip
         L.bnn_mi355x_last_find_usec.argtypes = []
         L.bnn_mi355x_last_find_usec.restype = C.c_float
+    if hasattr(L, "bnn_mi355x_read_page"):  # (likewise)
+        op, fo, po = C.POINTER(GlyphOpts), C.POINTER(FindOpts), C.POINTER(PageOpts)
+        L.bnn_mi355x_order_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bnn_mi355x_page_to_mnist.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, op, fo, po, C.c_int, ip, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bnn_mi355x_read_page.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, op, fo, po, C.c_int, C.c_int, ip, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, fp, fp, C.c_void_p]
+        L.bnn_mi355x_read_page.restype = ip
 
 
 _cache = {}

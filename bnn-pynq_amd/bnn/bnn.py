@@ -1217,10 +1217,78 @@ class LfcClassifier:
         self.glyphs_found = found.value
         return result, boxes[:k]
 
+    # -- extension: read a page -- lines of text, every glyph masked to its own ink (csrc/page.h) -----------------------
+    def _page_call(self, symbol, img, mask, lines, word_gap, reach, min_pixels, ink_level, order, max_glyphs, opts):
+        o = self._glyph_opts(**opts)
+        f, cap = self._find_opts(reach, min_pixels, ink_level, order, max_glyphs)
+        g = abi.PageOpts(1 if mask else 0, 1 if lines else 0, int(word_gap))
+        a, bands = self._picture(img)
+        lib = self._find_entry(symbol)
+        n = max(1, min(cap, ((a.shape[1] + 1) // 2) * ((a.shape[0] + 1) // 2)))
+        return lib, a, bands, o, f, g, cap, n
+
+    def page_to_mnist(self, img, mask=True, lines=True, word_gap=0, reach=(1, 1), min_pixels=1, ink_level=255, order="left", max_glyphs=4096,
+                      **opts):
+        """the records form of :meth:`read_page` (``bnn_mi355x_page_to_mnist``): (records uint8 [n, 784] with zeros for a
+        glyph of status 2, boxes [n, 4], status [n], lines [n], gaps [n]).  Sets ``self.glyphs_found``."""
+        lib, a, bands, o, f, g, cap, n = self._page_call("bnn_mi355x_page_to_mnist", img, mask, lines, word_gap, reach, min_pixels, ink_level,
+                                                         order, max_glyphs, opts)
+        recs, boxes = np.zeros((n, 784), np.uint8), np.zeros((n, 4), np.int32)
+        status, line, gap = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        found = ctypes.c_int(0)
+        if lib.bnn_mi355x_page_to_mnist(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, ctypes.byref(o), ctypes.byref(f), ctypes.byref(g), cap,
+                                        ctypes.byref(found), boxes.ctypes.data, recs.ctypes.data, status.ctypes.data, line.ctypes.data,
+                                        gap.ctypes.data) != 0:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        k = min(found.value, cap)
+        self.glyphs_found = found.value
+        return recs[:k], boxes[:k], status[:k], line[:k], gap[:k]
+
+    def read_page(self, img, mask=True, lines=True, word_gap=0, reach=(1, 1), min_pixels=1, ink_level=255, order="left", max_glyphs=4096,
+                  **opts):
+        """(classes, boxes, lines, gaps) of the glyphs of ONE picture that may hold several lines of glyphs whose boxes
+        overlap (``bnn_mi355x_read_page``).  ``mask``: a glyph's record holds its own ink alone -- whatever else lies
+        inside its box is white -- so a neighbour's stroke, a dot inside a "0" or a speck dropped by ``min_pixels`` does
+        not move its scale and class; False is :meth:`read_glyphs`' crop of the box.  ``lines``: the glyphs come line by
+        line, top to bottom, each line left to right (``lines[i]``: the line of glyph i; a glyph joins the line whose band
+        it overlaps by half its own or the band's height); False keeps ``order``.  ``word_gap`` > 0: ``gaps[i]`` is 1
+        where glyph i starts ``word_gap`` pixels or more to the right of everything before it in its line.  The other
+        knobs are :meth:`find_glyphs`' and :meth:`_glyph_opts`'.  ``self.glyph_status`` holds the status per glyph,
+        ``self.glyphs_found`` how many there were."""
+        lib, a, bands, o, f, g, cap, n = self._page_call("bnn_mi355x_read_page", img, mask, lines, word_gap, reach, min_pixels, ink_level, order,
+                                                         max_glyphs, opts)
+        boxes, status, line, gap = np.zeros((n, 4), np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        usec, pre, found = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_int(0)
+        ptr = lib.bnn_mi355x_read_page(a.ctypes.data, a.shape[1], a.shape[0], bands, 0, ctypes.byref(o), ctypes.byref(f), ctypes.byref(g),
+                                       len(self.classes), cap, ctypes.byref(found), boxes.ctypes.data, line.ctypes.data, gap.ctypes.data,
+                                       ctypes.byref(usec), ctypes.byref(pre), status.ctypes.data)
+        if not ptr:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        k = min(found.value, cap)
+        result = np.ctypeslib.as_array(ptr, shape=(max(k, 1),))[:k].astype(np.int32, copy=True)
+        lib.free_results(ptr)
+        self.usecPerImage = self.bnn.usecPerImage = usec.value
+        self.usecPreprocess = pre.value
+        self.glyph_status = status[:k]
+        self.glyphs_found = found.value
+        return result, boxes[:k], line[:k], gap[:k]
+
     def read_text(self, img, **kwargs):
-        """what the picture says: the class names of :meth:`read_glyphs`' glyphs in order, "?" for a glyph of status 2"""
-        classes, _ = self.read_glyphs(img, **kwargs)
-        return "".join(self.class_name(c) if c >= 0 else "?" for c in classes)
+        """what the picture says: the class names of :meth:`read_glyphs`' glyphs in order, "?" for a glyph of status 2.
+        Given ``mask=``, ``lines=`` or ``word_gap=`` it reads through :meth:`read_page`: the lines joined with "\\n", a
+        " " in front of a glyph whose gap is set."""
+        if not any(k in kwargs for k in ("mask", "lines", "word_gap")):
+            classes, _ = self.read_glyphs(img, **kwargs)
+            return "".join(self.class_name(c) if c >= 0 else "?" for c in classes)
+        classes, _, lines, gaps = self.read_page(img, **kwargs)
+        text = []
+        for i, c in enumerate(classes):
+            if i and lines[i] != lines[i - 1]:
+                text.append("\n")
+            elif gaps[i]:
+                text.append(" ")
+            text.append(self.class_name(c) if c >= 0 else "?")
+        return "".join(text)
 
     def classify_image(self, img, **opts):
         """the class of the one glyph in ``img`` (a PIL image or a uint8 array): the notebooks, from the camera frame to

@@ -58,6 +58,8 @@
 #include "components.h"
 #include "glyph_kernels.h"
 #include "glyphs.h"
+#include "page.h"
+#include "page_kernels.h"
 #include "packed_params.h"
 #include "pack_inputs.h"
 #include "topology.h"
@@ -5388,6 +5390,215 @@ int *bnn_mi355x_read_glyphs(const uint8_t *pixels, int width, int height, int ba
       if (status) status[i] = plan.status[(size_t)i];
     }
     std::memcpy(boxes, found.data(), found.size() * sizeof(int));
+    float pre = 0.f, pass = 0.f;
+    HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
+    HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));
+    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
+    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
+    return 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  return result;
+}
+
+}  // extern "C"
+
+// ---- a page: lines of text, glyphs masked to their own ink (LFC; page.h) --------------------------------------------
+namespace bnn {
+namespace {
+
+static_assert(kMaxLineComponents == BNN_MI355X_PAGE_MAX_LINE_COMPONENTS, "the header states the line model's limit");
+
+PageOpts page_opts(const bnn_mi355x_page_opts *g) {
+  PageOpts o;
+  if (g) { o.mask = g->mask; o.line_order = g->line_order; o.word_gap = g->word_gap; }
+  return o;
+}
+
+struct Page {
+  std::vector<Component> chosen;             // the returned glyphs in output order
+  std::vector<int32_t> line, gap;            // per returned glyph
+  std::vector<int32_t> index, meta, found;   // uploads and boxes that outlive the enqueue
+  GlyphPlan plan;
+  long total = 0;
+};
+
+// The masked route behind the component list, with NO further round trip: descriptors, keys and tables go up in one
+// upload, then k_page_record.  Record i lands at r.d_gl_rec + i * 784.  The stream is idle when this is called (the
+// component list has just come back): growing costs no second wait.
+int enqueue_page_records(const char *what, const GlyphPicture &p, const GlyphOpts &o, Page &pg) {
+  Runtime &r = rt();
+  const size_t n = pg.chosen.size();
+  std::vector<int32_t> keys;
+  const std::string bad = plan_page(pg.chosen, o.filter, o.square_blank, pg.plan, keys);
+  if (!bad.empty()) return fail(std::string(what) + ": " + bad);
+  const size_t off_keys = n * 16, off_coef = off_keys + n * 2;
+  pg.meta.assign(off_coef + pg.plan.coef.size(), 0);
+  std::memcpy(pg.meta.data(), pg.plan.desc.data(), n * sizeof(GlyphDesc));
+  std::memcpy(pg.meta.data() + off_keys, keys.data(), keys.size() * sizeof(int32_t));
+  if (!pg.plan.coef.empty()) std::memcpy(pg.meta.data() + off_coef, pg.plan.coef.data(), pg.plan.coef.size() * sizeof(int32_t));
+  if (grow(r.d_gl_plan, r.gl_plan_cap, pg.meta.size()) || grow(r.d_gl_rec, r.gl_rec_cap, n * kGlyphRecord) ||
+      (pg.plan.tmp_bytes && grow(r.d_gl_tmp, r.gl_tmp_cap, pg.plan.tmp_bytes)))
+    return -1;
+  HIP_OK(hipMemcpyAsync(r.d_gl_plan, pg.meta.data(), pg.meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  const hipError_t e = launch_page_record(p, r.d_cc_label, reinterpret_cast<const GlyphDesc *>(r.d_gl_plan), r.d_gl_plan + off_keys,
+                                          r.d_gl_plan + off_coef, pg.plan.tmp_bytes ? r.d_gl_tmp : nullptr, r.d_gl_rec, (int)n, r.stream);
+  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  return 0;
+}
+
+// Upload, enhance, label, collect, the component list's round trip, the order (select_components' result, put into lines
+// when asked for, then the cap) and the records: k_page_record under the mask, else exactly read_glyphs' sequence on the
+// ordered boxes.  `classify`: the pass's workspaces are reserved while the stream is idle.  With no glyph nothing is
+// enqueued behind the round trip.
+int enqueue_page(const char *what, const uint8_t *pixels, int width, int height, int bands, long row_stride, const GlyphOpts &o, const FindOpts &f,
+                 const PageOpts &g, int cap, bool classify, Page &pg) {
+  Runtime &r = rt();
+  GlyphPicture p;
+  if (enqueue_glyph_plane(what, pixels, width, height, bands, row_stride, o, p) ||
+      enqueue_components(what, p, f, g.line_order ? INT_MAX : cap, nullptr, pg.chosen, pg.total, pg.index))
+    return -1;
+  if (g.line_order) {
+    std::vector<int32_t> order;
+    const std::string bad = order_lines(pg.chosen, g.word_gap, order, pg.line, pg.gap);
+    if (!bad.empty()) return fail(std::string(what) + ": " + bad);
+    const size_t n = std::min(order.size(), (size_t)cap);
+    std::vector<Component> ordered(n);
+    for (size_t i = 0; i < n; i++) ordered[i] = pg.chosen[(size_t)order[i]];
+    pg.chosen.swap(ordered);
+    pg.line.resize(n);
+    pg.gap.resize(n);
+  } else {
+    pg.line.assign(pg.chosen.size(), 0);
+    pg.gap.assign(pg.chosen.size(), 0);
+  }
+  const int n = (int)pg.chosen.size();
+  pg.found.resize((size_t)n * 4);
+  boxes_of(pg.chosen, pg.found.data(), nullptr);
+  if (n == 0) return 0;
+  if (classify && reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n)) return -1;
+  if (g.mask) return enqueue_page_records(what, p, o, pg);
+  return enqueue_glyph_records(what, p, pg.found.data(), n, o, pg.plan, pg.meta);
+}
+
+std::string validate_page_call(const char *what, const uint8_t *pixels, int width, int height, int bands, long row_stride, const GlyphOpts *o,
+                               const FindOpts &f, const PageOpts &g, const void *n_found, const void *boxes, int cap) {
+  std::string bad = validate_glyphs(what, pixels, width, height, bands, row_stride, nullptr, 0, o, n_found);
+  if (bad.empty()) bad = validate_find(what, width, height, &f, boxes, cap);
+  if (bad.empty()) bad = validate_page(what, &g);
+  return bad;
+}
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_order_lines(const int *boxes, const int *first, int n, int word_gap, int *order, int *line, int *gap) {
+  const std::string bad = validate_order_lines("order_lines", boxes, first, n, word_gap, order);
+  if (!bad.empty()) return fail(bad);
+  std::vector<Component> kept((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const int *b = boxes + 4 * (size_t)i;
+    kept[(size_t)i] = Component{first[i], b[0], b[1], b[2], b[3], 1, first[i], 0};
+  }
+  std::vector<int32_t> o, l, g;
+  const std::string refused = order_lines(kept, word_gap, o, l, g);
+  if (!refused.empty()) return fail("order_lines: " + refused);
+  for (int i = 0; i < n; i++) {
+    order[i] = o[(size_t)i];
+    if (line) line[i] = l[(size_t)i];
+    if (gap) gap[i] = g[(size_t)i];
+  }
+  return 0;
+}
+
+int bnn_mi355x_page_to_mnist(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
+                             const bnn_mi355x_find_opts *find, const bnn_mi355x_page_opts *page, int cap, int *n_found, int *boxes,
+                             uint8_t *records, int *status, int *line, int *gap) {
+  Runtime &r = rt();
+  if (r.spec.is_cnv) return fail(std::string("page_to_mnist") + kGlyphsLfcOnly);
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  const PageOpts g = page_opts(page);
+  // (two outputs of the caller's that must not be null, one test: n_found stands for both)
+  const std::string bad = validate_page_call("page_to_mnist", pixels, width, height, bands, row_stride, opts ? &o : nullptr, f, g,
+                                             records ? n_found : nullptr, boxes, cap);
+  if (!bad.empty()) return fail(bad);
+  if (bind_device()) return -1;
+  Page pg;
+  if (reserve_components(width, height, false)) return -1;
+  DrainOnFailure drain;
+  if (enqueue_page("page_to_mnist", pixels, width, height, bands, row_stride, o, f, g, cap, false, pg)) return -1;
+  const size_t n = pg.chosen.size();
+  std::vector<uint8_t> staged(n * kGlyphRecord);
+  if (n) HIP_OK(hipMemcpyAsync(staged.data(), r.d_gl_rec, staged.size(), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  *n_found = (int)pg.total;
+  for (size_t i = 0; i < n; i++) {
+    // a status-2 glyph's record stays as the caller left it
+    if (pg.plan.status[i] != kGlyphTooThin) std::memcpy(records + i * kGlyphRecord, staged.data() + i * kGlyphRecord, kGlyphRecord);
+    if (status) status[i] = pg.plan.status[i];
+    if (line) line[i] = pg.line[i];
+    if (gap) gap[i] = pg.gap[i];
+  }
+  if (n) std::memcpy(boxes, pg.found.data(), pg.found.size() * sizeof(int));
+  return 0;
+}
+
+int *bnn_mi355x_read_page(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
+                          const bnn_mi355x_find_opts *find, const bnn_mi355x_page_opts *page, int number_class, int cap, int *n_found, int *boxes,
+                          int *line, int *gap, float *usecPerImage, float *usecPreprocess, int *status) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (r.spec.is_cnv) { fail(std::string("read_page") + kGlyphsLfcOnly); return nullptr; }
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  const PageOpts g = page_opts(page);
+  const std::string bad = validate_page_call("read_page", pixels, width, height, bands, row_stride, opts ? &o : nullptr, f, g, n_found, boxes, cap);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (!ready()) return nullptr;
+  int *result = nullptr;
+  // everything that can fail from here on frees `result`
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    Page pg;
+    std::vector<uint64_t> words;
+    if (reserve_components(width, height, false)) return -1;
+    for (hipEvent_t &e : r.gl_ev)
+      if (!e) HIP_OK(hipEventCreate(&e));
+    const bool on_device = number_class <= 47;  // (as classify_glyphs)
+    DrainOnFailure drain;
+    HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
+    if (enqueue_page("read_page", pixels, width, height, bands, row_stride, o, f, g, cap, true, pg)) return -1;
+    const int n = (int)pg.chosen.size();
+    result = new (std::nothrow) int[(size_t)(n > 0 ? n : 1)];
+    if (!result) return fail("out of memory");
+    *n_found = (int)pg.total;
+    if (n == 0) {  // nothing to read: a non-null, empty result
+      HIP_OK(hipStreamSynchronize(r.stream));
+      drain.ok();
+      return 0;
+    }
+    if (!on_device) words.resize((size_t)n);
+    HIP_OK(hipEventRecord(r.gl_ev[1], r.stream));
+    if (bnn_mi355x_inference_device(r.d_gl_rec, n, number_class, on_device ? r.d_classes : nullptr, nullptr, r.d_words, r.stream)) return -1;
+    HIP_OK(hipEventRecord(r.gl_ev[2], r.stream));
+    if (on_device) HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(words.data(), r.d_words, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    for (int i = 0; i < n; i++) {
+      if (!on_device) result[i] = lfc_class_batched(words[(size_t)i], number_class);
+      if (pg.plan.status[(size_t)i] == kGlyphTooThin) result[i] = -1;  // its record was never written
+      if (status) status[i] = pg.plan.status[(size_t)i];
+      if (line) line[i] = pg.line[(size_t)i];
+      if (gap) gap[i] = pg.gap[(size_t)i];
+    }
+    std::memcpy(boxes, pg.found.data(), pg.found.size() * sizeof(int));
     float pre = 0.f, pass = 0.f;
     HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
     HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));

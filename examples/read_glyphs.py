@@ -53,3 +53,23 @@ edges = np.flatnonzero(np.diff(np.concatenate([[0], ink_columns.astype(np.int8),
 split = [(int(a), int(b)) for a, b in zip(edges[::2], edges[1::2])]
 found = [(int(b[0]), int(b[2])) for b in boxes]
 print("x-ranges of the found boxes %s the column split's: %s" % ("equal" if found == split else "DIFFER from", found))
+
+# A page: two lines, and two strokes whose boxes overlap.  read_glyphs would interleave the lines by x and hand the net
+# each stroke with a piece of the other in its record; read_page puts the glyphs into lines (a glyph joins the line whose
+# band it overlaps by half), marks the word gaps, and masks every glyph to its own ink.
+page = Image.new("RGB", (40 + 50 * len(digits) + 130, 200), (238, 236, 230))
+draw = ImageDraw.Draw(page)
+for j, row in enumerate((digits, digits[::-1])):
+    for i, ch in enumerate(row):
+        draw.text((30 + 50 * i + (40 if i >= 3 else 0), 12 + 100 * j), ch, font=font, fill=(25, 25, 40))
+x = 40 + 50 * len(digits) + 45
+draw.line((x, 80, x + 40, 20), fill=(25, 25, 40), width=5)        # a "/" ...
+draw.line((x + 34, 45, x + 62, 95), fill=(25, 25, 40), width=5)   # ... and a "\\" under its arm: they do not touch, their boxes overlap
+classes, boxes, lines, gaps = classifier.read_page(page, word_gap=40)
+print("a page of %d glyphs in %d lines, read line by line with the glyphs masked to their own ink:" % (len(boxes), len(set(lines.tolist()))))
+print(classifier.read_text(page, mask=True, lines=True, word_gap=40))
+cropped, _, _, _ = classifier.read_page(page, mask=False, word_gap=40)
+changed = [i for i in range(len(boxes)) if classes[i] != cropped[i]]
+print("glyphs whose class differs when a neighbour's ink stays in the record (mask=False): %s"
+      % (", ".join("%d at x %d..%d" % (i, boxes[i][0], boxes[i][2]) for i in changed) or "none"))
+print("read_glyphs' order on the same page, by left edge alone:", classifier.read_text(page))

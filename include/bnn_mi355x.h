@@ -899,6 +899,59 @@ int *bnn_mi355x_read_glyphs(const uint8_t *pixels, int width, int height, int ba
                             int *n_found, int *boxes, float *usecPerImage, float *usecPreprocess, int *status);
 float bnn_mi355x_last_find_usec(void);
 
+/* Read a page: lines of text, every glyph masked to its own ink.  read_glyphs reads ONE line of glyphs whose boxes do
+ * not touch; these entry points lift both limits.  The reference has no segmentation; like the labelling above, the
+ * model is this project's own (csrc/page.h):
+ *   mask = 1   Glyph g is a component find returned.  Its picture is the enhanced plane with every pixel that does not
+ *              belong to component g replaced by 255: other components, filtered components, components beyond the cap,
+ *              and background, grey values in [ink_level, 255) included.  Steps 5-8 run on that picture with g's box as
+ *              the box.  Every member pixel is < ink_level <= 255, so the ink box IS the component's box: status 1
+ *              cannot occur; status 2 and square_blank work as before.  Slanted strokes, a dot inside a "0" or a speck
+ *              dropped by min_pixels no longer move a neighbour's ink box, scale and class.
+ *   mask = 0   read_glyphs' crop rule: whatever lies inside the box is part of the record.
+ *   line_order = 1   The components kept by min_pixels (before the cap), each with box (l, u, r, b) and first pixel f,
+ *              are visited in ascending (u, f).  Each line has a band [top, bottom).  For a visited component of height
+ *              h = b - u and each existing line, ov = min(b, bottom) - max(u, top); the component joins the line with
+ *              the largest ov among the lines with 2 ov >= min(h, bottom - top), on a tie the line created first, and
+ *              the band's bottom becomes max(bottom, b) (the top never moves, because of the visiting order).  If no
+ *              line qualifies it opens a new line [u, b).  Lines are numbered in creation order (ascending top); inside
+ *              a line the glyphs go in ascending (l, u, f); the output is line 0, then line 1, ...; the cap takes the
+ *              first min(cap, total) in that order.  find->order is not used (it must still be 0 or 1).  More than
+ *              BNN_MI355X_PAGE_MAX_LINE_COMPONENTS kept components are refused -- the one refusal that needs the
+ *              labelling's answer, so it comes after the device has worked: raise min_pixels.  Known limit: a dot above a
+ *              stem is a line of its own unless reach_y joins it to the stem.
+ *   line_order = 0   find->order, as read_glyphs; every line[i] and gap[i] is 0, a word_gap above 0 is refused.
+ *   word_gap   gap[i] = 1 iff word_gap > 0, glyph i is not the first of its line and l_i - max(r of the earlier glyphs of
+ *              its line) >= word_gap; else 0.
+ *   page:      NULL is {1, 1, 0}.
+ *   line[i], gap[i]: of output glyph i; cap ints each, either may be NULL.
+ * order_lines: host only, touches no GPU, any library: the line model on n boxes the caller has (boxes: n x 4, first: n
+ *       ints, ties in (u, f) or (l, u, f) go by input index).  order[i] = the input index of output glyph i; line and gap
+ *       may be NULL.  Returns 0, -1 + last_error (null pointers, a negative n or word_gap, an empty or inverted box, n
+ *       above BNN_MI355X_PAGE_MAX_LINE_COMPONENTS).
+ * page_to_mnist: records to the host (tests, display): min(cap, total) x 784 bytes, a status-2 glyph's record stays as
+ *       the caller left it; *n_found = total; boxes: cap x 4; status (may be NULL): cap ints.  Returns 0, -1.
+ * read_page: LFC only; the records stay in HBM and the LFC pass runs on them on the same stream.  Return convention,
+ *       ownership, the two times and status as read_glyphs.  Under the mask: upload, enhance, label, collect, ONE host
+ *       round trip (the component list down; descriptors, keys and tables up), the record kernel
+ *       (csrc/page_kernels.hip), the pass -- no ink-box launch, no second round trip.  Without the mask: exactly
+ *       read_glyphs' sequence on the ordered boxes; with page = {0, 0, 0} exactly read_glyphs.
+ * Refused before anything touches the GPU: what read_glyphs refuses; a mask or line_order other than 0 / 1; a negative
+ * word_gap; a word_gap without line_order.  last_find_usec covers these calls too. */
+#define BNN_MI355X_PAGE_MAX_LINE_COMPONENTS 65536
+typedef struct {
+  int mask, line_order, word_gap;
+} bnn_mi355x_page_opts;
+int bnn_mi355x_order_lines(const int *boxes, const int *first, int n, int word_gap, int *order, int *line, int *gap);
+int bnn_mi355x_page_to_mnist(const uint8_t *pixels, int width, int height, int bands, long row_stride,
+                             const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find,
+                             const bnn_mi355x_page_opts *page, int cap, int *n_found, int *boxes, uint8_t *records, int *status,
+                             int *line, int *gap);
+int *bnn_mi355x_read_page(const uint8_t *pixels, int width, int height, int bands, long row_stride,
+                          const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find,
+                          const bnn_mi355x_page_opts *page, int number_class, int cap, int *n_found, int *boxes, int *line,
+                          int *gap, float *usecPerImage, float *usecPreprocess, int *status);
+
 /* Test hook: run the stages 0..stage on n host images (n <= 32768) and copy that stage's output,
  * exactly as it sits in HBM (bit-packed activation layout), to dst.  CNV: stage L =
  * layer L (0..7, after the max-pool where there is one); LFC: stage 0 = binarised input, stage

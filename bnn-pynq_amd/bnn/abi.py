@@ -46,7 +46,9 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_tile_boxes", "bnn_mi355x_windows_to_cifar", "bnn_mi355x_classify_windows", "bnn_mi355x_glyph_fit",
        "bnn_mi355x_resample_coeffs", "bnn_mi355x_enhance_picture", "bnn_mi355x_glyphs_to_mnist", "bnn_mi355x_classify_glyphs",
        "bnn_mi355x_find_glyphs_host", "bnn_mi355x_find_glyphs", "bnn_mi355x_read_glyphs", "bnn_mi355x_last_find_usec",
-       "bnn_mi355x_order_lines", "bnn_mi355x_page_to_mnist", "bnn_mi355x_read_page"]
+       "bnn_mi355x_order_lines", "bnn_mi355x_page_to_mnist", "bnn_mi355x_read_page", "bnn_mi355x_scan_grid",
+       "bnn_mi355x_scan_boxes", "bnn_mi355x_scan_planes", "bnn_mi355x_scan_device", "bnn_mi355x_scan_scene",
+       "bnn_mi355x_debug_scan_stage", "bnn_mi355x_scan_resize"]
 
 
 class GlyphOpts(C.Structure):
@@ -304,6 +306,19 @@ def declare_extensions(L):
         L.bnn_mi355x_read_page.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, op, fo, po, C.c_int, C.c_int, ip, C.c_void_p,
                                            C.c_void_p, C.c_void_p, fp, fp, C.c_void_p]
         L.bnn_mi355x_read_page.restype = ip
+    if hasattr(L, "bnn_mi355x_scan_scene"):  # (likewise)
+        L.bnn_mi355x_scan_grid.argtypes = [C.c_int, C.c_int, ip, ip]
+        L.bnn_mi355x_scan_boxes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, ip, ip]
+        L.bnn_mi355x_scan_boxes.restype = C.c_long
+        L.bnn_mi355x_scan_planes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, ip, fp, C.c_int]
+        L.bnn_mi355x_scan_planes.restype = ip
+        L.bnn_mi355x_scan_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bnn_mi355x_scan_scene.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_void_p, fp, fp,
+                                            C.c_int]
+        L.bnn_mi355x_scan_scene.restype = ip
+        L.bnn_mi355x_debug_scan_stage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, ip, ip]
+        L.bnn_mi355x_debug_scan_stage.restype = C.c_long
+        L.bnn_mi355x_scan_resize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
 
 
 _cache = {}

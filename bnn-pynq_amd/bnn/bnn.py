@@ -895,9 +895,105 @@ class CnvClassifier:
         """what :meth:`classify_images_details` returns for the crops: ``len(classes)`` scores per window"""
         return self._classify_windows(img, boxes, True)
 
-    def locate(self, img, class_index, sizes=(64, 96), min_score=None):
+    # -- extension: the dense scan -- every 32 x 32 window at stride 4 from one pass over the picture ----------
+    def _scan_lib(self):
+        """the library when it scans on the device (cnvW1A1 with the ``bnn_mi355x_scan_*`` symbols), else None"""
+        lib = self.bnn.interface
+        if hasattr(lib, "bnn_mi355x_scan_scene") and lib.bnn_mi355x_network().decode().split("-")[0] == NETWORK_CNVW1A1:
+            return lib
+        return None
+
+    @staticmethod
+    def _as_pil(img):
+        return Image.fromarray(img) if isinstance(img, np.ndarray) else img
+
+    @staticmethod
+    def _planes(pil):
+        """planar uint8 [3, H, W] as a window's record holds the picture (L: the grey plane three times)"""
+        if pil.mode == "L":
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(pil)[None], (3,) + pil.size[::-1]))
+        a = np.asarray(pil if pil.mode == "RGB" else pil.convert("RGBA"))[:, :, :3]
+        return np.ascontiguousarray(a.transpose(2, 0, 1))
+
+    def _scan_planes(self, planes, details):
+        """[ny, nx] classes or [ny, nx, len(classes)] scores of a planar picture"""
+        _, h, w = planes.shape
+        if w < 32 or h < 32:
+            raise ValueError("scan: need a picture of 32 x 32 pixels or more")
+        nx, ny = (w - 32) // 4 + 1, (h - 32) // 4 + 1
+        ncls = len(self.classes)
+        lib = self._scan_lib()
+        if lib is None:  # the same records through the per-window pass: the same answers by construction
+            recs = np.stack([planes[:, 4 * j:4 * j + 32, 4 * i:4 * i + 32].reshape(3072) for j in range(ny) for i in range(nx)])
+            res = np.asarray(self.classify_array(recs, detail=details))
+        else:
+            gx, gy, usec = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_float(0)
+            ptr = lib.bnn_mi355x_scan_planes(planes.ctypes.data, w, h, ncls, ctypes.byref(gx), ctypes.byref(gy), ctypes.byref(usec),
+                                             1 if details else 0)
+            if not ptr:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            res = self.bnn._collect(ptr, nx * ny * (ncls if details else 1))
+            self.usecPerImage = self.bnn.usecPerImage = usec.value
+        return res.reshape((ny, nx, ncls) if details else (ny, nx))
+
+    def scan(self, img, details=False):
+        """the class (or, with ``details``, the ``len(classes)`` scores) of EVERY 32 x 32 window of ``img`` at stride 4:
+        entry [j, i] is what :meth:`classify_array` returns for the record cut at columns 4i .. 4i + 31, rows 4j .. 4j + 31,
+        computed from one pass over the whole picture (``bnn_mi355x_scan_planes``; cnvW1A1).  Other networks and libraries
+        without the entry point classify the cut records one by one."""
+        return self._scan_planes(self._planes(self._as_pil(img)), details)
+
+    @staticmethod
+    def scan_boxes(size, window):
+        """the level and the boxes of ONE window size ``window`` (8 or more, a multiple of 8) of a picture of ``size`` =
+        (width, height): ((level_w, level_h), int32 array [n, 4]) -- the picture is resized to the level, ``width * 32 //
+        window`` x ``height * 32 // window``, and cell (i, j) of the level's scan is the window (i w/8, j w/8, i w/8 + w, j w/8 + w)"""
+        width, height = size
+        if window < 8 or window % 8:
+            raise ValueError("scan_boxes: the window size must be a multiple of 8 (8 or more)")
+        lw, lh = width * 32 // window, height * 32 // window
+        if lw < 32 or lh < 32:
+            raise ValueError("scan_boxes: window size %d leaves a level below 32 x 32 pixels" % window)
+        nx, ny, step = (lw - 32) // 4 + 1, (lh - 32) // 4 + 1, window // 8
+        left, upper = np.meshgrid(np.arange(nx) * step, np.arange(ny) * step)
+        b = np.stack([left, upper, left + window, upper + window], axis=-1).reshape(-1, 4).astype(np.int32)
+        return (lw, lh), b
+
+    def scan_scene(self, img, sizes=(64, 96), details=False):
+        """a pyramid of dense scans: for each window size in ``sizes`` (size-major) the picture is resized like
+        ``img.resize(level, Image.LANCZOS)`` and scanned (:meth:`scan`) -> (boxes int32 [n, 4] in the picture's coordinates,
+        classes [n] or scores [n, len(classes)]).  On cnvW1A1 one upload and one stream (``bnn_mi355x_scan_scene``: RGB and L
+        pictures); otherwise PIL resizes on the host."""
+        pil = self._as_pil(img)
+        ncls = len(self.classes)
+        levels = [self.scan_boxes(pil.size, s) for s in sizes]
+        boxes = np.concatenate([b for _, b in levels]) if levels else np.zeros((0, 4), np.int32)
+        lib = self._scan_lib()
+        if lib is None or pil.mode not in ("RGB", "L"):
+            res = [self._scan_planes(self._planes(pil.resize(lv, Image.LANCZOS)), details).reshape((-1, ncls) if details else -1)
+                   for lv, _ in levels]
+            return boxes, (np.concatenate(res) if res else np.zeros((0, ncls) if details else 0, np.int32))
+        a = np.ascontiguousarray(np.asarray(pil))
+        sz = np.asarray(sizes, dtype=np.int32)
+        out = np.zeros((len(boxes), 4), np.int32)
+        usec, pre = ctypes.c_float(0), ctypes.c_float(0)
+        ptr = lib.bnn_mi355x_scan_scene(a.ctypes.data, a.shape[1], a.shape[0], 1 if a.ndim == 2 else 3, 0, sz.ctypes.data, len(sz), ncls,
+                                        out.ctypes.data, ctypes.byref(usec), ctypes.byref(pre), 1 if details else 0)
+        if not ptr:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        res = self.bnn._collect(ptr, len(boxes) * (ncls if details else 1))
+        self.usecPerImage = self.bnn.usecPerImage = usec.value
+        self.usecPreprocess = pre.value
+        return out, (res.reshape(-1, ncls) if details else res)
+
+    def locate(self, img, class_index, sizes=(64, 96), min_score=None, dense=False):
         """cells 14 and 16: the windows of the notebook's tiling (:meth:`tile_boxes`) whose class is ``class_index`` -- or,
-        with ``min_score``, those whose score for ``class_index`` exceeds it -> list of (left, upper, right, lower)"""
+        with ``min_score``, those whose score for ``class_index`` exceeds it -> list of (left, upper, right, lower).
+        ``dense``: the windows of :meth:`scan_scene` instead, a stride twice as fine in each direction (``size // 8``)."""
+        if dense:
+            boxes, res = self.scan_scene(img, sizes, details=min_score is not None)
+            hit = (res == class_index) if min_score is None else (res[:, class_index] > min_score)
+            return [tuple(int(v) for v in b) for b, h in zip(boxes, hit) if h]
         size = (img.shape[1], img.shape[0]) if isinstance(img, np.ndarray) else img.size
         bounds = self.tile_boxes(size, sizes)
         if not bounds:

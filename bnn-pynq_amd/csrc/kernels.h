@@ -31,6 +31,9 @@ struct CnvLaunch {
   // sets to done_seq behind its results -- the host spins on it; no t0 / t1 packets are queued then
   unsigned *done_flag;
   unsigned done_seq;
+  // run stages first_stage..last_stage only: stage k > 0 reads stage k-1's output where the full pass leaves it
+  // (stage_output_bytes).  The dense scan (scan_kernels.h) enters at stage 6, on the layer-5 map of a whole picture.
+  int first_stage = 0;
 };
 
 struct LfcLaunch {

@@ -3462,12 +3462,12 @@ void run_cnv_t(const CnvLaunch &a) {
     // throughput form (images staged in LDS, a block per kL0Imgs images) once its grid fills the chip; below
     // that the lane-per-pixel form, whose 15 waves per image spread over the CUs
     const dim3 g0((unsigned)((n * 900 + kBlock - 1) / kBlock));  // lane = pixel
-    if (a.last_stage >= 0) {
+    if (a.first_stage <= 0 && a.last_stage >= 0) {
       if (n >= l0_tile_min()) BNN_LAUNCH((k_conv0_tile<OUT2>), dim3((unsigned)((n + kL0Imgs - 1) / kL0Imgs)), s, a.images, A, a.l0_mfma, (int)n);
       else BNN_LAUNCH((k_conv0_mfma<OUT2>), g0, s, a.images, A, a.l0_mfma, (int)(n * 900));
     }
   } else {
-    if (a.last_stage >= 0) BNN_LAUNCH((k_conv0<OUT2>), grid_for(n * 900, 2 / gpb_for(n * 900, 2)), s, a.images, A, a.rows[0], (int)(n * 900), 2, gpb_for(n * 900, 2));
+    if (a.first_stage <= 0 && a.last_stage >= 0) BNN_LAUNCH((k_conv0<OUT2>), grid_for(n * 900, 2 / gpb_for(n * 900, 2)), s, a.images, A, a.rows[0], (int)(n * 900), 2, gpb_for(n * 900, 2));
   }
   BNN_MARK(a.events, 1, s);
   if constexpr (ARITH == AR_XNOR && !OUT2) {
@@ -3479,7 +3479,7 @@ void run_cnv_t(const CnvLaunch &a) {
     const uint8_t *const cm = conv_mfma_for<ARITH, OUT2>(a);
     const dim3 g1(persistent_grid((n + kConvMfmaImgsL1 - 1) / kConvMfmaImgsL1, kConvMfmaGrid)),
         gm(persistent_grid((n + kConvMfmaImgs - 1) / kConvMfmaImgs, kConvMfmaGrid));
-    if (a.last_stage >= 1) {
+    if (a.first_stage <= 1 && a.last_stage >= 1) {
       if (a.l1_literal) {  // comparison figure (BNN_MI355X_L1=lds): the north-star's wording, untuned
         BNN_LAUNCH(k_l1_literal, dim3((unsigned)((n * 784 + kBlock - 1) / kBlock)), s, A64, reinterpret_cast<uint64_t *>(B), a.rows[1], (int)(n * 784));
       } else if (a.l1_mfma) {  // side experiment (BNN_MI355X_L1=mfma): the layer on the matrix pipe
@@ -3493,13 +3493,13 @@ void run_cnv_t(const CnvLaunch &a) {
       else BNN_STAGE((k_quad_x<1, 30, true>), (k_quad_x<1, 30, true, 8>), n * 196, 2, A64, B, a.rows[1]);
     }
     BNN_MARK(a.events, 2, s);
-    if (a.last_stage >= 2) {
+    if (a.first_stage <= 2 && a.last_stage >= 2) {
       if (cm) hipLaunchKernelGGL((k_conv_mfma<14, 2, 4, false, kConvMfmaImgs>), gm, dim3(256), 0, s, B, A, cm + kConvMfmaL2Off, (int)n);
       else if (pix) BNN_LAUNCH((k_vec_x<9, true, 1, 14, 8>), grid_for(n * 144, 16), s, B64, A, a.rows[2], (int)(n * 144), 16, 1);
       else BNN_STAGE((k_quad_x<1, 14, false>), (k_quad_x<1, 14, false, 8>), n * 36, 4, B64, A, a.rows[2]);
     }
     BNN_MARK(a.events, 3, s);
-    if (a.last_stage >= 3) {
+    if (a.first_stage <= 3 && a.last_stage >= 3) {
       if (cm) hipLaunchKernelGGL((k_conv_mfma<12, 4, 4, true, kConvMfmaImgs>), gm, dim3(256), 0, s, A, B, cm + kConvMfmaL3Off, (int)n);
       else if (pix) BNN_LAUNCH((k_vec_x<18, true, 2, 12, 8, true>), grid_for(n * 100, 16), s, A64, B, a.rows[3], (int)(n * 100), 16, 1);
       else BNN_STAGE((k_quad_x<2, 12, true>), (k_quad_x<2, 12, true, 8>), n * 25, 4, A64, B, a.rows[3]);
@@ -3508,28 +3508,28 @@ void run_cnv_t(const CnvLaunch &a) {
     // the matrix forms of layers 4-7; from their edge on they go before the one-launch tail too
     const uint8_t *const tm = tail_mfma_for<ARITH>(a);
     const uint32_t *const A32 = A, *const B32 = B;
-    if (!tm && n <= kCnvTailMax && !a.events && a.last_stage >= kCnvStages - 1) {
+    if (!tm && n <= kCnvTailMax && !a.events && a.first_stage <= 4 && a.last_stage >= kCnvStages - 1) {
       // small batch: layers 4..8 as one launch (no per-stage events there: there are no stages)
       hipLaunchKernelGGL(k_cnv_tail, dim3((unsigned)n), dim3(512), 0, s, B64, a.scores, a.classes, a.rows[4], a.rows[5], a.rows[6],
                          a.rows[7], a.rows[8], a.number_class, n == 1 ? a.done_flag : nullptr, a.done_seq);
       return;
     }
-    if (a.last_stage >= 4) {
+    if (a.first_stage <= 4 && a.last_stage >= 4) {
       if (tm && (kTailMfmaStages & 16)) BNN_TAIL_MFMA(false, 18, 8, true, 8, kTailMfmaImgsL4, kTailMfmaGrid8, B32, A, tm + kTailMfmaL4Off);
       else BNN_STAGE((k_vec_x<18, true, 2, 5>), (k_vec_x<18, true, 2, 5, 8>), n * 9, 8, B64, A, a.rows[4]);
     }
     BNN_MARK(a.events, 5, s);
-    if (a.last_stage >= 5) {
+    if (a.first_stage <= 5 && a.last_stage >= 5) {
       if (tm && (kTailMfmaStages & 32)) BNN_TAIL_MFMA(false, 36, 8, false, 8, kTailMfmaImgsL5, kTailMfmaGrid8, A32, B, tm + kTailMfmaL5Off);
       else BNN_STAGE((k_vec_x<36, false, 1, 1>), (k_vec_x<36, false, 1, 1, 8>), n, 8, A64, B, a.rows[5]);
     }
     BNN_MARK(a.events, 6, s);
-    if (a.last_stage >= 6) {
+    if (a.first_stage <= 6 && a.last_stage >= 6) {
       if (tm && (kTailMfmaStages & 64)) BNN_TAIL_MFMA(false, 4, 16, false, 4, kTailMfmaImgsFc, kConvMfmaGrid, B32, A, tm + kTailMfmaL6Off);
       else BNN_STAGE((k_vec_x<4, false, 1, 1>), (k_vec_x<4, false, 1, 1, 8>), n, 16, B64, A, a.rows[6]);
     }
     BNN_MARK(a.events, 7, s);
-    if (a.last_stage >= 7) {
+    if (a.first_stage <= 7 && a.last_stage >= 7) {
       if (tm && (kTailMfmaStages & 128)) BNN_TAIL_MFMA(false, 8, 16, false, 8, kTailMfmaImgsFc, kTailMfmaGrid8, A32, B, tm + kTailMfmaL7Off);
       else BNN_STAGE((k_vec_x<8, false, 1, 1>), (k_vec_x<8, false, 1, 1, 8>), n, 16, A64, B, a.rows[7]);
     }
@@ -3541,19 +3541,19 @@ void run_cnv_t(const CnvLaunch &a) {
     const uint4 *const A128 = reinterpret_cast<const uint4 *>(a.buf0), *const B128 = reinterpret_cast<const uint4 *>(a.buf1);
     const dim3 g1(persistent_grid((n + kConvMfmaImgsL1 - 1) / kConvMfmaImgsL1, kConvMfmaGrid)),
         gm(persistent_grid((n + kConvMfmaImgs - 1) / kConvMfmaImgs, kConvMfmaGrid));
-    if (a.last_stage >= 1) {
+    if (a.first_stage <= 1 && a.last_stage >= 1) {
       if (cm) hipLaunchKernelGGL((k_conv_mfma_a2<30, 2, 2, true, kConvMfmaImgsL1>), g1, dim3(256), 0, s, A128, B, cm, (int)n);
       else if (pix) BNN_LAUNCH((k_vec<ARITH, 9, OUT2, true, 1, 30, 8, true, TWO>), grid_for(n * 784, 8), s, A64, B, a.rows[1], (int)(n * 784), 8, 1);
       else BNN_STAGE((k_quad<ARITH, 1, 30, true, OUT2, 32, TWO>), (k_quad<ARITH, 1, 30, true, OUT2, 8, TWO>), n * 196, 2, A64, B, a.rows[1]);
     }
     BNN_MARK(a.events, 2, s);
-    if (a.last_stage >= 2) {
+    if (a.first_stage <= 2 && a.last_stage >= 2) {
       if (cm) hipLaunchKernelGGL((k_conv_mfma_a2<14, 2, 4, false, kConvMfmaImgs>), gm, dim3(256), 0, s, B128, A, cm + kConvMfmaA2L2Off, (int)n);
       else if (pix) BNN_LAUNCH((k_vec<ARITH, 9, OUT2, true, 1, 14, 8, false, TWO>), grid_for(n * 144, 16), s, B64, A, a.rows[2], (int)(n * 144), 16, 1);
       else BNN_STAGE((k_quad<ARITH, 1, 14, false, OUT2, 32, TWO>), (k_quad<ARITH, 1, 14, false, OUT2, 8, TWO>), n * 36, 4, B64, A, a.rows[2]);
     }
     BNN_MARK(a.events, 3, s);
-    if (a.last_stage >= 3) {
+    if (a.first_stage <= 3 && a.last_stage >= 3) {
       if (cm) hipLaunchKernelGGL((k_conv_mfma_a2<12, 4, 4, true, kConvMfmaImgs>), gm, dim3(256), 0, s, A128, B, cm + kConvMfmaA2L3Off, (int)n);
       else if (pix) BNN_LAUNCH((k_vec<ARITH, 18, OUT2, true, 2, 12, 8, true, TWO>), grid_for(n * 100, 16), s, A64, B, a.rows[3], (int)(n * 100), 16, 1);
       else BNN_STAGE((k_quad<ARITH, 2, 12, true, OUT2, 32, TWO>), (k_quad<ARITH, 2, 12, true, OUT2, 8, TWO>), n * 25, 4, A64, B, a.rows[3]);
@@ -3562,34 +3562,34 @@ void run_cnv_t(const CnvLaunch &a) {
     // the matrix forms of layers 4-7, as in the XNOR branch
     const uint8_t *const tm = tail_mfma_for<ARITH>(a);
     if constexpr (!TWO) {  // (the -2-aware variant of this kernel would spill: such runs take the staged layers)
-      if (!tm && n <= kCnvTailMax && !a.events && a.last_stage >= kCnvStages - 1) {
+      if (!tm && n <= kCnvTailMax && !a.events && a.first_stage <= 4 && a.last_stage >= kCnvStages - 1) {
         hipLaunchKernelGGL((k_cnv_tail_a2<ARITH>), dim3((unsigned)n), dim3(512), 0, s, B64, a.scores, a.classes, a.rows[4], a.rows[5],
                            a.rows[6], a.rows[7], a.rows[8], a.number_class, n == 1 ? a.done_flag : nullptr, a.done_seq);
         return;
       }
     }
-    if (a.last_stage >= 4) {
+    if (a.first_stage <= 4 && a.last_stage >= 4) {
       if (tm && (kTailMfmaStages & 16)) BNN_TAIL_MFMA(true, 18, 8, true, 8, kTailMfmaImgsL4, kTailMfmaGrid8, B128, A, tm + kTailMfmaA2L4Off);
       else BNN_STAGE((k_vec<ARITH, 18, OUT2, true, 2, 5, 32, false, TWO>), (k_vec<ARITH, 18, OUT2, true, 2, 5, 8, false, TWO>), n * 9, 8, B64, A, a.rows[4]);
     }
     BNN_MARK(a.events, 5, s);
-    if (a.last_stage >= 5) {
+    if (a.first_stage <= 5 && a.last_stage >= 5) {
       if (tm && (kTailMfmaStages & 32)) BNN_TAIL_MFMA(true, 36, 8, false, 8, kTailMfmaImgsL5, kTailMfmaGrid8, A128, B, tm + kTailMfmaA2L5Off);
       else BNN_STAGE((k_vec<ARITH, 36, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 36, OUT2, false, 1, 1, 8, false, TWO>), n, 8, A64, B, a.rows[5]);
     }
     BNN_MARK(a.events, 6, s);
-    if (a.last_stage >= 6) {
+    if (a.first_stage <= 6 && a.last_stage >= 6) {
       if (tm && (kTailMfmaStages & 64)) BNN_TAIL_MFMA(true, 4, 16, false, 4, kTailMfmaImgsFc, kConvMfmaGrid, B128, A, tm + kTailMfmaA2L6Off);
       else BNN_STAGE((k_vec<ARITH, 4, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 4, OUT2, false, 1, 1, 8, false, TWO>), n, 16, B64, A, a.rows[6]);
     }
     BNN_MARK(a.events, 7, s);
-    if (a.last_stage >= 7) {
+    if (a.first_stage <= 7 && a.last_stage >= 7) {
       if (tm && (kTailMfmaStages & 128)) BNN_TAIL_MFMA(true, 8, 16, false, 8, kTailMfmaImgsFc, kTailMfmaGrid8, A128, B, tm + kTailMfmaA2L7Off);
       else BNN_STAGE((k_vec<ARITH, 8, OUT2, false, 1, 1, 32, false, TWO>), (k_vec<ARITH, 8, OUT2, false, 1, 1, 8, false, TWO>), n, 16, A64, B, a.rows[7]);
     }
     BNN_MARK(a.events, 8, s);
   }
-  if (a.last_stage >= 8) {
+  if (a.first_stage <= 8 && a.last_stage >= 8) {
     if (n <= kFcLastWaveMax) BNN_LAUNCH((k_fclast_wave<ARITH, 8, TWO>), dim3((unsigned)((n + 3) / 4)), s, B64, a.scores, a.classes, a.rows[8], (int)n, a.number_class);
     else BNN_LAUNCH((k_fclast<ARITH, 8, TWO>), grid_for(n, 1), s, B64, a.scores, a.classes, a.rows[8], (int)n, a.number_class);
   }

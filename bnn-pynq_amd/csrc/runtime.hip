@@ -54,6 +54,8 @@
 #include "resample.h"
 #include "window_kernels.h"
 #include "windows.h"
+#include "scan_kernels.h"
+#include "scan.h"
 #include "component_kernels.h"
 #include "components.h"
 #include "glyph_kernels.h"
@@ -326,6 +328,13 @@ struct Runtime {
   uint8_t *d_win_scene = nullptr, *d_win_body = nullptr;
   int32_t *d_win_meta = nullptr;
   hipEvent_t win_ev[3] = {nullptr, nullptr, nullptr};
+  // the dense scan (bnn_mi355x_scan_*; scan.h): the planar picture (or a level's), the interleaved scene of scan_scene, the
+  // first resize pass's output, the levels' coefficient tables (one upload), the two map buffers; time stamps around every
+  // resize and every scan of a call
+  size_t scan_planes_cap = 0, scan_scene_cap = 0, scan_tmp_cap = 0, scan_coef_cap = 0, scan_buf0_cap = 0, scan_buf1_cap = 0;
+  uint8_t *d_scan_planes = nullptr, *d_scan_scene = nullptr, *d_scan_tmp = nullptr, *d_scan_buf0 = nullptr, *d_scan_buf1 = nullptr;
+  int32_t *d_scan_coef = nullptr;
+  std::vector<hipEvent_t> scan_ev;
   // one picture and N boxes -> MNIST-format records / classes (bnn_mi355x_enhance_picture, bnn_mi355x_glyphs_to_mnist,
   // bnn_mi355x_classify_glyphs; LFC): the picture, its L plane, boxes + found ink boxes, descriptors + tables, the global
   // temporary of glyphs past the LDS budget, the 784-byte records, the plane's pixel sum; time stamps as win_ev
@@ -495,7 +504,7 @@ int upload_blob() {
 
 void free_workspace() {
   Runtime &r = rt();
-  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.gl_src_cap && !r.gl_plane_cap && !r.gl_box_cap && !r.gl_plan_cap && !r.gl_tmp_cap && !r.gl_rec_cap && !r.gl_sum_cap && !r.cc_bits_cap && !r.cc_label_cap && !r.cc_stat_cap && !r.cc_list_cap && !r.cc_index_cap && !r.cc_out_cap && !r.file_cap && !r.all_cap && !r.h_io &&
+  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.scan_planes_cap && !r.scan_scene_cap && !r.scan_tmp_cap && !r.scan_coef_cap && !r.scan_buf0_cap && !r.scan_buf1_cap && !r.gl_src_cap && !r.gl_plane_cap && !r.gl_box_cap && !r.gl_plan_cap && !r.gl_tmp_cap && !r.gl_rec_cap && !r.gl_sum_cap && !r.cc_bits_cap && !r.cc_label_cap && !r.cc_stat_cap && !r.cc_list_cap && !r.cc_index_cap && !r.cc_out_cap && !r.file_cap && !r.all_cap && !r.h_io &&
       !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
       !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.sw_prof_cap && !r.noise_cap && !r.in_stage_cap)
     return;
@@ -547,6 +556,11 @@ void free_workspace() {
   r.d_win_scene = r.d_win_body = nullptr;
   r.d_win_meta = nullptr;
   r.win_scene_cap = r.win_meta_cap = r.win_body_cap = 0;
+  (void)hipFree(r.d_scan_planes); (void)hipFree(r.d_scan_scene); (void)hipFree(r.d_scan_tmp); (void)hipFree(r.d_scan_buf0);
+  (void)hipFree(r.d_scan_buf1); (void)hipFree(r.d_scan_coef);
+  r.d_scan_planes = r.d_scan_scene = r.d_scan_tmp = r.d_scan_buf0 = r.d_scan_buf1 = nullptr;
+  r.d_scan_coef = nullptr;
+  r.scan_planes_cap = r.scan_scene_cap = r.scan_tmp_cap = r.scan_coef_cap = r.scan_buf0_cap = r.scan_buf1_cap = 0;
   (void)hipFree(r.d_gl_src); (void)hipFree(r.d_gl_plane); (void)hipFree(r.d_gl_tmp); (void)hipFree(r.d_gl_rec);
   (void)hipFree(r.d_gl_box); (void)hipFree(r.d_gl_plan); (void)hipFree(r.d_gl_sum);
   r.d_gl_src = r.d_gl_plane = r.d_gl_tmp = r.d_gl_rec = nullptr;
@@ -4985,6 +4999,336 @@ int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, i
   };
   if (run()) { delete[] result; return nullptr; }
   return result;
+}
+
+}  // extern "C"
+
+// ---- the dense scan: every 32 x 32 window of a picture at stride 4 from one pass (cnvW1A1; scan.h) ------------------
+namespace bnn {
+namespace {
+
+static_assert(kScanMaxSide == BNN_MI355X_SCAN_MAX_SIDE && kScanMaxWindows == BNN_MI355X_SCAN_MAX_WINDOWS &&
+                  kScanMaxMapBytes == BNN_MI355X_SCAN_MAX_MAP_BYTES,
+              "the header states the scan's limits");
+
+// Empty when this library scans, else the message for last_error
+std::string scan_refused(const char *what) {
+  const Runtime &r = rt();
+  if (!r.spec.is_cnv) return std::string(what) + ": CIFAR-10 records are the input of the CNV networks only";
+  if (r.spec.id != NET_CNVW1A1) return std::string(what) + ": the dense scan is built for cnvW1A1 only (this library is " + r.spec.name + ")";
+  return "";
+}
+
+// the map buffers of one picture (grow-only).  They may be in use by a scan_device call still in flight on a caller's
+// stream: growing waits for the whole device, like reserve().
+int reserve_scan(const ScanPlan &p) {
+  Runtime &r = rt();
+  if (p.buf0 <= r.scan_buf0_cap && p.buf1 <= r.scan_buf1_cap) return 0;
+  HIP_OK(hipDeviceSynchronize());
+  return (grow(r.d_scan_buf0, r.scan_buf0_cap, p.buf0) || grow(r.d_scan_buf1, r.scan_buf1_cap, p.buf1)) ? -1 : 0;
+}
+
+// Enqueues on s: stages 0..min(last_stage, 5) over the picture (run_scan) and, for last_stage >= 6, the existing stages
+// 6..8 with the decode on its nx * ny layer-5 pixels (run_cnv from first_stage 6: their matrix forms included).  The
+// caller has validated, bound the device and reserved the maps.
+int enqueue_scan(const char *what, const uint8_t *d_planes, long row_stride, long plane_stride, const ScanPlan &p, int ncls, int32_t *d_classes,
+                 int16_t *d_scores, hipStream_t s, int last_stage = kCnvStages - 1) {
+  Runtime &r = rt();
+  if (p.buf0 > r.scan_buf0_cap || p.buf1 > r.scan_buf1_cap) return fail(std::string(what) + ": internal: the picture's maps exceed the scan workspace");
+  if (settle_handover(s)) return -1;
+  ScanLaunch a{};
+  a.planes = d_planes; a.row_stride = row_stride; a.plane_stride = plane_stride; a.plan = p;
+  a.buf0 = r.d_scan_buf0; a.buf1 = r.d_scan_buf1;
+  for (int l = 0; l < kScanStages; l++) a.rows[l] = r.rows[l];
+  a.stream = s;
+  a.last_stage = last_stage < kScanStages - 1 ? last_stage : kScanStages - 1;
+  hipError_t e = run_scan(a);
+  if (e == hipSuccess && last_stage >= kScanStages) {
+    CnvLaunch c{};
+    c.n = p.nx * p.ny; c.buf0 = r.d_scan_buf0; c.buf1 = r.d_scan_buf1;
+    for (int l = 0; l < 9; l++) c.rows[l] = r.rows[l];
+    set_forms(c);
+    c.scores = d_scores; c.classes = d_classes; c.number_class = ncls; c.stream = s;
+    c.first_stage = kScanStages; c.last_stage = last_stage;
+    e = run_cnv(r.spec.id, c);
+  }
+  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  return 0;
+}
+
+// the four Lanczos tables of one resize, appended to `coef`
+struct ResizeTables { size_t off_kh = 0, off_bh = 0, off_kv = 0, off_bv = 0; int ksize_h = 0, ksize_v = 0; };
+ResizeTables resize_tables(int w, int h, int out_w, int out_h, std::vector<int32_t> &coef) {
+  ResizeTables t;
+  std::vector<int32_t> kh, bh, kv, bv;
+  t.ksize_h = lanczos_coeffs(w, out_w, kh, bh);
+  t.ksize_v = lanczos_coeffs(h, out_h, kv, bv);
+  const auto put = [&](const std::vector<int32_t> &v) { const size_t at = coef.size(); coef.insert(coef.end(), v.begin(), v.end()); return at; };
+  t.off_kh = put(kh); t.off_bh = put(bh); t.off_kv = put(kv); t.off_bv = put(bv);
+  return t;
+}
+
+// Enqueues on r.stream the resize of the scene in r.d_scan_scene (packed rows) to r.d_scan_planes; the tables are in HBM
+int enqueue_scan_resize(const char *what, int w, int h, int bands, int out_w, int out_h, const ResizeTables &t) {
+  Runtime &r = rt();
+  ScanResize j{};
+  j.src = r.d_scan_scene; j.w = w; j.h = h; j.bands = bands; j.stride = (long)w * bands;
+  j.out_w = out_w; j.out_h = out_h;
+  j.vertical_first = vertical_pass_first(w, h, out_h);
+  j.kh = r.d_scan_coef + t.off_kh; j.bh = r.d_scan_coef + t.off_bh; j.ksize_h = t.ksize_h;
+  j.kv = r.d_scan_coef + t.off_kv; j.bv = r.d_scan_coef + t.off_bv; j.ksize_v = t.ksize_v;
+  j.tmp = r.d_scan_tmp; j.planes = r.d_scan_planes;
+  const hipError_t e = launch_scan_resize(j, r.stream);
+  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  return 0;
+}
+size_t resize_tmp_bytes(int w, int h, int bands, int out_w, int out_h) {
+  const size_t a = (size_t)h * out_w, b = (size_t)out_h * w;
+  return (a > b ? a : b) * bands;
+}
+
+// uploads the interleaved scene (packed rows in HBM afterwards)
+int upload_scene(const uint8_t *pixels, int width, int height, int bands, long row_stride) {
+  Runtime &r = rt();
+  const size_t row_bytes = (size_t)width * bands;
+  if (row_stride == 0 || (size_t)row_stride == row_bytes)
+    HIP_OK(hipMemcpyAsync(r.d_scan_scene, pixels, row_bytes * height, hipMemcpyHostToDevice, r.stream));
+  else
+    HIP_OK(hipMemcpy2DAsync(r.d_scan_scene, row_bytes, pixels, (size_t)row_stride, row_bytes, (size_t)height, hipMemcpyHostToDevice, r.stream));
+  return 0;
+}
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_scan_grid(int width, int height, int *nx, int *ny) {
+  const std::string no = scan_refused("scan_grid");
+  if (!no.empty()) return fail(no);
+  if (!nx || !ny) return fail("scan_grid: bad arguments (null pointer)");
+  ScanPlan p;
+  const std::string bad = plan_scan("scan_grid", width, height, p);
+  if (!bad.empty()) return fail(bad);
+  *nx = p.nx; *ny = p.ny;
+  return 0;
+}
+
+long bnn_mi355x_scan_boxes(int width, int height, int size, int *boxes, long cap, int *level_w, int *level_h) {
+  const std::string no = scan_refused("scan_boxes");
+  if (!no.empty()) return fail(no);
+  // (plan_scene with a stand-in for the pointers it checks: the same refusals, in the same words, as scan_scene's)
+  ScenePlan plan;
+  const std::string bad = plan_scene("scan_boxes", &plan, width, height, 3, 0, &size, 1, &plan, plan);
+  if (!bad.empty()) return fail(bad);
+  if (level_w) *level_w = plan.levels[0].level_w;
+  if (level_h) *level_h = plan.levels[0].level_h;
+  return scan_boxes(width, height, size, boxes, cap < 0 ? 0 : cap);
+}
+
+int *bnn_mi355x_scan_planes(const uint8_t *planes, int width, int height, int number_class, int *nx, int *ny, float *usecPerImage,
+                            int enable_detail) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  const std::string no = scan_refused("scan_planes");
+  if (!no.empty()) { fail(no); return nullptr; }
+  if (!planes || !nx || !ny) { fail("scan_planes: bad arguments (null pointer)"); return nullptr; }
+  ScanPlan p;
+  const std::string bad = plan_scan("scan_planes", width, height, p);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (!ready()) return nullptr;
+  const int n = p.nx * p.ny;
+  int *result = new (std::nothrow) int[(size_t)n * (enable_detail ? number_class : 1)];
+  if (!result) { fail("out of memory"); return nullptr; }
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    std::vector<int16_t> scores;
+    const size_t plane = (size_t)width * height;
+    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n) || grow(r.d_scan_planes, r.scan_planes_cap, 3 * plane) || reserve_scan(p)) return -1;
+    while (r.scan_ev.size() < 2) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); r.scan_ev.push_back(e); }
+    if (enable_detail) scores.resize((size_t)n * 64);
+    DrainOnFailure drain;
+    HIP_OK(hipMemcpyAsync(r.d_scan_planes, planes, 3 * plane, hipMemcpyHostToDevice, r.stream));
+    HIP_OK(hipEventRecord(r.scan_ev[0], r.stream));
+    if (enqueue_scan("scan_planes", r.d_scan_planes, width, (long)plane, p, number_class, enable_detail ? nullptr : r.d_classes,
+                     enable_detail ? r.d_scores : nullptr, r.stream))
+      return -1;
+    HIP_OK(hipEventRecord(r.scan_ev[1], r.stream));
+    if (enable_detail) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, (size_t)n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    if (enable_detail)
+      for (int i = 0; i < n; i++)
+        for (int j = 0; j < number_class; j++) result[(size_t)i * number_class + j] = scores[(size_t)i * 64 + j];
+    float pass = 0.f;
+    HIP_OK(hipEventElapsedTime(&pass, r.scan_ev[0], r.scan_ev[1]));
+    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
+    return 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  *nx = p.nx; *ny = p.ny;
+  return result;
+}
+
+int bnn_mi355x_scan_device(const void *d_planes, int width, int height, int number_class, int32_t *d_classes, int16_t *d_scores,
+                           void *hip_stream) {
+  Runtime &r = rt();
+  const std::string no = scan_refused("scan_device");
+  if (!no.empty()) return fail(no);
+  if (!d_planes) return fail("scan_device: bad arguments (null pointer)");
+  ScanPlan p;
+  const std::string bad = plan_scan("scan_device", width, height, p);
+  if (!bad.empty()) return fail(bad);
+  if (number_class < 1 || number_class > 64) return fail("number_class must be in 1..64");
+  auto misaligned = [](const void *q, uintptr_t a) { return q && (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
+  if (misaligned(d_classes, 4) || misaligned(d_scores, 4)) return fail("scan_device: d_classes / d_scores must be 4-byte aligned");
+  if (!ready()) return -1;
+  if (bind_device() || reserve_scan(p)) return -1;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &capturing) != hipSuccess) capturing = hipStreamCaptureStatusNone;
+  const int rc = enqueue_scan("scan_device", static_cast<const uint8_t *>(d_planes), width, (long)width * height, p, number_class, d_classes, d_scores, s);
+  // the end of this call's use of the scan workspace, as bnn_mi355x_inference_device marks the end of its own
+  if (s != r.stream && capturing == hipStreamCaptureStatusNone) {
+    const std::string why = r.err;
+    if (hipEventRecord(r.ws_event, s) == hipSuccess) {
+      r.ws_last = s;
+      r.ws_pending = true;
+      r.ws_gen++;
+    } else if (rc == 0) {
+      return fail("scan_device: recording the workspace hand-over failed");
+    }
+    if (rc) r.err = why;
+  }
+  return rc;
+}
+
+int *bnn_mi355x_scan_scene(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *sizes, int n_sizes,
+                           int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess, int enable_detail) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  const std::string no = scan_refused("scan_scene");
+  if (!no.empty()) { fail(no); return nullptr; }
+  ScenePlan plan;
+  const std::string bad = plan_scene("scan_scene", pixels, width, height, bands, row_stride, sizes, n_sizes, boxes_out, plan);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (!ready()) return nullptr;
+  const size_t n = (size_t)plan.windows;
+  int *result = new (std::nothrow) int[n * (enable_detail ? number_class : 1)];
+  if (!result) { fail("out of memory"); return nullptr; }
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    std::vector<int16_t> scores;
+    std::vector<int32_t> coef;  // (outlives its asynchronous upload: declared before `drain`)
+    std::vector<ResizeTables> tabs(plan.levels.size());
+    size_t planes_need = 0, tmp_need = 1;
+    ScanPlan largest;
+    for (size_t k = 0; k < plan.levels.size(); k++) {
+      const ScanLevel &lv = plan.levels[k];
+      if (lv.resized) {
+        tabs[k] = resize_tables(width, height, lv.level_w, lv.level_h, coef);
+        tmp_need = std::max(tmp_need, resize_tmp_bytes(width, height, bands, lv.level_w, lv.level_h));
+      }
+      planes_need = std::max(planes_need, (size_t)3 * lv.level_w * lv.level_h);
+      largest.buf0 = std::max(largest.buf0, lv.plan.buf0);
+      largest.buf1 = std::max(largest.buf1, lv.plan.buf1);
+    }
+    // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
+    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, n) || grow(r.d_scan_scene, r.scan_scene_cap, (size_t)width * height * bands) ||
+        grow(r.d_scan_planes, r.scan_planes_cap, planes_need) || grow(r.d_scan_tmp, r.scan_tmp_cap, tmp_need) ||
+        grow(r.d_scan_coef, r.scan_coef_cap, coef.size() + 1) || reserve_scan(largest))
+      return -1;
+    while (r.scan_ev.size() < 2 * plan.levels.size() + 1) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); r.scan_ev.push_back(e); }
+    if (enable_detail) scores.resize(n * 64);
+    DrainOnFailure drain;
+    HIP_OK(hipEventRecord(r.scan_ev[0], r.stream));
+    if (upload_scene(pixels, width, height, bands, row_stride)) return -1;
+    if (!coef.empty()) HIP_OK(hipMemcpyAsync(r.d_scan_coef, coef.data(), coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+    for (size_t k = 0; k < plan.levels.size(); k++) {
+      const ScanLevel &lv = plan.levels[k];
+      // (a level of the picture's own size: Image.resize returns a copy -- the same kernels only re-lay it out)
+      if (enqueue_scan_resize("scan_scene", width, height, bands, lv.level_w, lv.level_h, tabs[k])) return -1;
+      HIP_OK(hipEventRecord(r.scan_ev[2 * k + 1], r.stream));
+      if (enqueue_scan("scan_scene", r.d_scan_planes, lv.level_w, (long)lv.level_w * lv.level_h, lv.plan, number_class,
+                       enable_detail ? nullptr : r.d_classes + lv.first, enable_detail ? r.d_scores + (size_t)lv.first * 64 : nullptr, r.stream))
+        return -1;
+      HIP_OK(hipEventRecord(r.scan_ev[2 * k + 2], r.stream));
+    }
+    if (enable_detail) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
+    else HIP_OK(hipMemcpyAsync(result, r.d_classes, n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    if (enable_detail)
+      for (size_t i = 0; i < n; i++)
+        for (int j = 0; j < number_class; j++) result[i * number_class + j] = scores[i * 64 + j];
+    float pre = 0.f, pass = 0.f;
+    for (size_t k = 0; k < plan.levels.size(); k++) {
+      float a = 0.f, b = 0.f;
+      HIP_OK(hipEventElapsedTime(&a, r.scan_ev[2 * k], r.scan_ev[2 * k + 1]));
+      HIP_OK(hipEventElapsedTime(&b, r.scan_ev[2 * k + 1], r.scan_ev[2 * k + 2]));
+      pre += a; pass += b;
+    }
+    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
+    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
+    return 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  for (const ScanLevel &lv : plan.levels) scan_boxes(width, height, lv.size, boxes_out + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
+  return result;
+}
+
+long bnn_mi355x_debug_scan_stage(const uint8_t *planes, int width, int height, int stage, void *out, size_t cap, int *map_w, int *map_h) {
+  Runtime &r = rt();
+  const std::string no = scan_refused("debug_scan_stage");
+  if (!no.empty()) return fail(no);
+  if (!planes || !out || !map_w || !map_h || stage < 0 || stage >= kScanStages) return fail("debug_scan_stage: bad arguments");
+  ScanPlan p;
+  const std::string bad = plan_scan("debug_scan_stage", width, height, p);
+  if (!bad.empty()) return fail(bad);
+  const size_t bytes = scan_stage_bytes(p, stage);
+  if (cap < bytes) return fail("debug_scan_stage: the stage's map takes " + std::to_string(bytes) + " bytes");
+  if (!ready() || bind_device()) return -1;
+  const size_t plane = (size_t)width * height;
+  if (grow(r.d_scan_planes, r.scan_planes_cap, 3 * plane) || reserve_scan(p)) return -1;
+  DrainOnFailure drain;
+  HIP_OK(hipMemcpyAsync(r.d_scan_planes, planes, 3 * plane, hipMemcpyHostToDevice, r.stream));
+  if (enqueue_scan("debug_scan_stage", r.d_scan_planes, width, (long)plane, p, 1, nullptr, nullptr, r.stream, stage)) return -1;
+  HIP_OK(hipMemcpyAsync(out, (stage & 1) ? r.d_scan_buf1 : r.d_scan_buf0, bytes, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  *map_w = p.w[stage]; *map_h = p.h[stage];
+  return (long)bytes;
+}
+
+int bnn_mi355x_scan_resize(const uint8_t *pixels, int width, int height, int bands, long row_stride, int out_w, int out_h,
+                           uint8_t *planes) {
+  Runtime &r = rt();
+  const std::string no = scan_refused("scan_resize");
+  if (!no.empty()) return fail(no);
+  if (!pixels || !planes) return fail("scan_resize: bad arguments (null pointer)");
+  if (bands != 1 && bands != 3) return fail("scan_resize: bands must be 1 (L) or 3 (RGB) bytes per pixel");
+  if (width < 1 || height < 1 || out_w < 1 || out_h < 1 || width > kScanMaxSide || height > kScanMaxSide || out_w > kScanMaxSide || out_h > kScanMaxSide)
+    return fail("scan_resize: need a picture and a level of 1.." + std::to_string(kScanMaxSide) + " pixels a side");
+  if (row_stride != 0 && row_stride < (long)width * bands) return fail("scan_resize: row stride shorter than a row");
+  if (bind_device()) return -1;
+  std::vector<int32_t> coef;
+  const ResizeTables t = resize_tables(width, height, out_w, out_h, coef);
+  const size_t out_bytes = (size_t)3 * out_w * out_h;
+  if (grow(r.d_scan_scene, r.scan_scene_cap, (size_t)width * height * bands) || grow(r.d_scan_planes, r.scan_planes_cap, out_bytes) ||
+      grow(r.d_scan_tmp, r.scan_tmp_cap, resize_tmp_bytes(width, height, bands, out_w, out_h)) || grow(r.d_scan_coef, r.scan_coef_cap, coef.size() + 1))
+    return -1;
+  DrainOnFailure drain;
+  if (upload_scene(pixels, width, height, bands, row_stride)) return -1;
+  HIP_OK(hipMemcpyAsync(r.d_scan_coef, coef.data(), coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  if (enqueue_scan_resize("scan_resize", width, height, bands, out_w, out_h, t)) return -1;
+  HIP_OK(hipMemcpyAsync(planes, r.d_scan_planes, out_bytes, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  return 0;
 }
 
 }  // extern "C"

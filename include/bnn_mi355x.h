@@ -796,7 +796,61 @@ int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, i
                                  int n_windows, int number_class, float *usecPerImage, float *usecPreprocess,
                                  int enable_detail);
 
-/* Read handwriting (LFC-BNN_MNIST_Webcam.ipynb and LFC-BNN_Chars_Webcam.ipynb, cells 9-13): ONE picture and N boxes
+/* Scan a scene densely: every 32 x 32 window of a picture at stride 4, from ONE pass over the whole picture
+ * (csrc/scan_kernels.hip; the model: csrc/scan.h).  All CNV convolutions are "valid" 3 x 3 and the two pools
+ * 2 x 2, so layers 0-5 are fully convolutional: layer-5 pixel (i, j) of the picture holds the 256 bits the per-window pass
+ * computes for the record cut at columns 4i .. 4i + 31, rows 4j .. 4j + 31, and layers 6-8 with the decode run on those as on
+ * nx * ny images.  Window (i, j) of a result -- raster order, j the outer index -- equals, bit for bit on all 64 raw scores,
+ * what bnn_mi355x_inference_buffer returns for that record.  cnvW1A1 libraries only: -1 / NULL + last_error on cnvW1A2 and
+ * cnvW2A2 ("... the dense scan is built for cnvW1A1 only") and on LFC libraries.
+ *   planes:    the picture as a "large CIFAR record body": planar uint8 [3][height][width], packed.
+ *   grid:      nx = (width - 32) / 4 + 1, ny = (height - 32) / 4 + 1; the up to 3 columns and rows beyond
+ *              32 + 4 (nx - 1) x 32 + 4 (ny - 1) are not read.
+ * scan_grid: host only; -1 + last_error for a side below 32.
+ * scan_boxes: host only.  The level rule of scan_scene for ONE window size (8 or more, a multiple of 8): the picture is
+ *       resized to level_w = width * 32 / size, level_h = height * 32 / size (integer division; refused below 32) and
+ *       cell (i, j) of that level's scan is the window (i size / 8, j size / 8, i size / 8 + size, j size / 8 + size) of the
+ *       picture -- always inside it.  Returns the number of boxes and writes at most `cap` of them (boxes may be NULL; 4
+ *       ints each, rows outer); level_w / level_h may be NULL; -1 + last_error for a refused size or level.
+ * scan_planes: host picture in, `new int[]` of nx * ny classes (or, with enable_detail, number_class scores per window)
+ *       out.  Return convention and ownership as bnn_mi355x_inference_buffer (free with free_results); usecPerImage: the
+ *       device time of the whole pass per window.
+ * scan_device: the same on a picture already in HBM (d_planes packed as above), enqueued on hip_stream under the
+ *       serialisation rules of bnn_mi355x_inference_device: d_classes (nx * ny ints) and d_scores (nx * ny x 64 int16)
+ *       may each be NULL; the maps live in a workspace of the library that every scan call shares.  The workspace for the
+ *       picture's size must exist before a stream capture begins (a first call of that size allocates it).
+ * scan_scene: a pyramid.  One upload of an interleaved picture (pixels, width, height, bands, row_stride as for
+ *       windows_to_cifar, bands 1 = "L" -- the grey plane in all three -- or 3 = "RGB"; RGBA is refused here); for each of
+ *       the n_sizes window sizes the picture is resized to its level like Image.resize((level_w, level_h), Image.LANCZOS) of
+ *       Pillow 12, byte for byte (a level of the picture's own size is taken as it is), and scanned, all on one stream.
+ *       Results are size-major, then raster; boxes_out receives every window's box (4 ints; size it with scan_boxes).
+ *       usecPerImage: the scans' device time per window; usecPreprocess (may be NULL): the upload's and the resizes'.
+ * debug_scan_stage: test hook, the twin of bnn_mi355x_debug_stage_output: runs stages 0..stage (0..5 = layers 0..5) on the
+ *       picture and copies that stage's map as it lies in HBM -- [map_h][map_w][dwords], dwords = 2, 2, 4, 4, 8, 8 per pixel,
+ *       bit-packed HWC -- to out; returns the bytes, or -1 (cap too small included).
+ * scan_resize: one level on its own, for any output size (1 .. BNN_MI355X_SCAN_MAX_SIDE a side): the planar picture
+ *       [3][out_h][out_w] (host) the scan of that level reads, i.e. Image.resize((out_w, out_h), Image.LANCZOS) of the
+ *       interleaved picture with the bands apart.  Exists so that the resize can be compared with Pillow by itself.
+ * Limits, refused before anything touches the GPU: a side of the picture (or of a level) above BNN_MI355X_SCAN_MAX_SIDE;
+ * more than BNN_MI355X_SCAN_MAX_WINDOWS windows in one picture (or level); maps of more than BNN_MI355X_SCAN_MAX_MAP_BYTES
+ * for one picture (or level).  Also refused: sides below 32, null pointers, number_class outside 1..64.  Workspaces are
+ * grow-only. */
+#define BNN_MI355X_SCAN_MAX_SIDE 8192
+#define BNN_MI355X_SCAN_MAX_WINDOWS 1048576
+#define BNN_MI355X_SCAN_MAX_MAP_BYTES 134217728
+int bnn_mi355x_scan_grid(int width, int height, int *nx, int *ny);
+long bnn_mi355x_scan_boxes(int width, int height, int size, int *boxes, long cap, int *level_w, int *level_h);
+int *bnn_mi355x_scan_planes(const uint8_t *planes, int width, int height, int number_class, int *nx, int *ny, float *usecPerImage,
+                            int enable_detail);
+int bnn_mi355x_scan_device(const void *d_planes, int width, int height, int number_class, int32_t *d_classes, int16_t *d_scores,
+                           void *hip_stream);
+int *bnn_mi355x_scan_scene(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *sizes, int n_sizes,
+                           int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess, int enable_detail);
+long bnn_mi355x_debug_scan_stage(const uint8_t *planes, int width, int height, int stage, void *out, size_t cap, int *map_w, int *map_h);
+int bnn_mi355x_scan_resize(const uint8_t *pixels, int width, int height, int bands, long row_stride, int out_w, int out_h,
+                           uint8_t *planes);
+
+/* Read handwriting(LFC-BNN_MNIST_Webcam.ipynb and LFC-BNN_Chars_Webcam.ipynb, cells 9-13): ONE picture and N boxes
  * become N MNIST-format records (28 x 28 bytes) -- and, with classify_glyphs, N classes -- in one call.  The notebooks
  * do this by hand with PIL for one camera frame, through two temporary files; here the picture goes to the device once
  * (csrc/glyph_kernels.hip) and classify_glyphs never brings the records back.  LFC libraries only (-1 / NULL +

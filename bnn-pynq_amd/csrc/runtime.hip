@@ -188,6 +188,34 @@ int largest_chunk(const std::vector<int> &base) {
   return m;
 }
 
+// Grow-only device buffer: the pointer and its capacity in elements are one object, so one cannot be freed without the
+// other being zeroed.  Every buffer joins the registry when it is constructed: free_workspace() reaches each of them there, and a
+// new buffer is one member of Runtime (the one Runtime lives as long as the library: nothing ever leaves the registry).
+struct DeviceBufBase {
+  void *ptr = nullptr;
+  size_t cap = 0;
+  static std::vector<DeviceBufBase *> &registry() {
+    static std::vector<DeviceBufBase *> v;
+    return v;
+  }
+  DeviceBufBase() { registry().push_back(this); }
+  DeviceBufBase(const DeviceBufBase &) = delete;
+  DeviceBufBase &operator=(const DeviceBufBase &) = delete;
+  int grow_to(size_t need, size_t elem_bytes);
+  void release() {
+    (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+  }
+};
+template <typename T>
+struct DeviceBuf : DeviceBufBase {
+  T *get() const { return static_cast<T *>(ptr); }
+  operator T *() const { return get(); }
+  // room for `need` elements (contents are not preserved)
+  int grow(size_t need) { return grow_to(need, sizeof(T)); }
+};
+
 struct Runtime {
   const NetSpec &spec = net_spec(BNN_NETWORK);
   int device = -1;  // -1: whatever HIP's current device is
@@ -256,38 +284,31 @@ struct Runtime {
   std::unique_ptr<uint8_t[]> h_file[2];
   uint8_t *d_file[2] = {nullptr, nullptr};
   hipEvent_t file_sent[2] = {nullptr, nullptr};
-  uint8_t *d_all = nullptr;  // a whole input file's images, resident (fault campaigns)
-  size_t all_cap = 0;
+  DeviceBuf<uint8_t> d_all;  // a whole input file's images, resident (fault campaigns)
   // bnn_mi355x_fault_campaigns: the runs' blob copies; the staging area (patches, patch spans, segment records); results
-  uint8_t *d_copies = nullptr, *d_camp = nullptr, *d_camp_res = nullptr;
-  size_t copies_cap = 0, camp_cap = 0, camp_res_cap = 0;
+  DeviceBuf<uint8_t> d_copies, d_camp, d_camp_res;
   std::vector<Fault> camp_faults;  // the faults of the last such call, run-major; camp_run[i]: the run of camp_faults[i]
   std::vector<int> camp_run;
   // bnn_mi355x_fault_sweep (the runs' blob copies: d_copies): the fault-free stage outputs and results of the call's images;
   // a run group's patches (staging + spans), segment records, survivor flags, results, counts + offsets, {image, class} pairs
-  uint8_t *d_sw_base = nullptr, *d_sw_stage = nullptr, *d_sw_segs = nullptr, *d_sw_alive = nullptr, *d_sw_res = nullptr,
-          *d_sw_cnt = nullptr, *d_sw_diffs = nullptr;
-  size_t sw_base_cap = 0, sw_stage_cap = 0, sw_segs_cap = 0, sw_alive_cap = 0, sw_res_cap = 0, sw_cnt_cap = 0, sw_diffs_cap = 0;
+  DeviceBuf<uint8_t> d_sw_base, d_sw_stage, d_sw_segs, d_sw_alive, d_sw_res, d_sw_cnt, d_sw_diffs;
   std::vector<long> sweep_pairs;  // the last sweep: per layer, the (fault, image) pairs it had to run (bnn_mi355x_last_sweep_stages)
   std::vector<long> act_sweep_pairs;  // the same of the last activation-fault sweep (bnn_mi355x_last_act_sweep_stages)
   // bnn_mi355x_sweep_profile: whether the single-fault sweeps record a propagation profile; a run group's [run][2]
   // counters in HBM; the last profiled sweep's [record][layer] images and activations that differ, its records and columns
   bool sweep_profile = false;
-  uint8_t *d_sw_prof = nullptr;
-  size_t sw_prof_cap = 0;
+  DeviceBuf<uint8_t> d_sw_prof;
   std::vector<long> prof_alive, prof_flipped;
   long prof_rows = 0;
   int prof_cols = 0;
   // bnn_mi355x_act_noise_campaigns: run seeds and [run][layer] upset counters in HBM (segment records: d_sw_segs, results:
   // d_camp_res); the counts and seeds of the last such call
-  uint8_t *d_noise = nullptr;
-  size_t noise_cap = 0;
+  DeviceBuf<uint8_t> d_noise;
   std::vector<long> noise_counts;
   std::vector<unsigned long long> noise_seeds;
   // bnn_mi355x_input_fault_sweep / bnn_mi355x_input_noise_campaigns: a group's faulted images; the last sweep's pairs per layer;
   // the flips per run and the seeds of the last campaign
-  uint8_t *d_in_stage = nullptr;
-  size_t in_stage_cap = 0;
+  DeviceBuf<uint8_t> d_in_stage;
   std::vector<long> input_sweep_pairs, input_noise_counts;
   std::vector<unsigned long long> input_noise_seeds;
   // bnn_mi355x_mem_noise_campaigns (the runs' blob copies: d_copies; patches and threshold tables: d_camp; seeds and counters:
@@ -319,37 +340,32 @@ struct Runtime {
   std::vector<unsigned long long> iwmem_seeds;
   // picture -> CIFAR record (bnn_mi355x_images_to_cifar): source picture, horizontal-pass output,
   // coefficient tables, records
-  size_t pp_src_cap = 0, pp_tmp_cap = 0, pp_coef_cap = 0, pp_rec_cap = 0;
-  uint8_t *d_pp_src = nullptr, *d_pp_tmp = nullptr, *d_pp_rec = nullptr;
-  int32_t *d_pp_coef = nullptr;
+  DeviceBuf<uint8_t> d_pp_src, d_pp_tmp, d_pp_rec;
+  DeviceBuf<int32_t> d_pp_coef;
   // windows of one scene -> records / classes (bnn_mi355x_windows_to_cifar, bnn_mi355x_classify_windows): the scene, the
   // boxes + grouped order + coefficient tables (one upload), the 3072-byte bodies; upload / kernels / pass time stamps
-  size_t win_scene_cap = 0, win_meta_cap = 0, win_body_cap = 0;
-  uint8_t *d_win_scene = nullptr, *d_win_body = nullptr;
-  int32_t *d_win_meta = nullptr;
+  DeviceBuf<uint8_t> d_win_scene, d_win_body;
+  DeviceBuf<int32_t> d_win_meta;
   hipEvent_t win_ev[3] = {nullptr, nullptr, nullptr};
   // the dense scan (bnn_mi355x_scan_*; scan.h): the planar picture (or a level's), the interleaved scene of scan_scene, the
   // first resize pass's output, the levels' coefficient tables (one upload), the two map buffers; time stamps around every
   // resize and every scan of a call
-  size_t scan_planes_cap = 0, scan_scene_cap = 0, scan_tmp_cap = 0, scan_coef_cap = 0, scan_buf0_cap = 0, scan_buf1_cap = 0;
-  uint8_t *d_scan_planes = nullptr, *d_scan_scene = nullptr, *d_scan_tmp = nullptr, *d_scan_buf0 = nullptr, *d_scan_buf1 = nullptr;
-  int32_t *d_scan_coef = nullptr;
+  DeviceBuf<uint8_t> d_scan_planes, d_scan_scene, d_scan_tmp, d_scan_buf0, d_scan_buf1;
+  DeviceBuf<int32_t> d_scan_coef;
   std::vector<hipEvent_t> scan_ev;
   // one picture and N boxes -> MNIST-format records / classes (bnn_mi355x_enhance_picture, bnn_mi355x_glyphs_to_mnist,
   // bnn_mi355x_classify_glyphs; LFC): the picture, its L plane, boxes + found ink boxes, descriptors + tables, the global
   // temporary of glyphs past the LDS budget, the 784-byte records, the plane's pixel sum; time stamps as win_ev
-  size_t gl_src_cap = 0, gl_plane_cap = 0, gl_box_cap = 0, gl_plan_cap = 0, gl_tmp_cap = 0, gl_rec_cap = 0, gl_sum_cap = 0;
-  uint8_t *d_gl_src = nullptr, *d_gl_plane = nullptr, *d_gl_tmp = nullptr, *d_gl_rec = nullptr;
-  int32_t *d_gl_box = nullptr, *d_gl_plan = nullptr;
-  unsigned long long *d_gl_sum = nullptr;
+  DeviceBuf<uint8_t> d_gl_src, d_gl_plane, d_gl_tmp, d_gl_rec;
+  DeviceBuf<int32_t> d_gl_box, d_gl_plan;
+  DeviceBuf<unsigned long long> d_gl_sum;
   hipEvent_t gl_ev[3] = {nullptr, nullptr, nullptr};
   // the glyphs of a picture (bnn_mi355x_find_glyphs, bnn_mi355x_read_glyphs; components.h): ink words, the label plane, the
   // components by root number, head + compacted list, and -- when the label map is asked for -- the index per root number
   // and the relabelled plane; time stamps around the labelling launches and what they measured in the last call
-  size_t cc_bits_cap = 0, cc_label_cap = 0, cc_stat_cap = 0, cc_list_cap = 0, cc_index_cap = 0, cc_out_cap = 0;
-  uint64_t *d_cc_bits = nullptr;
-  int32_t *d_cc_label = nullptr, *d_cc_list = nullptr, *d_cc_index = nullptr, *d_cc_out = nullptr;
-  Component *d_cc_stat = nullptr;
+  DeviceBuf<uint64_t> d_cc_bits;
+  DeviceBuf<int32_t> d_cc_label, d_cc_list, d_cc_index, d_cc_out;
+  DeviceBuf<Component> d_cc_stat;
   hipEvent_t cc_ev[2] = {nullptr, nullptr};
   float cc_usec = 0.f;
   // optional per-stage profiling (bnn_mi355x_profile): one event set per enqueued chunk
@@ -368,6 +384,13 @@ int fail(const std::string &msg) {
   std::fprintf(stderr, "bnn-mi355x[%s]: %s\n", rt().spec.name, msg.c_str());
   return -1;
 }
+// the refusal of every entry point that takes number_class; true: refused
+bool bad_number_class(int number_class) {
+  if (number_class >= 1 && number_class <= 64) return false;
+  fail("number_class must be in 1..64");
+  return true;
+}
+int launch_failed(const char *what, hipError_t e) { return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e)); }
 
 // BNN_MI355X_TRACE=1: host-side time stamps of a host-data call (microseconds since its start) on stderr -- where a call's
 // wall time goes that no device timeline shows (tools/small_call_sweep.py prints them next to the rates)
@@ -442,6 +465,24 @@ int bind_device() {
   return 0;
 }
 
+// time stamps of the picture entry points, created at first use (they are not destroyed at deinit())
+int ensure_events(hipEvent_t *ev, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!ev[i]) HIP_OK(hipEventCreate(&ev[i]));
+  return 0;
+}
+int ensure_events(std::vector<hipEvent_t> &ev, size_t n) {
+  if (ev.size() < n) ev.resize(n, nullptr);
+  return ensure_events(ev.data(), n);
+}
+// *out (may be null): the device time between two events of a finished call, in microseconds per image of n
+int usec_per_image(hipEvent_t a, hipEvent_t b, size_t n, float *out) {
+  float ms = 0.f;
+  HIP_OK(hipEventElapsedTime(&ms, a, b));
+  if (out) *out = ms * 1000.f / (float)n;
+  return 0;
+}
+
 // On a failing exit nothing may still be queued that reads the caller's buffers, the host chunks or the patch
 // images, or that writes the caller's result arrays: the caller is free to release them as soon as it sees
 // the error.  (A successful exit has waited for its streams anyway.)
@@ -504,9 +545,9 @@ int upload_blob() {
 
 void free_workspace() {
   Runtime &r = rt();
-  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.d_pp_src && !r.d_pp_rec && !r.win_scene_cap && !r.win_meta_cap && !r.win_body_cap && !r.scan_planes_cap && !r.scan_scene_cap && !r.scan_tmp_cap && !r.scan_coef_cap && !r.scan_buf0_cap && !r.scan_buf1_cap && !r.gl_src_cap && !r.gl_plane_cap && !r.gl_box_cap && !r.gl_plan_cap && !r.gl_tmp_cap && !r.gl_rec_cap && !r.gl_sum_cap && !r.cc_bits_cap && !r.cc_label_cap && !r.cc_stat_cap && !r.cc_list_cap && !r.cc_index_cap && !r.cc_out_cap && !r.file_cap && !r.all_cap && !r.h_io &&
-      !r.h_classes && !r.h_words && !r.copies_cap && !r.camp_cap && !r.camp_res_cap && !r.sw_base_cap && !r.sw_stage_cap &&
-      !r.sw_segs_cap && !r.sw_alive_cap && !r.sw_res_cap && !r.sw_cnt_cap && !r.sw_diffs_cap && !r.sw_prof_cap && !r.noise_cap && !r.in_stage_cap)
+  const auto &grown = DeviceBufBase::registry();
+  if (r.cap == 0 && r.cap2 == 0 && r.stage_cap == 0 && r.res_cap == 0 && !r.file_cap && !r.h_io && !r.h_classes && !r.h_words &&
+      std::none_of(grown.begin(), grown.end(), [](const DeviceBufBase *b) { return b->ptr != nullptr; }))
     return;
   if (r.device >= 0) (void)hipSetDevice(r.device);
   (void)hipDeviceSynchronize();
@@ -527,64 +568,19 @@ void free_workspace() {
   (void)hipFree(r.buf0b); (void)hipFree(r.buf1b);
   r.buf0b = r.buf1b = nullptr;
   r.cap2 = 0;
-  (void)hipFree(r.d_all);
-  r.d_all = nullptr;
-  r.all_cap = 0;
-  (void)hipFree(r.d_copies); (void)hipFree(r.d_camp); (void)hipFree(r.d_camp_res);
-  r.d_copies = r.d_camp = r.d_camp_res = nullptr;
-  r.copies_cap = r.camp_cap = r.camp_res_cap = 0;
-  for (uint8_t **b : {&r.d_sw_base, &r.d_sw_stage, &r.d_sw_segs, &r.d_sw_alive, &r.d_sw_res, &r.d_sw_cnt, &r.d_sw_diffs, &r.d_sw_prof}) {
-    (void)hipFree(*b);
-    *b = nullptr;
-  }
-  r.sw_base_cap = r.sw_stage_cap = r.sw_segs_cap = r.sw_alive_cap = r.sw_res_cap = r.sw_cnt_cap = r.sw_diffs_cap = r.sw_prof_cap = 0;
-  (void)hipFree(r.d_noise);
-  r.d_noise = nullptr;
-  r.noise_cap = 0;
-  (void)hipFree(r.d_in_stage);
-  r.d_in_stage = nullptr;
-  r.in_stage_cap = 0;
   (void)hipFree(r.d_file[0]); (void)hipFree(r.d_file[1]);
   r.d_file[0] = r.d_file[1] = nullptr;
   r.h_file[0].reset(); r.h_file[1].reset();
   r.file_cap = 0;
-  (void)hipFree(r.d_pp_src); (void)hipFree(r.d_pp_tmp); (void)hipFree(r.d_pp_rec); (void)hipFree(r.d_pp_coef);
-  r.d_pp_src = r.d_pp_tmp = r.d_pp_rec = nullptr;
-  r.d_pp_coef = nullptr;
-  r.pp_src_cap = r.pp_tmp_cap = r.pp_coef_cap = r.pp_rec_cap = 0;
-  (void)hipFree(r.d_win_scene); (void)hipFree(r.d_win_body); (void)hipFree(r.d_win_meta);
-  r.d_win_scene = r.d_win_body = nullptr;
-  r.d_win_meta = nullptr;
-  r.win_scene_cap = r.win_meta_cap = r.win_body_cap = 0;
-  (void)hipFree(r.d_scan_planes); (void)hipFree(r.d_scan_scene); (void)hipFree(r.d_scan_tmp); (void)hipFree(r.d_scan_buf0);
-  (void)hipFree(r.d_scan_buf1); (void)hipFree(r.d_scan_coef);
-  r.d_scan_planes = r.d_scan_scene = r.d_scan_tmp = r.d_scan_buf0 = r.d_scan_buf1 = nullptr;
-  r.d_scan_coef = nullptr;
-  r.scan_planes_cap = r.scan_scene_cap = r.scan_tmp_cap = r.scan_coef_cap = r.scan_buf0_cap = r.scan_buf1_cap = 0;
-  (void)hipFree(r.d_gl_src); (void)hipFree(r.d_gl_plane); (void)hipFree(r.d_gl_tmp); (void)hipFree(r.d_gl_rec);
-  (void)hipFree(r.d_gl_box); (void)hipFree(r.d_gl_plan); (void)hipFree(r.d_gl_sum);
-  r.d_gl_src = r.d_gl_plane = r.d_gl_tmp = r.d_gl_rec = nullptr;
-  r.d_gl_box = r.d_gl_plan = nullptr;
-  r.d_gl_sum = nullptr;
-  r.gl_src_cap = r.gl_plane_cap = r.gl_box_cap = r.gl_plan_cap = r.gl_tmp_cap = r.gl_rec_cap = r.gl_sum_cap = 0;
-  (void)hipFree(r.d_cc_bits); (void)hipFree(r.d_cc_label); (void)hipFree(r.d_cc_stat); (void)hipFree(r.d_cc_list);
-  (void)hipFree(r.d_cc_index); (void)hipFree(r.d_cc_out);
-  r.d_cc_bits = nullptr;
-  r.d_cc_label = r.d_cc_list = r.d_cc_index = r.d_cc_out = nullptr;
-  r.d_cc_stat = nullptr;
-  r.cc_bits_cap = r.cc_label_cap = r.cc_stat_cap = r.cc_list_cap = r.cc_index_cap = r.cc_out_cap = 0;
+  for (DeviceBufBase *b : grown) b->release();
 }
 
-// grow-only device buffer (contents are not preserved)
-template <typename T>
-int grow(T *&ptr, size_t &cap, size_t need) {
+int DeviceBufBase::grow_to(size_t need, size_t elem_bytes) {
   if (need <= cap) return 0;
   HIP_OK(hipStreamSynchronize(rt().stream));
-  (void)hipFree(ptr);
-  ptr = nullptr;
-  cap = 0;
+  release();
   const size_t n = need + need / 4 + 256;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&ptr), n * sizeof(T)));
+  HIP_OK(hipMalloc(&ptr, n * elem_bytes));
   cap = n;
   return 0;
 }
@@ -1642,7 +1638,7 @@ int infer_direct(const Source &src, int n, int ncls, int32_t *classes, int16_t *
 int infer_any(const Source &src, int n, int ncls, int32_t *classes, int16_t *scores, uint64_t *words, float *usec, const uint64_t **words_view = nullptr) {
   Runtime &r = rt();
   if (!ready()) return -1;
-  if (ncls < 1 || ncls > 64) return fail("number_class must be in 1..64");
+  if (bad_number_class(ncls)) return -1;
   if (usec) *usec = 0.f;
   if (n <= 0) return 0;
   if (!src.file) trace().start();  // (a file call started the clock before it opened the file)
@@ -1770,7 +1766,7 @@ int infer_file(const ImageFile &f, int n, int ncls, int32_t *classes, int16_t *s
 int load_file_resident(const ImageFile &f, int n) {
   Runtime &r = rt();
   const size_t isz = (size_t)r.spec.image_bytes();
-  if (bind_device() || grow(r.d_all, r.all_cap, (size_t)n * isz + 256)) return -1;
+  if (bind_device() || r.d_all.grow((size_t)n * isz + 256)) return -1;
   DrainOnFailure drain;
   if (stream_file(
           f, n, false, 1, [&](int base, int) { return r.d_all + (size_t)base * isz; }, [&](int, int, int, int) { return 0; }))
@@ -1841,6 +1837,114 @@ template <class T>
 int copy_out(const std::vector<T> &v, T *out, int cap) {
   for (int i = 0; out && i < cap && i < (int)v.size(); i++) out[i] = v[(size_t)i];
   return (int)v.size();
+}
+
+// ---- what the picture entry points share ----------------------------------------------------------------------------
+
+// Enqueues on r.stream the upload of `height` rows of row_bytes to packed rows at dst: one flat copy when the source is
+// packed (row_stride 0 or row_bytes), else a 2-D one
+int upload_rows(uint8_t *dst, const uint8_t *pixels, size_t row_bytes, long row_stride, int height) {
+  Runtime &r = rt();
+  if (row_stride == 0 || (size_t)row_stride == row_bytes)
+    HIP_OK(hipMemcpyAsync(dst, pixels, row_bytes * height, hipMemcpyHostToDevice, r.stream));
+  else
+    HIP_OK(hipMemcpy2DAsync(dst, row_bytes, pixels, (size_t)row_stride, row_bytes, (size_t)height, hipMemcpyHostToDevice, r.stream));
+  return 0;
+}
+
+// the four Lanczos tables of one resize, appended to `coef`: kh | bh | kv | bv
+struct ResizeTables { size_t off_kh = 0, off_bh = 0, off_kv = 0, off_bv = 0; int ksize_h = 0, ksize_v = 0; };
+ResizeTables resize_tables(int w, int h, int out_w, int out_h, std::vector<int32_t> &coef) {
+  ResizeTables t;
+  std::vector<int32_t> kh, bh, kv, bv;
+  t.ksize_h = lanczos_coeffs(w, out_w, kh, bh);
+  t.ksize_v = lanczos_coeffs(h, out_h, kv, bv);
+  const auto put = [&](const std::vector<int32_t> &v) { const size_t at = coef.size(); coef.insert(coef.end(), v.begin(), v.end()); return at; };
+  t.off_kh = put(kh); t.off_bh = put(bh); t.off_kv = put(kv); t.off_bv = put(bv);
+  return t;
+}
+// the six table fields of a launch-argument struct, from the tables' base in HBM and their offsets (ResizeTables, WindowGroup)
+template <class Job, class Offsets>
+void set_tables(Job &j, const int32_t *base, const Offsets &t) {
+  j.kh = base + t.off_kh; j.bh = base + t.off_bh; j.ksize_h = t.ksize_h;
+  j.kv = base + t.off_kv; j.bv = base + t.off_bv; j.ksize_v = t.ksize_v;
+}
+
+// The end of a device-pointer call's use of the shared workspaces, marked on the caller's stream `s` -- on a failing exit
+// (rc != 0) too: passes queued before the failure still run.  Not while the stream is being captured into a graph: a
+// replayed graph is serialised by its own stream, and the caller must not replay it concurrently with other calls into
+// this library (include/bnn_mi355x.h).  Returns rc, or -1 when the mark itself failed.
+int hand_over(const char *what, hipStream_t s, hipStreamCaptureStatus capturing, int rc) {
+  Runtime &r = rt();
+  if (s == r.stream || capturing != hipStreamCaptureStatusNone) return rc;
+  const std::string why = r.err;
+  if (hipEventRecord(r.ws_event, s) == hipSuccess) {
+    r.ws_last = s;
+    r.ws_pending = true;
+    r.ws_gen++;
+  } else if (rc == 0) {
+    return fail(std::string(what) + ": recording the workspace hand-over failed");
+  }
+  if (rc) r.err = why;
+  return rc;
+}
+
+// the result buffers of a pass of n images that bnn_mi355x_inference_device runs on records already in HBM
+int reserve_results(size_t n) { return reserve_host(rt().stage_cap > 0 ? rt().stage_cap : 1, n); }
+
+// the array an `int *` entry point returns (delete[]); null with last_error set
+int *new_result(size_t count) {
+  int *result = new (std::nothrow) int[count ? count : 1];
+  if (!result) fail("out of memory");
+  return result;
+}
+
+// The CNV results' way back on r.stream: the classes of n images straight into `result`, or -- `scores` sized by the
+// caller to n x 64 -- the scores, which widen_scores puts into `result` as number_class ints per image after the sync
+int enqueue_cnv_results(size_t n, int *result, std::vector<int16_t> &scores) {
+  Runtime &r = rt();
+  if (!scores.empty()) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
+  else HIP_OK(hipMemcpyAsync(result, r.d_classes, n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  return 0;
+}
+void widen_scores(const std::vector<int16_t> &scores, int number_class, int *result) {
+  for (size_t i = 0; i < scores.size() / 64; i++)
+    for (int j = 0; j < number_class; j++) result[i * number_class + j] = scores[i * 64 + j];
+}
+
+// The n records at r.d_gl_rec to classes (LFC), on r.stream: the pass bnn_mi355x_inference_device enqueues on records that
+// never left the device, between gl_ev[1] and gl_ev[2]; the results' way back; the wait.  Up to 47 classes the last stage
+// decodes on the device; beyond, the words come back and libm decodes them, as the reference does
+// (bnn_mi355x_inference_device).  A status-2 glyph reads -1: its record was never written.  `status` may be null.
+int classify_glyph_records(int n, int number_class, const std::vector<int32_t> &glyph_status, int *result, int *status) {
+  Runtime &r = rt();
+  const bool on_device = number_class <= 47;
+  std::vector<uint64_t> words(on_device ? 0 : (size_t)n);
+  HIP_OK(hipEventRecord(r.gl_ev[1], r.stream));
+  if (bnn_mi355x_inference_device(r.d_gl_rec, n, number_class, on_device ? r.d_classes : nullptr, nullptr, r.d_words, r.stream)) return -1;
+  HIP_OK(hipEventRecord(r.gl_ev[2], r.stream));
+  if (on_device) HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  else HIP_OK(hipMemcpyAsync(words.data(), r.d_words, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  for (int i = 0; i < n; i++) {
+    if (!on_device) result[i] = lfc_class_batched(words[(size_t)i], number_class);
+    if (glyph_status[(size_t)i] == kGlyphTooThin) result[i] = -1;
+    if (status) status[i] = glyph_status[(size_t)i];
+  }
+  return 0;
+}
+
+// The n records at r.d_gl_rec to the caller's `records`, and the wait: a status-2 glyph's record stays as the caller left it
+int download_glyph_records(size_t n, const std::vector<int32_t> &glyph_status, uint8_t *records, int *status) {
+  Runtime &r = rt();
+  std::vector<uint8_t> staged(n * kGlyphRecord);
+  if (n) HIP_OK(hipMemcpyAsync(staged.data(), r.d_gl_rec, staged.size(), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  for (size_t i = 0; i < n; i++) {
+    if (glyph_status[i] != kGlyphTooThin) std::memcpy(records + i * kGlyphRecord, staged.data() + i * kGlyphRecord, kGlyphRecord);
+    if (status) status[i] = glyph_status[i];
+  }
+  return 0;
 }
 
 }  // namespace
@@ -2181,8 +2285,8 @@ int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs
     // -- device buffers
     const bool cnv = r.spec.is_cnv;
     if (load_file_resident(f, n) || reserve(cap)) return -1;
-    if (grow(r.d_copies, r.copies_cap, (size_t)R * stride) || grow(r.d_camp, r.camp_cap, upload.size()) ||
-        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+    if (r.d_copies.grow((size_t)R * stride) || r.d_camp.grow(upload.size()) ||
+        r.d_camp_res.grow(total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
       return -1;
     std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
     if (!cnv) w.resize(total);
@@ -2219,8 +2323,8 @@ int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs
         a.l0_mfma = tab ? r.d_copies + h.l0_mfma_offset : nullptr;
         a.stride = stride;
         a.has_two = wave_two[(size_t)k] != 0;
-        a.classes = reinterpret_cast<int32_t *>(r.d_camp_res);
-        a.words = reinterpret_cast<uint64_t *>(r.d_camp_res);
+        a.classes = reinterpret_cast<int32_t *>(r.d_camp_res.get());
+        a.words = reinterpret_cast<uint64_t *>(r.d_camp_res.get());
         a.number_class = number_class;
         a.stream = r.stream;
         e = cnv ? run_cnv_multi(r.spec.id, a) : run_lfc_multi(r.spec.id, a);
@@ -2422,18 +2526,18 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     const size_t res_n = std::max<size_t>((size_t)max_pairs, (size_t)n);
     if (load_file_resident(f, n) || reserve(wcap)) return -1;
     const size_t isz = (size_t)net.image_bytes();
-    if (grow(r.d_copies, r.copies_cap, unpatched ? 0 : (size_t)max_runs * stride) || grow(r.d_sw_base, r.sw_base_cap, boff[(size_t)S]) ||
-        grow(r.d_in_stage, r.in_stage_cap, inp ? (size_t)max_pairs * isz + 256 : 0) ||
-        grow(r.d_sw_segs, r.sw_segs_cap, (size_t)max_pairs * sizeof(MultiSeg) * (inp ? 2 : 1)) || grow(r.d_sw_alive, r.sw_alive_cap, (size_t)max_pairs) ||
-        grow(r.d_sw_res, r.sw_res_cap, res_n * rb) || grow(r.d_sw_cnt, r.sw_cnt_cap, (size_t)max_runs * 12 + 512) ||
-        grow(r.d_sw_diffs, r.sw_diffs_cap, (size_t)max_pairs * 8) || grow(r.d_sw_prof, r.sw_prof_cap, profile ? (size_t)max_runs * 16 : 0))
+    if (r.d_copies.grow(unpatched ? 0 : (size_t)max_runs * stride) || r.d_sw_base.grow(boff[(size_t)S]) ||
+        r.d_in_stage.grow(inp ? (size_t)max_pairs * isz + 256 : 0) ||
+        r.d_sw_segs.grow((size_t)max_pairs * sizeof(MultiSeg) * (inp ? 2 : 1)) || r.d_sw_alive.grow((size_t)max_pairs) ||
+        r.d_sw_res.grow(res_n * rb) || r.d_sw_cnt.grow((size_t)max_runs * 12 + 512) ||
+        r.d_sw_diffs.grow((size_t)max_pairs * 8) || r.d_sw_prof.grow(profile ? (size_t)max_runs * 16 : 0))
       return -1;
     uint8_t *const bufs[2] = {static_cast<uint8_t *>(r.buf0), static_cast<uint8_t *>(r.buf1)};
     uint8_t *const base_res = r.d_sw_base + boff[(size_t)S - 1];
-    int *const d_counts = reinterpret_cast<int *>(r.d_sw_cnt);
+    int *const d_counts = reinterpret_cast<int *>(r.d_sw_cnt.get());
     long long *const d_offsets = reinterpret_cast<long long *>(r.d_sw_cnt + (((size_t)max_runs * 4 + 255) & ~(size_t)255));
-    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
-    MultiSeg *const d_seed_segs = reinterpret_cast<MultiSeg *>(r.d_sw_segs) + max_pairs;  // (input sites: layer 0's records, below)
+    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs.get());
+    MultiSeg *const d_seed_segs = reinterpret_cast<MultiSeg *>(r.d_sw_segs.get()) + max_pairs;  // (input sites: layer 0's records, below)
     // host buffers the queued copies read or write (declared before `drain`)
     std::vector<MultiSeg> segs, ran, seed_segs;
     std::vector<uint8_t> alive, upload;
@@ -2571,9 +2675,9 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           }
           upload.assign(ws.size() * sizeof(ActWinSite), 0);
           std::memcpy(upload.data(), ws.data(), upload.size());
-          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          if (r.d_sw_stage.grow(upload.size()) || begin()) return -1;
           HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
-          d_wsites = reinterpret_cast<const ActWinSite *>(r.d_sw_stage);
+          d_wsites = reinterpret_cast<const ActWinSite *>(r.d_sw_stage.get());
         } else if (inp) {  // input sites: each run's bit as k_input_seed flips it (the image's 16-byte lane, the bit inside it)
           std::vector<ActPatch> ap((size_t)g);
           for (int q = 0; q < g; q++) {
@@ -2582,9 +2686,9 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           }
           upload.assign(ap.size() * sizeof(ActPatch), 0);
           std::memcpy(upload.data(), ap.data(), upload.size());
-          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          if (r.d_sw_stage.grow(upload.size()) || begin()) return -1;
           HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
-          d_sites = reinterpret_cast<const ActPatch *>(r.d_sw_stage);
+          d_sites = reinterpret_cast<const ActPatch *>(r.d_sw_stage.get());
         } else if (act) {  // activation sites: each run's site as k_act_seed patches it
           ActShape sh{};
           act_shape(net, L, &sh);
@@ -2602,9 +2706,9 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           }
           upload.assign(ap.size() * sizeof(ActPatch), 0);
           std::memcpy(upload.data(), ap.data(), upload.size());
-          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          if (r.d_sw_stage.grow(upload.size()) || begin()) return -1;
           HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
-          d_sites = reinterpret_cast<const ActPatch *>(r.d_sw_stage);
+          d_sites = reinterpret_cast<const ActPatch *>(r.d_sw_stage.get());
         } else {  // parameter faults: the patches of the group's copies
           auto add_span = [&](int q, size_t off, size_t bytes) {
             patch.push_back(PatchSpan{(uint64_t)q * stride + off, (uint32_t)staging.size(), (uint32_t)bytes});
@@ -2636,7 +2740,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           std::memcpy(upload.data(), staging.data(), staging.size());
           std::memcpy(upload.data() + spans_off, patch.data(), patch.size() * sizeof(PatchSpan));
           std::memcpy(upload.data() + spans_off + patch.size() * sizeof(PatchSpan), undo.data(), undo.size() * sizeof(PatchSpan));
-          if (grow(r.d_sw_stage, r.sw_stage_cap, upload.size()) || begin()) return -1;
+          if (r.d_sw_stage.grow(upload.size()) || begin()) return -1;
           HIP_OK(hipMemcpyAsync(r.d_sw_stage, upload.data(), upload.size(), hipMemcpyHostToDevice, r.stream));
           d_spans = reinterpret_cast<const PatchSpan *>(r.d_sw_stage + spans_off);
           e = scatter_patches(r.d_sw_stage, d_spans, (int)patch.size(), r.d_copies, r.stream);
@@ -2695,7 +2799,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
             for (const Batch &b : batches) {
               e = profile ? sweep_profile(bufs[obuf[(size_t)l]], r.d_sw_base + boff[(size_t)l], (int)ob[(size_t)l], net.L[l].out_planes == 2,
                                           d_segs + b.seg0, b.nsegs, b.max_len, r.d_sw_alive,
-                                          reinterpret_cast<unsigned long long *>(r.d_sw_prof), r.stream)
+                                          reinterpret_cast<unsigned long long *>(r.d_sw_prof.get()), r.stream)
                           : sweep_mark(bufs[obuf[(size_t)l]], r.d_sw_base + boff[(size_t)l], (int)ob[(size_t)l], d_segs + b.seg0, b.nsegs, b.max_len,
                                        r.d_sw_alive, r.stream);
               if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
@@ -2744,7 +2848,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           // classes against the fault-free ones (pairs pruned at any layer kept the fault-free result)
           if (begin()) return -1;
           if (cnv) {
-            const int32_t *cls = reinterpret_cast<const int32_t *>(r.d_sw_res) + i0, *bcls = reinterpret_cast<const int32_t *>(base_res) + i0;
+            const int32_t *cls = reinterpret_cast<const int32_t *>(r.d_sw_res.get()) + i0, *bcls = reinterpret_cast<const int32_t *>(base_res) + i0;
             e = sweep_count(cls, bcls, n, m, g, d_counts, r.stream);
             if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
             counts.resize((size_t)g);
@@ -2760,7 +2864,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
             if (tot > 0 && cap_diffs > 0) {
               if (begin()) return -1;
               HIP_OK(hipMemcpyAsync(d_offsets, offs.data(), (size_t)g * 8, hipMemcpyHostToDevice, r.stream));
-              e = sweep_emit(cls, bcls, n, m, g, d_counts, d_offsets, reinterpret_cast<int *>(r.d_sw_diffs), r.stream);
+              e = sweep_emit(cls, bcls, n, m, g, d_counts, d_offsets, reinterpret_cast<int *>(r.d_sw_diffs.get()), r.stream);
               if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
               HIP_OK(hipMemcpyAsync(pv.data(), r.d_sw_diffs, (size_t)tot * 8, hipMemcpyDeviceToHost, r.stream));
               if (finish()) return -1;
@@ -3003,12 +3107,12 @@ int *bnn_mi355x_act_noise_campaigns(const char *path, int number_class, int num_
     const bool tab = h.l0_mfma_offset && r.l0_mfma;
     const size_t counts_off = ((size_t)R * 8 + 255) & ~(size_t)255;
     if (load_file_resident(f, n) || reserve((int)cap)) return -1;
-    if (grow(r.d_sw_segs, r.sw_segs_cap, segs.size() * sizeof(MultiSeg)) || grow(r.d_noise, r.noise_cap, counts_off + counts.size() * 8) ||
-        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+    if (r.d_sw_segs.grow(segs.size() * sizeof(MultiSeg)) || r.d_noise.grow(counts_off + counts.size() * 8) ||
+        r.d_camp_res.grow(total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
       return -1;
-    const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+    const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise.get());
     unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
-    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
+    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs.get());
     uint8_t *const bufs[2] = {static_cast<uint8_t *>(r.buf0), static_cast<uint8_t *>(r.buf1)};
     const uint8_t *const clean = static_cast<const uint8_t *>(r.d_blob);
     std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
@@ -3036,8 +3140,8 @@ int *bnn_mi355x_act_noise_campaigns(const char *path, int number_class, int num_
         a.l0_mfma = tab ? clean + h.l0_mfma_offset : nullptr;
         a.stride = 0;  // every run reads the one loaded blob
         a.has_two = r.two_rows > 0;
-        a.classes = reinterpret_cast<int32_t *>(r.d_camp_res);
-        a.words = reinterpret_cast<uint64_t *>(r.d_camp_res);
+        a.classes = reinterpret_cast<int32_t *>(r.d_camp_res.get());
+        a.words = reinterpret_cast<uint64_t *>(r.d_camp_res.get());
         a.number_class = number_class;
         a.stream = r.stream;
         a.first = a.last = l;
@@ -3207,10 +3311,10 @@ int *bnn_mi355x_input_noise_campaigns(const char *path, int number_class, int nu
     }
     const size_t isz = (size_t)net.image_bytes(), counts_off = ((size_t)R * 8 + 255) & ~(size_t)255;
     if (load_file_resident(f, n)) return -1;
-    if (grow(r.d_in_stage, r.in_stage_cap, cap * isz + 256) || grow(r.d_noise, r.noise_cap, counts_off + counts.size() * 8) ||
-        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+    if (r.d_in_stage.grow(cap * isz + 256) || r.d_noise.grow(counts_off + counts.size() * 8) ||
+        r.d_camp_res.grow(total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
       return -1;
-    const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+    const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise.get());
     unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
     std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
     if (!cnv) w.resize(total);
@@ -3238,8 +3342,8 @@ int *bnn_mi355x_input_noise_campaigns(const char *path, int number_class, int nu
         }
       }
       // (the device entry point itself, on the library's stream: whatever pass it takes for m images is the pass taken here)
-      if (bnn_mi355x_inference_device(r.d_in_stage, m, number_class, cnv ? reinterpret_cast<int32_t *>(r.d_camp_res) + p0 : nullptr, nullptr,
-                                      cnv ? nullptr : reinterpret_cast<uint64_t *>(r.d_camp_res) + p0, r.stream))
+      if (bnn_mi355x_inference_device(r.d_in_stage, m, number_class, cnv ? reinterpret_cast<int32_t *>(r.d_camp_res.get()) + p0 : nullptr, nullptr,
+                                      cnv ? nullptr : reinterpret_cast<uint64_t *>(r.d_camp_res.get()) + p0, r.stream))
         return -1;
     }
     HIP_OK(hipEventRecord(r.time_events[1], r.stream));
@@ -3517,10 +3621,10 @@ static int mem_noise_enqueue(const std::vector<unsigned long long> &seeds, const
   PackedHeader h;
   std::memcpy(&h, r.blob.data(), sizeof(h));
   const size_t stride = job.stride;
-  if (grow(r.d_copies, r.copies_cap, (size_t)R * stride) || grow(r.d_camp, r.camp_cap, job.upload.size() + 256) ||
-      grow(r.d_noise, r.noise_cap, counts_off + (size_t)R * S * 2 * 8))
+  if (r.d_copies.grow((size_t)R * stride) || r.d_camp.grow(job.upload.size() + 256) ||
+      r.d_noise.grow(counts_off + (size_t)R * S * 2 * 8))
     return -1;
-  const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+  const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise.get());
   unsigned long long *const d_counts = reinterpret_cast<unsigned long long *>(r.d_noise + counts_off);
   HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
   HIP_OK(hipMemsetAsync(d_counts, 0, (size_t)R * S * 2 * 8, r.stream));
@@ -3685,8 +3789,8 @@ static int exposure_prepare(const char *who, const std::vector<unsigned long lon
 static int exposure_begin(const std::vector<unsigned long long> &seeds, const MemNoiseJob &job, size_t counts_off, const ExposureCounters &cl) {
   Runtime &r = rt();
   const int R = (int)seeds.size();
-  if (grow(r.d_copies, r.copies_cap, (size_t)R * job.stride) || grow(r.d_camp, r.camp_cap, job.state_begin + job.state_bytes + 256) ||
-      grow(r.d_noise, r.noise_cap, counts_off + cl.bytes()))
+  if (r.d_copies.grow((size_t)R * job.stride) || r.d_camp.grow(job.state_begin + job.state_bytes + 256) ||
+      r.d_noise.grow(counts_off + cl.bytes()))
     return -1;
   HIP_OK(hipMemcpyAsync(r.d_noise, seeds.data(), (size_t)R * 8, hipMemcpyHostToDevice, r.stream));
   HIP_OK(hipMemsetAsync(r.d_noise + counts_off, 0, cl.bytes(), r.stream));
@@ -3707,7 +3811,7 @@ static int exposure_epoch(int t, const unsigned int *rw, const unsigned int *rth
   PackedHeader h;
   std::memcpy(&h, r.blob.data(), sizeof(h));
   const size_t stride = job.stride;
-  const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise);
+  const unsigned long long *const d_seeds = reinterpret_cast<const unsigned long long *>(r.d_noise.get());
   // epoch t of every block (a kernel whose block the family has not is never launched)
   uint8_t *const region = r.d_noise + counts_off;
   unsigned long long *const d_counts = cl.epoch(region, cl.COUNTS, t), *const d_ecc = cl.epoch(region, cl.STATUS, t),
@@ -3904,8 +4008,8 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     const bool tab = h.l0_mfma_offset && r.l0_mfma;
     const size_t counts_off = ((size_t)R * 8 + 255) & ~(size_t)255;
     if (load_file_resident(f, n) || reserve((int)cap)) return -1;
-    if (grow(r.d_sw_segs, r.sw_segs_cap, segs.size() * sizeof(MultiSeg)) ||
-        grow(r.d_camp_res, r.camp_res_cap, total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
+    if (r.d_sw_segs.grow(segs.size() * sizeof(MultiSeg)) ||
+        r.d_camp_res.grow(total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
       return -1;
     std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
     if (!cnv) w.resize(total);
@@ -3922,7 +4026,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
       return -1;
     // (all rates 0: no copy is made, every run reads the loaded blob)
     const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
-    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs);
+    const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs.get());
     HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
     int entered = -1;  // the last epoch whose scrub and upsets are in the stream
     for (const Group &g : groups) {
@@ -3938,8 +4042,8 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
       a.stride = any ? job.stride : 0;
       // (reading the flags back only to decide this would cost a host wait: the -2-aware instantiations are exact on rows without)
       a.has_two = r.two_rows > 0 || tt;
-      a.classes = reinterpret_cast<int32_t *>(r.d_camp_res);
-      a.words = reinterpret_cast<uint64_t *>(r.d_camp_res);
+      a.classes = reinterpret_cast<int32_t *>(r.d_camp_res.get());
+      a.words = reinterpret_cast<uint64_t *>(r.d_camp_res.get());
       a.number_class = number_class;
       a.stream = r.stream;
       const hipError_t e = cnv ? run_cnv_multi(net.id, a) : run_lfc_multi(net.id, a);
@@ -4683,15 +4787,14 @@ int bnn_mi355x_images_to_cifar(const uint8_t *const *pixels, const int *widths, 
     return fail("images_to_cifar: bad arguments");
   if (n_images == 0) return 0;
   if (bind_device()) return -1;
-  if (grow(r.d_pp_rec, r.pp_rec_cap, (size_t)n_images * 3073)) return -1;
+  if (r.d_pp_rec.grow((size_t)n_images * 3073)) return -1;
   // host copies of the coefficient tables must outlive their (asynchronous) upload: kept until the next sync
   std::vector<std::vector<int32_t>> keep;
   // declared after `keep`, so destroyed (= streams drained on a failing exit) before it: uploads from the caller's
   // pictures and from `keep` may still be queued when an error returns
   DrainOnFailure drain;
-  int last_w = -1, last_h = -1;
-  size_t off_bh = 0, off_kv = 0, off_bv = 0;
-  int ksize_h = 0, ksize_v = 0, ow = 0, oh = 0;
+  int last_w = -1, last_h = -1, ow = 0, oh = 0;
+  ResizeTables tabs;
   for (int i = 0; i < n_images; i++) {
     const int w = widths[i], h = heights[i], nb = bands[i];
     if (!pixels[i] || w < 1 || h < 1 || w > 65535 || h > 65535 || (nb != 1 && nb != 3 && nb != 4))
@@ -4702,34 +4805,25 @@ int bnn_mi355x_images_to_cifar(const uint8_t *const *pixels, const int *widths, 
     if (w != last_w || h != last_h) {
       ow = w; oh = h;
       (void)thumbnail_size(w, h, 32, &ow, &oh);
-      std::vector<int32_t> kh, bh, kv, bv, all;
-      ksize_h = lanczos_coeffs(w, ow, kh, bh);
-      ksize_v = lanczos_coeffs(h, oh, kv, bv);
-      off_bh = kh.size(); off_kv = off_bh + bh.size(); off_bv = off_kv + kv.size();
-      all.reserve(off_bv + bv.size());
-      all.insert(all.end(), kh.begin(), kh.end()); all.insert(all.end(), bh.begin(), bh.end());
-      all.insert(all.end(), kv.begin(), kv.end()); all.insert(all.end(), bv.begin(), bv.end());
-      if (grow(r.d_pp_coef, r.pp_coef_cap, all.size())) return -1;
+      std::vector<int32_t> all;
+      tabs = resize_tables(w, h, ow, oh, all);
+      if (r.d_pp_coef.grow(all.size())) return -1;
       if (keep.size() >= 16) { HIP_OK(hipStreamSynchronize(r.stream)); keep.clear(); }
       keep.push_back(std::move(all));
       HIP_OK(hipMemcpyAsync(r.d_pp_coef, keep.back().data(), keep.back().size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
       last_w = w; last_h = h;
     }
-    if (grow(r.d_pp_src, r.pp_src_cap, row_bytes * h) || grow(r.d_pp_tmp, r.pp_tmp_cap, (size_t)(h > w ? h : w) * 32 * 4 + 4096)) return -1;
-    if ((size_t)stride == row_bytes)
-      HIP_OK(hipMemcpyAsync(r.d_pp_src, pixels[i], row_bytes * h, hipMemcpyHostToDevice, r.stream));
-    else
-      HIP_OK(hipMemcpy2DAsync(r.d_pp_src, row_bytes, pixels[i], (size_t)stride, row_bytes, (size_t)h, hipMemcpyHostToDevice, r.stream));
+    if (r.d_pp_src.grow(row_bytes * h) || r.d_pp_tmp.grow((size_t)(h > w ? h : w) * 32 * 4 + 4096)) return -1;
+    if (upload_rows(r.d_pp_src, pixels[i], row_bytes, stride, h)) return -1;
     ResampleJob j{};
     j.src = r.d_pp_src; j.w = w; j.h = h; j.bands = nb; j.stride = (long)row_bytes;
     j.out_w = ow; j.out_h = oh;
     j.vertical_first = vertical_pass_first(w, h, oh);
-    j.kh = r.d_pp_coef; j.bh = r.d_pp_coef + off_bh; j.ksize_h = ksize_h;
-    j.kv = r.d_pp_coef + off_kv; j.bv = r.d_pp_coef + off_bv; j.ksize_v = ksize_v;
+    set_tables(j, r.d_pp_coef, tabs);
     j.tmp = r.d_pp_tmp;
     j.record = r.d_pp_rec + (size_t)i * 3073;
     const hipError_t e = launch_image_to_cifar(j, r.stream);
-    if (e != hipSuccess) return fail(std::string("images_to_cifar: kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return launch_failed("images_to_cifar", e);
   }
   HIP_OK(hipMemcpyAsync(records, r.d_pp_rec, (size_t)n_images * 3073, hipMemcpyDeviceToHost, r.stream));
   HIP_OK(hipStreamSynchronize(r.stream));
@@ -4770,7 +4864,7 @@ int bnn_mi355x_inference_device(const void *d_images, int n_images, int number_c
   Runtime &r = rt();
   if (!ready()) return -1;
   if (n_images < 0 || (n_images > 0 && !d_images)) return fail("inference_device: bad arguments");
-  if (number_class < 1 || number_class > 64) return fail("number_class must be in 1..64");
+  if (bad_number_class(number_class)) return -1;
   // the kernels read images with 128-bit loads and write scores as dwords (include/bnn_mi355x.h states the alignment)
   auto misaligned = [](const void *p, uintptr_t a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
   if (misaligned(d_images, 16)) return fail("inference_device: d_images must be 16-byte aligned");
@@ -4826,21 +4920,7 @@ int bnn_mi355x_inference_device(const void *d_images, int n_images, int number_c
   };
   int rc = 0;
   for (int base = 0; base < n_images && rc == 0; base += kMaxChunk) rc = pass(base, (n_images - base < kMaxChunk) ? n_images - base : kMaxChunk);
-  // mark the end of this call's use of the shared workspace -- on a failing exit too: passes queued before the failure
-  // still run (not while the stream is being captured into a graph: a replayed graph is serialised by its own stream, and
-  // the caller must not replay it concurrently with other calls into this library -- include/bnn_mi355x.h)
-  if (n_images > 0 && s != r.stream && capturing == hipStreamCaptureStatusNone) {
-    const std::string why = r.err;
-    if (hipEventRecord(r.ws_event, s) == hipSuccess) {
-      r.ws_last = s;
-      r.ws_pending = true;
-      r.ws_gen++;
-    } else if (rc == 0) {
-      return fail("inference_device: recording the workspace hand-over failed");
-    }
-    if (rc) r.err = why;
-  }
-  return rc;
+  return n_images > 0 ? hand_over("inference_device", s, capturing, rc) : rc;
 }
 
 long bnn_mi355x_tile_boxes(int width, int height, int size, int *boxes, long cap) {
@@ -4871,15 +4951,11 @@ int enqueue_windows(const char *what, const uint8_t *pixels, int width, int heig
   std::memcpy(meta.data(), boxes, (size_t)n * 4 * sizeof(int32_t));
   std::memcpy(meta.data() + off_order, plan.order.data(), (size_t)n * sizeof(int32_t));
   if (!plan.coef.empty()) std::memcpy(meta.data() + off_coef, plan.coef.data(), plan.coef.size() * sizeof(int32_t));
-  if (grow(r.d_win_scene, r.win_scene_cap, row_bytes * height) || grow(r.d_win_meta, r.win_meta_cap, meta.size())) return -1;
+  if (r.d_win_scene.grow(row_bytes * height) || r.d_win_meta.grow(meta.size())) return -1;
   for (const WindowGroup &g : plan.groups)
-    if (!g.fused && (grow(r.d_pp_src, r.pp_src_cap, (size_t)g.w * g.h * bands) || grow(r.d_pp_rec, r.pp_rec_cap, 3073) ||
-                     grow(r.d_pp_tmp, r.pp_tmp_cap, (size_t)(g.h > g.w ? g.h : g.w) * 32 * 4 + 4096)))
+    if (!g.fused && (r.d_pp_src.grow((size_t)g.w * g.h * bands) || r.d_pp_rec.grow(3073) || r.d_pp_tmp.grow((size_t)(g.h > g.w ? g.h : g.w) * 32 * 4 + 4096)))
       return -1;
-  if (row_stride == 0 || (size_t)row_stride == row_bytes)
-    HIP_OK(hipMemcpyAsync(r.d_win_scene, pixels, row_bytes * height, hipMemcpyHostToDevice, r.stream));
-  else
-    HIP_OK(hipMemcpy2DAsync(r.d_win_scene, row_bytes, pixels, (size_t)row_stride, row_bytes, (size_t)height, hipMemcpyHostToDevice, r.stream));
+  if (upload_rows(r.d_win_scene, pixels, row_bytes, row_stride, height)) return -1;
   HIP_OK(hipMemcpyAsync(r.d_win_meta, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
   const int32_t *d_coef = r.d_win_meta + off_coef;
   for (const WindowGroup &g : plan.groups) {
@@ -4890,11 +4966,10 @@ int enqueue_windows(const char *what, const uint8_t *pixels, int width, int heig
       a.boxes = r.d_win_meta; a.order = r.d_win_meta + off_order + g.first;
       a.w = g.w; a.h = g.h; a.out_w = g.out_w; a.out_h = g.out_h;
       a.horizontal = g.horizontal ? 1 : 0; a.vertical = g.vertical ? 1 : 0;
-      a.kh = d_coef + g.off_kh; a.bh = d_coef + g.off_bh; a.ksize_h = g.ksize_h;
-      a.kv = d_coef + g.off_kv; a.bv = d_coef + g.off_bv; a.ksize_v = g.ksize_v;
+      set_tables(a, d_coef, g);
       a.out = out; a.out_pitch = pitch; a.label = label;
       const hipError_t e = launch_windows_to_cifar(a, g.count, r.stream);
-      if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+      if (e != hipSuccess) return launch_failed(what, e);
       continue;
     }
     // one by one: a packed device-to-device copy of the window (RGBA: premultiplied in place there, never in the scene),
@@ -4909,12 +4984,11 @@ int enqueue_windows(const char *what, const uint8_t *pixels, int width, int heig
       j.src = r.d_pp_src; j.w = g.w; j.h = g.h; j.bands = bands; j.stride = (long)wrow;
       j.out_w = g.out_w; j.out_h = g.out_h;
       j.vertical_first = vertical_pass_first(g.w, g.h, g.out_h);
-      j.kh = d_coef + g.off_kh; j.bh = d_coef + g.off_bh; j.ksize_h = g.ksize_h;
-      j.kv = d_coef + g.off_kv; j.bv = d_coef + g.off_bv; j.ksize_v = g.ksize_v;
+      set_tables(j, d_coef, g);
       j.tmp = r.d_pp_tmp;
       j.record = label ? out + (size_t)i * pitch : r.d_pp_rec;
       const hipError_t e = launch_image_to_cifar(j, r.stream);
-      if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+      if (e != hipSuccess) return launch_failed(what, e);
       if (!label) HIP_OK(hipMemcpyAsync(out + (size_t)i * pitch, r.d_pp_rec + 1, 3072, hipMemcpyDeviceToDevice, r.stream));
     }
   }
@@ -4937,7 +5011,7 @@ int bnn_mi355x_windows_to_cifar(const uint8_t *pixels, int width, int height, in
   WindowPlan plan;
   std::vector<int32_t> meta;  // (outlives its asynchronous upload, like `plan`: declared before `drain`)
   plan_windows(boxes, n_windows, bands, plan);
-  if (grow(r.d_pp_rec, r.pp_rec_cap, (size_t)n_windows * 3073)) return -1;
+  if (r.d_pp_rec.grow((size_t)n_windows * 3073)) return -1;
   DrainOnFailure drain;
   if (enqueue_windows("windows_to_cifar", pixels, width, height, bands, row_stride, boxes, n_windows, plan, meta, r.d_pp_rec, 3073, 1)) return -1;
   HIP_OK(hipMemcpyAsync(records, r.d_pp_rec, (size_t)n_windows * 3073, hipMemcpyDeviceToHost, r.stream));
@@ -4955,13 +5029,11 @@ int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, i
   // (no output buffer of the caller's to check: the result array is the call's own)
   const std::string bad = validate_windows("classify_windows", pixels, width, height, bands, row_stride, boxes, n_windows, pixels);
   if (!bad.empty()) { fail(bad); return nullptr; }
-  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (bad_number_class(number_class)) return nullptr;
   const int n = n_windows;
   if (n > 0 && !ready()) return nullptr;
-  const size_t count = (size_t)n * (enable_detail ? number_class : 1);
-  int *result = new (std::nothrow) int[count ? count : 1];
-  if (!result) { fail("out of memory"); return nullptr; }
-  if (n == 0) return result;
+  int *result = new_result((size_t)n * (enable_detail ? number_class : 1));
+  if (!result || n == 0) return result;
   // everything that can fail from here on frees `result`
   auto run = [&]() -> int {
     if (bind_device()) return -1;
@@ -4970,9 +5042,7 @@ int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, i
     std::vector<int16_t> scores;
     plan_windows(boxes, n, bands, plan);
     // the pass's workspaces first (they synchronise when they grow), so that nothing is allocated between the kernels
-    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n) || grow(r.d_win_body, r.win_body_cap, (size_t)n * 3072)) return -1;
-    for (hipEvent_t &e : r.win_ev)
-      if (!e) HIP_OK(hipEventCreate(&e));
+    if (reserve_results((size_t)n) || r.d_win_body.grow((size_t)n * 3072) || ensure_events(r.win_ev, 3)) return -1;
     if (enable_detail) scores.resize((size_t)n * 64);
     DrainOnFailure drain;
     HIP_OK(hipEventRecord(r.win_ev[0], r.stream));
@@ -4983,19 +5053,11 @@ int *bnn_mi355x_classify_windows(const uint8_t *pixels, int width, int height, i
                                     nullptr, r.stream))
       return -1;
     HIP_OK(hipEventRecord(r.win_ev[2], r.stream));
-    if (enable_detail) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, (size_t)n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
-    else HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    if (enqueue_cnv_results((size_t)n, result, scores)) return -1;
     HIP_OK(hipStreamSynchronize(r.stream));
     drain.ok();
-    if (enable_detail)
-      for (int i = 0; i < n; i++)
-        for (int j = 0; j < number_class; j++) result[(size_t)i * number_class + j] = scores[(size_t)i * 64 + j];
-    float pre = 0.f, pass = 0.f;
-    HIP_OK(hipEventElapsedTime(&pre, r.win_ev[0], r.win_ev[1]));
-    HIP_OK(hipEventElapsedTime(&pass, r.win_ev[1], r.win_ev[2]));
-    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
-    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
-    return 0;
+    widen_scores(scores, number_class, result);
+    return (usec_per_image(r.win_ev[0], r.win_ev[1], (size_t)n, usecPreprocess) || usec_per_image(r.win_ev[1], r.win_ev[2], (size_t)n, usecPerImage)) ? -1 : 0;
   };
   if (run()) { delete[] result; return nullptr; }
   return result;
@@ -5023,9 +5085,9 @@ std::string scan_refused(const char *what) {
 // stream: growing waits for the whole device, like reserve().
 int reserve_scan(const ScanPlan &p) {
   Runtime &r = rt();
-  if (p.buf0 <= r.scan_buf0_cap && p.buf1 <= r.scan_buf1_cap) return 0;
+  if (p.buf0 <= r.d_scan_buf0.cap && p.buf1 <= r.d_scan_buf1.cap) return 0;
   HIP_OK(hipDeviceSynchronize());
-  return (grow(r.d_scan_buf0, r.scan_buf0_cap, p.buf0) || grow(r.d_scan_buf1, r.scan_buf1_cap, p.buf1)) ? -1 : 0;
+  return (r.d_scan_buf0.grow(p.buf0) || r.d_scan_buf1.grow(p.buf1)) ? -1 : 0;
 }
 
 // Enqueues on s: stages 0..min(last_stage, 5) over the picture (run_scan) and, for last_stage >= 6, the existing stages
@@ -5034,7 +5096,7 @@ int reserve_scan(const ScanPlan &p) {
 int enqueue_scan(const char *what, const uint8_t *d_planes, long row_stride, long plane_stride, const ScanPlan &p, int ncls, int32_t *d_classes,
                  int16_t *d_scores, hipStream_t s, int last_stage = kCnvStages - 1) {
   Runtime &r = rt();
-  if (p.buf0 > r.scan_buf0_cap || p.buf1 > r.scan_buf1_cap) return fail(std::string(what) + ": internal: the picture's maps exceed the scan workspace");
+  if (p.buf0 > r.d_scan_buf0.cap || p.buf1 > r.d_scan_buf1.cap) return fail(std::string(what) + ": internal: the picture's maps exceed the scan workspace");
   if (settle_handover(s)) return -1;
   ScanLaunch a{};
   a.planes = d_planes; a.row_stride = row_stride; a.plane_stride = plane_stride; a.plan = p;
@@ -5052,20 +5114,8 @@ int enqueue_scan(const char *what, const uint8_t *d_planes, long row_stride, lon
     c.first_stage = kScanStages; c.last_stage = last_stage;
     e = run_cnv(r.spec.id, c);
   }
-  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_failed(what, e);
   return 0;
-}
-
-// the four Lanczos tables of one resize, appended to `coef`
-struct ResizeTables { size_t off_kh = 0, off_bh = 0, off_kv = 0, off_bv = 0; int ksize_h = 0, ksize_v = 0; };
-ResizeTables resize_tables(int w, int h, int out_w, int out_h, std::vector<int32_t> &coef) {
-  ResizeTables t;
-  std::vector<int32_t> kh, bh, kv, bv;
-  t.ksize_h = lanczos_coeffs(w, out_w, kh, bh);
-  t.ksize_v = lanczos_coeffs(h, out_h, kv, bv);
-  const auto put = [&](const std::vector<int32_t> &v) { const size_t at = coef.size(); coef.insert(coef.end(), v.begin(), v.end()); return at; };
-  t.off_kh = put(kh); t.off_bh = put(bh); t.off_kv = put(kv); t.off_bv = put(bv);
-  return t;
 }
 
 // Enqueues on r.stream the resize of the scene in r.d_scan_scene (packed rows) to r.d_scan_planes; the tables are in HBM
@@ -5075,27 +5125,15 @@ int enqueue_scan_resize(const char *what, int w, int h, int bands, int out_w, in
   j.src = r.d_scan_scene; j.w = w; j.h = h; j.bands = bands; j.stride = (long)w * bands;
   j.out_w = out_w; j.out_h = out_h;
   j.vertical_first = vertical_pass_first(w, h, out_h);
-  j.kh = r.d_scan_coef + t.off_kh; j.bh = r.d_scan_coef + t.off_bh; j.ksize_h = t.ksize_h;
-  j.kv = r.d_scan_coef + t.off_kv; j.bv = r.d_scan_coef + t.off_bv; j.ksize_v = t.ksize_v;
+  set_tables(j, r.d_scan_coef, t);
   j.tmp = r.d_scan_tmp; j.planes = r.d_scan_planes;
   const hipError_t e = launch_scan_resize(j, r.stream);
-  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_failed(what, e);
   return 0;
 }
 size_t resize_tmp_bytes(int w, int h, int bands, int out_w, int out_h) {
   const size_t a = (size_t)h * out_w, b = (size_t)out_h * w;
   return (a > b ? a : b) * bands;
-}
-
-// uploads the interleaved scene (packed rows in HBM afterwards)
-int upload_scene(const uint8_t *pixels, int width, int height, int bands, long row_stride) {
-  Runtime &r = rt();
-  const size_t row_bytes = (size_t)width * bands;
-  if (row_stride == 0 || (size_t)row_stride == row_bytes)
-    HIP_OK(hipMemcpyAsync(r.d_scan_scene, pixels, row_bytes * height, hipMemcpyHostToDevice, r.stream));
-  else
-    HIP_OK(hipMemcpy2DAsync(r.d_scan_scene, row_bytes, pixels, (size_t)row_stride, row_bytes, (size_t)height, hipMemcpyHostToDevice, r.stream));
-  return 0;
 }
 
 }  // namespace
@@ -5136,17 +5174,16 @@ int *bnn_mi355x_scan_planes(const uint8_t *planes, int width, int height, int nu
   ScanPlan p;
   const std::string bad = plan_scan("scan_planes", width, height, p);
   if (!bad.empty()) { fail(bad); return nullptr; }
-  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (bad_number_class(number_class)) return nullptr;
   if (!ready()) return nullptr;
   const int n = p.nx * p.ny;
-  int *result = new (std::nothrow) int[(size_t)n * (enable_detail ? number_class : 1)];
-  if (!result) { fail("out of memory"); return nullptr; }
+  int *result = new_result((size_t)n * (enable_detail ? number_class : 1));
+  if (!result) return nullptr;
   auto run = [&]() -> int {
     if (bind_device()) return -1;
     std::vector<int16_t> scores;
     const size_t plane = (size_t)width * height;
-    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n) || grow(r.d_scan_planes, r.scan_planes_cap, 3 * plane) || reserve_scan(p)) return -1;
-    while (r.scan_ev.size() < 2) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); r.scan_ev.push_back(e); }
+    if (reserve_results((size_t)n) || r.d_scan_planes.grow(3 * plane) || reserve_scan(p) || ensure_events(r.scan_ev, 2)) return -1;
     if (enable_detail) scores.resize((size_t)n * 64);
     DrainOnFailure drain;
     HIP_OK(hipMemcpyAsync(r.d_scan_planes, planes, 3 * plane, hipMemcpyHostToDevice, r.stream));
@@ -5155,17 +5192,11 @@ int *bnn_mi355x_scan_planes(const uint8_t *planes, int width, int height, int nu
                      enable_detail ? r.d_scores : nullptr, r.stream))
       return -1;
     HIP_OK(hipEventRecord(r.scan_ev[1], r.stream));
-    if (enable_detail) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, (size_t)n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
-    else HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    if (enqueue_cnv_results((size_t)n, result, scores)) return -1;
     HIP_OK(hipStreamSynchronize(r.stream));
     drain.ok();
-    if (enable_detail)
-      for (int i = 0; i < n; i++)
-        for (int j = 0; j < number_class; j++) result[(size_t)i * number_class + j] = scores[(size_t)i * 64 + j];
-    float pass = 0.f;
-    HIP_OK(hipEventElapsedTime(&pass, r.scan_ev[0], r.scan_ev[1]));
-    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
-    return 0;
+    widen_scores(scores, number_class, result);
+    return usec_per_image(r.scan_ev[0], r.scan_ev[1], (size_t)n, usecPerImage);
   };
   if (run()) { delete[] result; return nullptr; }
   *nx = p.nx; *ny = p.ny;
@@ -5174,14 +5205,13 @@ int *bnn_mi355x_scan_planes(const uint8_t *planes, int width, int height, int nu
 
 int bnn_mi355x_scan_device(const void *d_planes, int width, int height, int number_class, int32_t *d_classes, int16_t *d_scores,
                            void *hip_stream) {
-  Runtime &r = rt();
   const std::string no = scan_refused("scan_device");
   if (!no.empty()) return fail(no);
   if (!d_planes) return fail("scan_device: bad arguments (null pointer)");
   ScanPlan p;
   const std::string bad = plan_scan("scan_device", width, height, p);
   if (!bad.empty()) return fail(bad);
-  if (number_class < 1 || number_class > 64) return fail("number_class must be in 1..64");
+  if (bad_number_class(number_class)) return -1;
   auto misaligned = [](const void *q, uintptr_t a) { return q && (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
   if (misaligned(d_classes, 4) || misaligned(d_scores, 4)) return fail("scan_device: d_classes / d_scores must be 4-byte aligned");
   if (!ready()) return -1;
@@ -5190,19 +5220,7 @@ int bnn_mi355x_scan_device(const void *d_planes, int width, int height, int numb
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &capturing) != hipSuccess) capturing = hipStreamCaptureStatusNone;
   const int rc = enqueue_scan("scan_device", static_cast<const uint8_t *>(d_planes), width, (long)width * height, p, number_class, d_classes, d_scores, s);
-  // the end of this call's use of the scan workspace, as bnn_mi355x_inference_device marks the end of its own
-  if (s != r.stream && capturing == hipStreamCaptureStatusNone) {
-    const std::string why = r.err;
-    if (hipEventRecord(r.ws_event, s) == hipSuccess) {
-      r.ws_last = s;
-      r.ws_pending = true;
-      r.ws_gen++;
-    } else if (rc == 0) {
-      return fail("scan_device: recording the workspace hand-over failed");
-    }
-    if (rc) r.err = why;
-  }
-  return rc;
+  return hand_over("scan_device", s, capturing, rc);
 }
 
 int *bnn_mi355x_scan_scene(const uint8_t *pixels, int width, int height, int bands, long row_stride, const int *sizes, int n_sizes,
@@ -5215,11 +5233,11 @@ int *bnn_mi355x_scan_scene(const uint8_t *pixels, int width, int height, int ban
   ScenePlan plan;
   const std::string bad = plan_scene("scan_scene", pixels, width, height, bands, row_stride, sizes, n_sizes, boxes_out, plan);
   if (!bad.empty()) { fail(bad); return nullptr; }
-  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (bad_number_class(number_class)) return nullptr;
   if (!ready()) return nullptr;
   const size_t n = (size_t)plan.windows;
-  int *result = new (std::nothrow) int[n * (enable_detail ? number_class : 1)];
-  if (!result) { fail("out of memory"); return nullptr; }
+  int *result = new_result(n * (enable_detail ? number_class : 1));
+  if (!result) return nullptr;
   auto run = [&]() -> int {
     if (bind_device()) return -1;
     std::vector<int16_t> scores;
@@ -5238,15 +5256,14 @@ int *bnn_mi355x_scan_scene(const uint8_t *pixels, int width, int height, int ban
       largest.buf1 = std::max(largest.buf1, lv.plan.buf1);
     }
     // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
-    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, n) || grow(r.d_scan_scene, r.scan_scene_cap, (size_t)width * height * bands) ||
-        grow(r.d_scan_planes, r.scan_planes_cap, planes_need) || grow(r.d_scan_tmp, r.scan_tmp_cap, tmp_need) ||
-        grow(r.d_scan_coef, r.scan_coef_cap, coef.size() + 1) || reserve_scan(largest))
+    if (reserve_results(n) || r.d_scan_scene.grow((size_t)width * height * bands) || r.d_scan_planes.grow(planes_need) ||
+        r.d_scan_tmp.grow(tmp_need) || r.d_scan_coef.grow(coef.size() + 1) || reserve_scan(largest) ||
+        ensure_events(r.scan_ev, 2 * plan.levels.size() + 1))
       return -1;
-    while (r.scan_ev.size() < 2 * plan.levels.size() + 1) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); r.scan_ev.push_back(e); }
     if (enable_detail) scores.resize(n * 64);
     DrainOnFailure drain;
     HIP_OK(hipEventRecord(r.scan_ev[0], r.stream));
-    if (upload_scene(pixels, width, height, bands, row_stride)) return -1;
+    if (upload_rows(r.d_scan_scene, pixels, (size_t)width * bands, row_stride, height)) return -1;
     if (!coef.empty()) HIP_OK(hipMemcpyAsync(r.d_scan_coef, coef.data(), coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
     for (size_t k = 0; k < plan.levels.size(); k++) {
       const ScanLevel &lv = plan.levels[k];
@@ -5258,13 +5275,10 @@ int *bnn_mi355x_scan_scene(const uint8_t *pixels, int width, int height, int ban
         return -1;
       HIP_OK(hipEventRecord(r.scan_ev[2 * k + 2], r.stream));
     }
-    if (enable_detail) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
-    else HIP_OK(hipMemcpyAsync(result, r.d_classes, n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    if (enqueue_cnv_results(n, result, scores)) return -1;
     HIP_OK(hipStreamSynchronize(r.stream));
     drain.ok();
-    if (enable_detail)
-      for (size_t i = 0; i < n; i++)
-        for (int j = 0; j < number_class; j++) result[i * number_class + j] = scores[i * 64 + j];
+    widen_scores(scores, number_class, result);
     float pre = 0.f, pass = 0.f;
     for (size_t k = 0; k < plan.levels.size(); k++) {
       float a = 0.f, b = 0.f;
@@ -5293,7 +5307,7 @@ long bnn_mi355x_debug_scan_stage(const uint8_t *planes, int width, int height, i
   if (cap < bytes) return fail("debug_scan_stage: the stage's map takes " + std::to_string(bytes) + " bytes");
   if (!ready() || bind_device()) return -1;
   const size_t plane = (size_t)width * height;
-  if (grow(r.d_scan_planes, r.scan_planes_cap, 3 * plane) || reserve_scan(p)) return -1;
+  if (r.d_scan_planes.grow(3 * plane) || reserve_scan(p)) return -1;
   DrainOnFailure drain;
   HIP_OK(hipMemcpyAsync(r.d_scan_planes, planes, 3 * plane, hipMemcpyHostToDevice, r.stream));
   if (enqueue_scan("debug_scan_stage", r.d_scan_planes, width, (long)plane, p, 1, nullptr, nullptr, r.stream, stage)) return -1;
@@ -5318,11 +5332,11 @@ int bnn_mi355x_scan_resize(const uint8_t *pixels, int width, int height, int ban
   std::vector<int32_t> coef;
   const ResizeTables t = resize_tables(width, height, out_w, out_h, coef);
   const size_t out_bytes = (size_t)3 * out_w * out_h;
-  if (grow(r.d_scan_scene, r.scan_scene_cap, (size_t)width * height * bands) || grow(r.d_scan_planes, r.scan_planes_cap, out_bytes) ||
-      grow(r.d_scan_tmp, r.scan_tmp_cap, resize_tmp_bytes(width, height, bands, out_w, out_h)) || grow(r.d_scan_coef, r.scan_coef_cap, coef.size() + 1))
+  if (r.d_scan_scene.grow((size_t)width * height * bands) || r.d_scan_planes.grow(out_bytes) ||
+      r.d_scan_tmp.grow(resize_tmp_bytes(width, height, bands, out_w, out_h)) || r.d_scan_coef.grow(coef.size() + 1))
     return -1;
   DrainOnFailure drain;
-  if (upload_scene(pixels, width, height, bands, row_stride)) return -1;
+  if (upload_rows(r.d_scan_scene, pixels, (size_t)width * bands, row_stride, height)) return -1;
   HIP_OK(hipMemcpyAsync(r.d_scan_coef, coef.data(), coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
   if (enqueue_scan_resize("scan_resize", width, height, bands, out_w, out_h, t)) return -1;
   HIP_OK(hipMemcpyAsync(planes, r.d_scan_planes, out_bytes, hipMemcpyDeviceToHost, r.stream));
@@ -5355,9 +5369,7 @@ int enqueue_glyph_plane(const char *what, const uint8_t *pixels, int width, int 
   Runtime &r = rt();
   const long pitch = glyph_plane_pitch(width);
   const size_t src_pitch = (size_t)pitch * bands, row_bytes = (size_t)width * bands;
-  if (grow(r.d_gl_src, r.gl_src_cap, src_pitch * height) || grow(r.d_gl_plane, r.gl_plane_cap, (size_t)pitch * height) ||
-      grow(r.d_gl_sum, r.gl_sum_cap, 1))
-    return -1;
+  if (r.d_gl_src.grow(src_pitch * height) || r.d_gl_plane.grow((size_t)pitch * height) || r.d_gl_sum.grow(1)) return -1;
   HIP_OK(hipMemcpy2DAsync(r.d_gl_src, src_pitch, pixels, row_stride ? (size_t)row_stride : row_bytes, row_bytes, (size_t)height, hipMemcpyHostToDevice,
                           r.stream));
   HIP_OK(hipMemsetAsync(r.d_gl_sum, 0, sizeof(unsigned long long), r.stream));
@@ -5366,7 +5378,7 @@ int enqueue_glyph_plane(const char *what, const uint8_t *pixels, int width, int 
   hipError_t e = launch_glyph_luma(p, r.stream);
   if (e == hipSuccess && (o.contrast != 1.0f || o.brightness != 1.0f || o.threshold >= 0))
     e = launch_glyph_enhance(p, o.contrast, o.brightness, o.threshold, r.stream);
-  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_failed(what, e);
   return 0;
 }
 
@@ -5386,12 +5398,10 @@ int enqueue_glyph_records(const char *what, const GlyphPicture &p, const int *bo
     f[2] = f[3] = -1;
     tallest = std::max(tallest, boxes[4 * (size_t)i + 3] - boxes[4 * (size_t)i + 1]);
   }
-  if (grow(r.d_gl_box, r.gl_box_cap, meta.size()) || grow(r.d_gl_rec, r.gl_rec_cap, (size_t)n * kGlyphRecord) ||
-      grow(r.d_gl_plan, r.gl_plan_cap, (size_t)n * 16 + 4096))
-    return -1;
+  if (r.d_gl_box.grow(meta.size()) || r.d_gl_rec.grow((size_t)n * kGlyphRecord) || r.d_gl_plan.grow((size_t)n * 16 + 4096)) return -1;
   HIP_OK(hipMemcpyAsync(r.d_gl_box, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
   hipError_t e = launch_glyph_bbox(p, r.d_gl_box, r.d_gl_box + off_found, n, tallest, r.stream);
-  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_failed(what, e);
   std::vector<int32_t> found((size_t)n * 4);
   HIP_OK(hipMemcpyAsync(found.data(), r.d_gl_box + off_found, found.size() * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
   HIP_OK(hipStreamSynchronize(r.stream));
@@ -5402,11 +5412,11 @@ int enqueue_glyph_records(const char *what, const GlyphPicture &p, const int *bo
   std::memcpy(meta.data(), plan.desc.data(), (size_t)n * sizeof(GlyphDesc));
   if (!plan.coef.empty()) std::memcpy(meta.data() + off_coef, plan.coef.data(), plan.coef.size() * sizeof(int32_t));
   // (the stream is idle here: growing costs no second wait)
-  if (grow(r.d_gl_plan, r.gl_plan_cap, meta.size()) || (plan.tmp_bytes && grow(r.d_gl_tmp, r.gl_tmp_cap, plan.tmp_bytes))) return -1;
+  if (r.d_gl_plan.grow(meta.size()) || (plan.tmp_bytes && r.d_gl_tmp.grow(plan.tmp_bytes))) return -1;
   HIP_OK(hipMemcpyAsync(r.d_gl_plan, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
-  e = launch_glyph_record(p, reinterpret_cast<const GlyphDesc *>(r.d_gl_plan), r.d_gl_plan + off_coef, plan.tmp_bytes ? r.d_gl_tmp : nullptr,
+  e = launch_glyph_record(p, reinterpret_cast<const GlyphDesc *>(r.d_gl_plan.get()), r.d_gl_plan + off_coef, plan.tmp_bytes ? r.d_gl_tmp : nullptr,
                           r.d_gl_rec, n, r.stream);
-  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_failed(what, e);
   return 0;
 }
 
@@ -5466,20 +5476,12 @@ int bnn_mi355x_glyphs_to_mnist(const uint8_t *pixels, int width, int height, int
   if (bind_device()) return -1;
   GlyphPlan plan;
   std::vector<int32_t> meta;
-  std::vector<uint8_t> staged((size_t)n * kGlyphRecord);
   DrainOnFailure drain;
   GlyphPicture p;
   if (enqueue_glyph_plane("glyphs_to_mnist", pixels, width, height, bands, row_stride, o, p) ||
-      enqueue_glyph_records("glyphs_to_mnist", p, boxes, n, o, plan, meta))
+      enqueue_glyph_records("glyphs_to_mnist", p, boxes, n, o, plan, meta) || download_glyph_records((size_t)n, plan.status, records, status))
     return -1;
-  HIP_OK(hipMemcpyAsync(staged.data(), r.d_gl_rec, staged.size(), hipMemcpyDeviceToHost, r.stream));
-  HIP_OK(hipStreamSynchronize(r.stream));
   drain.ok();
-  for (int i = 0; i < n; i++) {
-    // a status-2 glyph's record stays as the caller left it
-    if (plan.status[(size_t)i] != kGlyphTooThin) std::memcpy(records + (size_t)i * kGlyphRecord, staged.data() + (size_t)i * kGlyphRecord, kGlyphRecord);
-    if (status) status[i] = plan.status[(size_t)i];
-  }
   if (ink_boxes) std::memcpy(ink_boxes, plan.ink_boxes.data(), (size_t)n * 4 * sizeof(int32_t));
   return 0;
 }
@@ -5494,52 +5496,28 @@ int *bnn_mi355x_classify_glyphs(const uint8_t *pixels, int width, int height, in
   // (no output buffer of the caller's to check: the result array is the call's own)
   const std::string bad = validate_glyphs("classify_glyphs", pixels, width, height, bands, row_stride, boxes, n_boxes, opts ? &o : nullptr, pixels);
   if (!bad.empty()) { fail(bad); return nullptr; }
-  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
+  if (bad_number_class(number_class)) return nullptr;
   const int whole[4] = {0, 0, width, height};
   if (!boxes || n_boxes == 0) { boxes = whole; n_boxes = 1; }
   const int n = n_boxes;
   if (!ready()) return nullptr;
-  int *result = new (std::nothrow) int[(size_t)n];
-  if (!result) { fail("out of memory"); return nullptr; }
+  int *result = new_result((size_t)n);
+  if (!result) return nullptr;
   // everything that can fail from here on frees `result`
   auto run = [&]() -> int {
     if (bind_device()) return -1;
     GlyphPlan plan;
     std::vector<int32_t> meta;
-    std::vector<uint64_t> words;
     // the pass's workspaces first (they synchronise when they grow), so that nothing is allocated between the kernels
-    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n)) return -1;
-    for (hipEvent_t &e : r.gl_ev)
-      if (!e) HIP_OK(hipEventCreate(&e));
-    // up to 47 classes the last stage decodes on the device; beyond, the words come back and libm decodes them, as the
-    // reference does (bnn_mi355x_inference_device)
-    const bool on_device = number_class <= 47;
-    if (!on_device) words.resize((size_t)n);
+    if (reserve_results((size_t)n) || ensure_events(r.gl_ev, 3)) return -1;
     DrainOnFailure drain;
     GlyphPicture p;
     HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
     if (enqueue_glyph_plane("classify_glyphs", pixels, width, height, bands, row_stride, o, p) ||
-        enqueue_glyph_records("classify_glyphs", p, boxes, n, o, plan, meta))
+        enqueue_glyph_records("classify_glyphs", p, boxes, n, o, plan, meta) || classify_glyph_records(n, number_class, plan.status, result, status))
       return -1;
-    HIP_OK(hipEventRecord(r.gl_ev[1], r.stream));
-    // the pass bnn_mi355x_inference_device enqueues, on the same stream, on records that never left the device
-    if (bnn_mi355x_inference_device(r.d_gl_rec, n, number_class, on_device ? r.d_classes : nullptr, nullptr, r.d_words, r.stream)) return -1;
-    HIP_OK(hipEventRecord(r.gl_ev[2], r.stream));
-    if (on_device) HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
-    else HIP_OK(hipMemcpyAsync(words.data(), r.d_words, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
-    HIP_OK(hipStreamSynchronize(r.stream));
     drain.ok();
-    for (int i = 0; i < n; i++) {
-      if (!on_device) result[i] = lfc_class_batched(words[(size_t)i], number_class);
-      if (plan.status[(size_t)i] == kGlyphTooThin) result[i] = -1;  // its record was never written
-      if (status) status[i] = plan.status[(size_t)i];
-    }
-    float pre = 0.f, pass = 0.f;
-    HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
-    HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));
-    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
-    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
-    return 0;
+    return (usec_per_image(r.gl_ev[0], r.gl_ev[1], (size_t)n, usecPreprocess) || usec_per_image(r.gl_ev[1], r.gl_ev[2], (size_t)n, usecPerImage)) ? -1 : 0;
   };
   if (run()) { delete[] result; return nullptr; }
   return result;
@@ -5566,13 +5544,10 @@ constexpr size_t kFirstReadBack = 4096;  // components that come back with the c
 int reserve_components(int width, int height, bool labels) {
   Runtime &r = rt();
   const size_t n = (size_t)width * height, comps = max_components(width, height);
-  if (grow(r.d_cc_bits, r.cc_bits_cap, (size_t)height * cc_words_per_row(width)) || grow(r.d_cc_label, r.cc_label_cap, n) ||
-      grow(r.d_cc_stat, r.cc_stat_cap, comps) || grow(r.d_cc_list, r.cc_list_cap, kComponentHead + comps * 8) ||
-      (labels && (grow(r.d_cc_index, r.cc_index_cap, comps) || grow(r.d_cc_out, r.cc_out_cap, n))))
+  if (r.d_cc_bits.grow((size_t)height * cc_words_per_row(width)) || r.d_cc_label.grow(n) || r.d_cc_stat.grow(comps) ||
+      r.d_cc_list.grow(kComponentHead + comps * 8) || (labels && (r.d_cc_index.grow(comps) || r.d_cc_out.grow(n))))
     return -1;
-  for (hipEvent_t &e : r.cc_ev)
-    if (!e) HIP_OK(hipEventCreate(&e));
-  return 0;
+  return ensure_events(r.cc_ev, 2);
 }
 
 // Behind enqueue_glyph_plane, on r.stream: the six labelling launches, the call's round trip for the component list
@@ -5589,7 +5564,7 @@ int enqueue_components(const char *what, const GlyphPicture &p, const FindOpts &
   HIP_OK(hipEventRecord(r.cc_ev[0], r.stream));
   hipError_t e = launch_cc_label(c, f.ink_level, f.reach_x, f.reach_y, r.stream);
   if (e == hipSuccess) e = launch_cc_collect(c, r.d_cc_list, r.d_cc_stat, comps, f.min_pixels, r.stream);
-  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_failed(what, e);
   HIP_OK(hipEventRecord(r.cc_ev[1], r.stream));
   const size_t first = std::min((size_t)comps, kFirstReadBack);
   std::vector<int32_t> back(kComponentHead + first * 8);
@@ -5615,7 +5590,7 @@ int enqueue_components(const char *what, const GlyphPicture &p, const FindOpts &
     for (size_t k = 0; k < chosen.size(); k++) index[(size_t)chosen[k].id] = (int32_t)k;
     HIP_OK(hipMemcpyAsync(r.d_cc_index, index.data(), index.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
     e = launch_cc_relabel(c, r.d_cc_index, r.d_cc_out, r.stream);
-    if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+    if (e != hipSuccess) return launch_failed(what, e);
     HIP_OK(hipMemcpyAsync(labels, r.d_cc_out, (size_t)p.width * p.height * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
   }
   return 0;
@@ -5672,79 +5647,6 @@ int bnn_mi355x_find_glyphs(const uint8_t *pixels, int width, int height, int ban
   return (int)total;
 }
 
-int *bnn_mi355x_read_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
-                            const bnn_mi355x_find_opts *find, int number_class, int cap, int *n_found, int *boxes, float *usecPerImage,
-                            float *usecPreprocess, int *status) {
-  Runtime &r = rt();
-  if (usecPerImage) *usecPerImage = 0.f;
-  if (usecPreprocess) *usecPreprocess = 0.f;
-  if (r.spec.is_cnv) { fail(std::string("read_glyphs") + kGlyphsLfcOnly); return nullptr; }
-  const GlyphOpts o = glyph_opts(opts);
-  const FindOpts f = find_opts(find);
-  std::string bad = validate_glyphs("read_glyphs", pixels, width, height, bands, row_stride, nullptr, 0, opts ? &o : nullptr, n_found);
-  if (bad.empty()) bad = validate_find("read_glyphs", width, height, &f, boxes, cap);
-  if (!bad.empty()) { fail(bad); return nullptr; }
-  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
-  if (!ready()) return nullptr;
-  int *result = nullptr;
-  // everything that can fail from here on frees `result`
-  auto run = [&]() -> int {
-    if (bind_device()) return -1;
-    std::vector<Component> chosen;
-    std::vector<int32_t> index, meta, found;
-    std::vector<uint64_t> words;
-    GlyphPlan plan;
-    long total = 0;
-    if (reserve_components(width, height, false)) return -1;
-    for (hipEvent_t &e : r.gl_ev)
-      if (!e) HIP_OK(hipEventCreate(&e));
-    const bool on_device = number_class <= 47;  // (as classify_glyphs)
-    DrainOnFailure drain;
-    GlyphPicture p;
-    HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
-    if (enqueue_glyph_plane("read_glyphs", pixels, width, height, bands, row_stride, o, p) ||
-        enqueue_components("read_glyphs", p, f, cap, nullptr, chosen, total, index))
-      return -1;
-    const int n = (int)chosen.size();
-    result = new (std::nothrow) int[(size_t)(n > 0 ? n : 1)];
-    if (!result) return fail("out of memory");
-    *n_found = (int)total;
-    if (n == 0) {  // nothing to read: a non-null, empty result
-      HIP_OK(hipStreamSynchronize(r.stream));
-      drain.ok();
-      return 0;
-    }
-    found.resize((size_t)n * 4);
-    boxes_of(chosen, found.data(), nullptr);
-    // the stream is idle after the component list's round trip: the pass's workspaces grow without a second wait
-    if (reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n)) return -1;
-    if (!on_device) words.resize((size_t)n);
-    // the found boxes are boxes like any caller's: from here on this is classify_glyphs
-    if (enqueue_glyph_records("read_glyphs", p, found.data(), n, o, plan, meta)) return -1;
-    HIP_OK(hipEventRecord(r.gl_ev[1], r.stream));
-    if (bnn_mi355x_inference_device(r.d_gl_rec, n, number_class, on_device ? r.d_classes : nullptr, nullptr, r.d_words, r.stream)) return -1;
-    HIP_OK(hipEventRecord(r.gl_ev[2], r.stream));
-    if (on_device) HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
-    else HIP_OK(hipMemcpyAsync(words.data(), r.d_words, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
-    HIP_OK(hipStreamSynchronize(r.stream));
-    drain.ok();
-    for (int i = 0; i < n; i++) {
-      if (!on_device) result[i] = lfc_class_batched(words[(size_t)i], number_class);
-      if (plan.status[(size_t)i] == kGlyphTooThin) result[i] = -1;  // its record was never written
-      if (status) status[i] = plan.status[(size_t)i];
-    }
-    std::memcpy(boxes, found.data(), found.size() * sizeof(int));
-    float pre = 0.f, pass = 0.f;
-    HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
-    HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));
-    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
-    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
-    return 0;
-  };
-  if (run()) { delete[] result; return nullptr; }
-  return result;
-}
-
 }  // extern "C"
 
 // ---- a page: lines of text, glyphs masked to their own ink (LFC; page.h) --------------------------------------------
@@ -5781,27 +5683,26 @@ int enqueue_page_records(const char *what, const GlyphPicture &p, const GlyphOpt
   std::memcpy(pg.meta.data(), pg.plan.desc.data(), n * sizeof(GlyphDesc));
   std::memcpy(pg.meta.data() + off_keys, keys.data(), keys.size() * sizeof(int32_t));
   if (!pg.plan.coef.empty()) std::memcpy(pg.meta.data() + off_coef, pg.plan.coef.data(), pg.plan.coef.size() * sizeof(int32_t));
-  if (grow(r.d_gl_plan, r.gl_plan_cap, pg.meta.size()) || grow(r.d_gl_rec, r.gl_rec_cap, n * kGlyphRecord) ||
-      (pg.plan.tmp_bytes && grow(r.d_gl_tmp, r.gl_tmp_cap, pg.plan.tmp_bytes)))
-    return -1;
+  if (r.d_gl_plan.grow(pg.meta.size()) || r.d_gl_rec.grow(n * kGlyphRecord) || (pg.plan.tmp_bytes && r.d_gl_tmp.grow(pg.plan.tmp_bytes))) return -1;
   HIP_OK(hipMemcpyAsync(r.d_gl_plan, pg.meta.data(), pg.meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
-  const hipError_t e = launch_page_record(p, r.d_cc_label, reinterpret_cast<const GlyphDesc *>(r.d_gl_plan), r.d_gl_plan + off_keys,
+  const hipError_t e = launch_page_record(p, r.d_cc_label, reinterpret_cast<const GlyphDesc *>(r.d_gl_plan.get()), r.d_gl_plan + off_keys,
                                           r.d_gl_plan + off_coef, pg.plan.tmp_bytes ? r.d_gl_tmp : nullptr, r.d_gl_rec, (int)n, r.stream);
-  if (e != hipSuccess) return fail(std::string(what) + ": kernel launch: " + hipGetErrorString(e));
+  if (e != hipSuccess) return launch_failed(what, e);
   return 0;
 }
 
 // Upload, enhance, label, collect, the component list's round trip, the order (select_components' result, put into lines
 // when asked for, then the cap) and the records: k_page_record under the mask, else exactly read_glyphs' sequence on the
 // ordered boxes.  `classify`: the pass's workspaces are reserved while the stream is idle.  With no glyph nothing is
-// enqueued behind the round trip.
+// enqueued behind the round trip.  `total_early` (read_glyphs' n_found; may be null) is written as soon as the component
+// list is back.
 int enqueue_page(const char *what, const uint8_t *pixels, int width, int height, int bands, long row_stride, const GlyphOpts &o, const FindOpts &f,
-                 const PageOpts &g, int cap, bool classify, Page &pg) {
-  Runtime &r = rt();
+                 const PageOpts &g, int cap, bool classify, Page &pg, int *total_early = nullptr) {
   GlyphPicture p;
   if (enqueue_glyph_plane(what, pixels, width, height, bands, row_stride, o, p) ||
       enqueue_components(what, p, f, g.line_order ? INT_MAX : cap, nullptr, pg.chosen, pg.total, pg.index))
     return -1;
+  if (total_early) *total_early = (int)pg.total;
   if (g.line_order) {
     std::vector<int32_t> order;
     const std::string bad = order_lines(pg.chosen, g.word_gap, order, pg.line, pg.gap);
@@ -5820,17 +5721,63 @@ int enqueue_page(const char *what, const uint8_t *pixels, int width, int height,
   pg.found.resize((size_t)n * 4);
   boxes_of(pg.chosen, pg.found.data(), nullptr);
   if (n == 0) return 0;
-  if (classify && reserve_host(r.stage_cap > 0 ? r.stage_cap : 1, (size_t)n)) return -1;
+  if (classify && reserve_results((size_t)n)) return -1;
   if (g.mask) return enqueue_page_records(what, p, o, pg);
   return enqueue_glyph_records(what, p, pg.found.data(), n, o, pg.plan, pg.meta);
 }
 
+// (g null: read_glyphs, which has no page options to refuse)
 std::string validate_page_call(const char *what, const uint8_t *pixels, int width, int height, int bands, long row_stride, const GlyphOpts *o,
-                               const FindOpts &f, const PageOpts &g, const void *n_found, const void *boxes, int cap) {
+                               const FindOpts &f, const PageOpts *g, const void *n_found, const void *boxes, int cap) {
   std::string bad = validate_glyphs(what, pixels, width, height, bands, row_stride, nullptr, 0, o, n_found);
   if (bad.empty()) bad = validate_find(what, width, height, &f, boxes, cap);
-  if (bad.empty()) bad = validate_page(what, &g);
+  if (bad.empty() && g) bad = validate_page(what, g);
   return bad;
+}
+
+// bnn_mi355x_read_page, and bnn_mi355x_read_glyphs as the page with no mask and no line order (`page` null: its options are
+// not the caller's to get wrong, n_found is written as soon as the glyphs are counted, line and gap are null)
+int *read_page(const char *what, const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
+               const bnn_mi355x_find_opts *find, const PageOpts *page, int number_class, int cap, int *n_found, int *boxes, int *line, int *gap,
+               float *usecPerImage, float *usecPreprocess, int *status) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (r.spec.is_cnv) { fail(std::string(what) + kGlyphsLfcOnly); return nullptr; }
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  const PageOpts g = page ? *page : PageOpts{0, 0, 0};
+  const std::string bad = validate_page_call(what, pixels, width, height, bands, row_stride, opts ? &o : nullptr, f, page, n_found, boxes, cap);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (bad_number_class(number_class) || !ready()) return nullptr;
+  int *result = nullptr;
+  // everything that can fail from here on frees `result`
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    Page pg;
+    if (reserve_components(width, height, false) || ensure_events(r.gl_ev, 3)) return -1;
+    DrainOnFailure drain;
+    HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
+    if (enqueue_page(what, pixels, width, height, bands, row_stride, o, f, g, cap, true, pg, page ? nullptr : n_found)) return -1;
+    const int n = (int)pg.chosen.size();
+    if (!(result = new_result((size_t)n))) return -1;
+    *n_found = (int)pg.total;
+    if (n == 0) {  // nothing to read: a non-null, empty result
+      HIP_OK(hipStreamSynchronize(r.stream));
+      drain.ok();
+      return 0;
+    }
+    if (classify_glyph_records(n, number_class, pg.plan.status, result, status)) return -1;
+    drain.ok();
+    for (int i = 0; i < n; i++) {
+      if (line) line[i] = pg.line[(size_t)i];
+      if (gap) gap[i] = pg.gap[(size_t)i];
+    }
+    std::memcpy(boxes, pg.found.data(), pg.found.size() * sizeof(int));
+    return (usec_per_image(r.gl_ev[0], r.gl_ev[1], (size_t)n, usecPreprocess) || usec_per_image(r.gl_ev[1], r.gl_ev[2], (size_t)n, usecPerImage)) ? -1 : 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  return result;
 }
 
 }  // namespace
@@ -5866,7 +5813,7 @@ int bnn_mi355x_page_to_mnist(const uint8_t *pixels, int width, int height, int b
   const FindOpts f = find_opts(find);
   const PageOpts g = page_opts(page);
   // (two outputs of the caller's that must not be null, one test: n_found stands for both)
-  const std::string bad = validate_page_call("page_to_mnist", pixels, width, height, bands, row_stride, opts ? &o : nullptr, f, g,
+  const std::string bad = validate_page_call("page_to_mnist", pixels, width, height, bands, row_stride, opts ? &o : nullptr, f, &g,
                                              records ? n_found : nullptr, boxes, cap);
   if (!bad.empty()) return fail(bad);
   if (bind_device()) return -1;
@@ -5875,15 +5822,10 @@ int bnn_mi355x_page_to_mnist(const uint8_t *pixels, int width, int height, int b
   DrainOnFailure drain;
   if (enqueue_page("page_to_mnist", pixels, width, height, bands, row_stride, o, f, g, cap, false, pg)) return -1;
   const size_t n = pg.chosen.size();
-  std::vector<uint8_t> staged(n * kGlyphRecord);
-  if (n) HIP_OK(hipMemcpyAsync(staged.data(), r.d_gl_rec, staged.size(), hipMemcpyDeviceToHost, r.stream));
-  HIP_OK(hipStreamSynchronize(r.stream));
+  if (download_glyph_records(n, pg.plan.status, records, status)) return -1;
   drain.ok();
   *n_found = (int)pg.total;
   for (size_t i = 0; i < n; i++) {
-    // a status-2 glyph's record stays as the caller left it
-    if (pg.plan.status[i] != kGlyphTooThin) std::memcpy(records + i * kGlyphRecord, staged.data() + i * kGlyphRecord, kGlyphRecord);
-    if (status) status[i] = pg.plan.status[i];
     if (line) line[i] = pg.line[i];
     if (gap) gap[i] = pg.gap[i];
   }
@@ -5894,64 +5836,16 @@ int bnn_mi355x_page_to_mnist(const uint8_t *pixels, int width, int height, int b
 int *bnn_mi355x_read_page(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
                           const bnn_mi355x_find_opts *find, const bnn_mi355x_page_opts *page, int number_class, int cap, int *n_found, int *boxes,
                           int *line, int *gap, float *usecPerImage, float *usecPreprocess, int *status) {
-  Runtime &r = rt();
-  if (usecPerImage) *usecPerImage = 0.f;
-  if (usecPreprocess) *usecPreprocess = 0.f;
-  if (r.spec.is_cnv) { fail(std::string("read_page") + kGlyphsLfcOnly); return nullptr; }
-  const GlyphOpts o = glyph_opts(opts);
-  const FindOpts f = find_opts(find);
   const PageOpts g = page_opts(page);
-  const std::string bad = validate_page_call("read_page", pixels, width, height, bands, row_stride, opts ? &o : nullptr, f, g, n_found, boxes, cap);
-  if (!bad.empty()) { fail(bad); return nullptr; }
-  if (number_class < 1 || number_class > 64) { fail("number_class must be in 1..64"); return nullptr; }
-  if (!ready()) return nullptr;
-  int *result = nullptr;
-  // everything that can fail from here on frees `result`
-  auto run = [&]() -> int {
-    if (bind_device()) return -1;
-    Page pg;
-    std::vector<uint64_t> words;
-    if (reserve_components(width, height, false)) return -1;
-    for (hipEvent_t &e : r.gl_ev)
-      if (!e) HIP_OK(hipEventCreate(&e));
-    const bool on_device = number_class <= 47;  // (as classify_glyphs)
-    DrainOnFailure drain;
-    HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
-    if (enqueue_page("read_page", pixels, width, height, bands, row_stride, o, f, g, cap, true, pg)) return -1;
-    const int n = (int)pg.chosen.size();
-    result = new (std::nothrow) int[(size_t)(n > 0 ? n : 1)];
-    if (!result) return fail("out of memory");
-    *n_found = (int)pg.total;
-    if (n == 0) {  // nothing to read: a non-null, empty result
-      HIP_OK(hipStreamSynchronize(r.stream));
-      drain.ok();
-      return 0;
-    }
-    if (!on_device) words.resize((size_t)n);
-    HIP_OK(hipEventRecord(r.gl_ev[1], r.stream));
-    if (bnn_mi355x_inference_device(r.d_gl_rec, n, number_class, on_device ? r.d_classes : nullptr, nullptr, r.d_words, r.stream)) return -1;
-    HIP_OK(hipEventRecord(r.gl_ev[2], r.stream));
-    if (on_device) HIP_OK(hipMemcpyAsync(result, r.d_classes, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
-    else HIP_OK(hipMemcpyAsync(words.data(), r.d_words, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
-    HIP_OK(hipStreamSynchronize(r.stream));
-    drain.ok();
-    for (int i = 0; i < n; i++) {
-      if (!on_device) result[i] = lfc_class_batched(words[(size_t)i], number_class);
-      if (pg.plan.status[(size_t)i] == kGlyphTooThin) result[i] = -1;  // its record was never written
-      if (status) status[i] = pg.plan.status[(size_t)i];
-      if (line) line[i] = pg.line[(size_t)i];
-      if (gap) gap[i] = pg.gap[(size_t)i];
-    }
-    std::memcpy(boxes, pg.found.data(), pg.found.size() * sizeof(int));
-    float pre = 0.f, pass = 0.f;
-    HIP_OK(hipEventElapsedTime(&pre, r.gl_ev[0], r.gl_ev[1]));
-    HIP_OK(hipEventElapsedTime(&pass, r.gl_ev[1], r.gl_ev[2]));
-    if (usecPreprocess) *usecPreprocess = pre * 1000.f / (float)n;
-    if (usecPerImage) *usecPerImage = pass * 1000.f / (float)n;
-    return 0;
-  };
-  if (run()) { delete[] result; return nullptr; }
-  return result;
+  return read_page("read_page", pixels, width, height, bands, row_stride, opts, find, &g, number_class, cap, n_found, boxes, line, gap, usecPerImage,
+                   usecPreprocess, status);
+}
+
+int *bnn_mi355x_read_glyphs(const uint8_t *pixels, int width, int height, int bands, long row_stride, const bnn_mi355x_glyph_opts *opts,
+                            const bnn_mi355x_find_opts *find, int number_class, int cap, int *n_found, int *boxes, float *usecPerImage,
+                            float *usecPreprocess, int *status) {
+  return read_page("read_glyphs", pixels, width, height, bands, row_stride, opts, find, nullptr, number_class, cap, n_found, boxes, nullptr, nullptr,
+                   usecPerImage, usecPreprocess, status);
 }
 
 }  // extern "C"

@@ -61,6 +61,18 @@ def check_exports(network, runtime):
     assert exported == declared_symbols()
 
 
+@pytest.mark.parametrize("network", ["cnvW1A1", "lfcW1A1"])
+def test_deinit_of_an_unused_library_does_nothing(network):
+    """with nothing allocated (no test without a GPU allocates) deinit() returns without a device to talk to, and reports
+    nothing: last_error stays what it was"""
+    lib = ctypes.CDLL(gl.lib_path(network, "python_sw"))
+    lib.bnn_mi355x_last_error.restype = ctypes.c_char_p
+    before = lib.bnn_mi355x_last_error()
+    lib.deinit()
+    lib.deinit()
+    assert lib.bnn_mi355x_last_error() == before
+
+
 def test_no_gpu_fails_loudly(capfd):
     """without a HIP device the product must refuse to compute (no CPU fallback)"""
     try:

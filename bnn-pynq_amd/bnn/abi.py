@@ -48,7 +48,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_find_glyphs_host", "bnn_mi355x_find_glyphs", "bnn_mi355x_read_glyphs", "bnn_mi355x_last_find_usec",
        "bnn_mi355x_order_lines", "bnn_mi355x_page_to_mnist", "bnn_mi355x_read_page", "bnn_mi355x_scan_grid",
        "bnn_mi355x_scan_boxes", "bnn_mi355x_scan_planes", "bnn_mi355x_scan_device", "bnn_mi355x_scan_scene",
-       "bnn_mi355x_debug_scan_stage", "bnn_mi355x_scan_resize"]
+       "bnn_mi355x_debug_scan_stage", "bnn_mi355x_scan_resize", "bnn_mi355x_scan_clip", "bnn_mi355x_scan_clip_capacity",
+       "bnn_mi355x_scan_clip_layout", "bnn_mi355x_debug_scan_clip_stage"]
 
 
 class GlyphOpts(C.Structure):
@@ -319,6 +320,16 @@ def declare_extensions(L):
         L.bnn_mi355x_debug_scan_stage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, ip, ip]
         L.bnn_mi355x_debug_scan_stage.restype = C.c_long
         L.bnn_mi355x_scan_resize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "bnn_mi355x_scan_clip"):  # (likewise)
+        L.bnn_mi355x_scan_clip.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_void_p, fp, fp, C.c_int]
+        L.bnn_mi355x_scan_clip.restype = ip
+        L.bnn_mi355x_scan_clip_capacity.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.bnn_mi355x_scan_clip_layout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
+        L.bnn_mi355x_debug_scan_clip_stage.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int,
+                                                       C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_debug_scan_clip_stage.restype = C.c_long
 
 
 _cache = {}

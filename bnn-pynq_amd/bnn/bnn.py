@@ -1005,6 +1005,78 @@ class CnvClassifier:
             hit = scores[:, class_index] > min_score
         return [b for b, h in zip(bounds, hit) if h]
 
+    # -- extension: the clip scan -- all frames and pyramid levels of a clip in one set of launches ----------
+    @staticmethod
+    def _clip_frames(frames):
+        """(uint8 array [F, H, W] or [F, H, W, 3] for the device route, or None; the frames as a list)"""
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8 or frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] not in (3, 4)):
+                raise ValueError("a clip given as one array must be uint8 [F, H, W] (L), [F, H, W, 3] (RGB) or [F, H, W, 4] (RGBA)")
+            frames = list(frames)
+        else:
+            frames = list(frames)
+        if not frames:
+            raise ValueError("scan_clip: need one frame or more")
+        arrays = [f if isinstance(f, np.ndarray) else (np.asarray(f) if f.mode in ("RGB", "RGBA", "L") else None) for f in frames]
+        if any(a is None for a in arrays):
+            if any(isinstance(f, np.ndarray) or f.size != frames[0].size or f.mode != frames[0].mode for f in frames):
+                raise ValueError("scan_clip: the frames of a clip have one size and one mode")
+            return None, frames
+        if any(a.dtype != np.uint8 or a.shape != arrays[0].shape for a in arrays) or not (
+                arrays[0].ndim == 2 or (arrays[0].ndim == 3 and arrays[0].shape[2] in (3, 4))):
+            raise ValueError("scan_clip: the frames of a clip are uint8 pictures of one size and one mode")
+        if arrays[0].ndim == 3 and arrays[0].shape[2] == 4:  # RGBA: the host route of scan_scene, frame by frame
+            return None, frames
+        return np.ascontiguousarray(np.stack(arrays)), frames
+
+    def scan_clip(self, frames, sizes=(64, 96), details=False, max_frames=None):
+        """:meth:`scan_scene` of every frame of a clip -- a sequence of PIL images or uint8 arrays of one size and mode, or
+        one array ``[F, H, W(, 3)]`` -> (boxes int32 [n, 4], the same for every frame; classes [F, n] or scores
+        [F, n, len(classes)]).  On cnvW1A1 the clip goes up once and every (frame, level) map runs through ONE launch per
+        stage (``bnn_mi355x_scan_clip``: RGB and L frames); clips longer than one call accepts, or than ``max_frames``, go
+        in several calls and are joined.  Other networks, libraries without the entry point and RGBA frames loop over
+        :meth:`scan_scene`: the same answers by construction."""
+        clip, frames = self._clip_frames(frames)
+        ncls = len(self.classes)
+        if max_frames is not None and max_frames < 1:
+            raise ValueError("scan_clip: max_frames must be 1 or more")
+        lib = self._scan_lib()
+        if lib is None or clip is None or not hasattr(lib, "bnn_mi355x_scan_clip"):
+            res = [self.scan_scene(f, sizes, details) for f in frames]
+            return res[0][0], np.stack([r for _, r in res])
+        n_frames, height, width = clip.shape[:3]
+        boxes = np.concatenate([self.scan_boxes((width, height), s)[1] for s in sizes]) if len(sizes) else np.zeros((0, 4), np.int32)
+        sz = np.asarray(sizes, dtype=np.int32)
+        step = lib.bnn_mi355x_scan_clip_capacity(width, height, sz.ctypes.data, len(sz))
+        if step < 1:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        step = min(step, max_frames) if max_frames is not None else step
+        out = np.zeros((len(boxes), 4), np.int32)
+        parts, pre_us, pass_us = [], 0.0, 0.0
+        for first in range(0, n_frames, step):
+            part = clip[first:first + step]
+            usec, pre = ctypes.c_float(0), ctypes.c_float(0)
+            ptr = lib.bnn_mi355x_scan_clip(part.ctypes.data, len(part), 0, width, height, 1 if clip.ndim == 3 else 3, 0, sz.ctypes.data, len(sz), ncls,
+                                           out.ctypes.data, ctypes.byref(usec), ctypes.byref(pre), 1 if details else 0)
+            if not ptr:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            n = len(part) * len(boxes)
+            parts.append(self.bnn._collect(ptr, n * (ncls if details else 1)).reshape((len(part), len(boxes), ncls) if details else (len(part), len(boxes))))
+            pre_us += pre.value * n
+            pass_us += usec.value * n
+        total = n_frames * len(boxes)
+        self.usecPerImage = self.bnn.usecPerImage = pass_us / total if total else 0.0
+        self.usecPreprocess = pre_us / total if total else 0.0
+        return out, np.concatenate(parts)
+
+    def locate_clip(self, frames, class_index, sizes=(64, 96), min_score=None):
+        """:meth:`locate` with ``dense=True`` for every frame of a clip (:meth:`scan_clip`) -> a list, per frame, of the
+        windows (left, upper, right, lower) whose class is ``class_index`` -- or, with ``min_score``, whose score for it
+        exceeds ``min_score``"""
+        boxes, res = self.scan_clip(frames, sizes, details=min_score is not None)
+        hits = (res == class_index) if min_score is None else (res[:, :, class_index] > min_score)
+        return [[tuple(int(v) for v in b) for b, h in zip(boxes, hit) if h] for hit in hits]
+
     # extension
     def classify_array(self, images, detail=False):
         result = self.bnn.inference_array(images, detail)

@@ -56,6 +56,8 @@
 #include "windows.h"
 #include "scan_kernels.h"
 #include "scan.h"
+#include "scan_clip_kernels.h"
+#include "scan_clip.h"
 #include "component_kernels.h"
 #include "components.h"
 #include "glyph_kernels.h"
@@ -353,6 +355,9 @@ struct Runtime {
   DeviceBuf<uint8_t> d_scan_planes, d_scan_scene, d_scan_tmp, d_scan_buf0, d_scan_buf1;
   DeviceBuf<int32_t> d_scan_coef;
   std::vector<hipEvent_t> scan_ev;
+  // the clip scan (bnn_mi355x_scan_clip*; scan_clip.h) shares the scan's buffers -- d_scan_scene holds the clip, d_scan_planes
+  // every level's planes of every frame -- and adds the stage launches' lookup tables (one upload per call)
+  DeviceBuf<int32_t> d_scan_clip_tab;
   // one picture and N boxes -> MNIST-format records / classes (bnn_mi355x_enhance_picture, bnn_mi355x_glyphs_to_mnist,
   // bnn_mi355x_classify_glyphs; LFC): the picture, its L plane, boxes + found ink boxes, descriptors + tables, the global
   // temporary of glyphs past the LDS budget, the 784-byte records, the plane's pixel sum; time stamps as win_ev
@@ -5343,6 +5348,214 @@ int bnn_mi355x_scan_resize(const uint8_t *pixels, int width, int height, int ban
   HIP_OK(hipStreamSynchronize(r.stream));
   drain.ok();
   return 0;
+}
+
+}  // extern "C"
+
+// ---- the clip scan: all frames and levels of a clip through one launch per stage (cnvW1A1; scan_clip.h) ---------------
+namespace bnn {
+namespace {
+
+static_assert(kScanClipMaxFrames == BNN_MI355X_SCAN_CLIP_MAX_FRAMES && kScanClipMaxBytes == BNN_MI355X_SCAN_CLIP_MAX_BYTES,
+              "the header states the clip scan's limits");
+
+// what one clip call keeps alive until its stream is idle (declared before the call's DrainOnFailure)
+struct ClipJob {
+  ClipTables tables;
+  std::vector<int32_t> coef;
+  std::vector<ResizeTables> tabs;
+  size_t tmp_frame = 1;  // bytes of one frame's first resize pass, the largest of the levels
+};
+
+// every workspace of a clip call (grow-only; the map buffers are the scan's and grow as they do, behind a device
+// synchronise), and the level's Lanczos tables, built once for all frames
+int reserve_clip(const ClipPlan &p, ClipJob &job) {
+  Runtime &r = rt();
+  clip_tables(p, job.tables);
+  job.tabs.assign(p.scene.levels.size(), ResizeTables{});
+  for (size_t k = 0; k < p.scene.levels.size(); k++) {
+    const ScanLevel &lv = p.scene.levels[k];
+    if (!lv.resized) continue;
+    job.tabs[k] = resize_tables(p.width, p.height, lv.level_w, lv.level_h, job.coef);
+    job.tmp_frame = std::max(job.tmp_frame, resize_tmp_bytes(p.width, p.height, p.bands, lv.level_w, lv.level_h));
+  }
+  ScanPlan maps;
+  maps.buf0 = p.buf0; maps.buf1 = p.buf1;
+  return (r.d_scan_scene.grow((size_t)p.width * p.height * p.bands * p.frames) || r.d_scan_planes.grow(p.planes_bytes) ||
+          r.d_scan_tmp.grow(job.tmp_frame * p.frames) || r.d_scan_coef.grow(job.coef.size() + 1) ||
+          r.d_scan_clip_tab.grow(job.tables.words.size()) || reserve_scan(maps))
+             ? -1 : 0;
+}
+
+// Enqueues on r.stream the upload of the clip to packed frames at r.d_scan_scene: one copy when the frames (or all rows)
+// lie evenly apart, else one 2-D copy a frame
+int upload_clip(const ClipPlan &p, const uint8_t *pixels) {
+  Runtime &r = rt();
+  const size_t row_bytes = (size_t)p.width * p.bands, frame_bytes = row_bytes * p.height;
+  const size_t rows_apart = p.row_stride ? (size_t)p.row_stride : row_bytes, frames_apart = p.frame_stride ? (size_t)p.frame_stride : rows_apart * p.height;
+  if (rows_apart == row_bytes) {  // packed rows: a frame is one run of bytes
+    if (frames_apart == frame_bytes) HIP_OK(hipMemcpyAsync(r.d_scan_scene, pixels, frame_bytes * p.frames, hipMemcpyHostToDevice, r.stream));
+    else HIP_OK(hipMemcpy2DAsync(r.d_scan_scene, frame_bytes, pixels, frames_apart, frame_bytes, (size_t)p.frames, hipMemcpyHostToDevice, r.stream));
+    return 0;
+  }
+  if (frames_apart == rows_apart * p.height)  // the rows of all frames lie one stride apart
+    return upload_rows(r.d_scan_scene, pixels, row_bytes, (long)rows_apart, p.height * p.frames);
+  for (int f = 0; f < p.frames; f++)
+    if (upload_rows(r.d_scan_scene + (size_t)f * frame_bytes, pixels + (size_t)f * frames_apart, row_bytes, (long)rows_apart, p.height)) return -1;
+  return 0;
+}
+
+// Enqueues on r.stream: the upload of the clip and of the tables, the resizes of every level (one pair of launches a level
+// for all frames), then stages 0..min(last_stage, 5) over all maps (run_scan_clip) and, for last_stage >= 6, stages 6..8 with
+// the decode ONCE on all windows.  mid (may be null) is recorded between the resizes and the stages.  The caller has
+// validated, bound the device and reserved (reserve_clip, reserve_results).
+int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const uint8_t *pixels, int ncls, int32_t *d_classes, int16_t *d_scores,
+                 hipEvent_t mid, int last_stage) {
+  Runtime &r = rt();
+  if (p.buf0 > r.d_scan_buf0.cap || p.buf1 > r.d_scan_buf1.cap || p.planes_bytes > r.d_scan_planes.cap || job.tables.words.size() > r.d_scan_clip_tab.cap ||
+      job.tmp_frame * p.frames > r.d_scan_tmp.cap)
+    return fail(std::string(what) + ": internal: the clip exceeds the scan workspace");
+  if (settle_handover(r.stream)) return -1;
+  if (upload_clip(p, pixels)) return -1;
+  if (!job.coef.empty()) HIP_OK(hipMemcpyAsync(r.d_scan_coef, job.coef.data(), job.coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  HIP_OK(hipMemcpyAsync(r.d_scan_clip_tab, job.tables.words.data(), job.tables.words.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  const size_t frame_bytes = (size_t)p.width * p.height * p.bands;
+  for (size_t k = 0; k < p.scene.levels.size(); k++) {
+    const ScanLevel &lv = p.scene.levels[k];
+    // (a level of the frames' own size: the same kernels only re-lay it out, as in scan_scene)
+    ScanClipResize j{};
+    j.src = r.d_scan_scene; j.frames = p.frames; j.w = p.width; j.h = p.height; j.bands = p.bands;
+    j.stride = (long)p.width * p.bands; j.src_frame = (long)frame_bytes;
+    j.out_w = lv.level_w; j.out_h = lv.level_h;
+    j.vertical_first = vertical_pass_first(p.width, p.height, lv.level_h);
+    set_tables(j, r.d_scan_coef, job.tabs[k]);
+    j.tmp = r.d_scan_tmp; j.tmp_frame = (long)job.tmp_frame;
+    j.planes = r.d_scan_planes + p.level_planes[k];
+    const hipError_t e = launch_clip_resize(j, r.stream);
+    if (e != hipSuccess) return launch_failed(what, e);
+  }
+  if (mid) HIP_OK(hipEventRecord(mid, r.stream));
+  ScanClipLaunch a{};
+  a.planes = r.d_scan_planes; a.buf0 = r.d_scan_buf0; a.buf1 = r.d_scan_buf1;
+  for (int l = 0; l < kScanStages; l++) {
+    a.rows[l] = r.rows[l];
+    a.desc[l] = job.tables.desc[l]; a.block_map[l] = job.tables.block_map[l]; a.blocks[l] = p.blocks[l];
+  }
+  a.tables = r.d_scan_clip_tab;
+  a.stream = r.stream;
+  a.last_stage = last_stage < kScanStages - 1 ? last_stage : kScanStages - 1;
+  hipError_t e = run_scan_clip(a);
+  if (e == hipSuccess && last_stage >= kScanStages) {
+    CnvLaunch c{};
+    c.n = (int)p.windows; c.buf0 = r.d_scan_buf0; c.buf1 = r.d_scan_buf1;
+    for (int l = 0; l < 9; l++) c.rows[l] = r.rows[l];
+    set_forms(c);
+    c.scores = d_scores; c.classes = d_classes; c.number_class = ncls; c.stream = r.stream;
+    c.first_stage = kScanStages; c.last_stage = last_stage;
+    e = run_cnv(r.spec.id, c);
+  }
+  if (e != hipSuccess) return launch_failed(what, e);
+  return 0;
+}
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_scan_clip_capacity(int width, int height, const int *sizes, int n_sizes) {
+  const std::string no = scan_refused("scan_clip_capacity");
+  if (!no.empty()) return fail(no);
+  std::string why;
+  const int cap = scan_clip_capacity("scan_clip_capacity", width, height, sizes, n_sizes, why);
+  if (cap < 1) { fail(why); return 0; }
+  return cap;
+}
+
+int bnn_mi355x_scan_clip_layout(int width, int height, const int *sizes, int n_sizes, int n_frames, int *map_w, int *map_h, long *offsets,
+                                long *first, int *level_size, long *buf_bytes) {
+  const std::string no = scan_refused("scan_clip_layout");
+  if (!no.empty()) return fail(no);
+  // (plan_clip with a stand-in for the pointers it checks: RGB frames, packed)
+  ClipPlan p;
+  const std::string bad = plan_clip("scan_clip_layout", sizes ? (const void *)&p : nullptr, n_frames, 0, width, height, 3, 0, sizes, n_sizes, &p, p);
+  if (!bad.empty()) return fail(bad);
+  for (size_t m = 0; m < p.maps.size(); m++) {
+    const ClipMap &cm = p.maps[m];
+    const ScanLevel &lv = p.scene.levels[(size_t)cm.level];
+    for (int s = 0; s < kScanStages; s++) {
+      if (map_w) map_w[m * kScanStages + s] = lv.plan.w[s];
+      if (map_h) map_h[m * kScanStages + s] = lv.plan.h[s];
+      if (offsets) offsets[m * kScanStages + s] = (long)cm.off[s];
+    }
+    if (first) first[m] = cm.first;
+    if (level_size) level_size[m] = lv.size;
+  }
+  if (buf_bytes) { buf_bytes[0] = (long)p.buf0; buf_bytes[1] = (long)p.buf1; }
+  return (int)p.maps.size();
+}
+
+int *bnn_mi355x_scan_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                          const int *sizes, int n_sizes, int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess,
+                          int enable_detail) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  const std::string no = scan_refused("scan_clip");
+  if (!no.empty()) { fail(no); return nullptr; }
+  ClipPlan plan;
+  const std::string bad = plan_clip("scan_clip", pixels, n_frames, frame_stride, width, height, bands, row_stride, sizes, n_sizes, boxes_out, plan);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (bad_number_class(number_class)) return nullptr;
+  if (!ready()) return nullptr;
+  const size_t n = (size_t)plan.windows;
+  int *result = new_result(n * (enable_detail ? number_class : 1));
+  if (!result) return nullptr;
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    std::vector<int16_t> scores;
+    ClipJob job;  // (outlives its asynchronous uploads: declared before `drain`)
+    // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
+    if (reserve_results(n) || reserve_clip(plan, job) || ensure_events(r.scan_ev, 3)) return -1;
+    if (enable_detail) scores.resize(n * 64);
+    DrainOnFailure drain;
+    HIP_OK(hipEventRecord(r.scan_ev[0], r.stream));
+    if (enqueue_clip("scan_clip", plan, job, pixels, number_class, enable_detail ? nullptr : r.d_classes, enable_detail ? r.d_scores : nullptr,
+                     r.scan_ev[1], kCnvStages - 1))
+      return -1;
+    HIP_OK(hipEventRecord(r.scan_ev[2], r.stream));
+    if (enqueue_cnv_results(n, result, scores)) return -1;
+    HIP_OK(hipStreamSynchronize(r.stream));
+    drain.ok();
+    widen_scores(scores, number_class, result);
+    return (usec_per_image(r.scan_ev[0], r.scan_ev[1], n, usecPreprocess) || usec_per_image(r.scan_ev[1], r.scan_ev[2], n, usecPerImage)) ? -1 : 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  // (the boxes are the same for every frame: one frame's, exactly what scan_scene writes)
+  for (const ScanLevel &lv : plan.scene.levels) scan_boxes(width, height, lv.size, boxes_out + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
+  return result;
+}
+
+long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                                      const int *sizes, int n_sizes, int stage, void *out, size_t cap) {
+  Runtime &r = rt();
+  const std::string no = scan_refused("debug_scan_clip_stage");
+  if (!no.empty()) return fail(no);
+  if (!out || stage < 0 || stage >= kScanStages) return fail("debug_scan_clip_stage: bad arguments");
+  ClipPlan plan;
+  const std::string bad = plan_clip("debug_scan_clip_stage", pixels, n_frames, frame_stride, width, height, bands, row_stride, sizes, n_sizes, out, plan);
+  if (!bad.empty()) return fail(bad);
+  const size_t bytes = plan.stage_bytes[stage];
+  if (cap < bytes) return fail("debug_scan_clip_stage: the stage's maps take " + std::to_string(bytes) + " bytes");
+  if (!ready() || bind_device()) return -1;
+  ClipJob job;
+  if (reserve_clip(plan, job)) return -1;
+  DrainOnFailure drain;
+  if (enqueue_clip("debug_scan_clip_stage", plan, job, pixels, 1, nullptr, nullptr, nullptr, stage)) return -1;
+  HIP_OK(hipMemcpyAsync(out, (stage & 1) ? r.d_scan_buf1 : r.d_scan_buf0, bytes, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  return (long)bytes;
 }
 
 }  // extern "C"

@@ -850,6 +850,50 @@ long bnn_mi355x_debug_scan_stage(const uint8_t *planes, int width, int height, i
 int bnn_mi355x_scan_resize(const uint8_t *pixels, int width, int height, int bands, long row_stride, int out_w, int out_h,
                            uint8_t *planes);
 
+/* Scan a clip: n_frames pictures of ONE size (a video, a camera feed) and n_sizes window sizes in one call, every (frame,
+ * level) map through ONE launch per stage of layers 0-5 and layers 6-8 with the decode ONCE on all windows
+ * (csrc/scan_clip_kernels.hip; the model: csrc/scan_clip.h, DESIGN.md 9 "Clip scan").  The levels, grids and boxes are
+ * scan_scene's, and frame f of a result equals, bit for bit on all 64 raw scores, what bnn_mi355x_scan_scene returns for
+ * frame f; with n_frames = 1 the call merges the levels of one scene.  cnvW1A1 libraries only, refused elsewhere in the
+ * scan's two messages.
+ *   clip:      frames of interleaved uint8, bands 1 ("L") or 3 ("RGB") as for scan_scene; rows row_stride bytes apart
+ *              (0 = packed), frames frame_stride bytes apart (0 = packed: height rows at the row stride); a frame stride
+ *              shorter than that is refused.
+ *   maps:      map m = f * n_sizes + k is frame f at sizes[k].  Results are frame-major, then size-major, then raster:
+ *              the windows of map m are [first[m], first[m] + nx_k * ny_k), first the running sum in map order.
+ *   layout:    stage s (0..5) of map m lies at byte offset off[s][m] of buffer s & 1, off[s][m] the sum of the bytes of
+ *              the earlier maps of that stage ([map_h][map_w][dwords] each, as debug_scan_stage describes them); every
+ *              offset is a multiple of 8 and off[5][m] = 32 first[m].
+ * scan_clip: one upload of the clip; per level ONE pair of resize launches for all frames (Pillow's LANCZOS, byte for byte,
+ *       as scan_scene; the frames share the level's tables); six stage launches; layers 6-8 and the decode once.  Returns a
+ *       `new int[]` of windows classes (or, with enable_detail, number_class scores per window), return convention and
+ *       ownership as scan_scene (free with free_results).  boxes_out receives ONE frame's boxes, exactly what scan_scene
+ *       writes (they are the same for every frame).  usecPerImage: the device time of the stages per window;
+ *       usecPreprocess (may be NULL): the upload's and the resizes'.
+ * scan_clip_capacity: host only.  The largest n_frames one scan_clip call accepts for RGB frames of this size with these
+ *       window sizes (L frames: at least as many); 0 + last_error when even one frame is refused, -1 + last_error on a
+ *       library that does not scan.
+ * scan_clip_layout: host only.  Returns the number of maps M = n_frames * n_sizes (-1 + last_error when the clip is
+ *       refused) and writes, each pointer optional: map_w, map_h and offsets as [M][6] (map m, stage s at m * 6 + s), first
+ *       and level_size (the map's window size) as [M], buf_bytes[2] the bytes of the two map buffers.
+ * debug_scan_clip_stage: test hook, the twin of debug_scan_stage: runs the resizes and stages 0..stage on the clip and
+ *       copies that stage's whole buffer region -- every map packed as the layout says -- to out; returns the bytes, or -1
+ *       (cap too small included).
+ * Limits, refused before anything touches the GPU: every frame and every level stays inside the scan's per-picture limits;
+ * n_frames outside 1 .. BNN_MI355X_SCAN_CLIP_MAX_FRAMES; more than BNN_MI355X_SCAN_MAX_WINDOWS windows over all maps; either
+ * map buffer above BNN_MI355X_SCAN_MAX_MAP_BYTES; an uploaded clip (n_frames x width x height x bands) above
+ * BNN_MI355X_SCAN_CLIP_MAX_BYTES; what scan_scene refuses, in its words.  Workspaces are grow-only and shared with the scan's. */
+#define BNN_MI355X_SCAN_CLIP_MAX_FRAMES 4096
+#define BNN_MI355X_SCAN_CLIP_MAX_BYTES 1073741824
+int *bnn_mi355x_scan_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                          const int *sizes, int n_sizes, int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess,
+                          int enable_detail);
+int bnn_mi355x_scan_clip_capacity(int width, int height, const int *sizes, int n_sizes);
+int bnn_mi355x_scan_clip_layout(int width, int height, const int *sizes, int n_sizes, int n_frames, int *map_w, int *map_h, long *offsets,
+                                long *first, int *level_size, long *buf_bytes);
+long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                                      const int *sizes, int n_sizes, int stage, void *out, size_t cap);
+
 /* Read handwriting(LFC-BNN_MNIST_Webcam.ipynb and LFC-BNN_Chars_Webcam.ipynb, cells 9-13): ONE picture and N boxes
  * become N MNIST-format records (28 x 28 bytes) -- and, with classify_glyphs, N classes -- in one call.  The notebooks
  * do this by hand with PIL for one camera frame, through two temporary files; here the picture goes to the device once

@@ -5095,6 +5095,19 @@ int reserve_scan(const ScanPlan &p) {
   return (r.d_scan_buf0.grow(p.buf0) || r.d_scan_buf1.grow(p.buf1)) ? -1 : 0;
 }
 
+// The tail of a scan, enqueued on s: stages 6..last_stage with the decode on the layer-5 maps of n windows that the scan's
+// stages left in r.d_scan_buf0/1 (run_cnv from first_stage 6: their matrix forms included)
+hipError_t run_scan_tail(int n, int ncls, int32_t *d_classes, int16_t *d_scores, hipStream_t s, int last_stage) {
+  Runtime &r = rt();
+  CnvLaunch c{};
+  c.n = n; c.buf0 = r.d_scan_buf0; c.buf1 = r.d_scan_buf1;
+  for (int l = 0; l < 9; l++) c.rows[l] = r.rows[l];
+  set_forms(c);
+  c.scores = d_scores; c.classes = d_classes; c.number_class = ncls; c.stream = s;
+  c.first_stage = kScanStages; c.last_stage = last_stage;
+  return run_cnv(r.spec.id, c);
+}
+
 // Enqueues on s: stages 0..min(last_stage, 5) over the picture (run_scan) and, for last_stage >= 6, the existing stages
 // 6..8 with the decode on its nx * ny layer-5 pixels (run_cnv from first_stage 6: their matrix forms included).  The
 // caller has validated, bound the device and reserved the maps.
@@ -5110,15 +5123,7 @@ int enqueue_scan(const char *what, const uint8_t *d_planes, long row_stride, lon
   a.stream = s;
   a.last_stage = last_stage < kScanStages - 1 ? last_stage : kScanStages - 1;
   hipError_t e = run_scan(a);
-  if (e == hipSuccess && last_stage >= kScanStages) {
-    CnvLaunch c{};
-    c.n = p.nx * p.ny; c.buf0 = r.d_scan_buf0; c.buf1 = r.d_scan_buf1;
-    for (int l = 0; l < 9; l++) c.rows[l] = r.rows[l];
-    set_forms(c);
-    c.scores = d_scores; c.classes = d_classes; c.number_class = ncls; c.stream = s;
-    c.first_stage = kScanStages; c.last_stage = last_stage;
-    e = run_cnv(r.spec.id, c);
-  }
+  if (e == hipSuccess && last_stage >= kScanStages) e = run_scan_tail(p.nx * p.ny, ncls, d_classes, d_scores, s, last_stage);
   if (e != hipSuccess) return launch_failed(what, e);
   return 0;
 }
@@ -5445,15 +5450,7 @@ int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const 
   a.stream = r.stream;
   a.last_stage = last_stage < kScanStages - 1 ? last_stage : kScanStages - 1;
   hipError_t e = run_scan_clip(a);
-  if (e == hipSuccess && last_stage >= kScanStages) {
-    CnvLaunch c{};
-    c.n = (int)p.windows; c.buf0 = r.d_scan_buf0; c.buf1 = r.d_scan_buf1;
-    for (int l = 0; l < 9; l++) c.rows[l] = r.rows[l];
-    set_forms(c);
-    c.scores = d_scores; c.classes = d_classes; c.number_class = ncls; c.stream = r.stream;
-    c.first_stage = kScanStages; c.last_stage = last_stage;
-    e = run_cnv(r.spec.id, c);
-  }
+  if (e == hipSuccess && last_stage >= kScanStages) e = run_scan_tail((int)p.windows, ncls, d_classes, d_scores, r.stream, last_stage);
   if (e != hipSuccess) return launch_failed(what, e);
   return 0;
 }

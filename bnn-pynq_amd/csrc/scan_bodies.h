@@ -1,8 +1,8 @@
-// The loop bodies of the clip scan's kernels (scan_clip_kernels.hip): what a lane of scan_kernels.hip does once it knows
-// its item, as __device__ __forceinline__ functions that take the item.  They are COPIES of the bodies of k_scan_conv0,
-// k_scan_quad, k_scan_vec, k_scan_resize_h and k_scan_resize_v, statement for statement, as those are copies of
-// kernels.hip's: moving the originals here changed the instruction stream of build/scan_kernels.o (operand order of a
-// few scalar adds, inverted loop branches, the schedule of k_scan_resize_v's head), so scan_kernels.hip stays what it is.
+// The lane bodies of the dense scan (scan_kernels.hip) and of the clip scan (scan_clip_kernels.hip), stated once: what a
+// lane does once it knows its item, as __device__ __forceinline__ functions that take the item, and the order of the two
+// resize passes (resize_route, host).  The two kernel files differ only in how a lane finds its item and its map.  The
+// neuron loops are copies of k_conv0's, k_quad_x's and k_vec_x's, statement for statement: the shipped bodies
+// (kernels.hip) are pinned by build tests and stay where they are (see the comment above vec_x_group there).
 //
 // The mapping is that of DESIGN.md 5: one lane owns one output pixel (layers 0, 4, 5) or one 2 x 2 quad (layers 1-3; the
 // pool is a min over the quad before the sign), `cg` picks the group of 32 neurons, whose rows are wave-uniform and come
@@ -19,7 +19,7 @@ typedef const uint32_t __attribute__((address_space(4))) *kptr32;  // scalar (co
 
 constexpr int kBlock = 256;
 
-// ---- the helpers of kernels.hip these loops are written with (copies, as in scan_kernels.hip) ----
+// ---- the helpers of kernels.hip these loops are written with (copies: that file's are in its anonymous namespace) ----
 // uint8 p -> int8 q = p - 128 + (p >= 128) - (p == 255), four bytes at a time
 __device__ __forceinline__ uint32_t quantise4(uint32_t p) {
   const uint32_t t = p ^ 0x80808080u;
@@ -251,6 +251,27 @@ __device__ __forceinline__ void resize_v_item(const uint8_t *__restrict__ src, l
 }
 
 inline dim3 grid_of(long items) { return dim3((unsigned)((items + kBlock - 1) / kBlock)); }
+
+// ---- the order of the passes of Image.resize((out_w, out_h)) of an h x w x bands picture, rows `stride` bytes apart ------
+// A pass reads the picture or (from_tmp) the pass before it in `tmp`, packed rows.  horizontal: the resize_h kernel with
+// the horizontal tables over `extent` rows, `out` = out_w; else the resize_v kernel with the vertical tables over
+// `extent` columns, `out` = out_h, which only re-lays its source out where !vertical.
+struct ResizePass { bool horizontal, from_tmp; long items, pitch; int extent, out, vertical; ResizeOut o; };
+struct ResizeRoute { int n; ResizePass pass[2]; };
+inline ResizeRoute resize_route(int w, int h, int bands, int out_w, int out_h, bool vertical_first, long stride, uint8_t *tmp, uint8_t *planes) {
+  const bool horizontal = out_w != w, vertical = out_h != h;
+  const ResizeOut planar{planes, (long)out_w * out_h, out_w, 1, bands == 1 ? 1 : 0};
+  if (horizontal && vertical && vertical_first) {
+    const ResizeOut mid{tmp, 1, (long)w * bands, bands, 0};
+    return {2, {{false, false, (long)out_h * w, stride, w, out_h, 1, mid}, {true, true, (long)out_h * out_w, mid.row, out_h, out_w, 0, planar}}};
+  }
+  // a pass whose size does not change is skipped; the vertical kernel always runs last, for the planar layout
+  // (Pillow runs the horizontal pass over the rows the vertical pass will read; over all rows it gives the same samples)
+  const ResizeOut mid{tmp, 1, (long)out_w * bands, bands, 0};
+  const ResizePass first{true, false, (long)h * out_w, stride, h, out_w, 0, mid};
+  const ResizePass last{false, horizontal, (long)out_h * out_w, horizontal ? mid.row : stride, out_w, out_h, vertical ? 1 : 0, planar};
+  return horizontal ? ResizeRoute{2, {first, last}} : ResizeRoute{1, {last}};
+}
 
 }  // namespace
 }  // namespace bnn

@@ -26,7 +26,8 @@ struct ScanClipLaunch {
 hipError_t run_scan_clip(const ScanClipLaunch &a);
 
 // launch_scan_resize (scan_kernels.h) for `frames` pictures of one size at once: blockIdx.y is the frame, the frames
-// share the level's tables.  Pass order, skipped passes and the re-layout of an unresized level are launch_scan_resize's.
+// share the level's tables.  Pass order, skipped passes and the re-layout of an unresized level are launch_scan_resize's:
+// both launchers ask resize_route (scan_bodies.h) for the passes.
 struct ScanClipResize {
   const uint8_t *src;  // device, frames x h x w x bands, rows `stride` bytes and frames `src_frame` bytes apart; read only
   int frames, w, h, bands;

@@ -5,10 +5,10 @@
 // map having ceil(items / 256) blocks of its own.  A block reads its map's number from the stage's block -> map table
 // and the map's descriptor (ClipMapDesc: input and output offsets, widths, item count, first block) from the stage's
 // descriptor table; both reads are wave-uniform and go through scalar loads, like the neuron rows.  Lanes past the
-// map's item count return.  From there on a lane does exactly what it does in scan_kernels.hip: the bodies
-// (scan_clip_bodies.h) are copies of that file's.  No LDS, no scratch.
+// map's item count return.  From there on a lane does exactly what it does in scan_kernels.hip: both files call the
+// bodies of scan_bodies.h, and the order of the resize passes is that header's too.  No LDS, no scratch.
 #include "scan_clip_kernels.h"
-#include "scan_clip_bodies.h"
+#include "scan_bodies.h"
 
 namespace bnn {
 namespace {
@@ -102,33 +102,19 @@ hipError_t run_scan_clip(const ScanClipLaunch &a) {
 hipError_t launch_clip_resize(const ScanClipResize &j, hipStream_t s) {
   if ((j.bands != 1 && j.bands != 3) || j.w < 1 || j.h < 1 || j.out_w < 1 || j.out_h < 1 || j.frames < 1 || j.frames > kScanClipMaxFrames)
     return hipErrorInvalidValue;
-  const bool horizontal = j.out_w != j.w, vertical = j.out_h != j.h;
-  const long plane = (long)j.out_w * j.out_h;
-  const ResizeOut planar{j.planes, plane, j.out_w, 1, j.bands == 1 ? 1 : 0};
-  const uint8_t *in = j.src;
-  long pitch = j.stride, in_frame = j.src_frame;
-  auto grid = [&](long items) { dim3 g = grid_of(items); g.y = (unsigned)j.frames; return g; };
-#define CLIP_RESIZE(kern, items, ...)                                                                             \
-  do {                                                                                                            \
-    if (j.bands == 3) hipLaunchKernelGGL(kern<3>, grid(items), dim3(kBlock), 0, s, __VA_ARGS__);                   \
-    else hipLaunchKernelGGL(kern<1>, grid(items), dim3(kBlock), 0, s, __VA_ARGS__);                                \
-  } while (0)
-  if (horizontal && vertical && j.vertical_first) {
-    const ResizeOut mid{j.tmp, 1, (long)j.w * j.bands, j.bands, 0};
-    CLIP_RESIZE(k_clip_resize_v, (long)j.out_h * j.w, in, pitch, in_frame, j.w, j.out_h, j.kv, j.bv, j.ksize_v, 1, mid, j.tmp_frame);
-    CLIP_RESIZE(k_clip_resize_h, (long)j.out_h * j.out_w, j.tmp, mid.row, j.tmp_frame, j.out_h, j.out_w, j.kh, j.bh, j.ksize_h, planar, 3 * plane);
-    return hipGetLastError();
+  const auto vertical = j.bands == 3 ? k_clip_resize_v<3> : k_clip_resize_v<1>;
+  const auto horizontal = j.bands == 3 ? k_clip_resize_h<3> : k_clip_resize_h<1>;
+  const ResizeRoute r = resize_route(j.w, j.h, j.bands, j.out_w, j.out_h, j.vertical_first, j.stride, j.tmp, j.planes);
+  for (int i = 0; i < r.n; i++) {
+    const ResizePass &p = r.pass[i];
+    // the frame strides of a pass's source and of its output: tmp's, else the clip's and that of the three planes
+    const uint8_t *src = p.from_tmp ? j.tmp : j.src;
+    const long src_frame = p.from_tmp ? j.tmp_frame : j.src_frame, out_frame = p.o.dst == j.tmp ? j.tmp_frame : 3 * p.o.plane;
+    dim3 grid = grid_of(p.items);
+    grid.y = (unsigned)j.frames;
+    if (p.horizontal) hipLaunchKernelGGL(horizontal, grid, dim3(kBlock), 0, s, src, p.pitch, src_frame, p.extent, p.out, j.kh, j.bh, j.ksize_h, p.o, out_frame);
+    else hipLaunchKernelGGL(vertical, grid, dim3(kBlock), 0, s, src, p.pitch, src_frame, p.extent, p.out, j.kv, j.bv, j.ksize_v, p.vertical, p.o, out_frame);
   }
-  if (horizontal) {
-    const ResizeOut mid{j.tmp, 1, (long)j.out_w * j.bands, j.bands, 0};
-    CLIP_RESIZE(k_clip_resize_h, (long)j.h * j.out_w, in, pitch, in_frame, j.h, j.out_w, j.kh, j.bh, j.ksize_h, mid, j.tmp_frame);
-    in = j.tmp;
-    pitch = mid.row;
-    in_frame = j.tmp_frame;
-  }
-  CLIP_RESIZE(k_clip_resize_v, (long)j.out_h * j.out_w, in, pitch, in_frame, j.out_w, j.out_h, j.kv, j.bv, j.ksize_v, vertical ? 1 : 0, planar,
-              3 * plane);
-#undef CLIP_RESIZE
   return hipGetLastError();
 }
 

@@ -66,6 +66,24 @@ def test_the_stated_lds_bound():
         assert re.search(r"constexpr int kScanLdsBytes = 0;", f.read())
 
 
+def test_the_lane_bodies_are_stated_once():
+    """the neuron loops, the popcount helpers and clip8 stand in csrc/scan_bodies.h and in no other scan file; the dense
+    scan's and the clip scan's kernel files both include it"""
+    import glob
+    csrc = os.path.join(ROOT, "bnn-pynq_amd", "csrc")
+    files = sorted(f for ext in ("h", "hip", "cpp") for f in glob.glob(os.path.join(csrc, "scan*." + ext)))
+    text = {}
+    for f in files:
+        with open(f) as fh:
+            text[os.path.basename(f)] = fh.read()
+    assert "scan_bodies.h" in text and "scan_kernels.hip" in text and "scan_clip_kernels.hip" in text
+    for needle in ("__builtin_amdgcn_sdot4", "v_bcnt_u32_b32"):
+        assert [f for f in text if needle in text[f]] == ["scan_bodies.h"], needle
+    assert [f for f in text if re.search(r"^[^/\n]*\bclip8\(uint32_t \w+\) \{", text[f], re.M)] == ["scan_bodies.h"]
+    for f in ("scan_kernels.hip", "scan_clip_kernels.hip"):
+        assert '#include "scan_bodies.h"' in text[f], f
+
+
 def test_kernel_objects_are_separate_translation_units():
     """the Makefile and tools/build_variant.sh link the scan kernels' object, and the host-only model's, next to the older
     ones, whose rules do not depend on the new files (kernels.o is what it was but for run_cnv's first_stage)"""

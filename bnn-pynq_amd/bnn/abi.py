@@ -49,7 +49,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_order_lines", "bnn_mi355x_page_to_mnist", "bnn_mi355x_read_page", "bnn_mi355x_scan_grid",
        "bnn_mi355x_scan_boxes", "bnn_mi355x_scan_planes", "bnn_mi355x_scan_device", "bnn_mi355x_scan_scene",
        "bnn_mi355x_debug_scan_stage", "bnn_mi355x_scan_resize", "bnn_mi355x_scan_clip", "bnn_mi355x_scan_clip_capacity",
-       "bnn_mi355x_scan_clip_layout", "bnn_mi355x_debug_scan_clip_stage"]
+       "bnn_mi355x_scan_clip_layout", "bnn_mi355x_debug_scan_clip_stage", "bnn_mi355x_detect_windows_host",
+       "bnn_mi355x_detect_windows", "bnn_mi355x_detect_clip"]
 
 
 class GlyphOpts(C.Structure):
@@ -66,6 +67,12 @@ class FindOpts(C.Structure):
 class PageOpts(C.Structure):
     """``bnn_mi355x_page_opts``"""
     _fields_ = [("mask", C.c_int), ("line_order", C.c_int), ("word_gap", C.c_int)]
+
+
+class DetectOpts(C.Structure):
+    """``bnn_mi355x_detect_opts``"""
+    _fields_ = [("class_mask", C.c_uint64), ("by_score", C.c_int), ("min_score", C.c_int), ("iou_num", C.c_int), ("iou_den", C.c_int),
+                ("max_candidates", C.c_int), ("max_det", C.c_int)]
 
 
 def lib_path(network, runtime="python_sw", lib_dir=None):
@@ -330,6 +337,12 @@ def declare_extensions(L):
         L.bnn_mi355x_debug_scan_clip_stage.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int,
                                                        C.c_int, C.c_void_p, C.c_size_t]
         L.bnn_mi355x_debug_scan_clip_stage.restype = C.c_long
+    if hasattr(L, "bnn_mi355x_detect_clip"):  # (likewise)
+        do = C.POINTER(DetectOpts)
+        L.bnn_mi355x_detect_windows_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, do, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bnn_mi355x_detect_windows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, do, C.c_void_p, C.c_void_p, C.c_void_p, fp]
+        L.bnn_mi355x_detect_clip.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, do,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, fp, fp, fp]
 
 
 _cache = {}

@@ -1077,6 +1077,111 @@ class CnvClassifier:
         hits = (res == class_index) if min_score is None else (res[:, :, class_index] > min_score)
         return [[tuple(int(v) for v in b) for b, h in zip(boxes, hit) if h] for hit in hits]
 
+    # -- extension: detections -- threshold, order and non-maximum suppression on the windows of a scan ----------
+    def _detect_opts(self, classes, min_score, by_score, iou, max_det, max_candidates):
+        """``bnn_mi355x_detect_opts`` of the Python arguments: ``classes`` None (all of ``self.classes``), an int or an
+        iterable; ``iou`` a float, taken as ``round(iou * 65536) / 65536``, or an exact ``(num, den)`` pair"""
+        if classes is None:
+            wanted = range(len(self.classes))
+        else:
+            wanted = [classes] if isinstance(classes, (int, np.integer)) else list(classes)
+        mask = 0
+        for c in wanted:
+            if not 0 <= int(c) < 64:
+                raise ValueError("detect: class %r is outside 0..63" % (c,))
+            mask |= 1 << int(c)
+        num, den = (int(iou[0]), int(iou[1])) if isinstance(iou, (tuple, list)) else (int(round(float(iou) * 65536)), 65536)
+        return abi.DetectOpts(mask, 1 if by_score else 0, -32769 if min_score is None else int(min_score), num, den, int(max_candidates),
+                              int(max_det))
+
+    @staticmethod
+    def _detections(dets, counts):
+        """per frame a list of ((left, upper, right, lower), class, score)"""
+        return [[(tuple(int(v) for v in d[:4]), int(d[4]), int(d[5])) for d in frame[:k]] for frame, k in zip(dets, counts)]
+
+    def suppress(self, boxes, scores, classes=None, min_score=None, by_score=False, iou=0.5, max_det=64, max_candidates=4096):
+        """the detections among windows the caller has classified: ``boxes`` [n, 4] of ONE frame and ``scores`` [n, ncls]
+        (or [F, n, ncls] for F frames that share the boxes), e.g. :meth:`tile_boxes` and :meth:`classify_windows_details`
+        -> a list of ``((left, upper, right, lower), class, score)``, best first (for [F, n, ncls] one list per frame).  A
+        window is a candidate when its class -- its argmax, or with ``by_score`` the ONE class of ``classes`` whatever its
+        argmax -- is among ``classes`` and its score for that class exceeds ``min_score``; candidates are walked by score
+        and kept unless an already kept one of the same class overlaps them with an IoU above ``iou``.  On the device where
+        the library has ``bnn_mi355x_detect_windows``, else on the host: the same answers by construction.  After a call
+        ``self.n_candidates`` holds, per frame, how many windows passed ``min_score`` (above ``max_candidates``: a cut)."""
+        lib = self.bnn.interface
+        b = self._boxes(boxes)
+        s = np.ascontiguousarray(np.asarray(scores, dtype=np.int32))
+        single = s.ndim == 2
+        s = s[None] if single else s
+        if s.ndim != 3 or s.shape[1] != len(b):
+            raise ValueError("suppress: scores must be [n, ncls] or [F, n, ncls] for the n boxes given")
+        if not hasattr(lib, "bnn_mi355x_detect_windows_host"):
+            raise RuntimeError("suppress: the library has no bnn_mi355x_detect_windows_host")
+        frames, n, ncls = s.shape
+        o = self._detect_opts(classes if classes is not None else range(ncls), min_score, by_score, iou, max_det, max_candidates)
+        dets = np.zeros((frames, max(o.max_det, 1), 8), np.int32)
+        counts, ncand = np.zeros(frames, np.int32), np.zeros(frames, np.int32)
+        args = [b.ctypes.data, n, s.ctypes.data, frames, ncls, ctypes.byref(o), dets.ctypes.data, counts.ctypes.data, ncand.ctypes.data]
+        on_device = lib.bnn_mi355x_network().decode().startswith("cnv")
+        rc = lib.bnn_mi355x_detect_windows(*(args + [None])) if on_device else lib.bnn_mi355x_detect_windows_host(*args)
+        if rc != 0:
+            raise ValueError(lib.bnn_mi355x_last_error().decode())
+        self.n_candidates = ncand.tolist()
+        found = self._detections(dets, counts)
+        return found[0] if single else found
+
+    def detect_clip(self, frames, classes=None, sizes=(64, 96), min_score=None, by_score=False, iou=0.5, max_det=64, max_candidates=4096,
+                    max_frames=None):
+        """where the objects are in every frame of a clip: :meth:`scan_clip` followed by :meth:`suppress` -> per frame a
+        list of ``((left, upper, right, lower), class, score)``, best first.  On cnvW1A1 one call per piece of the clip
+        (``bnn_mi355x_detect_clip``: RGB and L frames): the scan's launches, then the detection kernels on the scores where
+        the scan left them, and only the lists come back; long clips are cut by the call's capacity and ``max_frames`` as
+        in :meth:`scan_clip`.  Other networks, libraries without the entry point and RGBA frames take
+        ``scan_clip(details=True)`` and :meth:`suppress`: the same answers by construction."""
+        if max_frames is not None and max_frames < 1:
+            raise ValueError("detect_clip: max_frames must be 1 or more")
+        ncls = len(self.classes)
+        o = self._detect_opts(classes, min_score, by_score, iou, max_det, max_candidates)
+        lib = self._scan_lib()
+        clip, listed = self._clip_frames(frames)
+        if lib is None or clip is None or not hasattr(lib, "bnn_mi355x_detect_clip"):
+            boxes, scores = self.scan_clip(listed, sizes, details=True, max_frames=max_frames)
+            wanted = [k for k in range(64) if (o.class_mask >> k) & 1]
+            return self.suppress(boxes, scores, wanted, o.min_score, by_score, (o.iou_num, o.iou_den), max_det, max_candidates)
+        n_frames, height, width = clip.shape[:3]
+        sz = np.asarray(sizes, dtype=np.int32)
+        step = lib.bnn_mi355x_scan_clip_capacity(width, height, sz.ctypes.data, len(sz))
+        if step < 1:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        step = min(step, max_frames) if max_frames is not None else step
+        found, ncand, pre_us, pass_us, det_us, windows = [], [], 0.0, 0.0, 0.0, 0
+        n = sum(len(self.scan_boxes((width, height), s)[1]) for s in sizes)
+        for first in range(0, n_frames, step):
+            part = clip[first:first + step]
+            dets = np.zeros((len(part), max(o.max_det, 1), 8), np.int32)
+            counts, nc = np.zeros(len(part), np.int32), np.zeros(len(part), np.int32)
+            usec, pre, det = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
+            rc = lib.bnn_mi355x_detect_clip(part.ctypes.data, len(part), 0, width, height, 1 if clip.ndim == 3 else 3, 0, sz.ctypes.data, len(sz),
+                                            ncls, ctypes.byref(o), dets.ctypes.data, counts.ctypes.data, nc.ctypes.data, ctypes.byref(usec),
+                                            ctypes.byref(pre), ctypes.byref(det))
+            if rc != 0:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            found += self._detections(dets, counts)
+            ncand += nc.tolist()
+            pre_us += pre.value * n * len(part)
+            pass_us += usec.value * n * len(part)
+            det_us += det.value * len(part)
+            windows += n * len(part)
+        self.usecPerImage = self.bnn.usecPerImage = pass_us / windows if windows else 0.0
+        self.usecPreprocess = pre_us / windows if windows else 0.0
+        self.usecDetect = det_us / n_frames
+        self.n_candidates = ncand
+        return found
+
+    def detect(self, img, classes=None, sizes=(64, 96), **kwargs):
+        """:meth:`detect_clip` on one picture -> a list of ``((left, upper, right, lower), class, score)``"""
+        return self.detect_clip([img], classes, sizes, **kwargs)[0]
+
     # extension
     def classify_array(self, images, detail=False):
         result = self.bnn.inference_array(images, detail)

@@ -58,6 +58,7 @@
 #include "scan.h"
 #include "scan_clip_kernels.h"
 #include "scan_clip.h"
+#include "detect_kernels.h"
 #include "component_kernels.h"
 #include "components.h"
 #include "glyph_kernels.h"
@@ -358,6 +359,13 @@ struct Runtime {
   // the clip scan (bnn_mi355x_scan_clip*; scan_clip.h) shares the scan's buffers -- d_scan_scene holds the clip, d_scan_planes
   // every level's planes of every frame -- and adds the stage launches' lookup tables (one upload per call)
   DeviceBuf<int32_t> d_scan_clip_tab;
+  // the detections (bnn_mi355x_detect_windows, bnn_mi355x_detect_clip; detect.h): the uploaded scores of detect_windows, a
+  // key per window, one frame's packed boxes, and dets + counts + n_candidates of all frames; time stamps around the launches
+  DeviceBuf<int16_t> d_det_scores;
+  DeviceBuf<uint32_t> d_det_keys;
+  DeviceBuf<uint64_t> d_det_boxes;
+  DeviceBuf<int32_t> d_det_out;
+  hipEvent_t det_ev[2] = {nullptr, nullptr};
   // one picture and N boxes -> MNIST-format records / classes (bnn_mi355x_enhance_picture, bnn_mi355x_glyphs_to_mnist,
   // bnn_mi355x_classify_glyphs; LFC): the picture, its L plane, boxes + found ink boxes, descriptors + tables, the global
   // temporary of glyphs past the LDS budget, the 784-byte records, the plane's pixel sum; time stamps as win_ev
@@ -5553,6 +5561,130 @@ long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long 
   HIP_OK(hipStreamSynchronize(r.stream));
   drain.ok();
   return (long)bytes;
+}
+
+}  // extern "C"
+
+// ---- detections: threshold, top-K and non-maximum suppression on the windows of a scan (CNV; detect.h) ----------------
+namespace bnn {
+namespace {
+
+static_assert(sizeof(DetectOpts) == sizeof(bnn_mi355x_detect_opts) && offsetof(DetectOpts, max_det) == offsetof(bnn_mi355x_detect_opts, max_det),
+              "DetectOpts is bnn_mi355x_detect_opts");
+static_assert(kDetectMaxCandidates == BNN_MI355X_DETECT_MAX_CANDIDATES && kDetectMaxWindows == BNN_MI355X_SCAN_MAX_WINDOWS &&
+                  kDetectMaxFrames == BNN_MI355X_SCAN_CLIP_MAX_FRAMES,
+              "the header states the detections' limits");
+
+// the workspaces of one detection call (grow-only) and one frame's boxes as the kernels hold them
+int reserve_detect(const int *boxes, size_t n, int frames, const DetectOpts &o, std::vector<uint64_t> &packed) {
+  Runtime &r = rt();
+  packed.resize(n);
+  for (size_t i = 0; i < n; i++) packed[i] = detect_pack_box(boxes + 4 * i);
+  return (r.d_det_keys.grow(n * frames) || r.d_det_boxes.grow(n) || r.d_det_out.grow((size_t)frames * ((size_t)o.max_det * kDetectFields + 2)) ||
+          ensure_events(r.det_ev, 2))
+             ? -1 : 0;
+}
+
+// Enqueues on r.stream: the upload of the boxes, the two detection launches between det_ev[0] and det_ev[1] on the scores
+// (and classes, when the decode left them) of frames x n windows in HBM, and the lists' way back.  `packed` outlives the call's wait.
+int enqueue_detect(const char *what, const std::vector<uint64_t> &packed, int frames, int ncls, const DetectOpts &o, const int16_t *d_scores,
+                   const int32_t *d_classes, int *dets, int *counts, int *n_candidates) {
+  Runtime &r = rt();
+  const size_t n = packed.size(), det_ints = (size_t)frames * o.max_det * kDetectFields;
+  if (n * frames > r.d_det_keys.cap || n > r.d_det_boxes.cap || det_ints + 2 * (size_t)frames > r.d_det_out.cap)
+    return fail(std::string(what) + ": internal: the call exceeds the detection workspace");
+  HIP_OK(hipMemcpyAsync(r.d_det_boxes, packed.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, r.stream));
+  HIP_OK(hipEventRecord(r.det_ev[0], r.stream));
+  DetectLaunch a{};
+  a.scores = d_scores; a.classes = d_classes; a.boxes = r.d_det_boxes; a.keys = r.d_det_keys;
+  a.dets = r.d_det_out; a.counts = r.d_det_out + det_ints; a.n_candidates = r.d_det_out + det_ints + frames;
+  a.n = (int)n; a.frames = frames; a.number_class = ncls; a.opts = o; a.stream = r.stream;
+  const hipError_t e = run_detect(a);
+  if (e != hipSuccess) return launch_failed(what, e);
+  HIP_OK(hipEventRecord(r.det_ev[1], r.stream));
+  HIP_OK(hipMemcpyAsync(dets, a.dets, det_ints * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipMemcpyAsync(counts, a.counts, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipMemcpyAsync(n_candidates, a.n_candidates, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  return 0;
+}
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_detect_windows_host(const int *boxes, int n, const int *scores, int frames, int number_class, const bnn_mi355x_detect_opts *opts,
+                                   int *dets, int *counts, int *n_candidates) {
+  const DetectOpts *o = reinterpret_cast<const DetectOpts *>(opts);
+  const std::string bad = validate_detect("detect_windows_host", boxes, n, scores, frames, number_class, o, dets, counts, n_candidates);
+  if (!bad.empty()) return fail(bad);
+  detect_windows(boxes, n, scores, frames, number_class, *o, dets, counts, n_candidates);
+  return 0;
+}
+
+int bnn_mi355x_detect_windows(const int *boxes, int n, const int *scores, int frames, int number_class, const bnn_mi355x_detect_opts *opts,
+                              int *dets, int *counts, int *n_candidates, float *usecDetect) {
+  Runtime &r = rt();
+  if (usecDetect) *usecDetect = 0.f;
+  if (!r.spec.is_cnv) return fail("detect_windows: the scores of a window are the output of the CNV networks only");
+  const DetectOpts *o = reinterpret_cast<const DetectOpts *>(opts);
+  const std::string bad = validate_detect("detect_windows", boxes, n, scores, frames, number_class, o, dets, counts, n_candidates);
+  if (!bad.empty()) return fail(bad);
+  if (bind_device()) return -1;
+  // the scores as the decode kernels leave them: 64 int16 a window
+  const size_t windows = (size_t)n * frames;
+  std::vector<int16_t> rows(windows * 64, 0);
+  for (size_t i = 0; i < windows; i++)
+    for (int c = 0; c < number_class; c++) rows[i * 64 + c] = (int16_t)scores[i * number_class + c];
+  std::vector<uint64_t> packed;
+  if (reserve_detect(boxes, (size_t)n, frames, *o, packed) || r.d_det_scores.grow(windows * 64)) return -1;
+  DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+  HIP_OK(hipMemcpyAsync(r.d_det_scores, rows.data(), rows.size() * sizeof(int16_t), hipMemcpyHostToDevice, r.stream));
+  if (enqueue_detect("detect_windows", packed, frames, number_class, *o, r.d_det_scores, nullptr, dets, counts, n_candidates)) return -1;
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  return usec_per_image(r.det_ev[0], r.det_ev[1], (size_t)frames, usecDetect);
+}
+
+int bnn_mi355x_detect_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                           const int *sizes, int n_sizes, int number_class, const bnn_mi355x_detect_opts *opts, int *dets, int *counts,
+                           int *n_candidates, float *usecPerImage, float *usecPreprocess, float *usecDetect) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (usecDetect) *usecDetect = 0.f;
+  const std::string no = scan_refused("detect_clip");
+  if (!no.empty()) return fail(no);
+  ClipPlan plan;
+  // (plan_clip refuses a null boxes_out: the boxes stay in this call, dets stands in for the check)
+  const std::string bad = plan_clip("detect_clip", pixels, n_frames, frame_stride, width, height, bands, row_stride, sizes, n_sizes, dets, plan);
+  if (!bad.empty()) return fail(bad);
+  if (!dets) return fail("detect_clip: dets is null");
+  if (!counts) return fail("detect_clip: counts is null");
+  if (!n_candidates) return fail("detect_clip: n_candidates is null");
+  const DetectOpts *o = reinterpret_cast<const DetectOpts *>(opts);
+  const std::string bad_opts = validate_detect_opts("detect_clip", number_class, o);
+  if (!bad_opts.empty()) return fail(bad_opts);
+  if (!ready()) return -1;
+  const size_t windows = (size_t)plan.windows, n = windows / (size_t)plan.frames;
+  std::vector<int> boxes(4 * n);
+  for (const ScanLevel &lv : plan.scene.levels) scan_boxes(width, height, lv.size, boxes.data() + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
+  if (bind_device()) return -1;
+  ClipJob job;  // (outlives its asynchronous uploads: declared before `drain`)
+  std::vector<uint64_t> packed;
+  // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
+  if (reserve_results(windows) || reserve_clip(plan, job) || reserve_detect(boxes.data(), n, plan.frames, *o, packed) || ensure_events(r.scan_ev, 3))
+    return -1;
+  DrainOnFailure drain;
+  HIP_OK(hipEventRecord(r.scan_ev[0], r.stream));
+  if (enqueue_clip("detect_clip", plan, job, pixels, number_class, r.d_classes, r.d_scores, r.scan_ev[1], kCnvStages - 1)) return -1;
+  HIP_OK(hipEventRecord(r.scan_ev[2], r.stream));
+  if (enqueue_detect("detect_clip", packed, plan.frames, number_class, *o, r.d_scores, r.d_classes, dets, counts, n_candidates)) return -1;
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  return (usec_per_image(r.scan_ev[0], r.scan_ev[1], windows, usecPreprocess) || usec_per_image(r.scan_ev[1], r.scan_ev[2], windows, usecPerImage) ||
+          usec_per_image(r.det_ev[0], r.det_ev[1], (size_t)plan.frames, usecDetect))
+             ? -1 : 0;
 }
 
 }  // extern "C"

@@ -894,6 +894,52 @@ int bnn_mi355x_scan_clip_layout(int width, int height, const int *sizes, int n_s
 long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
                                       const int *sizes, int n_sizes, int stage, void *out, size_t cap);
 
+/* Detect objects: the windows of a frame and their scores become a short list of boxes, each with a class and a score --
+ * threshold, order, cap and greedy non-maximum suppression, on the device (csrc/detect_kernels.hip; the model:
+ * csrc/detect.h, DESIGN.md 9 "Detections").  The model is this project's own (the reference notebook draws every window
+ * that fires, CNV-BNN_Road-Signs.ipynb cells 14 and 16); it is pure integer, and the device results equal the host's
+ * byte for byte.
+ *   inputs:    per frame n windows with a box (left, upper, right, lower) each -- 0 <= left < right <= 65535, likewise
+ *              upper < lower; ONE frame's boxes, shared by all frames -- and number_class scores each.
+ *   class:     by_score = 0: the decode's class (the first strict maximum over the first number_class scores, floored at
+ *              0: scores <= 0 never beat class 0).  by_score = 1: class_mask has exactly one bit k and the class is k
+ *              whatever the argmax (cell 16's rule, result[i][14] > 455).
+ *   candidate: the class is in class_mask and score[class] > min_score (-32769 admits every window).
+ *   order:     score descending, then window index ascending (size-major, then raster, as everywhere in the scan).  Only
+ *              the first max_candidates take part; n_candidates[f] counts all that passed, so a cut is visible.
+ *   suppress:  walk the order and keep a candidate unless an already kept candidate OF THE SAME CLASS has
+ *              inter * iou_den > iou_num * union (strictly, 64-bit integers); iou_num == iou_den never suppresses.  Stop
+ *              after max_det kept candidates.
+ *   output:    dets [frames][max_det][8]: left, upper, right, lower, class, score, window index in the frame, window
+ *              size (right - left); the rows of a frame past counts[f] are zero.  counts, n_candidates: [frames].
+ * detect_windows_host: the model on the host; any library, no GPU.  scores: int [frames][n][number_class], what every
+ *       *_details call returns; values outside int16 are refused.  Returns 0, -1 + last_error.
+ * detect_windows: the same arguments through the kernels on uploaded boxes and scores; only the lists come back.  CNV
+ *       libraries (all three; no parameters need be loaded).  usecDetect (may be NULL): the device time of the detection
+ *       launches per frame.
+ * detect_clip: scan_clip's upload, resizes, six stage launches and layers 6-8 with the decode writing classes AND scores,
+ *       then the detection launches on the same stream; nothing but dets, counts and n_candidates is downloaded.  One
+ *       scene is a clip of one frame.  cnvW1A1 only, refused elsewhere in the scan's words; whatever scan_clip refuses is
+ *       refused here.  usecPerImage, usecPreprocess: as scan_clip; usecDetect: as detect_windows.
+ * Refused before anything touches the GPU, the message naming the argument: null pointers; frames outside 1 ..
+ * BNN_MI355X_SCAN_CLIP_MAX_FRAMES; n below 1 or n x frames above BNN_MI355X_SCAN_MAX_WINDOWS; number_class outside 1..64;
+ * a class_mask of 0 or with a bit at or above number_class; by_score other than 0 / 1, or 1 with several bits in the
+ * mask; iou_den outside 1 .. 65536; iou_num outside 0 .. iou_den; max_candidates outside 1 ..
+ * BNN_MI355X_DETECT_MAX_CANDIDATES; max_det outside 1 .. max_candidates; an empty, inverted or out-of-range box; a score
+ * outside int16.  Workspaces are grow-only. */
+#define BNN_MI355X_DETECT_MAX_CANDIDATES 4096
+typedef struct {
+  uint64_t class_mask;
+  int by_score, min_score, iou_num, iou_den, max_candidates, max_det;
+} bnn_mi355x_detect_opts;
+int bnn_mi355x_detect_windows_host(const int *boxes, int n, const int *scores, int frames, int number_class, const bnn_mi355x_detect_opts *opts,
+                                   int *dets, int *counts, int *n_candidates);
+int bnn_mi355x_detect_windows(const int *boxes, int n, const int *scores, int frames, int number_class, const bnn_mi355x_detect_opts *opts,
+                              int *dets, int *counts, int *n_candidates, float *usecDetect);
+int bnn_mi355x_detect_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                           const int *sizes, int n_sizes, int number_class, const bnn_mi355x_detect_opts *opts, int *dets, int *counts,
+                           int *n_candidates, float *usecPerImage, float *usecPreprocess, float *usecDetect);
+
 /* Read handwriting(LFC-BNN_MNIST_Webcam.ipynb and LFC-BNN_Chars_Webcam.ipynb, cells 9-13): ONE picture and N boxes
  * become N MNIST-format records (28 x 28 bytes) -- and, with classify_glyphs, N classes -- in one call.  The notebooks
  * do this by hand with PIL for one camera frame, through two temporary files; here the picture goes to the device once

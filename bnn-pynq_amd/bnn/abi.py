@@ -50,7 +50,17 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_scan_boxes", "bnn_mi355x_scan_planes", "bnn_mi355x_scan_device", "bnn_mi355x_scan_scene",
        "bnn_mi355x_debug_scan_stage", "bnn_mi355x_scan_resize", "bnn_mi355x_scan_clip", "bnn_mi355x_scan_clip_capacity",
        "bnn_mi355x_scan_clip_layout", "bnn_mi355x_debug_scan_clip_stage", "bnn_mi355x_detect_windows_host",
-       "bnn_mi355x_detect_windows", "bnn_mi355x_detect_clip"]
+       "bnn_mi355x_detect_windows", "bnn_mi355x_detect_clip", "bnn_mi355x_unpack_frames_host", "bnn_mi355x_unpack_frames",
+       "bnn_mi355x_scan_clip_frames", "bnn_mi355x_detect_clip_frames", "bnn_mi355x_scan_clip_device", "bnn_mi355x_detect_clip_device"]
+
+# bnn_mi355x_frames.format by name (include/bnn_mi355x.h, BNN_MI355X_FORMAT_*)
+PIXEL_FORMATS = {"rgb": 0, "l": 1, "bgr": 2, "nv12": 3, "i420": 4, "yuyv": 5}
+
+
+class Frames(C.Structure):
+    """``bnn_mi355x_frames``"""
+    _fields_ = [("format", C.c_int), ("range", C.c_int), ("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int),
+                ("row_stride", C.c_long), ("frame_stride", C.c_long)]
 
 
 class GlyphOpts(C.Structure):
@@ -343,6 +353,17 @@ def declare_extensions(L):
         L.bnn_mi355x_detect_windows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, do, C.c_void_p, C.c_void_p, C.c_void_p, fp]
         L.bnn_mi355x_detect_clip.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, do,
                                              C.c_void_p, C.c_void_p, C.c_void_p, fp, fp, fp]
+    if hasattr(L, "bnn_mi355x_detect_clip_frames"):  # (likewise)
+        do, fr = C.POINTER(DetectOpts), C.POINTER(Frames)
+        L.bnn_mi355x_unpack_frames_host.argtypes = [fr, C.c_void_p, C.c_void_p]
+        L.bnn_mi355x_unpack_frames.argtypes = [fr, C.c_void_p, C.c_void_p, fp]
+        L.bnn_mi355x_scan_clip_frames.argtypes = [fr, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, fp, fp, C.c_int]
+        L.bnn_mi355x_scan_clip_frames.restype = ip
+        L.bnn_mi355x_detect_clip_frames.argtypes = [fr, C.c_void_p, C.c_void_p, C.c_int, C.c_int, do, C.c_void_p, C.c_void_p, C.c_void_p, fp, fp, fp]
+        L.bnn_mi355x_scan_clip_device.argtypes = [fr, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, fp, fp, C.c_int, C.c_void_p]
+        L.bnn_mi355x_scan_clip_device.restype = ip
+        L.bnn_mi355x_detect_clip_device.argtypes = [fr, C.c_void_p, C.c_void_p, C.c_int, C.c_int, do, C.c_void_p, C.c_void_p, C.c_void_p, fp, fp, fp,
+                                                    C.c_void_p]
 
 
 _cache = {}

@@ -1029,13 +1029,128 @@ class CnvClassifier:
             return None, frames
         return np.ascontiguousarray(np.stack(arrays)), frames
 
-    def scan_clip(self, frames, sizes=(64, 96), details=False, max_frames=None):
+    # -- extension: camera frames -- NV12, I420, YUYV and BGR clips, from host memory or from a CUDA tensor ----------
+    @staticmethod
+    def _is_cuda_tensor(frames):
+        return type(frames).__module__.split(".")[0] == "torch" and hasattr(frames, "data_ptr") and frames.is_cuda
+
+    def _camera_clip(self, frames, pixel_format, video_range, what, always=False):
+        """None for what the clip methods have always taken (``pixel_format="rgb"`` and no CUDA tensor; not with
+        ``always``), else the clip as ``bnn_mi355x_frames`` states it: a dict with the uint8 array or CUDA tensor ``clip``
+        (contiguous), ``format``, ``range``, ``width``, ``height`` and ``device``"""
+        fmt = str(pixel_format).lower()
+        if fmt not in abi.PIXEL_FORMATS:
+            raise ValueError("%s: pixel_format must be one of %s" % (what, ", ".join(sorted(abi.PIXEL_FORMATS))))
+        device = self._is_cuda_tensor(frames)
+        if fmt == "rgb" and not device and not always:
+            return None
+        if device:
+            import torch
+            if frames.dtype != torch.uint8:
+                raise ValueError("%s: a clip given as a tensor must be torch.uint8" % what)
+            clip = frames.contiguous()
+        else:
+            clip = np.ascontiguousarray(frames)
+            if clip.dtype != np.uint8:
+                raise ValueError("%s: a %s clip must be one uint8 array" % (what, fmt))
+        shape = tuple(clip.shape)
+        if fmt in ("nv12", "i420"):
+            ok, height = len(shape) == 3 and shape[1] % 3 == 0, shape[1] // 3 * 2 if len(shape) == 3 else 0
+            want = "[F, h * 3 / 2, w]"
+        elif fmt == "yuyv":
+            ok, height, want = len(shape) == 4 and shape[3] == 2, shape[1] if len(shape) > 1 else 0, "[F, h, w, 2]"
+        elif fmt == "l" or (fmt == "rgb" and len(shape) == 3):
+            ok, height, want, fmt = len(shape) == 3, shape[1] if len(shape) > 1 else 0, "[F, h, w]", "l"
+        else:
+            ok, height, want = len(shape) == 4 and shape[3] == 3, shape[1] if len(shape) > 1 else 0, "[F, h, w, 3]"
+        if not ok or shape[0] < 1:
+            raise ValueError("%s: a %s clip must be uint8 %s with one frame or more" % (what, fmt, want))
+        return dict(clip=clip, format=abi.PIXEL_FORMATS[fmt], range=1 if video_range else 0, width=shape[2], height=height, device=device)
+
+    @staticmethod
+    def _camera_piece(cam, first, step):
+        """frames [first, first + step) of a camera clip -> (``bnn_mi355x_frames``, pointer, stream handle or None, the piece)"""
+        part = cam["clip"][first:first + step]
+        fr = abi.Frames(cam["format"], cam["range"], cam["width"], cam["height"], len(part), 0, 0)
+        if cam["device"]:
+            import torch
+            return fr, part.data_ptr(), torch.cuda.current_stream(part.device).cuda_stream, part
+        return fr, part.ctypes.data, None, part
+
+    def unpack_frames(self, frames, pixel_format="nv12", video_range=False):
+        """the packed RGB frames, uint8 ``[F, h, w, 3]``, of a camera clip: ``[F, h * 3 / 2, w]`` for ``nv12`` and ``i420``
+        (a Y plane, then interleaved or planar chroma), ``[F, h, w, 2]`` for ``yuyv``, ``[F, h, w, 3]`` for ``bgr``.  Chroma is
+        replicated; the colour is Pillow's ``convert("RGB")`` from YCbCr byte for byte, or with ``video_range`` BT.601 video
+        range.  On the device where the library has ``bnn_mi355x_unpack_frames`` (CNV), else with the host model: the same
+        bytes."""
+        lib = self.bnn.interface
+        if not hasattr(lib, "bnn_mi355x_unpack_frames_host"):
+            raise RuntimeError("unpack_frames: the library has no bnn_mi355x_unpack_frames_host")
+        if self._is_cuda_tensor(frames):
+            frames = frames.cpu().numpy()
+        cam = self._camera_clip(frames, pixel_format, video_range, "unpack_frames", always=True)
+        fr, ptr, _, part = self._camera_piece(cam, 0, len(cam["clip"]))
+        out = np.empty((len(part), cam["height"], cam["width"], 3), np.uint8)
+        if lib.bnn_mi355x_network().decode().startswith("cnv"):
+            rc = lib.bnn_mi355x_unpack_frames(ctypes.byref(fr), ptr, out.ctypes.data, None)
+        else:
+            rc = lib.bnn_mi355x_unpack_frames_host(ctypes.byref(fr), ptr, out.ctypes.data)
+        if rc != 0:
+            raise ValueError(lib.bnn_mi355x_last_error().decode())
+        return out
+
+    def _camera_lib(self):
+        lib = self._scan_lib()
+        return lib if lib is not None and hasattr(lib, "bnn_mi355x_detect_clip_frames") else None
+
+    def _scan_camera_clip(self, cam, sizes, details, max_frames):
+        """:meth:`scan_clip` of a camera clip through ``bnn_mi355x_scan_clip_frames`` / ``_device``"""
+        lib, ncls = self._camera_lib(), len(self.classes)
+        width, height, n_frames = cam["width"], cam["height"], len(cam["clip"])
+        boxes = np.concatenate([self.scan_boxes((width, height), s)[1] for s in sizes]) if len(sizes) else np.zeros((0, 4), np.int32)
+        sz = np.asarray(sizes, dtype=np.int32)
+        step = lib.bnn_mi355x_scan_clip_capacity(width, height, sz.ctypes.data, len(sz))
+        if step < 1:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        step = min(step, max_frames) if max_frames is not None else step
+        out = np.zeros((len(boxes), 4), np.int32)
+        parts, pre_us, pass_us = [], 0.0, 0.0
+        for first in range(0, n_frames, step):
+            fr, ptr, stream, part = self._camera_piece(cam, first, step)
+            usec, pre = ctypes.c_float(0), ctypes.c_float(0)
+            args = [ctypes.byref(fr), ptr, sz.ctypes.data, len(sz), ncls, out.ctypes.data, ctypes.byref(usec), ctypes.byref(pre), 1 if details else 0]
+            res = lib.bnn_mi355x_scan_clip_device(*(args + [stream])) if cam["device"] else lib.bnn_mi355x_scan_clip_frames(*args)
+            if not res:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            n = len(part) * len(boxes)
+            parts.append(self.bnn._collect(res, n * (ncls if details else 1)).reshape((len(part), len(boxes), ncls) if details else (len(part), len(boxes))))
+            pre_us += pre.value * n
+            pass_us += usec.value * n
+        total = n_frames * len(boxes)
+        self.usecPerImage = self.bnn.usecPerImage = pass_us / total if total else 0.0
+        self.usecPreprocess = pre_us / total if total else 0.0
+        return out, np.concatenate(parts)
+
+    def scan_clip(self, frames, sizes=(64, 96), details=False, max_frames=None, pixel_format="rgb", video_range=False):
         """:meth:`scan_scene` of every frame of a clip -- a sequence of PIL images or uint8 arrays of one size and mode, or
         one array ``[F, H, W(, 3)]`` -> (boxes int32 [n, 4], the same for every frame; classes [F, n] or scores
         [F, n, len(classes)]).  On cnvW1A1 the clip goes up once and every (frame, level) map runs through ONE launch per
         stage (``bnn_mi355x_scan_clip``: RGB and L frames); clips longer than one call accepts, or than ``max_frames``, go
         in several calls and are joined.  Other networks, libraries without the entry point and RGBA frames loop over
-        :meth:`scan_scene`: the same answers by construction."""
+        :meth:`scan_scene`: the same answers by construction.
+
+        ``pixel_format`` ``"nv12"``, ``"i420"``, ``"yuyv"`` or ``"bgr"`` takes camera frames as one array (the shapes of
+        :meth:`unpack_frames`; ``video_range``: BT.601 video range instead of JFIF full range): they go up as they are and
+        become RGB on the device (``bnn_mi355x_scan_clip_frames``).  A CUDA ``torch.uint8`` tensor of any format, ``"rgb"``
+        and ``"l"`` included, is read where it lies, on the current stream (``bnn_mi355x_scan_clip_device``).  Libraries
+        without those entry points convert with :meth:`unpack_frames` and go on as above."""
+        cam = self._camera_clip(frames, pixel_format, video_range, "scan_clip")
+        if cam is not None:
+            if max_frames is not None and max_frames < 1:
+                raise ValueError("scan_clip: max_frames must be 1 or more")
+            if self._camera_lib() is None:
+                return self.scan_clip(self.unpack_frames(frames, pixel_format, video_range), sizes, details, max_frames)
+            return self._scan_camera_clip(cam, sizes, details, max_frames)
         clip, frames = self._clip_frames(frames)
         ncls = len(self.classes)
         if max_frames is not None and max_frames < 1:
@@ -1131,17 +1246,25 @@ class CnvClassifier:
         return found[0] if single else found
 
     def detect_clip(self, frames, classes=None, sizes=(64, 96), min_score=None, by_score=False, iou=0.5, max_det=64, max_candidates=4096,
-                    max_frames=None):
+                    max_frames=None, pixel_format="rgb", video_range=False):
         """where the objects are in every frame of a clip: :meth:`scan_clip` followed by :meth:`suppress` -> per frame a
         list of ``((left, upper, right, lower), class, score)``, best first.  On cnvW1A1 one call per piece of the clip
         (``bnn_mi355x_detect_clip``: RGB and L frames): the scan's launches, then the detection kernels on the scores where
         the scan left them, and only the lists come back; long clips are cut by the call's capacity and ``max_frames`` as
         in :meth:`scan_clip`.  Other networks, libraries without the entry point and RGBA frames take
-        ``scan_clip(details=True)`` and :meth:`suppress`: the same answers by construction."""
+        ``scan_clip(details=True)`` and :meth:`suppress`: the same answers by construction.
+
+        ``pixel_format``, ``video_range`` and CUDA tensors: as :meth:`scan_clip` (``bnn_mi355x_detect_clip_frames``,
+        ``bnn_mi355x_detect_clip_device``)."""
         if max_frames is not None and max_frames < 1:
             raise ValueError("detect_clip: max_frames must be 1 or more")
         ncls = len(self.classes)
         o = self._detect_opts(classes, min_score, by_score, iou, max_det, max_candidates)
+        cam = self._camera_clip(frames, pixel_format, video_range, "detect_clip")
+        if cam is not None and self._camera_lib() is None:
+            frames, cam = self.unpack_frames(frames, pixel_format, video_range), None
+        if cam is not None:
+            return self._detect_camera_clip(cam, sizes, o, max_frames)
         lib = self._scan_lib()
         clip, listed = self._clip_frames(frames)
         if lib is None or clip is None or not hasattr(lib, "bnn_mi355x_detect_clip"):
@@ -1178,9 +1301,44 @@ class CnvClassifier:
         self.n_candidates = ncand
         return found
 
+    def _detect_camera_clip(self, cam, sizes, o, max_frames):
+        """:meth:`detect_clip` of a camera clip through ``bnn_mi355x_detect_clip_frames`` / ``_device``"""
+        lib, ncls = self._camera_lib(), len(self.classes)
+        width, height, n_frames = cam["width"], cam["height"], len(cam["clip"])
+        sz = np.asarray(sizes, dtype=np.int32)
+        step = lib.bnn_mi355x_scan_clip_capacity(width, height, sz.ctypes.data, len(sz))
+        if step < 1:
+            raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        step = min(step, max_frames) if max_frames is not None else step
+        found, ncand, pre_us, pass_us, det_us, windows = [], [], 0.0, 0.0, 0.0, 0
+        n = sum(len(self.scan_boxes((width, height), s)[1]) for s in sizes)
+        for first in range(0, n_frames, step):
+            fr, ptr, stream, part = self._camera_piece(cam, first, step)
+            dets = np.zeros((len(part), max(o.max_det, 1), 8), np.int32)
+            counts, nc = np.zeros(len(part), np.int32), np.zeros(len(part), np.int32)
+            usec, pre, det = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
+            args = [ctypes.byref(fr), ptr, sz.ctypes.data, len(sz), ncls, ctypes.byref(o), dets.ctypes.data, counts.ctypes.data, nc.ctypes.data,
+                    ctypes.byref(usec), ctypes.byref(pre), ctypes.byref(det)]
+            rc = lib.bnn_mi355x_detect_clip_device(*(args + [stream])) if cam["device"] else lib.bnn_mi355x_detect_clip_frames(*args)
+            if rc != 0:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            found += self._detections(dets, counts)
+            ncand += nc.tolist()
+            pre_us += pre.value * n * len(part)
+            pass_us += usec.value * n * len(part)
+            det_us += det.value * len(part)
+            windows += n * len(part)
+        self.usecPerImage = self.bnn.usecPerImage = pass_us / windows if windows else 0.0
+        self.usecPreprocess = pre_us / windows if windows else 0.0
+        self.usecDetect = det_us / n_frames
+        self.n_candidates = ncand
+        return found
+
     def detect(self, img, classes=None, sizes=(64, 96), **kwargs):
-        """:meth:`detect_clip` on one picture -> a list of ``((left, upper, right, lower), class, score)``"""
-        return self.detect_clip([img], classes, sizes, **kwargs)[0]
+        """:meth:`detect_clip` on one picture -> a list of ``((left, upper, right, lower), class, score)``; with
+        ``pixel_format`` one camera frame (``[h * 3 / 2, w]``, ``[h, w, 2]`` or ``[h, w, 3]``), as an array or a CUDA tensor"""
+        one = img[None] if self._is_cuda_tensor(img) or str(kwargs.get("pixel_format", "rgb")).lower() != "rgb" else [img]
+        return self.detect_clip(one, classes, sizes, **kwargs)[0]
 
     # extension
     def classify_array(self, images, detail=False):

@@ -58,6 +58,8 @@
 #include "scan.h"
 #include "scan_clip_kernels.h"
 #include "scan_clip.h"
+#include "pixfmt_kernels.h"
+#include "pixfmt.h"
 #include "detect_kernels.h"
 #include "component_kernels.h"
 #include "components.h"
@@ -366,6 +368,10 @@ struct Runtime {
   DeviceBuf<uint64_t> d_det_boxes;
   DeviceBuf<int32_t> d_det_out;
   hipEvent_t det_ev[2] = {nullptr, nullptr};
+  // camera frames (bnn_mi355x_unpack_frames, bnn_mi355x_*_clip_frames; pixfmt.h): the uploaded raw frames, which
+  // k_unpack_frames turns into the RGB frames at d_scan_scene; time stamps around the launch of unpack_frames
+  DeviceBuf<uint8_t> d_clip_raw;
+  hipEvent_t pix_ev[2] = {nullptr, nullptr};
   // one picture and N boxes -> MNIST-format records / classes (bnn_mi355x_enhance_picture, bnn_mi355x_glyphs_to_mnist,
   // bnn_mi355x_classify_glyphs; LFC): the picture, its L plane, boxes + found ink boxes, descriptors + tables, the global
   // temporary of glyphs past the LDS budget, the 784-byte records, the plane's pixel sum; time stamps as win_ev
@@ -1912,14 +1918,15 @@ int *new_result(size_t count) {
   return result;
 }
 
-// The CNV results' way back on r.stream: the classes of n images straight into `result`, or -- `scores` sized by the
+// The CNV results' way back on s (r.stream when none is given): the classes of n images straight into `result`, or -- `scores` sized by the
 // caller to n x 64 -- the scores, which widen_scores puts into `result` as number_class ints per image after the sync
-int enqueue_cnv_results(size_t n, int *result, std::vector<int16_t> &scores) {
+int enqueue_cnv_results(size_t n, int *result, std::vector<int16_t> &scores, hipStream_t s) {
   Runtime &r = rt();
-  if (!scores.empty()) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, r.stream));
-  else HIP_OK(hipMemcpyAsync(result, r.d_classes, n * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  if (!scores.empty()) HIP_OK(hipMemcpyAsync(scores.data(), r.d_scores, n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+  else HIP_OK(hipMemcpyAsync(result, r.d_classes, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   return 0;
 }
+int enqueue_cnv_results(size_t n, int *result, std::vector<int16_t> &scores) { return enqueue_cnv_results(n, result, scores, rt().stream); }
 void widen_scores(const std::vector<int16_t> &scores, int number_class, int *result) {
   for (size_t i = 0; i < scores.size() / 64; i++)
     for (int j = 0; j < number_class; j++) result[i * number_class + j] = scores[i * 64 + j];
@@ -5380,9 +5387,22 @@ struct ClipJob {
   size_t tmp_frame = 1;  // bytes of one frame's first resize pass, the largest of the levels
 };
 
+// Where a clip call's frames come from (include/bnn_mi355x.h, "Camera frames").  Not raw: the plan's bands and strides
+// describe RGB or L frames, as the older entry points take them.  Raw: `frames` and `layout` do, and k_unpack_frames
+// makes the RGB frames at r.d_scan_scene.  A device source is read where it lies and the call runs on the caller's stream.
+struct ClipSource {
+  const uint8_t *pixels = nullptr;
+  bool device = false, raw = false;
+  Frames frames{};
+  PixLayout layout{};
+  hipStream_t stream = nullptr;  // r.stream for a host source
+  size_t raw_bytes() const { return raw && !device ? layout.frame_span * (size_t)layout.n_frames : 0; }
+};
+
 // every workspace of a clip call (grow-only; the map buffers are the scan's and grow as they do, behind a device
-// synchronise), and the level's Lanczos tables, built once for all frames
-int reserve_clip(const ClipPlan &p, ClipJob &job) {
+// synchronise), and the level's Lanczos tables, built once for all frames; raw_bytes: of uploaded raw frames (0: none)
+int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
+  if (raw_bytes && rt().d_clip_raw.grow(raw_bytes)) return -1;
   Runtime &r = rt();
   clip_tables(p, job.tables);
   job.tabs.assign(p.scene.levels.size(), ResizeTables{});
@@ -5400,54 +5420,93 @@ int reserve_clip(const ClipPlan &p, ClipJob &job) {
              ? -1 : 0;
 }
 
-// Enqueues on r.stream the upload of the clip to packed frames at r.d_scan_scene: one copy when the frames (or all rows)
-// lie evenly apart, else one 2-D copy a frame
-int upload_clip(const ClipPlan &p, const uint8_t *pixels) {
-  Runtime &r = rt();
-  const size_t row_bytes = (size_t)p.width * p.bands, frame_bytes = row_bytes * p.height;
-  const size_t rows_apart = p.row_stride ? (size_t)p.row_stride : row_bytes, frames_apart = p.frame_stride ? (size_t)p.frame_stride : rows_apart * p.height;
+// Enqueues on s the copy of `frames` frames of `rows` rows of row_bytes, rows_apart and frames_apart bytes apart at src, to
+// packed frames of packed rows at dst: one copy when the frames (or all rows) lie evenly apart, else one 2-D copy a frame
+int copy_spaced(uint8_t *dst, const uint8_t *src, size_t row_bytes, size_t rows, size_t rows_apart, size_t frames_apart, int frames, hipMemcpyKind kind,
+                hipStream_t s) {
+  const size_t frame_bytes = row_bytes * rows;
   if (rows_apart == row_bytes) {  // packed rows: a frame is one run of bytes
-    if (frames_apart == frame_bytes) HIP_OK(hipMemcpyAsync(r.d_scan_scene, pixels, frame_bytes * p.frames, hipMemcpyHostToDevice, r.stream));
-    else HIP_OK(hipMemcpy2DAsync(r.d_scan_scene, frame_bytes, pixels, frames_apart, frame_bytes, (size_t)p.frames, hipMemcpyHostToDevice, r.stream));
+    if (frames_apart == frame_bytes) HIP_OK(hipMemcpyAsync(dst, src, frame_bytes * frames, kind, s));
+    else HIP_OK(hipMemcpy2DAsync(dst, frame_bytes, src, frames_apart, frame_bytes, (size_t)frames, kind, s));
     return 0;
   }
-  if (frames_apart == rows_apart * p.height)  // the rows of all frames lie one stride apart
-    return upload_rows(r.d_scan_scene, pixels, row_bytes, (long)rows_apart, p.height * p.frames);
-  for (int f = 0; f < p.frames; f++)
-    if (upload_rows(r.d_scan_scene + (size_t)f * frame_bytes, pixels + (size_t)f * frames_apart, row_bytes, (long)rows_apart, p.height)) return -1;
+  if (frames_apart == rows_apart * rows) {  // the rows of all frames lie one stride apart
+    HIP_OK(hipMemcpy2DAsync(dst, row_bytes, src, rows_apart, row_bytes, rows * (size_t)frames, kind, s));
+    return 0;
+  }
+  for (int f = 0; f < frames; f++)
+    HIP_OK(hipMemcpy2DAsync(dst + (size_t)f * frame_bytes, row_bytes, src + (size_t)f * frames_apart, rows_apart, row_bytes, rows, kind, s));
   return 0;
 }
 
-// Enqueues on r.stream: the upload of the clip and of the tables, the resizes of every level (one pair of launches a level
-// for all frames), then stages 0..min(last_stage, 5) over all maps (run_scan_clip) and, for last_stage >= 6, stages 6..8 with
-// the decode ONCE on all windows.  mid (may be null) is recorded between the resizes and the stages.  The caller has
-// validated, bound the device and reserved (reserve_clip, reserve_results).
-int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const uint8_t *pixels, int ncls, int32_t *d_classes, int16_t *d_scores,
+// Enqueues on s the copy of the clip to packed frames at r.d_scan_scene (copy_spaced; the upload of a host clip by default)
+int upload_clip(const ClipPlan &p, const uint8_t *pixels, hipMemcpyKind kind = hipMemcpyHostToDevice, hipStream_t s = rt().stream) {
+  const size_t row_bytes = (size_t)p.width * p.bands;
+  const size_t rows_apart = p.row_stride ? (size_t)p.row_stride : row_bytes, frames_apart = p.frame_stride ? (size_t)p.frame_stride : rows_apart * p.height;
+  return copy_spaced(rt().d_scan_scene, pixels, row_bytes, (size_t)p.height, rows_apart, frames_apart, p.frames, kind, s);
+}
+
+// Enqueues on s the upload of host raw frames to dst.  The planes of a frame keep their row stride (a frame is ONE run of
+// frame_span bytes whatever its format; the kernel reads the width columns only) and the frames follow one another: one
+// copy, flat when the frames lie evenly apart and 2-D otherwise.  uploaded_layout states where they then lie.
+int upload_raw(uint8_t *dst, const uint8_t *pixels, const PixLayout &l, hipStream_t s) {
+  return copy_spaced(dst, pixels, l.frame_span, 1, l.frame_span, l.frames_apart, l.n_frames, hipMemcpyHostToDevice, s);
+}
+PixLayout uploaded_layout(const PixLayout &l) {
+  PixLayout p = l;
+  p.frames_apart = l.frame_span;
+  return p;
+}
+
+// Enqueues on the source's stream: the frames' way to packed RGB or L frames in HBM, the upload of the tables, the resizes of
+// every level (one pair of launches a level for all frames), then stages 0..min(last_stage, 5) over all maps (run_scan_clip)
+// and, for last_stage >= 6, stages 6..8 with the decode ONCE on all windows.  mid (may be null) is recorded between the
+// resizes and the stages.  The caller has validated, bound the device and reserved (reserve_clip, reserve_results).
+//   host RGB / L    the upload of the clip (upload_clip)
+//   host raw        the upload of the raw planes, then k_unpack_frames
+//   device raw      k_unpack_frames reads the caller's memory
+//   device RGB / L  packed frames are resized where they lie, others take one device-to-device copy
+int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const ClipSource &src, int ncls, int32_t *d_classes, int16_t *d_scores,
                  hipEvent_t mid, int last_stage) {
   Runtime &r = rt();
-  if (p.buf0 > r.d_scan_buf0.cap || p.buf1 > r.d_scan_buf1.cap || p.planes_bytes > r.d_scan_planes.cap || job.tables.words.size() > r.d_scan_clip_tab.cap ||
-      job.tmp_frame * p.frames > r.d_scan_tmp.cap)
-    return fail(std::string(what) + ": internal: the clip exceeds the scan workspace");
-  if (settle_handover(r.stream)) return -1;
-  if (upload_clip(p, pixels)) return -1;
-  if (!job.coef.empty()) HIP_OK(hipMemcpyAsync(r.d_scan_coef, job.coef.data(), job.coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
-  HIP_OK(hipMemcpyAsync(r.d_scan_clip_tab, job.tables.words.data(), job.tables.words.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  const hipStream_t s = src.stream;
   const size_t frame_bytes = (size_t)p.width * p.height * p.bands;
+  const bool in_place = src.device && !src.raw && (p.row_stride == 0 || (size_t)p.row_stride == (size_t)p.width * p.bands) &&
+                        (p.frame_stride == 0 || (size_t)p.frame_stride == frame_bytes);
+  if (p.buf0 > r.d_scan_buf0.cap || p.buf1 > r.d_scan_buf1.cap || p.planes_bytes > r.d_scan_planes.cap || job.tables.words.size() > r.d_scan_clip_tab.cap ||
+      job.tmp_frame * p.frames > r.d_scan_tmp.cap || (!in_place && frame_bytes * p.frames > r.d_scan_scene.cap) || src.raw_bytes() > r.d_clip_raw.cap)
+    return fail(std::string(what) + ": internal: the clip exceeds the scan workspace");
+  if (settle_handover(s)) return -1;
+  const uint8_t *scene = in_place ? src.pixels : r.d_scan_scene.get();
+  if (src.raw) {
+    UnpackLaunch u{};
+    u.src = src.pixels; u.dst = r.d_scan_scene; u.frames = src.frames; u.layout = src.layout; u.stream = s;
+    if (!src.device) {
+      if (upload_raw(r.d_clip_raw, src.pixels, src.layout, s)) return -1;
+      u.src = r.d_clip_raw; u.layout = uploaded_layout(src.layout);
+    }
+    const hipError_t e = run_unpack_frames(u);
+    if (e != hipSuccess) return launch_failed(what, e);
+  } else if (!in_place) {
+    if (upload_clip(p, src.pixels, src.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s)) return -1;
+  }
+  if (!job.coef.empty()) HIP_OK(hipMemcpyAsync(r.d_scan_coef, job.coef.data(), job.coef.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(r.d_scan_clip_tab, job.tables.words.data(), job.tables.words.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
   for (size_t k = 0; k < p.scene.levels.size(); k++) {
     const ScanLevel &lv = p.scene.levels[k];
     // (a level of the frames' own size: the same kernels only re-lay it out, as in scan_scene)
     ScanClipResize j{};
-    j.src = r.d_scan_scene; j.frames = p.frames; j.w = p.width; j.h = p.height; j.bands = p.bands;
+    j.src = scene; j.frames = p.frames; j.w = p.width; j.h = p.height; j.bands = p.bands;
     j.stride = (long)p.width * p.bands; j.src_frame = (long)frame_bytes;
     j.out_w = lv.level_w; j.out_h = lv.level_h;
     j.vertical_first = vertical_pass_first(p.width, p.height, lv.level_h);
     set_tables(j, r.d_scan_coef, job.tabs[k]);
     j.tmp = r.d_scan_tmp; j.tmp_frame = (long)job.tmp_frame;
     j.planes = r.d_scan_planes + p.level_planes[k];
-    const hipError_t e = launch_clip_resize(j, r.stream);
+    const hipError_t e = launch_clip_resize(j, s);
     if (e != hipSuccess) return launch_failed(what, e);
   }
-  if (mid) HIP_OK(hipEventRecord(mid, r.stream));
+  if (mid) HIP_OK(hipEventRecord(mid, s));
   ScanClipLaunch a{};
   a.planes = r.d_scan_planes; a.buf0 = r.d_scan_buf0; a.buf1 = r.d_scan_buf1;
   for (int l = 0; l < kScanStages; l++) {
@@ -5455,12 +5514,120 @@ int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const 
     a.desc[l] = job.tables.desc[l]; a.block_map[l] = job.tables.block_map[l]; a.blocks[l] = p.blocks[l];
   }
   a.tables = r.d_scan_clip_tab;
-  a.stream = r.stream;
+  a.stream = s;
   a.last_stage = last_stage < kScanStages - 1 ? last_stage : kScanStages - 1;
   hipError_t e = run_scan_clip(a);
-  if (e == hipSuccess && last_stage >= kScanStages) e = run_scan_tail((int)p.windows, ncls, d_classes, d_scores, r.stream, last_stage);
+  if (e == hipSuccess && last_stage >= kScanStages) e = run_scan_tail((int)p.windows, ncls, d_classes, d_scores, s, last_stage);
   if (e != hipSuccess) return launch_failed(what, e);
   return 0;
+}
+
+static_assert(sizeof(Frames) == sizeof(bnn_mi355x_frames) && offsetof(Frames, frame_stride) == offsetof(bnn_mi355x_frames, frame_stride),
+              "Frames is bnn_mi355x_frames");
+static_assert(kPixMaxSide == BNN_MI355X_SCAN_MAX_SIDE && kPixMaxFrames == BNN_MI355X_SCAN_CLIP_MAX_FRAMES && kPixMaxBytes == BNN_MI355X_SCAN_CLIP_MAX_BYTES,
+              "the frames' limits are the clip scan's");
+
+// What a clip entry point was asked for.  The *_frames and *_device ones hand `frames` over (null is refused); the older
+// ones (n_frames .. row_stride), whose bands state RGB or L.
+struct ClipRequest {
+  const char *what;
+  const void *pixels;
+  bool by_frames;
+  const Frames *frames;
+  int n_frames;
+  long frame_stride;
+  int width, height, bands;
+  long row_stride;
+  bool device;
+  void *hip_stream;
+};
+ClipRequest frames_request(const char *what, const void *pixels, const bnn_mi355x_frames *frames, bool device, void *hip_stream) {
+  return ClipRequest{what, pixels, true, reinterpret_cast<const Frames *>(frames), 0, 0, 0, 0, 0, 0, device, hip_stream};
+}
+
+// plan_clip for a request: empty, or the message for last_error.  Raw frames are validated by validate_frames, and the plan
+// is that of the packed RGB frames k_unpack_frames makes of them; RGB and L frames are planned as the older entry points' are.
+std::string plan_request(const ClipRequest &q, const int *sizes, int n_sizes, const void *out, ClipPlan &plan, ClipSource &src) {
+  src = ClipSource{};
+  src.pixels = static_cast<const uint8_t *>(q.pixels);
+  src.device = q.device;
+  if (!q.by_frames) return plan_clip(q.what, q.pixels, q.n_frames, q.frame_stride, q.width, q.height, q.bands, q.row_stride, sizes, n_sizes, out, plan);
+  const std::string bad = validate_frames(q.what, q.frames, q.pixels, src.layout);
+  if (!bad.empty()) return bad;
+  const Frames &f = *q.frames;
+  src.frames = f;
+  src.raw = f.format != PIX_RGB && f.format != PIX_L;
+  return plan_clip(q.what, q.pixels, f.n_frames, src.raw ? 0 : f.frame_stride, f.width, f.height, f.format == PIX_L ? 1 : 3, src.raw ? 0 : f.row_stride,
+                   sizes, n_sizes, out, plan);
+}
+
+// A device clip call waits for its stream and hands its results to the host: empty, or the refusal while that stream is
+// being captured (nothing has been enqueued or allocated: the capture stays valid)
+std::string capture_refused(const ClipRequest &q) {
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (!q.device || hipStreamIsCapturing(static_cast<hipStream_t>(q.hip_stream), &capturing) != hipSuccess || capturing == hipStreamCaptureStatusNone)
+    return "";
+  return std::string(q.what) + ": hip_stream is being captured: the call waits for its stream and returns its results on the host, which a graph cannot record";
+}
+
+// On a failing exit of a device clip call nothing may still be queued on the caller's stream that reads the call's host
+// buffers (DrainOnFailure waits for the library's own streams)
+struct DrainCaller {
+  const ClipSource &src;
+  bool armed = true;
+  void ok() { armed = false; }
+  ~DrainCaller() {
+    if (armed && src.device) (void)hipStreamSynchronize(src.stream);
+  }
+};
+
+// bnn_mi355x_scan_clip, _scan_clip_frames and _scan_clip_device.  A device call settles the workspaces' hand-over before
+// it enqueues (enqueue_clip) and has waited for its stream when it returns: it leaves nothing to hand over.
+int *scan_clip_call(const ClipRequest &q, const int *sizes, int n_sizes, int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess,
+                    int enable_detail) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  const std::string no = scan_refused(q.what);
+  if (!no.empty()) { fail(no); return nullptr; }
+  ClipPlan plan;
+  ClipSource src;
+  const std::string bad = plan_request(q, sizes, n_sizes, boxes_out, plan, src);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (bad_number_class(number_class)) return nullptr;
+  if (!ready()) return nullptr;
+  const std::string captured = capture_refused(q);
+  if (!captured.empty()) { fail(captured); return nullptr; }
+  const size_t n = (size_t)plan.windows;
+  int *result = new_result(n * (enable_detail ? number_class : 1));
+  if (!result) return nullptr;
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    const hipStream_t s = src.stream = q.device ? static_cast<hipStream_t>(q.hip_stream) : r.stream;
+    std::vector<int16_t> scores;
+    ClipJob job;  // (outlives its asynchronous uploads: declared before `drain`)
+    // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
+    if (reserve_results(n) || reserve_clip(plan, job, src.raw_bytes()) || ensure_events(r.scan_ev, 3)) return -1;
+    if (enable_detail) scores.resize(n * 64);
+    DrainOnFailure drain;
+    DrainCaller caller{src};
+    HIP_OK(hipEventRecord(r.scan_ev[0], s));
+    if (enqueue_clip(q.what, plan, job, src, number_class, enable_detail ? nullptr : r.d_classes, enable_detail ? r.d_scores : nullptr, r.scan_ev[1],
+                     kCnvStages - 1))
+      return -1;
+    HIP_OK(hipEventRecord(r.scan_ev[2], s));
+    if (enqueue_cnv_results(n, result, scores, s)) return -1;
+    HIP_OK(hipStreamSynchronize(s));
+    drain.ok();
+    caller.ok();
+    widen_scores(scores, number_class, result);
+    return (usec_per_image(r.scan_ev[0], r.scan_ev[1], n, usecPreprocess) || usec_per_image(r.scan_ev[1], r.scan_ev[2], n, usecPerImage)) ? -1 : 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  // (the boxes are the same for every frame: one frame's, exactly what scan_scene writes)
+  for (const ScanLevel &lv : plan.scene.levels)
+    scan_boxes(plan.width, plan.height, lv.size, boxes_out + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
+  return result;
 }
 
 }  // namespace
@@ -5503,42 +5670,65 @@ int bnn_mi355x_scan_clip_layout(int width, int height, const int *sizes, int n_s
 int *bnn_mi355x_scan_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
                           const int *sizes, int n_sizes, int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess,
                           int enable_detail) {
+  const ClipRequest q{"scan_clip", pixels, false, nullptr, n_frames, frame_stride, width, height, bands, row_stride, false, nullptr};
+  return scan_clip_call(q, sizes, n_sizes, number_class, boxes_out, usecPerImage, usecPreprocess, enable_detail);
+}
+
+int *bnn_mi355x_scan_clip_frames(const bnn_mi355x_frames *frames, const void *pixels, const int *sizes, int n_sizes, int number_class, int *boxes_out,
+                                 float *usecPerImage, float *usecPreprocess, int enable_detail) {
+  return scan_clip_call(frames_request("scan_clip_frames", pixels, frames, false, nullptr), sizes, n_sizes, number_class, boxes_out, usecPerImage,
+                        usecPreprocess, enable_detail);
+}
+
+int *bnn_mi355x_scan_clip_device(const bnn_mi355x_frames *frames, const void *d_pixels, const int *sizes, int n_sizes, int number_class, int *boxes_out,
+                                 float *usecPerImage, float *usecPreprocess, int enable_detail, void *hip_stream) {
+  return scan_clip_call(frames_request("scan_clip_device", d_pixels, frames, true, hip_stream), sizes, n_sizes, number_class, boxes_out, usecPerImage,
+                        usecPreprocess, enable_detail);
+}
+
+int bnn_mi355x_unpack_frames_host(const bnn_mi355x_frames *frames, const void *pixels, uint8_t *rgb_out) {
+  PixLayout layout;
+  const std::string bad = validate_frames("unpack_frames_host", reinterpret_cast<const Frames *>(frames), pixels, layout);
+  if (!bad.empty()) return fail(bad);
+  if (!rgb_out) return fail("unpack_frames_host: rgb_out is null");
+  unpack_frames(*reinterpret_cast<const Frames *>(frames), layout, static_cast<const uint8_t *>(pixels), rgb_out);
+  return 0;
+}
+
+int bnn_mi355x_unpack_frames(const bnn_mi355x_frames *frames, const void *pixels, uint8_t *rgb_out, float *usecUnpack) {
   Runtime &r = rt();
-  if (usecPerImage) *usecPerImage = 0.f;
-  if (usecPreprocess) *usecPreprocess = 0.f;
-  const std::string no = scan_refused("scan_clip");
-  if (!no.empty()) { fail(no); return nullptr; }
-  ClipPlan plan;
-  const std::string bad = plan_clip("scan_clip", pixels, n_frames, frame_stride, width, height, bands, row_stride, sizes, n_sizes, boxes_out, plan);
-  if (!bad.empty()) { fail(bad); return nullptr; }
-  if (bad_number_class(number_class)) return nullptr;
-  if (!ready()) return nullptr;
-  const size_t n = (size_t)plan.windows;
-  int *result = new_result(n * (enable_detail ? number_class : 1));
-  if (!result) return nullptr;
-  auto run = [&]() -> int {
-    if (bind_device()) return -1;
-    std::vector<int16_t> scores;
-    ClipJob job;  // (outlives its asynchronous uploads: declared before `drain`)
-    // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
-    if (reserve_results(n) || reserve_clip(plan, job) || ensure_events(r.scan_ev, 3)) return -1;
-    if (enable_detail) scores.resize(n * 64);
-    DrainOnFailure drain;
-    HIP_OK(hipEventRecord(r.scan_ev[0], r.stream));
-    if (enqueue_clip("scan_clip", plan, job, pixels, number_class, enable_detail ? nullptr : r.d_classes, enable_detail ? r.d_scores : nullptr,
-                     r.scan_ev[1], kCnvStages - 1))
-      return -1;
-    HIP_OK(hipEventRecord(r.scan_ev[2], r.stream));
-    if (enqueue_cnv_results(n, result, scores)) return -1;
-    HIP_OK(hipStreamSynchronize(r.stream));
-    drain.ok();
-    widen_scores(scores, number_class, result);
-    return (usec_per_image(r.scan_ev[0], r.scan_ev[1], n, usecPreprocess) || usec_per_image(r.scan_ev[1], r.scan_ev[2], n, usecPerImage)) ? -1 : 0;
-  };
-  if (run()) { delete[] result; return nullptr; }
-  // (the boxes are the same for every frame: one frame's, exactly what scan_scene writes)
-  for (const ScanLevel &lv : plan.scene.levels) scan_boxes(width, height, lv.size, boxes_out + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
-  return result;
+  if (usecUnpack) *usecUnpack = 0.f;
+  if (!r.spec.is_cnv) return fail("unpack_frames: frames are unpacked on the device for the CNV networks only");
+  PixLayout layout;
+  const std::string bad = validate_frames("unpack_frames", reinterpret_cast<const Frames *>(frames), pixels, layout);
+  if (!bad.empty()) return fail(bad);
+  if (!rgb_out) return fail("unpack_frames: rgb_out is null");
+  const Frames &f = *reinterpret_cast<const Frames *>(frames);
+  if (bind_device()) return -1;
+  // the RGB frames lie between two guards of kGuard bytes, which the kernel must leave as they were
+  constexpr size_t kGuard = 64;
+  const size_t rgb_bytes = (size_t)f.width * f.height * 3 * (size_t)f.n_frames;
+  uint8_t guards[2 * kGuard];
+  if (r.d_clip_raw.grow(layout.frame_span * (size_t)f.n_frames) || r.d_scan_scene.grow(rgb_bytes + 2 * kGuard) || ensure_events(r.pix_ev, 2)) return -1;
+  DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
+  if (upload_raw(r.d_clip_raw, static_cast<const uint8_t *>(pixels), layout, r.stream)) return -1;
+  uint8_t *const d_rgb = r.d_scan_scene + kGuard;
+  HIP_OK(hipMemsetAsync(r.d_scan_scene, 0xA5, kGuard, r.stream));
+  HIP_OK(hipMemsetAsync(d_rgb + rgb_bytes, 0xA5, kGuard, r.stream));
+  UnpackLaunch u{};
+  u.src = r.d_clip_raw; u.dst = d_rgb; u.frames = f; u.layout = uploaded_layout(layout); u.stream = r.stream;
+  HIP_OK(hipEventRecord(r.pix_ev[0], r.stream));
+  const hipError_t e = run_unpack_frames(u);
+  if (e != hipSuccess) return launch_failed("unpack_frames", e);
+  HIP_OK(hipEventRecord(r.pix_ev[1], r.stream));
+  HIP_OK(hipMemcpyAsync(rgb_out, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipMemcpyAsync(guards, r.d_scan_scene, kGuard, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipMemcpyAsync(guards + kGuard, d_rgb + rgb_bytes, kGuard, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  for (uint8_t g : guards)
+    if (g != 0xA5) return fail("unpack_frames: internal: the kernel wrote outside the RGB frames");
+  return usec_per_image(r.pix_ev[0], r.pix_ev[1], (size_t)f.n_frames, usecUnpack);
 }
 
 long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
@@ -5556,7 +5746,9 @@ long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long 
   ClipJob job;
   if (reserve_clip(plan, job)) return -1;
   DrainOnFailure drain;
-  if (enqueue_clip("debug_scan_clip_stage", plan, job, pixels, 1, nullptr, nullptr, nullptr, stage)) return -1;
+  ClipSource src;
+  src.pixels = pixels; src.stream = r.stream;
+  if (enqueue_clip("debug_scan_clip_stage", plan, job, src, 1, nullptr, nullptr, nullptr, stage)) return -1;
   HIP_OK(hipMemcpyAsync(out, (stage & 1) ? r.d_scan_buf1 : r.d_scan_buf0, bytes, hipMemcpyDeviceToHost, r.stream));
   HIP_OK(hipStreamSynchronize(r.stream));
   drain.ok();
@@ -5585,27 +5777,77 @@ int reserve_detect(const int *boxes, size_t n, int frames, const DetectOpts &o, 
              ? -1 : 0;
 }
 
-// Enqueues on r.stream: the upload of the boxes, the two detection launches between det_ev[0] and det_ev[1] on the scores
+// Enqueues on s: the upload of the boxes, the two detection launches between det_ev[0] and det_ev[1] on the scores
 // (and classes, when the decode left them) of frames x n windows in HBM, and the lists' way back.  `packed` outlives the call's wait.
 int enqueue_detect(const char *what, const std::vector<uint64_t> &packed, int frames, int ncls, const DetectOpts &o, const int16_t *d_scores,
-                   const int32_t *d_classes, int *dets, int *counts, int *n_candidates) {
+                   const int32_t *d_classes, int *dets, int *counts, int *n_candidates, hipStream_t s) {
   Runtime &r = rt();
   const size_t n = packed.size(), det_ints = (size_t)frames * o.max_det * kDetectFields;
   if (n * frames > r.d_det_keys.cap || n > r.d_det_boxes.cap || det_ints + 2 * (size_t)frames > r.d_det_out.cap)
     return fail(std::string(what) + ": internal: the call exceeds the detection workspace");
-  HIP_OK(hipMemcpyAsync(r.d_det_boxes, packed.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, r.stream));
-  HIP_OK(hipEventRecord(r.det_ev[0], r.stream));
+  HIP_OK(hipMemcpyAsync(r.d_det_boxes, packed.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipEventRecord(r.det_ev[0], s));
   DetectLaunch a{};
   a.scores = d_scores; a.classes = d_classes; a.boxes = r.d_det_boxes; a.keys = r.d_det_keys;
   a.dets = r.d_det_out; a.counts = r.d_det_out + det_ints; a.n_candidates = r.d_det_out + det_ints + frames;
-  a.n = (int)n; a.frames = frames; a.number_class = ncls; a.opts = o; a.stream = r.stream;
+  a.n = (int)n; a.frames = frames; a.number_class = ncls; a.opts = o; a.stream = s;
   const hipError_t e = run_detect(a);
   if (e != hipSuccess) return launch_failed(what, e);
-  HIP_OK(hipEventRecord(r.det_ev[1], r.stream));
-  HIP_OK(hipMemcpyAsync(dets, a.dets, det_ints * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
-  HIP_OK(hipMemcpyAsync(counts, a.counts, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
-  HIP_OK(hipMemcpyAsync(n_candidates, a.n_candidates, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipEventRecord(r.det_ev[1], s));
+  HIP_OK(hipMemcpyAsync(dets, a.dets, det_ints * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(counts, a.counts, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(n_candidates, a.n_candidates, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   return 0;
+}
+
+// bnn_mi355x_detect_clip, _detect_clip_frames and _detect_clip_device (a device call: as scan_clip_call)
+int detect_clip_call(const ClipRequest &q, const int *sizes, int n_sizes, int number_class, const bnn_mi355x_detect_opts *opts, int *dets, int *counts,
+                     int *n_candidates, float *usecPerImage, float *usecPreprocess, float *usecDetect) {
+  Runtime &r = rt();
+  const std::string name = std::string(q.what) + ": ";
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (usecDetect) *usecDetect = 0.f;
+  const std::string no = scan_refused(q.what);
+  if (!no.empty()) return fail(no);
+  ClipPlan plan;
+  ClipSource src;
+  // (plan_clip refuses a null boxes_out: the boxes stay in this call, dets stands in for the check)
+  const std::string bad = plan_request(q, sizes, n_sizes, dets, plan, src);
+  if (!bad.empty()) return fail(bad);
+  if (!dets) return fail(name + "dets is null");
+  if (!counts) return fail(name + "counts is null");
+  if (!n_candidates) return fail(name + "n_candidates is null");
+  const DetectOpts *o = reinterpret_cast<const DetectOpts *>(opts);
+  const std::string bad_opts = validate_detect_opts(q.what, number_class, o);
+  if (!bad_opts.empty()) return fail(bad_opts);
+  if (!ready()) return -1;
+  const std::string captured = capture_refused(q);
+  if (!captured.empty()) return fail(captured);
+  const size_t windows = (size_t)plan.windows, n = windows / (size_t)plan.frames;
+  std::vector<int> boxes(4 * n);
+  for (const ScanLevel &lv : plan.scene.levels)
+    scan_boxes(plan.width, plan.height, lv.size, boxes.data() + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
+  if (bind_device()) return -1;
+  const hipStream_t s = src.stream = q.device ? static_cast<hipStream_t>(q.hip_stream) : r.stream;
+  ClipJob job;  // (outlives its asynchronous uploads: declared before `drain`)
+  std::vector<uint64_t> packed;
+  // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
+  if (reserve_results(windows) || reserve_clip(plan, job, src.raw_bytes()) || reserve_detect(boxes.data(), n, plan.frames, *o, packed) ||
+      ensure_events(r.scan_ev, 3))
+    return -1;
+  DrainOnFailure drain;
+  DrainCaller caller{src};
+  HIP_OK(hipEventRecord(r.scan_ev[0], s));
+  if (enqueue_clip(q.what, plan, job, src, number_class, r.d_classes, r.d_scores, r.scan_ev[1], kCnvStages - 1)) return -1;
+  HIP_OK(hipEventRecord(r.scan_ev[2], s));
+  if (enqueue_detect(q.what, packed, plan.frames, number_class, *o, r.d_scores, r.d_classes, dets, counts, n_candidates, s)) return -1;
+  HIP_OK(hipStreamSynchronize(s));
+  drain.ok();
+  caller.ok();
+  return (usec_per_image(r.scan_ev[0], r.scan_ev[1], windows, usecPreprocess) || usec_per_image(r.scan_ev[1], r.scan_ev[2], windows, usecPerImage) ||
+          usec_per_image(r.det_ev[0], r.det_ev[1], (size_t)plan.frames, usecDetect))
+             ? -1 : 0;
 }
 
 }  // namespace
@@ -5640,7 +5882,7 @@ int bnn_mi355x_detect_windows(const int *boxes, int n, const int *scores, int fr
   if (reserve_detect(boxes, (size_t)n, frames, *o, packed) || r.d_det_scores.grow(windows * 64)) return -1;
   DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
   HIP_OK(hipMemcpyAsync(r.d_det_scores, rows.data(), rows.size() * sizeof(int16_t), hipMemcpyHostToDevice, r.stream));
-  if (enqueue_detect("detect_windows", packed, frames, number_class, *o, r.d_det_scores, nullptr, dets, counts, n_candidates)) return -1;
+  if (enqueue_detect("detect_windows", packed, frames, number_class, *o, r.d_det_scores, nullptr, dets, counts, n_candidates, r.stream)) return -1;
   HIP_OK(hipStreamSynchronize(r.stream));
   drain.ok();
   return usec_per_image(r.det_ev[0], r.det_ev[1], (size_t)frames, usecDetect);
@@ -5649,42 +5891,22 @@ int bnn_mi355x_detect_windows(const int *boxes, int n, const int *scores, int fr
 int bnn_mi355x_detect_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
                            const int *sizes, int n_sizes, int number_class, const bnn_mi355x_detect_opts *opts, int *dets, int *counts,
                            int *n_candidates, float *usecPerImage, float *usecPreprocess, float *usecDetect) {
-  Runtime &r = rt();
-  if (usecPerImage) *usecPerImage = 0.f;
-  if (usecPreprocess) *usecPreprocess = 0.f;
-  if (usecDetect) *usecDetect = 0.f;
-  const std::string no = scan_refused("detect_clip");
-  if (!no.empty()) return fail(no);
-  ClipPlan plan;
-  // (plan_clip refuses a null boxes_out: the boxes stay in this call, dets stands in for the check)
-  const std::string bad = plan_clip("detect_clip", pixels, n_frames, frame_stride, width, height, bands, row_stride, sizes, n_sizes, dets, plan);
-  if (!bad.empty()) return fail(bad);
-  if (!dets) return fail("detect_clip: dets is null");
-  if (!counts) return fail("detect_clip: counts is null");
-  if (!n_candidates) return fail("detect_clip: n_candidates is null");
-  const DetectOpts *o = reinterpret_cast<const DetectOpts *>(opts);
-  const std::string bad_opts = validate_detect_opts("detect_clip", number_class, o);
-  if (!bad_opts.empty()) return fail(bad_opts);
-  if (!ready()) return -1;
-  const size_t windows = (size_t)plan.windows, n = windows / (size_t)plan.frames;
-  std::vector<int> boxes(4 * n);
-  for (const ScanLevel &lv : plan.scene.levels) scan_boxes(width, height, lv.size, boxes.data() + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
-  if (bind_device()) return -1;
-  ClipJob job;  // (outlives its asynchronous uploads: declared before `drain`)
-  std::vector<uint64_t> packed;
-  // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
-  if (reserve_results(windows) || reserve_clip(plan, job) || reserve_detect(boxes.data(), n, plan.frames, *o, packed) || ensure_events(r.scan_ev, 3))
-    return -1;
-  DrainOnFailure drain;
-  HIP_OK(hipEventRecord(r.scan_ev[0], r.stream));
-  if (enqueue_clip("detect_clip", plan, job, pixels, number_class, r.d_classes, r.d_scores, r.scan_ev[1], kCnvStages - 1)) return -1;
-  HIP_OK(hipEventRecord(r.scan_ev[2], r.stream));
-  if (enqueue_detect("detect_clip", packed, plan.frames, number_class, *o, r.d_scores, r.d_classes, dets, counts, n_candidates)) return -1;
-  HIP_OK(hipStreamSynchronize(r.stream));
-  drain.ok();
-  return (usec_per_image(r.scan_ev[0], r.scan_ev[1], windows, usecPreprocess) || usec_per_image(r.scan_ev[1], r.scan_ev[2], windows, usecPerImage) ||
-          usec_per_image(r.det_ev[0], r.det_ev[1], (size_t)plan.frames, usecDetect))
-             ? -1 : 0;
+  const ClipRequest q{"detect_clip", pixels, false, nullptr, n_frames, frame_stride, width, height, bands, row_stride, false, nullptr};
+  return detect_clip_call(q, sizes, n_sizes, number_class, opts, dets, counts, n_candidates, usecPerImage, usecPreprocess, usecDetect);
+}
+
+int bnn_mi355x_detect_clip_frames(const bnn_mi355x_frames *frames, const void *pixels, const int *sizes, int n_sizes, int number_class,
+                                  const bnn_mi355x_detect_opts *opts, int *dets, int *counts, int *n_candidates, float *usecPerImage,
+                                  float *usecPreprocess, float *usecDetect) {
+  return detect_clip_call(frames_request("detect_clip_frames", pixels, frames, false, nullptr), sizes, n_sizes, number_class, opts, dets, counts,
+                          n_candidates, usecPerImage, usecPreprocess, usecDetect);
+}
+
+int bnn_mi355x_detect_clip_device(const bnn_mi355x_frames *frames, const void *d_pixels, const int *sizes, int n_sizes, int number_class,
+                                  const bnn_mi355x_detect_opts *opts, int *dets, int *counts, int *n_candidates, float *usecPerImage,
+                                  float *usecPreprocess, float *usecDetect, void *hip_stream) {
+  return detect_clip_call(frames_request("detect_clip_device", d_pixels, frames, true, hip_stream), sizes, n_sizes, number_class, opts, dets, counts,
+                          n_candidates, usecPerImage, usecPreprocess, usecDetect);
 }
 
 }  // extern "C"

@@ -940,6 +940,63 @@ int bnn_mi355x_detect_clip(const uint8_t *pixels, int n_frames, long frame_strid
                            const int *sizes, int n_sizes, int number_class, const bnn_mi355x_detect_opts *opts, int *dets, int *counts,
                            int *n_candidates, float *usecPerImage, float *usecPreprocess, float *usecDetect);
 
+/* Camera frames: the clip entry points on frames as a camera or a decoder delivers them, from host memory or from HBM
+ * (csrc/pixfmt_kernels.hip; the model: csrc/pixfmt.h, DESIGN.md 9 "Camera frames").  Everything is exact: the frames
+ * become the packed RGB frames scan_clip uploads, and everything behind that is scan_clip's code on the same bytes.
+ *   format 0 RGB, 1 L   the `bands` 3 and 1 of scan_clip.
+ *          2 BGR        3 bytes a pixel, reversed (OpenCV).
+ *          3 NV12       a Y plane of `height` rows at row_stride, then interleaved Cb Cr of height / 2 rows at the same
+ *                       stride.
+ *          4 I420       a Y plane, then a Cb plane of height / 2 rows at row_stride / 2, then a Cr plane likewise.
+ *          5 YUYV       Y0 Cb Y1 Cr, 2 bytes a pixel.
+ *   Chroma is replicated to the 2 x 2 (NV12, I420) or 2 x 1 (YUYV) pixels it covers; there is no interpolation.
+ *   range 0  JFIF full range, byte for byte Pillow's convert("RGB") from mode YCbCr: T_c[i] = (int)(c * 64 * (i - 128) + 0.5)
+ *            for c = 1.402, -0.34414, -0.71414, 1.772; R = clip8(Y + (T_1.402[Cr] >> 6)), G = clip8(Y + ((T_-.34414[Cb] +
+ *            T_-.71414[Cr]) >> 6)), B = clip8(Y + (T_1.772[Cb] >> 6)).
+ *   range 1  BT.601 video range, this project's own statement (parity unpinned): C = Y - 16, D = Cb - 128, E = Cr - 128,
+ *            R = clip8((298 C + 409 E + 128) >> 8), G = clip8((298 C - 100 D - 208 E + 128) >> 8), B = clip8((298 C + 516 D +
+ *            128) >> 8).  Every shift is arithmetic; range is ignored for RGB, L and BGR.
+ *   row_stride, frame_stride: bytes, 0 = packed (the planes of one frame follow one another, and so do the frames).
+ * unpack_frames_host: the model on the host; any library, no GPU.  rgb_out: [n_frames][height][width][3].
+ * unpack_frames: the kernel on uploaded frames, the RGB comes back.  CNV libraries (no parameters need be loaded).
+ *       usecUnpack (may be NULL): the device time of the launch per frame.
+ * scan_clip_frames, detect_clip_frames: scan_clip and detect_clip with the struct in place of (n_frames, frame_stride, width,
+ *       height, bands, row_stride).  RGB and L are the older entry points bit for bit; the other formats are uploaded as they
+ *       are (1.5 to 2 bytes a pixel, scan_clip's one-copy-when-evenly-spaced rules) and unpacked on the device.
+ * scan_clip_device, detect_clip_device: the same with d_pixels in HBM.  The work is enqueued on hip_stream under
+ *       bnn_mi355x_inference_device's hand-over rules; the call then WAITS for the stream and returns the classes / scores
+ *       or the lists on the host, as the host calls do.  The caller's memory is only read, where it lies (packed RGB or L
+ *       frames are resized in place, strided ones take one device-to-device copy); no alignment is asked for.  A stream
+ *       that is being captured is refused: a graph cannot record the wait or the host results.
+ * cnvW1A1 only for the four clip calls, refused elsewhere in the scan's words.  Refused before anything touches the GPU,
+ * the message naming the argument: null pointers; an unknown format or range; width or height outside 1 ..
+ * BNN_MI355X_SCAN_MAX_SIDE; an odd width (NV12, I420, YUYV) or height (NV12, I420); n_frames outside 1 ..
+ * BNN_MI355X_SCAN_CLIP_MAX_FRAMES; a row_stride shorter than a row or, for I420, odd; a frame_stride shorter than a
+ * frame; raw frames or RGB frames above BNN_MI355X_SCAN_CLIP_MAX_BYTES; what scan_clip / detect_clip refuse, in their
+ * words.  Workspaces are grow-only; bnn_mi355x_scan_clip_capacity holds for every format. */
+#define BNN_MI355X_FORMAT_RGB 0
+#define BNN_MI355X_FORMAT_L 1
+#define BNN_MI355X_FORMAT_BGR 2
+#define BNN_MI355X_FORMAT_NV12 3
+#define BNN_MI355X_FORMAT_I420 4
+#define BNN_MI355X_FORMAT_YUYV 5
+typedef struct {
+  int format, range, width, height, n_frames;
+  long row_stride, frame_stride;
+} bnn_mi355x_frames;
+int bnn_mi355x_unpack_frames_host(const bnn_mi355x_frames *frames, const void *pixels, uint8_t *rgb_out);
+int bnn_mi355x_unpack_frames(const bnn_mi355x_frames *frames, const void *pixels, uint8_t *rgb_out, float *usecUnpack);
+int *bnn_mi355x_scan_clip_frames(const bnn_mi355x_frames *frames, const void *pixels, const int *sizes, int n_sizes, int number_class, int *boxes_out,
+                                 float *usecPerImage, float *usecPreprocess, int enable_detail);
+int bnn_mi355x_detect_clip_frames(const bnn_mi355x_frames *frames, const void *pixels, const int *sizes, int n_sizes, int number_class,
+                                  const bnn_mi355x_detect_opts *opts, int *dets, int *counts, int *n_candidates, float *usecPerImage,
+                                  float *usecPreprocess, float *usecDetect);
+int *bnn_mi355x_scan_clip_device(const bnn_mi355x_frames *frames, const void *d_pixels, const int *sizes, int n_sizes, int number_class, int *boxes_out,
+                                 float *usecPerImage, float *usecPreprocess, int enable_detail, void *hip_stream);
+int bnn_mi355x_detect_clip_device(const bnn_mi355x_frames *frames, const void *d_pixels, const int *sizes, int n_sizes, int number_class,
+                                  const bnn_mi355x_detect_opts *opts, int *dets, int *counts, int *n_candidates, float *usecPerImage,
+                                  float *usecPreprocess, float *usecDetect, void *hip_stream);
+
 /* Read handwriting(LFC-BNN_MNIST_Webcam.ipynb and LFC-BNN_Chars_Webcam.ipynb, cells 9-13): ONE picture and N boxes
  * become N MNIST-format records (28 x 28 bytes) -- and, with classify_glyphs, N classes -- in one call.  The notebooks
  * do this by hand with PIL for one camera frame, through two temporary files; here the picture goes to the device once

@@ -5381,7 +5381,10 @@ static_assert(kScanClipMaxFrames == BNN_MI355X_SCAN_CLIP_MAX_FRAMES && kScanClip
 
 // what one clip call keeps alive until its stream is idle (declared before the call's DrainOnFailure)
 struct ClipJob {
-  ClipTables tables;
+  ClipTables tables;    // with the matrix form's tables behind them, from mfma_base on, when the call takes that form
+  ClipMfmaTables mfma;  // (offsets and block counts; its words have moved into tables.words)
+  size_t mfma_base = 0;
+  unsigned matrix = 0;  // clip_matrix_stages of the call, decided when it reserves
   std::vector<int32_t> coef;
   std::vector<ResizeTables> tabs;
   size_t tmp_frame = 1;  // bytes of one frame's first resize pass, the largest of the levels
@@ -5399,12 +5402,47 @@ struct ClipSource {
   size_t raw_bytes() const { return raw && !device ? layout.frame_span * (size_t)layout.n_frames : 0; }
 };
 
+// The form of a clip call's stages 1-3 (bnn_mi355x_scan_form): 0 the integer pipe (k_clip_quad), 1 the matrix cores
+// (k_clip_conv_mfma), -1 automatic: the matrix cores from scan_mfma_min() windows on.  The maps are the same either way.
+int &scan_form() {
+  static int form = [] {
+    const char *e = std::getenv("BNN_MI355X_SCAN");
+    return e && std::strcmp(e, "valu") == 0 ? 0 : e && std::strcmp(e, "mfma") == 0 ? 1 : -1;
+  }();
+  return form;
+}
+// The automatic form's edge, in windows of the call.  Built in: 5 387, one 640 x 480 frame at sizes (64, 96), the smallest
+// clip measured: from there to 64 frames the stages' device time under the matrix form is x0.77 .. x0.62 of the integer
+// kernels', whose own spread is x1.16 .. x1.01 (profiles/r33_scan_form_rate.txt, DESIGN.md 9 "Clip scan"); below it nothing
+// is measured and the integer kernels stay.  Read at every call, so that a process can move it.
+constexpr long kScanMfmaMin = 5387;
+long scan_mfma_min() {
+  const char *e = std::getenv("BNN_MI355X_SCAN_MFMA_MIN");
+  return e && *e ? std::atol(e) : kScanMfmaMin;
+}
+// bits 1-3: the stages a clip call with that many windows runs on the matrix cores.  0 where the operand tables are not
+// there: another network, BNN_MI355X_CONV=valu, nothing loaded.
+unsigned clip_matrix_stages(long windows) {
+  const Runtime &r = rt();
+  if (!r.d_blob || r.spec.id != NET_CNVW1A1 || !r.conv_mfma || !r.d_conv_mfma) return 0;
+  const int form = scan_form();
+  return form == 1 || (form == -1 && windows >= scan_mfma_min()) ? 0b1110u : 0u;
+}
+
 // every workspace of a clip call (grow-only; the map buffers are the scan's and grow as they do, behind a device
 // synchronise), and the level's Lanczos tables, built once for all frames; raw_bytes: of uploaded raw frames (0: none)
 int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
   if (raw_bytes && rt().d_clip_raw.grow(raw_bytes)) return -1;
   Runtime &r = rt();
   clip_tables(p, job.tables);
+  job.matrix = clip_matrix_stages(p.windows);
+  if (job.matrix) {  // the band tables go behind the others (16-byte aligned): one upload for both
+    clip_mfma_tables(p, job.mfma);
+    job.mfma_base = (job.tables.words.size() + 3) & ~(size_t)3;
+    job.tables.words.resize(job.mfma_base, 0);
+    job.tables.words.insert(job.tables.words.end(), job.mfma.words.begin(), job.mfma.words.end());
+    std::vector<int32_t>().swap(job.mfma.words);
+  }
   job.tabs.assign(p.scene.levels.size(), ResizeTables{});
   for (size_t k = 0; k < p.scene.levels.size(); k++) {
     const ScanLevel &lv = p.scene.levels[k];
@@ -5514,6 +5552,14 @@ int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const 
     a.desc[l] = job.tables.desc[l]; a.block_map[l] = job.tables.block_map[l]; a.blocks[l] = p.blocks[l];
   }
   a.tables = r.d_scan_clip_tab;
+  a.matrix_stages = job.matrix;
+  if (job.matrix) {
+    a.conv_mfma = r.d_conv_mfma;
+    a.conv_mfma_off[1] = 0; a.conv_mfma_off[2] = kConvMfmaL2Off; a.conv_mfma_off[3] = kConvMfmaL3Off;
+    for (int l = 1; l <= 3; l++) {
+      a.mfma_maps[l] = job.mfma_base + job.mfma.maps[l]; a.mfma_bands[l] = job.mfma_base + job.mfma.bands[l]; a.mfma_blocks[l] = job.mfma.blocks[l];
+    }
+  }
   a.stream = s;
   a.last_stage = last_stage < kScanStages - 1 ? last_stage : kScanStages - 1;
   hipError_t e = run_scan_clip(a);
@@ -5754,6 +5800,15 @@ long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long 
   drain.ok();
   return (long)bytes;
 }
+
+int bnn_mi355x_scan_form(int form) {
+  int &f = scan_form();
+  const int was = f;
+  if (form >= -1 && form <= 1) f = form;
+  return was;
+}
+
+int bnn_mi355x_scan_matrix_stages(long windows) { return (int)clip_matrix_stages(windows); }
 
 }  // extern "C"
 

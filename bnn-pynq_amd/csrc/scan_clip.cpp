@@ -154,4 +154,40 @@ void clip_tables(const ClipPlan &plan, ClipTables &t) {
   }
 }
 
+void clip_mfma_tables(const ClipPlan &plan, ClipMfmaTables &t) {
+  const size_t n_maps = plan.maps.size();
+  constexpr size_t kMapWords = sizeof(ClipMfmaMap) / sizeof(int32_t), kBandWords = sizeof(ClipMfmaBand) / sizeof(int32_t);
+  t = ClipMfmaTables{};
+  for (int s = 1; s <= 3; s++) {
+    t.maps[s] = t.words.size();
+    t.words.resize(t.words.size() + n_maps * kMapWords, 0);
+    t.bands[s] = t.words.size();
+    long block = 0;
+    for (size_t m = 0; m < n_maps; m++) {
+      const ClipMap &cm = plan.maps[m];
+      const ScanPlan &p = plan.scene.levels[(size_t)cm.level].plan;
+      const bool pool = s != 2;
+      ClipMfmaMap d{};
+      d.in_off = (long long)cm.off[s - 1];
+      d.out_off = (long long)cm.off[s];
+      d.iw = p.w[s - 1];
+      d.ow = p.w[s - 1] - 2;
+      d.row_pairs = (p.h[s - 1] - 2) / 2;
+      d.first_block = (int)block;
+      // whole quads (scan.h: the conv outputs of stages 1-3 are even both ways), and the map the stage leaves is theirs
+      assert(d.ow % 2 == 0 && (p.h[s - 1] - 2) % 2 == 0 && d.ow > 0 && d.row_pairs > 0);
+      assert(p.w[s] == (pool ? d.ow / 2 : d.ow) && p.h[s] == (pool ? d.row_pairs : 2 * d.row_pairs));
+      std::memcpy(&t.words[t.maps[s] + m * kMapWords], &d, sizeof(d));
+      for (int rp0 = 0; rp0 < d.row_pairs; rp0 += kClipMfmaRowPairs)
+        for (int x0 = 0; x0 < d.ow; x0 += kClipMfmaChunk) {
+          const ClipMfmaBand b{(int)m, rp0, x0, 0};
+          t.words.resize(t.words.size() + kBandWords);
+          std::memcpy(&t.words[t.words.size() - kBandWords], &b, sizeof(b));
+          block++;
+        }
+    }
+    t.blocks[s] = block;
+  }
+}
+
 }  // namespace bnn

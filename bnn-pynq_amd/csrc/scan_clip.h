@@ -80,4 +80,31 @@ struct ClipTables {
 };
 void clip_tables(const ClipPlan &plan, ClipTables &t);
 
+// ---- the matrix-core form of stages 1-3 (k_clip_conv_mfma, scan_mfma_kernels.hip; DESIGN.md 9 "Clip scan") ------------
+// A block owns a BAND of one map: kClipMfmaRowPairs output row pairs x kClipMfmaChunk conv-output columns (less at the
+// map's bottom and right edges).  Its input patch is (2 row pairs + 2) rows x (columns + 2) columns of the map before.
+constexpr int kClipMfmaRowPairs = 8, kClipMfmaChunk = 64;
+// What a block looks up, through scalar loads like ClipMapDesc: its map's descriptor and its own band.
+struct ClipMfmaMap {
+  long long in_off, out_off;  // bytes into the launch's input and output buffers (ClipMap::off of stages s - 1 and s)
+  int iw;                     // width of the input map, pixels
+  int ow;                     // conv-output width (even; the pooled stages store ow / 2 columns)
+  int row_pairs;              // conv-output rows / 2
+  int first_block;
+};
+static_assert(sizeof(ClipMfmaMap) == 32, "8 dwords");
+struct ClipMfmaBand {
+  int map, rp0, x0;  // first row pair and first conv-output column (a multiple of kClipMfmaChunk) of the band
+  int pad;
+};
+static_assert(sizeof(ClipMfmaBand) == 16, "4 dwords");
+// One int32 array: for stage s = 1..3 the ClipMfmaMap of all maps at maps[s], then the ClipMfmaBand of all blocks of the
+// stage's launch at bands[s] (offsets in int32 units, both 16-byte aligned).  Entry 0 of the arrays is unused.
+struct ClipMfmaTables {
+  std::vector<int32_t> words;
+  size_t maps[4] = {}, bands[4] = {};
+  long blocks[4] = {};
+};
+void clip_mfma_tables(const ClipPlan &plan, ClipMfmaTables &t);
+
 }  // namespace bnn

@@ -904,18 +904,18 @@ class CnvClassifier:
         return None
 
     def scan_form(self, form=None):
-        """The form of layers 1-3 in the clip calls (:meth:`scan_clip`, :meth:`detect_clip`): 0 the integer pipe, 1 the
-        matrix cores, -1 automatic (``bnn_mi355x_scan_form``).  Sets ``form`` when given; returns the form before the
-        call.  The answers do not depend on it."""
+        """The form of layers 1-5 in the clip calls (:meth:`scan_clip`, :meth:`detect_clip`): 0 the integer pipe, 1 layers 1-3
+        on the matrix cores, 2 layers 1-5 on the matrix cores, -1 automatic (``bnn_mi355x_scan_form``).  Sets ``form`` when
+        given; returns the form before the call.  The answers do not depend on it."""
         lib = self.bnn.interface
         if not hasattr(lib, "bnn_mi355x_scan_form"):
             raise RuntimeError("scan_form: this library has no bnn_mi355x_scan_form")
-        if form is not None and form not in (-1, 0, 1):
-            raise ValueError("scan_form: form must be -1, 0 or 1")
+        if form is not None and form not in (-1, 0, 1, 2):
+            raise ValueError("scan_form: form must be -1, 0, 1 or 2")
         return int(lib.bnn_mi355x_scan_form(7 if form is None else int(form)))
 
     def scan_matrix_stages(self, windows):
-        """bit mask (bits 1-3) of the stages a clip call with ``windows`` windows runs on the matrix cores under the current
+        """bit mask (bits 1-5) of the stages a clip call with ``windows`` windows runs on the matrix cores under the current
         form (``bnn_mi355x_scan_matrix_stages``); 0 on networks other than cnvW1A1"""
         lib = self.bnn.interface
         if not hasattr(lib, "bnn_mi355x_scan_matrix_stages"):

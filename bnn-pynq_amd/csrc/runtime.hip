@@ -5383,7 +5383,8 @@ static_assert(kScanClipMaxFrames == BNN_MI355X_SCAN_CLIP_MAX_FRAMES && kScanClip
 struct ClipJob {
   ClipTables tables;    // with the matrix form's tables behind them, from mfma_base on, when the call takes that form
   ClipMfmaTables mfma;  // (offsets and block counts; its words have moved into tables.words)
-  size_t mfma_base = 0;
+  ClipTailTables tail;  // stages 4 and 5's, behind them from tail_base on, under form 2 (likewise)
+  size_t mfma_base = 0, tail_base = 0;
   unsigned matrix = 0;  // clip_matrix_stages of the call, decided when it reserves
   std::vector<int32_t> coef;
   std::vector<ResizeTables> tabs;
@@ -5402,12 +5403,13 @@ struct ClipSource {
   size_t raw_bytes() const { return raw && !device ? layout.frame_span * (size_t)layout.n_frames : 0; }
 };
 
-// The form of a clip call's stages 1-3 (bnn_mi355x_scan_form): 0 the integer pipe (k_clip_quad), 1 the matrix cores
-// (k_clip_conv_mfma), -1 automatic: the matrix cores from scan_mfma_min() windows on.  The maps are the same either way.
+// The form of a clip call's stages 1-5 (bnn_mi355x_scan_form): 0 the integer pipe (k_clip_quad, k_clip_vec), 1 stages 1-3 on
+// the matrix cores (k_clip_conv_mfma), 2 stages 4 and 5 as well (k_clip_tail_mfma), -1 automatic: form 1 from scan_mfma_min()
+// windows on.  The maps are the same either way.
 int &scan_form() {
   static int form = [] {
     const char *e = std::getenv("BNN_MI355X_SCAN");
-    return e && std::strcmp(e, "valu") == 0 ? 0 : e && std::strcmp(e, "mfma") == 0 ? 1 : -1;
+    return e && std::strcmp(e, "valu") == 0 ? 0 : e && std::strcmp(e, "mfma") == 0 ? 1 : e && std::strcmp(e, "mfma5") == 0 ? 2 : -1;
   }();
   return form;
 }
@@ -5420,13 +5422,13 @@ long scan_mfma_min() {
   const char *e = std::getenv("BNN_MI355X_SCAN_MFMA_MIN");
   return e && *e ? std::atol(e) : kScanMfmaMin;
 }
-// bits 1-3: the stages a clip call with that many windows runs on the matrix cores.  0 where the operand tables are not
+// bits 1-5: the stages a clip call with that many windows runs on the matrix cores.  0 where the operand tables are not
 // there: another network, BNN_MI355X_CONV=valu, nothing loaded.
 unsigned clip_matrix_stages(long windows) {
   const Runtime &r = rt();
   if (!r.d_blob || r.spec.id != NET_CNVW1A1 || !r.conv_mfma || !r.d_conv_mfma) return 0;
   const int form = scan_form();
-  return form == 1 || (form == -1 && windows >= scan_mfma_min()) ? 0b1110u : 0u;
+  return form == 2 ? 0b111110u : form == 1 || (form == -1 && windows >= scan_mfma_min()) ? 0b1110u : 0u;
 }
 
 // every workspace of a clip call (grow-only; the map buffers are the scan's and grow as they do, behind a device
@@ -5442,6 +5444,13 @@ int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
     job.tables.words.resize(job.mfma_base, 0);
     job.tables.words.insert(job.tables.words.end(), job.mfma.words.begin(), job.mfma.words.end());
     std::vector<int32_t>().swap(job.mfma.words);
+  }
+  if (job.matrix & 0b110000u) {
+    clip_tail_tables(p, job.tail);
+    job.tail_base = (job.tables.words.size() + 3) & ~(size_t)3;
+    job.tables.words.resize(job.tail_base, 0);
+    job.tables.words.insert(job.tables.words.end(), job.tail.words.begin(), job.tail.words.end());
+    std::vector<int32_t>().swap(job.tail.words);
   }
   job.tabs.assign(p.scene.levels.size(), ResizeTables{});
   for (size_t k = 0; k < p.scene.levels.size(); k++) {
@@ -5558,6 +5567,10 @@ int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const 
     a.conv_mfma_off[1] = 0; a.conv_mfma_off[2] = kConvMfmaL2Off; a.conv_mfma_off[3] = kConvMfmaL3Off;
     for (int l = 1; l <= 3; l++) {
       a.mfma_maps[l] = job.mfma_base + job.mfma.maps[l]; a.mfma_bands[l] = job.mfma_base + job.mfma.bands[l]; a.mfma_blocks[l] = job.mfma.blocks[l];
+    }
+    a.conv_mfma_off[4] = kTailMfmaL4Off; a.conv_mfma_off[5] = kTailMfmaL5Off;
+    for (int l = 4; l <= 5 && (job.matrix >> l & 1); l++) {
+      a.mfma_maps[l] = job.tail_base + job.tail.maps[l - 4]; a.mfma_bands[l] = job.tail_base + job.tail.bands[l - 4]; a.mfma_blocks[l] = job.tail.blocks[l - 4];
     }
   }
   a.stream = s;
@@ -5804,7 +5817,7 @@ long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long 
 int bnn_mi355x_scan_form(int form) {
   int &f = scan_form();
   const int was = f;
-  if (form >= -1 && form <= 1) f = form;
+  if (form >= -1 && form <= 2) f = form;
   return was;
 }
 

@@ -190,4 +190,39 @@ void clip_mfma_tables(const ClipPlan &plan, ClipMfmaTables &t) {
   }
 }
 
+void clip_tail_tables(const ClipPlan &plan, ClipTailTables &t) {
+  const size_t n_maps = plan.maps.size();
+  constexpr size_t kMapWords = sizeof(ClipTailMap) / sizeof(int32_t), kBandWords = sizeof(ClipTailBand) / sizeof(int32_t);
+  t = ClipTailTables{};
+  for (int s = 4; s <= 5; s++) {
+    t.maps[s - 4] = t.words.size();
+    t.words.resize(t.words.size() + n_maps * kMapWords, 0);
+    t.bands[s - 4] = t.words.size();
+    long block = 0;
+    for (size_t m = 0; m < n_maps; m++) {
+      const ClipMap &cm = plan.maps[m];
+      const ScanPlan &p = plan.scene.levels[(size_t)cm.level].plan;
+      ClipTailMap d{};
+      d.in_off = (long long)cm.off[s - 1];
+      d.out_off = (long long)cm.off[s];
+      d.ow = p.w[s];
+      d.oh = p.h[s];
+      assert(d.ow > 0 && d.oh > 0 && p.w[s - 1] == d.ow + 2 && p.h[s - 1] == d.oh + 2);
+      const int rps = (d.oh + 1) / 2, nbx = (d.ow + kClipTailCols - 1) / kClipTailCols, nby = (rps + kClipTailRowPairs - 1) / kClipTailRowPairs;
+      d.band_cols = (d.ow + nbx - 1) / nbx;
+      d.band_rps = (rps + nby - 1) / nby;
+      d.first_block = (int)block;
+      std::memcpy(&t.words[t.maps[s - 4] + m * kMapWords], &d, sizeof(d));
+      for (int rp0 = 0; rp0 < rps; rp0 += d.band_rps)
+        for (int x0 = 0; x0 < d.ow; x0 += d.band_cols) {
+          const ClipTailBand b{(int)m, rp0, x0, 0};
+          t.words.resize(t.words.size() + kBandWords);
+          std::memcpy(&t.words[t.words.size() - kBandWords], &b, sizeof(b));
+          block++;
+        }
+    }
+    t.blocks[s - 4] = block;
+  }
+}
+
 }  // namespace bnn

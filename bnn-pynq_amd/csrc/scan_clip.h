@@ -107,4 +107,33 @@ struct ClipMfmaTables {
 };
 void clip_mfma_tables(const ClipPlan &plan, ClipMfmaTables &t);
 
+// ---- the matrix-core form of stages 4 and 5 (k_clip_tail_mfma, scan_tail_mfma_kernels.hip; DESIGN.md 9 "Clip scan") ----
+// Layers 4 and 5 have no pool and small ragged maps.  A block owns a BAND of one map: up to kClipTailRowPairs pairs of
+// output rows x up to kClipTailCols output columns.  A map's bands are equal shares, not full bands and a remainder: a map of
+// ow columns has ceil(ow / kClipTailCols) band columns of ceil(ow / that) columns each (the last may be narrower), and its
+// ceil(oh / 2) row pairs are shared out likewise; an odd oh leaves the last row pair with one row.  The band's input patch is
+// (2 row pairs + 2) rows x (columns + 2) columns of the stage before's map, less the row past its end when oh is odd.
+constexpr int kClipTailRowPairs = 4, kClipTailCols = 64;
+struct ClipTailMap {
+  long long in_off, out_off;  // bytes into the launch's input and output buffers (ClipMap::off of stages s - 1 and s)
+  int ow, oh;                 // the output map; the input map is (ow + 2) x (oh + 2)
+  int band_cols, band_rps;    // the map's share sizes: columns and row pairs of all its bands but the last of a row / column
+  int first_block;
+  int pad[3];
+};
+static_assert(sizeof(ClipTailMap) == 48, "12 dwords");
+struct ClipTailBand {
+  int map, rp0, x0;  // first row pair (a multiple of band_rps) and first output column (a multiple of band_cols)
+  int pad;
+};
+static_assert(sizeof(ClipTailBand) == 16, "4 dwords");
+// One int32 array: for stage s = 4, 5 the ClipTailMap of all maps at maps[s - 4], then the ClipTailBand of all blocks of
+// the stage's launch at bands[s - 4] (offsets in int32 units, both 16-byte aligned).
+struct ClipTailTables {
+  std::vector<int32_t> words;
+  size_t maps[2] = {}, bands[2] = {};
+  long blocks[2] = {};
+};
+void clip_tail_tables(const ClipPlan &plan, ClipTailTables &t);
+
 }  // namespace bnn

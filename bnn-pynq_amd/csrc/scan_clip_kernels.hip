@@ -10,6 +10,7 @@
 #include "scan_clip_kernels.h"
 #include "scan_bodies.h"
 #include "scan_mfma_kernels.h"
+#include "scan_tail_mfma_kernels.h"
 
 namespace bnn {
 namespace {
@@ -93,19 +94,21 @@ hipError_t run_scan_clip(const ScanClipLaunch &a) {
   auto descs = [&](int stage) { return reinterpret_cast<const ClipMapDesc *>(a.tables + a.desc[stage]); };
   auto bmap = [&](int stage) { return a.tables + a.block_map[stage]; };
   if (a.last_stage >= 0) hipLaunchKernelGGL(k_clip_conv0, grid(0, 2), dim3(kBlock), 0, s, a.planes, A, a.rows[0], descs(0), bmap(0));
-  // stages 1-3: the integer kernels, or the matrix-core form where the caller chose it (host code only: the kernels of this file are what they were)
+  // stages 1-5: the integer kernels, or the matrix-core form where the caller chose it (host code only: the kernels of this file are what they were)
   auto matrix = [&](int stage, const uint8_t *in, uint8_t *out) {
     if (stage > a.last_stage || !(a.matrix_stages >> stage & 1)) return false;
-    const ClipMfmaLaunch m{in, out, a.conv_mfma + a.conv_mfma_off[stage], a.tables + a.mfma_maps[stage], a.tables + a.mfma_bands[stage], a.mfma_blocks[stage], s};
-    const hipError_t e = launch_clip_conv_mfma(stage, m);
+    const uint8_t *tab = a.conv_mfma + a.conv_mfma_off[stage];
+    const int32_t *maps = a.tables + a.mfma_maps[stage], *bands = a.tables + a.mfma_bands[stage];
+    const hipError_t e = stage <= 3 ? launch_clip_conv_mfma(stage, ClipMfmaLaunch{in, out, tab, maps, bands, a.mfma_blocks[stage], s})
+                                    : launch_clip_tail_mfma(stage, ClipTailLaunch{in, out, tab, maps, bands, a.mfma_blocks[stage], s});
     if (e != hipSuccess && failed == hipSuccess) failed = e;
     return true;
   };
   if (a.last_stage >= 1 && !matrix(1, A, B)) hipLaunchKernelGGL((k_clip_quad<1, true>), grid(1, 2), dim3(kBlock), 0, s, A, B, a.rows[1], descs(1), bmap(1), 2);
   if (a.last_stage >= 2 && !matrix(2, B, A)) hipLaunchKernelGGL((k_clip_quad<1, false>), grid(2, 4), dim3(kBlock), 0, s, B, A, a.rows[2], descs(2), bmap(2), 4);
   if (a.last_stage >= 3 && !matrix(3, A, B)) hipLaunchKernelGGL((k_clip_quad<2, true>), grid(3, 4), dim3(kBlock), 0, s, A, B, a.rows[3], descs(3), bmap(3), 4);
-  if (a.last_stage >= 4) hipLaunchKernelGGL((k_clip_vec<2>), grid(4, 8), dim3(kBlock), 0, s, B, A, a.rows[4], descs(4), bmap(4), 8);
-  if (a.last_stage >= 5) hipLaunchKernelGGL((k_clip_vec<4>), grid(5, 8), dim3(kBlock), 0, s, A, B, a.rows[5], descs(5), bmap(5), 8);
+  if (a.last_stage >= 4 && !matrix(4, B, A)) hipLaunchKernelGGL((k_clip_vec<2>), grid(4, 8), dim3(kBlock), 0, s, B, A, a.rows[4], descs(4), bmap(4), 8);
+  if (a.last_stage >= 5 && !matrix(5, A, B)) hipLaunchKernelGGL((k_clip_vec<4>), grid(5, 8), dim3(kBlock), 0, s, A, B, a.rows[5], descs(5), bmap(5), 8);
   return failed != hipSuccess ? failed : hipGetLastError();
 }
 

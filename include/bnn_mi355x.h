@@ -894,17 +894,21 @@ int bnn_mi355x_scan_clip_layout(int width, int height, const int *sizes, int n_s
 long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
                                       const int *sizes, int n_sizes, int stage, void *out, size_t cap);
 
-/* The form of a clip call's stages 1-3 (layers 1-3 over all maps of the clip): the integer pipe (k_clip_quad: one lane per
- * 2 x 2 quad, XNOR and popcount) or the matrix cores (k_clip_conv_mfma, csrc/scan_mfma_kernels.hip: exact FP4 GEMMs on the
- * operand tables every load_parameters makes; DESIGN.md 9 "Clip scan").  Both write the same maps, byte for byte: no
- * answer of scan_clip, detect_clip, their _frames and _device twins or debug_scan_clip_stage depends on the form.
- * scan_form: sets the form and returns the previous one.  0: the integer pipe; 1: the matrix cores whatever the size; -1:
- *       automatic, the matrix cores from BNN_MI355X_SCAN_MFMA_MIN windows of a call on (built in: 5 387, the smallest
- *       clip measured faster).  Any other value changes nothing and returns the current form.  Initially
- *       -1, or what BNN_MI355X_SCAN says (valu: 0, mfma: 1).  Takes effect at the next clip call.
- * scan_matrix_stages: bits 1-3 are set for the stages a clip call with that many windows would run on the matrix cores
- *       under the current form.  0 under form 0, on a library that is not cnvW1A1, under BNN_MI355X_CONV=valu (no operand
- *       tables: the integer kernels run even under form 1) and while no parameters are loaded. */
+/* The form of a clip call's stages 1-5 (layers 1-5 over all maps of the clip): the integer pipe (k_clip_quad: one lane per
+ * 2 x 2 quad, k_clip_vec: one lane per pixel, XNOR and popcount) or the matrix cores (k_clip_conv_mfma,
+ * csrc/scan_mfma_kernels.hip, for stages 1-3 and k_clip_tail_mfma, csrc/scan_tail_mfma_kernels.hip, for stages 4 and 5:
+ * exact FP4 GEMMs on the operand tables every load_parameters makes; DESIGN.md 9 "Clip scan").  All write the same maps,
+ * byte for byte: no answer of scan_clip, detect_clip, their _frames and _device twins or debug_scan_clip_stage depends on
+ * the form.
+ * scan_form: sets the form and returns the previous one.  0: the integer pipe; 1: stages 1-3 on the matrix cores whatever
+ *       the size; 2: stages 1-5 on the matrix cores whatever the size; -1: automatic, form 1 from BNN_MI355X_SCAN_MFMA_MIN
+ *       windows of a call on (built in: 5 387, the smallest clip measured faster) and form 0 below.  Any other
+ *       value changes nothing and returns the current form.  Initially -1, or what BNN_MI355X_SCAN says (valu: 0, mfma: 1,
+ *       mfma5: 2).  Takes effect at the next clip call.
+ * scan_matrix_stages: bits 1-5 are set for the stages a clip call with that many windows would run on the matrix cores
+ *       under the current form: 0b1110 under form 1, 0b111110 under form 2.  0 under form 0, on a library that is not
+ *       cnvW1A1, under BNN_MI355X_CONV=valu (no operand tables: the integer kernels run under every form) and while no
+ *       parameters are loaded. */
 int bnn_mi355x_scan_form(int form);
 int bnn_mi355x_scan_matrix_stages(long windows);
 

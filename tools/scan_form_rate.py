@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""The two forms of the clip scan's stages 1-3: F frames of the 640 x 480 street picture (frame f is the picture rolled by
-4 f columns), window sizes (64, 96), cnvW1A1 road-signs, F = 1, 4, 16 and 64.  The yardstick is form 0, the integer
-kernels (k_clip_quad); it alternates in one process with form 1, the matrix cores (k_clip_conv_mfma), ONE scan_clip call
-each on the same frames.  Each form reports the wall time of the call and the device time the entry point returns
-(usecPerImage times the windows: the six stage launches with layers 6-8 and the decode behind them, between two events);
-medians and ranges of seven alternations after one untimed call each, scores asserted equal in every call.  The record
-goes to profiles/r33_scan_form_rate.txt.  usage: scan_form_rate.py [rounds]"""
+"""The three forms of the clip scan's stages 1-5: F frames of the 640 x 480 street picture (frame f is the picture rolled by
+4 f columns), window sizes (64, 96), cnvW1A1 road-signs, F = 1, 4, 16 and 64.  Form 0, the integer kernels (k_clip_quad,
+k_clip_vec), form 1, stages 1-3 on the matrix cores (k_clip_conv_mfma), and form 2, stages 4 and 5 there as well
+(k_clip_tail_mfma), alternate in one process, ONE scan_clip call each on the same frames, the order rotating every
+round.  Form 0 is form 1's yardstick and form 1, the fastest route before form 2, is form 2's.  Each form reports the wall
+time of the call and the device time the entry point returns (usecPerImage times the windows: the six stage launches
+with layers 6-8 and the decode behind them, between two events); medians and ranges of seven rounds after one untimed
+call each, scores asserted equal in every call.  The records are profiles/r33_scan_form_rate.txt (forms 0 and 1) and
+profiles/r34_scan_tail_rate.txt (all three).  usage: scan_form_rate.py [rounds]"""
 import contextlib
 import io
 import os
@@ -23,6 +25,8 @@ import bnn  # noqa: E402
 
 SIZES = (64, 96)
 CLIPS = (1, 4, 16, 64)
+MASKS = {0: 0, 1: 0b1110, 2: 0b111110}
+NAMES = ((0, "form 0, integer pipe:"), (1, "form 1, layers 1-3:"), (2, "form 2, layers 1-5:"))
 
 
 @contextlib.contextmanager
@@ -53,7 +57,7 @@ n = sum(len(clf.scan_boxes(im.size, s)[1]) for s in SIZES)
 
 def route(clip, form):
     clf.scan_form(form)
-    assert clf.scan_matrix_stages(n * len(clip)) == (0b1110 if form else 0)
+    assert clf.scan_matrix_stages(n * len(clip)) == MASKS[form]
     t0 = time.perf_counter()
     _, scores = clf.scan_clip(clip, SIZES, details=True)
     t1 = time.perf_counter()
@@ -65,23 +69,24 @@ def spread(v):
 
 
 print("cnvW1A1 road-signs, street_with_stop.jpg 640 x 480 RGB rolled by 4 f columns, sizes %s: %d windows a frame; ms per scan_clip call, %d "
-      "alternations in one process after one untimed call each; scores equal in every call" % (SIZES, n, rounds))
+      "rounds of the three forms in one process after one untimed call each; scores equal in every call" % (SIZES, n, rounds))
 was = clf.scan_form()
 for frames in CLIPS:
     clip = np.ascontiguousarray(np.stack([np.roll(picture, 4 * f, axis=1) for f in range(frames)]))
     ref = route(clip, 0)[0]  # once each, untimed
-    assert (route(clip, 1)[0] == ref).all()
-    wall, dev = {0: [], 1: []}, {0: [], 1: []}
+    assert (route(clip, 1)[0] == ref).all() and (route(clip, 2)[0] == ref).all()
+    wall, dev = {0: [], 1: [], 2: []}, {0: [], 1: [], 2: []}
     for r in range(rounds):
-        for form in ((0, 1) if r % 2 == 0 else (1, 0)):  # the order swaps every round: neither form always runs behind the other
+        for form in ((0, 1, 2), (1, 2, 0), (2, 0, 1))[r % 3]:  # the order rotates every round: no form always runs behind the same one
             s, w, d = route(clip, form)
             assert (s == ref).all()
             wall[form].append(w); dev[form].append(d)
     print("F = %d (%d windows)" % (frames, frames * n))
-    for form, name in ((0, "form 0, integer pipe:"), (1, "form 1, matrix cores:")):
+    for form, name in NAMES:
         print("  %-22s wall                %s" % (name, spread(wall[form])))
         print("  %-22s device, the stages  %s" % ("", spread(dev[form])))
     for what, v in (("wall", wall), ("device (stages)", dev)):
-        print("  %s, medians: form 1 x%.3f of form 0; form 0's own spread x%.3f (max / min of its %d repeats)"
-              % (what, statistics.median(v[1]) / statistics.median(v[0]), max(v[0]) / min(v[0]), rounds))
+        for form, base in ((1, 0), (2, 1)):
+            print("  %s, medians: form %d x%.3f of form %d; form %d's own spread x%.3f (max / min of its %d repeats)"
+                  % (what, form, statistics.median(v[form]) / statistics.median(v[base]), base, base, max(v[base]) / min(v[base]), rounds))
 clf.scan_form(was)

@@ -52,7 +52,7 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_scan_clip_layout", "bnn_mi355x_debug_scan_clip_stage", "bnn_mi355x_detect_windows_host",
        "bnn_mi355x_detect_windows", "bnn_mi355x_detect_clip", "bnn_mi355x_unpack_frames_host", "bnn_mi355x_unpack_frames",
        "bnn_mi355x_scan_clip_frames", "bnn_mi355x_detect_clip_frames", "bnn_mi355x_scan_clip_device", "bnn_mi355x_detect_clip_device",
-       "bnn_mi355x_scan_form", "bnn_mi355x_scan_matrix_stages"]
+       "bnn_mi355x_scan_form", "bnn_mi355x_scan_matrix_stages", "bnn_mi355x_scan_stage0_form"]
 
 # bnn_mi355x_frames.format by name (include/bnn_mi355x.h, BNN_MI355X_FORMAT_*)
 PIXEL_FORMATS = {"rgb": 0, "l": 1, "bgr": 2, "nv12": 3, "i420": 4, "yuyv": 5}
@@ -353,6 +353,9 @@ def declare_extensions(L):
         L.bnn_mi355x_scan_form.restype = C.c_int
         L.bnn_mi355x_scan_matrix_stages.argtypes = [C.c_long]
         L.bnn_mi355x_scan_matrix_stages.restype = C.c_int
+    if hasattr(L, "bnn_mi355x_scan_stage0_form"):  # (likewise)
+        L.bnn_mi355x_scan_stage0_form.argtypes = [C.c_int]
+        L.bnn_mi355x_scan_stage0_form.restype = C.c_int
     if hasattr(L, "bnn_mi355x_detect_clip"):  # (likewise)
         do = C.POINTER(DetectOpts)
         L.bnn_mi355x_detect_windows_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, do, C.c_void_p, C.c_void_p, C.c_void_p]

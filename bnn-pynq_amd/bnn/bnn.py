@@ -914,8 +914,19 @@ class CnvClassifier:
             raise ValueError("scan_form: form must be -1, 0, 1 or 2")
         return int(lib.bnn_mi355x_scan_form(7 if form is None else int(form)))
 
+    def scan_stage0_form(self, form=None):
+        """The form of layer 0 in the clip calls (:meth:`scan_clip`, :meth:`detect_clip`), beside :meth:`scan_form`: 0 the
+        integer pipe, 1 the matrix cores (``bnn_mi355x_scan_stage0_form``); never automatic.  Sets ``form`` when given;
+        returns the form before the call.  The answers do not depend on it."""
+        lib = self.bnn.interface
+        if not hasattr(lib, "bnn_mi355x_scan_stage0_form"):
+            raise RuntimeError("scan_stage0_form: this library has no bnn_mi355x_scan_stage0_form")
+        if form is not None and form not in (0, 1):
+            raise ValueError("scan_stage0_form: form must be 0 or 1")
+        return int(lib.bnn_mi355x_scan_stage0_form(7 if form is None else int(form)))
+
     def scan_matrix_stages(self, windows):
-        """bit mask (bits 1-5) of the stages a clip call with ``windows`` windows runs on the matrix cores under the current
+        """bit mask (bit 0: :meth:`scan_stage0_form`; bits 1-5) of the stages a clip call with ``windows`` windows runs on the matrix cores under the current
         form (``bnn_mi355x_scan_matrix_stages``); 0 on networks other than cnvW1A1"""
         lib = self.bnn.interface
         if not hasattr(lib, "bnn_mi355x_scan_matrix_stages"):

@@ -5384,7 +5384,8 @@ struct ClipJob {
   ClipTables tables;    // with the matrix form's tables behind them, from mfma_base on, when the call takes that form
   ClipMfmaTables mfma;  // (offsets and block counts; its words have moved into tables.words)
   ClipTailTables tail;  // stages 4 and 5's, behind them from tail_base on, under form 2 (likewise)
-  size_t mfma_base = 0, tail_base = 0;
+  ClipL0Tables l0;      // stage 0's, behind them from l0_base on, under stage-0 form 1 (likewise)
+  size_t mfma_base = 0, tail_base = 0, l0_base = 0;
   unsigned matrix = 0;  // clip_matrix_stages of the call, decided when it reserves
   std::vector<int32_t> coef;
   std::vector<ResizeTables> tabs;
@@ -5422,13 +5423,25 @@ long scan_mfma_min() {
   const char *e = std::getenv("BNN_MI355X_SCAN_MFMA_MIN");
   return e && *e ? std::atol(e) : kScanMfmaMin;
 }
-// bits 1-5: the stages a clip call with that many windows runs on the matrix cores.  0 where the operand tables are not
-// there: another network, BNN_MI355X_CONV=valu, nothing loaded.
+// The form of a clip call's stage 0 (bnn_mi355x_scan_stage0_form), an axis of its own: 0 the integer pipe (k_clip_conv0),
+// 1 the matrix cores (k_clip_conv0_mfma).  Never automatic.  The maps are the same either way.
+int &scan_stage0_form() {
+  static int form = [] {
+    const char *e = std::getenv("BNN_MI355X_SCAN_L0");
+    return e && std::strcmp(e, "mfma") == 0 ? 1 : 0;
+  }();
+  return form;
+}
+// bits 0-5: the stages a clip call with that many windows runs on the matrix cores.  Bits 1-5 are 0 where the operand
+// tables are not there: another network, BNN_MI355X_CONV=valu, nothing loaded; bit 0 likewise where layer 0's MFMA table is
+// not (BNN_MI355X_L0=valu).
 unsigned clip_matrix_stages(long windows) {
   const Runtime &r = rt();
-  if (!r.d_blob || r.spec.id != NET_CNVW1A1 || !r.conv_mfma || !r.d_conv_mfma) return 0;
+  if (!r.d_blob || r.spec.id != NET_CNVW1A1) return 0;
+  const unsigned l0 = scan_stage0_form() == 1 && r.l0_mfma ? 1u : 0u;
+  if (!r.conv_mfma || !r.d_conv_mfma) return l0;
   const int form = scan_form();
-  return form == 2 ? 0b111110u : form == 1 || (form == -1 && windows >= scan_mfma_min()) ? 0b1110u : 0u;
+  return l0 | (form == 2 ? 0b111110u : form == 1 || (form == -1 && windows >= scan_mfma_min()) ? 0b1110u : 0u);
 }
 
 // every workspace of a clip call (grow-only; the map buffers are the scan's and grow as they do, behind a device
@@ -5438,7 +5451,7 @@ int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
   Runtime &r = rt();
   clip_tables(p, job.tables);
   job.matrix = clip_matrix_stages(p.windows);
-  if (job.matrix) {  // the band tables go behind the others (16-byte aligned): one upload for both
+  if (job.matrix & 0b1110u) {  // the band tables go behind the others (16-byte aligned): one upload for both
     clip_mfma_tables(p, job.mfma);
     job.mfma_base = (job.tables.words.size() + 3) & ~(size_t)3;
     job.tables.words.resize(job.mfma_base, 0);
@@ -5452,6 +5465,15 @@ int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
     job.tables.words.insert(job.tables.words.end(), job.tail.words.begin(), job.tail.words.end());
     std::vector<int32_t>().swap(job.tail.words);
   }
+  size_t planes_need = p.planes_bytes;
+  if (job.matrix & 1u) {  // (its staging loads end up to 7 bytes behind the planes: the tables say where)
+    clip_l0_tables(p, job.l0);
+    job.l0_base = (job.tables.words.size() + 3) & ~(size_t)3;
+    job.tables.words.resize(job.l0_base, 0);
+    job.tables.words.insert(job.tables.words.end(), job.l0.words.begin(), job.l0.words.end());
+    std::vector<int32_t>().swap(job.l0.words);
+    planes_need = std::max(planes_need, job.l0.planes_top);
+  }
   job.tabs.assign(p.scene.levels.size(), ResizeTables{});
   for (size_t k = 0; k < p.scene.levels.size(); k++) {
     const ScanLevel &lv = p.scene.levels[k];
@@ -5461,7 +5483,7 @@ int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
   }
   ScanPlan maps;
   maps.buf0 = p.buf0; maps.buf1 = p.buf1;
-  return (r.d_scan_scene.grow((size_t)p.width * p.height * p.bands * p.frames) || r.d_scan_planes.grow(p.planes_bytes) ||
+  return (r.d_scan_scene.grow((size_t)p.width * p.height * p.bands * p.frames) || r.d_scan_planes.grow(planes_need) ||
           r.d_scan_tmp.grow(job.tmp_frame * p.frames) || r.d_scan_coef.grow(job.coef.size() + 1) ||
           r.d_scan_clip_tab.grow(job.tables.words.size()) || reserve_scan(maps))
              ? -1 : 0;
@@ -5520,7 +5542,7 @@ int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const 
   const size_t frame_bytes = (size_t)p.width * p.height * p.bands;
   const bool in_place = src.device && !src.raw && (p.row_stride == 0 || (size_t)p.row_stride == (size_t)p.width * p.bands) &&
                         (p.frame_stride == 0 || (size_t)p.frame_stride == frame_bytes);
-  if (p.buf0 > r.d_scan_buf0.cap || p.buf1 > r.d_scan_buf1.cap || p.planes_bytes > r.d_scan_planes.cap || job.tables.words.size() > r.d_scan_clip_tab.cap ||
+  if (p.buf0 > r.d_scan_buf0.cap || p.buf1 > r.d_scan_buf1.cap || std::max(p.planes_bytes, job.l0.planes_top) > r.d_scan_planes.cap || job.tables.words.size() > r.d_scan_clip_tab.cap ||
       job.tmp_frame * p.frames > r.d_scan_tmp.cap || (!in_place && frame_bytes * p.frames > r.d_scan_scene.cap) || src.raw_bytes() > r.d_clip_raw.cap)
     return fail(std::string(what) + ": internal: the clip exceeds the scan workspace");
   if (settle_handover(s)) return -1;
@@ -5562,7 +5584,11 @@ int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const 
   }
   a.tables = r.d_scan_clip_tab;
   a.matrix_stages = job.matrix;
-  if (job.matrix) {
+  if (job.matrix & 1u) {
+    a.l0_mfma = r.l0_mfma;
+    a.mfma_maps[0] = job.l0_base + job.l0.maps; a.mfma_bands[0] = job.l0_base + job.l0.bands; a.mfma_blocks[0] = job.l0.blocks;
+  }
+  if (job.matrix & ~1u) {
     a.conv_mfma = r.d_conv_mfma;
     a.conv_mfma_off[1] = 0; a.conv_mfma_off[2] = kConvMfmaL2Off; a.conv_mfma_off[3] = kConvMfmaL3Off;
     for (int l = 1; l <= 3; l++) {
@@ -5822,6 +5848,13 @@ int bnn_mi355x_scan_form(int form) {
 }
 
 int bnn_mi355x_scan_matrix_stages(long windows) { return (int)clip_matrix_stages(windows); }
+
+int bnn_mi355x_scan_stage0_form(int form) {
+  int &f = scan_stage0_form();
+  const int was = f;
+  if (form == 0 || form == 1) f = form;
+  return was;
+}
 
 }  // extern "C"
 

@@ -154,9 +154,23 @@ void clip_tables(const ClipPlan &plan, ClipTables &t) {
   }
 }
 
+// Appends the bands of map m, full bands of band_rows x band_cols and the remainders at the bottom and right edges, rows
+// outer: {m, first row (pair), first column, 0} each.  Returns their number.
+static long append_bands(std::vector<int32_t> &words, int m, int rows, int cols, int band_rows, int band_cols) {
+  constexpr size_t kBandWords = sizeof(ClipMfmaBand) / sizeof(int32_t);
+  long n = 0;
+  for (int r0 = 0; r0 < rows; r0 += band_rows)
+    for (int x0 = 0; x0 < cols; x0 += band_cols, n++) {
+      const ClipMfmaBand b{m, r0, x0, 0};
+      words.resize(words.size() + kBandWords);
+      std::memcpy(&words[words.size() - kBandWords], &b, sizeof(b));
+    }
+  return n;
+}
+
 void clip_mfma_tables(const ClipPlan &plan, ClipMfmaTables &t) {
   const size_t n_maps = plan.maps.size();
-  constexpr size_t kMapWords = sizeof(ClipMfmaMap) / sizeof(int32_t), kBandWords = sizeof(ClipMfmaBand) / sizeof(int32_t);
+  constexpr size_t kMapWords = sizeof(ClipMfmaMap) / sizeof(int32_t);
   t = ClipMfmaTables{};
   for (int s = 1; s <= 3; s++) {
     t.maps[s] = t.words.size();
@@ -178,13 +192,7 @@ void clip_mfma_tables(const ClipPlan &plan, ClipMfmaTables &t) {
       assert(d.ow % 2 == 0 && (p.h[s - 1] - 2) % 2 == 0 && d.ow > 0 && d.row_pairs > 0);
       assert(p.w[s] == (pool ? d.ow / 2 : d.ow) && p.h[s] == (pool ? d.row_pairs : 2 * d.row_pairs));
       std::memcpy(&t.words[t.maps[s] + m * kMapWords], &d, sizeof(d));
-      for (int rp0 = 0; rp0 < d.row_pairs; rp0 += kClipMfmaRowPairs)
-        for (int x0 = 0; x0 < d.ow; x0 += kClipMfmaChunk) {
-          const ClipMfmaBand b{(int)m, rp0, x0, 0};
-          t.words.resize(t.words.size() + kBandWords);
-          std::memcpy(&t.words[t.words.size() - kBandWords], &b, sizeof(b));
-          block++;
-        }
+      block += append_bands(t.words, (int)m, d.row_pairs, d.ow, kClipMfmaRowPairs, kClipMfmaChunk);
     }
     t.blocks[s] = block;
   }
@@ -222,6 +230,36 @@ void clip_tail_tables(const ClipPlan &plan, ClipTailTables &t) {
         }
     }
     t.blocks[s - 4] = block;
+  }
+}
+
+void clip_l0_tables(const ClipPlan &plan, ClipL0Tables &t) {
+  const size_t n_maps = plan.maps.size();
+  constexpr size_t kMapWords = sizeof(ClipL0Map) / sizeof(int32_t);
+  t = ClipL0Tables{};
+  t.words.resize((n_maps * kMapWords + 3) & ~(size_t)3, 0);
+  t.bands = t.words.size();
+  for (size_t m = 0; m < n_maps; m++) {
+    const ClipMap &cm = plan.maps[m];
+    const ScanLevel &lv = plan.scene.levels[(size_t)cm.level];
+    ClipL0Map d{};
+    d.in_off = (long long)cm.planes;
+    d.out_off = (long long)cm.off[0];
+    d.plane_stride = (long long)lv.level_w * lv.level_h;
+    d.row_stride = lv.level_w;
+    d.ow = lv.plan.w[0];
+    d.oh = lv.plan.h[0];
+    d.first_block = (int)t.blocks;
+    // the map's input, (ow + 2) x (oh + 2) of every plane, lies inside the level
+    assert(d.ow > 0 && d.oh > 0 && d.ow + 2 <= lv.level_w && d.oh + 2 <= lv.level_h);
+    std::memcpy(&t.words[m * kMapWords], &d, sizeof(d));
+    t.blocks += append_bands(t.words, (int)m, d.oh, d.ow, kClipL0Rows, kClipL0Cols);
+    // the highest load: the last patch row of plane 2 of the map's last band row; of its columns, whichever ends highest
+    const int y0 = (d.oh - 1) / kClipL0Rows * kClipL0Rows, rows = d.oh - y0;
+    for (int x0 = 0; x0 < d.ow; x0 += kClipL0Cols) {
+      const size_t top = clip_l0_row_top(d, y0, x0, d.ow - x0 < kClipL0Cols ? d.ow - x0 : kClipL0Cols, 2, rows + 1);
+      if (top > t.planes_top) t.planes_top = top;
+    }
   }
 }
 

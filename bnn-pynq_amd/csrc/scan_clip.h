@@ -136,4 +136,39 @@ struct ClipTailTables {
 };
 void clip_tail_tables(const ClipPlan &plan, ClipTailTables &t);
 
+// ---- the matrix-core form of stage 0 (k_clip_conv0_mfma, scan_l0_mfma_kernels.hip; DESIGN.md 9 "Clip scan") ------------
+// A block owns a BAND of one map: kClipL0Rows output rows x kClipL0Cols output columns (less at the map's bottom and right
+// edges).  Its input patch is 3 planes x (rows + 2) rows x (columns + 2) bytes of the level's planar picture, whose rows
+// start at any byte address: the kernel stages a patch row with the aligned dwords around it, dword d of a row being the
+// two aligned dwords at and behind (row start rounded down to 4) + 4 d, for d < ceil((columns + 2) / 4).
+constexpr int kClipL0Rows = 16, kClipL0Cols = 128;
+struct ClipL0Map {
+  long long in_off, out_off;  // bytes: the level's planes among the call's planes (ClipMap::planes), ClipMap::off[0] in buffer 0
+  long long plane_stride;     // bytes between the three planes
+  int row_stride;             // bytes between the rows of a plane (the level's width)
+  int ow, oh;                 // the stage-0 map
+  int first_block;
+};
+static_assert(sizeof(ClipL0Map) == 40, "10 dwords");
+// (a band is a ClipMfmaBand whose rp0 is the band's first output ROW and x0 its first output column)
+// One int32 array: the ClipL0Map of all maps at `maps`, then the ClipMfmaBand of all blocks of the launch at `bands`
+// (offsets in int32 units; maps 8-byte, bands 16-byte aligned when the array is).
+struct ClipL0Tables {
+  std::vector<int32_t> words;
+  size_t maps = 0, bands = 0;
+  long blocks = 0;
+  // One past the highest byte a staging load of the launch touches, from the start of the call's planes (which is 4-byte
+  // aligned): up to 7 bytes past ClipPlan::planes_bytes.  The planes' allocation must hold that many bytes.
+  size_t planes_top = 0;
+};
+void clip_l0_tables(const ClipPlan &plan, ClipL0Tables &t);
+// One past the highest byte the staging of patch row `row` (0 .. rows + 1) of plane `plane` of a band touches; the lowest is
+// clip_l0_row_first.  `rows`, `cols`: the band's output rows and columns.  The kernel's loads, stated once for the plan and its test.
+inline size_t clip_l0_row_first(const ClipL0Map &m, int y0, int x0, int plane, int row) {
+  return ((size_t)m.in_off + (size_t)plane * (size_t)m.plane_stride + (size_t)(y0 + row) * (size_t)m.row_stride + (size_t)x0) & ~(size_t)3;
+}
+inline size_t clip_l0_row_top(const ClipL0Map &m, int y0, int x0, int cols, int plane, int row) {
+  return clip_l0_row_first(m, y0, x0, plane, row) + 4 * (size_t)((cols + 2 + 3) / 4) + 4;
+}
+
 }  // namespace bnn

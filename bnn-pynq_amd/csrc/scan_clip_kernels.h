@@ -20,18 +20,22 @@ struct ScanClipLaunch {
   hipStream_t stream;
   int last_stage;           // run stages 0..last_stage only (bnn_mi355x_debug_scan_clip_stage); kScanStages - 1 = all
   // The matrix-core forms (scan_mfma_kernels.h, scan_tail_mfma_kernels.h): bit s of matrix_stages sends stage s = 1..3 to
-  // k_clip_conv_mfma and stage s = 4, 5 to k_clip_tail_mfma.  0: none, and the fields below are not read.
+  // k_clip_conv_mfma and stage s = 4, 5 to k_clip_tail_mfma; bit 0 sends stage 0 to k_clip_conv0_mfma (scan_l0_mfma_kernels.h).
+  // 0: none, and the fields below are not read.
   unsigned matrix_stages;
   const uint8_t *conv_mfma; // device: the operand tables of layers 1-7 (kernels.h, conv_mfma_table)
   size_t conv_mfma_off[kScanStages];  // of layer s in them
   // ClipMfmaTables' (s = 1..3) and ClipTailTables' (s = 4, 5) offsets, from `tables` on (int32 units, 16-byte aligned)
   size_t mfma_maps[kScanStages], mfma_bands[kScanStages];
   long mfma_blocks[kScanStages];      // ClipMfmaTables::blocks, ClipTailTables::blocks
+  // stage 0 (bit 0): mfma_maps[0], mfma_bands[0], mfma_blocks[0] are ClipL0Tables', and
+  const uint8_t *l0_mfma;   // device: layer 0's MFMA table of the loaded parameters (packed_params.h, from l0_mfma_offset);
+                            // `planes` is then 4-byte aligned with ClipL0Tables::planes_top bytes reserved
 };
 // Enqueues one launch per stage; stage s leaves every map [h][w][dwords] at its offset (ClipMap::off) of buf(s & 1).  The
 // layer-5 maps in buf1 are the stage-5 output of ClipPlan::windows images in result order: run_cnv with first_stage = 6
 // goes on, once.  Stages 1-3 go to k_clip_quad or, where matrix_stages says so, to k_clip_conv_mfma, stages 4 and 5 to k_clip_vec
-// or to k_clip_tail_mfma: the maps are the same.
+// or to k_clip_tail_mfma, stage 0 to k_clip_conv0 or to k_clip_conv0_mfma: the maps are the same.
 hipError_t run_scan_clip(const ScanClipLaunch &a);
 
 // launch_scan_resize (scan_kernels.h) for `frames` pictures of one size at once: blockIdx.y is the frame, the frames

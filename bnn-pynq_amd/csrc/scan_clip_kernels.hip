@@ -9,6 +9,7 @@
 // bodies of scan_bodies.h, and the order of the resize passes is that header's too.  No LDS, no scratch.
 #include "scan_clip_kernels.h"
 #include "scan_bodies.h"
+#include "scan_l0_mfma_kernels.h"
 #include "scan_mfma_kernels.h"
 #include "scan_tail_mfma_kernels.h"
 
@@ -93,7 +94,12 @@ hipError_t run_scan_clip(const ScanClipLaunch &a) {
   auto grid = [&](int stage, int groups) { return dim3((unsigned)a.blocks[stage], (unsigned)groups); };
   auto descs = [&](int stage) { return reinterpret_cast<const ClipMapDesc *>(a.tables + a.desc[stage]); };
   auto bmap = [&](int stage) { return a.tables + a.block_map[stage]; };
-  if (a.last_stage >= 0) hipLaunchKernelGGL(k_clip_conv0, grid(0, 2), dim3(kBlock), 0, s, a.planes, A, a.rows[0], descs(0), bmap(0));
+  if (a.last_stage >= 0 && (a.matrix_stages & 1)) {  // stage 0 on the matrix cores (host code only, as below)
+    failed = launch_clip_conv0_mfma(ClipL0Launch{a.planes, A, a.l0_mfma, a.tables + a.mfma_maps[0],
+                                                 a.tables + a.mfma_bands[0], a.mfma_blocks[0], s});
+  } else if (a.last_stage >= 0) {
+    hipLaunchKernelGGL(k_clip_conv0, grid(0, 2), dim3(kBlock), 0, s, a.planes, A, a.rows[0], descs(0), bmap(0));
+  }
   // stages 1-5: the integer kernels, or the matrix-core form where the caller chose it (host code only: the kernels of this file are what they were)
   auto matrix = [&](int stage, const uint8_t *in, uint8_t *out) {
     if (stage > a.last_stage || !(a.matrix_stages >> stage & 1)) return false;

@@ -908,9 +908,23 @@ long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long 
  * scan_matrix_stages: bits 1-5 are set for the stages a clip call with that many windows would run on the matrix cores
  *       under the current form: 0b1110 under form 1, 0b111110 under form 2.  0 under form 0, on a library that is not
  *       cnvW1A1, under BNN_MI355X_CONV=valu (no operand tables: the integer kernels run under every form) and while no
- *       parameters are loaded. */
+ *       parameters are loaded.  Bit 0 is stage 0's and follows scan_stage0_form, below, alone. */
 int bnn_mi355x_scan_form(int form);
 int bnn_mi355x_scan_matrix_stages(long windows);
+
+/* The form of a clip call's stage 0 (layer 0 over all maps of the clip), an axis of its own beside scan_form: the integer
+ * pipe (k_clip_conv0: one lane per output pixel, 27 single-byte fetches, v_dot4) or the matrix cores (k_clip_conv0_mfma,
+ * csrc/scan_l0_mfma_kernels.hip: a block stages a band of a level's planes in LDS and quantises it once, then int8 MFMAs
+ * on the layer-0 operand table every load_parameters makes; DESIGN.md 9 "Clip scan").  Both write the same maps, byte for
+ * byte.  cnvW1A1 and clip calls only (scan_clip, detect_clip, their _frames and _device twins, debug_scan_clip_stage);
+ * the single-scene scan is not affected.
+ * scan_stage0_form: sets the form and returns the previous one.  0: the integer pipe; 1: the matrix cores.  Any other value
+ *       changes nothing and returns the current form.  Initially 0, or what BNN_MI355X_SCAN_L0 says (valu: 0, mfma: 1).
+ *       Nothing selects form 1 automatically.  Takes effect at the next clip call.
+ * Bit 0 of scan_matrix_stages is set exactly when a clip call would run stage 0 on the matrix cores: under form 1, on a
+ *       cnvW1A1 library, with parameters loaded and the layer-0 operand table there.  Under BNN_MI355X_L0=valu the table is
+ *       not made: the integer kernel runs under either form and the bit is clear. */
+int bnn_mi355x_scan_stage0_form(int form);
 
 /* Detect objects: the windows of a frame and their scores become a short list of boxes, each with a class and a score --
  * threshold, order, cap and greedy non-maximum suppression, on the device (csrc/detect_kernels.hip; the model:

@@ -52,7 +52,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_scan_clip_layout", "bnn_mi355x_debug_scan_clip_stage", "bnn_mi355x_detect_windows_host",
        "bnn_mi355x_detect_windows", "bnn_mi355x_detect_clip", "bnn_mi355x_unpack_frames_host", "bnn_mi355x_unpack_frames",
        "bnn_mi355x_scan_clip_frames", "bnn_mi355x_detect_clip_frames", "bnn_mi355x_scan_clip_device", "bnn_mi355x_detect_clip_device",
-       "bnn_mi355x_scan_form", "bnn_mi355x_scan_matrix_stages", "bnn_mi355x_scan_stage0_form"]
+       "bnn_mi355x_scan_form", "bnn_mi355x_scan_matrix_stages", "bnn_mi355x_scan_stage0_form", "bnn_mi355x_scan_clip_fine",
+       "bnn_mi355x_scan_fine_boxes", "bnn_mi355x_debug_scan_clip_fine_stage"]
 
 # bnn_mi355x_frames.format by name (include/bnn_mi355x.h, BNN_MI355X_FORMAT_*)
 PIXEL_FORMATS = {"rgb": 0, "l": 1, "bgr": 2, "nv12": 3, "i420": 4, "yuyv": 5}
@@ -356,6 +357,14 @@ def declare_extensions(L):
     if hasattr(L, "bnn_mi355x_scan_stage0_form"):  # (likewise)
         L.bnn_mi355x_scan_stage0_form.argtypes = [C.c_int]
         L.bnn_mi355x_scan_stage0_form.restype = C.c_int
+    if hasattr(L, "bnn_mi355x_scan_clip_fine"):  # (likewise)
+        L.bnn_mi355x_scan_clip_fine.argtypes = L.bnn_mi355x_scan_clip.argtypes
+        L.bnn_mi355x_scan_clip_fine.restype = ip
+        L.bnn_mi355x_scan_fine_boxes.argtypes = L.bnn_mi355x_scan_boxes.argtypes
+        L.bnn_mi355x_scan_fine_boxes.restype = C.c_long
+        L.bnn_mi355x_debug_scan_clip_fine_stage.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_int,
+                                                            C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_debug_scan_clip_fine_stage.restype = C.c_long
     if hasattr(L, "bnn_mi355x_detect_clip"):  # (likewise)
         do = C.POINTER(DetectOpts)
         L.bnn_mi355x_detect_windows_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, do, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -989,12 +989,47 @@ class CnvClassifier:
         b = np.stack([left, upper, left + window, upper + window], axis=-1).reshape(-1, 4).astype(np.int32)
         return (lw, lh), b
 
-    def scan_scene(self, img, sizes=(64, 96), details=False):
+    @staticmethod
+    def _stride(stride, what):
+        if stride not in (2, 4):
+            raise ValueError("%s: stride must be 4 or 2 level pixels" % what)
+        return stride
+
+    @staticmethod
+    def scan_fine_boxes(size, window):
+        """:meth:`scan_boxes` at stride 2: the level and the boxes of ONE window size in the fine scan's order -- phase (py,
+        then px), then raster (j, i); window (I, J) = (2i + px, 2j + py) of the level is the box (I w // 16, J w // 16, + w, + w)"""
+        (lw, lh), _ = CnvClassifier.scan_boxes(size, window)
+        nx2, ny2 = (lw - 32) // 2 + 1, (lh - 32) // 2 + 1
+        parts = []
+        for py in (0, 1):
+            for px in (0, 1):
+                left, upper = np.meshgrid(np.arange(px, nx2, 2) * window // 16, np.arange(py, ny2, 2) * window // 16)
+                parts.append(np.stack([left, upper, left + window, upper + window], axis=-1).reshape(-1, 4))
+        return (lw, lh), np.concatenate(parts).astype(np.int32)
+
+    def _scan_scene_fine_host(self, pil, sizes, details):
+        """the fine scan of one picture through the per-window pass: the records cut from the level pictures in the fine
+        scan's order -- the same answers by construction"""
+        ncls, boxes, res = len(self.classes), [], []
+        for s in sizes:
+            (lw, lh), b = self.scan_fine_boxes(pil.size, s)
+            planes = self._planes(pil if (lw, lh) == pil.size else pil.resize((lw, lh), Image.LANCZOS))
+            recs = [planes[:, 2 * j:2 * j + 32, 2 * i:2 * i + 32].reshape(3072) for py in (0, 1) for px in (0, 1)
+                    for j in range(py, (lh - 32) // 2 + 1, 2) for i in range(px, (lw - 32) // 2 + 1, 2)]
+            boxes.append(b)
+            res.append(np.asarray(self.classify_array(np.stack(recs), detail=details)).reshape((-1, ncls) if details else -1))
+        return np.concatenate(boxes), np.concatenate(res)
+
+    def scan_scene(self, img, sizes=(64, 96), details=False, stride=4):
         """a pyramid of dense scans: for each window size in ``sizes`` (size-major) the picture is resized like
         ``img.resize(level, Image.LANCZOS)`` and scanned (:meth:`scan`) -> (boxes int32 [n, 4] in the picture's coordinates,
         classes [n] or scores [n, len(classes)]).  On cnvW1A1 one upload and one stream (``bnn_mi355x_scan_scene``: RGB and L
-        pictures); otherwise PIL resizes on the host."""
+        pictures); otherwise PIL resizes on the host.  ``stride=2``: :meth:`scan_clip` at stride 2 on the one picture."""
         pil = self._as_pil(img)
+        if self._stride(stride, "scan_scene") == 2:
+            boxes, res = self.scan_clip([pil], sizes, details, stride=2)
+            return boxes, res[0]
         ncls = len(self.classes)
         levels = [self.scan_boxes(pil.size, s) for s in sizes]
         boxes = np.concatenate([b for _, b in levels]) if levels else np.zeros((0, 4), np.int32)
@@ -1161,7 +1196,7 @@ class CnvClassifier:
         self.usecPreprocess = pre_us / total if total else 0.0
         return out, np.concatenate(parts)
 
-    def scan_clip(self, frames, sizes=(64, 96), details=False, max_frames=None, pixel_format="rgb", video_range=False):
+    def scan_clip(self, frames, sizes=(64, 96), details=False, max_frames=None, pixel_format="rgb", video_range=False, stride=4):
         """:meth:`scan_scene` of every frame of a clip -- a sequence of PIL images or uint8 arrays of one size and mode, or
         one array ``[F, H, W(, 3)]`` -> (boxes int32 [n, 4], the same for every frame; classes [F, n] or scores
         [F, n, len(classes)]).  On cnvW1A1 the clip goes up once and every (frame, level) map runs through ONE launch per
@@ -1173,8 +1208,17 @@ class CnvClassifier:
         :meth:`unpack_frames`; ``video_range``: BT.601 video range instead of JFIF full range): they go up as they are and
         become RGB on the device (``bnn_mi355x_scan_clip_frames``).  A CUDA ``torch.uint8`` tensor of any format, ``"rgb"``
         and ``"l"`` included, is read where it lies, on the current stream (``bnn_mi355x_scan_clip_device``).  Libraries
-        without those entry points convert with :meth:`unpack_frames` and go on as above."""
+        without those entry points convert with :meth:`unpack_frames` and go on as above.
+
+        ``stride=2``: every window at level offsets (2I, 2J), four times the windows, from one pass over layers 0-3 and one
+        over layers 4-8 per pool phase (``bnn_mi355x_scan_clip_fine``).  The order is size, then phase (py, then px), then
+        raster, and the boxes are :meth:`scan_fine_boxes`'.  Camera formats and CUDA tensors are converted with
+        :meth:`unpack_frames` first; other networks, RGBA frames and libraries without the entry point classify the cut
+        records on the host."""
+        fine = self._stride(stride, "scan_clip") == 2
         cam = self._camera_clip(frames, pixel_format, video_range, "scan_clip")
+        if cam is not None and fine:
+            frames, cam = self.unpack_frames(frames, pixel_format, video_range), None
         if cam is not None:
             if max_frames is not None and max_frames < 1:
                 raise ValueError("scan_clip: max_frames must be 1 or more")
@@ -1186,23 +1230,29 @@ class CnvClassifier:
         if max_frames is not None and max_frames < 1:
             raise ValueError("scan_clip: max_frames must be 1 or more")
         lib = self._scan_lib()
-        if lib is None or clip is None or not hasattr(lib, "bnn_mi355x_scan_clip"):
-            res = [self.scan_scene(f, sizes, details) for f in frames]
+        if lib is None or clip is None or not hasattr(lib, "bnn_mi355x_scan_clip_fine" if fine else "bnn_mi355x_scan_clip"):
+            res = [self._scan_scene_fine_host(self._as_pil(f), sizes, details) if fine else self.scan_scene(f, sizes, details) for f in frames]
             return res[0][0], np.stack([r for _, r in res])
         n_frames, height, width = clip.shape[:3]
-        boxes = np.concatenate([self.scan_boxes((width, height), s)[1] for s in sizes]) if len(sizes) else np.zeros((0, 4), np.int32)
+        level_boxes = self.scan_fine_boxes if fine else self.scan_boxes
+        boxes = np.concatenate([level_boxes((width, height), s)[1] for s in sizes]) if len(sizes) else np.zeros((0, 4), np.int32)
         sz = np.asarray(sizes, dtype=np.int32)
         step = lib.bnn_mi355x_scan_clip_capacity(width, height, sz.ctypes.data, len(sz))
         if step < 1:
             raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+        # a quarter of scan_clip's capacity always fits one fine call: nx2 <= 2 nx, so a frame has at most four times the windows;
+        # stages 0-2 are at most as large as scan_clip's (nx2 + 13 <= 2 nx + 12 + 1) and the four phase maps of stages 3-5 together
+        # at most four of its maps; the clip's own bytes are the same.  (plan_fine checks the call itself.)
+        step = max(1, step // 4) if fine else step
         step = min(step, max_frames) if max_frames is not None else step
+        call = lib.bnn_mi355x_scan_clip_fine if fine else lib.bnn_mi355x_scan_clip
         out = np.zeros((len(boxes), 4), np.int32)
         parts, pre_us, pass_us = [], 0.0, 0.0
         for first in range(0, n_frames, step):
             part = clip[first:first + step]
             usec, pre = ctypes.c_float(0), ctypes.c_float(0)
-            ptr = lib.bnn_mi355x_scan_clip(part.ctypes.data, len(part), 0, width, height, 1 if clip.ndim == 3 else 3, 0, sz.ctypes.data, len(sz), ncls,
-                                           out.ctypes.data, ctypes.byref(usec), ctypes.byref(pre), 1 if details else 0)
+            ptr = call(part.ctypes.data, len(part), 0, width, height, 1 if clip.ndim == 3 else 3, 0, sz.ctypes.data, len(sz), ncls,
+                       out.ctypes.data, ctypes.byref(usec), ctypes.byref(pre), 1 if details else 0)
             if not ptr:
                 raise RuntimeError(lib.bnn_mi355x_last_error().decode())
             n = len(part) * len(boxes)
@@ -1214,11 +1264,11 @@ class CnvClassifier:
         self.usecPreprocess = pre_us / total if total else 0.0
         return out, np.concatenate(parts)
 
-    def locate_clip(self, frames, class_index, sizes=(64, 96), min_score=None):
+    def locate_clip(self, frames, class_index, sizes=(64, 96), min_score=None, stride=4):
         """:meth:`locate` with ``dense=True`` for every frame of a clip (:meth:`scan_clip`) -> a list, per frame, of the
         windows (left, upper, right, lower) whose class is ``class_index`` -- or, with ``min_score``, whose score for it
-        exceeds ``min_score``"""
-        boxes, res = self.scan_clip(frames, sizes, details=min_score is not None)
+        exceeds ``min_score``; ``stride=2``: the windows of the fine scan"""
+        boxes, res = self.scan_clip(frames, sizes, details=min_score is not None, stride=stride)
         hits = (res == class_index) if min_score is None else (res[:, :, class_index] > min_score)
         return [[tuple(int(v) for v in b) for b, h in zip(boxes, hit) if h] for hit in hits]
 
@@ -1276,7 +1326,7 @@ class CnvClassifier:
         return found[0] if single else found
 
     def detect_clip(self, frames, classes=None, sizes=(64, 96), min_score=None, by_score=False, iou=0.5, max_det=64, max_candidates=4096,
-                    max_frames=None, pixel_format="rgb", video_range=False):
+                    max_frames=None, pixel_format="rgb", video_range=False, stride=4):
         """where the objects are in every frame of a clip: :meth:`scan_clip` followed by :meth:`suppress` -> per frame a
         list of ``((left, upper, right, lower), class, score)``, best first.  On cnvW1A1 one call per piece of the clip
         (``bnn_mi355x_detect_clip``: RGB and L frames): the scan's launches, then the detection kernels on the scores where
@@ -1285,11 +1335,17 @@ class CnvClassifier:
         ``scan_clip(details=True)`` and :meth:`suppress`: the same answers by construction.
 
         ``pixel_format``, ``video_range`` and CUDA tensors: as :meth:`scan_clip` (``bnn_mi355x_detect_clip_frames``,
-        ``bnn_mi355x_detect_clip_device``)."""
+        ``bnn_mi355x_detect_clip_device``).  ``stride=2``: the fine scan's scores (``scan_clip(details=True, stride=2)``)
+        followed by :meth:`suppress`."""
         if max_frames is not None and max_frames < 1:
             raise ValueError("detect_clip: max_frames must be 1 or more")
         ncls = len(self.classes)
         o = self._detect_opts(classes, min_score, by_score, iou, max_det, max_candidates)
+        if self._stride(stride, "detect_clip") == 2:
+            boxes, scores = self.scan_clip(frames, sizes, details=True, max_frames=max_frames, pixel_format=pixel_format, video_range=video_range,
+                                           stride=2)
+            wanted = [k for k in range(64) if (o.class_mask >> k) & 1]
+            return self.suppress(boxes, scores, wanted, o.min_score, by_score, (o.iou_num, o.iou_den), max_det, max_candidates)
         cam = self._camera_clip(frames, pixel_format, video_range, "detect_clip")
         if cam is not None and self._camera_lib() is None:
             frames, cam = self.unpack_frames(frames, pixel_format, video_range), None

@@ -58,6 +58,8 @@
 #include "scan.h"
 #include "scan_clip_kernels.h"
 #include "scan_clip.h"
+#include "scan_fine.h"
+#include "scan_phase_kernels.h"
 #include "pixfmt_kernels.h"
 #include "pixfmt.h"
 #include "detect_kernels.h"
@@ -5390,6 +5392,14 @@ struct ClipJob {
   std::vector<int32_t> coef;
   std::vector<ResizeTables> tabs;
   size_t tmp_frame = 1;  // bytes of one frame's first resize pass, the largest of the levels
+  // A fine call (scan_fine.h): the plan the call reserves and enqueues with is FinePlan::front, whose maps `tables` and `l0`
+  // describe; `tail` describes FinePlan::back's, and behind the others lie the back maps' tables of stages 4 and 5 (back_base),
+  // stages 2 and 3's band tables (phase_base) and, in place of `mfma`, stage 1's (mfma_base)
+  const FinePlan *fine = nullptr;
+  ClipTables back;
+  ClipPhaseTables phase;
+  FineStage1Tables stage1;
+  size_t back_base = 0, phase_base = 0;
 };
 
 // Where a clip call's frames come from (include/bnn_mi355x.h, "Camera frames").  Not raw: the plan's bands and strides
@@ -5444,14 +5454,43 @@ unsigned clip_matrix_stages(long windows) {
   return l0 | (form == 2 ? 0b111110u : form == 1 || (form == -1 && windows >= scan_mfma_min()) ? 0b1110u : 0u);
 }
 
+// Empty when this library scans at stride 2, else the message for last_error: scan_refused's, or that the operand tables
+// stages 2 and 3 run on (k_clip_conv_phase) are not there
+std::string fine_refused(const char *what) {
+  const std::string no = scan_refused(what);
+  if (!no.empty()) return no;
+  const Runtime &r = rt();
+  if (r.d_blob && (!r.conv_mfma || !r.d_conv_mfma))
+    return std::string(what) + ": layers 2 and 3 of the fine scan run on the matrix cores' operand tables, which BNN_MI355X_CONV=valu leaves out";
+  return "";
+}
+
 // every workspace of a clip call (grow-only; the map buffers are the scan's and grow as they do, behind a device
 // synchronise), and the level's Lanczos tables, built once for all frames; raw_bytes: of uploaded raw frames (0: none)
-int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
+int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0, const FinePlan *fine = nullptr) {
   if (raw_bytes && rt().d_clip_raw.grow(raw_bytes)) return -1;
   Runtime &r = rt();
   clip_tables(p, job.tables);
   job.matrix = clip_matrix_stages(p.windows);
-  if (job.matrix & 0b1110u) {  // the band tables go behind the others (16-byte aligned): one upload for both
+  job.fine = fine;
+  // moves a table behind the others (16-byte aligned: one upload for all) and returns where it starts
+  const auto behind = [&job](std::vector<int32_t> &words) {
+    const size_t base = (job.tables.words.size() + 3) & ~(size_t)3;
+    job.tables.words.resize(base, 0);
+    job.tables.words.insert(job.tables.words.end(), words.begin(), words.end());
+    std::vector<int32_t>().swap(words);
+    return base;
+  };
+  if (fine) {
+    clip_tables(fine->back, job.back);
+    job.back_base = behind(job.back.words);
+    clip_phase_tables(*fine, job.phase);
+    job.phase_base = behind(job.phase.words);
+    if (job.matrix & 0b10u) {
+      fine_stage1_tables(*fine, job.stage1);
+      job.mfma_base = behind(job.stage1.words);
+    }
+  } else if (job.matrix & 0b1110u) {  // the band tables go behind the others (16-byte aligned): one upload for both
     clip_mfma_tables(p, job.mfma);
     job.mfma_base = (job.tables.words.size() + 3) & ~(size_t)3;
     job.tables.words.resize(job.mfma_base, 0);
@@ -5459,7 +5498,7 @@ int reserve_clip(const ClipPlan &p, ClipJob &job, size_t raw_bytes = 0) {
     std::vector<int32_t>().swap(job.mfma.words);
   }
   if (job.matrix & 0b110000u) {
-    clip_tail_tables(p, job.tail);
+    clip_tail_tables(fine ? fine->back : p, job.tail);
     job.tail_base = (job.tables.words.size() + 3) & ~(size_t)3;
     job.tables.words.resize(job.tail_base, 0);
     job.tables.words.insert(job.tables.words.end(), job.tail.words.begin(), job.tail.words.end());
@@ -5525,6 +5564,31 @@ PixLayout uploaded_layout(const PixLayout &l) {
   PixLayout p = l;
   p.frames_apart = l.frame_span;
   return p;
+}
+
+// The stages of a fine call (scan_fine.h), `a` filled for the front maps as for any clip: stages 0 and 1 over the front maps in
+// the call's forms, stages 2 and 3 on k_clip_conv_phase, stages 4 and 5 over the back maps in the call's forms
+hipError_t run_fine_stages(ScanClipLaunch a, const ClipJob &job, int last_stage) {
+  Runtime &r = rt();
+  const FinePlan &f = *job.fine;
+  uint8_t *A = static_cast<uint8_t *>(a.buf0), *B = static_cast<uint8_t *>(a.buf1);
+  a.last_stage = std::min(last_stage, 1);
+  if (job.matrix & 0b10u) {
+    a.mfma_maps[1] = job.mfma_base + job.stage1.maps; a.mfma_bands[1] = job.mfma_base + job.stage1.bands; a.mfma_blocks[1] = job.stage1.blocks;
+  }
+  hipError_t e = run_scan_clip(a);
+  for (int st = 2; st <= 3 && st <= last_stage && e == hipSuccess; st++) {
+    const uint8_t *tab = r.d_conv_mfma + (st == 2 ? kConvMfmaL2Off : kConvMfmaL3Off);
+    e = launch_clip_conv_phase(st, ClipPhaseLaunch{st == 2 ? B : A, st == 2 ? A : B, tab, a.tables + job.phase_base + job.phase.maps[st - 2],
+                                                   a.tables + job.phase_base + job.phase.bands[st - 2], job.phase.blocks[st - 2], a.stream});
+  }
+  if (e != hipSuccess || last_stage < 4) return e;
+  for (int l = 4; l <= 5; l++) {
+    a.desc[l] = job.back_base + job.back.desc[l]; a.block_map[l] = job.back_base + job.back.block_map[l]; a.blocks[l] = f.back.blocks[l];
+  }
+  a.first_stage = 4;
+  a.last_stage = std::min(last_stage, kScanStages - 1);
+  return run_scan_clip(a);
 }
 
 // Enqueues on the source's stream: the frames' way to packed RGB or L frames in HBM, the upload of the tables, the resizes of
@@ -5601,7 +5665,7 @@ int enqueue_clip(const char *what, const ClipPlan &p, const ClipJob &job, const 
   }
   a.stream = s;
   a.last_stage = last_stage < kScanStages - 1 ? last_stage : kScanStages - 1;
-  hipError_t e = run_scan_clip(a);
+  hipError_t e = job.fine ? run_fine_stages(a, job, last_stage) : run_scan_clip(a);
   if (e == hipSuccess && last_stage >= kScanStages) e = run_scan_tail((int)p.windows, ncls, d_classes, d_scores, s, last_stage);
   if (e != hipSuccess) return launch_failed(what, e);
   return 0;
@@ -5668,17 +5732,23 @@ struct DrainCaller {
 
 // bnn_mi355x_scan_clip, _scan_clip_frames and _scan_clip_device.  A device call settles the workspaces' hand-over before
 // it enqueues (enqueue_clip) and has waited for its stream when it returns: it leaves nothing to hand over.
+// bnn_mi355x_scan_clip_fine (`fine`; host RGB or L frames): the same call on the fine plan's maps (scan_fine.h).
 int *scan_clip_call(const ClipRequest &q, const int *sizes, int n_sizes, int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess,
-                    int enable_detail) {
+                    int enable_detail, bool fine = false) {
   Runtime &r = rt();
   if (usecPerImage) *usecPerImage = 0.f;
   if (usecPreprocess) *usecPreprocess = 0.f;
-  const std::string no = scan_refused(q.what);
+  const std::string no = fine ? fine_refused(q.what) : scan_refused(q.what);
   if (!no.empty()) { fail(no); return nullptr; }
-  ClipPlan plan;
+  ClipPlan coarse;
+  FinePlan fplan;
   ClipSource src;
-  const std::string bad = plan_request(q, sizes, n_sizes, boxes_out, plan, src);
+  const std::string bad = fine ? plan_fine(q.what, q.pixels, q.n_frames, q.frame_stride, q.width, q.height, q.bands, q.row_stride, sizes, n_sizes,
+                                          boxes_out, fplan)
+                               : plan_request(q, sizes, n_sizes, boxes_out, coarse, src);
   if (!bad.empty()) { fail(bad); return nullptr; }
+  if (fine) src.pixels = static_cast<const uint8_t *>(q.pixels);
+  const ClipPlan &plan = fine ? fplan.front : coarse;
   if (bad_number_class(number_class)) return nullptr;
   if (!ready()) return nullptr;
   const std::string captured = capture_refused(q);
@@ -5692,7 +5762,7 @@ int *scan_clip_call(const ClipRequest &q, const int *sizes, int n_sizes, int num
     std::vector<int16_t> scores;
     ClipJob job;  // (outlives its asynchronous uploads: declared before `drain`)
     // every workspace first (they synchronise when they grow), so that nothing is allocated between the kernels
-    if (reserve_results(n) || reserve_clip(plan, job, src.raw_bytes()) || ensure_events(r.scan_ev, 3)) return -1;
+    if (reserve_results(n) || reserve_clip(plan, job, src.raw_bytes(), fine ? &fplan : nullptr) || ensure_events(r.scan_ev, 3)) return -1;
     if (enable_detail) scores.resize(n * 64);
     DrainOnFailure drain;
     DrainCaller caller{src};
@@ -5711,7 +5781,8 @@ int *scan_clip_call(const ClipRequest &q, const int *sizes, int n_sizes, int num
   if (run()) { delete[] result; return nullptr; }
   // (the boxes are the same for every frame: one frame's, exactly what scan_scene writes)
   for (const ScanLevel &lv : plan.scene.levels)
-    scan_boxes(plan.width, plan.height, lv.size, boxes_out + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
+    if (fine) scan_fine_boxes(plan.width, plan.height, lv.size, boxes_out + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
+    else scan_boxes(plan.width, plan.height, lv.size, boxes_out + 4 * (size_t)lv.first, (long)lv.plan.nx * lv.plan.ny);
   return result;
 }
 
@@ -5835,6 +5906,61 @@ long bnn_mi355x_debug_scan_clip_stage(const uint8_t *pixels, int n_frames, long 
   src.pixels = pixels; src.stream = r.stream;
   if (enqueue_clip("debug_scan_clip_stage", plan, job, src, 1, nullptr, nullptr, nullptr, stage)) return -1;
   HIP_OK(hipMemcpyAsync(out, (stage & 1) ? r.d_scan_buf1 : r.d_scan_buf0, bytes, hipMemcpyDeviceToHost, r.stream));
+  HIP_OK(hipStreamSynchronize(r.stream));
+  drain.ok();
+  return (long)bytes;
+}
+
+int *bnn_mi355x_scan_clip_fine(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                               const int *sizes, int n_sizes, int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess,
+                               int enable_detail) {
+  const ClipRequest q{"scan_clip_fine", pixels, false, nullptr, n_frames, frame_stride, width, height, bands, row_stride, false, nullptr};
+  return scan_clip_call(q, sizes, n_sizes, number_class, boxes_out, usecPerImage, usecPreprocess, enable_detail, true);
+}
+
+long bnn_mi355x_scan_fine_boxes(int width, int height, int size, int *boxes, long cap, int *level_w, int *level_h) {
+  const std::string no = scan_refused("scan_fine_boxes");
+  if (!no.empty()) return fail(no);
+  // (plan_scene with a stand-in for the pointers it checks: the same refusals, in the same words, as the scan's)
+  ScenePlan plan;
+  const std::string bad = plan_scene("scan_fine_boxes", &plan, width, height, 3, 0, &size, 1, &plan, plan);
+  if (!bad.empty()) return fail(bad);
+  if (level_w) *level_w = plan.levels[0].level_w;
+  if (level_h) *level_h = plan.levels[0].level_h;
+  return scan_fine_boxes(width, height, size, boxes, cap < 0 ? 0 : cap);
+}
+
+long bnn_mi355x_debug_scan_clip_fine_stage(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                                           const int *sizes, int n_sizes, int stage, int phase, void *out, size_t cap) {
+  Runtime &r = rt();
+  const std::string no = fine_refused("debug_scan_clip_fine_stage");
+  if (!no.empty()) return fail(no);
+  if (!out || stage < 0 || stage >= kScanStages || (stage >= 3 && (phase < 0 || phase >= kFinePhases))) return fail("debug_scan_clip_fine_stage: bad arguments");
+  FinePlan plan;
+  const std::string bad = plan_fine("debug_scan_clip_fine_stage", pixels, n_frames, frame_stride, width, height, bands, row_stride, sizes, n_sizes, out, plan);
+  if (!bad.empty()) return fail(bad);
+  // the pieces of the stage's buffer region that go out: all of it, or the maps of one phase
+  std::vector<std::pair<size_t, size_t>> pieces;  // (offset, bytes)
+  if (stage < 3) pieces.push_back({0, plan.front.stage_bytes[stage]});
+  else
+    for (size_t m = 0; m < plan.back.maps.size(); m++)
+      if (plan.phase[m] == phase) pieces.push_back({plan.back.maps[m].off[stage], scan_stage_bytes(plan.back.scene.levels[(size_t)plan.back.maps[m].level].plan, stage)});
+  size_t bytes = 0;
+  for (const auto &pc : pieces) bytes += pc.second;
+  if (cap < bytes) return fail("debug_scan_clip_fine_stage: the stage's maps take " + std::to_string(bytes) + " bytes");
+  if (!ready() || bind_device()) return -1;
+  ClipJob job;
+  if (reserve_clip(plan.front, job, 0, &plan)) return -1;
+  DrainOnFailure drain;
+  ClipSource src;
+  src.pixels = pixels; src.stream = r.stream;
+  if (enqueue_clip("debug_scan_clip_fine_stage", plan.front, job, src, 1, nullptr, nullptr, nullptr, stage)) return -1;
+  const uint8_t *buf = (stage & 1) ? r.d_scan_buf1.get() : r.d_scan_buf0.get();
+  size_t at = 0;
+  for (const auto &pc : pieces) {
+    HIP_OK(hipMemcpyAsync(static_cast<uint8_t *>(out) + at, buf + pc.first, pc.second, hipMemcpyDeviceToHost, r.stream));
+    at += pc.second;
+  }
   HIP_OK(hipStreamSynchronize(r.stream));
   drain.ok();
   return (long)bytes;

@@ -79,6 +79,11 @@ struct ClipTables {
   size_t desc[kScanStages] = {}, block_map[kScanStages] = {};
 };
 void clip_tables(const ClipPlan &plan, ClipTables &t);
+// Stages without maps.  A plan may leave a run of stages empty -- every level's ScanPlan 0 x 0 there, so that the stage has no
+// items, no blocks and no bytes (the fine scan's two plans, scan_fine.h: one holds stages 0-2, the other stages 3-5).
+// clip_tables writes descriptors with no blocks for such a stage; clip_l0_tables reads stage 0 alone and clip_tail_tables
+// stages 3-5 alone, and may be given a plan whose other stages are empty.  clip_mfma_tables needs stages 0-3.  A launch of a
+// stage without blocks is refused (run_scan_clip): whoever builds such a plan runs its own stages only.
 
 // ---- the matrix-core form of stages 1-3 (k_clip_conv_mfma, scan_mfma_kernels.hip; DESIGN.md 9 "Clip scan") ------------
 // A block owns a BAND of one map: kClipMfmaRowPairs output row pairs x kClipMfmaChunk conv-output columns (less at the

@@ -19,6 +19,7 @@ struct ScanClipLaunch {
   long blocks[kScanStages]; // ClipPlan::blocks
   hipStream_t stream;
   int last_stage;           // run stages 0..last_stage only (bnn_mi355x_debug_scan_clip_stage); kScanStages - 1 = all
+  int first_stage;          // ... and none before it (0 = from the start; the fine scan runs stages 2 and 3 itself, scan_fine.h)
   // The matrix-core forms (scan_mfma_kernels.h, scan_tail_mfma_kernels.h): bit s of matrix_stages sends stage s = 1..3 to
   // k_clip_conv_mfma and stage s = 4, 5 to k_clip_tail_mfma; bit 0 sends stage 0 to k_clip_conv0_mfma (scan_l0_mfma_kernels.h).
   // 0: none, and the fields below are not read.

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void k_clip_resize_v(const uint8_t *__restr
 }  // namespace
 
 hipError_t run_scan_clip(const ScanClipLaunch &a) {
-  for (int l = 0; l <= a.last_stage && l < kScanStages; l++)
+  for (int l = a.first_stage < 0 ? 0 : a.first_stage; l <= a.last_stage && l < kScanStages; l++)
     if (a.blocks[l] < 1 || a.blocks[l] > INT32_MAX) return hipErrorInvalidValue;
   uint8_t *A = static_cast<uint8_t *>(a.buf0), *B = static_cast<uint8_t *>(a.buf1);
   hipStream_t s = a.stream;
@@ -94,15 +94,16 @@ hipError_t run_scan_clip(const ScanClipLaunch &a) {
   auto grid = [&](int stage, int groups) { return dim3((unsigned)a.blocks[stage], (unsigned)groups); };
   auto descs = [&](int stage) { return reinterpret_cast<const ClipMapDesc *>(a.tables + a.desc[stage]); };
   auto bmap = [&](int stage) { return a.tables + a.block_map[stage]; };
-  if (a.last_stage >= 0 && (a.matrix_stages & 1)) {  // stage 0 on the matrix cores (host code only, as below)
+  auto runs = [&](int stage) { return a.first_stage <= stage && stage <= a.last_stage; };
+  if (runs(0) && (a.matrix_stages & 1)) {  // stage 0 on the matrix cores (host code only, as below)
     failed = launch_clip_conv0_mfma(ClipL0Launch{a.planes, A, a.l0_mfma, a.tables + a.mfma_maps[0],
                                                  a.tables + a.mfma_bands[0], a.mfma_blocks[0], s});
-  } else if (a.last_stage >= 0) {
+  } else if (runs(0)) {
     hipLaunchKernelGGL(k_clip_conv0, grid(0, 2), dim3(kBlock), 0, s, a.planes, A, a.rows[0], descs(0), bmap(0));
   }
   // stages 1-5: the integer kernels, or the matrix-core form where the caller chose it (host code only: the kernels of this file are what they were)
   auto matrix = [&](int stage, const uint8_t *in, uint8_t *out) {
-    if (stage > a.last_stage || !(a.matrix_stages >> stage & 1)) return false;
+    if (!runs(stage) || !(a.matrix_stages >> stage & 1)) return false;
     const uint8_t *tab = a.conv_mfma + a.conv_mfma_off[stage];
     const int32_t *maps = a.tables + a.mfma_maps[stage], *bands = a.tables + a.mfma_bands[stage];
     const hipError_t e = stage <= 3 ? launch_clip_conv_mfma(stage, ClipMfmaLaunch{in, out, tab, maps, bands, a.mfma_blocks[stage], s})
@@ -110,11 +111,11 @@ hipError_t run_scan_clip(const ScanClipLaunch &a) {
     if (e != hipSuccess && failed == hipSuccess) failed = e;
     return true;
   };
-  if (a.last_stage >= 1 && !matrix(1, A, B)) hipLaunchKernelGGL((k_clip_quad<1, true>), grid(1, 2), dim3(kBlock), 0, s, A, B, a.rows[1], descs(1), bmap(1), 2);
-  if (a.last_stage >= 2 && !matrix(2, B, A)) hipLaunchKernelGGL((k_clip_quad<1, false>), grid(2, 4), dim3(kBlock), 0, s, B, A, a.rows[2], descs(2), bmap(2), 4);
-  if (a.last_stage >= 3 && !matrix(3, A, B)) hipLaunchKernelGGL((k_clip_quad<2, true>), grid(3, 4), dim3(kBlock), 0, s, A, B, a.rows[3], descs(3), bmap(3), 4);
-  if (a.last_stage >= 4 && !matrix(4, B, A)) hipLaunchKernelGGL((k_clip_vec<2>), grid(4, 8), dim3(kBlock), 0, s, B, A, a.rows[4], descs(4), bmap(4), 8);
-  if (a.last_stage >= 5 && !matrix(5, A, B)) hipLaunchKernelGGL((k_clip_vec<4>), grid(5, 8), dim3(kBlock), 0, s, A, B, a.rows[5], descs(5), bmap(5), 8);
+  if (runs(1) && !matrix(1, A, B)) hipLaunchKernelGGL((k_clip_quad<1, true>), grid(1, 2), dim3(kBlock), 0, s, A, B, a.rows[1], descs(1), bmap(1), 2);
+  if (runs(2) && !matrix(2, B, A)) hipLaunchKernelGGL((k_clip_quad<1, false>), grid(2, 4), dim3(kBlock), 0, s, B, A, a.rows[2], descs(2), bmap(2), 4);
+  if (runs(3) && !matrix(3, A, B)) hipLaunchKernelGGL((k_clip_quad<2, true>), grid(3, 4), dim3(kBlock), 0, s, A, B, a.rows[3], descs(3), bmap(3), 4);
+  if (runs(4) && !matrix(4, B, A)) hipLaunchKernelGGL((k_clip_vec<2>), grid(4, 8), dim3(kBlock), 0, s, B, A, a.rows[4], descs(4), bmap(4), 8);
+  if (runs(5) && !matrix(5, A, B)) hipLaunchKernelGGL((k_clip_vec<4>), grid(5, 8), dim3(kBlock), 0, s, A, B, a.rows[5], descs(5), bmap(5), 8);
   return failed != hipSuccess ? failed : hipGetLastError();
 }
 

@@ -39,3 +39,10 @@ for f, found in enumerate(hits):
     print("frame %d: class %d (%s) in %d windows%s" % (f, STOP, classifier.class_name(STOP), len(found), ": " + str(found[:4]) + (" ..." if len(found) > 4 else "") if found else ""))
 # one frame by itself gives the same answer (locate with dense=True is scan_scene: the clip's frame, bit for bit)
 assert hits[-1] == classifier.locate(clip[-1], STOP, sizes=SIZES, dense=True)
+
+# finer localisation: every window at HALF the stride, four times the windows, from one pass over layers 0-3 (stride=2).  The
+# stride-4 hits are among them: they are the windows of pool phase (0, 0)
+fine = classifier.locate_clip(clip, STOP, sizes=SIZES, stride=2)
+for f, found in enumerate(fine):
+    assert set(hits[f]) <= set(found)
+    print("frame %d at stride 2: %d windows" % (f, len(found)))

@@ -926,6 +926,36 @@ int bnn_mi355x_scan_matrix_stages(long windows);
  *       not made: the integer kernel runs under either form and the bit is clear. */
 int bnn_mi355x_scan_stage0_form(int form);
 
+/* Scan a clip at stride 2: every 32 x 32 window of every level at level offsets (2I, 2J), four times the windows of
+ * scan_clip, from ONE pass over layers 0-3 (csrc/scan_phase_kernels.hip; the model: csrc/scan_fine.h, DESIGN.md 9 "Fine
+ * scan").  The first pool lies on even coordinates and is shared by all such windows; the second pool pairs layer-3 columns
+ * (2X + px, 2X + px + 1) with px = I & 1 and rows alike with py = J & 1, so layer 3 leaves four pooled PHASE maps (px, py)
+ * from one evaluation of its convolution and layers 4-8 run once on the windows of all phases.  Phase (0, 0) is scan_clip's
+ * scan.  cnvW1A1 libraries only, refused elsewhere in the scan's two messages.
+ *   windows:   along x a level has nx2 = (level_w - 32) / 2 + 1 windows, of which phase px holds ceil((nx2 - px) / 2); y alike.
+ *              A phase without windows (a 32-pixel side) is skipped.
+ *   order:     frame, then size, then phase (py, then px), then raster (j, i): window (I, J) = (2i + px, 2j + py), whose
+ *              box for size s is (I s / 16, J s / 16, + s, + s), integer division (for even I, J scan_boxes' i s / 8).
+ *   answers:   the windows of phase (px, py) equal, bit for bit on all 64 raw scores, scan_clip at size 32 on the level
+ *              picture cropped by (2 px, 2 py).
+ * scan_clip_fine: arguments, result, ownership and timings as scan_clip; boxes_out receives ONE frame's boxes in the order
+ *       above (size it with scan_fine_boxes).  Stages 0, 1, 4 and 5 run in the form scan_form, scan_stage0_form and the
+ *       automatic rule select for the call's window count; stages 2 and 3 always run k_clip_conv_phase, which needs the
+ *       operand tables (refused under BNN_MI355X_CONV=valu).
+ * scan_fine_boxes: host only, as scan_boxes: the level and the boxes of ONE window size in the order above.  It states the
+ *       geometry alone and answers whatever BNN_MI355X_CONV says; the two calls that run kernels refuse without the tables.
+ * debug_scan_clip_fine_stage: test hook, the twin of debug_scan_clip_stage.  Stages 0-2: the stage's buffer region, one map
+ *       per (frame, size) packed in that order ([h][w][dwords]: 2 nx2 + 28, nx2 + 13, nx2 + 11 wide, heights alike); `phase`
+ *       is ignored.  Stages 3-5: the maps of `phase` = 2 py + px alone, packed in (frame, size) order, nxp + 4, nxp + 2 and
+ *       nxp wide; sizes whose phase is empty add nothing.  Returns the bytes, or -1 (cap too small included).
+ * Limits: scan_clip's, with the windows and the map buffers counted over all phases. */
+int *bnn_mi355x_scan_clip_fine(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                               const int *sizes, int n_sizes, int number_class, int *boxes_out, float *usecPerImage, float *usecPreprocess,
+                               int enable_detail);
+long bnn_mi355x_scan_fine_boxes(int width, int height, int size, int *boxes, long cap, int *level_w, int *level_h);
+long bnn_mi355x_debug_scan_clip_fine_stage(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                                           const int *sizes, int n_sizes, int stage, int phase, void *out, size_t cap);
+
 /* Detect objects: the windows of a frame and their scores become a short list of boxes, each with a class and a score --
  * threshold, order, cap and greedy non-maximum suppression, on the device (csrc/detect_kernels.hip; the model:
  * csrc/detect.h, DESIGN.md 9 "Detections").  The model is this project's own (the reference notebook draws every window

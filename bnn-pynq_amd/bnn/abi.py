@@ -53,7 +53,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_detect_windows", "bnn_mi355x_detect_clip", "bnn_mi355x_unpack_frames_host", "bnn_mi355x_unpack_frames",
        "bnn_mi355x_scan_clip_frames", "bnn_mi355x_detect_clip_frames", "bnn_mi355x_scan_clip_device", "bnn_mi355x_detect_clip_device",
        "bnn_mi355x_scan_form", "bnn_mi355x_scan_matrix_stages", "bnn_mi355x_scan_stage0_form", "bnn_mi355x_scan_clip_fine",
-       "bnn_mi355x_scan_fine_boxes", "bnn_mi355x_debug_scan_clip_fine_stage"]
+       "bnn_mi355x_scan_fine_boxes", "bnn_mi355x_debug_scan_clip_fine_stage", "bnn_mi355x_find_glyphs_clip",
+       "bnn_mi355x_clip_to_mnist", "bnn_mi355x_read_clip"]
 
 # bnn_mi355x_frames.format by name (include/bnn_mi355x.h, BNN_MI355X_FORMAT_*)
 PIXEL_FORMATS = {"rgb": 0, "l": 1, "bgr": 2, "nv12": 3, "i420": 4, "yuyv": 5}
@@ -326,6 +327,13 @@ def declare_extensions(L):
         L.bnn_mi355x_read_page.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, op, fo, po, C.c_int, C.c_int, ip, C.c_void_p,
                                            C.c_void_p, C.c_void_p, fp, fp, C.c_void_p]
         L.bnn_mi355x_read_page.restype = ip
+    if hasattr(L, "bnn_mi355x_read_clip"):  # (likewise)
+        op, fo, po, vp = C.POINTER(GlyphOpts), C.POINTER(FindOpts), C.POINTER(PageOpts), C.c_void_p
+        clip = [vp, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, op, fo]
+        L.bnn_mi355x_find_glyphs_clip.argtypes = clip + [vp, vp, vp, C.c_int, vp, vp]
+        L.bnn_mi355x_clip_to_mnist.argtypes = clip + [po, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        L.bnn_mi355x_read_clip.argtypes = clip + [po, C.c_int, C.c_int, vp, vp, vp, vp, vp, fp, fp, vp]
+        L.bnn_mi355x_read_clip.restype = ip
     if hasattr(L, "bnn_mi355x_scan_scene"):  # (likewise)
         L.bnn_mi355x_scan_grid.argtypes = [C.c_int, C.c_int, ip, ip]
         L.bnn_mi355x_scan_boxes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, ip, ip]

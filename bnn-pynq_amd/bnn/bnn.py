@@ -1798,6 +1798,9 @@ class LfcClassifier:
             classes, _ = self.read_glyphs(img, **kwargs)
             return "".join(self.class_name(c) if c >= 0 else "?" for c in classes)
         classes, _, lines, gaps = self.read_page(img, **kwargs)
+        return self._page_text(classes, lines, gaps)
+
+    def _page_text(self, classes, lines, gaps):
         text = []
         for i, c in enumerate(classes):
             if i and lines[i] != lines[i - 1]:
@@ -1806,6 +1809,98 @@ class LfcClassifier:
                 text.append(" ")
             text.append(self.class_name(c) if c >= 0 else "?")
         return "".join(text)
+
+    # -- extension: read a clip -- the glyphs of all frames in one set of launches (csrc/clip_glyphs.h) -------------------
+    MAX_CLIP_PIXELS = 1 << 24  # BNN_MI355X_FIND_MAX_PIXELS: a longer clip is cut into several calls
+
+    def _glyph_clip(self, frames):
+        """uint8 array [F, H, W] or [F, H, W, bands] of a sequence of PIL images or arrays of one size and mode, or of one
+        array, as :meth:`CnvClassifier.scan_clip` takes a clip; other PIL modes are made "L" as :meth:`_picture` does"""
+        if isinstance(frames, np.ndarray) and frames.ndim in (3, 4) and frames.dtype == np.uint8 and (frames.ndim == 3 or frames.shape[3] in (3, 4)):
+            return np.ascontiguousarray(frames)
+        frames = list(frames)
+        if not frames:
+            raise ValueError("need one frame or more")
+        if len(set((f.shape, "array") if isinstance(f, np.ndarray) else (f.size, f.mode) for f in frames)) != 1:
+            raise ValueError("the frames of a clip have one size and one mode")
+        return np.stack([self._picture(f)[0] for f in frames])
+
+    def _clip_call(self, symbol, frames, mask, lines, word_gap, reach, min_pixels, ink_level, order, max_glyphs, opts, run):
+        """``run(lib, piece, n_frames, cap, clip_args) -> list with one entry per frame``, once per piece of at most
+        MAX_CLIP_PIXELS pixels; the pieces' lists concatenated"""
+        o = self._glyph_opts(**opts)
+        f, cap = self._find_opts(reach, min_pixels, ink_level, order, max_glyphs)
+        g = abi.PageOpts(1 if mask else 0, 1 if lines else 0, int(word_gap))
+        a = self._glyph_clip(frames)
+        lib = self._find_entry(symbol)
+        height, width = a.shape[1:3]
+        bands = 1 if a.ndim == 3 else a.shape[3]
+        cap = max(1, min(cap, ((width + 1) // 2) * ((height + 1) // 2)))  # never more glyphs a frame than 2 x 2 cells
+        step = max(1, self.MAX_CLIP_PIXELS // (width * height))
+        out = []
+        for first in range(0, len(a), step):
+            piece = a[first:first + step]
+            out += run(lib, piece, len(piece), cap, (piece.ctypes.data, len(piece), 0, width, height, bands, 0, ctypes.byref(o), ctypes.byref(f)), g)
+        return out
+
+    def find_glyphs_clip(self, frames, reach=(1, 1), min_pixels=1, ink_level=255, order="left", max_glyphs=4096, details=False, **opts):
+        """:meth:`find_glyphs` for every frame of a clip in one call (``bnn_mi355x_find_glyphs_clip``): a list with, per
+        frame, what :meth:`find_glyphs` returns for that frame alone."""
+        def run(lib, piece, n, cap, clip, g):
+            boxes, counts = np.zeros((n, cap, 4), np.int32), np.zeros((n, cap), np.int32)
+            labels = np.empty(piece.shape[:3], np.int32) if details else None
+            found, kept = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            if lib.bnn_mi355x_find_glyphs_clip(*clip, boxes.ctypes.data, counts.ctypes.data, None if labels is None else labels.ctypes.data, cap,
+                                               found.ctypes.data, kept.ctypes.data) != 0:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            return [(boxes[i, :kept[i]], counts[i, :kept[i]], int(found[i]), labels[i]) if details else boxes[i, :kept[i]] for i in range(n)]
+        return self._clip_call("bnn_mi355x_find_glyphs_clip", frames, True, False, 0, reach, min_pixels, ink_level, order, max_glyphs, opts, run)
+
+    def clip_to_mnist(self, frames, mask=True, lines=True, word_gap=0, reach=(1, 1), min_pixels=1, ink_level=255, order="left", max_glyphs=4096,
+                      **opts):
+        """the records form of :meth:`read_clip` (``bnn_mi355x_clip_to_mnist``): per frame (records, boxes, status, lines,
+        gaps), as :meth:`page_to_mnist` returns them for that frame alone."""
+        def run(lib, piece, n, cap, clip, g):
+            recs, boxes = np.zeros((n, cap, 784), np.uint8), np.zeros((n, cap, 4), np.int32)
+            status, line, gap = (np.zeros((n, cap), np.int32) for _ in range(3))
+            found, kept = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            if lib.bnn_mi355x_clip_to_mnist(*clip, ctypes.byref(g), cap, found.ctypes.data, kept.ctypes.data, boxes.ctypes.data, recs.ctypes.data,
+                                            status.ctypes.data, line.ctypes.data, gap.ctypes.data) != 0:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            return [tuple(v[i, :kept[i]] for v in (recs, boxes, status, line, gap)) for i in range(n)]
+        return self._clip_call("bnn_mi355x_clip_to_mnist", frames, mask, lines, word_gap, reach, min_pixels, ink_level, order, max_glyphs, opts, run)
+
+    def read_clip(self, frames, mask=True, lines=True, word_gap=0, reach=(1, 1), min_pixels=1, ink_level=255, order="left", max_glyphs=4096,
+                  **opts):
+        """:meth:`read_page` for every frame of a clip (a sequence of PIL images or arrays of one size and mode, or one array
+        [F, H, W] or [F, H, W, 3]) in one call: a list of (classes, boxes, lines, gaps), one per frame, each what
+        :meth:`read_page` returns for that frame alone (``bnn_mi355x_read_clip``).  The clip goes to the GPU once as one tall
+        plane, every frame is enhanced by its own mean, all frames' glyphs are labelled in one set of launches and
+        classified in one pass.  A clip of more than 2^24 pixels is cut into several calls.  ``self.glyph_status`` and
+        ``self.glyphs_found`` hold a list with one entry per frame."""
+        self.glyph_status, self.glyphs_found = [], []
+
+        def run(lib, piece, n, cap, clip, g):
+            boxes = np.zeros((n, cap, 4), np.int32)
+            status, line, gap = (np.zeros((n, cap), np.int32) for _ in range(3))
+            found, kept = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            usec, pre = ctypes.c_float(0), ctypes.c_float(0)
+            ptr = lib.bnn_mi355x_read_clip(*clip, ctypes.byref(g), len(self.classes), cap, found.ctypes.data, kept.ctypes.data, boxes.ctypes.data,
+                                           line.ctypes.data, gap.ctypes.data, ctypes.byref(usec), ctypes.byref(pre), status.ctypes.data)
+            if not ptr:
+                raise RuntimeError(lib.bnn_mi355x_last_error().decode())
+            classes = np.ctypeslib.as_array(ptr, shape=(n, cap)).astype(np.int32, copy=True)
+            lib.free_results(ptr)
+            self.usecPerImage = self.bnn.usecPerImage = usec.value
+            self.usecPreprocess = pre.value
+            self.glyph_status += [status[i, :kept[i]] for i in range(n)]
+            self.glyphs_found += [int(v) for v in found]
+            return [tuple(v[i, :kept[i]] for v in (classes, boxes, line, gap)) for i in range(n)]
+        return self._clip_call("bnn_mi355x_read_clip", frames, mask, lines, word_gap, reach, min_pixels, ink_level, order, max_glyphs, opts, run)
+
+    def read_clip_text(self, frames, **kwargs):
+        """what every frame of the clip says: per frame the string :meth:`read_text` makes of :meth:`read_page`'s answer"""
+        return [self._page_text(classes, lines, gaps) for classes, _, lines, gaps in self.read_clip(frames, **kwargs)]
 
     def classify_image(self, img, **opts):
         """the class of the one glyph in ``img`` (a PIL image or a uint8 array): the notebooks, from the camera frame to

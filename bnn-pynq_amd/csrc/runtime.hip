@@ -69,6 +69,8 @@
 #include "glyphs.h"
 #include "page.h"
 #include "page_kernels.h"
+#include "clip_glyphs.h"
+#include "clip_glyph_kernels.h"
 #include "packed_params.h"
 #include "pack_inputs.h"
 #include "topology.h"
@@ -6341,27 +6343,28 @@ int reserve_components(int width, int height, bool labels) {
   return ensure_events(r.cc_ev, 2);
 }
 
-// Behind enqueue_glyph_plane, on r.stream: the six labelling launches, the call's round trip for the component list
-// (the counters and the first kFirstReadBack components in one copy; a second copy only for more), select_components,
-// and -- when `labels` is not null -- the index map's upload, k_cc_relabel and the map's copy into `labels`, which the
-// caller waits for.  `chosen`: the returned components in order; `index` outlives its upload.
-int enqueue_components(const char *what, const GlyphPicture &p, const FindOpts &f, int cap, int32_t *labels, std::vector<Component> &chosen,
-                       long &total, std::vector<int32_t> &index) {
+// the plane of p (one picture, or a clip's tall plane) with this runtime's ink words and labels
+ComponentPlane component_plane(const GlyphPicture &p) {
   Runtime &r = rt();
-  const int comps = (int)max_components(p.width, p.height);
   ComponentPlane c{};
   c.plane = p.plane; c.plane_pitch = p.plane_pitch; c.width = p.width; c.height = p.height;
   c.words_per_row = cc_words_per_row(p.width); c.bits = r.d_cc_bits; c.label = r.d_cc_label;
-  HIP_OK(hipEventRecord(r.cc_ev[0], r.stream));
-  hipError_t e = launch_cc_label(c, f.ink_level, f.reach_x, f.reach_y, r.stream);
-  if (e == hipSuccess) e = launch_cc_collect(c, r.d_cc_list, r.d_cc_stat, comps, f.min_pixels, r.stream);
+  return c;
+}
+
+// Behind the labelling launches of c (`e`: what they returned; cc_ev[0] stands in front of them): launch_cc_collect, the
+// round trip for the list of up to `comps` components, its checks.  `all`: the kept components in arrival order.
+int collect_components(const char *what, const ComponentPlane &c, hipError_t e, int comps, int min_pixels, std::vector<Component> &all, long &roots) {
+  Runtime &r = rt();
+  if (e == hipSuccess) e = launch_cc_collect(c, r.d_cc_list, r.d_cc_stat, comps, min_pixels, r.stream);
   if (e != hipSuccess) return launch_failed(what, e);
   HIP_OK(hipEventRecord(r.cc_ev[1], r.stream));
   const size_t first = std::min((size_t)comps, kFirstReadBack);
   std::vector<int32_t> back(kComponentHead + first * 8);
   HIP_OK(hipMemcpyAsync(back.data(), r.d_cc_list, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
   HIP_OK(hipStreamSynchronize(r.stream));
-  const long roots = back[0], kept = back[1];
+  const long kept = back[1];
+  roots = back[0];
   if (roots < 0 || roots > comps || kept < 0 || kept > roots) return fail(std::string(what) + ": internal: the component counters are out of range");
   if ((size_t)kept > first) {
     back.resize(kComponentHead + (size_t)kept * 8);
@@ -6370,19 +6373,42 @@ int enqueue_components(const char *what, const GlyphPicture &p, const FindOpts &
   }
   HIP_OK(hipEventElapsedTime(&r.cc_usec, r.cc_ev[0], r.cc_ev[1]));
   r.cc_usec *= 1000.f;
-  std::vector<Component> all((size_t)kept);
+  all.resize((size_t)kept);
   if (kept) std::memcpy(all.data(), back.data() + kComponentHead, (size_t)kept * sizeof(Component));
   for (const Component &k : all)
-    if (k.id < 0 || k.id >= roots || k.left < 0 || k.upper < 0 || k.right > p.width || k.lower > p.height || k.left >= k.right || k.upper >= k.lower)
+    if (k.id < 0 || k.id >= roots || k.left < 0 || k.upper < 0 || k.right > c.width || k.lower > c.height || k.left >= k.right || k.upper >= k.lower)
       return fail(std::string(what) + ": internal: a component's box leaves the picture");
+  return 0;
+}
+
+// index_of_id (one entry per numbered root, uploaded from `index`, which outlives the upload) -> k_cc_relabel -> `labels`
+int enqueue_relabel(const char *what, const ComponentPlane &c, const std::vector<int32_t> &index, int32_t *labels) {
+  Runtime &r = rt();
+  HIP_OK(hipMemcpyAsync(r.d_cc_index, index.data(), index.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
+  const hipError_t e = launch_cc_relabel(c, r.d_cc_index, r.d_cc_out, r.stream);
+  if (e != hipSuccess) return launch_failed(what, e);
+  HIP_OK(hipMemcpyAsync(labels, r.d_cc_out, (size_t)c.width * c.height * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+  return 0;
+}
+
+// Behind enqueue_glyph_plane, on r.stream: the six labelling launches, the call's round trip for the component list
+// (the counters and the first kFirstReadBack components in one copy; a second copy only for more), select_components,
+// and -- when `labels` is not null -- the index map's upload, k_cc_relabel and the map's copy into `labels`, which the
+// caller waits for.  `chosen`: the returned components in order; `index` outlives its upload.
+int enqueue_components(const char *what, const GlyphPicture &p, const FindOpts &f, int cap, int32_t *labels, std::vector<Component> &chosen,
+                       long &total, std::vector<int32_t> &index) {
+  Runtime &r = rt();
+  const ComponentPlane c = component_plane(p);
+  HIP_OK(hipEventRecord(r.cc_ev[0], r.stream));
+  const hipError_t e = launch_cc_label(c, f.ink_level, f.reach_x, f.reach_y, r.stream);
+  std::vector<Component> all;
+  long roots = 0;
+  if (collect_components(what, c, e, (int)max_components(p.width, p.height), f.min_pixels, all, roots)) return -1;
   total = select_components(all, f, cap, chosen);
   if (labels) {
     index.assign((size_t)std::max(roots, 1L), -1);
     for (size_t k = 0; k < chosen.size(); k++) index[(size_t)chosen[k].id] = (int32_t)k;
-    HIP_OK(hipMemcpyAsync(r.d_cc_index, index.data(), index.size() * sizeof(int32_t), hipMemcpyHostToDevice, r.stream));
-    e = launch_cc_relabel(c, r.d_cc_index, r.d_cc_out, r.stream);
-    if (e != hipSuccess) return launch_failed(what, e);
-    HIP_OK(hipMemcpyAsync(labels, r.d_cc_out, (size_t)p.width * p.height * sizeof(int32_t), hipMemcpyDeviceToHost, r.stream));
+    return enqueue_relabel(what, c, index, labels);
   }
   return 0;
 }
@@ -6637,6 +6663,234 @@ int *bnn_mi355x_read_glyphs(const uint8_t *pixels, int width, int height, int ba
                             float *usecPreprocess, int *status) {
   return read_page("read_glyphs", pixels, width, height, bands, row_stride, opts, find, nullptr, number_class, cap, n_found, boxes, nullptr, nullptr,
                    usecPerImage, usecPreprocess, status);
+}
+
+}  // extern "C"
+
+// ---- a clip: the glyphs of all its frames in one set of launches (LFC; clip_glyphs.h) -------------------------------------
+namespace bnn {
+namespace {
+
+static_assert(kClipGlyphMaxFrames == BNN_MI355X_CLIP_GLYPHS_MAX_FRAMES, "the header states the clip's limit");
+
+struct ClipGlyphCall {  // what every clip entry point is given
+  const char *what;
+  const uint8_t *pixels;
+  int n_frames;
+  long frame_stride;
+  int width, height, bands;
+  long row_stride;
+  int cap;
+  long row_bytes() const { return row_stride ? row_stride : (long)width * bands; }
+};
+
+// (g null: find_glyphs_clip, which has no page options; `out`: an output of the caller's that must not be null)
+std::string validate_clip_call(const ClipGlyphCall &q, const GlyphOpts *o, const FindOpts &f, const PageOpts *g, const void *out, const void *boxes) {
+  std::string bad = validate_glyphs(q.what, q.pixels, q.width, q.height, q.bands, q.row_stride, nullptr, 0, o, out);
+  if (bad.empty()) bad = validate_clip_glyphs(q.what, q.n_frames, q.frame_stride, q.width, q.height, q.row_bytes(), q.cap);
+  if (bad.empty()) bad = validate_find(q.what, q.width, q.height, &f, boxes, q.cap);
+  if (bad.empty() && g) bad = validate_page(q.what, g);
+  return bad;
+}
+
+struct ClipPage {
+  ClipGlyphGeometry geo;
+  GlyphPicture tall;     // the clip as one picture of width x (frames * height)
+  ClipGlyphSplit split;
+  Page pg;               // the split's frame-major list as the record routes take a page's
+  long roots = 0;
+};
+
+// every workspace of the call, before anything is enqueued (growing synchronises)
+int reserve_clip_glyphs(const ClipGlyphGeometry &g, int bands, bool labels) {
+  Runtime &r = rt();
+  const size_t pitch = (size_t)glyph_plane_pitch(g.width), rows = (size_t)g.tall_height, n = (size_t)g.frame_pixels * g.frames;
+  if (r.d_gl_src.grow(pitch * bands * rows) || r.d_gl_plane.grow(pitch * rows) || r.d_gl_sum.grow((size_t)g.frames) ||
+      r.d_cc_bits.grow(rows * g.tiles_x) || r.d_cc_label.grow(n) || r.d_cc_stat.grow(g.max_components) ||
+      r.d_cc_list.grow(kComponentHead + g.max_components * 8) || (labels && (r.d_cc_index.grow(g.max_components) || r.d_cc_out.grow(n))))
+    return -1;
+  return ensure_events(r.cc_ev, 2);
+}
+
+// On r.stream: ONE upload of the clip (frame by frame only when the frames do not lie back to back), luma and enhance with a
+// mean per frame, the tile labelling, its seams, flatten, collect, the call's round trip for the component list, and the
+// split into frames.  Afterwards cp.pg holds the chosen glyphs of all frames in tall coordinates.
+int enqueue_clip_components(const ClipGlyphCall &q, const GlyphOpts &o, const FindOpts &f, const PageOpts *g, ClipPage &cp) {
+  Runtime &r = rt();
+  const ClipGlyphGeometry &geo = cp.geo;
+  const long pitch = glyph_plane_pitch(q.width);
+  const size_t src_pitch = (size_t)pitch * q.bands, row_bytes = (size_t)q.width * q.bands, rs = (size_t)q.row_bytes();
+  const size_t fs = q.frame_stride ? (size_t)q.frame_stride : rs * q.height;
+  if (fs == rs * q.height) {
+    HIP_OK(hipMemcpy2DAsync(r.d_gl_src, src_pitch, q.pixels, rs, row_bytes, (size_t)geo.tall_height, hipMemcpyHostToDevice, r.stream));
+  } else {
+    for (int i = 0; i < q.n_frames; i++)
+      HIP_OK(hipMemcpy2DAsync(r.d_gl_src + (size_t)i * q.height * src_pitch, src_pitch, q.pixels + (size_t)i * fs, rs, row_bytes, (size_t)q.height,
+                              hipMemcpyHostToDevice, r.stream));
+  }
+  HIP_OK(hipMemsetAsync(r.d_gl_sum, 0, (size_t)q.n_frames * sizeof(unsigned long long), r.stream));
+  cp.tall = GlyphPicture{};
+  cp.tall.src = r.d_gl_src; cp.tall.plane = r.d_gl_plane; cp.tall.width = q.width; cp.tall.height = (int)geo.tall_height; cp.tall.bands = q.bands;
+  cp.tall.plane_pitch = pitch; cp.tall.sum = r.d_gl_sum;
+  const ClipGlyphPlane plane{cp.tall, q.n_frames, q.height};
+  hipError_t e = launch_clip_plane(plane, o.contrast != 1.0f || o.brightness != 1.0f || o.threshold >= 0, o.contrast, o.brightness, o.threshold, r.stream);
+  if (e != hipSuccess) return launch_failed(q.what, e);
+  const ClipComponentPlane c{component_plane(cp.tall), q.n_frames, q.height, geo.tiles_x, geo.tiles_y};
+  HIP_OK(hipEventRecord(r.cc_ev[0], r.stream));
+  e = launch_clip_cc_label(c, f.ink_level, f.reach_x, f.reach_y, r.stream);
+  std::vector<Component> all;
+  if (collect_components(q.what, c.tall, e, (int)geo.max_components, f.min_pixels, all, cp.roots)) return -1;
+  const std::string bad = split_clip_components(all, geo, f, g, q.cap, cp.split);
+  if (!bad.empty()) return fail(std::string(q.what) + ": " + bad);
+  cp.pg.chosen = cp.split.chosen;
+  cp.pg.line = cp.split.line;
+  cp.pg.gap = cp.split.gap;
+  cp.pg.found.resize(cp.pg.chosen.size() * 4);
+  boxes_of(cp.pg.chosen, cp.pg.found.data(), nullptr);
+  return 0;
+}
+
+// ... and ONE record launch for all frames' glyphs: k_page_record on the tall plane under the mask, else read_glyphs' ink-box
+// sequence on it (its second round trip once per clip).  With no glyph nothing is enqueued.
+int enqueue_clip_records(const ClipGlyphCall &q, const GlyphOpts &o, const PageOpts &g, bool classify, ClipPage &cp) {
+  const int n = (int)cp.pg.chosen.size();
+  if (n == 0) return 0;
+  if (classify && reserve_results((size_t)n)) return -1;
+  if (g.mask) return enqueue_page_records(q.what, cp.tall, o, cp.pg);
+  return enqueue_glyph_records(q.what, cp.tall, cp.pg.found.data(), n, o, cp.pg.plan, cp.pg.meta);
+}
+
+// glyph k of the frame-major list -> slot (frame, k - start[frame]) of the caller's arrays, `cap` slots a frame; boxes go
+// back in frame coordinates.  Any of the arrays may be null.
+void clip_results(const ClipPage &cp, int cap, int *n_found, int *n_kept, int *boxes, int *pixel_counts, int *line, int *gap) {
+  const ClipGlyphSplit &s = cp.split;
+  for (int f = 0; f < cp.geo.frames; f++) {
+    const int first = s.start[(size_t)f], kept = s.start[(size_t)f + 1] - first;
+    if (n_found) n_found[f] = s.total[(size_t)f];
+    if (n_kept) n_kept[f] = kept;
+    for (int i = 0; i < kept; i++) {
+      const size_t k = (size_t)first + i, slot = (size_t)f * cap + i;
+      if (boxes) clip_frame_box(s.chosen[k], f, cp.geo.height, boxes + 4 * slot);
+      if (pixel_counts) pixel_counts[slot] = s.chosen[k].pixels;
+      if (line) line[slot] = s.line[k];
+      if (gap) gap[slot] = s.gap[k];
+    }
+  }
+}
+
+}  // namespace
+}  // namespace bnn
+
+extern "C" {
+
+int bnn_mi355x_find_glyphs_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                                const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find, int *boxes, int *pixel_counts,
+                                int32_t *labels, int cap, int *n_found, int *n_kept) {
+  Runtime &r = rt();
+  if (r.spec.is_cnv) return fail(std::string("find_glyphs_clip") + kGlyphsLfcOnly);
+  const ClipGlyphCall q{"find_glyphs_clip", pixels, n_frames, frame_stride, width, height, bands, row_stride, cap};
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  const std::string bad = validate_clip_call(q, opts ? &o : nullptr, f, nullptr, n_kept ? n_found : nullptr, boxes);
+  if (!bad.empty()) return fail(bad);
+  if (bind_device()) return -1;
+  ClipPage cp;
+  cp.geo = clip_glyph_geometry(n_frames, width, height);
+  std::vector<int32_t> index;
+  if (reserve_clip_glyphs(cp.geo, bands, labels != nullptr)) return -1;
+  DrainOnFailure drain;
+  if (enqueue_clip_components(q, o, f, nullptr, cp)) return -1;
+  if (labels) {  // a pixel's label: the index of its glyph in its FRAME's returned list
+    index.assign((size_t)std::max(cp.roots, 1L), -1);
+    for (int i = 0; i < n_frames; i++)
+      for (int k = cp.split.start[(size_t)i]; k < cp.split.start[(size_t)i + 1]; k++)
+        index[(size_t)cp.split.chosen[(size_t)k].id] = k - cp.split.start[(size_t)i];
+    if (enqueue_relabel(q.what, component_plane(cp.tall), index, labels)) return -1;
+    HIP_OK(hipStreamSynchronize(r.stream));
+  }
+  drain.ok();
+  clip_results(cp, cap, n_found, n_kept, boxes, pixel_counts, nullptr, nullptr);
+  return 0;
+}
+
+int bnn_mi355x_clip_to_mnist(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                             const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find, const bnn_mi355x_page_opts *page, int cap,
+                             int *n_found, int *n_kept, int *boxes, uint8_t *records, int *status, int *line, int *gap) {
+  Runtime &r = rt();
+  if (r.spec.is_cnv) return fail(std::string("clip_to_mnist") + kGlyphsLfcOnly);
+  const ClipGlyphCall q{"clip_to_mnist", pixels, n_frames, frame_stride, width, height, bands, row_stride, cap};
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  const PageOpts g = page_opts(page);
+  const std::string bad = validate_clip_call(q, opts ? &o : nullptr, f, &g, records && n_kept ? n_found : nullptr, boxes);
+  if (!bad.empty()) return fail(bad);
+  if (bind_device()) return -1;
+  ClipPage cp;
+  cp.geo = clip_glyph_geometry(n_frames, width, height);
+  if (reserve_clip_glyphs(cp.geo, bands, false)) return -1;
+  DrainOnFailure drain;
+  if (enqueue_clip_components(q, o, f, &g, cp) || enqueue_clip_records(q, o, g, false, cp)) return -1;
+  const size_t n = cp.pg.chosen.size();
+  std::vector<uint8_t> flat(n * kGlyphRecord);
+  std::vector<int> flat_status(n);
+  if (download_glyph_records(n, cp.pg.plan.status, flat.data(), flat_status.data())) return -1;
+  drain.ok();
+  clip_results(cp, cap, n_found, n_kept, boxes, nullptr, line, gap);
+  for (int i = 0; i < n_frames; i++)
+    for (int k = cp.split.start[(size_t)i]; k < cp.split.start[(size_t)i + 1]; k++) {
+      const size_t slot = (size_t)i * cap + (size_t)(k - cp.split.start[(size_t)i]);
+      // (a status-2 glyph's record stays as the caller left it)
+      if (flat_status[(size_t)k] != kGlyphTooThin) std::memcpy(records + slot * kGlyphRecord, flat.data() + (size_t)k * kGlyphRecord, kGlyphRecord);
+      if (status) status[slot] = flat_status[(size_t)k];
+    }
+  return 0;
+}
+
+int *bnn_mi355x_read_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands, long row_stride,
+                          const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find, const bnn_mi355x_page_opts *page, int number_class,
+                          int cap, int *n_found, int *n_kept, int *boxes, int *line, int *gap, float *usecPerImage, float *usecPreprocess,
+                          int *status) {
+  Runtime &r = rt();
+  if (usecPerImage) *usecPerImage = 0.f;
+  if (usecPreprocess) *usecPreprocess = 0.f;
+  if (r.spec.is_cnv) { fail(std::string("read_clip") + kGlyphsLfcOnly); return nullptr; }
+  const ClipGlyphCall q{"read_clip", pixels, n_frames, frame_stride, width, height, bands, row_stride, cap};
+  const GlyphOpts o = glyph_opts(opts);
+  const FindOpts f = find_opts(find);
+  const PageOpts g = page_opts(page);
+  const std::string bad = validate_clip_call(q, opts ? &o : nullptr, f, &g, n_kept ? n_found : nullptr, boxes);
+  if (!bad.empty()) { fail(bad); return nullptr; }
+  if (bad_number_class(number_class) || !ready()) return nullptr;
+  int *result = nullptr;
+  // everything that can fail from here on frees `result`
+  auto run = [&]() -> int {
+    if (bind_device()) return -1;
+    ClipPage cp;
+    cp.geo = clip_glyph_geometry(n_frames, width, height);
+    if (reserve_clip_glyphs(cp.geo, bands, false) || ensure_events(r.gl_ev, 3)) return -1;
+    DrainOnFailure drain;
+    HIP_OK(hipEventRecord(r.gl_ev[0], r.stream));
+    if (enqueue_clip_components(q, o, f, &g, cp) || enqueue_clip_records(q, o, g, true, cp)) return -1;
+    const int n = (int)cp.pg.chosen.size();
+    const size_t slots = (size_t)n_frames * cap;
+    if (!(result = new_result(slots))) return -1;
+    std::fill(result, result + slots, -1);
+    std::vector<int> flat((size_t)std::max(n, 1)), flat_status((size_t)std::max(n, 1));
+    if (n == 0) HIP_OK(hipStreamSynchronize(r.stream));  // nothing to read: a non-null result with no class in it
+    else if (classify_glyph_records(n, number_class, cp.pg.plan.status, flat.data(), flat_status.data())) return -1;
+    drain.ok();
+    clip_results(cp, cap, n_found, n_kept, boxes, nullptr, line, gap);
+    for (int i = 0; i < n_frames; i++)
+      for (int k = cp.split.start[(size_t)i]; k < cp.split.start[(size_t)i + 1]; k++) {
+        const size_t slot = (size_t)i * cap + (size_t)(k - cp.split.start[(size_t)i]);
+        result[slot] = flat[(size_t)k];
+        if (status) status[slot] = flat_status[(size_t)k];
+      }
+    if (n == 0) return 0;
+    return (usec_per_image(r.gl_ev[0], r.gl_ev[1], (size_t)n, usecPreprocess) || usec_per_image(r.gl_ev[1], r.gl_ev[2], (size_t)n, usecPerImage)) ? -1 : 0;
+  };
+  if (run()) { delete[] result; return nullptr; }
+  return result;
 }
 
 }  // extern "C"

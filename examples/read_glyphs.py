@@ -73,3 +73,11 @@ changed = [i for i in range(len(boxes)) if classes[i] != cropped[i]]
 print("glyphs whose class differs when a neighbour's ink stays in the record (mask=False): %s"
       % (", ".join("%d at x %d..%d" % (i, boxes[i][0], boxes[i][2]) for i in changed) or "none"))
 print("read_glyphs' order on the same page, by left edge alone:", classifier.read_text(page))
+
+# A clip: three frames of the feed, the sheet at three exposures.  read_clip reads them in ONE call -- one upload, one set of
+# launches (every frame enhanced by its own mean, the ink labelled tile by tile), one LFC pass for all frames' glyphs -- and
+# returns per frame what read_page returns for that frame alone.
+clip = [Image.eval(page, lambda v, k=k: v * k // 10) for k in (10, 8, 6)]
+for i, text in enumerate(classifier.read_clip_text(clip, word_gap=40)):
+    print("frame %d of the clip (%d glyphs):" % (i, classifier.glyphs_found[i]))
+    print(text)

@@ -1215,6 +1215,41 @@ int *bnn_mi355x_read_page(const uint8_t *pixels, int width, int height, int band
                           const bnn_mi355x_page_opts *page, int number_class, int cap, int *n_found, int *boxes, int *line,
                           int *gap, float *usecPerImage, float *usecPreprocess, int *status);
 
+/* ---- extension: read a clip -- the glyphs of all its frames in one set of launches (LFC) ----
+ * n_frames frames of width x height pixels, `bands` bytes a pixel, rows row_stride bytes apart (0: width * bands), frames
+ * frame_stride bytes apart (0: back to back), as scan_clip takes a clip.  Per frame the answer is find_glyphs' /
+ * page_to_mnist's / read_page's for that frame alone, from ONE upload, one set of launches, one host round trip and one LFC
+ * pass for all frames (csrc/clip_glyphs.h, csrc/clip_glyph_kernels.hip):
+ *   The clip is ONE tall L plane of width x (n_frames * height); frame f occupies rows [f * height, (f + 1) * height).  The
+ *   contrast step blends with the mean of the frame's OWN pixels; ink pixels of different frames are never adjacent; the
+ *   labelling works on tiles of 64 x 32 pixels in LDS and merges the tiles' borders afterwards; the component list is split
+ *   by frame on the host; everything else runs on the tall plane as it runs on a picture.
+ * Arrays are frame-major with `cap` slots a frame: slot (f, i) is entry f * cap + i; n_found[f] is frame f's total, n_kept[f]
+ * = min(cap, total) the slots in use; the other slots stay as the caller left them.  Boxes are in FRAME coordinates.
+ * find_glyphs_clip: boxes n_frames x cap x 4, pixel_counts n_frames x cap (may be NULL), labels n_frames x height x width
+ *       (may be NULL): the index of the pixel's glyph in its frame's returned list, -1 elsewhere.  Returns 0, -1.
+ * clip_to_mnist: records n_frames x cap x 784 (a status-2 glyph's record stays as the caller left it); status, line, gap
+ *       (n_frames x cap each) may be NULL.  Returns 0, -1.
+ * read_clip: the classes, n_frames x cap ints in the same layout (-1 in the unused slots and for a status-2 glyph).  Return
+ *       convention, ownership, the two times and status as read_page.  With mask = 1: k_page_record on the tall plane;
+ *       with mask = 0 read_glyphs' ink-box sequence on it, its second round trip once per clip.
+ * LFC only.  Refused before anything touches the GPU: what read_page refuses for one frame; n_frames outside
+ * 1..BNN_MI355X_CLIP_GLYPHS_MAX_FRAMES; a clip of more than BNN_MI355X_FIND_MAX_PIXELS pixels in all (cut it into several
+ * calls); a frame stride shorter than a frame's rows; n_frames x cap x 4 beyond an int.  The line model's limit of
+ * BNN_MI355X_PAGE_MAX_LINE_COMPONENTS applies per frame.  last_find_usec covers the labelling launches of these calls too. */
+#define BNN_MI355X_CLIP_GLYPHS_MAX_FRAMES 4096
+int bnn_mi355x_find_glyphs_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands,
+                                long row_stride, const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find, int *boxes,
+                                int *pixel_counts, int32_t *labels, int cap, int *n_found, int *n_kept);
+int bnn_mi355x_clip_to_mnist(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands,
+                             long row_stride, const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find,
+                             const bnn_mi355x_page_opts *page, int cap, int *n_found, int *n_kept, int *boxes, uint8_t *records,
+                             int *status, int *line, int *gap);
+int *bnn_mi355x_read_clip(const uint8_t *pixels, int n_frames, long frame_stride, int width, int height, int bands,
+                          long row_stride, const bnn_mi355x_glyph_opts *opts, const bnn_mi355x_find_opts *find,
+                          const bnn_mi355x_page_opts *page, int number_class, int cap, int *n_found, int *n_kept, int *boxes,
+                          int *line, int *gap, float *usecPerImage, float *usecPreprocess, int *status);
+
 /* Test hook: run the stages 0..stage on n host images (n <= 32768) and copy that stage's output,
  * exactly as it sits in HBM (bit-packed activation layout), to dst.  CNV: stage L =
  * layer L (0..7, after the max-pool where there is one); LFC: stage 0 = binarised input, stage

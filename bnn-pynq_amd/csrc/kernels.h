@@ -59,6 +59,11 @@ struct LfcLaunch {
   bool t_dispatch;
   unsigned *done_flag;        // as CnvLaunch::done_flag (n == 1: the one-block form of k_lfc_fused*)
   unsigned done_seq;
+  // device, the four layers as FP4 MFMA operands (lfc_mfma_table); null: the XNOR-popcount kernels only (the default:
+  // BNN_MI355X_LFC is not "mfma"; and the fault-injection paths).  With them, batches of lfc_mfma_min images and more run
+  // k_lfc_mfma (lfc_mfma_kernels.h) in every layer, whatever their size would otherwise select.
+  const uint8_t *lfc_mfma = nullptr;
+  long long lfc_mfma_min = 0;
 };
 
 // layer-0 MFMA table (packed_params.h): the tile-form operands sit behind the pixel-form ones
@@ -102,9 +107,23 @@ constexpr size_t kTailMfmaA2L5Off = kTailMfmaA2L4Off + 18 * 8 * 64 * 16 + 8 * 64
 // rows: device pointers to the net's packed layers (rows[1..7] are read: AR_TB rows for cnvW1A2, AR_TT for cnvW2A2)
 hipError_t conv_mfma_a2_table(NetId net, const uint32_t *const rows[9], uint8_t *dst, hipStream_t s);
 
+// The operand tables of the LFC nets' matrix form (lfc_mfma_kernels.h: layout, lfc_mfma_bytes), made with the table kernels
+// above.  rows: device pointers to the net's four packed layers; enqueued on s
+hipError_t lfc_mfma_table(NetId net, const uint32_t *const rows[4], uint8_t *dst, hipStream_t s);
+// images from which run_lfc takes the matrix form once the tables exist (BNN_MI355X_LFC=mfma; nothing selects the form without
+// the switch), each net its own edge, measured (tools/lfc_mfma_rate.py: one process alternating the two routes in seven
+// rounds, 1 024 ... 131 072 resident images, profiles/r38_lfc_mfma_rate.txt): the smallest measured size from which the
+// matrix form wins at every larger measured one.  Median us per call, matrix vs default route (whose spread over the rounds
+// was 0.1 ... 1.6) -- lfcW1A1: 1 024 images 41.1 vs 15.7, 4 096 41.6 vs 25.9, 10 000 42.6 vs 51.3, 32 768 71.1 vs 145.7,
+// 131 072 203.9 vs 563.4; lfcW1A2: 1 024 47.2 vs 21.1, 4 096 48.2 vs 48.8, 10 000 50.8 vs 78.4, 32 768 85.1 vs 180.6,
+// 131 072 256.1 vs 618.8.  BNN_MI355X_LFC_MFMA_MIN overrides
+constexpr long long kLfcMfmaMinW1A1 = 10000, kLfcMfmaMinW1A2 = 4096;
+
 // bit k set: stage k of run_cnv(net, a) runs on the matrix pipe (layer 0's MFMA forms count).  Decided by the code that
 // run_cnv itself decides with; nothing is launched.
 int cnv_matrix_stages(NetId net, const CnvLaunch &a);
+// the same for run_lfc: bits 1-4 (the four layers' stages of kLfcStages), all or none
+int lfc_matrix_stages(NetId net, const LfcLaunch &a);
 
 // enqueue all stages of one batch on a.stream; returns the launch error, if any
 hipError_t run_cnv(NetId net, const CnvLaunch &a);

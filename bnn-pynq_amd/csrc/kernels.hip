@@ -45,6 +45,7 @@
 #include "act_faults.h"
 #include "input_faults.h"
 #include "kernels.h"
+#include "lfc_mfma_kernels.h"
 #include "mem_faults.h"
 #include "mem_org.h"
 #include "packed_params.h"
@@ -904,8 +905,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const uint32_t *__restrict
 
 // The operand tables of the matrix forms of cnvW1A1 layers 1-3 (kernels.h, conv_mfma_table), made from the packed rows
 // in HBM.  One thread per 16-byte weight entry [k step][neuron tile][lane], then one per seed [tile][h][16].
+// two (layer 0 of lfcW1A2: XNOR rows with two thresholds; lfc_mfma_table): one more thread per neuron, for theta1 - theta0
+// behind the seeds, [tile][h][16] as well -- what not_fired subtracts to reach the second decision's value.
 __global__ __launch_bounds__(256) void k_conv_mfma_table(const uint32_t *__restrict__ rows, int row_dw, int ksteps, int tiles,
-                                                          int mw, uint8_t *__restrict__ dst) {
+                                                          int mw, uint8_t *__restrict__ dst, int two = 0) {
   const int idx = blockIdx.x * 256 + threadIdx.x, nw = ksteps * tiles * 64;
   if (idx < nw) {
     const int ks = idx / (tiles * 64), mt = (idx / 64) % tiles, lane = idx & 63, n = 32 * mt + (lane & 31), h = lane >> 5;
@@ -919,6 +922,13 @@ __global__ __launch_bounds__(256) void k_conv_mfma_table(const uint32_t *__restr
     long long t = (int)rows[(size_t)n * row_dw];
     t = t < -1 ? -1 : (t > mw + 2 ? mw + 2 : t);
     reinterpret_cast<float *>(dst + (size_t)nw * 16)[j] = (float)(-(mw - 2 * t) - 1);
+  } else if (two && idx < nw + tiles * 64) {
+    const int j = idx - nw - tiles * 32, mt = j >> 5, h = (j >> 4) & 1, reg = j & 15;
+    const int n = 32 * mt + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    long long t0 = (int)rows[(size_t)n * row_dw], t1 = (int)rows[(size_t)n * row_dw + 1];  // clamped as the seed's
+    t0 = t0 < -1 ? -1 : (t0 > mw + 2 ? mw + 2 : t0);
+    t1 = t1 < -1 ? -1 : (t1 > mw + 2 ? mw + 2 : t1);
+    reinterpret_cast<float *>(dst + (size_t)nw * 16)[tiles * 32 + j] = (float)(2 * (t0 - t1));  // (mw - 2 t1) - (mw - 2 t0)
   }
 }
 
@@ -3395,6 +3405,14 @@ inline const uint8_t *tail_mfma_for(const CnvLaunch &a) {
   if (a.done_flag && a.n == 1) return nullptr;
   return a.n >= tail_mfma_min<ARITH>() ? a.conv_mfma : nullptr;
 }
+// the operand tables a batch of a.n images runs the four LFC layers from (k_lfc_mfma), or null: the integer-pipe forms
+// (no tables: BNN_MI355X_LFC is not "mfma", or a fault-injection path; too small a batch; or the single-image call that
+// carries a completion word, which only k_lfc_fused* sets).  Non-null, the matrix form takes precedence over the
+// one-launch forms.  run_lfc and lfc_matrix_stages both decide here
+inline const uint8_t *lfc_mfma_for(const LfcLaunch &a) {
+  if (a.done_flag && a.n == 1) return nullptr;
+  return a.n >= a.lfc_mfma_min ? a.lfc_mfma : nullptr;
+}
 // persistent grid of the matrix forms: at most `cap` blocks (what stays resident on the 256 CUs), the `units` (image pairs
 // or groups) dealt evenly over them
 inline unsigned persistent_grid(long long units, long long cap) {
@@ -3762,6 +3780,22 @@ hipError_t conv_mfma_a2_table(NetId net, const uint32_t *const rows[9], uint8_t 
   return hipGetLastError();
 }
 
+hipError_t lfc_mfma_table(NetId net, const uint32_t *const rows[4], uint8_t *dst, hipStream_t s) {
+  const bool two = net == NET_LFCW1A2;
+  for (int l = 0; l < 4; l++) {
+    const int ks = lfc_mfma_ksteps(l), tiles = lfc_mfma_tiles(l);
+    const dim3 grid((unsigned)((ks * tiles * 64 + tiles * (two ? 64 : 32) + 255) / 256));
+    // XNOR rows (all of lfcW1A1, layer 0 of lfcW1A2: all 64 ks inputs are synapses, layer 0's padding included); else AR_TB rows
+    if (!two || l == 0) hipLaunchKernelGGL(k_conv_mfma_table, grid, dim3(256), 0, s, rows[l], 2 + 2 * ks, ks, tiles, 64 * ks, dst + lfc_mfma_offset(l, two), two ? 1 : 0);
+    else hipLaunchKernelGGL(k_conv_mfma_a2_table<false>, grid, dim3(256), 0, s, rows[l], ks, tiles, dst + lfc_mfma_offset(l, two));
+  }
+  return hipGetLastError();
+}
+
+int lfc_matrix_stages(NetId net, const LfcLaunch &a) {
+  return (net == NET_LFCW1A1 || net == NET_LFCW1A2) && a.n > 0 && lfc_mfma_for(a) ? 0x1E : 0;
+}
+
 int cnv_matrix_stages(NetId net, const CnvLaunch &a) {
   switch (net) {
     case NET_CNVW1A1: return matrix_stages_t<AR_XNOR, false>(a);
@@ -3794,7 +3828,8 @@ hipError_t run_lfc(NetId net, const LfcLaunch &a) {
   uint32_t *A = reinterpret_cast<uint32_t *>(a.buf0), *B = reinterpret_cast<uint32_t *>(a.buf1);
   uint64_t *A64 = reinterpret_cast<uint64_t *>(a.buf0), *B64 = reinterpret_cast<uint64_t *>(a.buf1);
   hipStream_t s = a.stream;
-  if (n <= (net == NET_LFCW1A1 ? lfc_fused_max() : kLfcFusedMaxA2) && !a.events && a.last_stage >= kLfcStages - 1) {
+  const uint8_t *const tm = lfc_mfma_for(a);  // the four layers on the matrix pipe: the staged route below, whatever the size
+  if (!tm && n <= (net == NET_LFCW1A1 ? lfc_fused_max() : kLfcFusedMaxA2) && !a.events && a.last_stage >= kLfcStages - 1) {
     // small batch: the one-launch form, a block per group of IPB images (no per-stage events: there are no
     // stages).  A block costs ~8 us + ~1.6 us per further image whatever the batch, so the group is the
     // smallest that still fits the batch in one round of 256 blocks (profiles/r01_lfc_forms.txt).
@@ -3835,7 +3870,7 @@ hipError_t run_lfc(NetId net, const LfcLaunch &a) {
 #undef BNN_FUSED_P
     return hipGetLastError();
   }
-  if (net == NET_LFCW1A1 && n <= lfc_block_max() && !a.events && a.last_stage >= kLfcStages - 1) {
+  if (!tm && net == NET_LFCW1A1 && n <= lfc_block_max() && !a.events && a.last_stage >= kLfcStages - 1) {
     // mid-size batch: two 1024-thread blocks per CU, each walking all four layers over its share of the images
     const int ipb = (int)((n + 511) / 512);
     const dim3 g((unsigned)((n + ipb - 1) / ipb)), b(1024);
@@ -3864,7 +3899,17 @@ hipError_t run_lfc(NetId net, const LfcLaunch &a) {
   }
   BNN_MARK(a.events, 1, s);
   uint32_t *W32 = reinterpret_cast<uint32_t *>(a.words);
-  if (net == NET_LFCW1A1) {
+  if (tm) {  // one launch per layer, as below: the stage events and the last_stage hook see the same stages
+    const void *const src[4] = {L0in, B, A, B};
+    void *const dst[4] = {B, A, B, W32};
+    for (int l = 0; l < 4; l++) {
+      if (a.last_stage >= l + 1) {
+        const hipError_t e = launch_lfc_mfma(net, l, src[l], dst[l], tm, (int)n, s);
+        if (e != hipSuccess) return e;
+      }
+      BNN_MARK(a.events, l + 2, s);
+    }
+  } else if (net == NET_LFCW1A1) {
     if (a.last_stage >= 1) BNN_STAGE((k_vec_x<13, false, 1, 1>), (k_vec_x<13, false, 1, 1, 8>), n, 32, L0in, B, a.rows[0]);
     BNN_MARK(a.events, 2, s);
     if (a.last_stage >= 2) BNN_STAGE((k_vec_x<16, false, 1, 1>), (k_vec_x<16, false, 1, 1, 8>), n, 32, B64, A, a.rows[1]);

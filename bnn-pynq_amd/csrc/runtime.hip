@@ -50,6 +50,7 @@
 #include "mem_faults.h"
 #include "mem_org.h"
 #include "kernels.h"
+#include "lfc_mfma_kernels.h"
 #include "preprocess.h"
 #include "resample.h"
 #include "window_kernels.h"
@@ -245,6 +246,12 @@ struct Runtime {
   // rows whenever they change; null under BNN_MI355X_CONV=valu.  conv_xnor: the call in progress runs the XNOR-popcount kernels only.
   uint8_t *d_conv_mfma = nullptr;
   bool conv_mfma = false, conv_xnor = false;
+  // The LFC nets' four layers as FP4 MFMA operands (lfc_mfma_kernels.h), made like the above, only under BNN_MI355X_LFC=mfma
+  // (read at every load, with BNN_MI355X_LFC_MFMA_MIN: the images from which run_lfc takes the matrix form); conv_xnor
+  // holds them back as it does the CNV tables.
+  uint8_t *d_lfc_mfma = nullptr;
+  bool lfc_mfma = false;
+  long long lfc_mfma_min = kLfcMfmaMinW1A1;
   bool warmed = false;  // warm_up() has run since the last deinit()
   int two_rows = 0;  // rows holding a weight of -2 (2-bit-weight net under fault injection): kernels.hip, two_extra
   // workspace
@@ -526,6 +533,11 @@ struct DrainOnFailure {
 // (re)make the matrix forms' operand tables from the rows in HBM, behind whatever changed them on stream s
 int make_conv_tables(hipStream_t s) {
   Runtime &r = rt();
+  if (r.lfc_mfma) {
+    if (!r.d_lfc_mfma) HIP_OK(hipMalloc(reinterpret_cast<void **>(&r.d_lfc_mfma), lfc_mfma_bytes(r.spec.id == NET_LFCW1A2)));
+    HIP_OK(lfc_mfma_table(r.spec.id, r.rows, r.d_lfc_mfma, s));
+    HIP_OK(hipStreamSynchronize(s));
+  }
   if (!r.conv_mfma) return 0;
   const bool a2 = r.spec.id != NET_CNVW1A1;  // cnvW1A2, cnvW2A2: two planes in, two thresholds
   if (!r.d_conv_mfma) HIP_OK(hipMalloc(reinterpret_cast<void **>(&r.d_conv_mfma), a2 ? kConvMfmaA2Bytes : kConvMfmaBytes));
@@ -563,6 +575,13 @@ int upload_blob() {
   }
   const char *cv = std::getenv("BNN_MI355X_CONV");
   r.conv_mfma = r.spec.is_cnv && !(cv && std::strcmp(cv, "valu") == 0);
+  const char *lf = std::getenv("BNN_MI355X_LFC"), *lm = std::getenv("BNN_MI355X_LFC_MFMA_MIN");
+  r.lfc_mfma = !r.spec.is_cnv && lf && std::strcmp(lf, "mfma") == 0;
+  r.lfc_mfma_min = lm ? std::atoll(lm) : (r.spec.id == NET_LFCW1A2 ? kLfcMfmaMinW1A2 : kLfcMfmaMinW1A1);
+  if (!r.lfc_mfma && r.d_lfc_mfma) {  // (nothing reads them: the device was synchronised above) under valu no table is kept
+    HIP_OK(hipFree(r.d_lfc_mfma));
+    r.d_lfc_mfma = nullptr;
+  }
   return make_conv_tables(r.stream);
 }
 
@@ -837,6 +856,11 @@ void set_forms(CnvLaunch &a) {
   a.conv_mfma = r.conv_mfma && !r.conv_xnor ? r.d_conv_mfma : nullptr;
   a.has_two = r.two_rows > 0;
 }
+void set_forms(LfcLaunch &a) {
+  Runtime &r = rt();
+  a.lfc_mfma = r.lfc_mfma && !r.conv_xnor ? r.d_lfc_mfma : nullptr;
+  a.lfc_mfma_min = r.lfc_mfma_min;
+}
 
 int enqueue(const uint8_t *d_imgs, int n, int ncls, int32_t *d_classes, int16_t *d_scores, uint64_t *d_words,
             hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, int lane = 0, bool t_dispatch = false, bool packed = false,
@@ -871,6 +895,7 @@ int enqueue(const uint8_t *d_imgs, int n, int ncls, int32_t *d_classes, int16_t 
     a.images = d_imgs; a.packed = packed; a.n = n; a.buf0 = ws0; a.buf1 = ws1;
     for (int l = 0; l < 4; l++) a.rows[l] = r.rows[l];
     a.words = d_words;
+    set_forms(a);
     a.classes = d_classes; a.number_class = ncls; a.stream = s; a.events = evs;
     a.last_stage = r.debug_last_stage >= 0 ? r.debug_last_stage : kLfcStages - 1;
     a.t0 = t0; a.t1 = t1; a.t_dispatch = t_dispatch; a.done_flag = done_flag; a.done_seq = done_seq;
@@ -4735,7 +4760,13 @@ int bnn_mi355x_debug_lfc_wstamps(unsigned long long *dst) {
 int bnn_mi355x_matrix_stages(int n_images) {
   Runtime &r = rt();
   if (!r.d_blob) return -1;
-  if (!r.spec.is_cnv || n_images <= 0) return 0;
+  if (n_images <= 0) return 0;
+  if (!r.spec.is_cnv) {
+    LfcLaunch a{};
+    a.n = n_images;
+    set_forms(a);
+    return lfc_matrix_stages(r.spec.id, a);
+  }
   CnvLaunch a{};
   a.n = n_images;
   set_forms(a);

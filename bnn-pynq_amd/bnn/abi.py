@@ -54,7 +54,8 @@ EXT = ["bnn_mi355x_network", "bnn_mi355x_image_bytes", "bnn_mi355x_last_error", 
        "bnn_mi355x_scan_clip_frames", "bnn_mi355x_detect_clip_frames", "bnn_mi355x_scan_clip_device", "bnn_mi355x_detect_clip_device",
        "bnn_mi355x_scan_form", "bnn_mi355x_scan_matrix_stages", "bnn_mi355x_scan_stage0_form", "bnn_mi355x_scan_clip_fine",
        "bnn_mi355x_scan_fine_boxes", "bnn_mi355x_debug_scan_clip_fine_stage", "bnn_mi355x_find_glyphs_clip",
-       "bnn_mi355x_clip_to_mnist", "bnn_mi355x_read_clip"]
+       "bnn_mi355x_clip_to_mnist", "bnn_mi355x_read_clip", "bnn_mi355x_campaign_form", "bnn_mi355x_campaign_matrix_stages",
+       "bnn_mi355x_debug_campaign_stage"]
 
 # bnn_mi355x_frames.format by name (include/bnn_mi355x.h, BNN_MI355X_FORMAT_*)
 PIXEL_FORMATS = {"rgb": 0, "l": 1, "bgr": 2, "nv12": 3, "i420": 4, "yuyv": 5}
@@ -362,6 +363,14 @@ def declare_extensions(L):
         L.bnn_mi355x_scan_form.restype = C.c_int
         L.bnn_mi355x_scan_matrix_stages.argtypes = [C.c_long]
         L.bnn_mi355x_scan_matrix_stages.restype = C.c_int
+    if hasattr(L, "bnn_mi355x_campaign_form"):  # (likewise)
+        L.bnn_mi355x_campaign_form.argtypes = [C.c_int]
+        L.bnn_mi355x_campaign_form.restype = C.c_int
+        L.bnn_mi355x_campaign_matrix_stages.argtypes = [C.c_int]
+        L.bnn_mi355x_campaign_matrix_stages.restype = C.c_int
+        L.bnn_mi355x_debug_campaign_stage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                                      C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        L.bnn_mi355x_debug_campaign_stage.restype = C.c_long
     if hasattr(L, "bnn_mi355x_scan_stage0_form"):  # (likewise)
         L.bnn_mi355x_scan_stage0_form.argtypes = [C.c_int]
         L.bnn_mi355x_scan_stage0_form.restype = C.c_int

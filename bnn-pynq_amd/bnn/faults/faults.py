@@ -157,6 +157,26 @@ class FaultTest:
             "word" if word_size > 1 else "bit",
             "any layer" if not target_layers else "layer(s) {}".format(target_layers))
 
+    def _campaign_lib(self, what):
+        lib = self.classifier_cls(self.network, self.dataset, self.runtime).bnn.interface
+        if not hasattr(lib, "bnn_mi355x_campaign_form"):
+            raise RuntimeError("%s: this library has no bnn_mi355x_campaign_form" % what)
+        return lib
+
+    def campaign_form(self, form=None):
+        """The form of layers 1-7 in the campaign calls (``run_test(batched=True)``, :meth:`run_noise_test` and the memory upset
+        campaigns): 0 the integer pipe, 1 the matrix cores, every run from operand tables made of its own copy of the
+        parameters (``bnn_mi355x_campaign_form``); never automatic.  Sets ``form`` when given; returns the form before the
+        call.  The answers do not depend on it."""
+        if form is not None and form not in (0, 1):
+            raise ValueError("campaign_form: form must be 0 or 1")
+        return int(self._campaign_lib("campaign_form").bnn_mi355x_campaign_form(7 if form is None else int(form)))
+
+    def campaign_matrix_stages(self, runs):
+        """bit mask of the layers a campaign of ``runs`` runs would run on the matrix cores under the current form: 0b11111110 or
+        0 (form 0, an LFC network, no operand tables, or more runs than the table memory holds)"""
+        return int(self._campaign_lib("campaign_matrix_stages").bnn_mi355x_campaign_matrix_stages(int(runs)))
+
     def run_test(self, num_runs, num_flips, word_size=1, target_type=-1, target_layers=(), batched=False, seed=0):
         """-> (results per run, usec per image per run, accuracy per run).
         batched: all runs in one call, side by side on the GPU (the usec figure is then the call's, per image of

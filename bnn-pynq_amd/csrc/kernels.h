@@ -16,8 +16,8 @@ struct CnvLaunch {
   const uint8_t *l1_mfma;     // device, cnvW1A1 layer 1 as FP4 MFMA operands (l1_mfma_table); null: the XNOR-popcount kernel.
                               // Side experiment only (BNN_MI355X_L1=mfma): never the default path.
   const uint8_t *conv_mfma;   // device, layers 1-7 as FP4 MFMA operands (cnvW1A1: conv_mfma_table, the 2-bit nets:
-                              // conv_mfma_a2_table); null: the XNOR-popcount kernels only (BNN_MI355X_CONV=valu, and the
-                              // fault-injection paths)
+                              // conv_mfma_a2_table); null: the XNOR-popcount kernels only (BNN_MI355X_CONV=valu).  The
+                              // campaign launches have a matrix form of their own: MultiLaunch::multi_mfma
   bool l1_literal;            // cnvW1A1, BNN_MI355X_L1=lds: layer 1 in the north-star's literal formulation (comparison figure only)
   bool has_two;               // cnvW2A2: some row holds a weight of -2 (fault injection): the -2-aware kernel variants
   int16_t *scores;            // device, n x 64, may be null
@@ -152,6 +152,12 @@ struct MultiLaunch {
   // run the stages of layers first..last only (bnn_mi355x_fault_sweep); layer l's stage reads layer l-1's output where
   // the full pass leaves it (stage_output_bytes).  LFC: layer 0's stage includes the binariser.
   int first = 0, last = 1 << 30;
+  // CNV: run 0's operand tables of layers 1-7 (multi_mfma_kernels.h, multi_mfma_tables); run q's mfma_stride bytes behind, 0
+  // when every run reads the loaded blob (stride 0: the tables load_parameters made).  Set, the covered layers of 1-7 run the
+  // segment forms of the matrix kernels, whatever the segment lengths and whatever has_two says (a -2 is an FP4 value of the
+  // tables); null: the integer kernels (campaign form 0, the sweeps, act_window, BNN_MI355X_CONV=valu)
+  const uint8_t *multi_mfma = nullptr;
+  size_t mfma_stride = 0;
 };
 hipError_t run_cnv_multi(NetId net, const MultiLaunch &a);
 hipError_t run_lfc_multi(NetId net, const MultiLaunch &a);

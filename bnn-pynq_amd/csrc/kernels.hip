@@ -48,6 +48,7 @@
 #include "lfc_mfma_kernels.h"
 #include "mem_faults.h"
 #include "mem_org.h"
+#include "multi_mfma_kernels.h"
 #include "packed_params.h"
 static_assert(bnn::kL0TileOffset == (int)bnn::kL0MfmaTileOffset && bnn::kL0BigBytes == (int)bnn::kL0MfmaBigBytes,
               "k_conv0_tile's operand offsets must be the ones packed_params.cpp writes the layer-0 table by");
@@ -3649,7 +3650,12 @@ void run_cnv_multi_t(const MultiLaunch &a) {
   } else if (in(0)) {
     BNN_MULTI((k_conv0<OUT2, true>), 900, 2, a.images, A, a.rows[0], false);
   }
-  if constexpr (ARITH == AR_XNOR && !OUT2) {
+  if (a.multi_mfma) {
+    // the matrix form of the campaign launches (multi_mfma_kernels.h): layers 1-7 from the runs' own operand tables
+    constexpr NetId id = ARITH == AR_XNOR ? NET_CNVW1A1 : ARITH == AR_TB ? NET_CNVW1A2 : NET_CNVW2A2;
+    for (int l = 1; l <= 7; l++)
+      if (in(l)) (void)run_cnv_multi_mfma(id, l, a);
+  } else if constexpr (ARITH == AR_XNOR && !OUT2) {
     if (in(1)) BNN_MULTI((k_quad_x<1, 30, true, 32, true>), 196, 2, A64, B, a.rows[1], false);
     if (in(2)) BNN_MULTI((k_quad_x<1, 14, false, 32, true>), 36, 4, B64, A, a.rows[2], false);
     if (in(3)) BNN_MULTI((k_quad_x<2, 12, true, 32, true>), 25, 4, A64, B, a.rows[3], false);

@@ -51,6 +51,7 @@
 #include "mem_org.h"
 #include "kernels.h"
 #include "lfc_mfma_kernels.h"
+#include "multi_mfma_kernels.h"
 #include "preprocess.h"
 #include "resample.h"
 #include "window_kernels.h"
@@ -303,6 +304,8 @@ struct Runtime {
   DeviceBuf<uint8_t> d_all;  // a whole input file's images, resident (fault campaigns)
   // bnn_mi355x_fault_campaigns: the runs' blob copies; the staging area (patches, patch spans, segment records); results
   DeviceBuf<uint8_t> d_copies, d_camp, d_camp_res;
+  // campaign form 1 (multi_mfma_kernels.h): the operand tables of every run's copy, multi_mfma_bytes apart
+  DeviceBuf<uint8_t> d_multi_mfma;
   std::vector<Fault> camp_faults;  // the faults of the last such call, run-major; camp_run[i]: the run of camp_faults[i]
   std::vector<int> camp_run;
   // bnn_mi355x_fault_sweep (the runs' blob copies: d_copies): the fault-free stage outputs and results of the call's images;
@@ -544,6 +547,41 @@ int make_conv_tables(hipStream_t s) {
   HIP_OK(a2 ? conv_mfma_a2_table(r.spec.id, r.rows, r.d_conv_mfma, s) : conv_mfma_table(r.rows, r.d_conv_mfma, s));
   HIP_OK(hipStreamSynchronize(s));  // (the second compute lane reads them too)
   return 0;
+}
+
+// The form of the campaign launches (bnn_mi355x_campaign_form): 0 the integer pipe, 1 layers 1-7 of every campaign launch
+// on the matrix cores (multi_mfma_kernels.h).  Never automatic.  The classes and counters are the same either way.
+int &campaign_form() {
+  static int form = [] {
+    const char *e = std::getenv("BNN_MI355X_CAMPAIGN");
+    return e && std::strcmp(e, "mfma") == 0 ? 1 : 0;
+  }();
+  return form;
+}
+// whether the campaign launches of a call of `runs` runs take the matrix form: form 1, a CNV net with its operand tables (not
+// under BNN_MI355X_CONV=valu), and the runs' tables within kCampaignTableCap
+bool campaign_mfma(int runs) {
+  const Runtime &r = rt();
+  const size_t bytes = multi_mfma_bytes(r.spec.id);
+  return campaign_form() == 1 && bytes && r.d_blob && r.conv_mfma && r.d_conv_mfma && runs >= 1 && (size_t)runs * bytes <= kCampaignTableCap;
+}
+// room for the tables of `runs` copies; before anything of the call is in the stream (growing waits for the stream)
+int campaign_reserve(int runs) { return rt().d_multi_mfma.grow((size_t)runs * multi_mfma_bytes(rt().spec.id)); }
+// (re)make the tables of the `runs` copies at `copies`, `stride` bytes apart, behind whatever changed them on r.stream
+int campaign_tables(const uint8_t *copies, size_t stride, int runs) {
+  Runtime &r = rt();
+  const PackedHeader *h = reinterpret_cast<const PackedHeader *>(r.blob.data());
+  const uint32_t *rows[9] = {};
+  for (int l = 0; l < r.spec.nlayers; l++) rows[l] = reinterpret_cast<const uint32_t *>(copies + h->layer[l].offset);
+  const hipError_t e = multi_mfma_tables(r.spec.id, rows, stride, runs, r.d_multi_mfma, multi_mfma_bytes(r.spec.id), r.stream);
+  if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+  return 0;
+}
+// the tables a campaign launch reads: the runs' own where they have copies (own), else the ones load_parameters made
+void set_campaign_tables(MultiLaunch &a, bool own) {
+  Runtime &r = rt();
+  a.multi_mfma = own ? r.d_multi_mfma.get() : r.d_conv_mfma;
+  a.mfma_stride = own ? multi_mfma_bytes(r.spec.id) : 0;
 }
 
 int upload_blob() {
@@ -2337,6 +2375,8 @@ int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs
     if (r.d_copies.grow((size_t)R * stride) || r.d_camp.grow(upload.size()) ||
         r.d_camp_res.grow(total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
       return -1;
+    const bool mfma = campaign_mfma(R);  // (campaign form 1: the runs' operand tables follow every wave's patches)
+    if (mfma && campaign_reserve(R)) return -1;
     std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
     if (!cnv) w.resize(total);
     DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
@@ -2361,6 +2401,7 @@ int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs
       const int ns = (int)(span_first[(size_t)k + 1] - span_first[(size_t)k]);
       hipError_t e = scatter_patches(r.d_camp, d_spans + span_first[(size_t)k], ns, r.d_copies, r.stream);
       if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      if (mfma && (k == 0 || ns > 0) && campaign_tables(r.d_copies, stride, R)) return -1;
       for (; li < launches.size() && launches[li].wave == k; li++) {
         const Launch &L = launches[li];
         MultiLaunch a{};
@@ -2372,6 +2413,7 @@ int *bnn_mi355x_fault_campaigns(const char *path, int number_class, int num_runs
         a.l0_mfma = tab ? r.d_copies + h.l0_mfma_offset : nullptr;
         a.stride = stride;
         a.has_two = wave_two[(size_t)k] != 0;
+        if (mfma) set_campaign_tables(a, true);
         a.classes = reinterpret_cast<int32_t *>(r.d_camp_res.get());
         a.words = reinterpret_cast<uint64_t *>(r.d_camp_res.get());
         a.number_class = number_class;
@@ -3189,6 +3231,7 @@ int *bnn_mi355x_act_noise_campaigns(const char *path, int number_class, int num_
         a.l0_mfma = tab ? clean + h.l0_mfma_offset : nullptr;
         a.stride = 0;  // every run reads the one loaded blob
         a.has_two = r.two_rows > 0;
+        if (campaign_mfma(1)) set_campaign_tables(a, false);  // (campaign form 1: ... and the loaded blob's operand tables)
         a.classes = reinterpret_cast<int32_t *>(r.d_camp_res.get());
         a.words = reinterpret_cast<uint64_t *>(r.d_camp_res.get());
         a.number_class = number_class;
@@ -3944,6 +3987,16 @@ struct MemNoiseEntry {
   bool file_first = false;     // the file is opened and its epochs are counted before mem_noise_check
 };
 
+// bnn_mi355x_debug_campaign_stage: the call body on images in host memory instead of a file, through layer `stage` only; that
+// stage's packed output of every (run, image) pair goes to out, run-major, `per` bytes each
+struct CampaignProbe {
+  const uint8_t *images;
+  int n, stage;
+  uint8_t *out;
+  size_t per;
+  int in_buf1;
+};
+
 // Random upsets of the parameter memories, many runs in one call.  Every run gets a copy of the loaded blob in HBM; the images
 // go epoch by epoch, each epoch's scrub and upsets enqueued in front of its pairs and applied to the copies in place
 // (exposure_epoch; the plain route: all of it in front of the one epoch's pairs, mem_noise_enqueue); an epoch's (run, image)
@@ -3952,7 +4005,7 @@ struct MemNoiseEntry {
 // well, so a call's runs always fit.  The counters are ExposureCounters' blocks; the plain route's are [run][layer][2].
 static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &hz, const Exposure &ex, const char *path, int number_class,
                                      int num_runs, unsigned long long seed, const unsigned int *rate_w_q32, const unsigned int *rate_t_q32,
-                                     int n_rates, int *image_number, float *usecPerImage) {
+                                     int n_rates, int *image_number, float *usecPerImage, const CampaignProbe *probe = nullptr) {
   Runtime &r = rt();
   const NetSpec &net = r.spec;
   const char *const who = en.who;
@@ -3969,7 +4022,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     fail(std::string(who) + ": repair_every must not be negative (0: never repair)");
     return nullptr;
   }
-  if (!path) {
+  if (!path && !probe) {
     fail(std::string(who) + ": bad arguments (path missing)");
     return nullptr;
   }
@@ -3983,6 +4036,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     return nullptr;
   }
   ImageFile f;
+  if (probe) f.n = (size_t)probe->n;  // (no file: the images are the caller's)
   // the epochs a file implies, refused where they or their counters are too many; `false` once that is known not to be so
   auto too_many_epochs = [&]() -> bool {
     const long long epochs = en.one_epoch ? 1 : ((long long)f.n + ex.epoch_images - 1) / ex.epoch_images;
@@ -3995,7 +4049,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
   // ready(), the first thing that may touch one -- and the file's size is known without a device; the others keep the order they had)
   if (en.file_first && (open_image_file(path, f) || too_many_epochs())) return nullptr;
   if (mem_noise_check(who, rate_w_q32, rate_t_q32, n_rates, hz, en.base_only)) return nullptr;
-  if (!en.file_first && open_image_file(path, f)) return nullptr;
+  if (!en.file_first && !probe && open_image_file(path, f)) return nullptr;
   const int n = (int)f.n;
   const size_t total = (size_t)R * n;
   const bool cnv = net.is_cnv;
@@ -4032,7 +4086,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
       if (v > 0) cap = std::min<size_t>(cap, (size_t)v);
     }
     // the records of every group: a run's images of one epoch, cut at the group's end; the epochs one after the other
-    struct Group { size_t seg0; int nsegs, max_len, total, epoch; };
+    struct Group { size_t seg0; int nsegs, max_len, total, epoch; size_t pair0; };  // (pair0: its first pair of the epoch, run-major)
     std::vector<MultiSeg> segs;
     std::vector<Group> groups;
     for (int t = 0; t < E; t++) {
@@ -4040,7 +4094,7 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
       const size_t pairs = (size_t)R * len;
       for (size_t p0 = 0; p0 < pairs; p0 += cap) {
         const size_t p1 = std::min(pairs, p0 + cap);
-        Group g{segs.size(), 0, 0, 0, t};
+        Group g{segs.size(), 0, 0, 0, t, p0};
         for (size_t p = p0; p < p1;) {
           const int q = (int)(p / (size_t)len), i = (int)(p % (size_t)len), m = (int)std::min<size_t>((size_t)(len - i), p1 - p);
           segs.push_back(MultiSeg{q, i0 + i, g.total, m});
@@ -4056,10 +4110,21 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     std::memcpy(&h, r.blob.data(), sizeof(h));
     const bool tab = h.l0_mfma_offset && r.l0_mfma;
     const size_t counts_off = ((size_t)R * 8 + 255) & ~(size_t)255;
-    if (load_file_resident(f, n) || reserve((int)cap)) return -1;
+    if (probe) {
+      const size_t bytes = (size_t)n * (size_t)net.image_bytes();
+      if (bind_device() || r.d_all.grow(bytes + 256)) return -1;
+      HIP_OK(hipMemcpy(r.d_all, probe->images, bytes, hipMemcpyHostToDevice));
+    } else if (load_file_resident(f, n)) {
+      return -1;
+    }
+    if (reserve((int)cap)) return -1;
     if (r.d_sw_segs.grow(segs.size() * sizeof(MultiSeg)) ||
         r.d_camp_res.grow(total * (cnv ? sizeof(int32_t) : sizeof(uint64_t))))
       return -1;
+    // campaign form 1: layers 1-7 on the matrix cores, from the runs' own operand tables where the runs have copies (remade
+    // behind everything that changes the copies), else from the loaded blob's
+    const bool mfma = campaign_mfma(R);
+    if (mfma && any && campaign_reserve(R)) return -1;
     std::vector<uint64_t> w;  // (LFC: raw words, decoded on the host)
     if (!cnv) w.resize(total);
     DrainOnFailure drain;  // (declared after the host buffers the queued copies read or write)
@@ -4073,14 +4138,17 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
     HIP_OK(hipEventRecord(r.time_events[0], r.stream));
     if (any && (en.plain ? mem_noise_enqueue(seeds, rate_w_q32, rate_t_q32, job, counts_off) : exposure_begin(seeds, job, counts_off, cl)))
       return -1;
+    if (mfma && any && en.plain && campaign_tables(r.d_copies, job.stride, R)) return -1;
     // (all rates 0: no copy is made, every run reads the loaded blob)
     const uint8_t *const base = any ? r.d_copies : static_cast<const uint8_t *>(r.d_blob);
     const MultiSeg *const d_segs = reinterpret_cast<const MultiSeg *>(r.d_sw_segs.get());
     HIP_OK(hipMemcpyAsync(r.d_sw_segs, segs.data(), segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
     int entered = -1;  // the last epoch whose scrub and upsets are in the stream
     for (const Group &g : groups) {
+      const int before = entered;
       for (; !en.plain && any && entered < g.epoch; entered++)
         if (exposure_epoch(entered + 1, rate_w_q32, rate_t_q32, job, counts_off, cl, ex, hz)) return -1;
+      if (mfma && entered != before && campaign_tables(r.d_copies, job.stride, R)) return -1;  // (behind the epoch's scrub, repair and upsets)
       MultiLaunch a{};
       a.images = r.d_all;
       a.segs = d_segs + g.seg0;
@@ -4091,12 +4159,17 @@ static int *mem_noise_campaigns_impl(const MemNoiseEntry &en, const Hardening &h
       a.stride = any ? job.stride : 0;
       // (reading the flags back only to decide this would cost a host wait: the -2-aware instantiations are exact on rows without)
       a.has_two = r.two_rows > 0 || tt;
+      if (mfma) set_campaign_tables(a, any);
       a.classes = reinterpret_cast<int32_t *>(r.d_camp_res.get());
       a.words = reinterpret_cast<uint64_t *>(r.d_camp_res.get());
       a.number_class = number_class;
       a.stream = r.stream;
+      if (probe) a.last = probe->stage;
       const hipError_t e = cnv ? run_cnv_multi(net.id, a) : run_lfc_multi(net.id, a);
       if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+      if (probe)  // (one epoch: the group's slots are the pairs pair0 ... of the call, in order)
+        HIP_OK(hipMemcpyAsync(probe->out + g.pair0 * probe->per, probe->in_buf1 ? r.buf1 : r.buf0, (size_t)g.total * probe->per, hipMemcpyDeviceToHost,
+                              r.stream));
     }
     HIP_OK(hipEventRecord(r.time_events[1], r.stream));
     if (any) HIP_OK(hipMemcpyAsync(counts.data(), r.d_noise + counts_off, counts.size() * 8, hipMemcpyDeviceToHost, r.stream));
@@ -4147,6 +4220,40 @@ int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_
 int bnn_mi355x_last_mem_noise_counts(long *flips, int cap) { return copy_out(rt().mem_noise_counts, flips, cap); }
 
 int bnn_mi355x_last_mem_noise_seeds(unsigned long long *seeds, int cap) { return copy_out(rt().mem_noise_seeds, seeds, cap); }
+
+int bnn_mi355x_campaign_form(int form) {
+  int &f = campaign_form();
+  const int was = f;
+  if (form == 0 || form == 1) f = form;
+  return was;
+}
+
+int bnn_mi355x_campaign_matrix_stages(int num_runs) {
+  if (!rt().d_blob) return -1;
+  return campaign_mfma(num_runs) ? kCampaignMatrixStages : 0;
+}
+
+long bnn_mi355x_debug_campaign_stage(const uint8_t *images, int n_images, int num_runs, unsigned long long seed, const unsigned *rate_w_q32,
+                                     const unsigned *rate_t_q32, int n_rates, int stage, void *out, size_t cap) {
+  Runtime &r = rt();
+  const char *const who = "debug_campaign_stage";
+  if (!r.spec.is_cnv) return fail(std::string(who) + ": the campaign stages that have two forms are the CNV networks'");
+  int in_buf1 = 0;
+  const size_t per = stage_output_bytes(true, r.spec.abits, stage, &in_buf1);
+  if (per == 0 || n_images <= 0 || num_runs < 1 || !images) return fail(std::string(who) + ": bad arguments (images, n_images, num_runs, or stage not 0 ... 7)");
+  if ((long long)n_images * num_runs > kMaxChunk)
+    return fail(std::string(who) + ": n_images * num_runs must not exceed one activation workspace (" + std::to_string(kMaxChunk) + " images)");
+  const size_t bytes = per * (size_t)n_images * (size_t)num_runs;
+  if (!out) return (long)bytes;
+  if (cap < bytes) return fail(std::string(who) + ": destination too small");
+  const MemNoiseEntry en{who, &Runtime::mem_noise_counts, &Runtime::mem_noise_seeds, true, true, true};
+  const CampaignProbe probe{images, n_images, stage, static_cast<uint8_t *>(out), per, in_buf1};
+  int *res = mem_noise_campaigns_impl(en, Hardening{HS_NONE, 1}, Exposure{0, 0}, nullptr, 10, num_runs, seed, rate_w_q32, rate_t_q32, n_rates, nullptr,
+                                      nullptr, &probe);
+  if (!res) return -1;
+  delete[] res;
+  return (long)bytes;
+}
 
 long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int target, unsigned int rate_q32, long first, int *records,
                                int cap_records) {

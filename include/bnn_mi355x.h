@@ -181,9 +181,10 @@ int bnn_mi355x_chunk_plan(int n_images, int from_file, int *bases, int cap);
  * bnn_mi355x_inference_device enqueues on one stream; calls the runtime splits (the chunks of chunk_plan, the two halves of a
  * device call of 16 384 images and more) decide per piece: ask with the piece's size.  The answer is for a pass without a
  * completion word: the host-timed single-image call (BNN_MI355X_DIRECT_TIMING=host) keeps layers 4-8 in one launch on the
- * integer pipe.  The fault-injection entry points always run layers 1-7 on the integer pipe (all but
- * bnn_mi355x_input_noise_campaigns, which classifies its faulted images by this very pass).  0 for the LFC networks, -1
- * before load_parameters.  Host only. */
+ * integer pipe.  The fault-injection entry points do not decide by this: the campaigns run layers 1-7 on the integer pipe
+ * or, under bnn_mi355x_campaign_form(1), on the matrix cores (ask bnn_mi355x_campaign_matrix_stages); the single-fault
+ * sweeps always run them on the integer pipe; bnn_mi355x_input_noise_campaigns classifies its faulted images by this very
+ * pass.  0 for the LFC networks, -1 before load_parameters.  Host only. */
 int bnn_mi355x_matrix_stages(int n_images);
 
 /* Fault campaigns: fix the seed of the fault planner (0 = std::random_device like the
@@ -402,6 +403,32 @@ int *bnn_mi355x_mem_noise_campaigns(const char *path, int number_class, int num_
                                     int *image_number, float *usecPerImage);
 int bnn_mi355x_last_mem_noise_counts(long *flips, int cap);
 int bnn_mi355x_last_mem_noise_seeds(unsigned long long *seeds, int cap);
+
+/* Campaigns on the matrix cores (CNV networks).  The campaign entry points -- fault_campaigns, act_noise_campaigns,
+ * mem_noise_campaigns and its hardened, exposure, ecc, repair, wecc and iwecc successors -- classify every run with its own
+ * (faulted) copy of the parameters.  Under form 1 layers 1-7 of their launches run as the exact FP4 GEMMs of the
+ * throughput pass: every run's operand tables are made on the device from its copy, and remade behind everything that
+ * changes the copies (a wave of patches, an epoch's upsets, a scrub, a repair); runs that read the loaded parameters
+ * (act_noise_campaigns, a call whose rates are all 0) use the tables load_parameters made.  Classes and counters are those of
+ * form 0, bit for bit.  The single-fault sweeps, the input campaigns, layers 0 and 8, the LFC networks and every call under
+ * BNN_MI355X_CONV=valu keep the integer pipe whatever the form.
+ * campaign_form: sets the form -- 0 the integer pipe, 1 the matrix cores, whatever the segment lengths -- and returns the
+ * one before; any other value changes nothing (a query).  Initially 0, or 1 under BNN_MI355X_CAMPAIGN=mfma: nothing selects
+ * form 1 by itself.
+ * campaign_matrix_stages: 0xFE (layers 1-7) when a campaign of num_runs runs would take the matrix form now, 0 when not:
+ * form 0, an LFC library, no operand tables (BNN_MI355X_CONV=valu), or num_runs x the tables' bytes (775 424 for cnvW1A1,
+ * 782 848 for the 2-bit networks) above 1 GiB, where the call runs form 0.  -1 before load_parameters.  Host only.
+ * debug_campaign_stage: the call body of mem_noise_campaigns for num_runs runs (seeds as there) on n_images images in host
+ * memory (the records' 3072-byte bodies), through layer `stage` (0 ... 7) only, under the current form and
+ * BNN_MI355X_NOISE_GROUP: out receives the stage's packed output of every (run, image) pair, run-major, as
+ * bnn_mi355x_debug_stage_output lays one image's out.  Returns the bytes written; with out NULL, the bytes needed.  Refuses
+ * (-1 + last_error) what the campaign refuses, an LFC library, and n_images x num_runs above one activation workspace
+ * (131 072).  It leaves the counts and seeds of a mem_noise_campaigns call behind. */
+int bnn_mi355x_campaign_form(int form);
+int bnn_mi355x_campaign_matrix_stages(int num_runs);
+long bnn_mi355x_debug_campaign_stage(const uint8_t *images, int n_images, int num_runs, unsigned long long seed,
+                                     const unsigned *rate_w_q32, const unsigned *rate_t_q32, int n_rates, int stage, void *out,
+                                     size_t cap);
 long bnn_mi355x_mem_noise_mask(unsigned long long run_seed, int layer, int target, unsigned int rate_q32, long first,
                                int *records, int cap_records);
 size_t bnn_mi355x_mem_noise_params(unsigned long long run_seed, const unsigned int *rate_w_q32,

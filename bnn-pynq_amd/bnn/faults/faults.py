@@ -166,8 +166,9 @@ class FaultTest:
     def campaign_form(self, form=None):
         """The form of layers 1-7 in the campaign calls (``run_test(batched=True)``, :meth:`run_noise_test` and the memory upset
         campaigns): 0 the integer pipe, 1 the matrix cores, every run from operand tables made of its own copy of the
-        parameters (``bnn_mi355x_campaign_form``); never automatic.  Sets ``form`` when given; returns the form before the
-        call.  The answers do not depend on it."""
+        parameters (``bnn_mi355x_campaign_form``); never automatic.  The single-fault sweeps follow it too: under form 1 their
+        stages of layers 1-7 that read the loaded parameters run on the matrix cores from the list of surviving pairs.  Sets
+        ``form`` when given; returns the form before the call.  The answers do not depend on it."""
         if form is not None and form not in (0, 1):
             raise ValueError("campaign_form: form must be 0 or 1")
         return int(self._campaign_lib("campaign_form").bnn_mi355x_campaign_form(7 if form is None else int(form)))

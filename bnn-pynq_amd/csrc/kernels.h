@@ -155,7 +155,8 @@ struct MultiLaunch {
   // CNV: run 0's operand tables of layers 1-7 (multi_mfma_kernels.h, multi_mfma_tables); run q's mfma_stride bytes behind, 0
   // when every run reads the loaded blob (stride 0: the tables load_parameters made).  Set, the covered layers of 1-7 run the
   // segment forms of the matrix kernels, whatever the segment lengths and whatever has_two says (a -2 is an FP4 value of the
-  // tables); null: the integer kernels (campaign form 0, the sweeps, act_window, BNN_MI355X_CONV=valu)
+  // tables); null: the integer kernels (campaign form 0, act_window, BNN_MI355X_CONV=valu, and the
+  // sweeps' launches through run_cnv_multi: under form 1 their stages on the loaded parameters bypass it, list_mfma_kernels.h)
   const uint8_t *multi_mfma = nullptr;
   size_t mfma_stride = 0;
 };

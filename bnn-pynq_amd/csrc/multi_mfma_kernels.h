@@ -5,9 +5,9 @@
 //
 // Which paths take it: fault_campaigns, act_noise_campaigns, mem_noise_campaigns and its hardened, exposure, ecc, repair,
 // wecc and iwecc successors -- everything that goes through run_cnv_multi with MultiLaunch::multi_mfma set.  Which keep the
-// integer pipe whatever the form: the single-fault sweeps (fault_sweep, act_fault_sweep, input_fault_sweep: a run per fault,
-// segments pruned short), act_window, input_noise_campaigns (it classifies by the fault-free pass), the LFC nets, layers 0
-// and 8 of every net, and every call under BNN_MI355X_CONV=valu.
+// integer pipe whatever the form: act_window, input_noise_campaigns (it classifies by the fault-free pass), the LFC nets, layers 0
+// and 8 of every net, and every call under BNN_MI355X_CONV=valu.  The single-fault sweeps (a run per fault, segments pruned
+// short) take neither these kernels nor the integer pipe under form 1 but the slot-list kernels of list_mfma_kernels.h.
 //
 // Split of a launch: grid (bx, nsegs).  Block (x, y) reads record y with scalar loads, loads its wave's neuron tile(s) of
 // run `run`'s tables into VGPRs once, and walks the record's image groups x, x + bx, ... (G images each: 2 for layer 1, 8

@@ -52,6 +52,7 @@
 #include "kernels.h"
 #include "lfc_mfma_kernels.h"
 #include "multi_mfma_kernels.h"
+#include "list_mfma_kernels.h"
 #include "preprocess.h"
 #include "resample.h"
 #include "window_kernels.h"
@@ -311,6 +312,8 @@ struct Runtime {
   // bnn_mi355x_fault_sweep (the runs' blob copies: d_copies): the fault-free stage outputs and results of the call's images;
   // a run group's patches (staging + spans), segment records, survivor flags, results, counts + offsets, {image, class} pairs
   DeviceBuf<uint8_t> d_sw_base, d_sw_stage, d_sw_segs, d_sw_alive, d_sw_res, d_sw_cnt, d_sw_diffs;
+  // campaign form 1 (list_mfma_kernels.h): a stage's alive slots, sized with the group as d_sw_segs is
+  DeviceBuf<uint8_t> d_sw_list;
   std::vector<long> sweep_pairs;  // the last sweep: per layer, the (fault, image) pairs it had to run (bnn_mi355x_last_sweep_stages)
   std::vector<long> act_sweep_pairs;  // the same of the last activation-fault sweep (bnn_mi355x_last_act_sweep_stages)
   // bnn_mi355x_sweep_profile: whether the single-fault sweeps record a propagation profile; a run group's [run][2]
@@ -2573,6 +2576,12 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
       if (!act || !cnv || L > 2) return false;
       return env_win ? std::atoi(env_win) != 0 : kWindowFaster[net.id][L];
     };
+    // Campaign form 1 (list_mfma_kernels.h): a CNV net with its operand tables runs every stage of layers 1-7 that reads the
+    // LOADED parameters on the matrix cores, from the list of the stage's alive slots: every such stage of the activation and
+    // input sites, the layers behind the faulted layer L of a parameter-fault group (layer L itself reads the run's copy).  The
+    // windowed first stage, layers 0 and 8 and everything that marks, counts and emits keep their segment records.
+    const bool list_form = campaign_form() == 1 && cnv && multi_mfma_bytes(net.id) && r.conv_mfma && r.d_conv_mfma;
+    const auto list_stage = [&](int l, int L) { return list_form && l >= 1 && l <= 7 && (unpatched || l > L); };
     long long group_cap = 0;
     if (const char *e = unpatched ? std::getenv("BNN_MI355X_SWEEP_GROUP") : nullptr) group_cap = std::atoll(e);
     // A run group that starts at stage s0 holds the outputs of layers s0-1 .. S-2 in the workspace at once, (run, image)
@@ -2620,6 +2629,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     if (r.d_copies.grow(unpatched ? 0 : (size_t)max_runs * stride) || r.d_sw_base.grow(boff[(size_t)S]) ||
         r.d_in_stage.grow(inp ? (size_t)max_pairs * isz + 256 : 0) ||
         r.d_sw_segs.grow((size_t)max_pairs * sizeof(MultiSeg) * (inp ? 2 : 1)) || r.d_sw_alive.grow((size_t)max_pairs) ||
+        r.d_sw_list.grow(list_form ? (size_t)max_pairs * sizeof(uint32_t) : 0) ||
         r.d_sw_res.grow(res_n * rb) || r.d_sw_cnt.grow((size_t)max_runs * 12 + 512) ||
         r.d_sw_diffs.grow((size_t)max_pairs * 8) || r.d_sw_prof.grow(profile ? (size_t)max_runs * 16 : 0))
       return -1;
@@ -2632,6 +2642,7 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
     // host buffers the queued copies read or write (declared before `drain`)
     std::vector<MultiSeg> segs, ran, seed_segs;
     std::vector<uint8_t> alive, upload;
+    std::vector<uint32_t> list;  // (form 1) the alive slots of the next stage, ascending
     std::vector<unsigned long long> prof;
     std::vector<int> counts, pv;
     std::vector<long long> offs;
@@ -2863,6 +2874,10 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
           if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
           segs.clear();
           for (int q = 0; q < g; q++) segs.push_back(MultiSeg{q, i0, q * m, m});
+          if (list_form) {  // the first stage of a group: every pair
+            list.resize((size_t)g * m);
+            for (size_t k = 0; k < list.size(); k++) list[k] = (uint32_t)k;
+          }
           for (int l = s0; l < S; l++) {
             if (plan()) return -1;
             const ActWinSite *const window = (wnd && l == s0) ? d_wsites : nullptr;  // (in place of k_act_seed + the whole stage)
@@ -2879,8 +2894,14 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
               for (MultiSeg &sg : seed_segs) sg.image = sg.slot;
               HIP_OK(hipMemcpyAsync(d_seed_segs, seed_segs.data(), seed_segs.size() * sizeof(MultiSeg), hipMemcpyHostToDevice, r.stream));
             }
-            if (unpatched ? stage(l, clean, 0, two, r.d_sw_res, window, from_staged ? r.d_in_stage : nullptr, d_seed_segs)
-                          : stage(l, r.d_copies, stride, two, r.d_sw_res))
+            if (list_stage(l, L) && !window) {  // the stage's alive slots, wherever they lie, through the loaded tables
+              HIP_OK(hipMemcpyAsync(r.d_sw_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream));
+              if (trace().on) std::fprintf(stderr, "bnn-mi355x trace sweep list: layer %d, %zu slots on the matrix cores\n", l, list.size());
+              e = run_cnv_list_mfma(net.id, l, ListLaunch{reinterpret_cast<const uint32_t *>(r.d_sw_list.get()), (int)list.size(), r.buf0,
+                                                          r.buf1, r.d_conv_mfma, r.stream});
+              if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+            } else if (unpatched ? stage(l, clean, 0, two, r.d_sw_res, window, from_staged ? r.d_in_stage : nullptr, d_seed_segs)
+                                 : stage(l, r.d_copies, stride, two, r.d_sw_res))
               return -1;
             if (l == s0) pairs[(size_t)l] += (long)g * m;
             if (l + 1 == S) break;
@@ -2911,9 +2932,14 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
             // grid per record (8 blocks of work items, map_block) is run through rather than cut: a pair that ran this
             // stage with the fault-free output gives the fault-free outputs again, and a record costs that grid however
             // short it is.  (Never across records: a pair dropped earlier holds stale activations.)
-            const int bridge = std::max(1, 8 * 256 / ipi[(size_t)l + 1]);
+            // (A list stage runs exactly the slots on its list: nothing is bridged before it, and its records, which the
+            // marking behind it reads, are the alive runs themselves.)
+            const bool to_list = list_stage(l + 1, L);
+            const int bridge = to_list ? 1 : std::max(1, 8 * 256 / ipi[(size_t)l + 1]);
+            bool ascending = true;
             ran.swap(segs);
             segs.clear();
+            list.clear();
             for (const MultiSeg &sg : ran) {
               const uint8_t *al = alive.data() + sg.slot;
               int b = -1, e2 = -1;  // the open segment [b, e2) of this record
@@ -2929,11 +2955,16 @@ static long single_fault_sweep(const char *path, int number_class, const std::ve
                 const int a0 = j;
                 while (j < sg.len && al[j]) j++;
                 pairs[(size_t)l + 1] += j - a0;
+                if (to_list) {
+                  ascending = ascending && (list.empty() || list.back() < (uint32_t)(sg.slot + a0));
+                  for (int k = a0; k < j; k++) list.push_back((uint32_t)(sg.slot + k));
+                }
                 e2 = j;
               }
               if (b >= 0) segs.push_back(MultiSeg{sg.run, sg.image + b, sg.slot + b, e2 - b});
             }
             if (segs.empty()) break;
+            if (!ascending) std::sort(list.begin(), list.end());  // (the records that ran were ordered by length class)
             if (begin()) return -1;
           }
           // classes against the fault-free ones (pairs pruned at any layer kept the fault-free result)

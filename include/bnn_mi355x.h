@@ -183,7 +183,7 @@ int bnn_mi355x_chunk_plan(int n_images, int from_file, int *bases, int cap);
  * completion word: the host-timed single-image call (BNN_MI355X_DIRECT_TIMING=host) keeps layers 4-8 in one launch on the
  * integer pipe.  The fault-injection entry points do not decide by this: the campaigns run layers 1-7 on the integer pipe
  * or, under bnn_mi355x_campaign_form(1), on the matrix cores (ask bnn_mi355x_campaign_matrix_stages); the single-fault
- * sweeps always run them on the integer pipe; bnn_mi355x_input_noise_campaigns classifies its faulted images by this very
+ * sweeps likewise, under form 1 every stage of layers 1-7 that reads the loaded parameters; bnn_mi355x_input_noise_campaigns classifies its faulted images by this very
  * pass.  0 for the LFC networks, -1 before load_parameters.  Host only. */
 int bnn_mi355x_matrix_stages(int n_images);
 
@@ -410,8 +410,15 @@ int bnn_mi355x_last_mem_noise_seeds(unsigned long long *seeds, int cap);
  * throughput pass: every run's operand tables are made on the device from its copy, and remade behind everything that
  * changes the copies (a wave of patches, an epoch's upsets, a scrub, a repair); runs that read the loaded parameters
  * (act_noise_campaigns, a call whose rates are all 0) use the tables load_parameters made.  Classes and counters are those of
- * form 0, bit for bit.  The single-fault sweeps, the input campaigns, layers 0 and 8, the LFC networks and every call under
- * BNN_MI355X_CONV=valu keep the integer pipe whatever the form.
+ * form 0, bit for bit.  The input campaigns, layers 0 and 8, the LFC networks and every call under BNN_MI355X_CONV=valu keep
+ * the integer pipe whatever the form.
+ * The single-fault sweeps (fault_sweep, act_fault_sweep, input_fault_sweep) follow the same switch with a split of their own:
+ * under form 1 every stage of layers 1-7 that reads the LOADED parameters -- all of them in the activation and input sweeps,
+ * the layers behind the faulted one in the parameter sweep -- runs as the same FP4 GEMMs on tiles packed from the list of the
+ * stage's surviving (fault, image) pairs, from the tables load_parameters made.  The faulted layer itself, the windowed first
+ * stage (BNN_MI355X_ACT_WINDOW), layers 0 and 8 and the marking and counting keep their segment records.  changed, diffs, the
+ * pairs per stage and the propagation profile are those of form 0.  Device time falls, wall time often does not
+ * (profiles/r40_sweep_form_rate.txt): measure before choosing it.
  * campaign_form: sets the form -- 0 the integer pipe, 1 the matrix cores, whatever the segment lengths -- and returns the
  * one before; any other value changes nothing (a query).  Initially 0, or 1 under BNN_MI355X_CAMPAIGN=mfma: nothing selects
  * form 1 by itself.
